@@ -14,8 +14,13 @@ quoted on: drone_risk, M = 1e5 samples per GPU, S = 50 steps, fp32.
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline     — the dominant kernel's algorithmic HBM bytes / its launch time
                  measured live with HIP events on the launch stream, vs 8 TB/s
+A plain run does only what that line's headline needs: set-up, W warm-up steps, the K timed steps (products
+Jacobian), the line.  --full adds every other measurement, after the timed steps:
+  the factored and regenerated-noise regions, the two-stream block, the SCP blocks, BASELINE C2-C5, the
+  beyond-cache roofline, the launch floor, the shader clock beside the hot kernel, and
   cpu_baseline — the oracle ("port": C + OpenMP for the drone, NumPy otherwise) timed on
                  this box's host cores, on a bounded sample of the same workload (rank 0, N=1 only).
+--dump-outputs DIR writes what the last timed step computed (collect_outputs).
 Other workloads (--workload driving|hopper, --M, --S, --mode eval) are for
 sweeps; they print the same line shape.
 """
@@ -55,17 +60,24 @@ def parse():
                     help="BASELINE.json configuration: metric = drone M=1e5 S=50 (the one the metric is quoted on); "
                          "C2 drone M=1e4 S=50; C3 driving M=1e4 S=40; C4 hopper M=5e4 S=60; C5 driving 125,000 "
                          "samples per GPU, S=40 (M=1e6 over 8 GPUs).  --workload/--M/--S override.")
-    ap.add_argument("--jacobian", default="both", choices=["both", "products", "factored", "regenerated"],
+    ap.add_argument("--jacobian", default=None, choices=["both", "products", "factored", "regenerated"],
                     help="drone linearize: representation the kernel writes.  products = every structural nonzero, "
                          "3S(S-1) numbers per sample (SURVEY 8d; this is what `value` and `roofline` are quoted on); "
                          "factored = W[j,t,a] * Phi[t,s,a], S(S-1)+6S numbers (reported as *_factored); regenerated = the "
                          "products output with the noise regenerated in the kernel instead of read (*_regenerated); both "
-                         "= one timed region for each of the three, same samples")
+                         "= one timed region for each of the three, same samples.  Default: both with --full, else products")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the other Jacobian representations, the two-stream "
+                         "block, the SCP blocks, BASELINE C2-C5, the beyond-cache roofline, the launch floor, the shader "
+                         "clock and the CPU baseline (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; "
+                         "per-sample arrays above 4 MB as a fixed seeded sample of the samples; see collect_outputs)")
     ap.add_argument("--philox", action="store_true",
                     help="drone, driving: no noise array in HBM, the Brownian increments are regenerated inside the "
                          "kernels (Philox4x32-10: rato_*_eval_philox, rato_*_linearize_philox); the algorithmic bytes "
                          "lose the 12 (8) B per sample-step of the noise")
-    ap.add_argument("--no-scp", action="store_true", help="skip the SCP wall-clock block (drone, N=1)")
+    ap.add_argument("--no-scp", action="store_true", help="--full: skip the SCP wall-clock block (drone, N=1)")
     ap.add_argument("--scp-iters", type=int, default=60)
     ap.add_argument("--dry-run", action="store_true", help="rank start-up + barrier only (no GPU work)")
     ap.add_argument("--strict-comm", action="store_true",
@@ -82,9 +94,9 @@ def parse():
                          "at N = 1, where it gains nothing (DESIGN.md 5)")
     ap.add_argument("--no-overlap", dest="overlap", action="store_false",
                     help="N > 1: kernel -> sums -> all-gather -> selection serially on one stream (A/B against the default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the `configs` block (BASELINE C2-C5 as whole steps after the metric configuration)")
+                    help="--full: skip the `configs` block (BASELINE C2-C5 as whole steps after the metric configuration)")
     ap.add_argument("--cpu-samples", type=int, default=0)
     args = ap.parse_args()
     preset = {"metric": ("drone", 100000, 50), "C2": ("drone", 10000, 50), "C3": ("driving", 10000, 40),
@@ -94,6 +106,8 @@ def parse():
     if args.workload == preset[0]:
         args.M = args.M or preset[1]
         args.S = args.S or preset[2]
+    if args.jacobian is None:
+        args.jacobian = "both" if args.full else "products"
     return args
 
 
@@ -191,6 +205,12 @@ class DroneWork:
                 self._no_sums = torch.zeros(1, dtype=torch.float64, device=r["Z"].device)
             return self._no_sums
         return r["sums"]
+
+    def outputs(self, r, sums):
+        """what a caller of the step receives (--dump-outputs); G is tile-blocked (collect_outputs untiles its sample)"""
+        if self.mode == "eval":
+            return {"Z": r["Z"]}
+        return {"G": r["G"], "W": r["W"], "g_up": r["g_up"], "Z": r["Z"], "du_sum": r["du_sum"], "rhs_sum": r["rhs_sum"]}
 
     def algorithmic_bytes(self):
         M, S = self.M, self.S
@@ -306,6 +326,11 @@ class DrivingWork:
             self._no_sums = torch.zeros(1, dtype=torch.float64, device=r["Z"].device)
         return self._no_sums
 
+    def outputs(self, r, sums):
+        if self.mode == "eval":
+            return {"Z": r["Z"]}
+        return {k: r[k] for k in ("G", "g_up", "Z", "final_du", "final_rhs")}
+
     def algorithmic_bytes(self):
         M, S = self.M, self.S
         eval_in = M * B * (2 * S + 6 + 1) + 2 * S * B
@@ -368,6 +393,13 @@ class HopperWork:
                 self._no_sums = torch.zeros(1, dtype=torch.float64, device=r["Z"].device)
             return self._no_sums
         return r["hess"].reshape(-1)
+
+    def outputs(self, r, sums):
+        """linearize: hess [C][2] = the step's sample sums (the single-GPU step folds their reduction into the statistics)"""
+        out = {k: r[k] for k in ("Z", "h", "dh_dfz", "dh_dpx")}
+        if self.mode == "linearize":
+            out["hess"] = sums.reshape(self.C, 2)
+        return out
 
     def algorithmic_bytes(self):
         M, C = self.M, self.C
@@ -476,8 +508,50 @@ def roofline_block(work, kern_ms, workload, mode, M, S, jacobian, kern_src):
             "traffic_from_profile": tr}
 
 
-def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, probe_clock=True, two_streams=False):
-    """W warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize; -> dict."""
+DUMP_FULL_BYTES = 4 << 20         # --dump-outputs: a per-sample array up to this size is written whole
+DUMP_SAMPLED_BYTES = 32 << 20     # the sampled arrays together (G, and the others above DUMP_FULL_BYTES)
+DUMP_MAX_SAMPLES = 1024
+
+
+def collect_outputs(work, r, sums, stats_row):
+    """--dump-outputs: the last timed step's outputs (work.outputs) and its risk statistics ("stats", the fp64 record of
+    stats.risk_stats_device) -> {name: float32 / float64 host array}.  Every array is written whole except G and any array
+    whose last axis is the sample axis and that is larger than DUMP_FULL_BYTES: those keep a fixed seeded sample of the
+    samples (np.random.RandomState(0), sorted; the same for every run of the same M), at most DUMP_MAX_SAMPLES and
+    DUMP_SAMPLED_BYTES in all.  The tile-blocked G [n_tiles][...][tile] is untiled on the way: [...][samples]."""
+    import torch
+    M = work.M
+    arrays = {k: v for k, v in work.outputs(r, sums).items() if v is not None}
+    sampled = {k for k, v in arrays.items()
+               if k == "G" or (v.shape[-1] == M and v.numel() * v.element_size() > DUMP_FULL_BYTES)}
+    per_sample = sum(v.numel() * v.element_size() // (v.shape[0] * v.shape[-1] if k == "G" else M)
+                     for k, v in arrays.items() if k in sampled)
+    n = max(1, min(M, DUMP_MAX_SAMPLES, DUMP_SAMPLED_BYTES // max(per_sample, 1)))
+    idx = np.sort(np.random.RandomState(0).choice(M, n, replace=False))
+    out = {"stats": np.asarray(stats_row.cpu().numpy(), dtype=np.float64)}
+    for k, v in arrays.items():
+        if k == "G":
+            tile = r["tile"]
+            v = v[torch.as_tensor(idx // tile, device=v.device), ..., torch.as_tensor(idx % tile, device=v.device)]
+            v = v.movedim(0, -1)
+        elif k in sampled:
+            v = v[..., torch.as_tensor(idx, device=v.device)]
+        a = v.detach().cpu().numpy()
+        out[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20, {k: a.nbytes for k, a in out.items()}
+    return out
+
+
+def write_outputs(outputs, d):
+    os.makedirs(d, exist_ok=True)
+    for k, a in outputs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
+def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, probe_clock=True, two_streams=False,
+                 dump=False):
+    """W warm-up steps, then EXACTLY K timed steps bracketed by barrier + synchronize; -> dict.  ``dump``: the dict's
+    "outputs" holds what the last timed step computed, on the host (collect_outputs; rank 0)."""
     M = work.M
     stats_out = torch.empty((2, stats.N_STATS), dtype=torch.float64, device=device)
     wss = [stats.new_workspace(M * world, device), stats.new_workspace(M * world, device)]
@@ -523,6 +597,7 @@ def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, pro
     pipe = rdist.PipelinedSteps(2, device, high_priority=bool(os.environ.get("RATO_PIPE_PRIORITY"))) if pipelined else None
     form_probe = None
     counter = [0]
+    last = {}      # the latest step's output dict ("r") and sample sums ("sums"): what --dump-outputs writes
     in_launch = (world == 1 and not pipelined and hasattr(work, "stats_in_launch") and work.stats_in_launch()
                  and not os.environ.get("RATO_BENCH_NO_IN_LAUNCH"))
 
@@ -535,30 +610,36 @@ def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, pro
             sums, Z_all = rdist.exchange(sums, r["Z"], agreed=True)   # the one collective (no-op at N=1; equal shards
             #                                                            were verified once, above)
         stats.risk_stats_device(Z_all, args.alpha, workspace=wss[slot], out=stats_out[slot])
+        last["sums"] = sums
         return sums
+
+    def produce(i, slot, **kw):
+        last["r"] = work.hot_kernel(events=ev[i] if i is not None else None, slot=slot, **kw)
+        return last["r"]
 
     def step(i=None):
         """One pass of the hot path: dominant kernel -> partial sums -> [one all-gather of the record when N > 1] ->
         exact VaR / CVaR / fraction satisfied.  (Pipelined: the exchange + statistics of step n run on a side stream
         beside the hot kernel of step n+1; both streams are drained before the clock stops.)"""
         if pipelined:
-            slot = pipe.step(lambda s: work.hot_kernel(events=ev[i] if i is not None else None, slot=s), finish)
+            slot = pipe.step(lambda s: produce(i, s), finish)
             counter[0] += 1
             return None
         slot = counter[0] & 1
         counter[0] += 1
         if in_launch:   # small batches: the kernel's own launch carries the statistics of its Z (+ the sample sums behind it)
-            r = work.hot_kernel(events=ev[i] if i is not None else None, slot=slot,
-                                stats_request=(wss[slot], stats_out[slot], args.alpha))
-            return work.sums(r)
+            r = produce(i, slot, stats_request=(wss[slot], stats_out[slot], args.alpha))
+            last["sums"] = work.sums(r)
+            return last["sums"]
         fold = (world == 1 and isinstance(work, (DroneWork, HopperWork)) and work.mode == "linearize"
                 and not os.environ.get("RATO_BENCH_NO_FOLD"))
         if fold:       # single GPU: linearize, then ONE launch for the sample sums + VaR / CVaR (2 launches per step)
-            r = work.hot_kernel(events=ev[i] if i is not None else None, slot=slot, reduce=False)
+            r = produce(i, slot, reduce=False)
             sums, _ = stats.sums_and_risk_stats_device(r["part"], r["Z"], args.alpha, workspace=wss[slot],
                                                        sums_out=r.get("sums"), out=stats_out[slot])
+            last["sums"] = sums
             return sums
-        r = work.hot_kernel(events=ev[i] if i is not None else None, slot=slot)
+        r = produce(i, slot)
         return finish(slot, r)
 
     # setup, not part of the W warm-up steps or of the timed region: ~10 ms of the hot kernel so that a short run
@@ -611,6 +692,7 @@ def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, pro
         graph = torch.cuda.CUDAGraph()     # capture/replay plumbing only: the nodes are this library's kernels
         with torch.cuda.graph(graph):
             step()
+        graph_last = dict(last)            # a replay rewrites these (the eager probe below moves `last` on)
         # setup (untimed): ~10 ms of replays, so that the K timed replays (often < 1 ms in total) do not run at the
         # clocks the capture pause and the spin kernel left behind; then the W warm-up steps proper
         for _ in range(200 + args.warmup):
@@ -671,6 +753,11 @@ def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, pro
     if os.environ.get("RATO_BENCH_TRACE") and not use_graph and two is None and rank == 0:      # per-launch kernel times, to stderr
         ts = [a.elapsed_time(b) for a, b in ev]
         print("kernel ms per launch:", " ".join("%.4f" % t for t in ts), file=sys.stderr)
+    outputs = None
+    if dump and rank == 0:          # before the clock probe below launches the hot kernel into slot 0 again
+        if use_graph and not eager_small:
+            last.update(graph_last)
+        outputs = collect_outputs(work, last["r"], last.get("sums"), stats_out[(counter[0] - 1) & 1])
     sclk = None
     if rank == 0 and probe_clock:
         # diagnostic, outside the timed region: the shader clock the device sustains WHILE the hot kernel runs (one wave
@@ -708,7 +795,8 @@ def timed_region(work, args, world, rank, device, stats, rdist, dist, torch, pro
         dist.all_gather_object(every, float(kern_ms))
         kern_ranks = {"min": min(every), "max": max(every), "per_rank": every}
     return {"elapsed": elapsed, "kern_ms": kern_ms, "kern_src": kern_src, "stats": final_stats, "launch": launch,
-            "sclk_mhz": sclk, "comm_selfcheck": selfcheck, "kernel_ms_ranks": kern_ranks, "form_probe": form_probe}
+            "sclk_mhz": sclk, "comm_selfcheck": selfcheck, "kernel_ms_ranks": kern_ranks, "form_probe": form_probe,
+            "outputs": outputs}
 
 
 def kkt_block(model, us_final, iters, first_cvar, where):
@@ -1207,9 +1295,13 @@ def main():
         args.force_factored = (var == "factored")
         args.philox = base_philox or var == "regenerated"
         work = WORKLOADS[args.workload](args, device, seed=1000 * rank + 7)
-        res = timed_region(work, args, world, rank, device, stats, rdist, dist, torch)
+        res = timed_region(work, args, world, rank, device, stats, rdist, dist, torch, probe_clock=args.full,
+                           dump=bool(args.dump_outputs) and var == variants[0])
+        if res["outputs"] is not None:
+            write_outputs(res["outputs"], args.dump_outputs)
         res["work"], res["variant"] = work, var
-        if world == 1 and var == variants[0] and args.config == "metric" and is_drone_lin and not args.no_configs:
+        if (args.full and world == 1 and var == variants[0] and args.config == "metric" and is_drone_lin
+                and not args.no_configs):
             try:   # the same K steps with consecutive steps on two alternating streams (an extra block, outside `value`)
                 r2 = timed_region(work, args, world, rank, device, stats, rdist, dist, torch, probe_clock=False, two_streams=True)
                 res["two_streams"] = {
@@ -1280,12 +1372,12 @@ def main():
                                                                res["variant"], res["kern_src"])
             line["value_" + res["variant"]] = world * M * unit_steps * args.steps / res["elapsed"]
             line["ms_per_step_" + res["variant"]] = 1e3 * res["elapsed"] / args.steps
-        if world == 1 and is_drone_lin and not args.no_scp:
+        if args.full and world == 1 and is_drone_lin and not args.no_scp:
             # on the resident samples of a variant that keeps its noise materialised (the reduced SCP reads it)
             scp_work = next((r["work"] for r in reversed(results) if not r["work"].philox), None)
             if scp_work is not None:
                 line["scp"] = scp_block(scp_work, args)
-        if world == 1 and args.config == "metric" and is_drone_lin and not args.no_configs:
+        if args.full and world == 1 and args.config == "metric" and is_drone_lin and not args.no_configs:
             for r in results:                             # free the metric configuration's 3 GB output slots first
                 w = r["work"]
                 for attr in ("outs", "records"):
@@ -1318,7 +1410,7 @@ def main():
                     line["scp_driving"] = scp_driving_block(device)
                 except Exception as e:                    # noqa: BLE001
                     line["scp_driving"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n = args.cpu_samples or CPU_SAMPLES[args.workload] or M
             cpu_step = work.cpu_baseline(n, args.alpha)
             threaded = getattr(cpu_step, "threaded", False)

@@ -1,10 +1,12 @@
-"""GPU: the driver's command line end to end at a small size — `python bench.py` with its default blocks (products,
-factored and regenerated-noise regions, SCP block, CPU baseline) prints exactly ONE JSON line carrying every block."""
+"""GPU: the driver's command line end to end at a small size — `python bench.py --full` with its blocks (products,
+factored and regenerated-noise regions, SCP block, CPU baseline) prints exactly ONE JSON line carrying every block; a
+plain run prints the headline alone and can dump what its last timed step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +23,7 @@ def _run(extra):
 
 
 def test_default_blocks_at_a_small_size():
-    d = _run(["--M", "3000", "--S", "20", "--steps", "3", "--warmup", "1", "--scp-iters", "3"])
+    d = _run(["--full", "--M", "3000", "--S", "20", "--steps", "3", "--warmup", "1", "--scp-iters", "3"])
     assert d["metric"] == "SAA constraint-eval throughput" and d["n_gpus"] == 1 and d["steps"] == 3
     assert d["value"] > 0 and d["value_factored"] > 0 and d["value_regenerated"] > 0
     for k in ("roofline", "roofline_factored", "roofline_regenerated"):
@@ -41,6 +43,29 @@ def test_default_blocks_at_a_small_size():
     assert cfg["scp_cuts_total"] == d["scp"]["cuts_total"] and cfg["gpu_over_cpu"] == cb["gpu_over_cpu"]
     assert list(d)[-1] == "config" and list(d)[-2] == "roofline"      # the contract's keys close the line
     assert d["device"]["sclk_mhz_beside_hot_kernel"] > 500
+
+
+def test_plain_run_and_its_dumped_outputs(tmp_path):
+    """without --full: the K timed steps and the line, none of the side blocks; --dump-outputs writes the last timed
+    step's arrays (float32 / float64), and a second run of the same command writes the same numbers"""
+    args = ["--M", "3000", "--S", "20", "--steps", "3", "--warmup", "1"]
+    d = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["kernel_ms"] > 0
+    assert not {"scp", "scp_driving", "cpu_baseline", "configs", "two_streams", "value_factored",
+                "value_regenerated", "roofline_beyond_cache"} & set(d)
+    assert d["config"]["workload"].endswith("Jacobian written as products")
+    _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert names == ["G.npy", "Z.npy", "du_sum.npy", "g_up.npy", "rhs_sum.npy", "stats.npy"]
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n, a in out.items():
+        assert a.dtype in (np.float32, np.float64), n
+        np.testing.assert_allclose(np.load(tmp_path / "b" / (n + ".npy")), a, rtol=1e-6, atol=0, err_msg=n)
+    # G: a sample of 1,024 of the 3,000 samples, untiled; g_up (720 KB, under bench.DUMP_FULL_BYTES) and Z: whole
+    assert out["Z"].shape == (3000,) and out["G"].shape == (190, 2, 3, 1024) and out["g_up"].shape == (3, 20, 3000)
+    assert out["du_sum"].shape == (20, 6) and out["rhs_sum"].shape == (6,)
+    assert out["stats"][0] == d["stats"]["VaR"] and out["stats"][1] == d["stats"]["CVaR"]
 
 
 @pytest.mark.parametrize("config", ["C3", "C4"])

@@ -21,7 +21,7 @@ for i in $(seq $reps); do
   for spec in "${specs[@]}"; do
     IFS='|' read -r name flags envs <<< "$spec"
     lib=""; [ -n "$flags" ] && lib=/tmp/ab_$name.so
-    env RATO_SAA_LIB=$lib $envs python $R/bench.py --no-cpu-baseline --no-scp --no-configs "$@" 2>/dev/null | python -c "
+    env RATO_SAA_LIB=$lib $envs python $R/bench.py --full --no-cpu-baseline --no-scp --no-configs "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 s = '%-14s kernel %.4f ms  frac %.3f  step %.4f ms' % ('$name', d['roofline']['kernel_ms'], d['roofline']['frac'], d['ms_per_step'])

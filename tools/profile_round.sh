@@ -5,10 +5,10 @@ tag=${1:-r03_x}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py"
-# 1. the driver's command line (default flags) -> bench line (roofline, roofline_factored / _regenerated, scp, configs, cpu_baseline)
-timeout 900 $B > $O/bench_default.json 2> $O/bench_default.err
+# 1. the full bench line (roofline, roofline_factored / _regenerated, scp, configs, cpu_baseline)
+timeout 900 $B --full > $O/bench_default.json 2> $O/bench_default.err
 # 2. kernel-trace stats of the same workload (eager; rocprofv3 and hipGraph replay do not mix on this pool)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_metric -- $B --steps 50 --warmup 10 --no-cpu-baseline --no-scp --no-configs > $O/kt_metric.json 2> /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_metric -- $B --full --steps 50 --warmup 10 --no-cpu-baseline --no-scp --no-configs > $O/kt_metric.json 2> /dev/null
 # 3. PMC passes, separate runs (HBM traffic of the dominant kernel)
 for jac in products factored; do
   for c in WRITE_SIZE FETCH_SIZE; do
@@ -18,12 +18,12 @@ for jac in products factored; do
 done
 # 4. BASELINE configs C2-C4 and C5's shard: step (hipGraph replay where the bench chooses it) and eager kernel stats
 for c in C2 C3 C4 C5; do
-  timeout 300 $B --config $c --no-cpu-baseline --no-scp --steps 50 --warmup 5 > $O/bench_$c.json 2> /dev/null
+  timeout 300 $B --full --config $c --no-cpu-baseline --no-scp --steps 50 --warmup 5 > $O/bench_$c.json 2> /dev/null
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$c -- $B --config $c --graph off --no-cpu-baseline --no-scp --steps 50 --warmup 5 > /dev/null 2>&1
 done
 # 4b. C2 / C3 in the reference's Monte-Carlo form (round 5): rollout kernel + exact selection
 for c in C2 C3; do
-  timeout 300 $B --config $c --mode eval --no-cpu-baseline --no-scp --steps 200 --warmup 5 > $O/bench_${c}_eval.json 2> /dev/null
+  timeout 300 $B --full --config $c --mode eval --no-cpu-baseline --no-scp --steps 200 --warmup 5 > $O/bench_${c}_eval.json 2> /dev/null
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_${c}_eval -- $B --config $c --mode eval --graph off --no-cpu-baseline --no-scp --steps 200 --warmup 5 > /dev/null 2>&1
 done
 cd $R

@@ -2,7 +2,7 @@
 # M-sweep of every kernel: prints one line per (workload, mode, M)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 run() {
-  timeout 200 python $R/bench.py --no-cpu-baseline --no-scp --no-configs --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
+  timeout 200 python $R/bench.py --full --no-cpu-baseline --no-scp --no-configs --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); r = d['roofline']
 s = '%-46s kernel %.4f ms  %6.0f GB/s  frac %.3f  step %.4f ms  %.3e %s' % ('$*', r['kernel_ms'], r['achieved'], r['frac'], d['ms_per_step'], d['value'], d['unit'])
