@@ -674,6 +674,41 @@ int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t iters, int
                        float* A22, float* part, double* sums_host, int32_t* keep, int32_t* keep_idle_count,
                        int32_t* n_keep_io, double* us_hist, rato_scp_iter* rec, int32_t* done, void* stream);
 
+/* The reduced SCP of K drone problems in lockstep (the reference's alpha x repeat grid, drone_risk.py:495-539), each problem
+ * a rato_cut_solver of its own (samples, alpha, rings, kept cuts) over ONE shared S, M and rato_drone_params (system 0,
+ * mode_saa 1, S >= 2, equal keep_max and cap, distinct solvers; RATO_EINVAL otherwise).  Per SCP iteration: one batched
+ * define for every problem still running, then rounds of one batched oracle round trip for every problem still cutting
+ * (a constant number of launches per round whatever K is), the masters of a round on up to n_threads host threads.  Every
+ * problem's iterates, cut counts, t_risk and kept cuts are bitwise those of rato_scp_run_drone on its solver alone.
+ * Nothing is allocated on the device here: rato_scp_batch_bytes gives the sizes of the caller-owned device buffer (aligned
+ * to 256 bytes) and PINNED host buffer (device-visible, aligned to 16) that rato_scp_batch_create binds to the batch; the
+ * solvers must outlive it.  One stream, one run at a time per batch. */
+typedef struct rato_scp_batch rato_scp_batch;
+typedef struct rato_scp_batch_iter {
+  double define_s;   /* the batched define, up to every problem's sample sums on the host */
+  double oracle_s;   /* the batched oracle round trips (staging, launches, read-back) */
+  double master_s;   /* the host masters of every round (wall time of the parallel phases) */
+  double total_s;    /* the whole iteration */
+  int32_t rounds, active, reserved0, reserved1; /* oracle round trips; problems that entered the iteration */
+} rato_scp_batch_iter;
+size_t rato_scp_batch_iter_bytes(void);
+int rato_scp_batch_bytes(rato_cut_solver* const* solvers, int32_t K, size_t* device_bytes, size_t* host_bytes);
+int rato_scp_batch_create(rato_scp_batch** out, rato_cut_solver* const* solvers, int32_t K, int32_t n_threads,
+                          void* device_buf, size_t device_bytes, void* host_buf, size_t host_bytes);
+void rato_scp_batch_destroy(rato_scp_batch* b);
+/* `iters` lockstep iterations from us0 [K][S][3] (iteration k < first_cvar without the CVaR rows).  keep /
+ * keep_idle_count [K][keep_max] and n_keep [K]: each problem's kept cuts, in and out as for rato_scp_run_drone.  Outputs:
+ * us_hist [K][iters][S][3]; rec [K][iters] -- cuts, t_risk, slack, phi, status, recycled per problem, and master_s = that
+ * problem's own master time; its define_s / solve_s / oracle_s are NaN (lockstep has no per-problem clock): the clocks
+ * are brec [iters], batch-level; status [K]: RATO_OK or the problem's first failure (RATO_ERANK / RATO_ESELECT: repeat it
+ * with the per-iteration calls; RATO_ENONFINITE, RATO_EINFEASIBLE, RATO_ENNLS, RATO_EINVAL: failed) -- a failed problem
+ * leaves the batch, the others go on; done [K]: iterations each completed; *rounds: batched oracle round trips.
+ * Returns RATO_OK unless the device fails (RATO_EHIP - e) or an argument is invalid. */
+int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, int32_t iters, int32_t first_cvar, double tol,
+                             int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
+                             int32_t* keep_idle_count, int32_t* n_keep, double* us_hist, rato_scp_iter* rec,
+                             rato_scp_batch_iter* brec, int32_t* status, int32_t* done, int32_t* rounds, void* stream);
+
 /* ------------------------------------------------------------ device sampler */
 
 /*

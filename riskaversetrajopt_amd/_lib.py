@@ -63,6 +63,12 @@ class ScpIter(C.Structure):
                [(k, C.c_int32) for k in ("cuts", "status", "recycled", "reserved")]
 
 
+class ScpBatchIter(C.Structure):
+    """rato_scp_batch_iter (include/rato_saa.h): the batch-level clocks of one lockstep SCP iteration"""
+    _fields_ = [(k, C.c_double) for k in ("define_s", "oracle_s", "master_s", "total_s")] + \
+               [(k, C.c_int32) for k in ("rounds", "active", "reserved0", "reserved1")]
+
+
 # name -> (restype, argtypes); mirrors include/rato_saa.h one to one
 SIGNATURES = {
     "rato_abi_version": (C.c_int, []),
@@ -98,6 +104,13 @@ SIGNATURES = {
     "rato_scp_iter_bytes": (C.c_size_t, []),
     "rato_scp_run_drone": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32] +
                            [C.c_void_p] * 11 + [c_stream]),
+    "rato_scp_batch_iter_bytes": (C.c_size_t, []),
+    "rato_scp_batch_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "rato_scp_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t]),
+    "rato_scp_batch_destroy": (None, [C.c_void_p]),
+    "rato_scp_batch_run_drone": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double,
+                                           C.c_int32] + [C.c_void_p] * 9 + [c_stream]),
     "rato_cut_define_drone": (C.c_int, [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 5 + [C.c_int32, c_stream]),
     "rato_cut_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                  C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32,

@@ -21,12 +21,19 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <thread>
 #include <utility>
 #include <vector>
 
 #include "rato_common.h"
 #include "rato_saa.h"
+#include "rato_select.h"
 
 namespace {
 
@@ -302,67 +309,95 @@ extern "C" int rato_cut_define_drone(rato_cut_solver* s, const double* us, float
   return RATO_OK;
 }
 
-extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const double* final_rhs, int32_t n_c,
-                              const double* u_lin, int32_t with_cvar, double tol, int32_t max_cuts,
-                              double final_cut_above, int32_t check_finite, int32_t* keep, int32_t* keep_idle_count,
-                              int32_t* n_keep_io, int32_t kept_in_flight, rato_cut_result* out, void* stream) {
-  if (!s || !final_du || !final_rhs || n_c < 0 || !u_lin || !out || !out->us || !keep || !keep_idle_count || !n_keep_io ||
-      max_cuts < 0)
-    return RATO_EINVAL;
-  const rato_cut_config& c = s->c;
-  const int nU = s->nU, n = s->n, S = c.S, nc = s->nc, n_u = nU / S;
-  const bool saa = c.mode_saa != 0;
-  const bool cvar = with_cvar != 0;
-  const bool slack_row = cvar && saa;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  double oracle_s = 0.0, master_s = 0.0;
-  std::vector<double> prod, row(n), g(nU), x(nU), z(n), lam, lam_tmp;
+namespace {
 
-  auto t0 = std::chrono::steady_clock::now();
-  // master: equalities [final_du | 0] z = final_rhs
-  std::vector<double> F((size_t)n_c * n, 0.0);
-  for (int r = 0; r < n_c; ++r) memcpy(&F[(size_t)r * n], final_du + (size_t)r * nU, sizeof(double) * nU);
+// One subproblem's cutting-plane loop as a RESUMABLE state: what rato_cut_solve runs start to end with the oracle round trip
+// in the middle, cut at the round trip so that a batch (rato_scp_batch_run_drone) can issue the round trips of many
+// subproblems as one.  init: the equality rows (+ the slack row) into a fresh master;  add_kept: the rows of the cuts kept
+// from the previous subproblem, from their sums under the new linearization point;  begin: the first master solve and the
+// first query;  then, while !done: x (u - u_k) and ring (the slot the round trip writes) are the query, consume(record)
+// takes the round trip's record and runs the master up to the next query;  finish: the keep rule and the outputs.  The
+// statements are those of the loop as it was written in one piece -- same order, same arithmetic: the iterates of
+// rato_cut_solve did not change bit for bit (tests/test_gpu_scp.py).  No state outside the object (and the solver's
+// read-only configuration) is touched: the masters of a batch run on several host threads.
+struct CutLoop {
+  struct BoundRows {
+    int r0;
+    std::vector<int> idx;
+    double sgn;
+  };
+  const rato_cut_solver* s = nullptr;
+  const double* u_lin = nullptr;
+  bool cvar = false, slack_row = false, check_finite = false, done = false, have_prev = false;
+  double tol = 0.0, final_cut_above = 0.0, phi = NAN, tstar = NAN, oracle_s = 0.0, master_s = 0.0;
+  int max_cuts = 0, nU = 0, n = 0, S = 0, nc = 0, n_u = 0, n_rows = 0, n_kept = 0, n_cuts = 0, status = 0, it = 0, slot = -1,
+      ring = -1;
+  int32_t *keep = nullptr, *keep_idle_count = nullptr, *n_keep_io = nullptr;
   rato_master* master = nullptr;
-  int rc = rato_master_create(&master, n, s->p_diag.data(), s->q.data(), n_c, F.data(), final_rhs);
-  if (rc != RATO_OK) return RATO_ERANK;
-  struct Guard {
-    rato_master* m;
-    ~Guard() { rato_master_destroy(m); }
-  } guard{master};
-  int n_rows = 0;
-  if (slack_row) {   // -slack <= 0
-    std::fill(row.begin(), row.end(), 0.0);
-    row[nU] = -1.0;
-    const double zero = 0.0;
-    if ((rc = rato_master_add_rows(master, 1, row.data(), &zero)) != RATO_OK) return rc;
-    n_rows = 1;
-  }
+  std::vector<double> prod, row, g, x, z, lam, z_prev;
   std::vector<std::pair<int, int>> cut_rows;   // (row of the master, ring slot)
-  const int n_kept = (cvar && c.recycle) ? *n_keep_io : 0;
-  if (n_kept < 0 || n_kept > c.keep_max) return RATO_EINVAL;
-  // the kept slots index host tables below (is_kept, idle) whether or not their re-linearization is already in flight:
-  // checked here unconditionally, not only inside rato_cut_begin / rato_cut_define_drone
-  if (*n_keep_io < 0 || *n_keep_io > c.keep_max || !keep_ok(s, keep, *n_keep_io)) return RATO_EINVAL;
-  master_s += seconds_since(t0);
+  std::vector<int> free_slots;                 // ascending; the loop takes from the back
+  std::vector<uint8_t> in_master;
+  std::vector<BoundRows> bound_rows;
 
-  if (n_kept > 0 && S >= 2) {
-    t0 = std::chrono::steady_clock::now();
-    if (!kept_in_flight) {
-      if ((rc = rato_cut_begin(s, u_lin, keep, n_kept, stream)) != RATO_OK) return rc;
+  CutLoop() = default;
+  CutLoop(const CutLoop&) = delete;
+  CutLoop& operator=(const CutLoop&) = delete;
+  ~CutLoop() { rato_master_destroy(master); }
+
+  int init(const rato_cut_solver* sv, const double* final_du, const double* final_rhs, int n_c, const double* u_lin_,
+           bool with_cvar, double tol_, int max_cuts_, double final_cut_above_, bool check_finite_, int32_t* keep_,
+           int32_t* keep_idle_count_, int32_t* n_keep_io_) {
+    s = sv;
+    const rato_cut_config& c = s->c;
+    u_lin = u_lin_;
+    cvar = with_cvar;
+    slack_row = cvar && c.mode_saa != 0;
+    tol = tol_;
+    max_cuts = max_cuts_;
+    final_cut_above = final_cut_above_;
+    check_finite = check_finite_;
+    keep = keep_;
+    keep_idle_count = keep_idle_count_;
+    n_keep_io = n_keep_io_;
+    nU = s->nU, n = s->n, S = c.S, nc = s->nc, n_u = nU / S;
+    row.resize(n);
+    g.resize(nU);
+    x.resize(nU);
+    z.resize(n);
+    z_prev.resize(n);
+    const auto t0 = std::chrono::steady_clock::now();
+    // master: equalities [final_du | 0] z = final_rhs
+    std::vector<double> F((size_t)n_c * n, 0.0);
+    for (int r = 0; r < n_c; ++r) memcpy(&F[(size_t)r * n], final_du + (size_t)r * nU, sizeof(double) * nU);
+    int rc = rato_master_create(&master, n, s->p_diag.data(), s->q.data(), n_c, F.data(), final_rhs);
+    if (rc != RATO_OK) return RATO_ERANK;
+    if (slack_row) {   // -slack <= 0
+      std::fill(row.begin(), row.end(), 0.0);
+      row[nU] = -1.0;
+      const double zero = 0.0;
+      if ((rc = rato_master_add_rows(master, 1, row.data(), &zero)) != RATO_OK) return rc;
+      n_rows = 1;
     }
-    // (the kept cuts' sums were armed where they were launched: rato_cut_begin / rato_cut_define_drone)
-    const bool armed = s->kept_armed;
-    s->kept_armed = false;
-    hipError_t e = armed ? rato::readback_wait(c.sums_b_host, n_kept * nc, st) : hipStreamSynchronize(st);
-    if (e != hipSuccess) return RATO_EHIP - (int)e;
-    // (not armed: the words were not watched -- a define that failed before its launch leaves them pre-set; never data)
-    if (!armed && rato::readback_pending(c.sums_b_host, n_kept * nc)) return RATO_EHIP - (int)hipErrorNotReady;
-    oracle_s += seconds_since(t0);
-    t0 = std::chrono::steady_clock::now();
+    n_kept = (cvar && c.recycle) ? *n_keep_io : 0;
+    if (n_kept < 0 || n_kept > c.keep_max) return RATO_EINVAL;
+    // the kept slots index host tables below (is_kept, idle) whether or not their re-linearization is already in flight:
+    // checked here unconditionally, not only inside rato_cut_begin / rato_cut_define_drone
+    if (*n_keep_io < 0 || *n_keep_io > c.keep_max || !keep_ok(s, keep, *n_keep_io)) return RATO_EINVAL;
+    master_s += seconds_since(t0);
+    return RATO_OK;
+  }
+
+  bool wants_kept() const { return n_kept > 0 && S >= 2; }
+
+  // sums [n_kept][nc]: the kept cuts' tail-row sums under the current linearization point
+  int add_kept(const double* sums) {
+    const rato_cut_config& c = s->c;
+    const auto t0 = std::chrono::steady_clock::now();
     // cut k under the current linearization (delta form):  rows_k . (u - u_k) + c0_k - c_s s <= rhs0
     std::vector<double> rows((size_t)n_kept * n, 0.0), rhs(n_kept);
     for (int k = 0; k < n_kept; ++k) {
-      const double* r = c.sums_b_host + (size_t)k * nc;
+      const double* r = sums + (size_t)k * nc;
       double* rk = &rows[(size_t)k * n];
       for (int t = 0; t < S - 1; ++t) {
         rk[t * n_u + 0] = r[2 * t + 0] / c.alphaM;
@@ -373,26 +408,28 @@ extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const 
       rhs[k] = (c.rhs0 + d) - 1.0 * (r[nc - 1] / c.alphaM);
       cut_rows.emplace_back(n_rows + k, keep[k]);
     }
-    if ((rc = rato_master_add_rows(master, n_kept, rows.data(), rhs.data())) != RATO_OK) return rc;
+    const int rc = rato_master_add_rows(master, n_kept, rows.data(), rhs.data());
+    if (rc != RATO_OK) return rc;
     n_rows += n_kept;
     master_s += seconds_since(t0);
+    return RATO_OK;
   }
-  std::vector<int> free_slots;   // ascending; the loop takes from the back
-  {
-    std::vector<uint8_t> is_kept(c.cap, 0);
-    for (int k = 0; k < n_kept; ++k) is_kept[keep[k]] = 1;
-    for (int sl = 0; sl < c.cap - 1; ++sl)
-      if (!is_kept[sl]) free_slots.push_back(sl);
-  }
-  std::vector<uint8_t> in_master(2 * (size_t)nU, 0);
-  struct BoundRows {
-    int r0;
-    std::vector<int> idx;
-    double sgn;
-  };
-  std::vector<BoundRows> bound_rows;
 
-  auto solve_master = [&]() -> int {   // the master with the control bounds entering lazily: only the violated ones
+  int begin() {
+    const rato_cut_config& c = s->c;
+    {
+      std::vector<uint8_t> is_kept(c.cap, 0);
+      for (int k = 0; k < n_kept; ++k) is_kept[keep[k]] = 1;
+      for (int sl = 0; sl < c.cap - 1; ++sl)
+        if (!is_kept[sl]) free_slots.push_back(sl);
+    }
+    in_master.assign(2 * (size_t)nU, 0);
+    it = 0;
+    return query();
+  }
+
+  int solve_master() {   // the master with the control bounds entering lazily: only the violated ones
+    const rato_cut_config& c = s->c;
     for (;;) {
       lam.assign(n_rows, 0.0);
       const int r = rato_master_solve(master, z.data(), lam.data());
@@ -419,36 +456,47 @@ extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const 
         n_rows += (int)idx.size();
       }
     }
-  };
+  }
 
-  double phi = NAN, tstar = NAN;
-  int n_cuts = 0, status = 0;
-  std::vector<double> z_prev(n);
-  bool have_prev = false;
-  const int scratch = c.cap - 1;
-  const size_t M = (size_t)c.M;
-  for (int it = 0; it <= max_cuts; ++it) {
-    t0 = std::chrono::steady_clock::now();
-    if ((rc = solve_master()) != RATO_OK) return rc;
+  // iteration `it` up to its oracle round trip: the master, then (CVaR rows on) the ring slot and x = z - u_k
+  int query() {
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = solve_master();
+    if (rc != RATO_OK) return rc;
     master_s += seconds_since(t0);
-    if (!cvar) break;
+    if (!cvar) {
+      done = true;
+      return RATO_OK;
+    }
     t0 = std::chrono::steady_clock::now();
-    int slot = -1;
+    slot = -1;
     if (!free_slots.empty()) {
       slot = free_slots.back();
       free_slots.pop_back();
     }
-    const int ring = slot >= 0 ? slot : scratch;
-    for (int i = 0; i < nU; ++i) {
-      x[i] = z[i] - u_lin[i];
-      c.x_host[i] = x[i];
-    }
-    rc = rato_cut_oracle_rollout(c.system, s->params(), c.uk_dev, c.s0, c.s1, c.s2, c.s3, c.x_host, c.x_dev,
-                                 c.ring_m + (size_t)ring * M, c.ring_arg + (size_t)ring * M, c.alpha, c.thr, c.alphaM,
-                                 c.workspace, c.workspace_bytes, c.ring_res + (size_t)ring * s->nres, c.part, c.res_host,
-                                 stream);
-    if (rc != RATO_OK) return rc;
-    const double* r = c.res_host;
+    ring = slot >= 0 ? slot : s->c.cap - 1;   // (the last slot: scratch for calls beyond the ring)
+    for (int i = 0; i < nU; ++i) x[i] = z[i] - u_lin[i];
+    oracle_s += seconds_since(t0);
+    return RATO_OK;
+  }
+
+  int add_cut() {   // phi(u) >= phi_k + g_k.(u - u_k)  =>  g_k.u - c_s s <= rhs0 + g_k.u_k - phi_k
+    const rato_cut_config& c = s->c;
+    memcpy(row.data(), g.data(), sizeof(double) * nU);
+    row[nU] = -c.c_s;
+    const double rhs = c.rhs0 + (dot_exact(g.data(), z.data(), nU, prod) - phi);
+    const int r2 = rato_master_add_rows(master, 1, row.data(), &rhs);
+    if (r2 != RATO_OK) return r2;
+    if (slot >= 0) cut_rows.emplace_back(n_rows, slot);
+    n_rows += 1;
+    n_cuts += 1;
+    return RATO_OK;
+  }
+
+  // the record of iteration `it`'s round trip: [RATO_N_STATS statistics | nc cut sums]
+  int consume(const double* r) {
+    const rato_cut_config& c = s->c;
+    auto t0 = std::chrono::steady_clock::now();
     if (isnan(r[0])) return RATO_ESELECT;     // the one-launch selection gave up (or the m values hold NaN): the caller
     //                                           repeats the subproblem with the recovering Python loop
     if (check_finite && !(isfinite(r[3]) && isfinite(r[4]))) return RATO_ENONFINITE;
@@ -473,22 +521,13 @@ extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const 
       for (int i = 0; i < n; ++i) step = fmax(step, fabs(z[i] - z_prev[i]));
       if (step <= 1e-10) {
         status = 2;
-        break;
+        done = true;
+        return RATO_OK;
       }
     }
     z_prev = z;
     have_prev = true;
-    auto add_cut = [&]() -> int {   // phi(u) >= phi_k + g_k.(u - u_k)  =>  g_k.u - c_s s <= rhs0 + g_k.u_k - phi_k
-      memcpy(row.data(), g.data(), sizeof(double) * nU);
-      row[nU] = -c.c_s;
-      const double rhs = c.rhs0 + (dot_exact(g.data(), z.data(), nU, prod) - phi);
-      const int r2 = rato_master_add_rows(master, 1, row.data(), &rhs);
-      if (r2 != RATO_OK) return r2;
-      if (slot >= 0) cut_rows.emplace_back(n_rows, slot);
-      n_rows += 1;
-      n_cuts += 1;
-      return RATO_OK;
-    };
+    int rc;
     if (viol <= tol) {
       if (viol > final_cut_above && it < max_cuts) {   // the cut just evaluated is paid for: it joins the master
         t0 = std::chrono::steady_clock::now();
@@ -496,73 +535,127 @@ extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const 
         if ((rc = solve_master()) != RATO_OK) return rc;
         master_s += seconds_since(t0);
       }
-      break;
+      done = true;
+      return RATO_OK;
     }
     if (it == max_cuts) {
       status = 1;
-      break;
+      done = true;
+      return RATO_OK;
     }
     if ((rc = add_cut()) != RATO_OK) return rc;
+    ++it;
+    return query();
   }
 
-  // multipliers of the last master solve, for whoever certifies the solution against the full QP
-  std::vector<double> lam_full(n_rows, 0.0);
-  for (size_t i = 0; i < lam.size() && i < (size_t)n_rows; ++i) lam_full[i] = lam[i];
-  if (cvar && c.recycle) {
-    // keep rule: the cuts that carry a multiplier (newest first; keep_idle > 0: or did within the last keep_idle solves),
-    // plus the newest keep_recent
-    std::vector<int> idle(c.cap, -1);
-    for (int k = 0; k < *n_keep_io; ++k) idle[keep[k]] = keep_idle_count[k];
-    for (auto& cr : cut_rows) {
-      const bool active = cr.first < (int)lam.size() && lam[cr.first] > 1e-12;
-      idle[cr.second] = active ? 0 : (idle[cr.second] < 0 ? 0 : idle[cr.second]) + 1;
-    }
-    std::vector<int> new_keep;
-    auto push = [&](int sl) {
-      if (std::find(new_keep.begin(), new_keep.end(), sl) == new_keep.end()) new_keep.push_back(sl);
-    };
-    for (auto it2 = cut_rows.rbegin(); it2 != cut_rows.rend(); ++it2)
-      if (idle[it2->second] <= c.keep_idle) push(it2->second);
-    int cnt = 0;
-    for (auto it2 = cut_rows.rbegin(); it2 != cut_rows.rend() && cnt < c.keep_recent; ++it2, ++cnt) push(it2->second);
-    if ((int)new_keep.size() > c.keep_max) new_keep.resize(c.keep_max);
-    for (size_t k = 0; k < new_keep.size(); ++k) {
-      keep[k] = new_keep[k];
-      keep_idle_count[k] = idle[new_keep[k]];
-    }
-    *n_keep_io = (int)new_keep.size();
-  }
-  memcpy(out->us, z.data(), sizeof(double) * nU);
-  out->slack = z[nU];
-  out->t_risk = slack_row ? tstar + z[nU] : 0.0;
-  out->phi = phi;
-  out->oracle_s = oracle_s;
-  out->master_s = master_s;
-  out->cuts = n_cuts;
-  out->recycled = n_kept;
-  out->status = status;
-  out->lam_slack = slack_row ? lam_full[0] : 0.0;
-  out->uncertified_cuts = n_cuts + n_kept - (int)cut_rows.size();
-  out->n_cut_rows = 0;
-  if (out->cut_slot && out->cut_lambda) {
-    for (auto& cr : cut_rows) {
-      if (out->n_cut_rows >= out->cut_capacity) break;
-      out->cut_slot[out->n_cut_rows] = cr.second;
-      out->cut_lambda[out->n_cut_rows] = lam_full[cr.first];
-      ++out->n_cut_rows;
-    }
-  }
-  out->n_bounds = 0;
-  if (out->bound_var && out->bound_sign && out->bound_lambda) {
-    for (auto& br : bound_rows)
-      for (size_t k = 0; k < br.idx.size(); ++k) {
-        if (out->n_bounds >= out->bound_capacity) break;
-        out->bound_var[out->n_bounds] = br.idx[k];
-        out->bound_sign[out->n_bounds] = br.sgn;
-        out->bound_lambda[out->n_bounds] = lam_full[br.r0 + (int)k];
-        ++out->n_bounds;
+  void finish(rato_cut_result* out) {
+    const rato_cut_config& c = s->c;
+    // multipliers of the last master solve, for whoever certifies the solution against the full QP
+    std::vector<double> lam_full(n_rows, 0.0);
+    for (size_t i = 0; i < lam.size() && i < (size_t)n_rows; ++i) lam_full[i] = lam[i];
+    if (cvar && c.recycle) {
+      // keep rule: the cuts that carry a multiplier (newest first; keep_idle > 0: or did within the last keep_idle solves),
+      // plus the newest keep_recent
+      std::vector<int> idle(c.cap, -1);
+      for (int k = 0; k < *n_keep_io; ++k) idle[keep[k]] = keep_idle_count[k];
+      for (auto& cr : cut_rows) {
+        const bool active = cr.first < (int)lam.size() && lam[cr.first] > 1e-12;
+        idle[cr.second] = active ? 0 : (idle[cr.second] < 0 ? 0 : idle[cr.second]) + 1;
       }
+      std::vector<int> new_keep;
+      auto push = [&](int sl) {
+        if (std::find(new_keep.begin(), new_keep.end(), sl) == new_keep.end()) new_keep.push_back(sl);
+      };
+      for (auto it2 = cut_rows.rbegin(); it2 != cut_rows.rend(); ++it2)
+        if (idle[it2->second] <= c.keep_idle) push(it2->second);
+      int cnt = 0;
+      for (auto it2 = cut_rows.rbegin(); it2 != cut_rows.rend() && cnt < c.keep_recent; ++it2, ++cnt) push(it2->second);
+      if ((int)new_keep.size() > c.keep_max) new_keep.resize(c.keep_max);
+      for (size_t k = 0; k < new_keep.size(); ++k) {
+        keep[k] = new_keep[k];
+        keep_idle_count[k] = idle[new_keep[k]];
+      }
+      *n_keep_io = (int)new_keep.size();
+    }
+    memcpy(out->us, z.data(), sizeof(double) * nU);
+    out->slack = z[nU];
+    out->t_risk = slack_row ? tstar + z[nU] : 0.0;
+    out->phi = phi;
+    out->oracle_s = oracle_s;
+    out->master_s = master_s;
+    out->cuts = n_cuts;
+    out->recycled = n_kept;
+    out->status = status;
+    out->lam_slack = slack_row ? lam_full[0] : 0.0;
+    out->uncertified_cuts = n_cuts + n_kept - (int)cut_rows.size();
+    out->n_cut_rows = 0;
+    if (out->cut_slot && out->cut_lambda) {
+      for (auto& cr : cut_rows) {
+        if (out->n_cut_rows >= out->cut_capacity) break;
+        out->cut_slot[out->n_cut_rows] = cr.second;
+        out->cut_lambda[out->n_cut_rows] = lam_full[cr.first];
+        ++out->n_cut_rows;
+      }
+    }
+    out->n_bounds = 0;
+    if (out->bound_var && out->bound_sign && out->bound_lambda) {
+      for (auto& br : bound_rows)
+        for (size_t k = 0; k < br.idx.size(); ++k) {
+          if (out->n_bounds >= out->bound_capacity) break;
+          out->bound_var[out->n_bounds] = br.idx[k];
+          out->bound_sign[out->n_bounds] = br.sgn;
+          out->bound_lambda[out->n_bounds] = lam_full[br.r0 + (int)k];
+          ++out->n_bounds;
+        }
+    }
   }
+};
+
+}  // namespace
+
+extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const double* final_rhs, int32_t n_c,
+                              const double* u_lin, int32_t with_cvar, double tol, int32_t max_cuts,
+                              double final_cut_above, int32_t check_finite, int32_t* keep, int32_t* keep_idle_count,
+                              int32_t* n_keep_io, int32_t kept_in_flight, rato_cut_result* out, void* stream) {
+  if (!s || !final_du || !final_rhs || n_c < 0 || !u_lin || !out || !out->us || !keep || !keep_idle_count || !n_keep_io ||
+      max_cuts < 0)
+    return RATO_EINVAL;
+  const rato_cut_config& c = s->c;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  CutLoop L;
+  int rc = L.init(s, final_du, final_rhs, n_c, u_lin, with_cvar != 0, tol, max_cuts, final_cut_above, check_finite != 0, keep,
+                  keep_idle_count, n_keep_io);
+  if (rc != RATO_OK) return rc;
+  if (L.wants_kept()) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!kept_in_flight) {
+      if ((rc = rato_cut_begin(s, u_lin, keep, L.n_kept, stream)) != RATO_OK) return rc;
+    }
+    // (the kept cuts' sums were armed where they were launched: rato_cut_begin / rato_cut_define_drone)
+    const bool armed = s->kept_armed;
+    s->kept_armed = false;
+    hipError_t e = armed ? rato::readback_wait(c.sums_b_host, L.n_kept * s->nc, st) : hipStreamSynchronize(st);
+    if (e != hipSuccess) return RATO_EHIP - (int)e;
+    // (not armed: the words were not watched -- a define that failed before its launch leaves them pre-set; never data)
+    if (!armed && rato::readback_pending(c.sums_b_host, L.n_kept * s->nc)) return RATO_EHIP - (int)hipErrorNotReady;
+    L.oracle_s += seconds_since(t0);
+    if ((rc = L.add_kept(c.sums_b_host)) != RATO_OK) return rc;
+  }
+  if ((rc = L.begin()) != RATO_OK) return rc;
+  const size_t M = (size_t)c.M;
+  while (!L.done) {
+    const auto t0 = std::chrono::steady_clock::now();
+    memcpy(c.x_host, L.x.data(), sizeof(double) * (size_t)s->nU);
+    const int ring = L.ring;
+    rc = rato_cut_oracle_rollout(c.system, s->params(), c.uk_dev, c.s0, c.s1, c.s2, c.s3, c.x_host, c.x_dev,
+                                 c.ring_m + (size_t)ring * M, c.ring_arg + (size_t)ring * M, c.alpha, c.thr, c.alphaM,
+                                 c.workspace, c.workspace_bytes, c.ring_res + (size_t)ring * s->nres, c.part, c.res_host,
+                                 stream);
+    if (rc != RATO_OK) return rc;
+    L.oracle_s += seconds_since(t0);
+    if ((rc = L.consume(c.res_host)) != RATO_OK) return rc;
+  }
+  L.finish(out);
   return RATO_OK;
 }
 
@@ -645,3 +738,455 @@ extern "C" int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t
 }
 
 extern "C" size_t rato_scp_iter_bytes(void) { return sizeof(rato_scp_iter); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The reduced SCP of MANY drone problems in lockstep (the reference's alpha x repeat grid, drone_risk.py:495-539): one
+// problem = one rato_cut_solver (its own samples, alpha, rings and kept cuts) over one shared S, M and rato_drone_params.
+// Per SCP iteration: ONE batched define for every problem still running (controls and u_k up, generators-only
+// linearization, sample sums, the kept cuts' re-linearization, one wait), the masters of all problems on up to n_threads
+// host threads, and then ROUNDS: one batched oracle round trip (rowmax -> exact selection -> tail rows -> cut_finish, one
+// wait) for every problem still cutting, whose records are fed back to their masters in parallel.  A round's launches do
+// not grow with the batch: the table of its problems travels in one copy and every launch indexes it with blockIdx.y.  A
+// problem that leaves its subproblem early waits for the others before the next define.  Each problem runs the statements
+// of rato_scp_run_drone on the workgroup bodies of its single-problem kernels: its iterates are those of a solo run, bit for
+// bit.  A problem that fails leaves the batch (status[p]); the others go on.
+namespace {
+
+constexpr size_t BATCH_ALIGN = 256;
+size_t align_up(size_t v) { return (v + BATCH_ALIGN - 1) / BATCH_ALIGN * BATCH_ALIGN; }
+
+// a small persistent pool: run(n, f) calls f(0 .. n-1) on the caller and up to n_threads - 1 workers
+class TaskPool {
+ public:
+  explicit TaskPool(int n_threads) {
+    for (int i = 1; i < n_threads; ++i) workers_.emplace_back([this] { work(); });
+  }
+  ~TaskPool() {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      stop_ = true;
+      ++gen_;
+    }
+    cv_.notify_all();
+    for (auto& t : workers_) t.join();
+  }
+  template <class F>
+  void run(int n, F&& f) {
+    if (workers_.empty() || n < 2) {
+      for (int i = 0; i < n; ++i) f(i);
+      return;
+    }
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      fn_ = [&f](int i) { f(i); };
+      total_ = n;
+      next_.store(0);
+      pending_ = (int)workers_.size();
+      ++gen_;
+    }
+    cv_.notify_all();
+    drain();
+    std::unique_lock<std::mutex> lk(mu_);
+    done_cv_.wait(lk, [this] { return pending_ == 0; });
+    fn_ = nullptr;
+  }
+
+ private:
+  void drain() {
+    for (;;) {
+      const int i = next_.fetch_add(1);
+      if (i >= total_) return;
+      fn_(i);
+    }
+  }
+  void work() {
+    uint64_t seen = 0;
+    for (;;) {
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return gen_ != seen; });
+        seen = gen_;
+        if (stop_) return;
+      }
+      drain();
+      std::lock_guard<std::mutex> lk(mu_);
+      if (--pending_ == 0) done_cv_.notify_one();
+    }
+  }
+  std::vector<std::thread> workers_;
+  std::mutex mu_;
+  std::condition_variable cv_, done_cv_;
+  std::function<void(int)> fn_;
+  std::atomic<int> next_{0};
+  int total_ = 0, pending_ = 0;
+  uint64_t gen_ = 0;
+  bool stop_ = false;
+};
+
+// sizes of a batch of K problems (S, M, ld, keep_max shared)
+struct BatchLayout {
+  size_t d_tab, d_uk, d_us, d_slots, d_rows, d_size;   // define region (table + staged inputs + kept-cut rows)
+  size_t r_tab, r_x, r_size;                           // round region (table + x)
+  size_t a22, gpart, dev_bytes;                        // device: [define | round | A22 [K][S 3 ld] | gpart [K][nblk][6S+6]]
+  size_t h_res, h_sums, h_ksums, host_bytes;           // pinned: [define | round | res [K][nres] | sums | kept sums]
+  BatchLayout(int K, int S, int64_t ld, int nblk, int keep_max, int nc, int nres) {
+    const size_t nU = 3 * (size_t)S, Kz = (size_t)K, km = (size_t)std::max(keep_max, 1);
+    d_tab = 0;
+    d_uk = align_up(Kz * sizeof(rato::BatchProb));
+    d_us = d_uk + align_up(Kz * nU * sizeof(double));
+    d_slots = d_us + align_up(Kz * nU * sizeof(float));
+    d_rows = d_slots + align_up(Kz * km * sizeof(int32_t));
+    d_size = d_rows + align_up(Kz * km * sizeof(rato::BatchCut));
+    r_tab = d_size;
+    r_x = r_tab + align_up(Kz * sizeof(rato::BatchProb));
+    r_size = r_x + align_up(Kz * nU * sizeof(double)) - r_tab;
+    a22 = r_tab + r_size;
+    gpart = a22 + align_up(Kz * nU * (size_t)ld * sizeof(float));
+    dev_bytes = gpart + align_up(Kz * (size_t)nblk * (6 * (size_t)S + 6) * sizeof(float));
+    h_res = r_tab + r_size;
+    h_sums = h_res + align_up(Kz * (size_t)nres * sizeof(double));
+    h_ksums = h_sums + align_up(Kz * (6 * (size_t)S + 6) * sizeof(double));
+    host_bytes = h_ksums + align_up(Kz * km * (size_t)nc * sizeof(double));
+  }
+};
+
+int batch_check(rato_cut_solver* const* solvers, int32_t K) {
+  if (!solvers || K < 1 || K > 65535) return RATO_EINVAL;
+  const rato_cut_solver* s0 = solvers[0];
+  for (int32_t p = 0; p < K; ++p) {
+    const rato_cut_solver* s = solvers[p];
+    if (!s || s->c.system != 0 || s->c.mode_saa == 0 || s->c.S < 2 || s->c.S != s0->c.S || s->c.M != s0->c.M ||
+        s->c.keep_max != s0->c.keep_max || s->c.cap != s0->c.cap || !s->c.part || (s->c.keep_max > 0 && !s->c.part_b) ||
+        memcmp(&s->drone, &s0->drone, sizeof(rato_drone_params)) != 0)
+      return RATO_EINVAL;
+    for (int32_t q = 0; q < p; ++q)
+      if (solvers[q] == s) return RATO_EINVAL;   // (one solver's rings cannot serve two problems)
+  }
+  return RATO_OK;
+}
+
+}  // namespace
+
+struct rato_scp_batch {
+  std::vector<rato_cut_solver*> sv;
+  rato_drone_params P;
+  int K = 0, S = 0, nU = 0, nc = 0, nres = 0, nblk = 0, keep_max = 0, ncols = 0;
+  int64_t M = 0, ld = 0;
+  unsigned char *dev = nullptr, *host = nullptr;
+  BatchLayout lay{1, 2, 1, 1, 0, 1, 1};
+  std::unique_ptr<TaskPool> pool;
+};
+
+extern "C" int rato_scp_batch_bytes(rato_cut_solver* const* solvers, int32_t K, size_t* device_bytes, size_t* host_bytes) {
+  if (!device_bytes || !host_bytes) return RATO_EINVAL;
+  const int rc = batch_check(solvers, K);
+  if (rc != RATO_OK) return rc;
+  const rato_cut_solver* s = solvers[0];
+  const BatchLayout lay(K, s->c.S, s->drone.ld, s->nblk, s->c.keep_max, s->nc, s->nres);
+  *device_bytes = lay.dev_bytes;
+  *host_bytes = lay.host_bytes;
+  return RATO_OK;
+}
+
+extern "C" int rato_scp_batch_create(rato_scp_batch** out, rato_cut_solver* const* solvers, int32_t K, int32_t n_threads,
+                                     void* device_buf, size_t device_bytes, void* host_buf, size_t host_bytes) {
+  if (!out || n_threads < 1 || n_threads > 256 || !device_buf || !host_buf) return RATO_EINVAL;
+  int rc = batch_check(solvers, K);
+  if (rc != RATO_OK) return rc;
+  const rato_cut_solver* s = solvers[0];
+  const BatchLayout lay(K, s->c.S, s->drone.ld, s->nblk, s->c.keep_max, s->nc, s->nres);
+  if (device_bytes < lay.dev_bytes || host_bytes < lay.host_bytes || ((uintptr_t)device_buf % BATCH_ALIGN) != 0 ||
+      ((uintptr_t)host_buf % 16) != 0)
+    return RATO_EINVAL;
+  rato_scp_batch* b = new rato_scp_batch;
+  b->sv.assign(solvers, solvers + K);
+  b->P = s->drone;
+  b->K = K;
+  b->S = s->c.S;
+  b->nU = s->nU;
+  b->nc = s->nc;
+  b->nres = s->nres;
+  b->nblk = s->nblk;
+  b->keep_max = s->c.keep_max;
+  b->ncols = 6 * b->S + 6;
+  b->M = s->c.M;
+  b->ld = s->drone.ld;
+  b->dev = static_cast<unsigned char*>(device_buf);
+  b->host = static_cast<unsigned char*>(host_buf);
+  b->lay = lay;
+  b->pool.reset(new TaskPool(std::min<int>(n_threads, K)));
+  *out = b;
+  return RATO_OK;
+}
+
+extern "C" void rato_scp_batch_destroy(rato_scp_batch* b) { delete b; }
+
+extern "C" size_t rato_scp_batch_iter_bytes(void) { return sizeof(rato_scp_batch_iter); }
+
+extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, int32_t iters, int32_t first_cvar, double tol,
+                                        int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
+                                        int32_t* keep_idle_count, int32_t* n_keep, double* us_hist, rato_scp_iter* rec,
+                                        rato_scp_batch_iter* brec, int32_t* status, int32_t* done, int32_t* rounds,
+                                        void* stream) {
+  if (!b || !us0 || iters < 0 || max_cuts < 0 || !keep || !keep_idle_count || !n_keep || !us_hist || !rec || !brec ||
+      !status || !done || !rounds)
+    return RATO_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int K = b->K, S = b->S, nU = b->nU, nc = b->nc, nres = b->nres, ncols = b->ncols, km = std::max(b->keep_max, 1);
+  const int n_c = 6, n_words = RATO_N_STATS + nc;
+  const size_t Mz = (size_t)b->M;
+  const double Md = (double)b->M, inv_M = 1.0 / Md;
+  const BatchLayout& L = b->lay;
+  double* res_host = reinterpret_cast<double*>(b->host + L.h_res);
+  double* sums_host = reinterpret_cast<double*>(b->host + L.h_sums);
+  double* ksums_host = reinterpret_cast<double*>(b->host + L.h_ksums);
+  auto dev_of = [&](const void* host_ptr) {   // the device address of a byte of the define / round mirrors
+    return b->dev + (static_cast<const unsigned char*>(host_ptr) - b->host);
+  };
+  std::vector<std::vector<double>> us(K), sol(K);
+  std::vector<std::unique_ptr<CutLoop>> loop(K);
+  std::vector<rato_cut_result> res(K);
+  std::vector<std::vector<int32_t>> cut_slot(K);
+  std::vector<std::vector<double>> cut_lambda(K);
+  std::vector<int> dpos(K, -1);
+  for (int p = 0; p < K; ++p) {
+    us[p].assign(us0 + (size_t)p * nU, us0 + (size_t)(p + 1) * nU);
+    sol[p].resize(nU);
+    cut_slot[p].resize(b->sv[p]->c.cap + 8);
+    cut_lambda[p].resize(b->sv[p]->c.cap + 8);
+    status[p] = RATO_OK;
+    done[p] = 0;
+    const int rc = settle_kept(b->sv[p], st);   // a kept-cuts launch of a solo define nobody waited for
+    if (rc != RATO_OK) return rc;
+  }
+  *rounds = 0;
+  // the problems' own device copies (only the pointers differ): the table's rows of a problem
+  auto fill_common = [&](rato::BatchProb& t, int p) {
+    const rato_cut_config& c = b->sv[p]->c;
+    memset(&t, 0, sizeof(t));
+    t.dW = c.s0;
+    t.mass = c.s1;
+    t.Qsym = c.s2;
+    t.alpha = c.alpha;
+    t.alphaM = c.alphaM;
+    t.thr = c.thr;
+    int vmax = 0;
+    unsigned kr = 0;
+    rato_sel::stats_rank(b->M, c.alpha, kr, vmax);
+    t.k = kr;
+    t.var_is_max = vmax;
+    t.m_base = c.ring_m;
+    t.arg_base = c.ring_arg;
+    t.res_base = c.ring_res;
+    t.part = c.part;
+    t.part_b = c.part_b;
+  };
+  const bool select_batched = rato::risk_stats_batch_applies(b->M);
+  for (int it = 0; it < iters; ++it) {
+    const auto t_it = std::chrono::steady_clock::now();
+    rato_scp_batch_iter& br = brec[it];
+    memset(&br, 0, sizeof(br));
+    const bool cvar = it >= first_cvar;
+    std::vector<int> act;
+    for (int p = 0; p < K; ++p)
+      if (status[p] == RATO_OK) act.push_back(p);
+    br.active = (int32_t)act.size();
+    if (act.empty()) continue;
+    // ---- define: every active problem's table row, staged inputs and kept-cut rows into the pinned mirror, ONE copy
+    rato::BatchProb* tab = reinterpret_cast<rato::BatchProb*>(b->host + L.d_tab);
+    double* uk_h = reinterpret_cast<double*>(b->host + L.d_uk);
+    float* us_h = reinterpret_cast<float*>(b->host + L.d_us);
+    int32_t* slots_h = reinterpret_cast<int32_t*>(b->host + L.d_slots);
+    rato::BatchCut* rows_h = reinterpret_cast<rato::BatchCut*>(b->host + L.d_rows);
+    std::vector<rato::BatchCut> plain, uni;
+    int n = 0, kn_max = 0, keep_top = 0;
+    for (int p : act) {
+      rato_cut_solver* s = b->sv[p];
+      int32_t* kp = keep + (size_t)p * km;
+      const int Kp = (cvar && s->c.recycle) ? n_keep[p] : 0;
+      if (n_keep[p] < 0 || n_keep[p] > s->c.keep_max || Kp < 0 || (Kp > 0 && !keep_ok(s, kp, Kp))) {
+        status[p] = RATO_EINVAL;
+        continue;
+      }
+      rato::BatchProb& t = tab[n];
+      fill_common(t, p);
+      double* uk = uk_h + (size_t)n * nU;
+      float* usf = us_h + (size_t)n * nU;
+      int32_t* sl = slots_h + (size_t)n * km;
+      for (int i = 0; i < nU; ++i) {
+        uk[i] = us[p][i];
+        usf[i] = (float)us[p][i];
+      }
+      for (int k = 0; k < Kp; ++k) sl[k] = kp[k];
+      t.uk = reinterpret_cast<const double*>(dev_of(uk));
+      t.us = reinterpret_cast<const float*>(dev_of(usf));
+      t.slots = reinterpret_cast<const int32_t*>(dev_of(sl));
+      t.n_keep = Kp;
+      t.A22 = reinterpret_cast<float*>(b->dev + L.a22) + (size_t)n * nU * (size_t)b->ld;
+      t.gpart = reinterpret_cast<float*>(b->dev + L.gpart) + (size_t)n * b->nblk * ncols;
+      t.sums_host = sums_host + (size_t)p * ncols;
+      t.sums_b_host = ksums_host + (size_t)p * km * nc;
+      if (rato::readback_poll_enabled()) rato::readback_arm(t.sums_host, ncols);
+      if (Kp > 0) {
+        if (rato::readback_poll_enabled()) rato::readback_arm(t.sums_b_host, Kp * nc);
+        keep_top = std::max(keep_top, Kp);
+        if (rato::drone_tail_union_form(S, Kp)) {
+          for (int k0 = 0; k0 < Kp; k0 += 16) {   // (TRU_KMAX cuts per row: the single launcher's chunks)
+            const int kn = std::min(16, Kp - k0);
+            uni.push_back({n, k0, kn, Kp});
+            kn_max = std::max(kn_max, kn);
+          }
+        } else {
+          for (int k = 0; k < Kp; ++k) plain.push_back({n, k, 1, Kp});
+        }
+      }
+      dpos[p] = n++;
+    }
+    act.erase(std::remove_if(act.begin(), act.end(), [&](int p) { return status[p] != RATO_OK; }), act.end());
+    if (n == 0) continue;
+    for (size_t i = 0; i < plain.size(); ++i) rows_h[i] = plain[i];
+    for (size_t i = 0; i < uni.size(); ++i) rows_h[plain.size() + i] = uni[i];
+    hipError_t e = hipMemcpyAsync(b->dev + L.d_tab, b->host + L.d_tab, L.d_size, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return RATO_EHIP - (int)e;
+    const rato::BatchProb* tab_d = reinterpret_cast<const rato::BatchProb*>(b->dev + L.d_tab);
+    const rato::BatchCut* rows_d = reinterpret_cast<const rato::BatchCut*>(b->dev + L.d_rows);
+    int rc = rato::launch_drone_linearize_generators_batch(&b->P, tab_d, n, st);
+    if (rc == RATO_OK) rc = rato::launch_define_sums_batch(tab_d, n, b->nblk, ncols, st);
+    if (rc == RATO_OK && !plain.empty())
+      rc = rato::launch_drone_tail_kept_batch(&b->P, tab_d, rows_d, (int)plain.size(), false, 1, st);
+    if (rc == RATO_OK && !uni.empty())
+      rc = rato::launch_drone_tail_kept_batch(&b->P, tab_d, rows_d + plain.size(), (int)uni.size(), true, kn_max, st);
+    if (rc == RATO_OK && keep_top > 0) rc = rato::launch_kept_sums_batch(tab_d, n, b->nblk, nc, keep_top, st);
+    if (rc != RATO_OK) return rc;
+    for (int p : act) {
+      const rato::BatchProb& t = tab[dpos[p]];
+      e = rato::readback_wait(t.sums_host, ncols, st);
+      if (e == hipSuccess && t.n_keep > 0) e = rato::readback_wait(t.sums_b_host, t.n_keep * nc, st);
+      if (e != hipSuccess) return RATO_EHIP - (int)e;
+    }
+    br.define_s = seconds_since(t_it);
+    // ---- the subproblems up to their first query (equality rows, kept cuts, first master), in parallel
+    auto t0 = std::chrono::steady_clock::now();
+    b->pool->run((int)act.size(), [&](int i) {
+      const int p = act[i];
+      rato_cut_solver* s = b->sv[p];
+      const double* sm = tab[dpos[p]].sums_host;
+      if (check_finite)
+        for (int j = 0; j < ncols; ++j)
+          if (!std::isfinite(sm[j])) {
+            status[p] = RATO_ENONFINITE;
+            return;
+          }
+      // the equality rows (as rato_scp_run_drone builds them)
+      std::vector<double> final_du((size_t)n_c * nU, 0.0), final_rhs(n_c);
+      for (int t = 0; t < S; ++t)
+        for (int a = 0; a < 3; ++a) {
+          final_du[(size_t)a * nU + t * 3 + a] = sm[t * 6 + a] * inv_M;
+          final_du[(size_t)(3 + a) * nU + t * 3 + a] = sm[t * 6 + 3 + a] * inv_M;
+        }
+      for (int r = 0; r < n_c; ++r) final_rhs[r] = sm[6 * S + r] / Md;
+      loop[p].reset(new CutLoop);
+      CutLoop& lp = *loop[p];
+      int r2 = lp.init(s, final_du.data(), final_rhs.data(), n_c, us[p].data(), cvar, tol, max_cuts, final_cut_above,
+                       check_finite != 0, keep + (size_t)p * km, keep_idle_count + (size_t)p * km, n_keep + p);
+      if (r2 == RATO_OK && lp.wants_kept()) r2 = lp.add_kept(tab[dpos[p]].sums_b_host);
+      if (r2 == RATO_OK) r2 = lp.begin();
+      if (r2 != RATO_OK) status[p] = r2;
+    });
+    br.master_s += seconds_since(t0);
+    // ---- rounds: one batched oracle round trip for every problem still cutting
+    rato::BatchProb* rtab = reinterpret_cast<rato::BatchProb*>(b->host + L.r_tab);
+    double* x_h = reinterpret_cast<double*>(b->host + L.r_x);
+    for (;;) {
+      std::vector<int> q;
+      for (int p : act)
+        if (status[p] == RATO_OK && !loop[p]->done) q.push_back(p);
+      if (q.empty()) break;
+      t0 = std::chrono::steady_clock::now();
+      const int nq = (int)q.size();
+      for (int i = 0; i < nq; ++i) {
+        const int p = q[i];
+        const rato_cut_config& c = b->sv[p]->c;
+        const CutLoop& lp = *loop[p];
+        rato::BatchProb& t = rtab[i];
+        t = tab[dpos[p]];
+        double* x = x_h + (size_t)i * nU;
+        memcpy(x, lp.x.data(), sizeof(double) * nU);
+        t.x = reinterpret_cast<const double*>(dev_of(x));
+        t.m_out = c.ring_m + (size_t)lp.ring * Mz;
+        t.arg_out = c.ring_arg + (size_t)lp.ring * Mz;
+        t.res_dev = c.ring_res + (size_t)lp.ring * nres;
+        t.res_host = res_host + (size_t)p * nres;
+        if (rato::readback_poll_enabled()) rato::readback_arm(t.res_host, n_words);
+      }
+      // (one copy: the rows, then x at a fixed offset -- only the rows' and x's used parts travel)
+      e = hipMemcpyAsync(b->dev + L.r_tab, b->host + L.r_tab, (size_t)nq * sizeof(rato::BatchProb), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(b->dev + L.r_x, b->host + L.r_x, (size_t)nq * nU * sizeof(double), hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) return RATO_EHIP - (int)e;
+      const rato::BatchProb* rtab_d = reinterpret_cast<const rato::BatchProb*>(b->dev + L.r_tab);
+      rc = rato::launch_drone_rowmax_rollout_batch(&b->P, rtab_d, nq, st);
+      if (rc == RATO_OK) {
+        if (select_batched) {
+          rc = rato::launch_risk_stats_batch(rtab_d, nq, b->M, st);
+        } else {   // beyond the one-workgroup selection: each problem's own (on its own workspace), stream-ordered
+          for (int i = 0; i < nq && rc == RATO_OK; ++i) {
+            const rato_cut_config& c = b->sv[q[i]]->c;
+            rc = rato_risk_stats(rtab[i].m_out, b->M, c.alpha, c.thr, c.workspace, c.workspace_bytes, rtab[i].res_dev, stream);
+          }
+        }
+      }
+      if (rc == RATO_OK) rc = rato::launch_drone_tail_rows_batch(&b->P, rtab_d, nq, st);
+      if (rc == RATO_OK) rc = rato::launch_cut_finish_batch(rtab_d, nq, b->nblk, nc, RATO_N_STATS, st);
+      if (rc != RATO_OK) return rc;
+      for (int i = 0; i < nq; ++i) {
+        e = rato::readback_wait(rtab[i].res_host, n_words, st);
+        if (e != hipSuccess) return RATO_EHIP - (int)e;
+      }
+      br.oracle_s += seconds_since(t0);
+      ++br.rounds;
+      ++*rounds;
+      t0 = std::chrono::steady_clock::now();
+      b->pool->run(nq, [&](int i) {
+        const int p = q[i];
+        const int r2 = loop[p]->consume(rtab[i].res_host);
+        if (r2 != RATO_OK) status[p] = r2;
+      });
+      br.master_s += seconds_since(t0);
+    }
+    // ---- the keep rule and the outputs of every problem that solved its subproblem
+    for (int p : act) {
+      if (status[p] != RATO_OK) {
+        loop[p].reset();
+        continue;
+      }
+      rato_cut_result& r = res[p];
+      memset(&r, 0, sizeof(r));
+      r.us = sol[p].data();
+      r.cut_slot = cut_slot[p].data();
+      r.cut_lambda = cut_lambda[p].data();
+      r.cut_capacity = (int)cut_slot[p].size();
+      loop[p]->finish(&r);
+      loop[p].reset();
+      rato_scp_iter& ri = rec[(size_t)p * iters + it];
+      ri.define_s = ri.solve_s = ri.oracle_s = NAN;   // (per problem only the master's own time is known: brec has the clocks)
+      ri.master_s = r.master_s;
+      ri.t_risk = r.t_risk;
+      ri.slack = r.slack;
+      ri.phi = r.phi;
+      ri.cuts = r.cuts;
+      ri.status = r.status;
+      ri.recycled = r.recycled;
+      ri.reserved = 0;
+      memcpy(us_hist + ((size_t)p * iters + it) * nU, sol[p].data(), sizeof(double) * nU);
+      us[p] = sol[p];
+      done[p] = it + 1;
+    }
+    if (it == iters - 1) {
+      e = hipStreamSynchronize(st);
+      if (e != hipSuccess) return RATO_EHIP - (int)e;
+    }
+    br.total_s = seconds_since(t_it);
+  }
+  return RATO_OK;
+}

@@ -474,12 +474,11 @@ struct XArg {
   double v[XARG_MAX];
 };
 
-template <bool BYVAL>
-__global__ __launch_bounds__(RATO_BLOCK) void drone_rowmax_rollout_kernel(
-    rato_drone_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
-    const float* __restrict__ Qsym, const double* __restrict__ xs_mem, const XArg xv, float* __restrict__ m_out,
-    int* __restrict__ arg_out) {
-  const double* __restrict__ xs = BYVAL ? xv.v : xs_mem;
+// the body of one workgroup (samples blockIdx.x * 256 ..): shared by the single-problem kernel and the batched one
+__device__ __forceinline__ void drone_rowmax_rollout_block(const rato_drone_params& P, const double* __restrict__ uk,
+                                                           const float* __restrict__ dW, const float* __restrict__ mass,
+                                                           const float* __restrict__ Qsym, const double* __restrict__ xs,
+                                                           float* __restrict__ m_out, int* __restrict__ arg_out) {
   const long m = (long)blockIdx.x * RATO_BLOCK + threadIdx.x;
   if (m >= P.M) return;
   const size_t ld = (size_t)P.ld;
@@ -580,6 +579,21 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_rowmax_rollout_kernel(
     }
   m_out[m] = (float)bv;
   arg_out[m] = bi;
+}
+
+template <bool BYVAL>
+__global__ __launch_bounds__(RATO_BLOCK) void drone_rowmax_rollout_kernel(
+    rato_drone_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
+    const float* __restrict__ Qsym, const double* __restrict__ xs_mem, const XArg xv, float* __restrict__ m_out,
+    int* __restrict__ arg_out) {
+  drone_rowmax_rollout_block(P, uk, dW, mass, Qsym, BYVAL ? xv.v : xs_mem, m_out, arg_out);
+}
+
+// batched: workgroup (b, i) is block b of table row i (x from device memory)
+__global__ __launch_bounds__(RATO_BLOCK) void drone_rowmax_rollout_batch_kernel(rato_drone_params P,
+                                                                                const rato::BatchProb* __restrict__ tab) {
+  const rato::BatchProb& t = tab[blockIdx.y];
+  drone_rowmax_rollout_block(P, t.uk, t.dW, t.mass, t.Qsym, t.x, t.m_out, t.arg_out);
 }
 
 // maximum of a non-negative int over the wave, in every lane (DPP tree: no LDS crossbar round trips)
@@ -774,12 +788,12 @@ __device__ __forceinline__ void drone_tail_block(const rato_drone_params& P, con
 // rollout in fp64 up to their own t*, leaving e22 = 1 - a22 of both axes in LDS ([S][2][64] floats: exact to 1e-10 of
 // a22), pick up W and g of their arg-max row on the way, and then run the adjoint sweep from t* down, exactly as
 // drone_tail_rows_implicit_kernel does from its table.  Output layout of tail_rows_batch_kernel (offset sum = sum w g).
-__global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_kernel(
-    rato_drone_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
+// one workgroup of cut kk of K (slots[kk], or slot 0 without slots): shared by the single-problem and the batched kernels
+__device__ __forceinline__ void drone_tail_rows_rollout_block(
+    const rato_drone_params& P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
     const float* __restrict__ Qsym, const float* __restrict__ m_base, const int* __restrict__ arg_base,
     const double* __restrict__ stats_base, long stats_stride, const int* __restrict__ slots, double alphaM,
-    double* __restrict__ part, int c_tab) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char trr_lds[];
+    double* __restrict__ part, int c_tab, int K, int kk, unsigned char* trr_lds) {
   const int S = P.S;
   const long M = P.M, ld = P.ld;
   const int nw = 2 * (S - 1), nc = nw + 1;
@@ -787,7 +801,6 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_kernel(
   TSTAMP(0);
   double* Ctab = c_tab ? acc + nc : nullptr;                          // [2][S-1][TAIL_CSTRIDE] the sweep's terms per lane
   float* E = reinterpret_cast<float*>(acc + nc + (c_tab ? tail_ctab_doubles(S) : 0));   // [S][2][64] e22 of the current chunk
-  const int K = gridDim.y, kk = blockIdx.y;
   const long slot = slots ? slots[kk] : 0;
   const float* __restrict__ mvals = m_base + slot * M;
   const int* __restrict__ arg = arg_base + slot * M;
@@ -814,6 +827,39 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_kernel(
   for (int i = threadIdx.x; i < nc; i += RATO_BLOCK) part[((size_t)blockIdx.x * K + kk) * nc + i] = acc[i];
 }
 
+__global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_kernel(
+    rato_drone_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
+    const float* __restrict__ Qsym, const float* __restrict__ m_base, const int* __restrict__ arg_base,
+    const double* __restrict__ stats_base, long stats_stride, const int* __restrict__ slots, double alphaM,
+    double* __restrict__ part, int c_tab) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char trr_lds[];
+  drone_tail_rows_rollout_block(P, uk, dW, mass, Qsym, m_base, arg_base, stats_base, stats_stride, slots, alphaM, part, c_tab,
+                                gridDim.y, blockIdx.y, trr_lds);
+}
+
+// batched, one cut per problem (the oracle round trip: the cut in ring slot m_out / arg_out / res_dev): workgroup (b, i)
+// is block b of table row i
+__global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_batch_kernel(rato_drone_params P,
+                                                                                   const rato::BatchProb* __restrict__ tab,
+                                                                                   long stats_stride, int c_tab) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char trr_lds[];
+  const rato::BatchProb& t = tab[blockIdx.y];
+  drone_tail_rows_rollout_block(P, t.uk, t.dW, t.mass, t.Qsym, t.m_out, t.arg_out, t.res_dev, stats_stride, nullptr,
+                                t.alphaM, t.part, c_tab, 1, 0, trr_lds);
+}
+
+// batched kept cuts, one cut per row (the per-cut form of rato_drone_tail_rows_rollout): row j = cut rows[j].k0 of the
+// problem's rows[j].K kept cuts
+__global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_kept_batch_kernel(
+    rato_drone_params P, const rato::BatchProb* __restrict__ tab, const rato::BatchCut* __restrict__ rows, long stats_stride,
+    int c_tab) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char trr_lds[];
+  const rato::BatchCut r = rows[blockIdx.y];
+  const rato::BatchProb& t = tab[r.prob];
+  drone_tail_rows_rollout_block(P, t.uk, t.dW, t.mass, t.Qsym, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
+                                t.alphaM, t.part_b, c_tab, r.K, r.k0, trr_lds);
+}
+
 // K > 1 (the cuts kept from the previous subproblem, re-linearized at the new u_k): ONE pass per block of 256 samples for
 // all the cuts.  The rollout at u_k is the same for every cut and their tails are nearly the same samples, so the UNION of
 // the tails is compacted (in sample order) and walked in chunks of 64: wave 0 re-runs the rollout once per chunk (e22 of
@@ -829,12 +875,11 @@ __host__ __device__ inline size_t tail_union_lds_bytes(int S, int K) {
   return sizeof(double) * ((size_t)K * nc + (size_t)K * 2 * RATO_WAVE) + sizeof(float) * (size_t)S * 2 * RATO_WAVE +
          (sizeof(float) + sizeof(int)) * (size_t)K * RATO_WAVE + sizeof(unsigned) * (size_t)S;
 }
-__global__ __launch_bounds__(TRU_NW* RATO_WAVE) void drone_tail_rows_rollout_union_kernel(
-    rato_drone_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
+__device__ __forceinline__ void drone_tail_rows_rollout_union_block(
+    const rato_drone_params& P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
     const float* __restrict__ Qsym, const float* __restrict__ m_base, const int* __restrict__ arg_base,
     const double* __restrict__ stats_base, long stats_stride, const int* __restrict__ slots, int k0, int K, int K_total,
-    double alphaM, double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char tru_lds[];
+    double alphaM, double* __restrict__ part, unsigned char* tru_lds) {
   constexpr int NT = TRU_NW * RATO_WAVE;
   const int S = P.S;
   const long M = P.M, ld = P.ld;
@@ -1027,6 +1072,27 @@ __global__ __launch_bounds__(TRU_NW* RATO_WAVE) void drone_tail_rows_rollout_uni
     const int kk = i / nc, j = i - kk * nc;
     part[((size_t)blockIdx.x * K_total + (k0 + kk)) * nc + j] = acc[i];
   }
+}
+
+__global__ __launch_bounds__(TRU_NW* RATO_WAVE) void drone_tail_rows_rollout_union_kernel(
+    rato_drone_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ mass,
+    const float* __restrict__ Qsym, const float* __restrict__ m_base, const int* __restrict__ arg_base,
+    const double* __restrict__ stats_base, long stats_stride, const int* __restrict__ slots, int k0, int K, int K_total,
+    double alphaM, double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tru_lds[];
+  drone_tail_rows_rollout_union_block(P, uk, dW, mass, Qsym, m_base, arg_base, stats_base, stats_stride, slots, k0, K, K_total,
+                                      alphaM, part, tru_lds);
+}
+
+// batched kept cuts in the union form: row j = cuts k0 .. k0 + kn of the problem's K kept cuts (the chunks of TRU_KMAX the
+// single launcher issues one launch each)
+__global__ __launch_bounds__(TRU_NW* RATO_WAVE) void drone_tail_rows_rollout_union_batch_kernel(
+    rato_drone_params P, const rato::BatchProb* __restrict__ tab, const rato::BatchCut* __restrict__ rows, long stats_stride) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tru_lds[];
+  const rato::BatchCut r = rows[blockIdx.y];
+  const rato::BatchProb& t = tab[r.prob];
+  drone_tail_rows_rollout_union_block(P, t.uk, t.dW, t.mass, t.Qsym, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
+                                      r.k0, r.kn, r.K, t.alphaM, t.part_b, tru_lds);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1476,6 +1542,28 @@ extern "C" int rato_saa_tail_rows_batch(const float* G, const float* W, int64_t 
 }
 
 namespace {
+// dynamic LDS of drone_tail_rows_rollout_kernel for horizon S (0: beyond 160 KB), and whether the sweep's terms go through
+// LDS (c_tab): the per-lane terms in LDS (summed after the sweep) while two workgroups still fit a CU; RATO_TAIL_CTAB=0: the
+// wave-wide sum inside every step of the sweep
+size_t tail_rows_lds(int S, int& c_tab) {
+  const size_t lds = (size_t)(2 * (S - 1) + 1) * sizeof(double) + (size_t)S * 2 * RATO_WAVE * sizeof(float);
+  c_tab = 0;
+  if (lds + 4096 > 160 * 1024) return 0;   // S <= 300 (4 KB: the static lists of the tail compaction)
+  static const int ctab_env = [] { const char* e = getenv("RATO_TAIL_CTAB"); return e ? atoi(e) : 1; }();
+  const size_t lds_c = lds + tail_ctab_doubles(S) * sizeof(double);
+  c_tab = (ctab_env && lds_c + 4096 <= 80 * 1024) ? 1 : 0;
+  return c_tab ? lds_c : lds;
+}
+}  // namespace
+
+namespace rato {
+bool drone_tail_union_form(int S, int K) {
+  static const int union_env = [] { const char* e = getenv("RATO_TAIL_UNION"); return e ? atoi(e) : 1; }();
+  return K > 1 && union_env && tail_union_lds_bytes(S, K < TRU_KMAX ? K : TRU_KMAX) + 4096 <= 160 * 1024;
+}
+}  // namespace rato
+
+namespace {
 // xs_host != NULL and S n_u <= XARG_MAX: x is passed by value (no device copy of it is read)
 int drone_rowmax_rollout_launch(const rato_drone_params* p, const double* uk, const float* dW, const float* mass,
                                 const float* Qsym, const double* xs, const double* xs_host, float* m_out,
@@ -1517,14 +1605,9 @@ extern "C" int rato_drone_tail_rows_rollout(const rato_drone_params* p, const do
       !Qsym || !m_base || !arg_base || !stats_base || !part || K < 1 || K > 65535 || (!slots && K != 1) ||
       stats_stride < 11)
     return RATO_EINVAL;
-  size_t lds = (size_t)(2 * (p->S - 1) + 1) * sizeof(double) + (size_t)p->S * 2 * RATO_WAVE * sizeof(float);
-  if (lds + 4096 > 160 * 1024) return RATO_EINVAL;   // S <= 300 (4 KB: the static lists of the tail compaction)
-  // the sweep's per-lane terms in LDS (summed after the sweep) while two workgroups still fit a CU; RATO_TAIL_CTAB=0: the
-  // wave-wide sum inside every step of the sweep
-  static const int ctab_env = [] { const char* e = getenv("RATO_TAIL_CTAB"); return e ? atoi(e) : 1; }();
-  const size_t lds_c = lds + tail_ctab_doubles(p->S) * sizeof(double);
-  const int c_tab = (ctab_env && lds_c + 4096 <= 80 * 1024) ? 1 : 0;
-  if (c_tab) lds = lds_c;
+  int c_tab = 0;
+  const size_t lds = tail_rows_lds(p->S, c_tab);
+  if (!lds) return RATO_EINVAL;
   static rato::DynamicLdsLimit lds_limit;
   {
     const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
@@ -1534,10 +1617,9 @@ extern "C" int rato_drone_tail_rows_rollout(const rato_drone_params* p, const do
     if (e != hipSuccess) return RATO_EHIP - (int)e;
   }
   // several cuts (the kept cuts of a subproblem): the union form, up to TRU_KMAX cuts per launch (A/B: RATO_TAIL_UNION=0)
-  static const int union_env = [] { const char* e = getenv("RATO_TAIL_UNION"); return e ? atoi(e) : 1; }();
-  if (K > 1 && union_env) {
+  if (rato::drone_tail_union_form(p->S, K)) {
     const size_t lds_u = tail_union_lds_bytes(p->S, K < TRU_KMAX ? K : TRU_KMAX);
-    if (lds_u + 4096 <= 160 * 1024) {
+    {
       static rato::DynamicLdsLimit lds_limit_u;
       const hipError_t e = lds_limit_u.ensure(lds_u, [](size_t bytes) {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_union_kernel),
@@ -1561,6 +1643,71 @@ extern "C" int rato_drone_tail_rows_rollout(const rato_drone_params* p, const do
   return RATO_OK;
 }
 
+
+// ---- batched forms (cutloop.hip: rato_scp_batch_run_drone): the launches above over (sample blocks) x (table rows), the
+// same workgroup bodies, the same form decisions (S decides them: it is shared by the batch)
+namespace rato {
+int launch_drone_rowmax_rollout_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!p || !tab || n < 1 || n > 65535) return RATO_EINVAL;
+  hipLaunchKernelGGL(drone_rowmax_rollout_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), 0,
+                     st, *p, tab);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+int launch_drone_tail_rows_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!p || !tab || n < 1 || n > 65535 || p->S < 2) return RATO_EINVAL;
+  int c_tab = 0;
+  const size_t lds = tail_rows_lds(p->S, c_tab);
+  if (!lds) return RATO_EINVAL;
+  static rato::DynamicLdsLimit lds_limit;
+  const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_batch_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
+  hipLaunchKernelGGL(drone_tail_rows_rollout_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK),
+                     lds, st, *p, tab, stride, c_tab);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+// rows: the union form's chunks (union_form; kn_max = the largest chunk) or one row per cut
+int launch_drone_tail_kept_batch(const rato_drone_params* p, const BatchProb* tab, const BatchCut* rows, int n_rows,
+                                 bool union_form, int kn_max, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!p || !tab || !rows || n_rows < 1 || n_rows > 65535 || p->S < 2 || kn_max < 1 || kn_max > TRU_KMAX) return RATO_EINVAL;
+  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
+  const dim3 grid((unsigned)rato::nblocks_for(p->M), (unsigned)n_rows);
+  if (union_form) {
+    const size_t lds_u = tail_union_lds_bytes(p->S, kn_max);   // (the largest chunk's size; each row lays out its own)
+    static rato::DynamicLdsLimit lds_limit_u;
+    const hipError_t e = lds_limit_u.ensure(lds_u, [](size_t bytes) {
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_union_batch_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    });
+    if (e != hipSuccess) return RATO_EHIP - (int)e;
+    hipLaunchKernelGGL(drone_tail_rows_rollout_union_batch_kernel, grid, dim3(TRU_NW * RATO_WAVE), lds_u, st, *p, tab, rows, stride);
+    RATO_LAUNCH_CHECK();
+    return RATO_OK;
+  }
+  int c_tab = 0;
+  const size_t lds = tail_rows_lds(p->S, c_tab);
+  if (!lds) return RATO_EINVAL;
+  static rato::DynamicLdsLimit lds_limit;
+  const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_kept_batch_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  hipLaunchKernelGGL(drone_tail_rows_rollout_kept_batch_kernel, grid, dim3(RATO_BLOCK), lds, st, *p, tab, rows, stride, c_tab);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+}  // namespace rato
 
 namespace {
 bool car_params64_ok(const rato_car_params* p) {

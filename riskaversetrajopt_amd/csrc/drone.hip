@@ -291,8 +291,8 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_tiles_kernel(
 #define RATO_GEN_LDS_REDUCE 1   // A/B: 0 = six fp64 DPP trees per backward step
 #endif
 template <bool TABLES, bool WANT_Z>
-__global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_kernel(
-    rato_drone_params P, const float* __restrict__ us, const float* __restrict__ dW,
+__device__ __forceinline__ void drone_linearize_generators_block(
+    const rato_drone_params& P, const float* __restrict__ us, const float* __restrict__ dW,
     const float* __restrict__ mass, const float* __restrict__ Qsym, float* __restrict__ A22,
     float* __restrict__ W, float* __restrict__ g_up, float* __restrict__ Z, float* __restrict__ part) {
   // Arithmetic in fp64, outputs rounded ONCE to fp32 (round 3).  The kernel is bound by the latency of its loads, one
@@ -539,6 +539,22 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_kernel(
     for (int w = 0; w < NWV; ++w) acc += gen_red[w * (S + 1) * 6 + i];   // fixed order
     part[(size_t)blockIdx.x * (6 * S + 6) + i] = (float)acc;
   }
+}
+
+template <bool TABLES, bool WANT_Z>
+__global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_kernel(
+    rato_drone_params P, const float* __restrict__ us, const float* __restrict__ dW,
+    const float* __restrict__ mass, const float* __restrict__ Qsym, float* __restrict__ A22,
+    float* __restrict__ W, float* __restrict__ g_up, float* __restrict__ Z, float* __restrict__ part) {
+  drone_linearize_generators_block<TABLES, WANT_Z>(P, us, dW, mass, Qsym, A22, W, g_up, Z, part);
+}
+
+// batched (cutloop.hip: rato_scp_batch_run_drone), the form rato_cut_define_drone runs (no tables, no Z): workgroup (b, i) is
+// block b of table row i
+__global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_batch_kernel(rato_drone_params P,
+                                                                                     const rato::BatchProb* __restrict__ tab) {
+  const rato::BatchProb& t = tab[blockIdx.y];
+  drone_linearize_generators_block<false, false>(P, t.us, t.dW, t.mass, t.Qsym, t.A22, nullptr, nullptr, nullptr, t.gpart);
 }
 
 __global__ __launch_bounds__(RATO_BLOCK) void drone_obstacle_kernel(rato_drone_params P,
@@ -1553,6 +1569,25 @@ extern "C" int rato_drone_linearize_generators(const rato_drone_params* p, const
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }
+
+namespace rato {
+int launch_drone_linearize_generators_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!params_ok(p) || !params64_ok(p) || !tab || n < 1 || n > 65535) return RATO_EINVAL;
+  const size_t lds = (size_t)(RATO_BLOCK / RATO_WAVE) * ((size_t)(p->S + 1) * 6 + (RATO_GEN_LDS_REDUCE ? 24 * 65 : 0)) * sizeof(double);
+  if (lds > 160 * 1024) return RATO_EINVAL;
+  static rato::DynamicLdsLimit lds_limit;
+  const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_linearize_generators_batch_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  hipLaunchKernelGGL(drone_linearize_generators_batch_kernel, dim3(rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), lds, st,
+                     *p, tab);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+}  // namespace rato
 
 extern "C" int rato_drone_linearize_plan(int32_t M, int32_t S, int32_t ld, int32_t* cols_per_thread,
                                          int32_t* samples_per_lane, int32_t* tile) {

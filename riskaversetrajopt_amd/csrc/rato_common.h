@@ -246,6 +246,49 @@ class TileQueuePool {
 int launch_cut_finish(const double* part, int nblocks, int ncols, double* rec_dev, double* rec_host, int n_stats,
                       hipStream_t st);
 
+// ---- Batched rounds of the drone's reduced SCP (cutloop.hip: rato_scp_batch_*).  Every problem of a batch shares S, M and
+// the rato_drone_params; a device-resident table of BatchProb says where each problem's inputs and outputs live, and each
+// batched launch runs (sample blocks) x (table rows) workgroups whose body is the single-problem kernel's device code.
+struct BatchProb {
+  const double* uk;                          // [S][3] linearization point (fp64)
+  const float *dW, *mass, *Qsym;             // the problem's samples
+  const double* x;                           // [S][3] oracle query x = u - u_k
+  const float* us;                           // [S][3] controls (fp32) of the define
+  float *A22, *gpart;                        // define scratch; the sample sums' block partials [nblk][6S+6]
+  double* sums_host;                         // pinned [6S+6]: the sample sums
+  const int32_t* slots;                      // [n_keep] kept ring slots (device)
+  int32_t n_keep;
+  uint32_t k;                                // ascending rank of the VaR (stats_rank of alpha, M)
+  int32_t var_is_max;
+  float thr;
+  double alpha, alphaM;
+  const float* m_base;                       // the solver's rings (kept cuts index them by slot)
+  const int32_t* arg_base;
+  const double* res_base;
+  float* m_out;                              // the oracle's ring slot of this round
+  int32_t* arg_out;
+  double *res_dev, *res_host, *part;         // its record (device / pinned) and the tail's block partials
+  double *part_b, *sums_b_host;              // kept cuts: block partials [nblk][n_keep nc], sums (pinned)
+};
+// one row of a batched kept-cuts launch: table row, first cut, cuts in this row, the problem's number of kept cuts
+struct BatchCut {
+  int32_t prob, k0, kn, K;
+};
+// cvar.hip
+int launch_drone_rowmax_rollout_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st);
+int launch_drone_tail_rows_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st);   // K = 1
+bool drone_tail_union_form(int S, int K);    // the kept cuts' form rato_drone_tail_rows_rollout picks for K cuts
+int launch_drone_tail_kept_batch(const rato_drone_params* p, const BatchProb* tab, const BatchCut* rows, int n_rows,
+                                 bool union_form, int kn_max, hipStream_t st);
+// stats.hip
+bool risk_stats_batch_applies(int64_t M);    // the one-workgroup selection is what rato_risk_stats runs for M samples
+int launch_risk_stats_batch(const BatchProb* tab, int n, int64_t M, hipStream_t st);
+int launch_cut_finish_batch(const BatchProb* tab, int n, int nblocks, int ncols, int n_stats, hipStream_t st);
+int launch_define_sums_batch(const BatchProb* tab, int n, int nblocks, int ncols, hipStream_t st);
+int launch_kept_sums_batch(const BatchProb* tab, int n, int nblocks, int nc, int max_keep, hipStream_t st);
+// drone.hip (the generators-only linearization without tables or Z, as rato_cut_define_drone runs it)
+int launch_drone_linearize_generators_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st);
+
 // Read-back of a few doubles that a kernel writes into PINNED, device-visible host memory: the host pre-sets every word
 // to a NaN payload no arithmetic produces (arm) and then watches the words arrive (wait) instead of asking the runtime
 // for the end of the stream -- hipStreamSynchronize / hipEventSynchronize enqueue a completion packet behind the last

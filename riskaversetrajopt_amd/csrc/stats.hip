@@ -65,9 +65,8 @@ __global__ __launch_bounds__(SP_COLS* SP_ROWS) void sum_partials_kernel(const T*
 // partials, written to the record on the device AND straight into the pinned host copy of it, while one more workgroup
 // copies the statistics the selection left in the record -- instead of a reduction launch followed by a device-to-host
 // copy (a copy node costs more than this whole kernel).  Same fixed-order sums as sum_partials_kernel<double>.
-__global__ __launch_bounds__(SP_COLS* SP_ROWS) void cut_finish_kernel(const double* __restrict__ part, int nblocks, int ncols,
-                                                                     double* __restrict__ rec_dev,
-                                                                     double* __restrict__ rec_host, int n_stats) {
+__device__ __forceinline__ void cut_finish_block(const double* __restrict__ part, int nblocks, int ncols,
+                                                 double* __restrict__ rec_dev, double* __restrict__ rec_host, int n_stats) {
   const int col_blocks = (ncols + SP_COLS - 1) / SP_COLS;
   if ((int)blockIdx.x == col_blocks) {
     if ((int)threadIdx.x < n_stats) rec_host[threadIdx.x] = rec_dev[threadIdx.x];
@@ -78,6 +77,33 @@ __global__ __launch_bounds__(SP_COLS* SP_ROWS) void cut_finish_kernel(const doub
   const int cx = threadIdx.x % SP_COLS, ry = threadIdx.x / SP_COLS;
   const int c = blockIdx.x * SP_COLS + cx;
   if (ry == 0 && c < ncols) rec_host[n_stats + c] = rec_dev[n_stats + c];
+}
+__global__ __launch_bounds__(SP_COLS* SP_ROWS) void cut_finish_kernel(const double* __restrict__ part, int nblocks, int ncols,
+                                                                     double* __restrict__ rec_dev,
+                                                                     double* __restrict__ rec_host, int n_stats) {
+  cut_finish_block(part, nblocks, ncols, rec_dev, rec_host, n_stats);
+}
+
+// ---- batched forms (cutloop.hip: rato_scp_batch_run_drone): workgroup (c, i) is workgroup c of table row i's launch
+__global__ __launch_bounds__(SP_COLS* SP_ROWS) void cut_finish_batch_kernel(const rato::BatchProb* __restrict__ tab, int nblocks,
+                                                                           int ncols, int n_stats) {
+  const rato::BatchProb& t = tab[blockIdx.y];
+  cut_finish_block(t.part, nblocks, ncols, t.res_dev, t.res_host, n_stats);
+}
+// the define's sample sums (float partials [nblocks][ncols]) into the pinned sums (rato_sum_partials, scale 1)
+__global__ __launch_bounds__(SP_COLS* SP_ROWS) void define_sums_batch_kernel(const rato::BatchProb* __restrict__ tab, int nblocks,
+                                                                            int ncols) {
+  const rato::BatchProb& t = tab[blockIdx.y];
+  sum_partials_block(blockIdx.x, t.gpart, nblocks, ncols, 1.0, t.sums_host);
+}
+// the kept cuts' sums (double partials [nblocks][n_keep nc]) into the pinned sums_b_host (rato_sum_partials_f64, scale 1);
+// rows with fewer kept cuts leave the surplus workgroups idle (n_keep = 0: no row at all)
+__global__ __launch_bounds__(SP_COLS* SP_ROWS) void kept_sums_batch_kernel(const rato::BatchProb* __restrict__ tab, int nblocks,
+                                                                          int nc) {
+  const rato::BatchProb& t = tab[blockIdx.y];
+  const int ncols = t.n_keep * nc;
+  if ((int)blockIdx.x * SP_COLS >= ncols) return;
+  sum_partials_block(blockIdx.x, t.part_b, nblocks, ncols, 1.0, t.sums_b_host);
 }
 
 // ------------------------------------------------------------ non-finite check
@@ -272,6 +298,15 @@ __global__ __launch_bounds__(RS1_T) void rs_small(const float* __restrict__ Z, l
   rs_small_body<RS1_T>(Z, M, alpha, k, var_is_max, thr, out, nullptr, h, red, redmax);   // rato_select.h (no producer to wait for)
 }
 
+// the oracle's selection of every table row (rs_small's body with the row's own Z, alpha and record)
+__global__ __launch_bounds__(RS1_T) void rs_small_tab(const rato::BatchProb* __restrict__ tab, long M) {
+  __shared__ unsigned h[B1];
+  __shared__ double red[5 * (RS1_T / RATO_WAVE)];
+  __shared__ float redmax[RS1_T / RATO_WAVE];
+  const rato::BatchProb& t = tab[blockIdx.x];
+  rs_small_body<RS1_T>(t.m_out, M, t.alpha, t.k, t.var_is_max, t.thr, t.res_dev, nullptr, h, red, redmax);
+}
+
 // K independent selections in one launch (rato_risk_stats_batch): workgroup k on row k of Z [K][ldz] -> out [K][RATO_N_STATS]
 __global__ __launch_bounds__(RS1_T) void rs_small_batch(const float* __restrict__ Z, long M, long ldz, double alpha, unsigned k,
                                                         int var_is_max, float thr, double* __restrict__ out) {
@@ -374,6 +409,46 @@ extern "C" int rato_sum_partials_f64(const double* part, int32_t nblocks, int32_
 }
 
 namespace rato {
+bool risk_stats_batch_applies(int64_t M) {   // (the conditions under which risk_stats_impl launches rs_small)
+  const char* e = getenv("RATO_RS_PATH");
+  return M > 0 && M <= RS_SMALL_MAX && !(e && (e[0] == 'm' || e[0] == 'c'));
+}
+
+int launch_risk_stats_batch(const BatchProb* tab, int n, int64_t M, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!tab || n < 1 || n > 65535 || !risk_stats_batch_applies(M)) return RATO_EINVAL;
+  hipLaunchKernelGGL(rs_small_tab, dim3((unsigned)n), dim3(RS1_T), 0, st, tab, (long)M);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+int launch_cut_finish_batch(const BatchProb* tab, int n, int nblocks, int ncols, int n_stats, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!tab || n < 1 || n > 65535 || nblocks < 1 || ncols < 0) return RATO_EINVAL;
+  const int col_blocks = ncols > 0 ? (ncols + SP_COLS - 1) / SP_COLS : 0;
+  hipLaunchKernelGGL(cut_finish_batch_kernel, dim3(col_blocks + 1, n), dim3(SP_COLS * SP_ROWS), 0, st, tab, nblocks, ncols, n_stats);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+int launch_define_sums_batch(const BatchProb* tab, int n, int nblocks, int ncols, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!tab || n < 1 || n > 65535 || nblocks < 1 || ncols < 1) return RATO_EINVAL;
+  hipLaunchKernelGGL(define_sums_batch_kernel, dim3((ncols + SP_COLS - 1) / SP_COLS, n), dim3(SP_COLS * SP_ROWS), 0, st, tab,
+                     nblocks, ncols);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+int launch_kept_sums_batch(const BatchProb* tab, int n, int nblocks, int nc, int max_keep, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!tab || n < 1 || n > 65535 || nblocks < 1 || nc < 1 || max_keep < 1) return RATO_EINVAL;
+  hipLaunchKernelGGL(kept_sums_batch_kernel, dim3((max_keep * nc + SP_COLS - 1) / SP_COLS, n), dim3(SP_COLS * SP_ROWS), 0, st, tab,
+                     nblocks, nc);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
 int launch_cut_finish(const double* part, int nblocks, int ncols, double* rec_dev, double* rec_host, int n_stats,
                       hipStream_t st) {
   const int col_blocks = ncols > 0 ? (ncols + SP_COLS - 1) / SP_COLS : 0;

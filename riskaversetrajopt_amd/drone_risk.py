@@ -9,6 +9,7 @@ Host-facing methods return NumPy arrays in the reference's shapes; ``*_device``
 methods return the kernels' SoA tensors (sample index fastest).
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -931,6 +932,20 @@ class Model:
                 "master_s": f("master_s"), "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
                 "status": f("status").astype(np.int64)}
 
+    def _native_loop_solver(self):
+        """the cut solver of the native SCP loop with its table-free oracle attached, or None where that loop does not
+        apply (no materialised dW, sharded, S < 2)"""
+        dW, mass, Qsym, _ = self._inputs(None)
+        if dW is None or getattr(self, "_world", 1) != 1 or self.S < 2:
+            return None
+        cs = self._reduced_cut_solver(int(self._inputs(None)[3]), mass.numel())
+        cs.implicit = None
+        rp = getattr(self, "_rollout_params", None)
+        if rp is None or rp[0] != (cs.M, mass.numel()):
+            rp = self._rollout_params = ((cs.M, mass.numel()), self._params(cs.M, mass.numel()))
+        cs.rollout = ("drone", rp[1], dW, mass, Qsym)
+        return cs
+
     def certify_reduced(self, info):
         """Matrix-free KKT certificate of the last ``solve_reduced`` (its ``info``; an iteration with the CVaR rows,
         before any other solve) against the reference's full QP (drone_risk.py:327-368): certificate.py."""
@@ -974,6 +989,113 @@ class StepGraph:
             self.us.copy_(torch.as_tensor(np.asarray(us_mat), dtype=torch.float32), non_blocking=True)
         self.graph.replay()
         return self.out, self.stats
+
+
+def _check_batch(models):
+    """ValueError unless the Models can share one native batch (rato_scp_batch_run_drone): drone Models of method 'saa' with
+    materialised samples on one GPU, one S, one M and one row stride.  Nothing runs on the device here."""
+    if not models:
+        raise ValueError("an SCP batch needs at least one Model")
+    for k, m in enumerate(models):
+        if not isinstance(m, Model):
+            raise ValueError(f"problem {k}: the SCP batch covers the drone (drone_risk.Model) only, got {type(m).__name__}")
+        if m.method != 'saa':
+            raise ValueError(f"problem {k}: the SCP batch covers method 'saa' only, got {m.method!r}")
+        if getattr(m, "_dW", None) is None or getattr(m, "_world", 1) != 1 or m.S < 2:
+            raise ValueError(f"problem {k}: the SCP batch needs materialised samples on one GPU and S >= 2")
+        if os.environ.get("RATO_PY_CUT_LOOP") == "1":
+            raise ValueError("the SCP batch runs the native cut loop, which RATO_PY_CUT_LOOP=1 switches off")
+    m0 = models[0]
+    for k, m in enumerate(models):
+        if (m.S, m.M, m._mass.numel(), m.dt) != (m0.S, m0.M, m0._mass.numel(), m0.dt):
+            raise ValueError(f"problem {k}: every problem of an SCP batch has the same S and M "
+                             f"(S={m.S}, M={m.M} against S={m0.S}, M={m0.M})")
+        if m.device != m0.device:
+            raise ValueError(f"problem {k}: every problem of an SCP batch is on one device")
+    if len({id(m) for m in models}) != len(models):
+        raise ValueError("a Model appears twice in the SCP batch")
+
+
+def scp_run_native_batch(models, us0, iters, first_cvar=2, tol=1e-9, max_cuts=400, final_cut_above=1e-11, n_threads=16,
+                         check_finite=True):
+    """The reduced SCP of several drone Models in lockstep as ONE library call (rato_scp_batch_run_drone): per SCP iteration
+    one batched define and rounds of one batched oracle round trip for every problem still cutting, the host masters on up
+    to ``n_threads`` threads.  Each Model brings its own cut solver (its samples, alpha, rings and kept cuts) and leaves it as
+    ``scp_run_native`` would; ``us0`` [K][S][3].  ValueError (before any device work) for what the batch does not cover.
+    -> dict(us_hist (K, iters, S, n_u), cuts / t_risk / slack / status / master_s (K, iters), status (K) (RATO_* per
+    problem), done (K), rounds, and the batch-level clocks define_s / oracle_s / master_s / total_s / rounds_per_iter
+    (iters))"""
+    models = list(models)
+    _check_batch(models)
+    K, S = len(models), models[0].S
+    us0 = np.ascontiguousarray(us0, dtype=np.float64)
+    if us0.shape != (K, S, n_u):
+        raise ValueError(f"us0 must be ({K},{S},{n_u}), got {us0.shape}")
+    solvers = []
+    for k, m in enumerate(models):
+        cs = m._native_loop_solver()
+        if cs is None or not cs.native_loop_applies():
+            raise ValueError(f"problem {k}: its cut solver does not take the native loop")
+        solvers.append(cs)
+    lib = models[0]._lib
+    handles = (C.c_void_p * K)(*[cs._native_solver() for cs in solvers])
+    for cs in solvers:
+        cs.check_finite = bool(check_finite)
+    dev_b, host_b = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(lib.rato_scp_batch_bytes(handles, K, C.byref(dev_b), C.byref(host_b)), "rato_scp_batch_bytes")
+    device = models[0].device
+    dev = torch.empty(dev_b.value + 256, dtype=torch.uint8, device=device)
+    dev_ptr = (dev.data_ptr() + 255) // 256 * 256
+    host = torch.zeros(host_b.value + 16, dtype=torch.uint8).pin_memory()
+    host_ptr = (host.data_ptr() + 15) // 16 * 16
+    km = max(solvers[0].keep_max, 1)
+    keep = np.zeros((K, km), dtype=np.int32)
+    idle = np.zeros((K, km), dtype=np.int32)
+    n_keep = np.zeros(K, dtype=np.int32)
+    for k, cs in enumerate(solvers):
+        n_keep[k] = len(cs.keep)
+        keep[k, :len(cs.keep)] = cs.keep
+        idle[k, :len(cs.keep)] = [cs.idle.get(sl, 0) for sl in cs.keep]
+    assert C.sizeof(_lib.ScpIter) == lib.rato_scp_iter_bytes()
+    assert C.sizeof(_lib.ScpBatchIter) == lib.rato_scp_batch_iter_bytes()
+    n_it = max(int(iters), 1)
+    rec = (_lib.ScpIter * (K * n_it))()
+    brec = (_lib.ScpBatchIter * n_it)()
+    us_hist = np.zeros((K, n_it, S, n_u))
+    status = np.zeros(K, dtype=np.int32)
+    done = np.zeros(K, dtype=np.int32)
+    rounds = C.c_int32(0)
+    h = C.c_void_p()
+    _lib.check(lib.rato_scp_batch_create(C.byref(h), handles, K, int(n_threads), dev_ptr, dev_b.value, host_ptr, host_b.value),
+               "rato_scp_batch_create")
+    try:
+        rc = lib.rato_scp_batch_run_drone(
+            h, us0.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
+            int(bool(check_finite)), keep.ctypes.data, idle.ctypes.data, n_keep.ctypes.data, us_hist.ctypes.data,
+            C.addressof(rec), C.addressof(brec), status.ctypes.data, done.ctypes.data, C.addressof(rounds),
+            _lib.current_stream())
+        _lib.synchronize()
+    finally:
+        lib.rato_scp_batch_destroy(h)
+        del dev, host
+    # every solver's Python-side state follows its native one (a later solve_reduced continues from here)
+    for k, cs in enumerate(solvers):
+        Kk = int(n_keep[k])
+        cs.keep = [int(v) for v in keep[k, :Kk]]
+        cs.idle = {int(sl): int(c) for sl, c in zip(keep[k, :Kk], idle[k, :Kk])}
+        cs._relin_pending = None
+        n = int(done[k])
+        if n:
+            cs.u_lin = (us_hist[k, n - 2] if n >= 2 else us0[k]).reshape(-1).copy()   # the last linearization point
+    _lib.check(rc, "rato_scp_batch_run_drone")
+    it = int(iters)
+    f = lambda key: np.array([[getattr(rec[k * n_it + i], key) for i in range(it)] for k in range(K)]).reshape(K, it)
+    g = lambda key: np.array([getattr(brec[i], key) for i in range(it)])
+    return {"us_hist": us_hist[:, :it], "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
+            "iter_status": f("status").astype(np.int64), "master_s_problem": f("master_s"), "status": status.copy(),
+            "done": done.copy(), "rounds": int(rounds.value), "define_s": g("define_s"), "oracle_s": g("oracle_s"),
+            "master_s": g("master_s"), "total_s": g("total_s"), "rounds_per_iter": g("rounds").astype(np.int64),
+            "active": g("active").astype(np.int64)}
 
 
 def L2_error_us(us_mat, us_mat_prev):

@@ -5,6 +5,7 @@ Mirrors the script-level driver of the reference (``drone_risk.py:495-540``,
 from the initial guess, a FIXED number of iterations (no convergence test),
 per-iteration wall-clock of "define" (linearize + assemble) and "solve" (host
 QP) with cumulative times, and the L2 change of the controls."""
+import os
 import time
 
 import numpy as np
@@ -114,6 +115,126 @@ def run_drone_reduced(model, num_scp_iters_max=60, verbose=False, check_finite=T
             "cumulative_s": np.cumsum(define_s + solve_s), "L2_error": np.array(err), "cuts": np.array(cuts),
             "oracle_s": np.array(oracle_s), "us_hist": np.array(hist),
             "loop": "python (one define + one solve call per iteration)"}
+
+
+def _default_threads():
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS") or 16)
+    except ValueError:
+        n = 16
+    return max(1, min(16, n))
+
+
+def _batch_error(k, code):
+    """the exception a solo run raises for RATO status ``code``, naming problem ``k`` of the batch"""
+    from . import _lib, dense_qp
+    if code == _lib.RATO_ENONFINITE:
+        return _lib.RatoNonFiniteError(f"SCP batch, problem {k}: non-finite sample sums / constraint values (RATO_ENONFINITE)")
+    if code == _lib.RATO_EINFEASIBLE:
+        return dense_qp.InfeasibleError(f"SCP batch, problem {k}: master QP infeasible")
+    return _lib.RatoError(f"SCP batch, problem {k}: rato_scp_batch_run_drone status {code}")
+
+
+def run_drone_reduced_batch(models, num_scp_iters_max=60, tol=None, n_threads=None, on_error="raise", check_finite=True):
+    """``run_drone_reduced`` for MANY drone Models at once (the reference's alpha x repeat grid, drone_risk.py:495-539): the
+    SCP iterations run in lockstep in ONE library call (``drone_risk.scp_run_native_batch`` -> rato_scp_batch_run_drone) --
+    per iteration one batched define, then rounds of one batched oracle round trip for every problem still cutting, the
+    host masters of a round on ``n_threads`` threads (default min(16, OMP_NUM_THREADS)).  Every problem's iterates are those
+    of ``run_drone_reduced(model)`` on it alone, bit for bit.  Scope: drone Models of method 'saa' sharing S and M (each
+    with its own samples and alpha); anything else is a ValueError.
+    -> one dict per Model with the keys of run_drone_reduced (us, us_hist, t_risk, cuts, L2_error, loop), where define_s /
+    solve_s / cumulative_s are the BATCH's per-iteration clocks (lockstep has no per-problem clock), plus ``rounds`` (the
+    batched oracle round trips of the whole run).  A problem the native loop hands back (rank-deficient master, a selection
+    that gave up) is re-run alone through run_drone_reduced from the initial guess with a fresh cut solver (cold; tagged in
+    ``loop``).  A problem that fails (non-finite values, infeasible master) leaves the batch while the others finish; then
+    the exception class of the solo path is raised, naming the problem -- or, with on_error="return", its dict is
+    {"status": RATO code, "error": exception, "done": iterations completed}."""
+    from . import _lib, dense_qp, drone_risk
+    if on_error not in ("raise", "return"):
+        raise ValueError(f"on_error must be 'raise' or 'return', got {on_error!r}")
+    models = list(models)
+    drone_risk._check_batch(models)
+    dense_qp.require_native()
+    iters = int(num_scp_iters_max)
+    if iters <= 0:
+        return [run_drone_reduced(m, num_scp_iters_max=iters, check_finite=check_finite, tol=tol) for m in models]
+    for m in models:
+        _finite_guard(m, check_finite)
+    us0 = np.stack([np.asarray(m.initial_guess_us_mat(), dtype=np.float64) for m in models])
+    _sync()
+    r = drone_risk.scp_run_native_batch(models, us0, iters, n_threads=_default_threads() if n_threads is None else int(n_threads),
+                                        check_finite=bool(check_finite), **({} if tol is None else {"tol": tol}))
+    define_s, solve_s = r["define_s"], r["oracle_s"] + r["master_s"]
+    cumulative = np.cumsum(r["total_s"])
+    out, failed = [], []
+    for k, m in enumerate(models):
+        code = int(r["status"][k])
+        if code in (_lib.RATO_ERANK, _lib.RATO_ESELECT):
+            m._cut_solver = None                       # (cold: a fresh cut solver, from the initial guess)
+            d = run_drone_reduced(m, num_scp_iters_max=iters, check_finite=check_finite, native_loop=False, tol=tol)
+            d["loop"] = d["loop"] + " -- handed back by the batch (status %d), re-run alone" % code
+            d["rounds"] = r["rounds"]
+            out.append(d)
+            continue
+        if code != 0:
+            err = _batch_error(k, code)
+            failed.append((k, err))
+            out.append({"status": code, "error": err, "done": int(r["done"][k])})
+            continue
+        hist = r["us_hist"][k]
+        prev = [us0[k]] + list(hist[:-1])
+        err = np.array([L2_error_us(u, p) for u, p in zip(hist, prev)])
+        out.append({"us": hist[-1], "t_risk": float(r["t_risk"][k, -1]), "define_s": define_s, "solve_s": solve_s,
+                    "cumulative_s": cumulative, "L2_error": err, "cuts": r["cuts"][k], "us_hist": hist,
+                    "rounds": r["rounds"], "loop": "native batch (rato_scp_batch_run_drone)"})
+    if failed and on_error == "raise":
+        raise failed[0][1]
+    return out
+
+
+def draw_saa_batches(num_repeats=30, M=50, S=None, seed=0):
+    """The sample batches of the reference's drone experiment in ITS draw order (drone_risk.py:57, :480-490):
+    ``np.random.seed(seed)``, then ``sample_uncertain_parameters('saa', M)`` once per repeat.  Host only (no GPU).
+    -> list of (DWs (M,S,6), masses (M,), obs_Qs (M,n_obs,3,3)), one per repeat."""
+    from . import drone_params as P
+    from .drone_utils import sample_uncertain_parameters
+    S = P.S if S is None else int(S)
+    np.random.seed(seed)
+    return [sample_uncertain_parameters('saa', M=M, S=S, dt=P.T / S) for _ in range(num_repeats)]
+
+
+def drone_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3), num_repeats=30, M=50, S=20, iters=60, seed=0, mc_model=None,
+                         results_dir=None, n_threads=None, device='cuda:0'):
+    """The reference's drone SAA experiment (drone_risk.py:480-539, :697-725) as one call: the sample batches drawn in the
+    reference's order (``draw_saa_batches``), the alpha x repeat grid solved in ONE lockstep batch
+    (``run_drone_reduced_batch``; each alpha reuses the same batches), with ``mc_model`` the Monte-Carlo report per alpha
+    (``monte_carlo_report``), with ``results_dir`` the reference's result files drone_alpha=<alpha>_repeat=<r>.npy (us, then
+    xs: ``save_results``).  -> dict(alphas, results [alpha][repeat] (the run_drone_reduced_batch dicts), us (A, R, S, 3),
+    reports {alpha: report} (with mc_model), rounds, wall_s)"""
+    import time as _time
+    from . import drone_risk
+    batches = draw_saa_batches(num_repeats, M, S, seed)
+    alphas = [float(a) for a in alphas]
+    models = [drone_risk.Model(S, *batches[r], 'saa', a, device=device) for a in alphas for r in range(num_repeats)]
+    _sync()
+    t0 = _time.perf_counter()
+    res = run_drone_reduced_batch(models, num_scp_iters_max=iters, n_threads=n_threads)
+    _sync()
+    wall = _time.perf_counter() - t0
+    grid = [[res[i * num_repeats + r] for r in range(num_repeats)] for i in range(len(alphas))]
+    us = np.stack([np.stack([g["us"] for g in row]) for row in grid])
+    out = {"alphas": alphas, "results": grid, "us": us, "rounds": res[0].get("rounds"), "wall_s": wall, "models": models}
+    if results_dir is not None:
+        os.makedirs(results_dir, exist_ok=True)
+        for i, a in enumerate(alphas):
+            for r in range(num_repeats):
+                m = models[i * num_repeats + r]
+                xs = m.us_to_state_trajectories(us[i, r])
+                xs = xs.cpu().numpy() if hasattr(xs, "cpu") else np.asarray(xs)
+                save_results(os.path.join(results_dir, f"drone_alpha={a}_repeat={r}.npy"), us[i, r], xs)
+    if mc_model is not None:
+        out["reports"] = {a: monte_carlo_report(mc_model, list(us[i]), a) for i, a in enumerate(alphas)}
+    return out
 
 
 def run_driving(model, num_scp_iters_max=15, verbose=False, check_finite=True):
