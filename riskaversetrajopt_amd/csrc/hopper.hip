@@ -195,9 +195,10 @@ int hopper_slip_impl(int32_t M, int32_t C, const float* px, const float* fx, con
   const bool deriv = dh_dfz || dh_dpx || part_hess;
   const int SW = (RATO_BLOCK / RATO_WAVE) >> nw_log2;
   const size_t lds = (size_t)(RATO_BLOCK + (part_hess ? SW * C * hc : 0)) * sizeof(float);
-  // the Hessian sums keep 2 C floats per sample-wave in LDS: C <= 4064 (two sample-waves) / 2032 (four) contacts; the
-  // reference's hopper has 2 S / 3 contacts (hopper.py:306-311).  Beyond the 64 KB default the kernels are raised (per
-  // device) up to the 160 KB of a CU; past that the call is refused instead of failing inside the launch.
+  // the Hessian sums keep HC C floats per sample-wave in LDS behind the 256 of the Z fold: (256 + SW C HC) * 4 bytes
+  // <= 160 KiB, i.e. C <= 20,352 (one sample-wave) / 10,176 (two) contacts with HC = 2 and 13,568 / 6,784 with HC = 3;
+  // the reference's hopper has 2 S / 3 contacts (hopper.py:306-311).  Beyond the 64 KB default the kernels are raised
+  // (per device) up to the 160 KB of a CU; past that the call is refused instead of failing inside the launch.
   if (lds > RATO_HOPPER_LDS_MAX) return RATO_EINVAL;
   static rato::DynamicLdsLimit lds_limit;
   {
