@@ -1307,9 +1307,12 @@ int car_linearize_impl(const rato_car_params* p, const float* us, const float* d
     int grid_x = n_tiles;
     if (dynamic_env && n_tiles > slots)
       queue = g_car_queue_pool.take(st, resolve_car_tile_queues);   // per stream / per captured launch; none left: static form
-    // Two queue workgroups per CU, not the three the LDS allows: same box, alternating (tools/ab_car_slots.sh), 3 -> 2:
+    // At most two queue workgroups per CU even where the LDS allows more (S <= 33).  Measured when the S = 40 layout still
+    // fitted three per CU: same box, alternating (tools/ab_car_slots.sh), 3 -> 2:
     // C5 shard (M = 125,000) 0.1923-0.1938 -> 0.1846-0.1877 ms (noise read), 0.1768-0.1771 -> 0.1728-0.1734 (regenerated);
     // M = 1e6 1.162-1.175 -> 1.158-1.163 / 1.105-1.108 -> 1.102-1.111; one per CU: +17 %.  RATO_CAR_SLOTS_PER_CU overrides.
+    // Today S = 40 takes 16,208 floats (64,832 B) per workgroup: the LDS itself allows two per CU, 512 slots on 256 CUs
+    // (tests/_car_shapes.py restates this rule; tests/test_gpu_driving_shapes.py checks the slot count on the device).
     const int qslots = (slots_env < 1 && per_cu > 2) ? cus * 2 : slots;
     if (queue) {
       grid_x = qslots;
@@ -1318,7 +1321,8 @@ int car_linearize_impl(const rato_car_params* p, const float* us, const float* d
     int split = 1;
     static const int small_split = [] { const char* e = getenv("RATO_CAR_SMALL_SPLIT"); return e ? atoi(e) : -1; }();
     if (!queue && n_tiles < slots) {
-      // C3 (M = 1e4: 157 tiles on 768 slots), same box, alternating, kern_ms: split 1 / 2 / 3 / 4 = 0.0302-0.0307 /
+      // C3 (M = 1e4: 157 tiles; 768 slots when measured, 512 with today's LDS layout: split 2 either way), same box,
+      // alternating, kern_ms: split 1 / 2 / 3 / 4 = 0.0302-0.0307 /
       // 0.0279-0.0282 / 0.0270-0.0271 (one run 0.0411) / 0.0360-0.0361: every part rebuilds the fp64 ego tables and
       // re-stages the noise tile, so two parts per tile is where it stops paying reliably.
       split = small_split >= 1 ? small_split : (slots / n_tiles >= 2 ? 2 : 1);
@@ -1354,7 +1358,8 @@ int car_linearize_impl(const rato_car_params* p, const float* us, const float* d
     if (queue) {
       // the last `tail_tiles` tiles of the queue as `tail_split` parts each (RATO_CAR_TAIL_SPLIT / RATO_CAR_TAIL_TILES).
       // OFF by default: unlike the drone's products output it does not pay here -- C5 shard (M = 125,000, 1954 tiles
-      // on 768 slots), same box, alternating (tools/ab_car_tail.sh), kernel ms: whole tiles 0.1813-0.1816 | halves over
+      // on 768 slots when measured; 512 queue workgroups with today's LDS layout), same box, alternating
+      // (tools/ab_car_tail.sh), kernel ms: whole tiles 0.1813-0.1816 | halves over
       // the last 384 / 768 tiles 0.1817-0.1823 / 0.1844-0.1856 | thirds 0.1904-0.1907 | quarters 0.1994-0.2012.
       static const int tail_split_env = [] { const char* e = getenv("RATO_CAR_TAIL_SPLIT"); return e ? atoi(e) : 1; }();
       static const int tail_tiles_env = [] { const char* e = getenv("RATO_CAR_TAIL_TILES"); return e ? atoi(e) : -1; }();
