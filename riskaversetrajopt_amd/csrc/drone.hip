@@ -1708,7 +1708,10 @@ int drone_linearize_impl(const rato_drone_params* p, const float* us, const floa
           if (want_split > max_split) want_split = max_split;
           if (want_split > 1 && want_tiles > 0) {
             split = want_split;
-            n_whole = n_tiles - (want_tiles < n_tiles - qslots ? want_tiles : n_tiles - qslots);
+            // (RATO_ROWS_QSLOTS above the tile count: no tail at all.  Unclamped, n_tiles - qslots < 0 pushed n_whole past
+            // n_tiles and the unit count below it: S = 90, M = 20,001 with 512 queue workgroups ran 114 of 313 tiles.)
+            const int tail_max = n_tiles > qslots ? n_tiles - qslots : 0;
+            n_whole = n_tiles - (want_tiles < tail_max ? want_tiles : tail_max);
           }
         }
       }

@@ -327,8 +327,8 @@ def test_ragged_last_tile_at_the_C2_size():
     """M = 10,007 (prime; BASELINE C2 is 10,000): ld = 10,008, the last 64-sample tile holds 23 samples.  Samples around
     the tile boundaries against the fp64 oracle on the same device-drawn numbers, exact statistics, run-to-run bitwise."""
     import torch
-    from oracle import drone as od
     from riskaversetrajopt_amd import drone_risk, drone_utils, stats
+    from tests._drone_shapes import oracle_model
     S, M = 50, 10007
     dW, mass, Qsym = drone_utils.sample_uncertain_parameters_device(M, S, seed=5)
     d = drone_risk.Model.from_device(S, dW, mass, Qsym, 'saa', 0.1, M=M)
@@ -337,12 +337,7 @@ def test_ragged_last_tile_at_the_C2_size():
     r = d.linearize_device(us)
     idx = np.array([0, 63, 64, 9983, 9984, 10000, 10006])
     ti = torch.as_tensor(idx, device=dW.device)
-    DWs = np.zeros((len(idx), S, 6))
-    DWs[:, :, 3:6] = dW[:, :, ti].permute(2, 0, 1).double().cpu().numpy()
-    Qs = Qsym[:, :, ti].double().cpu().numpy()
-    Q = np.zeros((len(idx), 3, 3, 3))
-    Q[:, :, 0, 0], Q[:, :, 0, 1], Q[:, :, 1, 1] = Qs[:, 0].T, Qs[:, 1].T, Qs[:, 2].T
-    sub = od.Model(S, DWs, mass[ti].double().cpu().numpy(), Q, 'saa', 0.1)
+    sub = oracle_model(dW[:, :, ti].cpu().numpy(), mass[ti].cpu().numpy(), Qsym[:, :, ti].cpu().numpy())
     _, _, _, gdu_o, gup_o = sub.get_all_constraints_coeffs(us)
     gdu = d.expand_g_obs_du(d.packed_jacobian(r)[..., ti])
     tol.assert_jac_close(gdu, gdu_o, what="g_obs_du (ragged tile)")

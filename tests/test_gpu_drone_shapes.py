@@ -1,0 +1,247 @@
+"""GPU: the drone row kernel (drone_linearize_rows_kernel) at every launch shape.  The launcher deals a batch out as
+split tiles, one static tile per workgroup or a tile queue whose last tiles go out as row-interleaved parts
+(tests/_drone_shapes.py restates the rule); these tests run both sides of each edge against the fp64 oracle on the
+device's own inputs -- the Jacobian or its factors, g_up, Z, single rows of ``part`` and the sample means -- and every
+launch structure and noise source against the one-tile-per-workgroup launch bit for bit.  Every launch writes into
+buffers filled with NaN beforehand, so a unit that was skipped cannot read back right.  The library reads its switches
+once per process: one child process per variant."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import _drone_shapes as ds
+from tests import _tol as tol
+from tests.test_drone_shapes import BASE, CASES, TABLE, VARIANTS, graze
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXACT = [0, 2, 4, 5, 7, 8, 9, 10]          # stats record: var, frac_satisfied, max, counts, rank, t_star
+SUMS = [1, 3, 6]                           # cvar, mean, tail_sum (fp64 sums)
+BUFFERS = ("G", "_W", "_A22", "_g_up", "_Z", "part")
+_ORACLE = {}                               # (S, M, seed) -> full_batch of the last case (products and factored share it)
+
+
+def cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def batch(M, S, seed, noise="tiled"):
+    """device-drawn inputs (rato_drone_sample) and a Model on them; noise: 'tiled' / 'plain' (the [S][3][ld] array,
+    re-tiled once or read as it lies: Model.TILED_NOISE at the call) or 'regen' (Philox in the kernel, no array)"""
+    from riskaversetrajopt_amd import drone_risk, drone_utils
+    dW, mass, Q = drone_utils.sample_uncertain_parameters_device(M, S, seed=seed, want_dW=noise != "regen")
+    if noise == "regen":
+        return drone_risk.Model.from_device(S, None, mass, Q, 'saa', 0.1, M=M, noise_seed=seed), (dW, mass, Q)
+    return drone_risk.Model.from_device(S, dW, mass, Q, 'saa', 0.1, M=M), (dW, mass, Q)
+
+
+def poisoned_step(d, us, factored, out=None, tiled=True):
+    """step_device into buffers of an earlier call (a warm-up call if none are given) filled with NaN in place: G keeps
+    its packed, 2 MiB-aligned layout, and an unwritten word stays NaN"""
+    from riskaversetrajopt_amd import drone_risk
+    kw = dict(factored=factored, want_A22=factored)
+    drone_risk.Model.TILED_NOISE = tiled
+    try:
+        if out is None:
+            out = d.linearize_device(us, **kw)
+        ptrs = {k: out[k].data_ptr() for k in BUFFERS if out.get(k) is not None}
+        for k in ptrs:
+            out[k].fill_(float("nan"))
+        r, rec = d.step_device(us, out=out, **kw)
+    finally:
+        drone_risk.Model.TILED_NOISE = True
+    assert {k: r[k].data_ptr() for k in ptrs} == ptrs and len(ptrs) == (6 if factored else 4)
+    return r, rec
+
+
+def host(*ts):
+    return tuple(t.cpu().numpy() for t in ts)
+
+
+def owned_finite(r, M):
+    """nothing NaN in the words the kernel owns: samples < M of every tile and row"""
+    import torch
+    G = r["G"]
+    nv = M - (G.shape[0] - 1) * ds.TILE
+    ok = bool(torch.isfinite(G[:-1]).all()) and bool(torch.isfinite(G[-1][..., :nv]).all())
+    return ok and all(bool(torch.isfinite(r[k]).all()) for k in ("g_up", "Z", "part", "W", "A22") if r.get(k) is not None)
+
+
+# ---- 1. the slot count on the device -----------------------------------------------------------------------------
+@pytest.mark.parametrize("S", [20, 36, 50, 90])
+def test_stats_in_launch_flips_at_the_slot_count(S):
+    """rato_drone_stats_in_launch(M, S) is 1 while the tiles fit the resident slots (the statistics workgroups fit up
+    to M = 524,288): its flip, found by bisection on the device, is 64 x slots"""
+    from riskaversetrajopt_amd import _lib
+    lib = _lib.load()
+    n = cus()
+    sh = ds.drone_rows_shape(1, S, False, n)
+    lo, hi = 1, 8192                                           # in launch at lo tiles, not at hi tiles
+    assert lib.rato_drone_stats_in_launch(64 * lo, S) == 1 and lib.rato_drone_stats_in_launch(64 * hi, S) == 0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if lib.rato_drone_stats_in_launch(64 * mid, S) == 1 else (lo, mid)
+    assert lo == sh["slots"], (f"S = {S}: the device has {lo} row-kernel slots, tests/_drone_shapes.py says "
+                               f"{sh['slots']} ({n} CUs x {sh['per_cu']}): the shape table moved, the edge tests below "
+                               f"no longer run the shapes they name")
+    assert lib.rato_drone_stats_in_launch(64 * lo + 1, S) == 0
+    assert ds.drone_rows_shape(64 * lo, S, False, n)["stats_in_launch"]
+    assert not ds.drone_rows_shape(64 * lo + 1, S, False, n)["stats_in_launch"]
+    print(f"S = {S}: {lo} slots on {n} CUs ({sh['per_cu']} per CU, {sh['lds_bytes']} B of LDS per workgroup)")
+
+
+# ---- 2. fp64 parity on both sides of each edge ---------------------------------------------------------------------
+@pytest.mark.parametrize("S,M,factored", sorted(TABLE))
+def test_fp64_parity_at_the_shape_edges(S, M, factored):
+    import torch
+    from riskaversetrajopt_amd import _lib
+    sh = ds.drone_rows_shape(M, S, factored, cus())
+    assert (sh["form"], sh["n_tiles"], sh["workgroups"], sh["split"], sh["n_whole"]) == TABLE[(S, M, factored)], sh
+    seed = S + M % 97
+    d, (dW, mass, Q) = batch(M, S, seed)
+    us = graze(S)
+    r, rec = poisoned_step(d, us, factored)
+    _, _, g = d.eval_device(us, want_g=True)
+    torch.cuda.synchronize()
+    assert _lib.load().rato_drone_stats_in_launch(M, S) == int(sh["stats_in_launch"])
+    what = f"S={S} M={M} {'factored' if factored else 'products'} ({sh['form']})"
+    # every lane of the first, middle and last tiles and every 61st sample against the oracle
+    idx = ds.sample_set(M)
+    ti = torch.as_tensor(idx, device=mass.device)
+    out = {"g_up": r["g_up"][:, :, ti].cpu().numpy(), "Z": r["Z"][ti].cpu().numpy()}
+    if factored:
+        out["Phi"] = r["G"][ti // ds.TILE, :, :, ti % ds.TILE].permute(1, 2, 0).cpu().numpy()
+        out["W"], out["A22"] = r["W"][..., ti].cpu().numpy(), r["A22"][..., ti].cpu().numpy()
+    else:
+        out["G"] = r["G"][ti // ds.TILE, :, :, :, ti % ds.TILE].permute(1, 2, 3, 0).cpu().numpy()
+    ref = ds.reference(*host(dW[:, :, ti], mass[ti], Q[:, :, ti]), us, want_A22=factored)
+    ds.check(out, ref, idx, S, what)
+    # the whole batch: Z, single rows of part, the sample means; nothing left unwritten
+    if (S, M, seed) not in _ORACLE:
+        _ORACLE.clear()
+        _ORACLE[(S, M, seed)] = ds.full_batch(*host(dW[:, :, :M], mass[:M], Q[:, :, :M]), us)
+    Z_o, rows = _ORACLE[(S, M, seed)]
+    Zh = r["Z"].double().cpu().numpy()
+    ds.check_Z(Zh, Z_o, what)
+    n = sh["n_tiles"]
+    ds.check_part(r["part"].cpu().numpy(), rows, sorted({t for t in (0, 1, n // 2, n - 2, n - 1) if 0 <= t < n}), what)
+    ds.check_means(r["sums"].cpu().numpy(), rows, what)
+    assert owned_finite(r, M), what
+    # linearity g_up + g = G.u through the packed layout, as test_full_size_C2_properties forms it
+    Gp = d.packed_jacobian(r)
+    u = torch.as_tensor(us, dtype=torch.float32, device=Gp.device)
+    Gu = torch.zeros_like(g)
+    for t in range(1, S):
+        off = t * (t - 1) // 2
+        Gu[:, t, :] = (Gp[off:off + t] * u[:t, :2, None, None]).sum(dim=(0, 1))
+    resid = (r["g_up"] + g - Gu).abs().max().item()
+    del Gp, Gu
+    if S == 50:
+        tol.assert_below(resid, tol.LINEARITY_ABS_DRONE_C2, f"{what} linearity |g_up + g - G.u|")
+    else:       # the limit was measured at S = 50 on these controls: elsewhere the value is reported
+        tol.report(f"{what} linearity |g_up + g - G.u| (limit: the C2 one, not asserted)", resid, tol.LINEARITY_ABS_DRONE_C2)
+        assert np.isfinite(resid), what
+    # the statistics of the same fp32 Z (in the launch up to 64 x slots samples, behind it above)
+    b = rec.cpu().numpy()
+    srt = np.sort(Zh)
+    k = M - int(np.floor(d.alpha * M)) - 1
+    assert b[0] == srt[k] and b[4] == srt[-1], (what, b)
+    cvar = srt[k] + np.maximum(Zh - srt[k], 0).sum() / (d.alpha * M)
+    assert abs(b[1] - cvar) < 1e-9 * max(1.0, abs(cvar)), (what, b[1], cvar)
+
+
+# ---- 3. every launch structure and noise source gives the same bits ------------------------------------------------
+def digests(cases):
+    """{case: digests} of the row kernel's outputs under this process's switches, both outputs x the noise tiled,
+    plain and regenerated: the positional digest of G over the words the kernel owns, sha256 of g_up, Z, W, A22, part
+    and the exact fields of the fused statistics record, the fp64 sums"""
+    import torch
+    res = {}
+    for S, M in cases:
+        us = graze(S) * 0.9 + 0.01
+        for fact in (False, True):
+            out = None
+            for noise in ("tiled", "plain", "regen"):
+                d, _ = batch(M, S, seed=7 + S, noise=noise)
+                r, rec = poisoned_step(d, us, fact, out=out, tiled=noise != "plain")
+                torch.cuda.synchronize()
+                assert owned_finite(r, M), (S, M, fact, noise)
+                small = [r[k] for k in ("g_up", "Z", "W", "A22", "part") if r.get(k) is not None] + [rec[EXACT]]
+                idx = [0, 63, 64, M // 2, M - 1]
+                res[f"S{S}_M{M}_{'factored' if fact else 'products'}_{noise}"] = {
+                    "G": ds.digest_G(r["G"], M), "sha256": ds.sha(*host(*small)),
+                    "sums": rec[SUMS].tolist() + r["sums"].tolist(),
+                    "Z": [float(r["Z"][i]) for i in idx], "g_up": [float(r["g_up"][2, S - 1, i]) for i in idx],
+                    "last_tile": r["part"][-1, :6].tolist()}
+                out = r
+            del out, r, rec
+    return res
+
+
+CHILD = r'''
+import json, sys
+sys.path.insert(0, %(root)r)
+from tests import test_gpu_drone_shapes as T
+json.dump(T.%(fn)s(%(arg)r), open(%(path)r, "w"))
+'''
+
+
+def run_child(tmp_path, name, env, fn, arg, timeout=420):
+    path = str(tmp_path / (name + ".json"))
+    e = {k: v for k, v in os.environ.items()
+         if not k.startswith(("RATO_ROWS_", "RATO_SMALL_SPLIT", "RATO_DYN_TAIL_", "RATO_POISON"))}
+    e.update(env)
+    p = subprocess.run([sys.executable, "-c", CHILD % dict(root=ROOT, fn=fn, arg=arg, path=path)], env=e,
+                       capture_output=True, text=True, timeout=timeout)
+    assert p.returncode == 0, (name, p.returncode, p.stderr[-3000:])
+    with open(path) as f:
+        return json.load(f)
+
+
+def test_launch_structures_and_noise_sources_are_bit_identical(tmp_path):
+    """base: RATO_ROWS_DYNAMIC=0 RATO_SMALL_SPLIT=1, one tile per workgroup at any M.  Every other variant
+    (tests/test_drone_shapes.py pins the forms they make of each case: split 3 / 4, queues of 256 / 300 / 512 / 768 /
+    1024 workgroups, whole tiles only, halves, thirds of the last tile, quarters of every queued tile, more workgroups
+    than tiles) must reproduce it bit for bit in both outputs, with the noise tiled, plain or regenerated."""
+    base = run_child(tmp_path, "base", BASE, "digests", CASES)
+    assert len(base) == len(CASES) * 6
+    for key, v in base.items():
+        ref = base[key.rsplit("_", 1)[0] + "_tiled"]
+        assert (v["G"], v["sha256"]) == (ref["G"], ref["sha256"]), ("noise source", key, v, ref)
+        np.testing.assert_allclose(v["sums"], ref["sums"], rtol=1e-12, atol=1e-300)
+    for name, env in VARIANTS.items():
+        got = run_child(tmp_path, name, env, "digests", CASES)
+        for key in base:
+            assert (got[key]["G"], got[key]["sha256"]) == (base[key]["G"], base[key]["sha256"]), \
+                (name, key, {k: (base[key][k], got[key][k]) for k in ("Z", "g_up", "last_tile")})
+            np.testing.assert_allclose(got[key]["sums"], base[key]["sums"], rtol=1e-12, atol=1e-300)
+
+
+# ---- 4. reuse across calls ---------------------------------------------------------------------------------------
+def test_queue_launches_in_a_row_into_the_same_buffers():
+    """(50, 100003), products, the default queue form: three control sequences one after the other into the same
+    NaN-filled buffers, each equal to a result in fresh buffers bit for bit -- a queue left non-zero by the launch
+    before would show as skipped leading units"""
+    import torch
+    S, M = 50, 100003
+    assert ds.drone_rows_shape(M, S, False, cus())["form"] == "queue"
+    d, _ = batch(M, S, seed=11)
+    out = None
+    for k in range(3):
+        us = graze(S) * (1.0 - 0.1 * k) + 0.02 * k
+        r, rec = poisoned_step(d, us, False, out=out)
+        got = (ds.digest_G(r["G"], M), ds.sha(*host(r["g_up"], r["Z"], r["part"], rec[EXACT])), r["sums"].tolist())
+        assert owned_finite(r, M), k
+        fresh, frec = d.step_device(us, factored=False)
+        assert fresh["G"].data_ptr() != r["G"].data_ptr()
+        want = (ds.digest_G(fresh["G"], M), ds.sha(*host(fresh["g_up"], fresh["Z"], fresh["part"], frec[EXACT])),
+                fresh["sums"].tolist())
+        assert got == want, k
+        assert torch.equal(fresh["G"][-3:, ..., :3], r["G"][-3:, ..., :3])
+        out = r
+        del fresh
