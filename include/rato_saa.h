@@ -94,7 +94,8 @@ extern "C" {
  * params.stats_* -- the statistics of Z in extra workgroups of the row-parallel linearize launch itself)
  * rato_copy_async, rato_stream_synchronize, rato_risk_stats_recover; 12: rato_hopper_slip_hessian,
  * rato_hopper_jacobian_nnz / rato_hopper_emit_jacobian_values -- the hopper's jacrev / Lagrangian Hessian in the reference's
- * layout; rato_scp_run_drone / rato_scp_iter -- the reduced SCP loop as one call).
+ * layout; rato_scp_run_drone / rato_scp_iter -- the reduced SCP loop as one call; rato_car_ego_final_rows, rato_scp_run_car,
+ * rato_scp_batch_run_car -- additions within version 12: the same for the driving problem).
  * The Python binding refuses a library that reports another version. */
 #define RATO_ABI_VERSION 12
 #define RATO_STATS_IN_LAUNCH 1   /* params.stats_flags */
@@ -674,9 +675,28 @@ int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t iters, int
                        float* A22, float* part, double* sums_host, int32_t* keep, int32_t* keep_idle_count,
                        int32_t* n_keep_io, double* us_hist, rato_scp_iter* rec, int32_t* done, void* stream);
 
-/* The reduced SCP of K drone problems in lockstep (the reference's alpha x repeat grid, drone_risk.py:495-539), each problem
- * a rato_cut_solver of its own (samples, alpha, rings, kept cuts) over ONE shared S, M and rato_drone_params (system 0,
- * mode_saa 1, S >= 2, equal keep_max and cap, distinct solvers; RATO_EINVAL otherwise).  Per SCP iteration: one batched
+/* The final-state rows of the ego (driving.py:283-288) on the host, in fp64: the ego carries no noise, so they are sample
+ * independent and the driving problem's "define" needs no device linearization.  us [S][2] (host), goal [4] (the ego's goal
+ * position, speed and heading) -> final_du [4][2S], final_rhs [4] = -(x_S - goal) + final_du . u.  p->ego_init64 and
+ * p->dt64 are the inputs.  Sequential sums in ascending k and libm's sincos, compiled without contraction: a pure function
+ * of its inputs, shared by rato_scp_run_car, rato_scp_batch_run_car and their per-iteration checker. */
+int rato_car_ego_final_rows(const rato_car_params* p, const double* us /* [S][2] */, const double* goal /* [4] */,
+                            double* final_du /* [4][2S] */, double* final_rhs /* [4] */);
+
+/* The reduced SCP of the driving problem as ONE call (driving.py:486-513), modelled on rato_scp_run_drone: `iters` iterations
+ * of [rato_car_ego_final_rows at the current controls -> rato_cut_begin -> rato_cut_solve with the 4 equality rows],
+ * starting from us0 [S][2]; iteration k < first_cvar runs without the CVaR rows (1: driving.py:411-415).  Clocks, records
+ * (us_hist [iters][S][2], rec [iters]), kept cuts and the statuses handed back (RATO_ERANK / RATO_ESELECT; check_finite:
+ * RATO_ENONFINITE for non-finite rows or m values) as for rato_scp_run_drone.  RATO_EINVAL unless the solver's system is 1. */
+int rato_scp_run_car(rato_cut_solver* s, const double* us0, const double* goal, int32_t iters, int32_t first_cvar, double tol,
+                     int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep, int32_t* keep_idle_count,
+                     int32_t* n_keep_io, double* us_hist, rato_scp_iter* rec, int32_t* done, void* stream);
+
+/* The reduced SCP of K problems of ONE system in lockstep (the reference's alpha x repeat grids, drone_risk.py:495-539,
+ * driving.py:467-529), each problem a rato_cut_solver of its own (samples, alpha, rings, kept cuts) over ONE shared S, M
+ * and parameter struct (all of system 0 with equal rato_drone_params, or all of system 1 with equal rato_car_params;
+ * mode_saa 1, S >= 2, equal keep_max and cap, distinct solvers; RATO_EINVAL otherwise).  A drone batch is run by
+ * rato_scp_batch_run_drone, a driving batch by rato_scp_batch_run_car (RATO_EINVAL for the other system's batch).  Per SCP iteration: one batched
  * define for every problem still running, then rounds of one batched oracle round trip for every problem still cutting
  * (a constant number of launches per round whatever K is), the masters of a round on up to n_threads host threads.  Every
  * problem's iterates, cut counts, t_risk and kept cuts are bitwise those of rato_scp_run_drone on its solver alone.
@@ -708,6 +728,13 @@ int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, int32_t iters
                              int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
                              int32_t* keep_idle_count, int32_t* n_keep, double* us_hist, rato_scp_iter* rec,
                              rato_scp_batch_iter* brec, int32_t* status, int32_t* done, int32_t* rounds, void* stream);
+/* The same for a driving batch: us0 [K][S][2], goal [4] as for rato_scp_run_car, first_cvar 1.  Per SCP iteration the final
+ * rows of every problem on the host threads, one copy (u_k, kept slots, kept-cut rows), one kept-cuts launch when any
+ * problem keeps cuts, then the rounds.  Every problem's iterates are bitwise those of rato_scp_run_car on its solver alone. */
+int rato_scp_batch_run_car(rato_scp_batch* b, const double* us0, const double* goal, int32_t iters, int32_t first_cvar,
+                           double tol, int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
+                           int32_t* keep_idle_count, int32_t* n_keep, double* us_hist, rato_scp_iter* rec,
+                           rato_scp_batch_iter* brec, int32_t* status, int32_t* done, int32_t* rounds, void* stream);
 
 /* ------------------------------------------------------------ device sampler */
 

@@ -104,6 +104,11 @@ SIGNATURES = {
     "rato_scp_iter_bytes": (C.c_size_t, []),
     "rato_scp_run_drone": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32] +
                            [C.c_void_p] * 11 + [c_stream]),
+    "rato_car_ego_final_rows": (C.c_int, [C.POINTER(CarParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rato_scp_run_car": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double,
+                                   C.c_int32] + [C.c_void_p] * 6 + [c_stream]),
+    "rato_scp_batch_run_car": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                         C.c_double, C.c_int32] + [C.c_void_p] * 9 + [c_stream]),
     "rato_scp_batch_iter_bytes": (C.c_size_t, []),
     "rato_scp_batch_bytes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "rato_scp_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,

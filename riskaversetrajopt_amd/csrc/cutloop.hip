@@ -94,8 +94,8 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 struct rato_cut_solver {
   rato_cut_config c;
-  rato_drone_params drone;
-  rato_car_params car;
+  rato_drone_params drone = {};
+  rato_car_params car = {};
   int nU = 0, n = 0, nc = 0, nres = 0, nblk = 0;
   std::vector<double> p_diag, q;
   hipEvent_t sums_ready = nullptr;   // rato_cut_define_drone: recorded behind the linearization's sample sums (lazily created)
@@ -660,6 +660,23 @@ extern "C" int rato_cut_solve(rato_cut_solver* s, const double* final_du, const 
 }
 
 
+namespace {
+// the record of one iteration of a native SCP loop: solve = oracle round trips + master, define = the rest of `total`
+void scp_record(rato_scp_iter& r, const rato_cut_result& res, double total) {
+  r.oracle_s = res.oracle_s;
+  r.master_s = res.master_s;
+  r.solve_s = res.oracle_s + res.master_s;
+  r.define_s = total - r.solve_s;
+  r.t_risk = res.t_risk;
+  r.slack = res.slack;
+  r.phi = res.phi;
+  r.cuts = res.cuts;
+  r.status = res.status;
+  r.recycled = res.recycled;
+  r.reserved = 0;
+}
+}  // namespace
+
 // The reduced SCP of the drone as ONE call: `iters` iterations of [rato_cut_define_drone at the current controls -> the
 // equality rows from the sample sums -> rato_cut_solve], the reference's fixed-count protocol (drone_risk.py:519-532,
 // drone_times.py:509-550) with its per-iteration wall clocks taken here.  Each iteration is timed from its first
@@ -717,19 +734,7 @@ extern "C" int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t
       const hipError_t e = hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream));
       if (e != hipSuccess) return RATO_EHIP - (int)e;
     }
-    const double total = seconds_since(t0);
-    rato_scp_iter& r = rec[it];
-    r.oracle_s = res.oracle_s;
-    r.master_s = res.master_s;
-    r.solve_s = res.oracle_s + res.master_s;
-    r.define_s = total - r.solve_s;
-    r.t_risk = res.t_risk;
-    r.slack = res.slack;
-    r.phi = res.phi;
-    r.cuts = res.cuts;
-    r.status = res.status;
-    r.recycled = res.recycled;
-    r.reserved = 0;
+    scp_record(rec[it], res, seconds_since(t0));
     memcpy(us_hist + (size_t)it * nU, sol.data(), sizeof(double) * nU);
     us = sol;
     *done = it + 1;
@@ -739,17 +744,129 @@ extern "C" int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t
 
 extern "C" size_t rato_scp_iter_bytes(void) { return sizeof(rato_scp_iter); }
 
+// The final-state rows of the ego (driving.py:283-288) on the host, in fp64: the ego carries no noise, so x_S[0:4] and its
+// control Jacobian are sample independent -- the car's "define" has no device linearization.  The formulas of
+// driving.Model.ego_final_rows with plain sequential sums in ascending k and libm's sincos (this file is compiled with
+// contraction off): the native SCP loops below and the per-iteration Python loop that checks them call THIS function, so
+// their equality rows agree to the bit; against NumPy's cos / sin / pairwise sums they agree to rounding.
+//   v_k = v_0 + dt sum_{j<k} u_j0,  phi_k alike;   x_S = (x_0 + dt sum_k v_k cos phi_k, y_0 + dt sum_k v_k sin phi_k, v_S, phi_S)
+//   d x_S / d u_t0 = dt^2 sum_{k>t} cos phi_k,  d x_S / d u_t1 = -dt^2 sum_{k>t} v_k sin phi_k  (y alike);  rows 2, 3: dt
+//   final_rhs = -(x_S - goal) + final_du . u
+extern "C" int rato_car_ego_final_rows(const rato_car_params* p, const double* us, const double* goal, double* final_du,
+                                       double* final_rhs) {
+  if (!p || p->S < 1 || !(p->dt64 > 0.0) || !us || !goal || !final_du || !final_rhs) return RATO_EINVAL;
+  const int S = p->S, nU = 2 * S;
+  const double dt = p->dt64;
+  std::vector<double> v(S + 1), cs(S), sn(S), vs(S), vc(S);
+  double cu0 = 0.0, cu1 = 0.0, ph = 0.0;
+  v[0] = p->ego_init64[2] + dt * 0.0;
+  for (int k = 0; k < S; ++k) {
+    ph = p->ego_init64[3] + dt * cu1;        // phi_k
+    sincos(ph, &sn[k], &cs[k]);
+    vc[k] = v[k] * cs[k];
+    vs[k] = v[k] * sn[k];
+    cu0 += us[2 * k + 0];
+    cu1 += us[2 * k + 1];
+    v[k + 1] = p->ego_init64[2] + dt * cu0;
+  }
+  ph = p->ego_init64[3] + dt * cu1;          // phi_S
+  double sx = 0.0, sy = 0.0;
+  for (int k = 0; k < S; ++k) {
+    sx += vc[k];
+    sy += vs[k];
+  }
+  const double xS[4] = {p->ego_init64[0] + dt * sx, p->ego_init64[1] + dt * sy, v[S], ph};
+  std::fill(final_du, final_du + (size_t)4 * nU, 0.0);
+  for (int t = 0; t < S; ++t) {
+    double ac = 0.0, as = 0.0, avs = 0.0, avc = 0.0;
+    for (int k = t + 1; k < S; ++k) {
+      ac += cs[k];
+      as += sn[k];
+      avs += vs[k];
+      avc += vc[k];
+    }
+    final_du[(size_t)0 * nU + 2 * t + 0] = dt * dt * ac;
+    final_du[(size_t)0 * nU + 2 * t + 1] = -dt * dt * avs;
+    final_du[(size_t)1 * nU + 2 * t + 0] = dt * dt * as;
+    final_du[(size_t)1 * nU + 2 * t + 1] = dt * dt * avc;
+    final_du[(size_t)2 * nU + 2 * t + 0] = dt;
+    final_du[(size_t)3 * nU + 2 * t + 1] = dt;
+  }
+  for (int r = 0; r < 4; ++r) {
+    double d = 0.0;
+    for (int i = 0; i < nU; ++i) d += final_du[(size_t)r * nU + i] * us[i];
+    final_rhs[r] = -(xS[r] - goal[r]) + d;
+  }
+  return RATO_OK;
+}
+
+namespace {
+bool all_finite(const double* v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+}  // namespace
+
+// The reduced SCP of the DRIVING problem as ONE call (driving.py:486-513), modelled on rato_scp_run_drone: `iters`
+// iterations of [rato_car_ego_final_rows at the current controls -> rato_cut_begin (u_k in fp64 + the kept cuts against it)
+// -> rato_cut_solve with the 4 equality rows], the same per-iteration clocks and records, the stream synchronised once inside
+// the last iteration's clock.  scp.run_driving_reduced(native_loop=False, final_rows='native') is the per-iteration checker:
+// same iterates bit for bit (tests/test_gpu_scp_car_native.py).
+//   us0 [S][2];  goal [4]: the ego's goal state (position, speed, heading);  first_cvar: 1 (driving.py:411-415);
+//   us_hist [iters][S][2];  rec [iters];  keep / keep_idle_count / n_keep_io: in and out as for rato_cut_solve.
+extern "C" int rato_scp_run_car(rato_cut_solver* s, const double* us0, const double* goal, int32_t iters, int32_t first_cvar,
+                                double tol, int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
+                                int32_t* keep_idle_count, int32_t* n_keep_io, double* us_hist, rato_scp_iter* rec, int32_t* done,
+                                void* stream) {
+  if (!s || s->c.system != 1 || !us0 || !goal || iters < 0 || !keep || !keep_idle_count || !n_keep_io || !us_hist || !rec || !done)
+    return RATO_EINVAL;
+  const int S = s->c.S, nU = s->nU, n_c = 4;
+  std::vector<double> us(us0, us0 + nU), final_du((size_t)n_c * nU), final_rhs(n_c), sol(nU);
+  std::vector<int32_t> cut_slot(s->c.cap + 8);
+  std::vector<double> cut_lambda(s->c.cap + 8);
+  *done = 0;
+  for (int it = 0; it < iters; ++it) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool cvar = it >= first_cvar;
+    const int K = (cvar && s->c.recycle && S >= 2) ? *n_keep_io : 0;
+    int rc = rato_car_ego_final_rows(&s->car, us.data(), goal, final_du.data(), final_rhs.data());
+    if (rc != RATO_OK) return rc;
+    if (check_finite && !(all_finite(final_du.data(), final_du.size()) && all_finite(final_rhs.data(), final_rhs.size())))
+      return RATO_ENONFINITE;
+    if ((rc = rato_cut_begin(s, us.data(), keep, K, stream)) != RATO_OK) return rc;
+    rato_cut_result res = {};
+    res.us = sol.data();
+    res.cut_slot = cut_slot.data();
+    res.cut_lambda = cut_lambda.data();
+    res.cut_capacity = (int)cut_slot.size();
+    rc = rato_cut_solve(s, final_du.data(), final_rhs.data(), n_c, us.data(), cvar ? 1 : 0, tol, max_cuts, final_cut_above,
+                        check_finite, keep, keep_idle_count, n_keep_io, K > 0 ? 1 : 0, &res, stream);
+    if (rc != RATO_OK) return rc;
+    if (it == iters - 1) {   // the protocol's closing synchronisation, once: inside the last iteration's clock
+      const hipError_t e = hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream));
+      if (e != hipSuccess) return RATO_EHIP - (int)e;
+    }
+    scp_record(rec[it], res, seconds_since(t0));
+    memcpy(us_hist + (size_t)it * nU, sol.data(), sizeof(double) * nU);
+    us = sol;
+    *done = it + 1;
+  }
+  return RATO_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
-// The reduced SCP of MANY drone problems in lockstep (the reference's alpha x repeat grid, drone_risk.py:495-539): one
-// problem = one rato_cut_solver (its own samples, alpha, rings and kept cuts) over one shared S, M and rato_drone_params.
-// Per SCP iteration: ONE batched define for every problem still running (controls and u_k up, generators-only
-// linearization, sample sums, the kept cuts' re-linearization, one wait), the masters of all problems on up to n_threads
-// host threads, and then ROUNDS: one batched oracle round trip (rowmax -> exact selection -> tail rows -> cut_finish, one
+// The reduced SCP of MANY problems of one system in lockstep (the reference's alpha x repeat grids, drone_risk.py:495-539,
+// driving.py:467-529): one problem = one rato_cut_solver (its own samples, alpha, rings and kept cuts) over one shared S, M
+// and parameter struct.  Per SCP iteration: ONE batched define for every problem still running (drone: controls and u_k up,
+// generators-only linearization, sample sums, the kept cuts' re-linearization, one wait;  driving: the sample-independent
+// final rows on the host threads, u_k up, the kept cuts' re-linearization, one wait), the masters of all problems on up to
+// n_threads host threads, and then ROUNDS: one batched oracle round trip (rowmax -> exact selection -> tail rows -> cut_finish, one
 // wait) for every problem still cutting, whose records are fed back to their masters in parallel.  A round's launches do
 // not grow with the batch: the table of its problems travels in one copy and every launch indexes it with blockIdx.y.  A
 // problem that leaves its subproblem early waits for the others before the next define.  Each problem runs the statements
-// of rato_scp_run_drone on the workgroup bodies of its single-problem kernels: its iterates are those of a solo run, bit for
-// bit.  A problem that fails leaves the batch (status[p]); the others go on.
+// of rato_scp_run_drone / rato_scp_run_car on the workgroup bodies of its single-problem kernels: its iterates are those of
+// a solo run, bit for bit.  A problem that fails leaves the batch (status[p]); the others go on.
 namespace {
 
 constexpr size_t BATCH_ALIGN = 256;
@@ -823,29 +940,31 @@ class TaskPool {
   bool stop_ = false;
 };
 
-// sizes of a batch of K problems (S, M, ld, keep_max shared)
+// sizes of a batch of K problems (S, M, ld, keep_max shared).  The driving problem (system 1) has no device linearization:
+// its fp32 controls, A22, gpart and sample-sum regions are empty.
 struct BatchLayout {
   size_t d_tab, d_uk, d_us, d_slots, d_rows, d_size;   // define region (table + staged inputs + kept-cut rows)
   size_t r_tab, r_x, r_size;                           // round region (table + x)
   size_t a22, gpart, dev_bytes;                        // device: [define | round | A22 [K][S 3 ld] | gpart [K][nblk][6S+6]]
   size_t h_res, h_sums, h_ksums, host_bytes;           // pinned: [define | round | res [K][nres] | sums | kept sums]
-  BatchLayout(int K, int S, int64_t ld, int nblk, int keep_max, int nc, int nres) {
-    const size_t nU = 3 * (size_t)S, Kz = (size_t)K, km = (size_t)std::max(keep_max, 1);
+  BatchLayout(int system, int K, int S, int64_t ld, int nblk, int keep_max, int nc, int nres) {
+    const size_t nU = (system == 0 ? 3 : 2) * (size_t)S, Kz = (size_t)K, km = (size_t)std::max(keep_max, 1);
+    const size_t lin = system == 0 ? 1 : 0;            // (the drone's define linearizes on the device)
     d_tab = 0;
     d_uk = align_up(Kz * sizeof(rato::BatchProb));
     d_us = d_uk + align_up(Kz * nU * sizeof(double));
-    d_slots = d_us + align_up(Kz * nU * sizeof(float));
+    d_slots = d_us + align_up(lin * Kz * nU * sizeof(float));
     d_rows = d_slots + align_up(Kz * km * sizeof(int32_t));
     d_size = d_rows + align_up(Kz * km * sizeof(rato::BatchCut));
     r_tab = d_size;
     r_x = r_tab + align_up(Kz * sizeof(rato::BatchProb));
     r_size = r_x + align_up(Kz * nU * sizeof(double)) - r_tab;
     a22 = r_tab + r_size;
-    gpart = a22 + align_up(Kz * nU * (size_t)ld * sizeof(float));
-    dev_bytes = gpart + align_up(Kz * (size_t)nblk * (6 * (size_t)S + 6) * sizeof(float));
+    gpart = a22 + align_up(lin * Kz * nU * (size_t)ld * sizeof(float));
+    dev_bytes = gpart + align_up(lin * Kz * (size_t)nblk * (6 * (size_t)S + 6) * sizeof(float));
     h_res = r_tab + r_size;
     h_sums = h_res + align_up(Kz * (size_t)nres * sizeof(double));
-    h_ksums = h_sums + align_up(Kz * (6 * (size_t)S + 6) * sizeof(double));
+    h_ksums = h_sums + align_up(lin * Kz * (6 * (size_t)S + 6) * sizeof(double));
     host_bytes = h_ksums + align_up(Kz * km * (size_t)nc * sizeof(double));
   }
 };
@@ -855,9 +974,10 @@ int batch_check(rato_cut_solver* const* solvers, int32_t K) {
   const rato_cut_solver* s0 = solvers[0];
   for (int32_t p = 0; p < K; ++p) {
     const rato_cut_solver* s = solvers[p];
-    if (!s || s->c.system != 0 || s->c.mode_saa == 0 || s->c.S < 2 || s->c.S != s0->c.S || s->c.M != s0->c.M ||
+    if (!s || s->c.system != s0->c.system || s->c.mode_saa == 0 || s->c.S < 2 || s->c.S != s0->c.S || s->c.M != s0->c.M ||
         s->c.keep_max != s0->c.keep_max || s->c.cap != s0->c.cap || !s->c.part || (s->c.keep_max > 0 && !s->c.part_b) ||
-        memcmp(&s->drone, &s0->drone, sizeof(rato_drone_params)) != 0)
+        (s->c.system == 0 ? memcmp(&s->drone, &s0->drone, sizeof(rato_drone_params))
+                          : memcmp(&s->car, &s0->car, sizeof(rato_car_params))) != 0)
       return RATO_EINVAL;
     for (int32_t q = 0; q < p; ++q)
       if (solvers[q] == s) return RATO_EINVAL;   // (one solver's rings cannot serve two problems)
@@ -865,15 +985,21 @@ int batch_check(rato_cut_solver* const* solvers, int32_t K) {
   return RATO_OK;
 }
 
+BatchLayout batch_layout(const rato_cut_solver* s, int K) {
+  return BatchLayout(s->c.system, K, s->c.S, s->c.system == 0 ? s->drone.ld : s->c.M, s->nblk, s->c.keep_max, s->nc, s->nres);
+}
+
 }  // namespace
 
 struct rato_scp_batch {
   std::vector<rato_cut_solver*> sv;
-  rato_drone_params P;
+  int system = 0;
+  rato_drone_params P;   // system 0
+  rato_car_params C;     // system 1
   int K = 0, S = 0, nU = 0, nc = 0, nres = 0, nblk = 0, keep_max = 0, ncols = 0;
   int64_t M = 0, ld = 0;
   unsigned char *dev = nullptr, *host = nullptr;
-  BatchLayout lay{1, 2, 1, 1, 0, 1, 1};
+  BatchLayout lay{0, 1, 2, 1, 1, 0, 1, 1};
   std::unique_ptr<TaskPool> pool;
 };
 
@@ -882,7 +1008,7 @@ extern "C" int rato_scp_batch_bytes(rato_cut_solver* const* solvers, int32_t K, 
   const int rc = batch_check(solvers, K);
   if (rc != RATO_OK) return rc;
   const rato_cut_solver* s = solvers[0];
-  const BatchLayout lay(K, s->c.S, s->drone.ld, s->nblk, s->c.keep_max, s->nc, s->nres);
+  const BatchLayout lay = batch_layout(s, K);
   *device_bytes = lay.dev_bytes;
   *host_bytes = lay.host_bytes;
   return RATO_OK;
@@ -894,13 +1020,15 @@ extern "C" int rato_scp_batch_create(rato_scp_batch** out, rato_cut_solver* cons
   int rc = batch_check(solvers, K);
   if (rc != RATO_OK) return rc;
   const rato_cut_solver* s = solvers[0];
-  const BatchLayout lay(K, s->c.S, s->drone.ld, s->nblk, s->c.keep_max, s->nc, s->nres);
+  const BatchLayout lay = batch_layout(s, K);
   if (device_bytes < lay.dev_bytes || host_bytes < lay.host_bytes || ((uintptr_t)device_buf % BATCH_ALIGN) != 0 ||
       ((uintptr_t)host_buf % 16) != 0)
     return RATO_EINVAL;
   rato_scp_batch* b = new rato_scp_batch;
   b->sv.assign(solvers, solvers + K);
+  b->system = s->c.system;
   b->P = s->drone;
+  b->C = s->car;
   b->K = K;
   b->S = s->c.S;
   b->nU = s->nU;
@@ -908,9 +1036,9 @@ extern "C" int rato_scp_batch_create(rato_scp_batch** out, rato_cut_solver* cons
   b->nres = s->nres;
   b->nblk = s->nblk;
   b->keep_max = s->c.keep_max;
-  b->ncols = 6 * b->S + 6;
+  b->ncols = b->system == 0 ? 6 * b->S + 6 : 0;   // the define's sample sums (drone only)
   b->M = s->c.M;
-  b->ld = s->drone.ld;
+  b->ld = b->system == 0 ? s->drone.ld : s->c.M;
   b->dev = static_cast<unsigned char*>(device_buf);
   b->host = static_cast<unsigned char*>(host_buf);
   b->lay = lay;
@@ -923,17 +1051,23 @@ extern "C" void rato_scp_batch_destroy(rato_scp_batch* b) { delete b; }
 
 extern "C" size_t rato_scp_batch_iter_bytes(void) { return sizeof(rato_scp_batch_iter); }
 
-extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, int32_t iters, int32_t first_cvar, double tol,
-                                        int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
-                                        int32_t* keep_idle_count, int32_t* n_keep, double* us_hist, rato_scp_iter* rec,
-                                        rato_scp_batch_iter* brec, int32_t* status, int32_t* done, int32_t* rounds,
-                                        void* stream) {
+namespace {
+
+// The lockstep run of both systems.  What differs between them sits behind `car`: the define (the drone linearizes on the
+// device and reads its sample sums back; the car's equality rows come from rato_car_ego_final_rows on the host threads and
+// only u_k and the kept cuts travel) and the two oracle launches of a round.  goal: the car's goal state [4] (drone: unused).
+int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t iters, int32_t first_cvar, double tol,
+              int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep, int32_t* keep_idle_count,
+              int32_t* n_keep, double* us_hist, rato_scp_iter* rec, rato_scp_batch_iter* brec, int32_t* status, int32_t* done,
+              int32_t* rounds, void* stream) {
   if (!b || !us0 || iters < 0 || max_cuts < 0 || !keep || !keep_idle_count || !n_keep || !us_hist || !rec || !brec ||
       !status || !done || !rounds)
     return RATO_EINVAL;
+  const bool car = b->system == 1;
+  if (car && !goal) return RATO_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int K = b->K, S = b->S, nU = b->nU, nc = b->nc, nres = b->nres, ncols = b->ncols, km = std::max(b->keep_max, 1);
-  const int n_c = 6, n_words = RATO_N_STATS + nc;
+  const int n_c = car ? 4 : 6, n_words = RATO_N_STATS + nc;
   const size_t Mz = (size_t)b->M;
   const double Md = (double)b->M, inv_M = 1.0 / Md;
   const BatchLayout& L = b->lay;
@@ -949,9 +1083,14 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
   std::vector<std::vector<int32_t>> cut_slot(K);
   std::vector<std::vector<double>> cut_lambda(K);
   std::vector<int> dpos(K, -1);
+  std::vector<std::vector<double>> car_du(car ? K : 0), car_rhs(car ? K : 0);   // the car's equality rows of the iteration
   for (int p = 0; p < K; ++p) {
     us[p].assign(us0 + (size_t)p * nU, us0 + (size_t)(p + 1) * nU);
     sol[p].resize(nU);
+    if (car) {
+      car_du[p].resize((size_t)n_c * nU);
+      car_rhs[p].resize(n_c);
+    }
     cut_slot[p].resize(b->sv[p]->c.cap + 8);
     cut_lambda[p].resize(b->sv[p]->c.cap + 8);
     status[p] = RATO_OK;
@@ -964,9 +1103,10 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
   auto fill_common = [&](rato::BatchProb& t, int p) {
     const rato_cut_config& c = b->sv[p]->c;
     memset(&t, 0, sizeof(t));
-    t.dW = c.s0;
-    t.mass = c.s1;
-    t.Qsym = c.s2;
+    t.s0 = c.s0;
+    t.s1 = c.s1;
+    t.s2 = c.s2;
+    t.s3 = c.s3;
     t.alpha = c.alpha;
     t.alphaM = c.alphaM;
     t.thr = c.thr;
@@ -992,6 +1132,18 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
       if (status[p] == RATO_OK) act.push_back(p);
     br.active = (int32_t)act.size();
     if (act.empty()) continue;
+    if (car) {   // ---- the car's equality rows at the current controls (as rato_scp_run_car computes them), in parallel
+      b->pool->run((int)act.size(), [&](int i) {
+        const int p = act[i];
+        const int r2 = rato_car_ego_final_rows(&b->C, us[p].data(), goal, car_du[p].data(), car_rhs[p].data());
+        if (r2 != RATO_OK)
+          status[p] = r2;
+        else if (check_finite && !(all_finite(car_du[p].data(), car_du[p].size()) && all_finite(car_rhs[p].data(), n_c)))
+          status[p] = RATO_ENONFINITE;
+      });
+      act.erase(std::remove_if(act.begin(), act.end(), [&](int p) { return status[p] != RATO_OK; }), act.end());
+      if (act.empty()) continue;
+    }
     // ---- define: every active problem's table row, staged inputs and kept-cut rows into the pinned mirror, ONE copy
     rato::BatchProb* tab = reinterpret_cast<rato::BatchProb*>(b->host + L.d_tab);
     double* uk_h = reinterpret_cast<double*>(b->host + L.d_uk);
@@ -1013,24 +1165,24 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
       double* uk = uk_h + (size_t)n * nU;
       float* usf = us_h + (size_t)n * nU;
       int32_t* sl = slots_h + (size_t)n * km;
-      for (int i = 0; i < nU; ++i) {
-        uk[i] = us[p][i];
-        usf[i] = (float)us[p][i];
-      }
+      for (int i = 0; i < nU; ++i) uk[i] = us[p][i];
       for (int k = 0; k < Kp; ++k) sl[k] = kp[k];
       t.uk = reinterpret_cast<const double*>(dev_of(uk));
-      t.us = reinterpret_cast<const float*>(dev_of(usf));
       t.slots = reinterpret_cast<const int32_t*>(dev_of(sl));
       t.n_keep = Kp;
-      t.A22 = reinterpret_cast<float*>(b->dev + L.a22) + (size_t)n * nU * (size_t)b->ld;
-      t.gpart = reinterpret_cast<float*>(b->dev + L.gpart) + (size_t)n * b->nblk * ncols;
-      t.sums_host = sums_host + (size_t)p * ncols;
       t.sums_b_host = ksums_host + (size_t)p * km * nc;
-      if (rato::readback_poll_enabled()) rato::readback_arm(t.sums_host, ncols);
+      if (!car) {   // the linearization's inputs, scratch and sample sums
+        for (int i = 0; i < nU; ++i) usf[i] = (float)us[p][i];
+        t.us = reinterpret_cast<const float*>(dev_of(usf));
+        t.A22 = reinterpret_cast<float*>(b->dev + L.a22) + (size_t)n * nU * (size_t)b->ld;
+        t.gpart = reinterpret_cast<float*>(b->dev + L.gpart) + (size_t)n * b->nblk * ncols;
+        t.sums_host = sums_host + (size_t)p * ncols;
+        if (rato::readback_poll_enabled()) rato::readback_arm(t.sums_host, ncols);
+      }
       if (Kp > 0) {
         if (rato::readback_poll_enabled()) rato::readback_arm(t.sums_b_host, Kp * nc);
         keep_top = std::max(keep_top, Kp);
-        if (rato::drone_tail_union_form(S, Kp)) {
+        if (!car && rato::drone_tail_union_form(S, Kp)) {
           for (int k0 = 0; k0 < Kp; k0 += 16) {   // (TRU_KMAX cuts per row: the single launcher's chunks)
             const int kn = std::min(16, Kp - k0);
             uni.push_back({n, k0, kn, Kp});
@@ -1046,21 +1198,28 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
     if (n == 0) continue;
     for (size_t i = 0; i < plain.size(); ++i) rows_h[i] = plain[i];
     for (size_t i = 0; i < uni.size(); ++i) rows_h[plain.size() + i] = uni[i];
-    hipError_t e = hipMemcpyAsync(b->dev + L.d_tab, b->host + L.d_tab, L.d_size, hipMemcpyHostToDevice, st);
+    // (a car iteration without the CVaR rows has no device work at all: nothing reads its table)
+    hipError_t e = (car && !cvar) ? hipSuccess
+                                  : hipMemcpyAsync(b->dev + L.d_tab, b->host + L.d_tab, L.d_size, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return RATO_EHIP - (int)e;
     const rato::BatchProb* tab_d = reinterpret_cast<const rato::BatchProb*>(b->dev + L.d_tab);
     const rato::BatchCut* rows_d = reinterpret_cast<const rato::BatchCut*>(b->dev + L.d_rows);
-    int rc = rato::launch_drone_linearize_generators_batch(&b->P, tab_d, n, st);
-    if (rc == RATO_OK) rc = rato::launch_define_sums_batch(tab_d, n, b->nblk, ncols, st);
-    if (rc == RATO_OK && !plain.empty())
-      rc = rato::launch_drone_tail_kept_batch(&b->P, tab_d, rows_d, (int)plain.size(), false, 1, st);
-    if (rc == RATO_OK && !uni.empty())
-      rc = rato::launch_drone_tail_kept_batch(&b->P, tab_d, rows_d + plain.size(), (int)uni.size(), true, kn_max, st);
+    int rc = RATO_OK;
+    if (car) {   // (no union form: every kept cut is one row)
+      if (!plain.empty()) rc = rato::launch_car_tail_kept_batch(&b->C, tab_d, rows_d, (int)plain.size(), st);
+    } else {
+      rc = rato::launch_drone_linearize_generators_batch(&b->P, tab_d, n, st);
+      if (rc == RATO_OK) rc = rato::launch_define_sums_batch(tab_d, n, b->nblk, ncols, st);
+      if (rc == RATO_OK && !plain.empty())
+        rc = rato::launch_drone_tail_kept_batch(&b->P, tab_d, rows_d, (int)plain.size(), false, 1, st);
+      if (rc == RATO_OK && !uni.empty())
+        rc = rato::launch_drone_tail_kept_batch(&b->P, tab_d, rows_d + plain.size(), (int)uni.size(), true, kn_max, st);
+    }
     if (rc == RATO_OK && keep_top > 0) rc = rato::launch_kept_sums_batch(tab_d, n, b->nblk, nc, keep_top, st);
     if (rc != RATO_OK) return rc;
     for (int p : act) {
       const rato::BatchProb& t = tab[dpos[p]];
-      e = rato::readback_wait(t.sums_host, ncols, st);
+      e = car ? hipSuccess : rato::readback_wait(t.sums_host, ncols, st);
       if (e == hipSuccess && t.n_keep > 0) e = rato::readback_wait(t.sums_b_host, t.n_keep * nc, st);
       if (e != hipSuccess) return RATO_EHIP - (int)e;
     }
@@ -1070,21 +1229,24 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
     b->pool->run((int)act.size(), [&](int i) {
       const int p = act[i];
       rato_cut_solver* s = b->sv[p];
-      const double* sm = tab[dpos[p]].sums_host;
-      if (check_finite)
-        for (int j = 0; j < ncols; ++j)
-          if (!std::isfinite(sm[j])) {
-            status[p] = RATO_ENONFINITE;
-            return;
-          }
-      // the equality rows (as rato_scp_run_drone builds them)
-      std::vector<double> final_du((size_t)n_c * nU, 0.0), final_rhs(n_c);
-      for (int t = 0; t < S; ++t)
-        for (int a = 0; a < 3; ++a) {
-          final_du[(size_t)a * nU + t * 3 + a] = sm[t * 6 + a] * inv_M;
-          final_du[(size_t)(3 + a) * nU + t * 3 + a] = sm[t * 6 + 3 + a] * inv_M;
+      std::vector<double> drone_du, drone_rhs;
+      if (!car) {
+        const double* sm = tab[dpos[p]].sums_host;
+        if (check_finite && !all_finite(sm, ncols)) {
+          status[p] = RATO_ENONFINITE;
+          return;
         }
-      for (int r = 0; r < n_c; ++r) final_rhs[r] = sm[6 * S + r] / Md;
+        // the equality rows (as rato_scp_run_drone builds them)
+        drone_du.assign((size_t)n_c * nU, 0.0);
+        drone_rhs.resize(n_c);
+        for (int t = 0; t < S; ++t)
+          for (int a = 0; a < 3; ++a) {
+            drone_du[(size_t)a * nU + t * 3 + a] = sm[t * 6 + a] * inv_M;
+            drone_du[(size_t)(3 + a) * nU + t * 3 + a] = sm[t * 6 + 3 + a] * inv_M;
+          }
+        for (int r = 0; r < n_c; ++r) drone_rhs[r] = sm[6 * S + r] / Md;
+      }
+      const std::vector<double>&final_du = car ? car_du[p] : drone_du, &final_rhs = car ? car_rhs[p] : drone_rhs;
       loop[p].reset(new CutLoop);
       CutLoop& lp = *loop[p];
       int r2 = lp.init(s, final_du.data(), final_rhs.data(), n_c, us[p].data(), cvar, tol, max_cuts, final_cut_above,
@@ -1125,7 +1287,8 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
         e = hipMemcpyAsync(b->dev + L.r_x, b->host + L.r_x, (size_t)nq * nU * sizeof(double), hipMemcpyHostToDevice, st);
       if (e != hipSuccess) return RATO_EHIP - (int)e;
       const rato::BatchProb* rtab_d = reinterpret_cast<const rato::BatchProb*>(b->dev + L.r_tab);
-      rc = rato::launch_drone_rowmax_rollout_batch(&b->P, rtab_d, nq, st);
+      rc = car ? rato::launch_car_rowmax_rollout_batch(&b->C, rtab_d, nq, st)
+               : rato::launch_drone_rowmax_rollout_batch(&b->P, rtab_d, nq, st);
       if (rc == RATO_OK) {
         if (select_batched) {
           rc = rato::launch_risk_stats_batch(rtab_d, nq, b->M, st);
@@ -1136,7 +1299,8 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
           }
         }
       }
-      if (rc == RATO_OK) rc = rato::launch_drone_tail_rows_batch(&b->P, rtab_d, nq, st);
+      if (rc == RATO_OK)
+        rc = car ? rato::launch_car_tail_rows_batch(&b->C, rtab_d, nq, st) : rato::launch_drone_tail_rows_batch(&b->P, rtab_d, nq, st);
       if (rc == RATO_OK) rc = rato::launch_cut_finish_batch(rtab_d, nq, b->nblk, nc, RATO_N_STATS, st);
       if (rc != RATO_OK) return rc;
       for (int i = 0; i < nq; ++i) {
@@ -1189,4 +1353,26 @@ extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, in
     br.total_s = seconds_since(t_it);
   }
   return RATO_OK;
+}
+
+}  // namespace
+
+extern "C" int rato_scp_batch_run_drone(rato_scp_batch* b, const double* us0, int32_t iters, int32_t first_cvar, double tol,
+                                        int32_t max_cuts, double final_cut_above, int32_t check_finite, int32_t* keep,
+                                        int32_t* keep_idle_count, int32_t* n_keep, double* us_hist, rato_scp_iter* rec,
+                                        rato_scp_batch_iter* brec, int32_t* status, int32_t* done, int32_t* rounds,
+                                        void* stream) {
+  if (!b || b->system != 0) return RATO_EINVAL;
+  return batch_run(b, us0, nullptr, iters, first_cvar, tol, max_cuts, final_cut_above, check_finite, keep, keep_idle_count, n_keep,
+                   us_hist, rec, brec, status, done, rounds, stream);
+}
+
+extern "C" int rato_scp_batch_run_car(rato_scp_batch* b, const double* us0, const double* goal, int32_t iters,
+                                      int32_t first_cvar, double tol, int32_t max_cuts, double final_cut_above,
+                                      int32_t check_finite, int32_t* keep, int32_t* keep_idle_count, int32_t* n_keep,
+                                      double* us_hist, rato_scp_iter* rec, rato_scp_batch_iter* brec, int32_t* status,
+                                      int32_t* done, int32_t* rounds, void* stream) {
+  if (!b || b->system != 1) return RATO_EINVAL;
+  return batch_run(b, us0, goal, iters, first_cvar, tol, max_cuts, final_cut_above, check_finite, keep, keep_idle_count, n_keep,
+                   us_hist, rec, brec, status, done, rounds, stream);
 }

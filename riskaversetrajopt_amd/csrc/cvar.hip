@@ -593,7 +593,7 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_rowmax_rollout_kernel(
 __global__ __launch_bounds__(RATO_BLOCK) void drone_rowmax_rollout_batch_kernel(rato_drone_params P,
                                                                                 const rato::BatchProb* __restrict__ tab) {
   const rato::BatchProb& t = tab[blockIdx.y];
-  drone_rowmax_rollout_block(P, t.uk, t.dW, t.mass, t.Qsym, t.x, t.m_out, t.arg_out);
+  drone_rowmax_rollout_block(P, t.uk, t.s0, t.s1, t.s2, t.x, t.m_out, t.arg_out);
 }
 
 // maximum of a non-negative int over the wave, in every lane (DPP tree: no LDS crossbar round trips)
@@ -844,7 +844,7 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_batch_kern
                                                                                    long stats_stride, int c_tab) {
   extern __shared__ __attribute__((aligned(16))) unsigned char trr_lds[];
   const rato::BatchProb& t = tab[blockIdx.y];
-  drone_tail_rows_rollout_block(P, t.uk, t.dW, t.mass, t.Qsym, t.m_out, t.arg_out, t.res_dev, stats_stride, nullptr,
+  drone_tail_rows_rollout_block(P, t.uk, t.s0, t.s1, t.s2, t.m_out, t.arg_out, t.res_dev, stats_stride, nullptr,
                                 t.alphaM, t.part, c_tab, 1, 0, trr_lds);
 }
 
@@ -856,7 +856,7 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_tail_rows_rollout_kept_batch
   extern __shared__ __attribute__((aligned(16))) unsigned char trr_lds[];
   const rato::BatchCut r = rows[blockIdx.y];
   const rato::BatchProb& t = tab[r.prob];
-  drone_tail_rows_rollout_block(P, t.uk, t.dW, t.mass, t.Qsym, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
+  drone_tail_rows_rollout_block(P, t.uk, t.s0, t.s1, t.s2, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
                                 t.alphaM, t.part_b, c_tab, r.K, r.k0, trr_lds);
 }
 
@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(TRU_NW* RATO_WAVE) void drone_tail_rows_rollout_uni
   extern __shared__ __attribute__((aligned(16))) unsigned char tru_lds[];
   const rato::BatchCut r = rows[blockIdx.y];
   const rato::BatchProb& t = tab[r.prob];
-  drone_tail_rows_rollout_union_block(P, t.uk, t.dW, t.mass, t.Qsym, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
+  drone_tail_rows_rollout_union_block(P, t.uk, t.s0, t.s1, t.s2, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
                                       r.k0, r.kn, r.K, t.alphaM, t.part_b, tru_lds);
 }
 
@@ -1171,13 +1171,11 @@ __host__ __device__ inline size_t car_rollout_ego_doubles(int S) {   // U (uk | 
 //   F = -w_r n + w_s (v_des - qv_y) (1, 1)                       dF = -w_r H (de_t - dq_t) - w_s dqv_y (1, 1)
 //   q_{t+1} = q_t + dt qv_t,  qv_{t+1} = qv_t + dt F + sqrt(dt) beta dW_t          (same recursion for dq, dqv with dF)
 //   row t = g_t - n_{t+1} . (de_{t+1} - dq_{t+1})
-template <bool BYVAL>
-__global__ __launch_bounds__(RATO_BLOCK) void car_rowmax_rollout_kernel(
-    rato_car_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ x0_ped,
-    const float* __restrict__ w_speed, const float* __restrict__ w_rep, const double* __restrict__ xs_mem,
-    const XArg xv, float* __restrict__ m_out, int* __restrict__ arg_out) {
-  const double* xs = BYVAL ? xv.v : xs_mem;
-  extern __shared__ __attribute__((aligned(16))) unsigned char crr_lds[];
+// the body of one workgroup (samples blockIdx.x * 256 ..): shared by the single-problem kernel and the batched one
+__device__ __forceinline__ void car_rowmax_rollout_block(
+    const rato_car_params& P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ x0_ped,
+    const float* __restrict__ w_speed, const float* __restrict__ w_rep, const double* __restrict__ xs,
+    float* __restrict__ m_out, int* __restrict__ arg_out, unsigned char* crr_lds) {
   const int S = P.S;
   double* U = reinterpret_cast<double*>(crr_lds);
   double* TERM = U + 4 * S;
@@ -1257,17 +1255,34 @@ __global__ __launch_bounds__(RATO_BLOCK) void car_rowmax_rollout_kernel(
   arg_out[m] = best_idx;
 }
 
+template <bool BYVAL>
+__global__ __launch_bounds__(RATO_BLOCK) void car_rowmax_rollout_kernel(
+    rato_car_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ x0_ped,
+    const float* __restrict__ w_speed, const float* __restrict__ w_rep, const double* __restrict__ xs_mem,
+    const XArg xv, float* __restrict__ m_out, int* __restrict__ arg_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char crr_lds[];
+  car_rowmax_rollout_block(P, uk, dW, x0_ped, w_speed, w_rep, BYVAL ? xv.v : xs_mem, m_out, arg_out, crr_lds);
+}
+
+// batched: workgroup (b, i) is block b of table row i (x from device memory)
+__global__ __launch_bounds__(RATO_BLOCK) void car_rowmax_rollout_batch_kernel(rato_car_params P,
+                                                                              const rato::BatchProb* __restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char crr_lds[];
+  const rato::BatchProb& t = tab[blockIdx.y];
+  car_rowmax_rollout_block(P, t.uk, t.s0, t.s1, t.s2, t.s3, t.x, t.m_out, t.arg_out, crr_lds);
+}
+
 // The cut of the rollout form.  The tail samples of the block (compacted, walked by wave 0 in chunks of 64) re-run the
 // pedestrian in fp64 up to their own t*, leaving K_k = dt w_r H_k (3 numbers; ~1e-3, a correction to the identity, kept
 // as floats: 1e-10 of the step Jacobian) in LDS, pick up g and n of their arg-max row on the way, and run the 8-state
 // adjoint from t* down in the reduced form of car_linearize_rows_kernel (eta_e = -eta_q; E = dt (eta_v, eta_phi) IS the
 // Jacobian entry):      E += q . C_k;   qv' = qv + dt q - dt w_s (qv_x + qv_y) e_y;   q += qv K_k;   column k - 1 = E.
-__global__ __launch_bounds__(RATO_BLOCK) void car_tail_rows_rollout_kernel(
-    rato_car_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ x0_ped,
+// one workgroup of cut kk of K (slots[kk], or slot 0 without slots): shared by the single-problem and the batched kernels
+__device__ __forceinline__ void car_tail_rows_rollout_block(
+    const rato_car_params& P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ x0_ped,
     const float* __restrict__ w_speed, const float* __restrict__ w_rep, const float* __restrict__ m_base,
     const int* __restrict__ arg_base, const double* __restrict__ stats_base, long stats_stride,
-    const int* __restrict__ slots, double alphaM, double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char ctr_lds[];
+    const int* __restrict__ slots, double alphaM, double* __restrict__ part, int K, int kk, unsigned char* ctr_lds) {
   const int S = P.S;
   const long M = P.M;
   const int nw = 2 * (S - 1), nc = nw + 1;
@@ -1278,7 +1293,6 @@ __global__ __launch_bounds__(RATO_BLOCK) void car_tail_rows_rollout_kernel(
   double* acc = C + (size_t)(S + 1) * 4;                              // [nc] column sums of the block
   float* KT = reinterpret_cast<float*>(acc + nc);                     // [S][3][64] K of the current chunk
   car_ego64_tables<false>(P, uk, nullptr, U, TERM, EGO, C);
-  const int K = gridDim.y, kk = blockIdx.y;
   const long slot = slots ? slots[kk] : 0;
   const float* __restrict__ mvals = m_base + slot * M;
   const int* __restrict__ arg = arg_base + slot * M;
@@ -1401,6 +1415,37 @@ __global__ __launch_bounds__(RATO_BLOCK) void car_tail_rows_rollout_kernel(
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nc; i += RATO_BLOCK) part[((size_t)blockIdx.x * K + kk) * nc + i] = acc[i];
+}
+
+__global__ __launch_bounds__(RATO_BLOCK) void car_tail_rows_rollout_kernel(
+    rato_car_params P, const double* __restrict__ uk, const float* __restrict__ dW, const float* __restrict__ x0_ped,
+    const float* __restrict__ w_speed, const float* __restrict__ w_rep, const float* __restrict__ m_base,
+    const int* __restrict__ arg_base, const double* __restrict__ stats_base, long stats_stride,
+    const int* __restrict__ slots, double alphaM, double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ctr_lds[];
+  car_tail_rows_rollout_block(P, uk, dW, x0_ped, w_speed, w_rep, m_base, arg_base, stats_base, stats_stride, slots, alphaM,
+                              part, gridDim.y, blockIdx.y, ctr_lds);
+}
+
+// batched, one cut per problem (the oracle round trip: the cut in ring slot m_out / arg_out / res_dev): workgroup (b, i)
+// is block b of table row i
+__global__ __launch_bounds__(RATO_BLOCK) void car_tail_rows_rollout_batch_kernel(rato_car_params P,
+                                                                                 const rato::BatchProb* __restrict__ tab,
+                                                                                 long stats_stride) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ctr_lds[];
+  const rato::BatchProb& t = tab[blockIdx.y];
+  car_tail_rows_rollout_block(P, t.uk, t.s0, t.s1, t.s2, t.s3, t.m_out, t.arg_out, t.res_dev, stats_stride, nullptr, t.alphaM,
+                              t.part, 1, 0, ctr_lds);
+}
+
+// batched kept cuts, one cut per row (the car has no union form): row j = cut rows[j].k0 of the problem's rows[j].K kept cuts
+__global__ __launch_bounds__(RATO_BLOCK) void car_tail_rows_rollout_kept_batch_kernel(
+    rato_car_params P, const rato::BatchProb* __restrict__ tab, const rato::BatchCut* __restrict__ rows, long stats_stride) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ctr_lds[];
+  const rato::BatchCut r = rows[blockIdx.y];
+  const rato::BatchProb& t = tab[r.prob];
+  car_tail_rows_rollout_block(P, t.uk, t.s0, t.s1, t.s2, t.s3, t.m_base, t.arg_base, t.res_base, stats_stride, t.slots,
+                              t.alphaM, t.part_b, r.K, r.k0, ctr_lds);
 }
 
 
@@ -1713,6 +1758,10 @@ namespace {
 bool car_params64_ok(const rato_car_params* p) {
   return p && p->M > 0 && p->S >= 1 && p->S <= 1024 && p->dt64 > 0.0 && p->d_min64 >= 0.0;
 }
+// dynamic LDS of the car's tail-rows kernels: the ego tables, the block's column sums, K of the current chunk
+size_t car_tail_rows_lds(int S) {
+  return (car_rollout_ego_doubles(S) + (size_t)(2 * (S - 1) + 1)) * sizeof(double) + (size_t)S * 3 * RATO_WAVE * sizeof(float);
+}
 }  // namespace
 
 namespace {
@@ -1756,8 +1805,7 @@ extern "C" int rato_car_tail_rows_rollout(const rato_car_params* p, const double
   if (!car_params64_ok(p) || p->S < 2 || !uk || !dW || !x0_ped || !w_speed || !w_rep || !m_base || !arg_base ||
       !stats_base || !part || K < 1 || K > 65535 || (!slots && K != 1) || stats_stride < 11)
     return RATO_EINVAL;
-  const size_t lds = (car_rollout_ego_doubles(p->S) + (size_t)(2 * (p->S - 1) + 1)) * sizeof(double) +
-                     (size_t)p->S * 3 * RATO_WAVE * sizeof(float);
+  const size_t lds = car_tail_rows_lds(p->S);
   static rato::DynamicLdsLimit limit;
   if (lds + 4096 > 160 * 1024) return RATO_EINVAL;
   {
@@ -1773,6 +1821,58 @@ extern "C" int rato_car_tail_rows_rollout(const rato_car_params* p, const double
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }
+
+// ---- batched forms (cutloop.hip: rato_scp_batch_run_car): the two launches above over (sample blocks) x (table rows), the
+// same workgroup bodies and the same dynamic LDS
+namespace rato {
+int launch_car_rowmax_rollout_batch(const rato_car_params* p, const BatchProb* tab, int n, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!car_params64_ok(p) || !tab || n < 1 || n > 65535) return RATO_EINVAL;
+  const size_t lds = car_rollout_ego_doubles(p->S) * sizeof(double);
+  if (lds > 64 * 1024) return RATO_EINVAL;
+  hipLaunchKernelGGL(car_rowmax_rollout_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), lds,
+                     st, *p, tab);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+int launch_car_tail_rows_batch(const rato_car_params* p, const BatchProb* tab, int n, hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!car_params64_ok(p) || p->S < 2 || !tab || n < 1 || n > 65535) return RATO_EINVAL;
+  const size_t lds = car_tail_rows_lds(p->S);
+  if (lds + 4096 > 160 * 1024) return RATO_EINVAL;   // (4 KB: the static lists of the tail compaction)
+  static rato::DynamicLdsLimit limit;
+  const hipError_t e = limit.ensure(lds + 4096, [](size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(car_tail_rows_rollout_batch_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
+  hipLaunchKernelGGL(car_tail_rows_rollout_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK),
+                     lds, st, *p, tab, stride);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+int launch_car_tail_kept_batch(const rato_car_params* p, const BatchProb* tab, const BatchCut* rows, int n_rows,
+                               hipStream_t st) {
+  RATO_CLEAR_ERROR();
+  if (!car_params64_ok(p) || p->S < 2 || !tab || !rows || n_rows < 1 || n_rows > 65535) return RATO_EINVAL;
+  const size_t lds = car_tail_rows_lds(p->S);
+  if (lds + 4096 > 160 * 1024) return RATO_EINVAL;
+  static rato::DynamicLdsLimit limit;
+  const hipError_t e = limit.ensure(lds + 4096, [](size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(car_tail_rows_rollout_kept_batch_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
+  hipLaunchKernelGGL(car_tail_rows_rollout_kept_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n_rows),
+                     dim3(RATO_BLOCK), lds, st, *p, tab, rows, stride);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+}  // namespace rato
 
 // One oracle round trip of the cutting-plane loop in ONE call: upload x = u - u_k, m(u) by the table-free rowmax, exact
 // tail selection, the cut's sums, read-back, stream synchronisation.  The same five stream-ordered steps the Python

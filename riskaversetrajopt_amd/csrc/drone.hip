@@ -554,7 +554,7 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_kernel(
 __global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_batch_kernel(rato_drone_params P,
                                                                                      const rato::BatchProb* __restrict__ tab) {
   const rato::BatchProb& t = tab[blockIdx.y];
-  drone_linearize_generators_block<false, false>(P, t.us, t.dW, t.mass, t.Qsym, t.A22, nullptr, nullptr, nullptr, t.gpart);
+  drone_linearize_generators_block<false, false>(P, t.us, t.s0, t.s1, t.s2, t.A22, nullptr, nullptr, nullptr, t.gpart);
 }
 
 __global__ __launch_bounds__(RATO_BLOCK) void drone_obstacle_kernel(rato_drone_params P,

@@ -246,13 +246,16 @@ class TileQueuePool {
 int launch_cut_finish(const double* part, int nblocks, int ncols, double* rec_dev, double* rec_host, int n_stats,
                       hipStream_t st);
 
-// ---- Batched rounds of the drone's reduced SCP (cutloop.hip: rato_scp_batch_*).  Every problem of a batch shares S, M and
-// the rato_drone_params; a device-resident table of BatchProb says where each problem's inputs and outputs live, and each
-// batched launch runs (sample blocks) x (table rows) workgroups whose body is the single-problem kernel's device code.
+// ---- Batched rounds of the reduced SCP (cutloop.hip: rato_scp_batch_*), drone or driving.  Every problem of a batch shares
+// S, M and the system's parameter struct; a device-resident table of BatchProb says where each problem's inputs and outputs
+// live, and each batched launch runs (sample blocks) x (table rows) workgroups whose body is the single-problem kernel's
+// device code.  n_u = 3 (drone) / 2 (driving).
 struct BatchProb {
-  const double* uk;                          // [S][3] linearization point (fp64)
-  const float *dW, *mass, *Qsym;             // the problem's samples
-  const double* x;                           // [S][3] oracle query x = u - u_k
+  const double* uk;                          // [S][n_u] linearization point (fp64)
+  const float *s0, *s1, *s2, *s3;            // the problem's samples, as rato_cut_config names them: drone dW, mass, Qsym
+                                             // (s3 unused); driving dW, x0_ped, w_speed, w_rep
+  const double* x;                           // [S][n_u] oracle query x = u - u_k
+  // drone only (its define linearizes on the device; the car's equality rows are sample independent and come from the host)
   const float* us;                           // [S][3] controls (fp32) of the define
   float *A22, *gpart;                        // define scratch; the sample sums' block partials [nblk][6S+6]
   double* sums_host;                         // pinned [6S+6]: the sample sums
@@ -280,6 +283,10 @@ int launch_drone_tail_rows_batch(const rato_drone_params* p, const BatchProb* ta
 bool drone_tail_union_form(int S, int K);    // the kept cuts' form rato_drone_tail_rows_rollout picks for K cuts
 int launch_drone_tail_kept_batch(const rato_drone_params* p, const BatchProb* tab, const BatchCut* rows, int n_rows,
                                  bool union_form, int kn_max, hipStream_t st);
+int launch_car_rowmax_rollout_batch(const rato_car_params* p, const BatchProb* tab, int n, hipStream_t st);
+int launch_car_tail_rows_batch(const rato_car_params* p, const BatchProb* tab, int n, hipStream_t st);       // K = 1
+int launch_car_tail_kept_batch(const rato_car_params* p, const BatchProb* tab, const BatchCut* rows, int n_rows,
+                               hipStream_t st);                                                             // one cut per row
 // stats.hip
 bool risk_stats_batch_applies(int64_t M);    // the one-workgroup selection is what rato_risk_stats runs for M samples
 int launch_risk_stats_batch(const BatchProb* tab, int n, int64_t M, hipStream_t st);

@@ -677,3 +677,70 @@ class CvarCutSolver:
         info.update(us=u_vec.reshape(self.S, self.n_u).copy(), slack=float(s), t_risk=t_risk,
                     cuts=n_cuts, phi=float(phi), status=status, loop="python")
         return info
+
+
+def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, check_finite=True):
+    """The lockstep batch of reduced SCPs behind ``drone_risk.scp_run_native_batch`` / ``driving.scp_run_native_batch``:
+    binds the solvers' native handles to one rato_scp_batch (its device and pinned buffers live for this call), runs it and
+    lets every solver's Python-side state follow its native one (a later solve_reduced continues from there).
+    ``run(handle, keep, idle, n_keep, us_hist, rec, brec, status, done, rounds, stream)`` -> status: the system's
+    rato_scp_batch_run_* with its own leading arguments bound; ``what``: its name, for error messages.
+    -> dict(us_hist (K, iters, S, n_u), cuts / t_risk / slack / iter_status / master_s_problem (K, iters), status (K) (RATO_*
+    per problem), done (K), rounds, and the batch-level clocks define_s / oracle_s / master_s / total_s / rounds_per_iter
+    (iters))"""
+    C = _lib.C
+    K, S, n_u = us0.shape
+    handles = (C.c_void_p * K)(*[cs._native_solver() for cs in solvers])
+    for cs in solvers:
+        cs.check_finite = bool(check_finite)
+    dev_b, host_b = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(lib.rato_scp_batch_bytes(handles, K, C.byref(dev_b), C.byref(host_b)), "rato_scp_batch_bytes")
+    dev = torch.empty(dev_b.value + 256, dtype=torch.uint8, device=device)
+    dev_ptr = (dev.data_ptr() + 255) // 256 * 256
+    host = torch.zeros(host_b.value + 16, dtype=torch.uint8).pin_memory()
+    host_ptr = (host.data_ptr() + 15) // 16 * 16
+    km = max(solvers[0].keep_max, 1)
+    keep = np.zeros((K, km), dtype=np.int32)
+    idle = np.zeros((K, km), dtype=np.int32)
+    n_keep = np.zeros(K, dtype=np.int32)
+    for k, cs in enumerate(solvers):
+        n_keep[k] = len(cs.keep)
+        keep[k, :len(cs.keep)] = cs.keep
+        idle[k, :len(cs.keep)] = [cs.idle.get(sl, 0) for sl in cs.keep]
+    assert C.sizeof(_lib.ScpIter) == lib.rato_scp_iter_bytes()
+    assert C.sizeof(_lib.ScpBatchIter) == lib.rato_scp_batch_iter_bytes()
+    n_it = max(int(iters), 1)
+    rec = (_lib.ScpIter * (K * n_it))()
+    brec = (_lib.ScpBatchIter * n_it)()
+    us_hist = np.zeros((K, n_it, S, n_u))
+    status = np.zeros(K, dtype=np.int32)
+    done = np.zeros(K, dtype=np.int32)
+    rounds = C.c_int32(0)
+    h = C.c_void_p()
+    _lib.check(lib.rato_scp_batch_create(C.byref(h), handles, K, int(n_threads), dev_ptr, dev_b.value, host_ptr, host_b.value),
+               "rato_scp_batch_create")
+    try:
+        rc = run(h, keep.ctypes.data, idle.ctypes.data, n_keep.ctypes.data, us_hist.ctypes.data, C.addressof(rec),
+                 C.addressof(brec), status.ctypes.data, done.ctypes.data, C.addressof(rounds), _lib.current_stream())
+        _lib.synchronize()
+    finally:
+        lib.rato_scp_batch_destroy(h)
+        del dev, host
+    # every solver's Python-side state follows its native one (a later solve_reduced continues from here)
+    for k, cs in enumerate(solvers):
+        Kk = int(n_keep[k])
+        cs.keep = [int(v) for v in keep[k, :Kk]]
+        cs.idle = {int(sl): int(c) for sl, c in zip(keep[k, :Kk], idle[k, :Kk])}
+        cs._relin_pending = None
+        n = int(done[k])
+        if n:
+            cs.u_lin = (us_hist[k, n - 2] if n >= 2 else us0[k]).reshape(-1).copy()   # the last linearization point
+    _lib.check(rc, what)
+    it = int(iters)
+    f = lambda key: np.array([[getattr(rec[k * n_it + i], key) for i in range(it)] for k in range(K)]).reshape(K, it)
+    g = lambda key: np.array([getattr(brec[i], key) for i in range(it)])
+    return {"us_hist": us_hist[:, :it], "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
+            "iter_status": f("status").astype(np.int64), "master_s_problem": f("master_s"), "status": status.copy(),
+            "done": done.copy(), "rounds": int(rounds.value), "define_s": g("define_s"), "oracle_s": g("oracle_s"),
+            "master_s": g("master_s"), "total_s": g("total_s"), "rounds_per_iter": g("rounds").astype(np.int64),
+            "active": g("active").astype(np.int64)}

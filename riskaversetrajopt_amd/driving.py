@@ -6,6 +6,7 @@ with its sample-axis hot path on the MI355X.
 reference fixes S as a module constant; here it is a keyword (default 20).
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -75,6 +76,12 @@ def to_soa_inputs(states_init, omegas_speed, omegas_repulsive, DWs, device):
 
 
 class Model:
+    # scp.run_drone_reduced takes the native SCP loop by default only where a Model says so: the driving loop's native form
+    # (rato_scp_run_car) computes its final rows natively, to rounding the NumPy ones -- it is asked for explicitly
+    # (scp.run_driving_reduced(native_loop=True)), so that the default results stay what they were to the bit
+    SCP_NATIVE_LOOP_DEFAULT = False
+    SCP_NATIVE_ENTRY = "rato_scp_run_car"
+
     def __init__(self, M, method='saa', alpha=0.05, S=P.S, device='cuda:0', rng=None,
                  samples=None, verbose=False, check_finite=False):
         self.check_finite = check_finite        # scan every linearization for NaN/Inf -> RatoNonFiniteError (scp.py)
@@ -561,7 +568,33 @@ class Model:
         goal = np.concatenate((P.position_ego_goal, P.velocity_ego_goal)).astype(np.float64)
         return E, -(xS - goal) + E @ us.reshape(-1)
 
-    def solve_reduced(self, us_mat_p, scp_iter=1, tol=1e-9, verbose=False, delta=True, rollout=None):
+    def _goal64(self):
+        return np.ascontiguousarray(np.concatenate((P.position_ego_goal, P.velocity_ego_goal)), dtype=np.float64)
+
+    def ego_final_rows_native(self, us_mat):
+        """``ego_final_rows`` by the library (rato_car_ego_final_rows: the same formulas with sequential sums and libm's
+        sincos) -- what the native SCP loops compute per iteration; agrees with the NumPy rows to rounding, not to the bit."""
+        S = self.S
+        us = np.ascontiguousarray(us_mat, dtype=np.float64).reshape(S, n_u)
+        goal = self._goal64()
+        final_du, final_rhs = np.zeros((4, n_u * S)), np.zeros(4)
+        p = self._params(self.M)
+        _lib.check(self._lib.rato_car_ego_final_rows(C.byref(p), us.ctypes.data, goal.ctypes.data, final_du.ctypes.data,
+                                                     final_rhs.ctypes.data), "rato_car_ego_final_rows")
+        return final_du, final_rhs
+
+    def _reduced_cut_solver(self, M):
+        cs = getattr(self, "_cut_solver", None)
+        if cs is None:
+            cs = cvar_cuts.CvarCutSolver(self._lib, self.device, n_u=n_u, S=self.S, M=M, ld=M, R=1, alpha=self.alpha,
+                                         dt=self.dt, Rcost=P.R, slack_penalty=self.SLACK_PENALTY,
+                                         u_min=self.u_min, u_max=self.u_max,
+                                         group=getattr(self, "_group", None), world=getattr(self, "_world", 1),
+                                         mode=self.method, rhs0=0.0)
+            self._cut_solver = cs
+        return cs
+
+    def solve_reduced(self, us_mat_p, scp_iter=1, tol=1e-9, verbose=False, delta=True, rollout=None, final_rows='numpy'):
         """One SCP iteration without the O(M) QP (see cvar_cuts.py / drone_risk.Model.solve_reduced).
         scp_iter < 1 zeroes every separation row (driving.py:411-415), i.e. no CVaR constraint.
         ``method='baseline'`` (driving.py:320-329): the rows (G_i u)_t <= g_up_{i,t} of every sample as the one
@@ -571,26 +604,24 @@ class Model:
         ``rollout`` (default: on with the delta form and a materialised dW): NO Jacobian is formed at all.  The cut
         oracle re-runs the rollout at ``us_mat_p`` in fp64 from the samples (rato_car_rowmax_rollout /
         rato_car_tail_rows_rollout: 344 bytes per sample at S = 40 instead of the 6240 of the packed Jacobian) and the
-        sample-independent final rows come from ``ego_final_rows``."""
+        sample-independent final rows come from ``ego_final_rows`` -- or, ``final_rows='native'`` (rollout form only), from
+        ``ego_final_rows_native``: the per-iteration checker of the native SCP loop (``scp_run_native``)."""
+        if final_rows not in ('numpy', 'native'):
+            raise ValueError(f"final_rows must be 'numpy' or 'native', got {final_rows!r}")
         dW, x0, ws, wr = self._dW, self._x0, self._ws, self._wr
         if rollout is None:
             rollout = bool(delta and dW is not None and self.S >= 2)
         if rollout and not (delta and dW is not None):
             raise ValueError("the rollout form of the oracle needs delta=True and a materialised dW")
+        if final_rows == 'native' and not rollout:
+            raise ValueError("final_rows='native' belongs to the rollout form of the oracle")
         M, S = int(ws.numel()), self.S
-        cs = getattr(self, "_cut_solver", None)
-        if cs is None:
-            cs = cvar_cuts.CvarCutSolver(self._lib, self.device, n_u=n_u, S=S, M=M, ld=M, R=1, alpha=self.alpha,
-                                         dt=self.dt, Rcost=P.R, slack_penalty=self.SLACK_PENALTY,
-                                         u_min=self.u_min, u_max=self.u_max,
-                                         group=getattr(self, "_group", None), world=getattr(self, "_world", 1),
-                                         mode=self.method, rhs0=0.0)
-            self._cut_solver = cs
+        cs = self._reduced_cut_solver(M)
         u_lin = np.asarray(us_mat_p, dtype=np.float64) if delta else None
         if rollout:
             cs.rollout = ("driving", self._params(M), dW, x0, ws, wr)
             cs.check_finite = self.check_finite          # (no linearization to scan: the oracle's statistics are checked)
-            final_du, final_rhs = self.ego_final_rows(us_mat_p)
+            final_du, final_rhs = (self.ego_final_rows_native if final_rows == 'native' else self.ego_final_rows)(us_mat_p)
             if self.check_finite and not (np.isfinite(final_du).all() and np.isfinite(final_rhs).all()):
                 raise _lib.RatoNonFiniteError("driving final rows: non-finite values (RATO_ENONFINITE)")
             # unconditionally: the upload of u_k to the device happens only while cs.rollout is set, so a table-form call
@@ -610,6 +641,64 @@ class Model:
                         r["final_rhs"].double().cpu().numpy(), u_lin=u_lin,
                         with_cvar=(scp_iter >= 1), tol=tol, verbose=verbose)
         return info["us"], info["t_risk"], info
+
+    def _native_loop_solver(self):
+        """the cut solver of the native SCP loop with its table-free oracle attached, or None where that loop does not
+        apply (no materialised dW, sharded, S < 2)"""
+        dW, x0, ws, wr = self._dW, self._x0, self._ws, self._wr
+        if dW is None or getattr(self, "_world", 1) != 1 or self.S < 2:
+            return None
+        M = int(ws.numel())
+        cs = self._reduced_cut_solver(M)
+        cs.rollout = ("driving", self._params(M), dW, x0, ws, wr)
+        return cs
+
+    def scp_run_native(self, us0, iters, first_cvar=1, tol=1e-9, max_cuts=400, final_cut_above=1e-11):
+        """The whole reduced SCP as ONE library call (rato_scp_run_car: ``iters`` x [final rows, begin, solve] with the
+        per-iteration clocks of the reference's protocol taken natively), as ``drone_risk.Model.scp_run_native``.
+        -> dict(us_hist (iters, S, n_u), define_s, solve_s, oracle_s, cuts, t_risk, status) or None when the configuration
+        is not the native one (no materialised dW, sharded, S < 2, a cut solver that keeps the Python loop) / the native
+        loop handed back (rank-deficient master, a selection that gave up): the caller then runs the per-iteration loop."""
+        cs = self._native_loop_solver()
+        if cs is None or not cs.native_loop_applies():
+            return None
+        S = self.S
+        us0 = np.ascontiguousarray(us0, dtype=np.float64)
+        if us0.shape != (S, n_u):
+            raise ValueError(f"us0 must be ({S},{n_u}), got {us0.shape}")
+        h = cs._native_solver()
+        out = cs._keep_arrays()
+        assert C.sizeof(_lib.ScpIter) == self._lib.rato_scp_iter_bytes()
+        rec = (_lib.ScpIter * max(iters, 1))()
+        us_hist = np.zeros((max(iters, 1), S, n_u))
+        done = C.c_int32(0)
+        goal = self._goal64()
+        cs.check_finite = bool(self.check_finite)
+        rc = self._lib.rato_scp_run_car(
+            h, us0.ctypes.data, goal.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts),
+            float(final_cut_above), int(bool(self.check_finite)), out["keep"].ctypes.data, out["idle"].ctypes.data,
+            C.addressof(out["n_keep"]), us_hist.ctypes.data, C.addressof(rec), C.addressof(done), _lib.current_stream())
+        # the solver's Python-side state follows the native one (a later solve_reduced continues from here)
+        K = out["n_keep"].value
+        cs.keep = [int(v) for v in out["keep"][:K]]
+        cs.idle = {int(sl): int(c) for sl, c in zip(out["keep"][:K], out["idle"][:K])}
+        cs._relin_pending = None
+        n = done.value
+        if n:
+            cs.u_lin = (us_hist[n - 2] if n >= 2 else us0).reshape(-1).copy()      # the last linearization point
+        if rc in (_lib.RATO_ERANK, _lib.RATO_ESELECT):
+            _lib.synchronize()
+            return None
+        if rc == _lib.RATO_EINFEASIBLE:
+            raise cvar_cuts.dense_qp.InfeasibleError("master QP infeasible")
+        if rc == _lib.RATO_ENONFINITE:
+            raise _lib.RatoNonFiniteError("reduced SCP (native loop): non-finite final rows / constraint values (RATO_ENONFINITE)")
+        _lib.check(rc, "rato_scp_run_car")
+        recs = rec[:iters]
+        f = lambda k: np.array([getattr(r, k) for r in recs])
+        return {"us_hist": us_hist[:iters], "define_s": f("define_s"), "solve_s": f("solve_s"), "oracle_s": f("oracle_s"),
+                "master_s": f("master_s"), "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
+                "status": f("status").astype(np.int64)}
 
     def certify_reduced(self, info):
         """Matrix-free KKT certificate of the last ``solve_reduced`` (table-free oracle, an iteration with the CVaR rows)
@@ -639,6 +728,64 @@ class Model:
         return dict(zip(stats._STAT_NAMES, r.tolist()))
 
     monte_carlo_avar = staticmethod(stats.monte_carlo_avar)
+
+
+def _check_batch(models):
+    """ValueError unless the Models can share one native batch (rato_scp_batch_run_car): driving Models of method 'saa' with
+    a materialised dW on one GPU, one S, one M and the same parameter bytes.  Nothing runs on the device here."""
+    if not models:
+        raise ValueError("an SCP batch needs at least one Model")
+    for k, m in enumerate(models):
+        if not isinstance(m, Model):
+            raise ValueError(f"problem {k}: the driving SCP batch covers driving.Model only, got {type(m).__name__}")
+        if m.method != 'saa':
+            raise ValueError(f"problem {k}: the SCP batch covers method 'saa' only, got {m.method!r}")
+        if getattr(m, "_dW", None) is None or getattr(m, "_world", 1) != 1 or m.S < 2:
+            raise ValueError(f"problem {k}: the SCP batch needs a materialised dW on one GPU and S >= 2")
+        if os.environ.get("RATO_PY_CUT_LOOP") == "1":
+            raise ValueError("the SCP batch runs the native cut loop, which RATO_PY_CUT_LOOP=1 switches off")
+    m0 = models[0]
+    M0 = int(m0._ws.numel())
+    p0 = bytes(m0._params(M0))
+    for k, m in enumerate(models):
+        M = int(m._ws.numel())
+        if (m.S, M) != (m0.S, M0):
+            raise ValueError(f"problem {k}: every problem of an SCP batch has the same S and M "
+                             f"(S={m.S}, M={M} against S={m0.S}, M={M0})")
+        if bytes(m._params(M)) != p0:
+            raise ValueError(f"problem {k}: every problem of an SCP batch has the same parameters (dt, beta, ego state ...)")
+        if m.device != m0.device:
+            raise ValueError(f"problem {k}: every problem of an SCP batch is on one device")
+    if len({id(m) for m in models}) != len(models):
+        raise ValueError("a Model appears twice in the SCP batch")
+
+
+def scp_run_native_batch(models, us0, iters, first_cvar=1, tol=1e-9, max_cuts=400, final_cut_above=1e-11, n_threads=16,
+                         check_finite=True):
+    """The reduced SCP of several driving Models in lockstep as ONE library call (rato_scp_batch_run_car), as
+    ``drone_risk.scp_run_native_batch``: per SCP iteration the final rows of every problem on the host threads, one copy, the
+    kept cuts of all problems in one launch, then rounds of one batched oracle round trip for every problem still cutting.
+    Each Model brings its own cut solver and leaves it as ``scp_run_native`` would; ``us0`` [K][S][2].  ValueError (before any
+    device work) for what the batch does not cover.  -> the dict of ``cvar_cuts.scp_batch_run``."""
+    models = list(models)
+    _check_batch(models)
+    K, S = len(models), models[0].S
+    us0 = np.ascontiguousarray(us0, dtype=np.float64)
+    if us0.shape != (K, S, n_u):
+        raise ValueError(f"us0 must be ({K},{S},{n_u}), got {us0.shape}")
+    solvers = []
+    for k, m in enumerate(models):
+        cs = m._native_loop_solver()
+        if cs is None or not cs.native_loop_applies():
+            raise ValueError(f"problem {k}: its cut solver does not take the native loop")
+        solvers.append(cs)
+    lib = models[0]._lib
+    goal = models[0]._goal64()
+    run = lambda h, *tail: lib.rato_scp_batch_run_car(
+        h, us0.ctypes.data, goal.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
+        int(bool(check_finite)), *tail)
+    return cvar_cuts.scp_batch_run(lib, models[0].device, solvers, us0, iters, run, "rato_scp_batch_run_car",
+                                   n_threads=n_threads, check_finite=check_finite)
 
 
 def L2_error_us(us_mat, us_mat_prev):

@@ -1038,64 +1038,11 @@ def scp_run_native_batch(models, us0, iters, first_cvar=2, tol=1e-9, max_cuts=40
             raise ValueError(f"problem {k}: its cut solver does not take the native loop")
         solvers.append(cs)
     lib = models[0]._lib
-    handles = (C.c_void_p * K)(*[cs._native_solver() for cs in solvers])
-    for cs in solvers:
-        cs.check_finite = bool(check_finite)
-    dev_b, host_b = C.c_size_t(0), C.c_size_t(0)
-    _lib.check(lib.rato_scp_batch_bytes(handles, K, C.byref(dev_b), C.byref(host_b)), "rato_scp_batch_bytes")
-    device = models[0].device
-    dev = torch.empty(dev_b.value + 256, dtype=torch.uint8, device=device)
-    dev_ptr = (dev.data_ptr() + 255) // 256 * 256
-    host = torch.zeros(host_b.value + 16, dtype=torch.uint8).pin_memory()
-    host_ptr = (host.data_ptr() + 15) // 16 * 16
-    km = max(solvers[0].keep_max, 1)
-    keep = np.zeros((K, km), dtype=np.int32)
-    idle = np.zeros((K, km), dtype=np.int32)
-    n_keep = np.zeros(K, dtype=np.int32)
-    for k, cs in enumerate(solvers):
-        n_keep[k] = len(cs.keep)
-        keep[k, :len(cs.keep)] = cs.keep
-        idle[k, :len(cs.keep)] = [cs.idle.get(sl, 0) for sl in cs.keep]
-    assert C.sizeof(_lib.ScpIter) == lib.rato_scp_iter_bytes()
-    assert C.sizeof(_lib.ScpBatchIter) == lib.rato_scp_batch_iter_bytes()
-    n_it = max(int(iters), 1)
-    rec = (_lib.ScpIter * (K * n_it))()
-    brec = (_lib.ScpBatchIter * n_it)()
-    us_hist = np.zeros((K, n_it, S, n_u))
-    status = np.zeros(K, dtype=np.int32)
-    done = np.zeros(K, dtype=np.int32)
-    rounds = C.c_int32(0)
-    h = C.c_void_p()
-    _lib.check(lib.rato_scp_batch_create(C.byref(h), handles, K, int(n_threads), dev_ptr, dev_b.value, host_ptr, host_b.value),
-               "rato_scp_batch_create")
-    try:
-        rc = lib.rato_scp_batch_run_drone(
-            h, us0.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
-            int(bool(check_finite)), keep.ctypes.data, idle.ctypes.data, n_keep.ctypes.data, us_hist.ctypes.data,
-            C.addressof(rec), C.addressof(brec), status.ctypes.data, done.ctypes.data, C.addressof(rounds),
-            _lib.current_stream())
-        _lib.synchronize()
-    finally:
-        lib.rato_scp_batch_destroy(h)
-        del dev, host
-    # every solver's Python-side state follows its native one (a later solve_reduced continues from here)
-    for k, cs in enumerate(solvers):
-        Kk = int(n_keep[k])
-        cs.keep = [int(v) for v in keep[k, :Kk]]
-        cs.idle = {int(sl): int(c) for sl, c in zip(keep[k, :Kk], idle[k, :Kk])}
-        cs._relin_pending = None
-        n = int(done[k])
-        if n:
-            cs.u_lin = (us_hist[k, n - 2] if n >= 2 else us0[k]).reshape(-1).copy()   # the last linearization point
-    _lib.check(rc, "rato_scp_batch_run_drone")
-    it = int(iters)
-    f = lambda key: np.array([[getattr(rec[k * n_it + i], key) for i in range(it)] for k in range(K)]).reshape(K, it)
-    g = lambda key: np.array([getattr(brec[i], key) for i in range(it)])
-    return {"us_hist": us_hist[:, :it], "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
-            "iter_status": f("status").astype(np.int64), "master_s_problem": f("master_s"), "status": status.copy(),
-            "done": done.copy(), "rounds": int(rounds.value), "define_s": g("define_s"), "oracle_s": g("oracle_s"),
-            "master_s": g("master_s"), "total_s": g("total_s"), "rounds_per_iter": g("rounds").astype(np.int64),
-            "active": g("active").astype(np.int64)}
+    run = lambda h, *tail: lib.rato_scp_batch_run_drone(
+        h, us0.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
+        int(bool(check_finite)), *tail)
+    return cvar_cuts.scp_batch_run(lib, models[0].device, solvers, us0, iters, run, "rato_scp_batch_run_drone",
+                                   n_threads=n_threads, check_finite=check_finite)
 
 
 def L2_error_us(us_mat, us_mat_prev):

@@ -71,13 +71,21 @@ def run_drone_reduced(model, num_scp_iters_max=60, verbose=False, check_finite=T
     ``native_loop`` (default: whenever the Model offers it -- the drone, one GPU, table-free oracle): the whole loop as ONE
     library call with the per-iteration clocks taken natively (``Model.scp_run_native`` -> rato_scp_run_drone); False: the
     per-iteration Python loop below, which is also the checker of the native one (same iterates bit for bit) and what the
-    native call hands back to when it meets a case only the Python loop recovers.
+    native call hands back to when it meets a case only the Python loop recovers.  (A driving Model offers the native loop
+    too, but only when asked: ``native_loop=True`` / ``run_driving_reduced``.)
     ``tol``: stopping violation of the cutting-plane loops (default: ``solve_reduced``'s own, 1e-9)."""
+    return _run_reduced(model, num_scp_iters_max, verbose, check_finite, native_loop, tol, {})
+
+
+def _run_reduced(model, num_scp_iters_max, verbose, check_finite, native_loop, tol, solve_kw):
+    """run_drone_reduced / run_driving_reduced; ``solve_kw``: further keywords of the per-iteration ``solve_reduced``"""
     _finite_guard(model, check_finite)
     if hasattr(model, "_lib"):                 # a device Model: its master QP must be the native one (no silent NumPy leg)
         from . import dense_qp
         dense_qp.require_native()
     us_prev = model.initial_guess_us_mat()
+    if native_loop is None:                    # (a Model may offer the native loop without making it its default: driving)
+        native_loop = None if getattr(model, "SCP_NATIVE_LOOP_DEFAULT", True) else False
     if native_loop is not False and not verbose and num_scp_iters_max > 0 and hasattr(model, "scp_run_native"):
         _sync()
         r = model.scp_run_native(us_prev, num_scp_iters_max, **({} if tol is None else {"tol": tol}))
@@ -87,7 +95,8 @@ def run_drone_reduced(model, num_scp_iters_max=60, verbose=False, check_finite=T
             err = np.array([L2_error_us(u, p) for u, p in zip(hist, prev)])
             return {"us": hist[-1], "t_risk": float(r["t_risk"][-1]), "define_s": r["define_s"], "solve_s": r["solve_s"],
                     "cumulative_s": np.cumsum(r["define_s"] + r["solve_s"]), "L2_error": err, "cuts": r["cuts"],
-                    "oracle_s": r["oracle_s"], "us_hist": hist, "loop": "native (rato_scp_run_drone)"}
+                    "oracle_s": r["oracle_s"], "us_hist": hist,
+                    "loop": "native (%s)" % getattr(model, "SCP_NATIVE_ENTRY", "rato_scp_run_drone")}
         if native_loop is True:
             raise RuntimeError("run_drone_reduced(native_loop=True): the native SCP loop does not apply to this Model / "
                                "handed back")
@@ -97,7 +106,7 @@ def run_drone_reduced(model, num_scp_iters_max=60, verbose=False, check_finite=T
     for scp_iter in range(num_scp_iters_max):
         _sync()
         t0 = time.perf_counter()
-        us, t_risk, info = model.solve_reduced(us_prev, scp_iter, **({} if tol is None else {"tol": tol}))
+        us, t_risk, info = model.solve_reduced(us_prev, scp_iter, **({} if tol is None else {"tol": tol}), **solve_kw)
         _sync()
         dt_total = time.perf_counter() - t0
         solve_s.append(info["oracle_s"] + info["master_s"])
@@ -125,14 +134,14 @@ def _default_threads():
     return max(1, min(16, n))
 
 
-def _batch_error(k, code):
+def _batch_error(k, code, entry="rato_scp_batch_run_drone"):
     """the exception a solo run raises for RATO status ``code``, naming problem ``k`` of the batch"""
     from . import _lib, dense_qp
     if code == _lib.RATO_ENONFINITE:
         return _lib.RatoNonFiniteError(f"SCP batch, problem {k}: non-finite sample sums / constraint values (RATO_ENONFINITE)")
     if code == _lib.RATO_EINFEASIBLE:
         return dense_qp.InfeasibleError(f"SCP batch, problem {k}: master QP infeasible")
-    return _lib.RatoError(f"SCP batch, problem {k}: rato_scp_batch_run_drone status {code}")
+    return _lib.RatoError(f"SCP batch, problem {k}: {entry} status {code}")
 
 
 def run_drone_reduced_batch(models, num_scp_iters_max=60, tol=None, n_threads=None, on_error="raise", check_finite=True):
@@ -149,21 +158,32 @@ def run_drone_reduced_batch(models, num_scp_iters_max=60, tol=None, n_threads=No
     ``loop``).  A problem that fails (non-finite values, infeasible master) leaves the batch while the others finish; then
     the exception class of the solo path is raised, naming the problem -- or, with on_error="return", its dict is
     {"status": RATO code, "error": exception, "done": iterations completed}."""
-    from . import _lib, dense_qp, drone_risk
+    from . import drone_risk
+    solo = lambda m, **kw: run_drone_reduced(m, num_scp_iters_max=int(num_scp_iters_max), check_finite=check_finite, tol=tol,
+                                             **kw)
+    return _run_reduced_batch(drone_risk, "rato_scp_batch_run_drone", solo, lambda m: solo(m, native_loop=False), models,
+                              num_scp_iters_max, tol, n_threads, on_error, check_finite)
+
+
+def _run_reduced_batch(system, entry, solo, rerun, models, num_scp_iters_max, tol, n_threads, on_error, check_finite):
+    """run_drone_reduced_batch / run_driving_reduced_batch.  ``system``: the module with ``_check_batch`` and
+    ``scp_run_native_batch``; ``solo(model)``: the problem alone (no iterations to run); ``rerun(model)``: a handed-back
+    problem alone through the per-iteration loop"""
+    from . import _lib, dense_qp
     if on_error not in ("raise", "return"):
         raise ValueError(f"on_error must be 'raise' or 'return', got {on_error!r}")
     models = list(models)
-    drone_risk._check_batch(models)
+    system._check_batch(models)
     dense_qp.require_native()
     iters = int(num_scp_iters_max)
     if iters <= 0:
-        return [run_drone_reduced(m, num_scp_iters_max=iters, check_finite=check_finite, tol=tol) for m in models]
+        return [solo(m) for m in models]
     for m in models:
         _finite_guard(m, check_finite)
     us0 = np.stack([np.asarray(m.initial_guess_us_mat(), dtype=np.float64) for m in models])
     _sync()
-    r = drone_risk.scp_run_native_batch(models, us0, iters, n_threads=_default_threads() if n_threads is None else int(n_threads),
-                                        check_finite=bool(check_finite), **({} if tol is None else {"tol": tol}))
+    r = system.scp_run_native_batch(models, us0, iters, n_threads=_default_threads() if n_threads is None else int(n_threads),
+                                    check_finite=bool(check_finite), **({} if tol is None else {"tol": tol}))
     define_s, solve_s = r["define_s"], r["oracle_s"] + r["master_s"]
     cumulative = np.cumsum(r["total_s"])
     out, failed = [], []
@@ -171,13 +191,19 @@ def run_drone_reduced_batch(models, num_scp_iters_max=60, tol=None, n_threads=No
         code = int(r["status"][k])
         if code in (_lib.RATO_ERANK, _lib.RATO_ESELECT):
             m._cut_solver = None                       # (cold: a fresh cut solver, from the initial guess)
-            d = run_drone_reduced(m, num_scp_iters_max=iters, check_finite=check_finite, native_loop=False, tol=tol)
+            try:
+                d = rerun(m)
+            except (_lib.RatoError, dense_qp.InfeasibleError) as e:     # the recovering loop failed too: a failed problem
+                err = type(e)(f"SCP batch, problem {k} (handed back, status {code}; re-run alone): {e}")
+                failed.append((k, err))
+                out.append({"status": int(getattr(err, "status", code)), "error": err, "done": int(r["done"][k])})
+                continue
             d["loop"] = d["loop"] + " -- handed back by the batch (status %d), re-run alone" % code
             d["rounds"] = r["rounds"]
             out.append(d)
             continue
         if code != 0:
-            err = _batch_error(k, code)
+            err = _batch_error(k, code, entry)
             failed.append((k, err))
             out.append({"status": code, "error": err, "done": int(r["done"][k])})
             continue
@@ -186,7 +212,7 @@ def run_drone_reduced_batch(models, num_scp_iters_max=60, tol=None, n_threads=No
         err = np.array([L2_error_us(u, p) for u, p in zip(hist, prev)])
         out.append({"us": hist[-1], "t_risk": float(r["t_risk"][k, -1]), "define_s": define_s, "solve_s": solve_s,
                     "cumulative_s": cumulative, "L2_error": err, "cuts": r["cuts"][k], "us_hist": hist,
-                    "rounds": r["rounds"], "loop": "native batch (rato_scp_batch_run_drone)"})
+                    "rounds": r["rounds"], "loop": "native batch (%s)" % entry})
     if failed and on_error == "raise":
         raise failed[0][1]
     return out
@@ -282,9 +308,76 @@ def load_results(path, n):
         return [np.load(f) for _ in range(n)]
 
 
-def run_driving_reduced(model, num_scp_iters_max=15, verbose=False, check_finite=True):
-    """driving.py:486-513 with ``Model.solve_reduced`` subproblems (same loop as run_drone_reduced)."""
-    return run_drone_reduced(model, num_scp_iters_max=num_scp_iters_max, verbose=verbose, check_finite=check_finite)
+def run_driving_reduced(model, num_scp_iters_max=15, verbose=False, check_finite=True, native_loop=False, final_rows='numpy',
+                        tol=None):
+    """driving.py:486-513 with ``Model.solve_reduced`` subproblems (same loop as run_drone_reduced).  The defaults are the
+    per-iteration Python loop with the NumPy final rows.  ``native_loop=True``: the whole loop as ONE library call
+    (``Model.scp_run_native`` -> rato_scp_run_car), which computes the final rows natively (rato_car_ego_final_rows: to
+    rounding, not to the bit, the NumPy ones); ``native_loop=False, final_rows='native'`` is its per-iteration checker -- the
+    same iterates bit for bit -- and what a handed-back problem is repeated with."""
+    if final_rows not in ('numpy', 'native'):
+        raise ValueError(f"final_rows must be 'numpy' or 'native', got {final_rows!r}")
+    return _run_reduced(model, num_scp_iters_max, verbose, check_finite, bool(native_loop), tol,
+                        {} if final_rows == 'numpy' else {"final_rows": final_rows})
+
+
+def run_driving_reduced_batch(models, num_scp_iters_max=15, tol=None, n_threads=None, on_error="raise", check_finite=True):
+    """``run_driving_reduced(native_loop=True)`` for MANY driving Models at once (the reference's alpha x repeat grid,
+    driving.py:467-529) in ONE library call (``driving.scp_run_native_batch`` -> rato_scp_batch_run_car): the contract and the
+    result dicts of ``run_drone_reduced_batch``.  Every problem's iterates are those of its solo native run, bit for bit.
+    Scope: driving Models of method 'saa' with a materialised dW sharing S, M and the parameters; anything else is a
+    ValueError.  A handed-back problem is re-run alone, cold, with ``native_loop=False, final_rows='native'``."""
+    from . import driving
+    solo = lambda m, **kw: run_driving_reduced(m, num_scp_iters_max=int(num_scp_iters_max), check_finite=check_finite, tol=tol,
+                                               **kw)
+    return _run_reduced_batch(driving, "rato_scp_batch_run_car", lambda m: solo(m, native_loop=True),
+                              lambda m: solo(m, native_loop=False, final_rows='native'), models, num_scp_iters_max, tol,
+                              n_threads, on_error, check_finite)
+
+
+def draw_driving_saa_batches(alphas, num_repeats=30, M=50, S=None, seed=0):
+    """The sample batches of the reference's driving experiment in ITS draw order (driving.py:61, :470-472):
+    ``np.random.seed(seed)``, then one ``Model(M, 'saa', alpha)`` -- i.e. ``driving.sample_uncertain_parameters`` -- per
+    (alpha, repeat), alpha-major: every cell of the grid has samples of its own (unlike the drone's, whose alphas share the
+    repeats' batches).  Host only (no GPU).  -> [alpha][repeat] of (states_init, omegas_speed, omegas_repulsive, DWs)."""
+    from . import driving
+    from . import driving_params as P
+    S = P.S if S is None else int(S)
+    np.random.seed(seed)
+    return [[driving.sample_uncertain_parameters(M, 'saa', S) for _ in range(num_repeats)] for _ in alphas]
+
+
+def driving_saa_experiment(alphas=(0.01, 0.02, 0.05, 0.1), num_repeats=30, M=50, S=20, iters=15, seed=0, mc_model=None,
+                           results_dir=None, n_threads=None, device='cuda:0'):
+    """The reference's driving SAA experiment (driving.py:467-529, :672-700) as one call, shaped like
+    ``drone_saa_experiment``: the samples of every (alpha, repeat) drawn in the reference's order
+    (``draw_driving_saa_batches``), the grid solved in ONE lockstep batch (``run_driving_reduced_batch``), with ``mc_model``
+    the Monte-Carlo report per alpha, with ``results_dir`` the reference's result files driving_alpha=<alpha>_repeat=<r>.npy
+    (us, then xs).  -> dict(alphas, results [alpha][repeat], us (A, R, S, 2), reports {alpha: report} (with mc_model), rounds,
+    wall_s, models)"""
+    import time as _time
+    from . import driving
+    alphas = [float(a) for a in alphas]
+    draws = draw_driving_saa_batches(alphas, num_repeats, M, S, seed)
+    models = [driving.Model(M, 'saa', a, S=S, device=device, samples=draws[i][r])
+              for i, a in enumerate(alphas) for r in range(num_repeats)]
+    _sync()
+    t0 = _time.perf_counter()
+    res = run_driving_reduced_batch(models, num_scp_iters_max=iters, n_threads=n_threads)
+    _sync()
+    wall = _time.perf_counter() - t0
+    grid = [[res[i * num_repeats + r] for r in range(num_repeats)] for i in range(len(alphas))]
+    us = np.stack([np.stack([g["us"] for g in row]) for row in grid])
+    out = {"alphas": alphas, "results": grid, "us": us, "rounds": res[0].get("rounds"), "wall_s": wall, "models": models}
+    if results_dir is not None:
+        os.makedirs(results_dir, exist_ok=True)
+        for i, a in enumerate(alphas):
+            for r in range(num_repeats):
+                xs = models[i * num_repeats + r].us_to_state_trajectories(us[i, r])
+                save_results(os.path.join(results_dir, f"driving_alpha={a}_repeat={r}.npy"), us[i, r], np.asarray(xs))
+    if mc_model is not None:
+        out["reports"] = {a: monte_carlo_report(mc_model, list(us[i]), a) for i, a in enumerate(alphas)}
+    return out
 
 
 def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
