@@ -90,6 +90,12 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+bool all_finite(const double* v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
 }  // namespace
 
 struct rato_cut_solver {
@@ -130,8 +136,8 @@ extern "C" int rato_cut_solver_create(rato_cut_solver** out, const rato_cut_conf
   }
   s->nU = n_u * c.S;
   s->n = s->nU + 1;
-  s->nc = 2 * std::max(c.S - 1, 0) + 1;
-  s->nres = RATO_N_STATS + s->nc;
+  s->nres = rato::record_words(c.S);
+  s->nc = s->nres - RATO_N_STATS;
   s->nblk = (int)((c.M + 255) / 256);
   s->p_diag.assign(c.p_diag, c.p_diag + s->n);
   s->q.assign(c.q, c.q + s->n);
@@ -221,11 +227,17 @@ int settle_kept(rato_cut_solver* s, hipStream_t st) {
   return e == hipSuccess ? RATO_OK : RATO_EHIP - (int)e;
 }
 
-bool keep_ok(const rato_cut_solver* s, const int32_t* keep, int n_keep) {
+// the kept cuts as every entry takes them: a count within keep_max and ring slots below the scratch slot (cap - 1).  The
+// slots are checked at S = 1 too, where nothing re-linearizes them: CutLoop::init indexes host tables with them regardless.
+bool keep_args_ok(const rato_cut_solver* s, const int32_t* keep, int n_keep) {
+  if (n_keep < 0 || n_keep > s->c.keep_max || (n_keep > 0 && !keep)) return false;
   for (int k = 0; k < n_keep; ++k)
     if (keep[k] < 0 || keep[k] >= s->c.cap - 1) return false;
   return true;
 }
+
+// are there kept cuts to re-linearize?  (no control enters the only row of S = 1: its cuts have no rows)
+bool with_cuts(const rato_cut_solver* s, int n_keep) { return n_keep > 0 && s->c.S >= 2; }
 
 }  // namespace
 
@@ -234,17 +246,16 @@ bool keep_ok(const rato_cut_solver* s, const int32_t* keep, int n_keep) {
 // (sums_b_host).  Nothing is synchronised: the caller's own read-back of the linearization's sample sums waits for
 // this work too (one device round trip per "define" instead of two).
 extern "C" int rato_cut_begin(rato_cut_solver* s, const double* u_lin, const int32_t* keep, int32_t n_keep, void* stream) {
-  if (!s || !u_lin || n_keep < 0 || n_keep > s->c.keep_max || (n_keep > 0 && !keep)) return RATO_EINVAL;
+  if (!s || !u_lin || !keep_args_ok(s, keep, n_keep)) return RATO_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool with_cuts = n_keep > 0 && s->c.S >= 2;
-  if (with_cuts && !keep_ok(s, keep, n_keep)) return RATO_EINVAL;
+  const int n_cuts = with_cuts(s, n_keep) ? n_keep : 0;
   int rc = settle_kept(s, st);
   if (rc != RATO_OK) return rc;
-  rc = stage_inputs(s, u_lin, nullptr, nullptr, keep, with_cuts ? n_keep : 0, st);
+  rc = stage_inputs(s, u_lin, nullptr, nullptr, keep, n_cuts, st);
   if (rc != RATO_OK) return rc;
-  const bool arm_kept = with_cuts && rato::readback_poll_enabled();
-  if (arm_kept) rato::readback_arm(s->c.sums_b_host, n_keep * s->nc);
-  rc = kept_cuts_launch(s, with_cuts ? n_keep : 0, stream);
+  const bool arm_kept = n_cuts > 0 && rato::readback_poll_enabled();
+  if (arm_kept) rato::readback_arm(s->c.sums_b_host, n_cuts * s->nc);
+  rc = kept_cuts_launch(s, n_cuts, stream);
   s->kept_armed = arm_kept && rc == RATO_OK;   // armed words with nothing launched behind them are never waited for
   return rc;
 }
@@ -262,13 +273,11 @@ extern "C" int rato_cut_define_drone(rato_cut_solver* s, const double* us, float
                                      float* Z, int64_t z_floats, float* part, double* sums_host, uint32_t* bad_dev,
                                      uint32_t* bad_host, const int32_t* keep, int32_t n_keep, void* stream) {
   if (!s || s->c.system != 0 || !us || !us_host || !us_dev || !A22 || !part || !sums_host || (!bad_dev != !bad_host) ||
-      (bad_dev && !Z) || (Z && z_floats < s->c.M))
+      (bad_dev && !Z) || (Z && z_floats < s->c.M) || !keep_args_ok(s, keep, n_keep))
     return RATO_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int nU = s->nU, S = s->c.S, ncols = 6 * S + 6;
-  if (n_keep < 0 || n_keep > s->c.keep_max || (n_keep > 0 && !keep)) return RATO_EINVAL;
-  const bool with_cuts = n_keep > 0 && S >= 2;
-  if (with_cuts && !keep_ok(s, keep, n_keep)) return RATO_EINVAL;
+  const int n_cuts = with_cuts(s, n_keep) ? n_keep : 0;
   for (int i = 0; i < nU; ++i) us_host[i] = (float)us[i];
   hipError_t e = hipSuccess;
   // the sample sums land in pinned memory and are watched for (rato_common.h: readback_*); with the non-finite count
@@ -277,9 +286,9 @@ extern "C" int rato_cut_define_drone(rato_cut_solver* s, const double* us, float
   int rc = settle_kept(s, st);   // a kept-cuts launch nobody waited for must not write into words armed anew
   if (rc != RATO_OK) return rc;
   if (watch) rato::readback_arm(sums_host, ncols);
-  const bool arm_kept = with_cuts && rato::readback_poll_enabled();
-  if (arm_kept) rato::readback_arm(s->c.sums_b_host, n_keep * s->nc);   // (kept_armed only once the launch is out)
-  rc = stage_inputs(s, us, us_host, us_dev, keep, with_cuts ? n_keep : 0, st);   // us, u_k (fp64) and the kept slots: one launch
+  const bool arm_kept = n_cuts > 0 && rato::readback_poll_enabled();
+  if (arm_kept) rato::readback_arm(s->c.sums_b_host, n_cuts * s->nc);   // (kept_armed only once the launch is out)
+  rc = stage_inputs(s, us, us_host, us_dev, keep, n_cuts, st);   // us, u_k (fp64) and the kept slots: one launch
   if (rc != RATO_OK) return rc;
   rc = rato_drone_linearize_generators(&s->drone, us_dev, s->c.s0, s->c.s1, s->c.s2, A22, nullptr, nullptr, Z, part,
                                            stream);
@@ -301,7 +310,7 @@ extern "C" int rato_cut_define_drone(rato_cut_solver* s, const double* us, float
     e = hipEventRecord(s->sums_ready, st);
     if (e != hipSuccess) return RATO_EHIP - (int)e;
   }
-  if ((rc = kept_cuts_launch(s, with_cuts ? n_keep : 0, stream)) != RATO_OK) return rc;
+  if ((rc = kept_cuts_launch(s, n_cuts, stream)) != RATO_OK) return rc;
   s->kept_armed = arm_kept;
   e = watch ? rato::readback_wait(sums_host, ncols, st) : hipEventSynchronize(s->sums_ready);
   if (e != hipSuccess) return RATO_EHIP - (int)e;
@@ -379,16 +388,15 @@ struct CutLoop {
       if ((rc = rato_master_add_rows(master, 1, row.data(), &zero)) != RATO_OK) return rc;
       n_rows = 1;
     }
-    n_kept = (cvar && c.recycle) ? *n_keep_io : 0;
-    if (n_kept < 0 || n_kept > c.keep_max) return RATO_EINVAL;
     // the kept slots index host tables below (is_kept, idle) whether or not their re-linearization is already in flight:
-    // checked here unconditionally, not only inside rato_cut_begin / rato_cut_define_drone
-    if (*n_keep_io < 0 || *n_keep_io > c.keep_max || !keep_ok(s, keep, *n_keep_io)) return RATO_EINVAL;
+    // checked here too, not only inside rato_cut_begin / rato_cut_define_drone
+    if (!keep_args_ok(s, keep, *n_keep_io)) return RATO_EINVAL;
+    n_kept = (cvar && c.recycle) ? *n_keep_io : 0;
     master_s += seconds_since(t0);
     return RATO_OK;
   }
 
-  bool wants_kept() const { return n_kept > 0 && S >= 2; }
+  bool wants_kept() const { return with_cuts(s, n_kept); }
 
   // sums [n_kept][nc]: the kept cuts' tail-row sums under the current linearization point
   int add_kept(const double* sums) {
@@ -675,58 +683,61 @@ void scp_record(rato_scp_iter& r, const rato_cut_result& res, double total) {
   r.recycled = res.recycled;
   r.reserved = 0;
 }
-}  // namespace
 
-// The reduced SCP of the drone as ONE call: `iters` iterations of [rato_cut_define_drone at the current controls -> the
-// equality rows from the sample sums -> rato_cut_solve], the reference's fixed-count protocol (drone_risk.py:519-532,
-// drone_times.py:509-550) with its per-iteration wall clocks taken here.  Each iteration is timed from its first
-// instruction to the moment its solution is on the host (the last oracle round trip has been read back: the device has
-// nothing of this iteration left to do); the stream is synchronised ONCE, after the last iteration, inside that
-// iteration's clock.  scp.run_drone_reduced's Python loop (one define + one solve call per iteration, a device
-// synchronisation on both sides of each) stays as the checker: same iterates bit for bit (tests/test_gpu_scp.py).
-//   us0 [S][3]: the initial guess;  first_cvar: the first iteration with the CVaR rows (2: drone_risk.py:413-417);
-//   us_hist [iters][S][3] (host): the solution of every iteration;  rec [iters];
-//   the define's buffers as for rato_cut_define_drone;  keep / keep_idle_count / n_keep_io: in and out as for rato_cut_solve.
-// Returns the first non-OK status of a define / solve (RATO_ERANK, RATO_ESELECT: repeat with the per-iteration calls,
-// whose Python loop recovers), *done = iterations completed.
-extern "C" int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t iters, int32_t first_cvar, double tol,
-                                  int32_t max_cuts, double final_cut_above, int32_t check_finite, float* us_host,
-                                  float* us_dev, float* A22, float* part, double* sums_host, int32_t* keep,
-                                  int32_t* keep_idle_count, int32_t* n_keep_io, double* us_hist, rato_scp_iter* rec,
-                                  int32_t* done, void* stream) {
-  if (!s || s->c.system != 0 || !us0 || iters < 0 || !us_host || !us_dev || !A22 || !part || !sums_host || !keep ||
-      !keep_idle_count || !n_keep_io || !us_hist || !rec || !done)
-    return RATO_EINVAL;
-  const int S = s->c.S, nU = s->nU, n_c = 6;
-  const double M = (double)s->c.M, inv_M = 1.0 / M;
-  std::vector<double> us(us0, us0 + nU), final_du((size_t)n_c * nU), final_rhs(n_c), sol(nU);
-  std::vector<int32_t> cut_slot(s->c.cap + 8);
-  std::vector<double> cut_lambda(s->c.cap + 8);
+// where a subproblem's outputs land: the solution and the certificate's (slot, multiplier) pairs
+struct ResultBuf {
+  std::vector<double> sol, cut_lambda;
+  std::vector<int32_t> cut_slot;
+  explicit ResultBuf(const rato_cut_solver* s) : sol(s->nU), cut_lambda(s->c.cap + 8), cut_slot(s->c.cap + 8) {}
+  rato_cut_result wired() {   // a zeroed result pointing into this storage
+    rato_cut_result r = {};
+    r.us = sol.data();
+    r.cut_slot = cut_slot.data();
+    r.cut_lambda = cut_lambda.data();
+    r.cut_capacity = (int)cut_slot.size();
+    return r;
+  }
+};
+
+// The drone's equality rows from the sample sums [6S + 6] of its linearization: mean of the final-state Jacobian (axis a: row a
+// = position, row 3 + a = velocity; the axes decouple) and of its right-hand side (drone_risk.py:271-273, :294-300).  The rows
+// are sums * (1 / M), the right-hand side sums / M: the two roundings of the Python checker (expand_final_du(.., 1.0 / M),
+// sums[6S:] / M), which the solo loop and the batch must both reproduce to the bit.  final_du [6][3S], final_rhs [6].
+void drone_final_rows(const double* sums, int S, int64_t M, double* final_du, double* final_rhs) {
+  const int nU = 3 * S;
+  const double Md = (double)M, inv_M = 1.0 / Md;
+  std::fill(final_du, final_du + (size_t)6 * nU, 0.0);
+  for (int t = 0; t < S; ++t)
+    for (int a = 0; a < 3; ++a) {
+      final_du[(size_t)a * nU + t * 3 + a] = sums[t * 6 + a] * inv_M;
+      final_du[(size_t)(3 + a) * nU + t * 3 + a] = sums[t * 6 + 3 + a] * inv_M;
+    }
+  for (int r = 0; r < 6; ++r) final_rhs[r] = sums[6 * S + r] / Md;
+}
+
+// The reduced SCP of one problem as ONE call: `iters` iterations of [define at the current controls -> rato_cut_solve], the
+// reference's fixed-count protocol (drone_risk.py:519-532, drone_times.py:509-550; driving.py:486-513) with its per-iteration
+// wall clocks taken here.  define(us, K, final_du, final_rhs) -> rc is the system's: it leaves the n_c equality rows on the
+// host and u_k plus the K kept cuts' re-linearization on the stream.  Each iteration is timed from its first instruction to
+// the moment its solution is on the host (the last oracle round trip has been read back: the device has nothing of this
+// iteration left to do); the stream is synchronised ONCE, after the last iteration, inside that iteration's clock.
+// Returns the first non-OK status of a define / solve (RATO_ERANK, RATO_ESELECT: repeat with the per-iteration calls, whose
+// Python loop recovers), *done = iterations completed.
+template <class Define>
+int scp_run(rato_cut_solver* s, int n_c, const double* us0, int32_t iters, int32_t first_cvar, double tol, int32_t max_cuts,
+            double final_cut_above, int32_t check_finite, int32_t* keep, int32_t* keep_idle_count, int32_t* n_keep_io,
+            double* us_hist, rato_scp_iter* rec, int32_t* done, void* stream, Define&& define) {
+  const int nU = s->nU;
+  std::vector<double> us(us0, us0 + nU), final_du((size_t)n_c * nU), final_rhs(n_c);
+  ResultBuf out(s);
   *done = 0;
   for (int it = 0; it < iters; ++it) {
     const auto t0 = std::chrono::steady_clock::now();
     const bool cvar = it >= first_cvar;
-    const int K = (cvar && s->c.recycle && S >= 2) ? *n_keep_io : 0;
-    int rc = rato_cut_define_drone(s, us.data(), us_host, us_dev, A22, nullptr, 0, part, sums_host, nullptr, nullptr, keep, K,
-                                   stream);
+    const int K = (cvar && s->c.recycle && s->c.S >= 2) ? *n_keep_io : 0;
+    int rc = define(us.data(), K, final_du.data(), final_rhs.data());
     if (rc != RATO_OK) return rc;
-    if (check_finite)
-      for (int i = 0; i < 6 * S + 6; ++i)
-        if (!std::isfinite(sums_host[i])) return RATO_ENONFINITE;
-    // the equality rows: mean of the final-state Jacobian (axis a: row a = position, row 3 + a = velocity; the axes decouple)
-    // and of its right-hand side (drone_risk.py:271-273, :294-300)
-    std::fill(final_du.begin(), final_du.end(), 0.0);
-    for (int t = 0; t < S; ++t)
-      for (int a = 0; a < 3; ++a) {
-        final_du[(size_t)a * nU + t * 3 + a] = sums_host[t * 6 + a] * inv_M;
-        final_du[(size_t)(3 + a) * nU + t * 3 + a] = sums_host[t * 6 + 3 + a] * inv_M;
-      }
-    for (int r = 0; r < n_c; ++r) final_rhs[r] = sums_host[6 * S + r] / M;
-    rato_cut_result res = {};
-    res.us = sol.data();
-    res.cut_slot = cut_slot.data();
-    res.cut_lambda = cut_lambda.data();
-    res.cut_capacity = (int)cut_slot.size();
+    rato_cut_result res = out.wired();
     rc = rato_cut_solve(s, final_du.data(), final_rhs.data(), n_c, us.data(), cvar ? 1 : 0, tol, max_cuts, final_cut_above,
                         check_finite, keep, keep_idle_count, n_keep_io, K > 0 ? 1 : 0, &res, stream);
     if (rc != RATO_OK) return rc;
@@ -735,11 +746,38 @@ extern "C" int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t
       if (e != hipSuccess) return RATO_EHIP - (int)e;
     }
     scp_record(rec[it], res, seconds_since(t0));
-    memcpy(us_hist + (size_t)it * nU, sol.data(), sizeof(double) * nU);
-    us = sol;
+    memcpy(us_hist + (size_t)it * nU, out.sol.data(), sizeof(double) * nU);
+    us = out.sol;
     *done = it + 1;
   }
   return RATO_OK;
+}
+}  // namespace
+
+// The reduced SCP of the drone (scp_run above); its define: rato_cut_define_drone at the current controls -> the equality rows
+// from the sample sums.  scp.run_drone_reduced's Python loop (one define + one solve call per iteration, a device
+// synchronisation on both sides of each) stays as the checker: same iterates bit for bit (tests/test_gpu_scp.py).
+//   us0 [S][3]: the initial guess;  first_cvar: the first iteration with the CVaR rows (2: drone_risk.py:413-417);
+//   us_hist [iters][S][3] (host): the solution of every iteration;  rec [iters];
+//   the define's buffers as for rato_cut_define_drone;  keep / keep_idle_count / n_keep_io: in and out as for rato_cut_solve.
+extern "C" int rato_scp_run_drone(rato_cut_solver* s, const double* us0, int32_t iters, int32_t first_cvar, double tol,
+                                  int32_t max_cuts, double final_cut_above, int32_t check_finite, float* us_host,
+                                  float* us_dev, float* A22, float* part, double* sums_host, int32_t* keep,
+                                  int32_t* keep_idle_count, int32_t* n_keep_io, double* us_hist, rato_scp_iter* rec,
+                                  int32_t* done, void* stream) {
+  if (!s || s->c.system != 0 || !us0 || iters < 0 || !us_host || !us_dev || !A22 || !part || !sums_host || !keep ||
+      !keep_idle_count || !n_keep_io || !us_hist || !rec || !done)
+    return RATO_EINVAL;
+  const int S = s->c.S;
+  return scp_run(s, 6, us0, iters, first_cvar, tol, max_cuts, final_cut_above, check_finite, keep, keep_idle_count, n_keep_io,
+                 us_hist, rec, done, stream, [&](const double* us, int K, double* final_du, double* final_rhs) {
+                   const int rc = rato_cut_define_drone(s, us, us_host, us_dev, A22, nullptr, 0, part, sums_host, nullptr,
+                                                        nullptr, keep, K, stream);
+                   if (rc != RATO_OK) return rc;
+                   if (check_finite && !all_finite(sums_host, 6 * (size_t)S + 6)) return RATO_ENONFINITE;
+                   drone_final_rows(sums_host, S, s->c.M, final_du, final_rhs);
+                   return RATO_OK;
+                 });
 }
 
 extern "C" size_t rato_scp_iter_bytes(void) { return sizeof(rato_scp_iter); }
@@ -800,19 +838,10 @@ extern "C" int rato_car_ego_final_rows(const rato_car_params* p, const double* u
   return RATO_OK;
 }
 
-namespace {
-bool all_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-}  // namespace
-
-// The reduced SCP of the DRIVING problem as ONE call (driving.py:486-513), modelled on rato_scp_run_drone: `iters`
-// iterations of [rato_car_ego_final_rows at the current controls -> rato_cut_begin (u_k in fp64 + the kept cuts against it)
-// -> rato_cut_solve with the 4 equality rows], the same per-iteration clocks and records, the stream synchronised once inside
-// the last iteration's clock.  scp.run_driving_reduced(native_loop=False, final_rows='native') is the per-iteration checker:
-// same iterates bit for bit (tests/test_gpu_scp_car_native.py).
+// The reduced SCP of the DRIVING problem (scp_run above; driving.py:486-513); its define: rato_car_ego_final_rows at the
+// current controls -> rato_cut_begin (u_k in fp64 + the kept cuts against it).
+// scp.run_driving_reduced(native_loop=False, final_rows='native') is the per-iteration checker: same iterates bit for bit
+// (tests/test_gpu_scp_car_native.py).
 //   us0 [S][2];  goal [4]: the ego's goal state (position, speed, heading);  first_cvar: 1 (driving.py:411-415);
 //   us_hist [iters][S][2];  rec [iters];  keep / keep_idle_count / n_keep_io: in and out as for rato_cut_solve.
 extern "C" int rato_scp_run_car(rato_cut_solver* s, const double* us0, const double* goal, int32_t iters, int32_t first_cvar,
@@ -821,38 +850,14 @@ extern "C" int rato_scp_run_car(rato_cut_solver* s, const double* us0, const dou
                                 void* stream) {
   if (!s || s->c.system != 1 || !us0 || !goal || iters < 0 || !keep || !keep_idle_count || !n_keep_io || !us_hist || !rec || !done)
     return RATO_EINVAL;
-  const int S = s->c.S, nU = s->nU, n_c = 4;
-  std::vector<double> us(us0, us0 + nU), final_du((size_t)n_c * nU), final_rhs(n_c), sol(nU);
-  std::vector<int32_t> cut_slot(s->c.cap + 8);
-  std::vector<double> cut_lambda(s->c.cap + 8);
-  *done = 0;
-  for (int it = 0; it < iters; ++it) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool cvar = it >= first_cvar;
-    const int K = (cvar && s->c.recycle && S >= 2) ? *n_keep_io : 0;
-    int rc = rato_car_ego_final_rows(&s->car, us.data(), goal, final_du.data(), final_rhs.data());
-    if (rc != RATO_OK) return rc;
-    if (check_finite && !(all_finite(final_du.data(), final_du.size()) && all_finite(final_rhs.data(), final_rhs.size())))
-      return RATO_ENONFINITE;
-    if ((rc = rato_cut_begin(s, us.data(), keep, K, stream)) != RATO_OK) return rc;
-    rato_cut_result res = {};
-    res.us = sol.data();
-    res.cut_slot = cut_slot.data();
-    res.cut_lambda = cut_lambda.data();
-    res.cut_capacity = (int)cut_slot.size();
-    rc = rato_cut_solve(s, final_du.data(), final_rhs.data(), n_c, us.data(), cvar ? 1 : 0, tol, max_cuts, final_cut_above,
-                        check_finite, keep, keep_idle_count, n_keep_io, K > 0 ? 1 : 0, &res, stream);
-    if (rc != RATO_OK) return rc;
-    if (it == iters - 1) {   // the protocol's closing synchronisation, once: inside the last iteration's clock
-      const hipError_t e = hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream));
-      if (e != hipSuccess) return RATO_EHIP - (int)e;
-    }
-    scp_record(rec[it], res, seconds_since(t0));
-    memcpy(us_hist + (size_t)it * nU, sol.data(), sizeof(double) * nU);
-    us = sol;
-    *done = it + 1;
-  }
-  return RATO_OK;
+  const size_t nU = (size_t)s->nU;
+  return scp_run(s, 4, us0, iters, first_cvar, tol, max_cuts, final_cut_above, check_finite, keep, keep_idle_count, n_keep_io,
+                 us_hist, rec, done, stream, [&](const double* us, int K, double* final_du, double* final_rhs) {
+                   const int rc = rato_car_ego_final_rows(&s->car, us, goal, final_du, final_rhs);
+                   if (rc != RATO_OK) return rc;
+                   if (check_finite && !(all_finite(final_du, 4 * nU) && all_finite(final_rhs, 4))) return RATO_ENONFINITE;
+                   return rato_cut_begin(s, us, keep, K, stream);
+                 });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1067,9 +1072,8 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
   if (car && !goal) return RATO_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int K = b->K, S = b->S, nU = b->nU, nc = b->nc, nres = b->nres, ncols = b->ncols, km = std::max(b->keep_max, 1);
-  const int n_c = car ? 4 : 6, n_words = RATO_N_STATS + nc;
+  const int n_c = car ? 4 : 6;
   const size_t Mz = (size_t)b->M;
-  const double Md = (double)b->M, inv_M = 1.0 / Md;
   const BatchLayout& L = b->lay;
   double* res_host = reinterpret_cast<double*>(b->host + L.h_res);
   double* sums_host = reinterpret_cast<double*>(b->host + L.h_sums);
@@ -1077,22 +1081,19 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
   auto dev_of = [&](const void* host_ptr) {   // the device address of a byte of the define / round mirrors
     return b->dev + (static_cast<const unsigned char*>(host_ptr) - b->host);
   };
-  std::vector<std::vector<double>> us(K), sol(K);
+  std::vector<std::vector<double>> us(K);
   std::vector<std::unique_ptr<CutLoop>> loop(K);
-  std::vector<rato_cut_result> res(K);
-  std::vector<std::vector<int32_t>> cut_slot(K);
-  std::vector<std::vector<double>> cut_lambda(K);
+  std::vector<ResultBuf> out;
+  out.reserve(K);
   std::vector<int> dpos(K, -1);
   std::vector<std::vector<double>> car_du(car ? K : 0), car_rhs(car ? K : 0);   // the car's equality rows of the iteration
   for (int p = 0; p < K; ++p) {
     us[p].assign(us0 + (size_t)p * nU, us0 + (size_t)(p + 1) * nU);
-    sol[p].resize(nU);
+    out.emplace_back(b->sv[p]);
     if (car) {
       car_du[p].resize((size_t)n_c * nU);
       car_rhs[p].resize(n_c);
     }
-    cut_slot[p].resize(b->sv[p]->c.cap + 8);
-    cut_lambda[p].resize(b->sv[p]->c.cap + 8);
     status[p] = RATO_OK;
     done[p] = 0;
     const int rc = settle_kept(b->sv[p], st);   // a kept-cuts launch of a solo define nobody waited for
@@ -1155,11 +1156,11 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
     for (int p : act) {
       rato_cut_solver* s = b->sv[p];
       int32_t* kp = keep + (size_t)p * km;
-      const int Kp = (cvar && s->c.recycle) ? n_keep[p] : 0;
-      if (n_keep[p] < 0 || n_keep[p] > s->c.keep_max || Kp < 0 || (Kp > 0 && !keep_ok(s, kp, Kp))) {
+      if (!keep_args_ok(s, kp, n_keep[p])) {
         status[p] = RATO_EINVAL;
         continue;
       }
+      const int Kp = (cvar && s->c.recycle) ? n_keep[p] : 0;   // (S >= 2 in a batch: every kept cut has rows)
       rato::BatchProb& t = tab[n];
       fill_common(t, p);
       double* uk = uk_h + (size_t)n * nU;
@@ -1236,15 +1237,9 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
           status[p] = RATO_ENONFINITE;
           return;
         }
-        // the equality rows (as rato_scp_run_drone builds them)
-        drone_du.assign((size_t)n_c * nU, 0.0);
+        drone_du.resize((size_t)n_c * nU);
         drone_rhs.resize(n_c);
-        for (int t = 0; t < S; ++t)
-          for (int a = 0; a < 3; ++a) {
-            drone_du[(size_t)a * nU + t * 3 + a] = sm[t * 6 + a] * inv_M;
-            drone_du[(size_t)(3 + a) * nU + t * 3 + a] = sm[t * 6 + 3 + a] * inv_M;
-          }
-        for (int r = 0; r < n_c; ++r) drone_rhs[r] = sm[6 * S + r] / Md;
+        drone_final_rows(sm, S, b->M, drone_du.data(), drone_rhs.data());
       }
       const std::vector<double>&final_du = car ? car_du[p] : drone_du, &final_rhs = car ? car_rhs[p] : drone_rhs;
       loop[p].reset(new CutLoop);
@@ -1279,7 +1274,7 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
         t.arg_out = c.ring_arg + (size_t)lp.ring * Mz;
         t.res_dev = c.ring_res + (size_t)lp.ring * nres;
         t.res_host = res_host + (size_t)p * nres;
-        if (rato::readback_poll_enabled()) rato::readback_arm(t.res_host, n_words);
+        if (rato::readback_poll_enabled()) rato::readback_arm(t.res_host, nres);
       }
       // (one copy: the rows, then x at a fixed offset -- only the rows' and x's used parts travel)
       e = hipMemcpyAsync(b->dev + L.r_tab, b->host + L.r_tab, (size_t)nq * sizeof(rato::BatchProb), hipMemcpyHostToDevice, st);
@@ -1304,7 +1299,7 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
       if (rc == RATO_OK) rc = rato::launch_cut_finish_batch(rtab_d, nq, b->nblk, nc, RATO_N_STATS, st);
       if (rc != RATO_OK) return rc;
       for (int i = 0; i < nq; ++i) {
-        e = rato::readback_wait(rtab[i].res_host, n_words, st);
+        e = rato::readback_wait(rtab[i].res_host, nres, st);
         if (e != hipSuccess) return RATO_EHIP - (int)e;
       }
       br.oracle_s += seconds_since(t0);
@@ -1324,26 +1319,14 @@ int batch_run(rato_scp_batch* b, const double* us0, const double* goal, int32_t 
         loop[p].reset();
         continue;
       }
-      rato_cut_result& r = res[p];
-      memset(&r, 0, sizeof(r));
-      r.us = sol[p].data();
-      r.cut_slot = cut_slot[p].data();
-      r.cut_lambda = cut_lambda[p].data();
-      r.cut_capacity = (int)cut_slot[p].size();
+      rato_cut_result r = out[p].wired();
       loop[p]->finish(&r);
       loop[p].reset();
       rato_scp_iter& ri = rec[(size_t)p * iters + it];
+      scp_record(ri, r, 0.0);
       ri.define_s = ri.solve_s = ri.oracle_s = NAN;   // (per problem only the master's own time is known: brec has the clocks)
-      ri.master_s = r.master_s;
-      ri.t_risk = r.t_risk;
-      ri.slack = r.slack;
-      ri.phi = r.phi;
-      ri.cuts = r.cuts;
-      ri.status = r.status;
-      ri.recycled = r.recycled;
-      ri.reserved = 0;
-      memcpy(us_hist + ((size_t)p * iters + it) * nU, sol[p].data(), sizeof(double) * nU);
-      us[p] = sol[p];
+      memcpy(us_hist + ((size_t)p * iters + it) * nU, out[p].sol.data(), sizeof(double) * nU);
+      us[p] = out[p].sol;
       done[p] = it + 1;
     }
     if (it == iters - 1) {

@@ -1653,39 +1653,25 @@ extern "C" int rato_drone_tail_rows_rollout(const rato_drone_params* p, const do
   int c_tab = 0;
   const size_t lds = tail_rows_lds(p->S, c_tab);
   if (!lds) return RATO_EINVAL;
-  static rato::DynamicLdsLimit lds_limit;
-  {
-    const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    });
-    if (e != hipSuccess) return RATO_EHIP - (int)e;
-  }
   // several cuts (the kept cuts of a subproblem): the union form, up to TRU_KMAX cuts per launch (A/B: RATO_TAIL_UNION=0)
   if (rato::drone_tail_union_form(p->S, K)) {
-    const size_t lds_u = tail_union_lds_bytes(p->S, K < TRU_KMAX ? K : TRU_KMAX);
-    {
-      static rato::DynamicLdsLimit lds_limit_u;
-      const hipError_t e = lds_limit_u.ensure(lds_u, [](size_t bytes) {
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_union_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      });
-      if (e != hipSuccess) return RATO_EHIP - (int)e;
-      for (int k0 = 0; k0 < K; k0 += TRU_KMAX) {
-        const int kn = (K - k0) < TRU_KMAX ? (K - k0) : TRU_KMAX;
-        hipLaunchKernelGGL(drone_tail_rows_rollout_union_kernel, dim3((unsigned)rato::nblocks_for(p->M)),
-                           dim3(TRU_NW * RATO_WAVE), tail_union_lds_bytes(p->S, kn), rato::as_stream(stream), *p, uk, dW,
-                           mass, Qsym, m_base, arg_base, stats_base, (long)stats_stride, slots, k0, kn, K, alphaM, part);
-        RATO_LAUNCH_CHECK();
-      }
-      return RATO_OK;
+    static rato::DynamicLdsLimit lds_limit_u;   // (the first chunk is the largest: it raises the limit for all)
+    for (int k0 = 0; k0 < K; k0 += TRU_KMAX) {
+      const int kn = (K - k0) < TRU_KMAX ? (K - k0) : TRU_KMAX;
+      const size_t lds_u = tail_union_lds_bytes(p->S, kn);
+      const int rc = rato::launch_dynamic_lds(drone_tail_rows_rollout_union_kernel, lds_limit_u, lds_u, lds_u,
+                                              dim3((unsigned)rato::nblocks_for(p->M)), dim3(TRU_NW * RATO_WAVE),
+                                              rato::as_stream(stream), *p, uk, dW, mass, Qsym, m_base, arg_base, stats_base,
+                                              (long)stats_stride, slots, k0, kn, K, alphaM, part);
+      if (rc != RATO_OK) return rc;
     }
+    return RATO_OK;
   }
+  static rato::DynamicLdsLimit lds_limit;
   dim3 grid((unsigned)rato::nblocks_for(p->M), (unsigned)K), block(RATO_BLOCK);
-  hipLaunchKernelGGL(drone_tail_rows_rollout_kernel, grid, block, lds, rato::as_stream(stream), *p, uk, dW, mass, Qsym,
-                     m_base, arg_base, stats_base, (long)stats_stride, slots, alphaM, part, c_tab);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return rato::launch_dynamic_lds(drone_tail_rows_rollout_kernel, lds_limit, lds, lds, grid, block, rato::as_stream(stream), *p,
+                                  uk, dW, mass, Qsym, m_base, arg_base, stats_base, (long)stats_stride, slots, alphaM, part,
+                                  c_tab);
 }
 
 
@@ -1708,16 +1694,9 @@ int launch_drone_tail_rows_batch(const rato_drone_params* p, const BatchProb* ta
   const size_t lds = tail_rows_lds(p->S, c_tab);
   if (!lds) return RATO_EINVAL;
   static rato::DynamicLdsLimit lds_limit;
-  const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_batch_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
-  if (e != hipSuccess) return RATO_EHIP - (int)e;
-  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
-  hipLaunchKernelGGL(drone_tail_rows_rollout_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK),
-                     lds, st, *p, tab, stride, c_tab);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return launch_dynamic_lds(drone_tail_rows_rollout_batch_kernel, lds_limit, lds, lds,
+                            dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), st, *p, tab,
+                            (long)record_words(p->S), c_tab);
 }
 
 // rows: the union form's chunks (union_form; kn_max = the largest chunk) or one row per cut
@@ -1725,32 +1704,20 @@ int launch_drone_tail_kept_batch(const rato_drone_params* p, const BatchProb* ta
                                  bool union_form, int kn_max, hipStream_t st) {
   RATO_CLEAR_ERROR();
   if (!p || !tab || !rows || n_rows < 1 || n_rows > 65535 || p->S < 2 || kn_max < 1 || kn_max > TRU_KMAX) return RATO_EINVAL;
-  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
+  const long stride = record_words(p->S);
   const dim3 grid((unsigned)rato::nblocks_for(p->M), (unsigned)n_rows);
   if (union_form) {
     const size_t lds_u = tail_union_lds_bytes(p->S, kn_max);   // (the largest chunk's size; each row lays out its own)
     static rato::DynamicLdsLimit lds_limit_u;
-    const hipError_t e = lds_limit_u.ensure(lds_u, [](size_t bytes) {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_union_batch_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    });
-    if (e != hipSuccess) return RATO_EHIP - (int)e;
-    hipLaunchKernelGGL(drone_tail_rows_rollout_union_batch_kernel, grid, dim3(TRU_NW * RATO_WAVE), lds_u, st, *p, tab, rows, stride);
-    RATO_LAUNCH_CHECK();
-    return RATO_OK;
+    return launch_dynamic_lds(drone_tail_rows_rollout_union_batch_kernel, lds_limit_u, lds_u, lds_u, grid,
+                              dim3(TRU_NW * RATO_WAVE), st, *p, tab, rows, stride);
   }
   int c_tab = 0;
   const size_t lds = tail_rows_lds(p->S, c_tab);
   if (!lds) return RATO_EINVAL;
   static rato::DynamicLdsLimit lds_limit;
-  const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_tail_rows_rollout_kept_batch_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
-  if (e != hipSuccess) return RATO_EHIP - (int)e;
-  hipLaunchKernelGGL(drone_tail_rows_rollout_kept_batch_kernel, grid, dim3(RATO_BLOCK), lds, st, *p, tab, rows, stride, c_tab);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return launch_dynamic_lds(drone_tail_rows_rollout_kept_batch_kernel, lds_limit, lds, lds, grid, dim3(RATO_BLOCK), st, *p, tab,
+                            rows, stride, c_tab);
 }
 }  // namespace rato
 
@@ -1806,20 +1773,12 @@ extern "C" int rato_car_tail_rows_rollout(const rato_car_params* p, const double
       !stats_base || !part || K < 1 || K > 65535 || (!slots && K != 1) || stats_stride < 11)
     return RATO_EINVAL;
   const size_t lds = car_tail_rows_lds(p->S);
+  if (lds + 4096 > 160 * 1024) return RATO_EINVAL;   // (4 KB: the static lists of the tail compaction)
   static rato::DynamicLdsLimit limit;
-  if (lds + 4096 > 160 * 1024) return RATO_EINVAL;
-  {
-    const hipError_t e = limit.ensure(lds + 4096, [](size_t bytes) {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(car_tail_rows_rollout_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    });
-    if (e != hipSuccess) return RATO_EHIP - (int)e;
-  }
   dim3 grid((unsigned)rato::nblocks_for(p->M), (unsigned)K), block(RATO_BLOCK);
-  hipLaunchKernelGGL(car_tail_rows_rollout_kernel, grid, block, lds, rato::as_stream(stream), *p, uk, dW, x0_ped,
-                     w_speed, w_rep, m_base, arg_base, stats_base, (long)stats_stride, slots, alphaM, part);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return rato::launch_dynamic_lds(car_tail_rows_rollout_kernel, limit, lds + 4096, lds, grid, block, rato::as_stream(stream),
+                                  *p, uk, dW, x0_ped, w_speed, w_rep, m_base, arg_base, stats_base, (long)stats_stride, slots,
+                                  alphaM, part);
 }
 
 // ---- batched forms (cutloop.hip: rato_scp_batch_run_car): the two launches above over (sample blocks) x (table rows), the
@@ -1842,16 +1801,9 @@ int launch_car_tail_rows_batch(const rato_car_params* p, const BatchProb* tab, i
   const size_t lds = car_tail_rows_lds(p->S);
   if (lds + 4096 > 160 * 1024) return RATO_EINVAL;   // (4 KB: the static lists of the tail compaction)
   static rato::DynamicLdsLimit limit;
-  const hipError_t e = limit.ensure(lds + 4096, [](size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(car_tail_rows_rollout_batch_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
-  if (e != hipSuccess) return RATO_EHIP - (int)e;
-  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
-  hipLaunchKernelGGL(car_tail_rows_rollout_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK),
-                     lds, st, *p, tab, stride);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return launch_dynamic_lds(car_tail_rows_rollout_batch_kernel, limit, lds + 4096, lds,
+                            dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), st, *p, tab,
+                            (long)record_words(p->S));
 }
 
 int launch_car_tail_kept_batch(const rato_car_params* p, const BatchProb* tab, const BatchCut* rows, int n_rows,
@@ -1861,16 +1813,9 @@ int launch_car_tail_kept_batch(const rato_car_params* p, const BatchProb* tab, c
   const size_t lds = car_tail_rows_lds(p->S);
   if (lds + 4096 > 160 * 1024) return RATO_EINVAL;
   static rato::DynamicLdsLimit limit;
-  const hipError_t e = limit.ensure(lds + 4096, [](size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(car_tail_rows_rollout_kept_batch_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
-  if (e != hipSuccess) return RATO_EHIP - (int)e;
-  const long stride = RATO_N_STATS + 2 * (p->S - 1) + 1;
-  hipLaunchKernelGGL(car_tail_rows_rollout_kept_batch_kernel, dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n_rows),
-                     dim3(RATO_BLOCK), lds, st, *p, tab, rows, stride);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return launch_dynamic_lds(car_tail_rows_rollout_kept_batch_kernel, limit, lds + 4096, lds,
+                            dim3((unsigned)rato::nblocks_for(p->M), (unsigned)n_rows), dim3(RATO_BLOCK), st, *p, tab, rows,
+                            (long)record_words(p->S));
 }
 }  // namespace rato
 
@@ -1896,10 +1841,10 @@ extern "C" int rato_cut_oracle_rollout(int32_t system, const void* params, const
     S = p->S, n_u = 2, M = p->M;
   }
   if (S < 1 || M < 1) return RATO_EINVAL;
-  const int nc = 2 * (S - 1) + 1;
+  const int nres = rato::record_words(S), nc = nres - RATO_N_STATS;
   hipError_t e = hipSuccess;
   // read-back: the last launch writes the record into res_host (pinned) and the host watches it arrive (rato_common.h)
-  const int n_words = RATO_N_STATS + (S > 1 ? nc : 0);
+  const int n_words = S > 1 ? nres : RATO_N_STATS;
   if (rato::readback_poll_enabled()) rato::readback_arm(res_host, n_words);
   if (S * n_u > XARG_MAX) {   // long horizons: x goes through device memory; otherwise it rides in the kernel arguments
     e = hipMemcpyAsync(x_dev, x_host, sizeof(double) * (size_t)S * n_u, hipMemcpyHostToDevice, st);
@@ -1915,7 +1860,7 @@ extern "C" int rato_cut_oracle_rollout(int32_t system, const void* params, const
   if (rc != RATO_OK) return rc;
   if (S > 1) {
     if (!part_dev) return RATO_EINVAL;
-    const int64_t stride = RATO_N_STATS + nc;
+    const int64_t stride = nres;
     rc = system == 0 ? rato_drone_tail_rows_rollout(static_cast<const rato_drone_params*>(params), uk, s0, s1, s2, m_out,
                                                     arg_out, res_dev, stride, nullptr, 1, alphaM, part_dev, stream)
                      : rato_car_tail_rows_rollout(static_cast<const rato_car_params*>(params), uk, s0, s1, s2, s3, m_out,

@@ -273,6 +273,9 @@ struct BatchProb {
   double *res_dev, *res_host, *part;         // its record (device / pinned) and the tail's block partials
   double *part_b, *sums_b_host;              // kept cuts: block partials [nblk][n_keep nc], sums (pinned)
 };
+// doubles in one oracle record (a ring slot's statistics, the pinned read-back): [RATO_N_STATS statistics | the cut's 2 (S - 1)
+// row sums | its constant]
+inline int record_words(int S) { return RATO_N_STATS + 2 * (S - 1) + 1; }
 // one row of a batched kept-cuts launch: table row, first cut, cuts in this row, the problem's number of kept cuts
 struct BatchCut {
   int32_t prob, k0, kn, K;
@@ -362,5 +365,20 @@ class DynamicLdsLimit {
   std::mutex mu_;
   size_t set_[kMaxDev] = {};
 };
+
+// One launch of a kernel with dynamic LDS beyond what a kernel gets unasked: raise `kernel`'s limit to `raise_to` bytes
+// (`limit`: the launch site's own function-local static -- one per kernel symbol), launch with `lds` bytes, check the launch.
+// -> RATO status.
+template <class... Params, class... Args>
+int launch_dynamic_lds(void (*kernel)(Params...), DynamicLdsLimit& limit, size_t raise_to, size_t lds, dim3 grid, dim3 block,
+                       hipStream_t st, Args&&... args) {
+  const hipError_t e = limit.ensure(raise_to, [kernel](size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<Args&&>(args)...);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
 
 }  // namespace rato

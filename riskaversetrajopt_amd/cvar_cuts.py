@@ -470,6 +470,18 @@ class CvarCutSolver:
         out["n_keep"].value = K
         return out
 
+    def _follow_native(self, keep, idle, n_keep, done=None, us_hist=None, us0=None):
+        """The Python-side state follows the native one: the kept cuts ``keep`` / ``idle`` [>= n_keep] and -- after a native
+        SCP run of ``done`` iterations from ``us0`` with the solutions ``us_hist`` -- nothing in flight and the last
+        linearization point, so that a later solve_reduced continues from there."""
+        self.keep = [int(v) for v in keep[:n_keep]]
+        self.idle = {int(sl): int(c) for sl, c in zip(keep[:n_keep], idle[:n_keep])}
+        if done is None:
+            return
+        self._relin_pending = None
+        if done:
+            self.u_lin = (us_hist[done - 2] if done >= 2 else us0).reshape(-1).copy()
+
     def _solve_native(self, final_du, final_rhs, u_lin, with_cvar, tol, max_cuts, final_cut_above):
         """one rato_cut_solve call -> the same ``info`` dict as the Python loop below"""
         h = self._native_solver()
@@ -491,9 +503,7 @@ class CvarCutSolver:
             raise _lib.RatoNonFiniteError("CVaR-cut oracle: non-finite constraint values m_i(u) (RATO_ENONFINITE)")
         _lib.check(rc, "rato_cut_solve")
         if self.recycle and with_cvar:
-            K = out["n_keep"].value
-            self.keep = [int(v) for v in out["keep"][:K]]
-            self.idle = {int(sl): int(c) for sl, c in zip(out["keep"][:K], out["idle"][:K])}
+            self._follow_native(out["keep"], out["idle"], out["n_keep"].value)
         nb = res.n_bounds
         bounds = []
         if nb:       # grouped by sign run, as the Python loop reports them
@@ -679,6 +689,89 @@ class CvarCutSolver:
         return info
 
 
+def scp_run(lib, cs, us0, iters, run, what, check_finite):
+    """The native SCP loop of ONE problem behind ``drone_risk.Model.scp_run_native`` / ``driving.Model.scp_run_native``: runs
+    it on the solver's native handle and lets the solver's Python-side state follow the native one.
+    ``run(handle, keep, idle, n_keep, us_hist, rec, done, stream)`` -> status: the system's rato_scp_run_* with its own leading
+    arguments bound; ``what`` = (its name, what its define checks for finiteness), for error messages.
+    -> dict(us_hist (iters, S, n_u), define_s, solve_s, oracle_s, master_s, cuts, t_risk, slack, status), or None when the
+    native loop handed back (rank-deficient master, a selection that gave up): the caller runs the per-iteration loop."""
+    C = _lib.C
+    S, n_u = cs.S, cs.n_u
+    us0 = np.ascontiguousarray(us0, dtype=np.float64)
+    if us0.shape != (S, n_u):
+        raise ValueError(f"us0 must be ({S},{n_u}), got {us0.shape}")
+    h = cs._native_solver()
+    out = cs._keep_arrays()
+    assert C.sizeof(_lib.ScpIter) == lib.rato_scp_iter_bytes()
+    rec = (_lib.ScpIter * max(iters, 1))()
+    us_hist = np.zeros((max(iters, 1), S, n_u))
+    done = C.c_int32(0)
+    cs.check_finite = bool(check_finite)
+    rc = run(h, out["keep"].ctypes.data, out["idle"].ctypes.data, C.addressof(out["n_keep"]), us_hist.ctypes.data,
+             C.addressof(rec), C.addressof(done), _lib.current_stream())
+    cs._follow_native(out["keep"], out["idle"], out["n_keep"].value, done.value, us_hist, us0)
+    if rc in (_lib.RATO_ERANK, _lib.RATO_ESELECT):
+        _lib.synchronize()
+        return None
+    if rc == _lib.RATO_EINFEASIBLE:
+        raise dense_qp.InfeasibleError("master QP infeasible")
+    if rc == _lib.RATO_ENONFINITE:
+        raise _lib.RatoNonFiniteError(f"reduced SCP (native loop): non-finite {what[1]} / constraint values (RATO_ENONFINITE)")
+    _lib.check(rc, what[0])
+    recs = rec[:iters]
+    f = lambda k: np.array([getattr(r, k) for r in recs])
+    return {"us_hist": us_hist[:iters], "define_s": f("define_s"), "solve_s": f("solve_s"), "oracle_s": f("oracle_s"),
+            "master_s": f("master_s"), "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
+            "status": f("status").astype(np.int64)}
+
+
+def check_scp_batch(models, model_cls, what, same):
+    """ValueError unless ``models`` can share one native batch: Models of ``model_cls`` (``what`` = (what the batch covers,
+    what a Model must have materialised), for the messages) of method 'saa' on one GPU with S >= 2 that agree in ``same(model)`` -> ((S,
+    M, ...), further keys ...): what the library compares -- the shape first, then the rest of the parameter struct.
+    Nothing runs on the device here."""
+    if not models:
+        raise ValueError("an SCP batch needs at least one Model")
+    for k, m in enumerate(models):
+        if not isinstance(m, model_cls):
+            raise ValueError(f"problem {k}: {what[0]} only, got {type(m).__name__}")
+        if m.method != 'saa':
+            raise ValueError(f"problem {k}: the SCP batch covers method 'saa' only, got {m.method!r}")
+        if getattr(m, "_dW", None) is None or getattr(m, "_world", 1) != 1 or m.S < 2:
+            raise ValueError(f"problem {k}: the SCP batch needs {what[1]} on one GPU and S >= 2")
+        if os.environ.get("RATO_PY_CUT_LOOP") == "1":
+            raise ValueError("the SCP batch runs the native cut loop, which RATO_PY_CUT_LOOP=1 switches off")
+    key0 = same(models[0])
+    for k, m in enumerate(models):
+        key = same(m)
+        if key[0] != key0[0]:
+            raise ValueError(f"problem {k}: every problem of an SCP batch has the same S and M "
+                             f"(S={key[0][0]}, M={key[0][1]} against S={key0[0][0]}, M={key0[0][1]})")
+        if key != key0:
+            raise ValueError(f"problem {k}: every problem of an SCP batch has the same parameters (dt, beta, ego state ...)")
+        if m.device != models[0].device:
+            raise ValueError(f"problem {k}: every problem of an SCP batch is on one device")
+    if len({id(m) for m in models}) != len(models):
+        raise ValueError("a Model appears twice in the SCP batch")
+
+
+def scp_batch_inputs(models, us0, n_u):
+    """What ``drone_risk.scp_run_native_batch`` / ``driving.scp_run_native_batch`` hand to ``scp_batch_run`` after their
+    ``_check_batch`` -> (us0 [K][S][n_u] contiguous fp64, every Model's cut solver with its table-free oracle attached)."""
+    K, S = len(models), models[0].S
+    us0 = np.ascontiguousarray(us0, dtype=np.float64)
+    if us0.shape != (K, S, n_u):
+        raise ValueError(f"us0 must be ({K},{S},{n_u}), got {us0.shape}")
+    solvers = []
+    for k, m in enumerate(models):
+        cs = m._native_loop_solver()
+        if cs is None or not cs.native_loop_applies():
+            raise ValueError(f"problem {k}: its cut solver does not take the native loop")
+        solvers.append(cs)
+    return us0, solvers
+
+
 def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, check_finite=True):
     """The lockstep batch of reduced SCPs behind ``drone_risk.scp_run_native_batch`` / ``driving.scp_run_native_batch``:
     binds the solvers' native handles to one rato_scp_batch (its device and pinned buffers live for this call), runs it and
@@ -726,15 +819,8 @@ def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, che
     finally:
         lib.rato_scp_batch_destroy(h)
         del dev, host
-    # every solver's Python-side state follows its native one (a later solve_reduced continues from here)
     for k, cs in enumerate(solvers):
-        Kk = int(n_keep[k])
-        cs.keep = [int(v) for v in keep[k, :Kk]]
-        cs.idle = {int(sl): int(c) for sl, c in zip(keep[k, :Kk], idle[k, :Kk])}
-        cs._relin_pending = None
-        n = int(done[k])
-        if n:
-            cs.u_lin = (us_hist[k, n - 2] if n >= 2 else us0[k]).reshape(-1).copy()   # the last linearization point
+        cs._follow_native(keep[k], idle[k], int(n_keep[k]), int(done[k]), us_hist[k], us0[k])
     _lib.check(rc, what)
     it = int(iters)
     f = lambda key: np.array([[getattr(rec[k * n_it + i], key) for i in range(it)] for k in range(K)]).reshape(K, it)

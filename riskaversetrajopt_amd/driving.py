@@ -6,13 +6,13 @@ with its sample-axis hot path on the MI355X.
 reference fixes S as a module constant; here it is a keyword (default 20).
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
 from . import _lib, assemble, cvar_cuts, qp, stats
 from . import driving_params as P
+from .scp import L2_error_us  # noqa: F401  (the reference's module-level name, driving.py:459-464)
 
 n_x, n_u = P.n_x, P.n_u
 OSQP_TOL = P.OSQP_TOL
@@ -656,49 +656,18 @@ class Model:
     def scp_run_native(self, us0, iters, first_cvar=1, tol=1e-9, max_cuts=400, final_cut_above=1e-11):
         """The whole reduced SCP as ONE library call (rato_scp_run_car: ``iters`` x [final rows, begin, solve] with the
         per-iteration clocks of the reference's protocol taken natively), as ``drone_risk.Model.scp_run_native``.
-        -> dict(us_hist (iters, S, n_u), define_s, solve_s, oracle_s, cuts, t_risk, status) or None when the configuration
+        -> the dict of ``cvar_cuts.scp_run`` or None when the configuration
         is not the native one (no materialised dW, sharded, S < 2, a cut solver that keeps the Python loop) / the native
         loop handed back (rank-deficient master, a selection that gave up): the caller then runs the per-iteration loop."""
         cs = self._native_loop_solver()
         if cs is None or not cs.native_loop_applies():
             return None
-        S = self.S
         us0 = np.ascontiguousarray(us0, dtype=np.float64)
-        if us0.shape != (S, n_u):
-            raise ValueError(f"us0 must be ({S},{n_u}), got {us0.shape}")
-        h = cs._native_solver()
-        out = cs._keep_arrays()
-        assert C.sizeof(_lib.ScpIter) == self._lib.rato_scp_iter_bytes()
-        rec = (_lib.ScpIter * max(iters, 1))()
-        us_hist = np.zeros((max(iters, 1), S, n_u))
-        done = C.c_int32(0)
         goal = self._goal64()
-        cs.check_finite = bool(self.check_finite)
-        rc = self._lib.rato_scp_run_car(
+        run = lambda h, *tail: self._lib.rato_scp_run_car(
             h, us0.ctypes.data, goal.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts),
-            float(final_cut_above), int(bool(self.check_finite)), out["keep"].ctypes.data, out["idle"].ctypes.data,
-            C.addressof(out["n_keep"]), us_hist.ctypes.data, C.addressof(rec), C.addressof(done), _lib.current_stream())
-        # the solver's Python-side state follows the native one (a later solve_reduced continues from here)
-        K = out["n_keep"].value
-        cs.keep = [int(v) for v in out["keep"][:K]]
-        cs.idle = {int(sl): int(c) for sl, c in zip(out["keep"][:K], out["idle"][:K])}
-        cs._relin_pending = None
-        n = done.value
-        if n:
-            cs.u_lin = (us_hist[n - 2] if n >= 2 else us0).reshape(-1).copy()      # the last linearization point
-        if rc in (_lib.RATO_ERANK, _lib.RATO_ESELECT):
-            _lib.synchronize()
-            return None
-        if rc == _lib.RATO_EINFEASIBLE:
-            raise cvar_cuts.dense_qp.InfeasibleError("master QP infeasible")
-        if rc == _lib.RATO_ENONFINITE:
-            raise _lib.RatoNonFiniteError("reduced SCP (native loop): non-finite final rows / constraint values (RATO_ENONFINITE)")
-        _lib.check(rc, "rato_scp_run_car")
-        recs = rec[:iters]
-        f = lambda k: np.array([getattr(r, k) for r in recs])
-        return {"us_hist": us_hist[:iters], "define_s": f("define_s"), "solve_s": f("solve_s"), "oracle_s": f("oracle_s"),
-                "master_s": f("master_s"), "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
-                "status": f("status").astype(np.int64)}
+            float(final_cut_above), int(bool(self.check_finite)), *tail)
+        return cvar_cuts.scp_run(self._lib, cs, us0, iters, run, ("rato_scp_run_car", "final rows"), self.check_finite)
 
     def certify_reduced(self, info):
         """Matrix-free KKT certificate of the last ``solve_reduced`` (table-free oracle, an iteration with the CVaR rows)
@@ -717,47 +686,15 @@ class Model:
         Zh = Z.double().cpu().numpy()
         return Zh <= 1e-6, Zh
 
-    def monte_carlo_statistics(self, us_mat, alpha=None):
-        """rollout -> Z -> fraction satisfied, VaR, CVaR (``mc_step_device``); a NaN record on finite Z is recovered
-        through ``stats.risk_stats``."""
-        alpha = self.alpha if alpha is None else alpha
-        Z, rec = self.mc_step_device(us_mat, alpha)
-        r = rec.cpu().numpy()
-        if np.isnan(r[0]):
-            return stats.risk_stats(Z, alpha)
-        return dict(zip(stats._STAT_NAMES, r.tolist()))
-
+    monte_carlo_statistics = stats.monte_carlo_statistics
     monte_carlo_avar = staticmethod(stats.monte_carlo_avar)
 
 
 def _check_batch(models):
     """ValueError unless the Models can share one native batch (rato_scp_batch_run_car): driving Models of method 'saa' with
     a materialised dW on one GPU, one S, one M and the same parameter bytes.  Nothing runs on the device here."""
-    if not models:
-        raise ValueError("an SCP batch needs at least one Model")
-    for k, m in enumerate(models):
-        if not isinstance(m, Model):
-            raise ValueError(f"problem {k}: the driving SCP batch covers driving.Model only, got {type(m).__name__}")
-        if m.method != 'saa':
-            raise ValueError(f"problem {k}: the SCP batch covers method 'saa' only, got {m.method!r}")
-        if getattr(m, "_dW", None) is None or getattr(m, "_world", 1) != 1 or m.S < 2:
-            raise ValueError(f"problem {k}: the SCP batch needs a materialised dW on one GPU and S >= 2")
-        if os.environ.get("RATO_PY_CUT_LOOP") == "1":
-            raise ValueError("the SCP batch runs the native cut loop, which RATO_PY_CUT_LOOP=1 switches off")
-    m0 = models[0]
-    M0 = int(m0._ws.numel())
-    p0 = bytes(m0._params(M0))
-    for k, m in enumerate(models):
-        M = int(m._ws.numel())
-        if (m.S, M) != (m0.S, M0):
-            raise ValueError(f"problem {k}: every problem of an SCP batch has the same S and M "
-                             f"(S={m.S}, M={M} against S={m0.S}, M={M0})")
-        if bytes(m._params(M)) != p0:
-            raise ValueError(f"problem {k}: every problem of an SCP batch has the same parameters (dt, beta, ego state ...)")
-        if m.device != m0.device:
-            raise ValueError(f"problem {k}: every problem of an SCP batch is on one device")
-    if len({id(m) for m in models}) != len(models):
-        raise ValueError("a Model appears twice in the SCP batch")
+    cvar_cuts.check_scp_batch(models, Model, ("the driving SCP batch covers driving.Model", "a materialised dW"),
+                              lambda m: ((m.S, int(m._ws.numel())), bytes(m._params(int(m._ws.numel())))))
 
 
 def scp_run_native_batch(models, us0, iters, first_cvar=1, tol=1e-9, max_cuts=400, final_cut_above=1e-11, n_threads=16,
@@ -769,16 +706,7 @@ def scp_run_native_batch(models, us0, iters, first_cvar=1, tol=1e-9, max_cuts=40
     device work) for what the batch does not cover.  -> the dict of ``cvar_cuts.scp_batch_run``."""
     models = list(models)
     _check_batch(models)
-    K, S = len(models), models[0].S
-    us0 = np.ascontiguousarray(us0, dtype=np.float64)
-    if us0.shape != (K, S, n_u):
-        raise ValueError(f"us0 must be ({K},{S},{n_u}), got {us0.shape}")
-    solvers = []
-    for k, m in enumerate(models):
-        cs = m._native_loop_solver()
-        if cs is None or not cs.native_loop_applies():
-            raise ValueError(f"problem {k}: its cut solver does not take the native loop")
-        solvers.append(cs)
+    us0, solvers = cvar_cuts.scp_batch_inputs(models, us0, n_u)
     lib = models[0]._lib
     goal = models[0]._goal64()
     run = lambda h, *tail: lib.rato_scp_batch_run_car(
@@ -786,9 +714,3 @@ def scp_run_native_batch(models, us0, iters, first_cvar=1, tol=1e-9, max_cuts=40
         int(bool(check_finite)), *tail)
     return cvar_cuts.scp_batch_run(lib, models[0].device, solvers, us0, iters, run, "rato_scp_batch_run_car",
                                    n_threads=n_threads, check_finite=check_finite)
-
-
-def L2_error_us(us_mat, us_mat_prev):
-    """driving.py:459-464."""
-    error = np.mean(np.linalg.norm(us_mat - us_mat_prev, axis=-1))
-    return error / np.mean(np.linalg.norm(us_mat, axis=-1))

@@ -9,13 +9,13 @@ Host-facing methods return NumPy arrays in the reference's shapes; ``*_device``
 methods return the kernels' SoA tensors (sample index fastest).
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
 from . import _lib, assemble, cvar_cuts, qp, stats
 from . import drone_params as P
+from .scp import L2_error_us  # noqa: F401  (the reference's module-level name, drone_risk.py:471-476)
 
 n_x, n_u, n_obs = P.n_x, P.n_u, P.n_obs
 OSQP_TOL = P.OSQP_TOL
@@ -759,12 +759,8 @@ class Model:
         world = getattr(self, "_world", 1)
         if rollout and world == 1 and not verbose:
             # the benchmarked configuration: define (rato_cut_define_drone) and solve (rato_cut_solve) are one native call each
-            cs = self._reduced_cut_solver(int(self._inputs(None)[3]), mass.numel())
-            cs.implicit = None
-            rp = getattr(self, "_rollout_params", None)      # (built once: ~20 us of ctypes field stores per call otherwise)
-            if rp is None or rp[0] != (cs.M, mass.numel()):
-                rp = self._rollout_params = ((cs.M, mass.numel()), self._params(cs.M, mass.numel()))
-            cs.rollout = ("drone", rp[1], dW, mass, Qsym)
+            cs = self._native_loop_solver(min_S=1)       # (the SCP loops need S >= 2; one define + solve runs at S = 1 too)
+            assert cs is not None                        # rollout: dW is materialised; world == 1; S >= 1
             cs.check_finite = False
             if cs.native_loop_applies():
                 return self._solve_reduced_native(cs, us_mat_p, scp_iter, tol)
@@ -879,68 +875,29 @@ class Model:
     def scp_run_native(self, us0, iters, first_cvar=2, tol=1e-9, max_cuts=400, final_cut_above=1e-11):
         """The whole reduced SCP as ONE library call (rato_scp_run_drone: ``iters`` x [define, solve] with the per-iteration
         clocks of the reference's protocol taken natively) -- for the configuration ``solve_reduced`` runs natively (table-free
-        oracle, one GPU).  -> dict(us_hist (iters, S, n_u), define_s, solve_s, oracle_s, cuts, t_risk, status) or None when the
-        configuration is not the native one / the native loop handed back (rank-deficient master, a selection that gave
-        up): the caller then runs the per-iteration loop."""
-        dW, mass, Qsym, _ = self._inputs(None)
-        if dW is None or getattr(self, "_world", 1) != 1 or self.S < 2:
+        oracle, one GPU).  -> the dict of ``cvar_cuts.scp_run`` or None when the configuration is not the native one / the
+        native loop handed back (rank-deficient master, a selection that gave up): the caller then runs the per-iteration
+        loop."""
+        cs = self._native_loop_solver()
+        if cs is None or not cs.native_loop_applies():
             return None
-        cs = self._reduced_cut_solver(int(self._inputs(None)[3]), mass.numel())
-        cs.implicit = None
-        rp = getattr(self, "_rollout_params", None)
-        if rp is None or rp[0] != (cs.M, mass.numel()):
-            rp = self._rollout_params = ((cs.M, mass.numel()), self._params(cs.M, mass.numel()))
-        cs.rollout = ("drone", rp[1], dW, mass, Qsym)
-        if not cs.native_loop_applies():
-            return None
-        S = self.S
         b = self._native_define_buffers(cs)
         us0 = np.ascontiguousarray(us0, dtype=np.float64)
-        if us0.shape != (S, n_u):
-            raise ValueError(f"us0 must be ({S},{n_u}), got {us0.shape}")
-        h = cs._native_solver()
-        out = cs._keep_arrays()
-        assert C.sizeof(_lib.ScpIter) == self._lib.rato_scp_iter_bytes()
-        rec = (_lib.ScpIter * max(iters, 1))()
-        us_hist = np.zeros((max(iters, 1), S, n_u))
-        done = C.c_int32(0)
-        cs.check_finite = bool(self.check_finite)
-        rc = self._lib.rato_scp_run_drone(
+        run = lambda h, *tail: self._lib.rato_scp_run_drone(
             h, us0.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
             int(bool(self.check_finite)), b["us_host"].data_ptr(), b["us_dev"].data_ptr(), b["A22"].data_ptr(),
-            b["part"].data_ptr(), b["sums_host"].data_ptr(), out["keep"].ctypes.data, out["idle"].ctypes.data,
-            C.addressof(out["n_keep"]), us_hist.ctypes.data, C.addressof(rec), C.addressof(done), _lib.current_stream())
-        # the solver's Python-side state follows the native one (a later solve_reduced continues from here)
-        K = out["n_keep"].value
-        cs.keep = [int(v) for v in out["keep"][:K]]
-        cs.idle = {int(sl): int(c) for sl, c in zip(out["keep"][:K], out["idle"][:K])}
-        cs._relin_pending = None
-        n = done.value
-        if n:
-            cs.u_lin = (us_hist[n - 2] if n >= 2 else us0).reshape(-1).copy()      # the last linearization point
-        if rc in (_lib.RATO_ERANK, _lib.RATO_ESELECT):
-            _lib.synchronize()
-            return None
-        if rc == _lib.RATO_EINFEASIBLE:
-            raise cvar_cuts.dense_qp.InfeasibleError("master QP infeasible")
-        if rc == _lib.RATO_ENONFINITE:
-            raise _lib.RatoNonFiniteError("reduced SCP (native loop): non-finite sample sums / constraint values (RATO_ENONFINITE)")
-        _lib.check(rc, "rato_scp_run_drone")
-        recs = rec[:iters]
-        f = lambda k: np.array([getattr(r, k) for r in recs])
-        return {"us_hist": us_hist[:iters], "define_s": f("define_s"), "solve_s": f("solve_s"), "oracle_s": f("oracle_s"),
-                "master_s": f("master_s"), "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
-                "status": f("status").astype(np.int64)}
+            b["part"].data_ptr(), b["sums_host"].data_ptr(), *tail)
+        return cvar_cuts.scp_run(self._lib, cs, us0, iters, run, ("rato_scp_run_drone", "sample sums"), self.check_finite)
 
-    def _native_loop_solver(self):
-        """the cut solver of the native SCP loop with its table-free oracle attached, or None where that loop does not
-        apply (no materialised dW, sharded, S < 2)"""
-        dW, mass, Qsym, _ = self._inputs(None)
-        if dW is None or getattr(self, "_world", 1) != 1 or self.S < 2:
+    def _native_loop_solver(self, min_S=2):
+        """the cut solver with its table-free oracle attached -- the one place that does so -- or None where the native loops
+        do not apply (no materialised dW, sharded, S < ``min_S``: 2 for the SCP loops, 1 for a single define + solve)"""
+        dW, mass, Qsym, M = self._inputs(None)
+        if dW is None or getattr(self, "_world", 1) != 1 or self.S < min_S:
             return None
-        cs = self._reduced_cut_solver(int(self._inputs(None)[3]), mass.numel())
+        cs = self._reduced_cut_solver(int(M), mass.numel())
         cs.implicit = None
-        rp = getattr(self, "_rollout_params", None)
+        rp = getattr(self, "_rollout_params", None)      # (built once: ~20 us of ctypes field stores per call otherwise)
         if rp is None or rp[0] != (cs.M, mass.numel()):
             rp = self._rollout_params = ((cs.M, mass.numel()), self._params(cs.M, mass.numel()))
         cs.rollout = ("drone", rp[1], dW, mass, Qsym)
@@ -963,17 +920,7 @@ class Model:
         Zh = Z.double().cpu().numpy()
         return Zh <= 1e-6, Zh
 
-    def monte_carlo_statistics(self, us_mat, alpha=None):
-        """Fused device path: rollout -> Z -> fraction satisfied, VaR, CVaR (``mc_step_device``: one call, for small
-        batches one launch).  A NaN record on finite Z (a one-launch selection that gave up) is recovered through
-        ``stats.risk_stats``."""
-        alpha = self.alpha if alpha is None else alpha
-        Z, rec = self.mc_step_device(us_mat, alpha)
-        r = rec.cpu().numpy()
-        if np.isnan(r[0]):
-            return stats.risk_stats(Z, alpha)
-        return dict(zip(stats._STAT_NAMES, r.tolist()))
-
+    monte_carlo_statistics = stats.monte_carlo_statistics
     monte_carlo_avar = staticmethod(stats.monte_carlo_avar)
     monte_carlo_var = staticmethod(stats.monte_carlo_var)
 
@@ -994,26 +941,8 @@ class StepGraph:
 def _check_batch(models):
     """ValueError unless the Models can share one native batch (rato_scp_batch_run_drone): drone Models of method 'saa' with
     materialised samples on one GPU, one S, one M and one row stride.  Nothing runs on the device here."""
-    if not models:
-        raise ValueError("an SCP batch needs at least one Model")
-    for k, m in enumerate(models):
-        if not isinstance(m, Model):
-            raise ValueError(f"problem {k}: the SCP batch covers the drone (drone_risk.Model) only, got {type(m).__name__}")
-        if m.method != 'saa':
-            raise ValueError(f"problem {k}: the SCP batch covers method 'saa' only, got {m.method!r}")
-        if getattr(m, "_dW", None) is None or getattr(m, "_world", 1) != 1 or m.S < 2:
-            raise ValueError(f"problem {k}: the SCP batch needs materialised samples on one GPU and S >= 2")
-        if os.environ.get("RATO_PY_CUT_LOOP") == "1":
-            raise ValueError("the SCP batch runs the native cut loop, which RATO_PY_CUT_LOOP=1 switches off")
-    m0 = models[0]
-    for k, m in enumerate(models):
-        if (m.S, m.M, m._mass.numel(), m.dt) != (m0.S, m0.M, m0._mass.numel(), m0.dt):
-            raise ValueError(f"problem {k}: every problem of an SCP batch has the same S and M "
-                             f"(S={m.S}, M={m.M} against S={m0.S}, M={m0.M})")
-        if m.device != m0.device:
-            raise ValueError(f"problem {k}: every problem of an SCP batch is on one device")
-    if len({id(m) for m in models}) != len(models):
-        raise ValueError("a Model appears twice in the SCP batch")
+    cvar_cuts.check_scp_batch(models, Model, ("the SCP batch covers the drone (drone_risk.Model)", "materialised samples"),
+                              lambda m: ((m.S, m.M, m._mass.numel(), m.dt),))
 
 
 def scp_run_native_batch(models, us0, iters, first_cvar=2, tol=1e-9, max_cuts=400, final_cut_above=1e-11, n_threads=16,
@@ -1022,30 +951,13 @@ def scp_run_native_batch(models, us0, iters, first_cvar=2, tol=1e-9, max_cuts=40
     one batched define and rounds of one batched oracle round trip for every problem still cutting, the host masters on up
     to ``n_threads`` threads.  Each Model brings its own cut solver (its samples, alpha, rings and kept cuts) and leaves it as
     ``scp_run_native`` would; ``us0`` [K][S][3].  ValueError (before any device work) for what the batch does not cover.
-    -> dict(us_hist (K, iters, S, n_u), cuts / t_risk / slack / status / master_s (K, iters), status (K) (RATO_* per
-    problem), done (K), rounds, and the batch-level clocks define_s / oracle_s / master_s / total_s / rounds_per_iter
-    (iters))"""
+    -> the dict of ``cvar_cuts.scp_batch_run``."""
     models = list(models)
     _check_batch(models)
-    K, S = len(models), models[0].S
-    us0 = np.ascontiguousarray(us0, dtype=np.float64)
-    if us0.shape != (K, S, n_u):
-        raise ValueError(f"us0 must be ({K},{S},{n_u}), got {us0.shape}")
-    solvers = []
-    for k, m in enumerate(models):
-        cs = m._native_loop_solver()
-        if cs is None or not cs.native_loop_applies():
-            raise ValueError(f"problem {k}: its cut solver does not take the native loop")
-        solvers.append(cs)
+    us0, solvers = cvar_cuts.scp_batch_inputs(models, us0, n_u)
     lib = models[0]._lib
     run = lambda h, *tail: lib.rato_scp_batch_run_drone(
         h, us0.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
         int(bool(check_finite)), *tail)
     return cvar_cuts.scp_batch_run(lib, models[0].device, solvers, us0, iters, run, "rato_scp_batch_run_drone",
                                    n_threads=n_threads, check_finite=check_finite)
-
-
-def L2_error_us(us_mat, us_mat_prev):
-    """drone_risk.py:471-476."""
-    error = np.mean(np.linalg.norm(us_mat - us_mat_prev, axis=-1))
-    return error / np.mean(np.linalg.norm(us_mat, axis=-1))

@@ -12,6 +12,7 @@ import numpy as np
 
 
 def L2_error_us(us_mat, us_mat_prev):
+    """drone_risk.py:471-476, driving.py:459-464 (both Model modules carry it under this name)."""
     error = np.mean(np.linalg.norm(us_mat - us_mat_prev, axis=-1))
     return error / np.mean(np.linalg.norm(us_mat, axis=-1))
 
@@ -237,16 +238,22 @@ def drone_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3), num_repeats=30, M=50, S=2
     (``monte_carlo_report``), with ``results_dir`` the reference's result files drone_alpha=<alpha>_repeat=<r>.npy (us, then
     xs: ``save_results``).  -> dict(alphas, results [alpha][repeat] (the run_drone_reduced_batch dicts), us (A, R, S, 3),
     reports {alpha: report} (with mc_model), rounds, wall_s)"""
-    import time as _time
     from . import drone_risk
     batches = draw_saa_batches(num_repeats, M, S, seed)
     alphas = [float(a) for a in alphas]
     models = [drone_risk.Model(S, *batches[r], 'saa', a, device=device) for a in alphas for r in range(num_repeats)]
+    return _saa_experiment(models, run_drone_reduced_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir,
+                           "drone")
+
+
+def _saa_experiment(models, run_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir, name):
+    """drone_saa_experiment / driving_saa_experiment once the alpha-major grid of ``models`` is built: ONE batched solve
+    (``run_batch``), the result files <name>_alpha=<alpha>_repeat=<r>.npy and the Monte-Carlo reports"""
     _sync()
-    t0 = _time.perf_counter()
-    res = run_drone_reduced_batch(models, num_scp_iters_max=iters, n_threads=n_threads)
+    t0 = time.perf_counter()
+    res = run_batch(models, num_scp_iters_max=iters, n_threads=n_threads)
     _sync()
-    wall = _time.perf_counter() - t0
+    wall = time.perf_counter() - t0
     grid = [[res[i * num_repeats + r] for r in range(num_repeats)] for i in range(len(alphas))]
     us = np.stack([np.stack([g["us"] for g in row]) for row in grid])
     out = {"alphas": alphas, "results": grid, "us": us, "rounds": res[0].get("rounds"), "wall_s": wall, "models": models}
@@ -254,10 +261,9 @@ def drone_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3), num_repeats=30, M=50, S=2
         os.makedirs(results_dir, exist_ok=True)
         for i, a in enumerate(alphas):
             for r in range(num_repeats):
-                m = models[i * num_repeats + r]
-                xs = m.us_to_state_trajectories(us[i, r])
+                xs = models[i * num_repeats + r].us_to_state_trajectories(us[i, r])
                 xs = xs.cpu().numpy() if hasattr(xs, "cpu") else np.asarray(xs)
-                save_results(os.path.join(results_dir, f"drone_alpha={a}_repeat={r}.npy"), us[i, r], xs)
+                save_results(os.path.join(results_dir, f"{name}_alpha={a}_repeat={r}.npy"), us[i, r], xs)
     if mc_model is not None:
         out["reports"] = {a: monte_carlo_report(mc_model, list(us[i]), a) for i, a in enumerate(alphas)}
     return out
@@ -355,29 +361,13 @@ def driving_saa_experiment(alphas=(0.01, 0.02, 0.05, 0.1), num_repeats=30, M=50,
     the Monte-Carlo report per alpha, with ``results_dir`` the reference's result files driving_alpha=<alpha>_repeat=<r>.npy
     (us, then xs).  -> dict(alphas, results [alpha][repeat], us (A, R, S, 2), reports {alpha: report} (with mc_model), rounds,
     wall_s, models)"""
-    import time as _time
     from . import driving
     alphas = [float(a) for a in alphas]
     draws = draw_driving_saa_batches(alphas, num_repeats, M, S, seed)
     models = [driving.Model(M, 'saa', a, S=S, device=device, samples=draws[i][r])
               for i, a in enumerate(alphas) for r in range(num_repeats)]
-    _sync()
-    t0 = _time.perf_counter()
-    res = run_driving_reduced_batch(models, num_scp_iters_max=iters, n_threads=n_threads)
-    _sync()
-    wall = _time.perf_counter() - t0
-    grid = [[res[i * num_repeats + r] for r in range(num_repeats)] for i in range(len(alphas))]
-    us = np.stack([np.stack([g["us"] for g in row]) for row in grid])
-    out = {"alphas": alphas, "results": grid, "us": us, "rounds": res[0].get("rounds"), "wall_s": wall, "models": models}
-    if results_dir is not None:
-        os.makedirs(results_dir, exist_ok=True)
-        for i, a in enumerate(alphas):
-            for r in range(num_repeats):
-                xs = models[i * num_repeats + r].us_to_state_trajectories(us[i, r])
-                save_results(os.path.join(results_dir, f"driving_alpha={a}_repeat={r}.npy"), us[i, r], np.asarray(xs))
-    if mc_model is not None:
-        out["reports"] = {a: monte_carlo_report(mc_model, list(us[i]), a) for i, a in enumerate(alphas)}
-    return out
+    return _saa_experiment(models, run_driving_reduced_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir,
+                           "driving")
 
 
 def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
@@ -388,6 +378,15 @@ def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
     model has the batched entry point (drone, driving: ``Model.eval_batch_device``), one rollout kernel + one exact selection
     per solution otherwise; all on the device.  -> dict of per-solution arrays and the aggregates."""
     frac, avar, var, cost = [], [], [], []
+
+    def _append(st, us):
+        frac.append(st["frac_satisfied"])
+        avar.append(st["cvar"])
+        var.append(st["var"])
+        cost.append(mc_model.monte_carlo_cost(us))
+        if verbose:
+            print("B_satisfied_vec =", frac[-1])
+
     batched = getattr(mc_model, "eval_batch_device", None)
     if batched is not None and len(us_list) > 1 and getattr(mc_model, "_dW", None) is not None:
         # all repeats of this alpha in ONE call (rato_*_eval_batch: one rollout launch over tiles x K, one launch of K
@@ -400,21 +399,10 @@ def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
             st = dict(zip(names, rec[k].tolist()))
             if np.isnan(st["var"]):                    # (a selection that gave up: the recovering per-solution path)
                 st = mc_model.monte_carlo_statistics(us, alpha=alpha)
-            frac.append(st["frac_satisfied"])
-            avar.append(st["cvar"])
-            var.append(st["var"])
-            cost.append(mc_model.monte_carlo_cost(us))
-            if verbose:
-                print("B_satisfied_vec =", frac[-1])
+            _append(st, us)
         us_list = []
     for us in us_list:
-        st = mc_model.monte_carlo_statistics(us, alpha=alpha)
-        frac.append(st["frac_satisfied"])
-        avar.append(st["cvar"])
-        var.append(st["var"])
-        cost.append(mc_model.monte_carlo_cost(us))
-        if verbose:
-            print("B_satisfied_vec =", frac[-1])
+        _append(mc_model.monte_carlo_statistics(us, alpha=alpha), us)
     out = {"frac_satisfied": np.array(frac), "avar": np.array(avar), "var": np.array(var), "cost": np.array(cost)}
     for k in ("frac_satisfied", "avar", "cost"):
         out[k + "_mean"], out[k + "_median"] = float(np.mean(out[k])), float(np.median(out[k]))

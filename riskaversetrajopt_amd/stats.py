@@ -123,6 +123,18 @@ def risk_stats(Z, alpha, thr=SATISFIED_THRESHOLD, workspace=None):
     return dict(zip(_STAT_NAMES, out.tolist()))
 
 
+def monte_carlo_statistics(model, us_mat, alpha=None):
+    """``Model.monte_carlo_statistics`` of the drone and the driving problem -- fused device path: rollout -> Z -> fraction
+    satisfied, VaR, CVaR (``model.mc_step_device``: one call, for small batches one launch).  A NaN record on finite Z (a
+    one-launch selection that gave up) is recovered through ``risk_stats``."""
+    alpha = model.alpha if alpha is None else alpha
+    Z, rec = model.mc_step_device(us_mat, alpha)
+    r = rec.cpu().numpy()
+    if np.isnan(r[0]):
+        return risk_stats(Z, alpha)
+    return dict(zip(_STAT_NAMES, r.tolist()))
+
+
 def monte_carlo_var(Z_samples, alpha):
     """drone_main_plot.py:640-652."""
     return risk_stats(Z_samples, alpha)["var"]

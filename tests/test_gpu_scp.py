@@ -1064,3 +1064,47 @@ def test_native_solver_is_rebuilt_when_its_parameter_struct_changes_in_place():
     cs.keep_max = cs.keep_max - 1
     cs._native_solver()
     assert cs._native[0] != key_before
+
+
+def test_bad_kept_cut_arguments_are_rejected_before_any_launch():
+    """rato_cut_begin and rato_cut_define_drone share one validation of the kept cuts (csrc/cutloop.hip: keep_args_ok): a
+    count beyond keep_max, a negative count, a count without slots and a slot that is the ring's scratch slot (cap - 1) are
+    each RATO_EINVAL, answered before anything is staged or launched -- the solver's state is untouched and the next
+    solve_reduced gives the iterate of a twin Model that never saw the bad calls, to the bit.  M = 50, S = 20 (the
+    reference's size: one sample block, inputs staged through kernel arguments); two relaxed iterations, then two with the
+    CVaR rows, leave kept cuts behind."""
+    from riskaversetrajopt_amd import _lib
+    RATO_EINVAL = -1                                          # rato_saa.h
+
+    def prepared():
+        d = _drone(50, 20, alpha=0.1, seed=4)[1]
+        us = d.initial_guess_us_mat()
+        for k in range(4):
+            us, _, _ = d.solve_reduced(us, k)
+        return d, us
+    (a, us_a), (b, us_b) = prepared(), prepared()
+    cs = a._cut_solver
+    assert np.array_equal(us_a, us_b) and len(cs.keep) > 0 and cs.S >= 2
+    buf = a._native_define_buffers(cs)
+    h, out = cs._native_solver(), cs._keep_arrays()
+    K = len(cs.keep)
+    u = np.ascontiguousarray(us_a, dtype=np.float64)
+    good = out["keep"].copy()
+    scratch = good.copy()
+    scratch[K - 1] = cs.cap - 1
+    state = lambda: (cs._native[0], cs._native[1].value, list(cs.keep), dict(cs.idle), cs._relin_pending,
+                     out["keep"].tolist(), out["idle"].tolist(), out["n_keep"].value, cs.u_lin.tolist())
+    before = state()
+    st = _lib.current_stream()
+    for keep, n_keep in ((good, cs.keep_max + 1), (good, -1), (None, 1), (scratch, K)):
+        kp = None if keep is None else keep.ctypes.data
+        assert a._lib.rato_cut_begin(h, u.ctypes.data, kp, n_keep, st) == RATO_EINVAL
+        assert state() == before
+        rc = a._lib.rato_cut_define_drone(h, u.ctypes.data, buf["us_host"].data_ptr(), buf["us_dev"].data_ptr(),
+                                          buf["A22"].data_ptr(), None, 0, buf["part"].data_ptr(), buf["sums_host"].data_ptr(),
+                                          None, None, kp, n_keep, st)
+        assert rc == RATO_EINVAL
+        assert state() == before
+    ua, ta, ia = a.solve_reduced(us_a, 4)
+    ub, tb, ib = b.solve_reduced(us_b, 4)
+    assert np.array_equal(ua, ub) and ta == tb and ia["cuts"] == ib["cuts"] and ia["loop"] == ib["loop"] == "native"

@@ -80,3 +80,17 @@ def test_batch_rejects_a_driving_model_before_device_work():
         scp.run_drone_reduced_batch([object()], num_scp_iters_max=1)
     with pytest.raises(ValueError):
         scp.run_drone_reduced_batch([], num_scp_iters_max=1)
+
+
+@pytest.mark.parametrize("system", ["drone_risk", "driving"])
+def test_check_batch_and_l2_error_are_shared_by_both_systems(system):
+    """both Model modules keep ``_check_batch`` (one body, cvar_cuts.check_scp_batch) and the reference's module-level
+    ``L2_error_us`` (one definition, scp.py); no device is touched"""
+    import importlib
+    from riskaversetrajopt_amd import scp
+    mod = importlib.import_module("riskaversetrajopt_amd." + system)
+    with pytest.raises(ValueError, match="at least one"):
+        mod._check_batch([])
+    with pytest.raises(ValueError, match=system.split("_")[0]):
+        mod._check_batch([object()])
+    assert mod.L2_error_us is scp.L2_error_us
