@@ -249,6 +249,39 @@ int rato_drone_eval_batch(const rato_drone_params* p, int32_t K, const float* us
                           const float* Qsym, float* Z, int64_t ldz, double alpha, float thr, void* workspace,
                           size_t workspace_bytes, double* stats_out, void* stream);
 /* (driving: rato_car_eval_batch, below) */
+
+/*
+ * The obstacle metric of an evaluation (ABI 12, additive).  The paper's main figure (drone_main_plot.py) validates with
+ * the EUCLIDEAN form of the ellipsoid constraint, g = 1 - sqrt((p-o)' Q (p-o)) (:198-208), where drone_risk.py:170-180
+ * uses the quadratic form g = 1 - (p-o)' Q (p-o).  Both have the same sign; the Euclidean one measures the clearance
+ * in units of the ellipsoid's radius, which is what the figure's histogram shows.
+ *   metric 1: a = (p-o)' Q (p-o) by the instructions of metric 0, then g = 1.0f - sqrtf(fmaxf(a, 0.0f)), nothing
+ *             contracted.  (An a that is NaN gives g = 1: fmaxf returns its other operand.)  Z = max g - p->tol as in
+ *             rato_drone_eval: the main-plot closure keeps the raw maximum and tests it against OSQP_TOL + 1e-6
+ *             (:254-269), i.e. its caller passes tol = 0 and the threshold 1e-3 + 1e-6.
+ *   metric 0: every output is, to the bit, that of the entry point without a metric.
+ * Any other metric is RATO_EINVAL.
+ *   arg   [M] int32 or NULL (rato_drone_eval_batch_metric: [K][ldz])   the row j*S + t of g that attains the sample's
+ *         maximum (the obstacle an unsafe sample hit and the step at which it did: drone_main_plot.py:791-800) -- the
+ *         first such row in the kernels' loop order (t ascending, then j ascending, strict >); -1 when no row compared
+ *         greater than -inf (every row NaN).  A call without arg runs the kernel without the index.
+ * Everything else -- the tiled kernel without xs, the plain one with, p->stats_* and RATO_STATS_IN_LAUNCH, the batch
+ * form's stats_out -- is as in rato_drone_eval / rato_drone_eval_batch.
+ */
+#define RATO_DRONE_METRIC_QUADRATIC 0   /* drone_risk.py:170-180 */
+#define RATO_DRONE_METRIC_EUCLIDEAN 1   /* drone_main_plot.py:198-208 */
+int rato_drone_eval_metric(const rato_drone_params* p, int32_t metric, const float* us, const float* dW,
+                           const float* mass, const float* Qsym,
+                           float* Z, int32_t* arg, float* xs, float* g, void* stream);
+int rato_drone_eval_batch_metric(const rato_drone_params* p, int32_t metric, int32_t K, const float* us, const float* dW,
+                                 const float* mass, const float* Qsym, float* Z, int64_t ldz, double alpha, float thr,
+                                 void* workspace, size_t workspace_bytes, double* stats_out,
+                                 int32_t* arg /* [K][ldz] or NULL */, void* stream);
+/* Model.obstacle_avoidance_constraints_euclidean on given trajectories (drone_main_plot.py:198-208) for metric 1, with
+ * the arithmetic of the eval kernels' row: on the xs an eval call returned, g equals that call's g to the bit.
+ * Metric 0 is rato_drone_obstacle_constraints.    xs [S+1][6][M] -> g [3 obs][S][M] */
+int rato_drone_obstacle_constraints_metric(const rato_drone_params* p, int32_t metric, const float* xs,
+                                           const float* Qsym, float* g, void* stream);
 /* the records of K rows of Z [K][ldz] -> out [K][RATO_N_STATS] (one launch while M <= 12,288) */
 int rato_risk_stats_batch(const float* Z, int64_t M, int64_t ldz, int32_t K, double alpha, float thr, void* workspace,
                           size_t workspace_bytes, double* out, void* stream);
@@ -948,6 +981,18 @@ int rato_risk_stats(const float* Z, int64_t M, double alpha, float thr,
  * unclean by an aborted call.  The Python facades do this by themselves (stats.risk_stats, CvarCutSolver.evaluate). */
 int rato_risk_stats_recover(const float* Z, int64_t M, double alpha, float thr,
                             void* workspace, size_t workspace_bytes, double* out, void* stream);
+
+/*
+ * Histogram of Z on the device (the main figure's histogram of the per-sample maxima, drone_main_plot.py:716-759, for
+ * validation batches too large to bin on the host).  counts: uint32[bins + 3]
+ *   [0] #{z < lo}    [1 + b] bin b    [bins + 1] #{z >= hi}    [bins + 2] #{z is NaN}
+ *   b = min((int)((z - lo) * inv_w), bins - 1),  inv_w = (float)bins / (hi - lo)   -- all in fp32, nothing contracted, so
+ *   that the same three float32 operations in NumPy give the same bin for every z.
+ * 1 <= bins <= 4096, lo < hi, both finite (and hi - lo, inv_w finite), M >= 1; otherwise RATO_EINVAL.  The call zeroes
+ * counts itself on the stream.  Integer atomics only (a histogram private to each workgroup in LDS, flushed once): the
+ * result is deterministic and does not depend on the grid.
+ */
+int rato_histogram(const float* Z, int64_t M, float lo, float hi, int32_t bins, uint32_t* counts, void* stream);
 
 /* rato_sum_partials(part, nblocks, ncols, scale, sums_out) and rato_risk_stats(Z, ...) in ONE launch when
  * M <= 1,048,576 (the partial-sum workgroups ride along with the selection workgroups; two stream-ordered calls

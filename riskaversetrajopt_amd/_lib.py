@@ -208,7 +208,15 @@ SIGNATURES = {
     "rato_car_stats_in_launch": (C.c_int, [C.c_int32, C.c_int32]),
     "rato_risk_stats_recover": (C.c_int, [c_float_p, C.c_int64, C.c_double, C.c_float, C.c_void_p, C.c_size_t,
                                   c_float_p, c_stream]),
+    "rato_drone_eval_metric": (C.c_int, [C.POINTER(DroneParams), C.c_int32] + [c_float_p] * 8 + [c_stream]),
+    "rato_drone_eval_batch_metric": (C.c_int, [C.POINTER(DroneParams), C.c_int32, C.c_int32, c_float_p, c_float_p, c_float_p,
+                                               c_float_p, c_float_p, C.c_int64, C.c_double, C.c_float, C.c_void_p, C.c_size_t,
+                                               c_float_p, c_float_p, c_stream]),
+    "rato_drone_obstacle_constraints_metric": (C.c_int, [C.POINTER(DroneParams), C.c_int32] + [c_float_p] * 3 + [c_stream]),
+    "rato_histogram": (C.c_int, [c_float_p, C.c_int64, C.c_float, C.c_float, C.c_int32, c_float_p, c_stream]),
 }
+
+DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h
 
 
 RATO_ENONFINITE, RATO_EINFEASIBLE, RATO_ERANK, RATO_ESELECT, RATO_ENNLS = -2, -4, -6, -7, -8     # rato_saa.h

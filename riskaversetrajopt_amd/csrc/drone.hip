@@ -51,7 +51,7 @@ __device__ __forceinline__ SampleConsts load_consts(const rato_drone_params& P, 
 // (:169-196), with every rounding spelled out (contraction off: only the written fmas fuse).
 // -ffp-contract=fast leaves the contraction pattern to the optimiser, and the same source compiled into ANOTHER kernel came
 // out one rounding different (1e-7 relative, round 5).  Every kernel that reports Z / g / trajectories of the plain rollout
-// -- drone_eval_kernel (trajectories, Philox) and drone_eval_tiles_kernel -- calls THESE, so that they agree to the bit by
+// -- drone_eval_kernel (trajectories, Philox) and drone_eval_tiles_kernel -- calls THESE (obstacle_row_exact below), so that they agree to the bit by
 // construction and not by what a compiler version happens to fuse.
 __device__ __forceinline__ void step_axis_exact(const rato_drone_params& P, const SampleConsts& c, float u, float xi,
                                                 float& p, float& v) {
@@ -65,23 +65,43 @@ __device__ __forceinline__ void step_axis_exact(const rato_drone_params& P, cons
   v = __builtin_fmaf(c.cn, xi, __builtin_fmaf(P.dt, acc, v));
   p = pn;
 }
-__device__ __forceinline__ float obstacle_value_exact(const rato_drone_params& P, const SampleConsts& c, int j, float px, float py) {
+// a = (p - o_j)' Q_j (p - o_j): the quadratic form both metrics of the obstacle row start from
+__device__ __forceinline__ float obstacle_quad_exact(const rato_drone_params& P, float q00, float qs, float q11, int j, float px,
+                                                     float py) {
 #pragma clang fp contract(off)
   const float dx = px - P.obs_xy[j][0], dy = py - P.obs_xy[j][1];
-  float a = dy * (c.qs[j] * dx);
-  a = __builtin_fmaf(dx, c.q00[j] * dx, a);
-  a = __builtin_fmaf(dy, c.q11[j] * dy, a);
+  float a = dy * (qs * dx);
+  a = __builtin_fmaf(dx, q00 * dx, a);
+  a = __builtin_fmaf(dy, q11 * dy, a);
+  return a;
+}
+// METRIC (rato_saa.h): RATO_DRONE_METRIC_QUADRATIC g = 1 - a (drone_risk.py:170-180), RATO_DRONE_METRIC_EUCLIDEAN
+// g = 1 - sqrt(a) (drone_main_plot.py:198-208) on the SAME a; the clamp only guards the root against an a that rounding
+// left below zero (Q is positive definite), and maps a NaN a to g = 1 (fmaxf returns its other operand).
+template <int METRIC>
+__device__ __forceinline__ float obstacle_row_exact(const rato_drone_params& P, float q00, float qs, float q11, int j, float px,
+                                                    float py) {
+#pragma clang fp contract(off)
+  const float a = obstacle_quad_exact(P, q00, qs, q11, j, px, py);
+  if constexpr (METRIC == RATO_DRONE_METRIC_EUCLIDEAN) return 1.0f - sqrtf(fmaxf(a, 0.0f));
   return 1.0f - a;
+}
+// WANT_ARG: the running maximum also keeps the row j S + t that set it -- the first one in the kernels' loop order (t
+// ascending, then j; strict >), -1 while no row has compared greater than -inf.  The maximum itself is the same fmaxf.
+template <bool WANT_ARG>
+__device__ __forceinline__ void row_max_update(float gj, int row, float& zmax, int& amax) {
+  if constexpr (WANT_ARG) amax = (gj > zmax) ? row : amax;
+  zmax = fmaxf(zmax, gj);
 }
 
 // PHILOX: the noise of step t is REGENERATED in the kernel (Philox4x32-10 at counter (m, t), philox.h) instead of
 // read from dW: bit-identical to rato_drone_sample's dW, no 12 B per sample-step of HBM reads, no 3 S floats per
 // sample of HBM capacity.  noise_scale = sqrt(sampler dt) (drone_utils.py:90).
-template <bool PHILOX>
+template <bool PHILOX, int METRIC = RATO_DRONE_METRIC_QUADRATIC, bool WANT_ARG = false>
 __device__ __forceinline__ void drone_eval_block(
     const rato_drone_params& P, size_t blk, const float* __restrict__ us, const float* __restrict__ dW, uint64_t seed,
     float noise_scale, const float* __restrict__ mass, const float* __restrict__ Qsym, float* __restrict__ Z,
-    float* __restrict__ xs, float* __restrict__ g) {
+    float* __restrict__ xs, float* __restrict__ g, int32_t* __restrict__ arg) {
   const size_t M = (size_t)P.M, ld = (size_t)P.ld;
   const size_t m = blk * RATO_BLOCK + threadIdx.x;
   if (m >= M) return;
@@ -101,6 +121,7 @@ __device__ __forceinline__ void drone_eval_block(
     }
   }
   float zmax = -INFINITY;
+  int amax = -1;
   float xi[3];
   if (!PHILOX) {
 #pragma unroll
@@ -131,8 +152,8 @@ __device__ __forceinline__ void drone_eval_block(
     }
 #pragma unroll
     for (int j = 0; j < NOBS; ++j) {
-      const float gj = obstacle_value_exact(P, c, j, p[0], p[1]);
-      zmax = fmaxf(zmax, gj);
+      const float gj = obstacle_row_exact<METRIC>(P, c.q00[j], c.qs[j], c.q11[j], j, p[0], p[1]);
+      row_max_update<WANT_ARG>(gj, j * S + t, zmax, amax);
       if (g) g[((size_t)j * S + t) * ld + m] = gj;
     }
     if (!PHILOX) {
@@ -141,23 +162,24 @@ __device__ __forceinline__ void drone_eval_block(
     }
   }
   if (Z) Z[m] = zmax - P.tol;
+  if constexpr (WANT_ARG) arg[m] = amax;
 }
 
 // tile_queue != NULL (large batches): 8 workgroups per CU, each taking 256-sample blocks from a global counter until
 // none is left -- the hardware deals a plain grid out to the XCDs up front and every other XCD streams slower (see
 // drone_linearize_rows_kernel), so with one block per workgroup half the chip idles at the end of the launch.
-template <bool PHILOX>
+template <bool PHILOX, int METRIC = RATO_DRONE_METRIC_QUADRATIC, bool WANT_ARG = false>
 __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_kernel(
     rato_drone_params P, const float* __restrict__ us, const float* __restrict__ dW, uint64_t seed,
     float noise_scale, const float* __restrict__ mass, const float* __restrict__ Qsym, float* __restrict__ Z,
-    float* __restrict__ xs, float* __restrict__ g, unsigned* __restrict__ tile_queue, int nblk) {
+    float* __restrict__ xs, float* __restrict__ g, unsigned* __restrict__ tile_queue, int nblk, int32_t* __restrict__ arg) {
   if (!tile_queue) {
-    drone_eval_block<PHILOX>(P, blockIdx.x, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g);
+    drone_eval_block<PHILOX, METRIC, WANT_ARG>(P, blockIdx.x, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g, arg);
     return;
   }
   __shared__ int next_blk;
   for (int blk = blockIdx.x; blk < nblk;) {
-    drone_eval_block<PHILOX>(P, (size_t)blk, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g);
+    drone_eval_block<PHILOX, METRIC, WANT_ARG>(P, (size_t)blk, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g, arg);
     __syncthreads();
     if (threadIdx.x == 0)
       next_blk = (int)gridDim.x + (int)__hip_atomic_fetch_add(tile_queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -182,17 +204,18 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_kernel(
 //     (two register buffers): the rollout is bound by its own arithmetic chain, not by memory;
 //   * the statistics of Z ride in the same launch (params.stats_*: extra workgroups at the end of the grid run the exact
 //     selection as soon as the last tile's Z has landed -- rato_select.h), so that a Monte-Carlo step is ONE launch.
-// Same arithmetic per sample as drone_eval_kernel, rounding for rounding (step_axis_exact, obstacle_value_exact): Z and g
+// Same arithmetic per sample as drone_eval_kernel, rounding for rounding (step_axis_exact, obstacle_row_exact): Z and g
 // agree to the bit (tests/test_gpu_fused_stats.py).
 constexpr int EV_TB = 16;
 constexpr int EV_NW = RATO_BLOCK / RATO_WAVE;
 
 // blockIdx.y = control sequence k of a batch of K (rato_drone_eval_batch: us [K][S][3], Z [K][ldz]); K = 1: rato_drone_eval.
-template <bool WANT_G>
+// arg_base [K][ldz] (WANT_ARG): the row that set each sample's maximum (row_max_update).
+template <bool WANT_G, int METRIC = RATO_DRONE_METRIC_QUADRATIC, bool WANT_ARG = false>
 __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_tiles_kernel(
     rato_drone_params P, const float* __restrict__ us_base, const float* __restrict__ dW, const float* __restrict__ mass,
     const float* __restrict__ Qsym, float* __restrict__ Z_base, long ldz, float* __restrict__ g, int n_tiles,
-    const rato_sel::StatsTail tail) {
+    const rato_sel::StatsTail tail, int32_t* __restrict__ arg_base) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ev_lds[];
   if (tail.is_stats((int)blockIdx.x)) {
     rato_sel::stats_tail_run<RATO_BLOCK>(tail, Z_base, (long)P.M, ev_lds);
@@ -231,6 +254,7 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_tiles_kernel(
   const SampleConsts c = load_consts(P, mass, Qsym, ld, m);
   float p[2] = {P.x_init[0], P.x_init[1]}, v[2] = {P.x_init[3], P.x_init[4]};
   float zmax = -INFINITY;
+  int amax = -1;
   auto steps = [&](const float (&xi)[EV_TB][2], int t0) {
 #pragma unroll
     for (int i = 0; i < EV_TB; ++i) {
@@ -242,8 +266,8 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_tiles_kernel(
         step_axis_exact(P, c, u1, xi[i][1], p[1], v[1]);
 #pragma unroll
         for (int j = 0; j < NOBS; ++j) {
-          const float gj = obstacle_value_exact(P, c, j, p[0], p[1]);
-          zmax = fmaxf(zmax, gj);
+          const float gj = obstacle_row_exact<METRIC>(P, c.q00[j], c.qs[j], c.q11[j], j, p[0], p[1]);
+          row_max_update<WANT_ARG>(gj, j * S + t, zmax, amax);
           if (WANT_G && valid) g[((size_t)j * S + t) * ld + m] = gj;
         }
       }
@@ -255,6 +279,9 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_tiles_kernel(
     if (t0 + 2 * EV_TB < S) load(xa, t0 + 2 * EV_TB);
     steps(xb, t0 + EV_TB);
     if (t0 + 3 * EV_TB < S) load(xb, t0 + 3 * EV_TB);
+  }
+  if constexpr (WANT_ARG) {
+    if (valid) arg_base[(size_t)blockIdx.y * ldz + m] = amax;
   }
   if (!Z) return;
   if (!tail.ws) {
@@ -557,6 +584,9 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_linearize_generators_batch_k
   drone_linearize_generators_block<false, false>(P, t.us, t.s0, t.s1, t.s2, t.A22, nullptr, nullptr, nullptr, t.gpart);
 }
 
+// METRIC = RATO_DRONE_METRIC_EUCLIDEAN: the row of the eval kernels (obstacle_row_exact), so that g on the trajectories an
+// eval call returned equals that call's g to the bit; the quadratic metric keeps its own expression.
+template <int METRIC = RATO_DRONE_METRIC_QUADRATIC>
 __global__ __launch_bounds__(RATO_BLOCK) void drone_obstacle_kernel(rato_drone_params P,
                                                                     const float* __restrict__ xs,
                                                                     const float* __restrict__ Qsym,
@@ -571,8 +601,12 @@ __global__ __launch_bounds__(RATO_BLOCK) void drone_obstacle_kernel(rato_drone_p
   for (int j = 0; j < NOBS; ++j) {
     const float q00 = Qsym[(size_t)(j * 3 + 0) * ld + m], qs = Qsym[(size_t)(j * 3 + 1) * ld + m],
                 q11 = Qsym[(size_t)(j * 3 + 2) * ld + m];
-    const float dx = px - P.obs_xy[j][0], dy = py - P.obs_xy[j][1];
-    g[((size_t)j * P.S + t) * ld + m] = 1.0f - (q00 * dx * dx + qs * dx * dy + q11 * dy * dy);
+    if constexpr (METRIC == RATO_DRONE_METRIC_EUCLIDEAN) {
+      g[((size_t)j * P.S + t) * ld + m] = obstacle_row_exact<METRIC>(P, q00, qs, q11, j, px, py);
+    } else {
+      const float dx = px - P.obs_xy[j][0], dy = py - P.obs_xy[j][1];
+      g[((size_t)j * P.S + t) * ld + m] = 1.0f - (q00 * dx * dx + qs * dx * dy + q11 * dy * dy);
+    }
   }
 }
 
@@ -1392,24 +1426,40 @@ int stats_tail_for(const void* workspace, double* out, double alpha, float thr, 
 extern "C" int rato_drone_eval_stats_in_launch(int32_t M) { return M > 0 && M <= EVAL_STATS_IN_LAUNCH_MAX_M && M <= eval_tiles_max_m(); }
 
 namespace {
-int drone_eval_tiles_launch(const rato_drone_params* p, int K, const float* us, const float* dW, const float* mass,
-                            const float* Qsym, float* Z, int64_t ldz, float* g, const rato_sel::StatsTail& tail, int grid_launch,
-                            size_t lds, int n_tiles, hipStream_t st) {
-  if (g)
-    hipLaunchKernelGGL(drone_eval_tiles_kernel<true>, dim3(grid_launch, K), dim3(RATO_BLOCK), lds, st, *p, us, dW, mass, Qsym, Z,
-                       (long)ldz, g, n_tiles, tail);
+// (metric, arg != NULL) of a call -> the kernel's template arguments; the calls of the entry points without a metric
+// land on <QUADRATIC, false>, the instantiation they have always run
+template <typename F>
+void with_metric(int metric, bool want_arg, F&& f) {
+  using Q = std::integral_constant<int, RATO_DRONE_METRIC_QUADRATIC>;
+  using E = std::integral_constant<int, RATO_DRONE_METRIC_EUCLIDEAN>;
+  if (metric == RATO_DRONE_METRIC_EUCLIDEAN)
+    want_arg ? f(E{}, std::true_type{}) : f(E{}, std::false_type{});
   else
-    hipLaunchKernelGGL(drone_eval_tiles_kernel<false>, dim3(grid_launch, K), dim3(RATO_BLOCK), lds, st, *p, us, dW, mass, Qsym, Z,
-                       (long)ldz, g, n_tiles, tail);
+    want_arg ? f(Q{}, std::true_type{}) : f(Q{}, std::false_type{});
+}
+bool metric_ok(int32_t metric) { return metric == RATO_DRONE_METRIC_QUADRATIC || metric == RATO_DRONE_METRIC_EUCLIDEAN; }
+
+int drone_eval_tiles_launch(const rato_drone_params* p, int metric, int K, const float* us, const float* dW, const float* mass,
+                            const float* Qsym, float* Z, int64_t ldz, int32_t* arg, float* g, const rato_sel::StatsTail& tail,
+                            int grid_launch, size_t lds, int n_tiles, hipStream_t st) {
+  with_metric(metric, arg != nullptr, [&](auto mt, auto wa) {
+    constexpr int MT = decltype(mt)::value;
+    constexpr bool WA = decltype(wa)::value;
+    if (g)
+      hipLaunchKernelGGL((drone_eval_tiles_kernel<true, MT, WA>), dim3(grid_launch, K), dim3(RATO_BLOCK), lds, st, *p, us, dW,
+                         mass, Qsym, Z, (long)ldz, g, n_tiles, tail, arg);
+    else
+      hipLaunchKernelGGL((drone_eval_tiles_kernel<false, MT, WA>), dim3(grid_launch, K), dim3(RATO_BLOCK), lds, st, *p, us, dW,
+                         mass, Qsym, Z, (long)ldz, g, n_tiles, tail, arg);
+  });
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }
-}  // namespace
 
-extern "C" int rato_drone_eval(const rato_drone_params* p, const float* us, const float* dW, const float* mass,
-                               const float* Qsym, float* Z, float* xs, float* g, void* stream) {
+int drone_eval_impl(const rato_drone_params* p, int32_t metric, const float* us, const float* dW, const float* mass,
+                    const float* Qsym, float* Z, int32_t* arg, float* xs, float* g, void* stream) {
   RATO_CLEAR_ERROR();
-  if (!params_ok(p) || !us || !dW || !mass || !Qsym) return RATO_EINVAL;
+  if (!params_ok(p) || !metric_ok(metric) || !us || !dW || !mass || !Qsym) return RATO_EINVAL;
   if (p->stats_workspace && (!Z || !p->stats_out || !(p->stats_alpha > 0.0) || !(p->stats_alpha <= 1.0))) return RATO_EINVAL;
   hipStream_t st = rato::as_stream(stream);
   if (!xs && p->M <= eval_tiles_max_m()) {
@@ -1427,7 +1477,7 @@ extern "C" int rato_drone_eval(const rato_drone_params* p, const float* us, cons
                                                 grid_launch, lds);
       if (rc != RATO_OK) return rc;
     }
-    const int rc = drone_eval_tiles_launch(p, 1, us, dW, mass, Qsym, Z, p->ld, g, tail, grid_launch, lds, n_tiles, st);
+    const int rc = drone_eval_tiles_launch(p, metric, 1, us, dW, mass, Qsym, Z, p->ld, arg, g, tail, grid_launch, lds, n_tiles, st);
     if (rc != RATO_OK) return rc;
     if (p->stats_workspace && !in_launch)
       return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace,
@@ -1446,8 +1496,10 @@ extern "C" int rato_drone_eval(const rato_drone_params* p, const float* us, cons
     if (queue) grid_x = 8 * device_cus();
   }
   dim3 grid(grid_x), block(RATO_BLOCK);
-  hipLaunchKernelGGL(drone_eval_kernel<false>, grid, block, 0, st, *p, us, dW, (uint64_t)0, 0.0f,
-                     mass, Qsym, Z, xs, g, queue, nblk);
+  with_metric(metric, arg != nullptr, [&](auto mt, auto wa) {
+    hipLaunchKernelGGL((drone_eval_kernel<false, decltype(mt)::value, decltype(wa)::value>), grid, block, 0, st, *p, us, dW,
+                       (uint64_t)0, 0.0f, mass, Qsym, Z, xs, g, queue, nblk, arg);
+  });
   RATO_LAUNCH_CHECK();
   if (p->stats_workspace)
     return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace, rato_risk_stats_workspace_bytes(p->M),
@@ -1455,20 +1507,50 @@ extern "C" int rato_drone_eval(const rato_drone_params* p, const float* us, cons
   return RATO_OK;
 }
 
-// K control sequences against ONE resident batch in one call: us [K][S][3] -> Z [K][ldz] (+ stats_out [K][RATO_N_STATS]).
-extern "C" int rato_drone_eval_batch(const rato_drone_params* p, int32_t K, const float* us, const float* dW, const float* mass,
-                                     const float* Qsym, float* Z, int64_t ldz, double alpha, float thr, void* workspace,
-                                     size_t workspace_bytes, double* stats_out, void* stream) {
+int drone_eval_batch_impl(const rato_drone_params* p, int32_t metric, int32_t K, const float* us, const float* dW,
+                          const float* mass, const float* Qsym, float* Z, int64_t ldz, double alpha, float thr, void* workspace,
+                          size_t workspace_bytes, double* stats_out, int32_t* arg, void* stream) {
   RATO_CLEAR_ERROR();
-  if (!params_ok(p) || K < 1 || K > 65535 || !us || !dW || !mass || !Qsym || !Z || ldz < p->M) return RATO_EINVAL;
+  if (!params_ok(p) || !metric_ok(metric) || K < 1 || K > 65535 || !us || !dW || !mass || !Qsym || !Z || ldz < p->M)
+    return RATO_EINVAL;
   if (stats_out && (!(alpha > 0.0) || !(alpha <= 1.0) || !workspace)) return RATO_EINVAL;
   hipStream_t st = rato::as_stream(stream);
   const int n_tiles = (int)((p->M + RATO_WAVE - 1) / RATO_WAVE);
   const int grid = (n_tiles + EV_NW - 1) / EV_NW;
   rato_sel::StatsTail tail = {};
-  const int rc = drone_eval_tiles_launch(p, K, us, dW, mass, Qsym, Z, ldz, nullptr, tail, grid, 0, n_tiles, st);
+  const int rc = drone_eval_tiles_launch(p, metric, K, us, dW, mass, Qsym, Z, ldz, arg, nullptr, tail, grid, 0, n_tiles, st);
   if (rc != RATO_OK || !stats_out) return rc;
   return rato_risk_stats_batch(Z, p->M, ldz, K, alpha, thr, workspace, workspace_bytes, stats_out, stream);
+}
+}  // namespace
+
+extern "C" int rato_drone_eval(const rato_drone_params* p, const float* us, const float* dW, const float* mass,
+                               const float* Qsym, float* Z, float* xs, float* g, void* stream) {
+  return drone_eval_impl(p, RATO_DRONE_METRIC_QUADRATIC, us, dW, mass, Qsym, Z, nullptr, xs, g, stream);
+}
+
+// rato_drone_eval with the obstacle metric chosen by the caller and, with arg != NULL, the row behind each sample's maximum
+// (drone_main_plot.py:198-208,254-269,791-800): the same two kernels, instantiated for the metric.
+extern "C" int rato_drone_eval_metric(const rato_drone_params* p, int32_t metric, const float* us, const float* dW,
+                                      const float* mass, const float* Qsym, float* Z, int32_t* arg, float* xs, float* g,
+                                      void* stream) {
+  return drone_eval_impl(p, metric, us, dW, mass, Qsym, Z, arg, xs, g, stream);
+}
+
+// K control sequences against ONE resident batch in one call: us [K][S][3] -> Z [K][ldz] (+ stats_out [K][RATO_N_STATS]).
+extern "C" int rato_drone_eval_batch(const rato_drone_params* p, int32_t K, const float* us, const float* dW, const float* mass,
+                                     const float* Qsym, float* Z, int64_t ldz, double alpha, float thr, void* workspace,
+                                     size_t workspace_bytes, double* stats_out, void* stream) {
+  return drone_eval_batch_impl(p, RATO_DRONE_METRIC_QUADRATIC, K, us, dW, mass, Qsym, Z, ldz, alpha, thr, workspace,
+                               workspace_bytes, stats_out, nullptr, stream);
+}
+
+extern "C" int rato_drone_eval_batch_metric(const rato_drone_params* p, int32_t metric, int32_t K, const float* us,
+                                            const float* dW, const float* mass, const float* Qsym, float* Z, int64_t ldz,
+                                            double alpha, float thr, void* workspace, size_t workspace_bytes, double* stats_out,
+                                            int32_t* arg, void* stream) {
+  return drone_eval_batch_impl(p, metric, K, us, dW, mass, Qsym, Z, ldz, alpha, thr, workspace, workspace_bytes, stats_out, arg,
+                               stream);
 }
 
 extern "C" int rato_drone_eval_philox(const rato_drone_params* p, const float* us, uint64_t seed, float sampler_dt,
@@ -1478,7 +1560,7 @@ extern "C" int rato_drone_eval_philox(const rato_drone_params* p, const float* u
   if (!params_ok(p) || !us || !mass || !Qsym || !(sampler_dt >= 0.0f) || p->S > 65535) return RATO_EINVAL;
   dim3 grid(rato::nblocks_for(p->M)), block(RATO_BLOCK);
   hipLaunchKernelGGL(drone_eval_kernel<true>, grid, block, 0, rato::as_stream(stream), *p, us, (const float*)nullptr,
-                     seed, sqrtf(sampler_dt), mass, Qsym, Z, xs, g, (unsigned*)nullptr, 0);
+                     seed, sqrtf(sampler_dt), mass, Qsym, Z, xs, g, (unsigned*)nullptr, 0, (int32_t*)nullptr);
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }
@@ -1488,7 +1570,20 @@ extern "C" int rato_drone_obstacle_constraints(const rato_drone_params* p, const
   RATO_CLEAR_ERROR();
   if (!params_ok(p) || !xs || !Qsym || !g) return RATO_EINVAL;
   dim3 grid(rato::nblocks_for(p->M), p->S), block(RATO_BLOCK);
-  hipLaunchKernelGGL(drone_obstacle_kernel, grid, block, 0, rato::as_stream(stream), *p, xs, Qsym, g);
+  hipLaunchKernelGGL(drone_obstacle_kernel<>, grid, block, 0, rato::as_stream(stream), *p, xs, Qsym, g);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+// Model.obstacle_avoidance_constraints_euclidean (drone_main_plot.py:198-208) for metric 1; metric 0 is the call above
+extern "C" int rato_drone_obstacle_constraints_metric(const rato_drone_params* p, int32_t metric, const float* xs,
+                                                      const float* Qsym, float* g, void* stream) {
+  if (metric == RATO_DRONE_METRIC_QUADRATIC) return rato_drone_obstacle_constraints(p, xs, Qsym, g, stream);
+  RATO_CLEAR_ERROR();
+  if (!params_ok(p) || metric != RATO_DRONE_METRIC_EUCLIDEAN || !xs || !Qsym || !g) return RATO_EINVAL;
+  dim3 grid(rato::nblocks_for(p->M), p->S), block(RATO_BLOCK);
+  hipLaunchKernelGGL(drone_obstacle_kernel<RATO_DRONE_METRIC_EUCLIDEAN>, grid, block, 0, rato::as_stream(stream), *p, xs, Qsym,
+                     g);
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }

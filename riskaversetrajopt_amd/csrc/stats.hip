@@ -483,6 +483,67 @@ extern "C" int rato_count_nonfinite_acc(const float* x, int64_t n, uint32_t* cou
   return RATO_OK;
 }
 
+namespace {
+// ------------------------------------------------------------- histogram
+// Fixed-range histogram of Z (rato_saa.h: rato_histogram).  Z of a validation batch is CLUSTERED: most samples sit in a
+// few bins.  So nothing is added to global memory per element: every workgroup counts into its own LDS histogram and
+// flushes the non-empty bins once (the note on the selection's grid below: it is the number of workgroups flushing into
+// the same few words that costs, hence at most HG_MAX_BLOCKS of them), and a thread merges a run of equal bins in a
+// register before it touches LDS.  Integer adds commute: the counts do not depend on the grid or on timing.
+constexpr int HG_MAX_BINS = 4096, HG_MAX_BLOCKS = 256, HG_PER_THREAD = 16;
+
+__device__ __forceinline__ int histogram_slot(float z, float lo, float hi, float inv_w, int bins) {
+#pragma clang fp contract(off)
+  if (z != z) return bins + 2;
+  if (z < lo) return 0;
+  if (z >= hi) return bins + 1;
+  const float x = (z - lo) * inv_w;
+  const int b = (int)x;
+  return 1 + (b < bins - 1 ? b : bins - 1);
+}
+
+__global__ __launch_bounds__(RATO_BLOCK) void histogram_kernel(const float* __restrict__ Z, long M, float lo, float hi,
+                                                               float inv_w, int bins, unsigned* __restrict__ counts) {
+  __shared__ unsigned h[HG_MAX_BINS + 3];
+  const int n = bins + 3;
+  for (int i = threadIdx.x; i < n; i += RATO_BLOCK) h[i] = 0;
+  __syncthreads();
+  int cur = 0;
+  unsigned run = 0;
+  for (long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x; i < M; i += (long)gridDim.x * RATO_BLOCK) {
+    const int slot = histogram_slot(Z[i], lo, hi, inv_w, bins);
+    if (slot != cur) {
+      if (run) atomicAdd(&h[cur], run);
+      cur = slot;
+      run = 0;
+    }
+    ++run;
+  }
+  if (run) atomicAdd(&h[cur], run);
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += RATO_BLOCK) {
+    const unsigned v = h[i];
+    if (v) atomicAdd(&counts[i], v);
+  }
+}
+}  // namespace
+
+extern "C" int rato_histogram(const float* Z, int64_t M, float lo, float hi, int32_t bins, uint32_t* counts, void* stream) {
+  RATO_CLEAR_ERROR();
+  if (!Z || !counts || M < 1 || bins < 1 || bins > HG_MAX_BINS || !isfinite(lo) || !isfinite(hi) || !(lo < hi)) return RATO_EINVAL;
+  const float width = hi - lo;
+  const float inv_w = (float)bins / width;
+  if (!isfinite(width) || !isfinite(inv_w)) return RATO_EINVAL;
+  hipStream_t st = rato::as_stream(stream);
+  hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)(bins + 3), st);
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
+  long nb = (M + (long)RATO_BLOCK * HG_PER_THREAD - 1) / ((long)RATO_BLOCK * HG_PER_THREAD);
+  if (nb > HG_MAX_BLOCKS) nb = HG_MAX_BLOCKS;
+  hipLaunchKernelGGL(histogram_kernel, dim3((unsigned)nb), dim3(RATO_BLOCK), 0, st, Z, (long)M, lo, hi, inv_w, (int)bins, counts);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
 extern "C" size_t rato_risk_stats_workspace_bytes(int64_t M) {
   (void)M;
   return sizeof(Workspace);

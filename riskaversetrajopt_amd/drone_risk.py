@@ -120,9 +120,11 @@ class Model:
     def convert_us_mat_to_us_jaxvec(self, us_mat):
         return np.reshape(np.asarray(us_mat), (self.S * n_u), 'C')
 
-    def initial_guess_us_mat(self):
+    def initial_guess_us_mat(self, all_axes=False):
+        """drone_risk.py:119 offsets the first two controls by 1e-2; ``all_axes=True`` is the main-plot script's guess,
+        which offsets all three (drone_main_plot.py:137-148)."""
         us = np.zeros((self.S, n_u))
-        us[:, :(n_u - 1)] = (self.u_max + self.u_min) / 2.0 + 1e-2
+        us[:, :(n_u if all_axes else n_u - 1)] = (self.u_max + self.u_min) / 2.0 + 1e-2
         return us
 
     # ---- plumbing ----------------------------------------------------------
@@ -183,9 +185,21 @@ class Model:
         return self._empty(*shape) if shape[-1] == M else torch.zeros(shape, dtype=torch.float32, device=self.device)
 
     # ---- rollout + constraint values (K1) ----------------------------------
-    def eval_device(self, us_mat, want_xs=False, want_g=False, inputs=None, out=None, stats_request=None):
+    @staticmethod
+    def _metric(metric):
+        try:
+            return _lib.DRONE_METRICS[metric]
+        except (KeyError, TypeError):
+            raise ValueError(f"metric must be one of {sorted(_lib.DRONE_METRICS)}, got {metric!r}") from None
+
+    def eval_device(self, us_mat, want_xs=False, want_g=False, inputs=None, out=None, stats_request=None,
+                    metric='quadratic', want_arg=False, tol=None):
         """-> (Z [M], xs [S+1][6][M] or None, g [n_obs][S][M] or None): device tensors
         (views of row-stride-ld buffers).
+        ``metric``: 'quadratic' g = 1 - d'Qd (drone_risk.py:170-180) or 'euclidean' g = 1 - sqrt(d'Qd)
+        (drone_main_plot.py:198-208); ``want_arg=True`` appends a fourth entry arg [M] (int32): the row j*S + t of g that
+        attains each sample's maximum, -1 if none (rato_drone_eval_metric).  ``tol``: what Z = max g - tol subtracts
+        (default OSQP_TOL; the main-plot closure keeps the raw maximum: 0).
         ``out``: a dict whose ``_Z`` / ``_g`` buffers (shapes of an earlier call) are reused.
         ``stats_request`` = (workspace, record, alpha): the call also leaves the ``rato_risk_stats`` record of Z in
         ``record`` (double[N_STATS], device) -- in the SAME launch for small batches without trajectories
@@ -208,9 +222,22 @@ class Model:
         if g is not None:                                # (a call without g keeps the reusable g buffer of an earlier one)
             o["_g"] = g
         p = self._params(M, ld)
+        if tol is not None:
+            p.tol, p.tol64 = float(tol), float(tol)
         if stats_request is not None:        # (workspace, record, alpha[, in_launch])
             stats.request_in_launch(p, *stats_request[:3], flags=(stats.STATS_IN_LAUNCH if (len(stats_request) > 3 and
                                                                                              stats_request[3]) else 0))
+        metric_id = self._metric(metric)
+        if metric_id or want_arg:
+            if dW is None:
+                raise ValueError("metric='euclidean' / want_arg=True read a materialised dW (this Model regenerates its noise: "
+                                 "the Philox kernel has no such form)")
+            arg = torch.empty(ld, dtype=torch.int32, device=self.device) if want_arg else None
+            _lib.check(self._lib.rato_drone_eval_metric(C.byref(p), metric_id, _lib.ptr(us), _lib.ptr(dW), _lib.ptr(mass),
+                                                        _lib.ptr(Qsym), _lib.ptr(Z), _lib.ptr(arg), _lib.ptr(xs), _lib.ptr(g),
+                                                        _lib.current_stream()), "rato_drone_eval_metric")
+            r = (Z[:M], (xs[..., :M] if want_xs else None), (g[..., :M] if want_g else None))
+            return r + (arg[:M],) if want_arg else r
         if dW is None:                                   # noise regenerated in the kernel (Philox, csrc/philox.h)
             _lib.check(self._lib.rato_drone_eval_philox(C.byref(p), _lib.ptr(us), self._noise_seed, self._sampler_dt,
                                                         _lib.ptr(mass), _lib.ptr(Qsym), _lib.ptr(Z), _lib.ptr(xs),
@@ -238,13 +265,18 @@ class Model:
         Z, _, _ = self.eval_device(us_mat, inputs=inputs, out=out, stats_request=(workspace, stats_out, alpha, in_launch))
         return Z, stats_out
 
-    def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None):
+    def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None, metric='quadratic',
+                          want_arg=False, tol=None):
         """K control sequences on the model's batch in ONE call (rato_drone_eval_batch): what the reference's Monte-Carlo
         report does one sequence at a time for its 4 alpha x 30 repeats (drone_risk.py:697-725).  ``us_batch``
         (K, S, n_u) -> (Z [K][M] device, records [K][N_STATS] device double or None).  Row k equals, to the bit, what
-        ``eval_device`` / ``stats.risk_stats_device`` give for sequence k."""
+        ``eval_device`` / ``stats.risk_stats_device`` give for sequence k.  ``metric`` / ``want_arg`` / ``tol`` as in
+        ``eval_device`` (rato_drone_eval_batch_metric); ``want_arg=True`` appends arg [K][M] (int32)."""
         dW, mass, Qsym, M = self._inputs(None)
+        metric_id = self._metric(metric)
         if dW is None:
+            if metric_id or want_arg:
+                raise ValueError("metric='euclidean' / want_arg=True read a materialised dW (this Model regenerates its noise)")
             raise _lib.RatoError("eval_batch_device reads a materialised dW (this Model regenerates its noise)")
         alpha = self.alpha if alpha is None else alpha
         if isinstance(us_batch, torch.Tensor) and us_batch.is_cuda:
@@ -269,10 +301,19 @@ class Model:
                 workspace = stats.new_workspace(M, self.device)
         o["_Zb"], o["_recb"], o["_wsb"] = Z, rec, workspace
         p = self._params(M, ld)
+        if tol is not None:
+            p.tol, p.tol64 = float(tol), float(tol)
+        tail = (ld, float(alpha), float(stats.SATISFIED_THRESHOLD), _lib.ptr(workspace),
+                workspace.numel() if workspace is not None else 0, _lib.ptr(rec))
+        if metric_id or want_arg:
+            arg = torch.empty((K, ld), dtype=torch.int32, device=self.device) if want_arg else None
+            _lib.check(self._lib.rato_drone_eval_batch_metric(
+                C.byref(p), metric_id, K, _lib.ptr(us), _lib.ptr(dW), _lib.ptr(mass), _lib.ptr(Qsym), _lib.ptr(Z), *tail,
+                _lib.ptr(arg), _lib.current_stream()), "rato_drone_eval_batch_metric")
+            return (Z[:, :M], rec, arg[:, :M]) if want_arg else (Z[:, :M], rec)
         _lib.check(self._lib.rato_drone_eval_batch(
-            C.byref(p), K, _lib.ptr(us), _lib.ptr(dW), _lib.ptr(mass), _lib.ptr(Qsym), _lib.ptr(Z), ld, float(alpha),
-            float(stats.SATISFIED_THRESHOLD), _lib.ptr(workspace), workspace.numel() if workspace is not None else 0,
-            _lib.ptr(rec), _lib.current_stream()), "rato_drone_eval_batch")
+            C.byref(p), K, _lib.ptr(us), _lib.ptr(dW), _lib.ptr(mass), _lib.ptr(Qsym), _lib.ptr(Z), *tail,
+            _lib.current_stream()), "rato_drone_eval_batch")
         return Z[:, :M], rec
 
     def us_to_state_trajectories(self, us_mat):
@@ -293,6 +334,13 @@ class Model:
     def obstacle_avoidance_constraints(self, xs, obs_Q):
         """drone_risk.py:198-213: xs (S+1,n_x), obs_Q (n_obs,3,3) -> (n_obs,S);
         also batched: (M,S+1,n_x), (M,n_obs,3,3) -> (M,n_obs,S)."""
+        return self._obstacle_constraints(xs, obs_Q, 'quadratic')
+
+    def obstacle_avoidance_constraints_euclidean(self, xs, obs_Q):
+        """drone_main_plot.py:254-269: g = 1 - sqrt((p-o)' Q (p-o)); shapes of ``obstacle_avoidance_constraints``."""
+        return self._obstacle_constraints(xs, obs_Q, 'euclidean')
+
+    def _obstacle_constraints(self, xs, obs_Q, metric):
         xs, obs_Q = np.asarray(xs), np.asarray(obs_Q)
         single = xs.ndim == 2
         if single:
@@ -304,9 +352,14 @@ class Model:
         xs_d[..., :M] = torch.as_tensor(xs, device=self.device).permute(1, 2, 0).float()
         g = self._empty(n_obs, self.S, ld)
         p = self._params(M, ld)
-        _lib.check(self._lib.rato_drone_obstacle_constraints(C.byref(p), _lib.ptr(xs_d), _lib.ptr(Qsym),
-                                                             _lib.ptr(g), _lib.current_stream()),
-                   "rato_drone_obstacle_constraints")
+        if self._metric(metric):
+            _lib.check(self._lib.rato_drone_obstacle_constraints_metric(C.byref(p), self._metric(metric), _lib.ptr(xs_d),
+                                                                        _lib.ptr(Qsym), _lib.ptr(g), _lib.current_stream()),
+                       "rato_drone_obstacle_constraints_metric")
+        else:
+            _lib.check(self._lib.rato_drone_obstacle_constraints(C.byref(p), _lib.ptr(xs_d), _lib.ptr(Qsym),
+                                                                 _lib.ptr(g), _lib.current_stream()),
+                       "rato_drone_obstacle_constraints")
         out = g[..., :M].permute(2, 0, 1).double().cpu().numpy()
         return out[0] if single else out
 
@@ -919,6 +972,13 @@ class Model:
         Z, _, _ = self.eval_device(us_mat)
         Zh = Z.double().cpu().numpy()
         return Zh <= 1e-6, Zh
+
+    def monte_carlo_no_collisions_constraint_verification_euclidean(self, us_mat):
+        """vmap of the main-plot script's closure (drone_main_plot.py:633-639) -> (xs (M,S+1,n_x), B_satisfied (M,) bool,
+        max_constraint (M,)): the Euclidean rows, the RAW maximum (nothing subtracted), tested against OSQP_TOL + 1e-6."""
+        Z, xs, _ = self.eval_device(us_mat, want_xs=True, metric='euclidean', tol=0.0)
+        Zh = Z.double().cpu().numpy()
+        return xs.permute(2, 0, 1).double().cpu().numpy(), Zh <= OSQP_TOL + 1e-6, Zh
 
     monte_carlo_statistics = stats.monte_carlo_statistics
     monte_carlo_avar = staticmethod(stats.monte_carlo_avar)

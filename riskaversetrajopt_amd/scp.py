@@ -269,6 +269,65 @@ def _saa_experiment(models, run_batch, iters, n_threads, alphas, num_repeats, mc
     return out
 
 
+def draw_main_figure_batches(M=50, M_mc=10000, S=20, seed=0):
+    """The two sample batches of the main-figure script in ITS draw order: ``np.random.seed(seed)``
+    (drone_main_plot.py:26), the SAA batch of ``Model(M, 'saa', alpha)`` (:603), then the validation batch of
+    ``Model(10000)`` (:632) from the SAME continuing stream -- the script does not reseed in between.  Its inline sampler
+    (:92-121) draws in ``drone_utils.sample_uncertain_parameters``' order with dt = T / S.  Host only (no GPU).
+    -> ((DWs, masses, obs_Qs) of the SAA batch, (DWs, masses, obs_Qs) of the validation batch)"""
+    from . import drone_params as P
+    from .drone_utils import sample_uncertain_parameters
+    np.random.seed(seed)
+    saa = sample_uncertain_parameters('saa', M=int(M), S=int(S), dt=P.T / S)
+    return saa, sample_uncertain_parameters('saa', M=int(M_mc), S=int(S), dt=P.T / S)
+
+
+def drone_main_figure_experiment(alpha=0.1, M=50, S=20, iters=20, M_mc=10000, seed=0, bins=100, hist_range=(-0.6, 0.4),
+                                 results_dir=None, device='cuda:0'):
+    """The Monte-Carlo block behind the paper's main figure (drone_main_plot.py:603-710) as one call: the two batches in
+    the script's draw order (``draw_main_figure_batches``), ``iters`` iterations of the reduced SCP from the script's
+    all-axes initial guess (``run_drone_reduced``; the script's own loop solves the full QP with OSQP -- no claim about
+    its iterates), then on the validation batch ONE rollout with the Euclidean rows that returns the trajectories, the
+    raw per-sample maxima and the row behind each (rato_drone_eval_metric), their VaR / AVaR (rato_risk_stats) and
+    their histogram over ``hist_range`` (rato_histogram; the figure's axis is [-0.6, 0.4], :750).
+    -> dict, all on the host: us (S,3), xs (M,S+1,6) of the SAA batch, xs_MC (M_mc,S+1,6), obs_Qs (M_mc,n_obs,3,3),
+    B_satisfied_vec = constraints_vec <= OSQP_TOL + 1e-6, constraints_vec (M_mc,), percentage_safe, var_val, avar_val,
+    mean, arg (M_mc,) int32 = j*S + t of each sample's maximum, hist_counts (bins + 3: below, the bins, at or above, NaN),
+    hist_edges (bins + 1).
+    ``percentage_safe`` keeps the reference's value under the reference's name: 1 - mean(B_satisfied_vec) (:697), i.e.
+    the share of UNSAFE samples.  With ``results_dir``: drone_main_monte_carlo.npy, the script's nine arrays in its order
+    (:700-710; ``load_results(path, 9)``)."""
+    import torch
+    from . import drone_risk, stats
+    from .drone_params import OSQP_TOL
+    saa, mc = draw_main_figure_batches(M, M_mc, S, seed)
+    model = drone_risk.Model(S, *saa, 'saa', alpha, device=device)
+    guess = model.initial_guess_us_mat
+    model.initial_guess_us_mat = lambda: guess(all_axes=True)            # drone_main_plot.py:137-148
+    us = np.asarray(run_drone_reduced(model, num_scp_iters_max=int(iters))["us"], dtype=np.float64)
+    xs = model.us_to_state_trajectories(us)
+    mc_model = drone_risk.Model(S, *mc, 'saa', alpha, device=device)
+    Z, xs_MC, _, arg = mc_model.eval_device(us, want_xs=True, metric='euclidean', want_arg=True, tol=0.0)
+    rec = stats.risk_stats_device(Z, alpha, thr=OSQP_TOL + 1e-6)
+    counts = stats.histogram_device(Z, hist_range[0], hist_range[1], bins)
+    st = dict(zip(stats._STAT_NAMES, rec.cpu().numpy().tolist()))
+    if np.isnan(st["var"]):                                                 # (a selection that gave up: the recovering path)
+        st = stats.risk_stats(Z, alpha, thr=OSQP_TOL + 1e-6)
+    constraints_vec = Z.double().cpu().numpy()
+    B = constraints_vec <= OSQP_TOL + 1e-6
+    lo, hi = float(hist_range[0]), float(hist_range[1])
+    out = {"us": us, "xs": xs, "xs_MC": xs_MC.permute(2, 0, 1).double().cpu().numpy(), "obs_Qs": np.asarray(mc[2]),
+           "B_satisfied_vec": B, "constraints_vec": constraints_vec, "percentage_safe": 1.0 - float(np.mean(B)),
+           "var_val": st["var"], "avar_val": st["cvar"], "mean": st["mean"], "arg": arg.cpu().numpy(),
+           "hist_counts": counts.cpu().numpy().view(np.uint32).astype(np.int64),
+           "hist_edges": lo + np.arange(int(bins) + 1, dtype=np.float64) * ((hi - lo) / int(bins))}
+    if results_dir is not None:
+        os.makedirs(results_dir, exist_ok=True)
+        save_results(os.path.join(results_dir, "drone_main_monte_carlo.npy"), *(out[k] for k in (
+            "us", "xs", "xs_MC", "obs_Qs", "B_satisfied_vec", "constraints_vec", "percentage_safe", "var_val", "avar_val")))
+    return out
+
+
 def run_driving(model, num_scp_iters_max=15, verbose=False, check_finite=True):
     """driving.py:474-513: two warm-up solves (scp_iter 0 and 1), restart, then a fixed number of
     define_problem/solve iterations (define re-sets the solver up at iterations 0 and 1)."""

@@ -145,6 +145,30 @@ def monte_carlo_avar(Z_samples, alpha):
     return risk_stats(Z_samples, alpha)["cvar"]
 
 
+HISTOGRAM_MAX_BINS = 4096
+
+
+def histogram_device(Z, lo, hi, bins, out=None, stream=None):
+    """Fixed-range histogram of a device tensor Z on the device (rato_histogram; the main figure's histogram of the
+    per-sample maxima, drone_main_plot.py:716-759) -> int32 device tensor [bins + 3]:
+    [0] #{z < lo}, [1 + b] bin b = min(int((z - lo) * (float32(bins) / (hi - lo))), bins - 1) in float32 arithmetic,
+    [bins + 1] #{z >= hi}, [bins + 2] #{NaN}.  Deterministic; asynchronous on the current stream."""
+    lib = _lib.load()
+    Z = _as_device_f32(Z)
+    bins = int(bins)
+    if out is None:
+        out = torch.empty(max(bins, 0) + 3, dtype=torch.int32, device=Z.device)
+    _lib.check(lib.rato_histogram(_lib.ptr(Z), Z.numel(), float(lo), float(hi), bins, _lib.ptr(out),
+                                  _lib.current_stream() if stream is None else stream), "rato_histogram")
+    return out
+
+
+def histogram(Z, lo, hi, bins):
+    """``histogram_device`` read back -> (counts int64 [bins + 3], edges float64 [bins + 1] = lo + b (hi - lo) / bins)."""
+    counts = histogram_device(Z, lo, hi, bins).cpu().numpy().view(np.uint32).astype(np.int64)
+    return counts, float(lo) + np.arange(int(bins) + 1, dtype=np.float64) * ((float(hi) - float(lo)) / int(bins))
+
+
 def sum_partials(part, scale=1.0, out=None, stream=None):
     """part: device (nblocks, ...) fp32 (or fp64: the block sums of the CVaR-cut oracle) -> device double tensor of
     shape part.shape[1:] holding scale * sum over blocks (fixed order, fp64)."""
