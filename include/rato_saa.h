@@ -1001,6 +1001,52 @@ int rato_sums_and_risk_stats(const float* part, int32_t nblocks, int32_t ncols, 
                              const float* Z, int64_t M, double alpha, float thr, void* workspace,
                              size_t workspace_bytes, double* out, void* stream);
 
+/* ---- Driving Gaussian baseline (car/driving_gaussian.py) ------------------------------------------------------------
+ * The define step of the baseline's SCP (get_all_constraints_coeffs, :303-354) has no sample axis but a tangent axis: it
+ * is jacfwd of an S-step recursion of the mean (Euler, x+ = x + dt b(x, u; omega_nom), :172-186) and of the 8x8 covariance
+ * (Sigma+ = A Sigma A^T + dt sigma sigma^T + Sigma_omega with A = I + dt db/dx, :188-228) with respect to the 2S controls
+ * and the S risk allocations.  rato_car_gaussian_linearize evaluates values and closed-form derivatives for K problems in
+ * ONE launch, fp64 throughout: one workgroup per problem, one lane per control direction (csrc/car_gaussian.hip).
+ *
+ *   g_t = -( |d| - ppf(1 - alpha_t) sqrt(n^T Sigma[4:6,4:6] n) - min_separation_distance ),  d = p_ego - p_ped, n = d/|d|,
+ *   at steps 1..S (:238-264); ppf is Wichura's AS 241 (PPND16) evaluated at 1 - alpha as the reference does;
+ *   d g_t / d alpha_t = -sqrt(n^T Sigma n) / pdf(ppf(1 - alpha_t)), and d g_t / d alpha_s = 0 for s != t.
+ *
+ * Reproduced as written in the reference (outer_product = 0):
+ *   - force_on_pedestrian reads x[7] (the pedestrian's y velocity) as "speed_ego_along_y" (:120) and adds the SCALAR
+ *     omega_speed (speed_ped_des - x[7]) to both force components (:127);
+ *   - b_ds and b_dr are 1-D, so `b_ds @ b_ds.T` (:209-211) is an inner product and Sigma_due_to_omega is one scalar that
+ *     `Sig_next +=` adds to all 64 entries (the quirk oracle/gaussian.py documents for the drone): the ego block of Sigma
+ *     is not zero and the full symmetric 8x8 is carried.
+ * outer_product = 1 adds the rank-one terms var_s b_ds b_ds^T + var_r b_dr b_dr^T instead.
+ *
+ * Every constant comes from the caller (the facade fills it from driving_params): nothing is baked into the kernel. */
+typedef struct rato_car_gauss_params {
+  int32_t S;                      /* 1..64 */
+  int32_t outer_product;          /* 0: the reference's scalar Sigma_omega; 1: the rank-one terms */
+  double dt;
+  double omega_speed_nom, omega_repulsive_nom;     /* :79-80 */
+  double omega_speed_var, omega_repulsive_var;     /* (2 del)^2 / 12, :81-84 */
+  double beta;                    /* diffusion magnitude, 3e-2 (:77) */
+  double speed_ped_des, min_separation_distance;
+  double mean_init[8];            /* state_init */
+  double ped_var_init[4];         /* diagonal of variance_ped_initial_state: Sigma_0[4+i][4+i] */
+  double ego_goal[4];             /* (position_ego_goal, velocity_ego_goal) */
+} rato_car_gauss_params;
+size_t rato_car_gauss_params_bytes(void); /* sizeof the struct as this library was built: a binding checks its layout */
+
+/* Device pointers (fp64), stream ordered, no allocation.  mus / Sigmas may be NULL (not written); every other pointer is
+ * required.  g_obs_du column t*2+i is d/d u[t][i] (reshape(.., 'C') at :330); its strict upper triangle (column step >= row
+ * step: step t+1 of the recursion does not see u[t'] for t' > t) is written as exactly 0.0.  g_obs_dalpha holds the diagonal
+ * of the S x S block (the off-diagonal is identically zero).  v_final = x_S[0:4] - ego_goal (:230-235).
+ * RATO_EINVAL without a launch unless 1 <= S <= 64, K >= 1 and the required pointers are non-NULL. */
+int rato_car_gaussian_linearize(const rato_car_gauss_params* p, int32_t K,
+                                const double* us /* [K][S][2] */, const double* alphas_risk /* [K][S] */,
+                                double* mus /* [K][S+1][8] or NULL */, double* Sigmas /* [K][S+1][8][8] or NULL */,
+                                double* g_obs /* [K][S] = -separation_distances_at_all_times */,
+                                double* g_obs_du /* [K][S][2S] */, double* g_obs_dalpha /* [K][S] */,
+                                double* v_final /* [K][4] */, double* v_final_du /* [K][4][2S] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

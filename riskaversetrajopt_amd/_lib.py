@@ -35,6 +35,14 @@ class CarParams(C.Structure):
                 ("stats_thr", C.c_float), ("stats_flags", C.c_int32)]
 
 
+class CarGaussParams(C.Structure):
+    """rato_car_gauss_params (include/rato_saa.h)"""
+    _fields_ = [("S", C.c_int32), ("outer_product", C.c_int32)] + \
+               [(k, C.c_double) for k in ("dt", "omega_speed_nom", "omega_repulsive_nom", "omega_speed_var",
+                                          "omega_repulsive_var", "beta", "speed_ped_des", "min_separation_distance")] + \
+               [("mean_init", C.c_double * 8), ("ped_var_init", C.c_double * 4), ("ego_goal", C.c_double * 4)]
+
+
 class CutConfig(C.Structure):
     """rato_cut_config (include/rato_saa.h)"""
     _fields_ = [(k, C.c_int32) for k in ("system", "S", "cap", "keep_max", "keep_recent", "keep_idle", "mode_saa",
@@ -214,6 +222,8 @@ SIGNATURES = {
                                                c_float_p, c_float_p, c_stream]),
     "rato_drone_obstacle_constraints_metric": (C.c_int, [C.POINTER(DroneParams), C.c_int32] + [c_float_p] * 3 + [c_stream]),
     "rato_histogram": (C.c_int, [c_float_p, C.c_int64, C.c_float, C.c_float, C.c_int32, c_float_p, c_stream]),
+    "rato_car_gauss_params_bytes": (C.c_size_t, []),
+    "rato_car_gaussian_linearize": (C.c_int, [C.POINTER(CarGaussParams), C.c_int32] + [c_float_p] * 9 + [c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h
@@ -259,6 +269,9 @@ def load():
     if lib.rato_abi_version() != ABI_VERSION:
         raise RatoError(f"{path} reports ABI version {lib.rato_abi_version()}, this binding needs {ABI_VERSION}: "
                         "rebuild with `python -m riskaversetrajopt_amd._build`")
+    if lib.rato_car_gauss_params_bytes() != C.sizeof(CarGaussParams):
+        raise RatoError(f"rato_car_gauss_params is {lib.rato_car_gauss_params_bytes()} bytes in {path}, "
+                        f"{C.sizeof(CarGaussParams)} in this binding")
     _LIB = lib
     return lib
 

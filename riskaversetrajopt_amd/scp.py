@@ -473,3 +473,100 @@ def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
         print("avar (median) =", out["avar_median"])
         print("cost (median) =", out["cost_median"])
     return out
+
+
+def driving_gaussian_tol():
+    from . import driving_gaussian
+    return driving_gaussian.OSQP_TOL
+
+
+def _gaussian_solve_all(models, us_list, alphas_list, scp_iter, clocks=None):
+    """One lockstep SCP iteration of K driving Gaussian problems: ONE K-problem linearize launch (models[0] launches: the
+    kernel's parameters do not depend on alpha), then K host QPs.  -> ([us], [alphas_risk], [status])"""
+    t0 = time.perf_counter()
+    lin = models[0].linearize_device(np.stack(us_list), np.stack(alphas_list))
+    lin = {k: v.cpu().numpy() for k, v in lin.items()}             # (the copy waits for the launch)
+    t1 = time.perf_counter()
+    us_out, al_out, status = [], [], []
+    for k, m in enumerate(models):
+        m.define_problem(us_list[k], alphas_list[k], scp_iter, lin={key: v[k] for key, v in lin.items()})
+        us, al = m.solve()
+        if not (np.all(np.isfinite(us)) and np.all(np.isfinite(al))):
+            # a solve that hands back no point (qp.OSQP: 'primal infeasible' -> nan): the reference prints and carries the
+            # nan on (:451-452); here the problem keeps its iterate, and the status list says so
+            us, al = np.array(us_list[k]), np.array(alphas_list[k])
+        elif m.res.info.status != 'solved':
+            # an ADMM point that missed eps (iteration cap) may sit outside the QP's own box 100 OSQP_TOL <= alpha_t <= alpha
+            # by more than eps, and ppf(1 - alpha_t) does not exist for alpha_t <= 0: carry its projection onto the box
+            al = np.clip(al, 100 * driving_gaussian_tol(), m.alpha)
+        us_out.append(us)
+        al_out.append(al)
+        status.append(m.res.info.status)
+    if clocks is not None:
+        clocks[0].append(t1 - t0)
+        clocks[1].append(time.perf_counter() - t1)
+    return us_out, al_out, status
+
+
+def run_driving_gaussian_batch(models, num_scp_iters_max=60):
+    """``run_driving_gaussian`` for K ``driving_gaussian.Model``s of one S in lockstep (the reference's four alphas,
+    driving_gaussian.py:469-498): per iteration one K-problem launch and K host QPs.  -> list of the result dicts."""
+    S, outer = models[0].S, models[0].outer_product
+    if any(m.S != S or m.outer_product != outer for m in models):
+        raise ValueError("the models of a lockstep batch share S and outer_product")
+    K = len(models)
+    us_prev = [m.initial_guess_us_mat() for m in models]           # the two warm-up solves (:472-479)
+    al_prev = [m.initial_guess_alphas_risk() for m in models]
+    us, _, _ = _gaussian_solve_all(models, us_prev, al_prev, 0)
+    _gaussian_solve_all(models, us, al_prev, 1)
+    us_prev = [m.initial_guess_us_mat() for m in models]           # restart (:481-482)
+    al_prev = [m.initial_guess_alphas_risk() for m in models]
+    clocks, err, statuses = ([], []), [], []
+    for scp_iter in range(num_scp_iters_max):
+        us, al, st = _gaussian_solve_all(models, us_prev, al_prev, scp_iter, clocks)
+        err.append([L2_error_us(us[k], us_prev[k]) for k in range(K)])
+        statuses.append(st)
+        us_prev, al_prev = us, al                                  # the alphas are carried along (:491-492)
+    xs = models[0].linearize_device(np.stack(us_prev), np.stack(al_prev), want_trajectory=True)["mus"].cpu().numpy()
+    define_s, solve_s = np.array(clocks[0]), np.array(clocks[1])
+    err = np.array(err).reshape(num_scp_iters_max, K)
+    return [{"us": us_prev[k], "alphas_risk": al_prev[k], "xs": xs[k], "L2_error": err[:, k],
+             "status": [st[k] for st in statuses], "define_s": define_s, "solve_s": solve_s} for k in range(K)]
+
+
+def run_driving_gaussian(model, num_scp_iters_max=60):
+    """driving_gaussian.py:471-492: two warm-up solves (scp_iter 0 and 1), restart from the initial guess, then a fixed number
+    of define_problem / solve iterations with the risk allocation carried from one iteration to the next.  -> dict(us (S, 2),
+    alphas_risk (S,), xs (S+1, 8) [the mean trajectory of us], L2_error per iteration, status per solve, define_s, solve_s)"""
+    return run_driving_gaussian_batch([model], num_scp_iters_max)[0]
+
+
+def driving_gaussian_experiment(alphas=(0.01, 0.02, 0.05, 0.1), S=None, iters=60, M_mc=10000, seed=0, results_dir=None,
+                                device='cuda:0'):
+    """The reference's driving Gaussian baseline (driving_gaussian.py:466-498) and its Monte-Carlo report (driving.py:719-739)
+    as one call: the problems of all alphas in lockstep (``run_driving_gaussian_batch``), then ONE ``eval_batch_device`` call of
+    a fresh ``driving.Model(M_mc)`` (drawn under ``np.random.seed(seed)``) over the solutions.  Per alpha
+    percentage_safe = mean(max_t(-distance) - OSQP_TOL <= 1e-6) with the SAA model's OSQP_TOL, as the block computes it, and
+    monte_carlo_cost.  With ``results_dir``: driving_gaussian_alpha=<alpha>.npy holding (us, xs).
+    -> dict(alphas, results [alpha], us (A, S, 2), Z (A, M_mc) [max_t(-distance) - OSQP_TOL per sample], percentage_safe (A,),
+    cost (A,), wall_s)"""
+    from . import driving, driving_gaussian
+    from . import driving_params as P
+    S = P.S if S is None else int(S)
+    alphas = [float(a) for a in alphas]
+    t0 = time.perf_counter()
+    models = [driving_gaussian.Model(alpha=a, S=S, device=device) for a in alphas]
+    results = run_driving_gaussian_batch(models, iters)
+    wall = time.perf_counter() - t0
+    us = np.stack([r["us"] for r in results])
+    np.random.seed(seed)
+    mc_model = driving.Model(M_mc, S=S, device=device)
+    Z, _ = mc_model.eval_batch_device(us, want_stats=False)       # Z = max_t(-distance) - OSQP_TOL (driving.py:630-638)
+    Z = Z.double().cpu().numpy()
+    out = {"alphas": alphas, "results": results, "us": us, "Z": Z, "percentage_safe": np.mean(Z <= 1e-6, axis=1),
+           "cost": np.array([mc_model.monte_carlo_cost(u) for u in us]), "wall_s": wall}
+    if results_dir is not None:
+        os.makedirs(results_dir, exist_ok=True)
+        for a, r in zip(alphas, results):
+            save_results(os.path.join(results_dir, f"driving_gaussian_alpha={a}.npy"), r["us"], r["xs"])
+    return out
