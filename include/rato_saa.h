@@ -95,7 +95,8 @@ extern "C" {
  * rato_copy_async, rato_stream_synchronize, rato_risk_stats_recover; 12: rato_hopper_slip_hessian,
  * rato_hopper_jacobian_nnz / rato_hopper_emit_jacobian_values -- the hopper's jacrev / Lagrangian Hessian in the reference's
  * layout; rato_scp_run_drone / rato_scp_iter -- the reduced SCP loop as one call; rato_car_ego_final_rows, rato_scp_run_car,
- * rato_scp_batch_run_car -- additions within version 12: the same for the driving problem).
+ * rato_scp_batch_run_car -- additions within version 12: the same for the driving problem; rato_drone_rows_plan /
+ * rato_car_rows_plan -- a further addition within version 12: the row kernels' launch geometry as a query).
  * The Python binding refuses a library that reports another version. */
 #define RATO_ABI_VERSION 12
 #define RATO_STATS_IN_LAUNCH 1   /* params.stats_flags */
@@ -298,6 +299,34 @@ int rato_car_stats_in_launch(int32_t M, int32_t S);
  * noise stays cached from one linearization to the next.  factored: the drone's (Phi, W) output. */
 int rato_drone_rows_streaming_stores(int64_t M, int32_t S, int32_t factored);
 int rato_car_rows_streaming_stores(int64_t M, int32_t S);
+/* The launch the row-parallel linearize kernel would get for a batch (csrc/rato_rows_plan.h holds the rule and describes
+ * the three forms): a query, nothing is launched.  cus <= 0: the current device's CU count (256 without a device); with
+ * cus > 0 no device is touched.  queue_available 0: the form taken when the work-queue pool hands out no queue.
+ * switches: the A/B switches as integers, NULL = what this process read from its environment --
+ *   drone   [6] RATO_ROWS_SLOTS_PER_CU, RATO_SMALL_SPLIT, RATO_ROWS_DYNAMIC, RATO_ROWS_QSLOTS, RATO_DYN_TAIL_SPLIT,
+ *               RATO_DYN_TAIL_TILES      (unset: 0, 0, 1, 0, 0, 0)
+ *   driving [5] RATO_CAR_SLOTS_PER_CU, RATO_CAR_SMALL_SPLIT, RATO_ROWS_DYNAMIC, RATO_CAR_TAIL_SPLIT, RATO_CAR_TAIL_TILES
+ *               (unset: 0, -1, 1, 1, -1)
+ * RATO_EINVAL where the row-parallel kernel does not apply (M < 1, S < 2, more than 160 KiB of LDS per workgroup). */
+#define RATO_ROWS_FORM_SPLIT 0    /* every tile dealt to `split` workgroups */
+#define RATO_ROWS_FORM_STATIC 1   /* one tile per workgroup */
+#define RATO_ROWS_FORM_QUEUE 2    /* `workgroups` of them take n_whole whole tiles, then the other tiles' `split` parts */
+typedef struct rato_rows_plan {
+  int32_t n_tiles;       /* ceil(M / 64) */
+  int32_t per_cu;        /* resident workgroups per CU */
+  int32_t slots;         /* cus * per_cu */
+  int32_t qslots;        /* workgroups of the queue form (drone: 0 in the other forms) */
+  int32_t wants_queue;   /* the shape takes a queue when one is available */
+  int32_t form;          /* RATO_ROWS_FORM_* */
+  int32_t split;
+  int32_t n_whole;       /* static form: n_tiles (drone), 0 (driving) */
+  int32_t workgroups;    /* producer workgroups of the launch (statistics workgroups not counted) */
+  int32_t n_units;       /* n_whole + (n_tiles - n_whole) * split */
+} rato_rows_plan;
+int rato_drone_rows_plan(int32_t M, int32_t S, int32_t factored, int32_t cus, int32_t queue_available,
+                         const int32_t* switches, rato_rows_plan* out);
+int rato_car_rows_plan(int32_t M, int32_t S, int32_t cus, int32_t queue_available, const int32_t* switches,
+                       rato_rows_plan* out);
 
 typedef struct rato_car_params {
   int32_t M;

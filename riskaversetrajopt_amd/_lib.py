@@ -43,6 +43,12 @@ class CarGaussParams(C.Structure):
                [("mean_init", C.c_double * 8), ("ped_var_init", C.c_double * 4), ("ego_goal", C.c_double * 4)]
 
 
+class RowsPlan(C.Structure):
+    """rato_rows_plan (include/rato_saa.h): form 0 split, 1 static, 2 queue"""
+    _fields_ = [(k, C.c_int32) for k in ("n_tiles", "per_cu", "slots", "qslots", "wants_queue", "form", "split", "n_whole",
+                                         "workgroups", "n_units")]
+
+
 class CutConfig(C.Structure):
     """rato_cut_config (include/rato_saa.h)"""
     _fields_ = [(k, C.c_int32) for k in ("system", "S", "cap", "keep_max", "keep_recent", "keep_idle", "mode_saa",
@@ -205,6 +211,8 @@ SIGNATURES = {
     "rato_drone_stats_in_launch": (C.c_int, [C.c_int32, C.c_int32]),
     "rato_drone_rows_streaming_stores": (C.c_int, [C.c_int64, C.c_int32, C.c_int32]),
     "rato_car_rows_streaming_stores": (C.c_int, [C.c_int64, C.c_int32]),
+    "rato_drone_rows_plan": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.POINTER(RowsPlan)]),
+    "rato_car_rows_plan": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32), C.POINTER(RowsPlan)]),
     "rato_drone_eval_stats_in_launch": (C.c_int, [C.c_int32]),
     "rato_drone_eval_batch": (C.c_int, [C.POINTER(DroneParams), C.c_int32, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                                         C.c_int64, C.c_double, C.c_float, C.c_void_p, C.c_size_t, c_float_p, c_stream]),

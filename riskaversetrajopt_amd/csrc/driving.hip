@@ -18,6 +18,7 @@
 
 #include "philox.h"
 #include "rato_common.h"
+#include "rato_rows_plan.h"
 #include "rato_select.h"
 
 namespace {
@@ -1139,18 +1140,9 @@ extern "C" int rato_car_eval(const rato_car_params* p, const float* us, const fl
     size_t lds = car_eval_tiles_lds_bytes(p->S);
     const bool in_launch = p->stats_workspace && (p->stats_flags & RATO_STATS_IN_LAUNCH) && rato_car_eval_stats_in_launch(p->M);
     if (in_launch) {
-      int Gs = 0;
-      const int extra = rato_sel::stats_tail_workgroups<RATO_BLOCK>(p->M, Gs);
-      if (extra < 0) return RATO_EINVAL;
-      tail.ws = static_cast<rato_sel::Workspace*>(p->stats_workspace);
-      tail.out = p->stats_out;
-      tail.alpha = p->stats_alpha;
-      tail.thr = p->stats_thr;
-      tail.G = Gs;
-      tail.n_prod = grid;
-      rato_sel::stats_rank(p->M, p->stats_alpha, tail.k, tail.var_is_max);
-      grid_launch = grid + extra;
-      if (lds < rato_sel::rs_body_lds_bytes<RATO_BLOCK>()) lds = rato_sel::rs_body_lds_bytes<RATO_BLOCK>();
+      const int rc = rato_sel::stats_tail_for<RATO_BLOCK>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr, p->M,
+                                                          grid, tail, grid_launch, lds);
+      if (rc != RATO_OK) return rc;
     }
     const int rc = car_eval_tiles_launch(p, 1, us, dW, x0_ped, w_speed, w_rep, Z, p->M, g, tail, grid_launch, lds, n_tiles, st);
     if (rc != RATO_OK) return rc;
@@ -1221,16 +1213,33 @@ unsigned* resolve_car_tile_queues() {
   return hipGetSymbolAddress(&sym, HIP_SYMBOL(g_car_tile_queues)) == hipSuccess ? static_cast<unsigned*>(sym) : nullptr;
 }
 rato::TileQueuePool g_car_queue_pool;
-constexpr size_t CAR_ROWS_LDS_MAX = 160 * 1024;
+constexpr size_t CAR_ROWS_LDS_MAX = rato_plan::LDS_MAX;
+static_assert(CROWS_SAMPLES == rato_plan::TILE, "the launch plan counts tiles of one wave");
 size_t car_rows_lds_bytes(int S) { return car_rows_lds_floats(S) * sizeof(float); }
+// the row kernel as rato_rows_plan.h sees it, and this process' A/B switches (read once)
+rato_plan::Geometry car_rows_geometry(int S) { return {car_rows_lds_bytes(S), CROWS_NW}; }
+const rato_plan::CarSwitches& car_rows_switches() {
+  static const rato_plan::CarSwitches sw = {rato::env_int("RATO_CAR_SLOTS_PER_CU", 0), rato::env_int("RATO_CAR_SMALL_SPLIT", -1),
+                                            rato::env_int("RATO_ROWS_DYNAMIC", 1), rato::env_int("RATO_CAR_TAIL_SPLIT", 1),
+                                            rato::env_int("RATO_CAR_TAIL_TILES", -1)};
+  return sw;
+}
 }  // namespace
 
-// the launcher's store policy for the row-parallel kernel (see rato_drone_rows_streaming_stores)
+// the launcher's store policy for the row-parallel kernel (rato_plan::streaming_stores; per causal pair 2 floats out, per
+// step 2 noise floats in)
 extern "C" int rato_car_rows_streaming_stores(int64_t M, int32_t S) {
-  static const int nt_env = [] { const char* e = getenv("RATO_NT_STORES"); return e ? atoi(e) : 1; }();
-  const double out_bytes = (double)M * (double)rato::pair_row_offset(S) * 2.0 * 4.0;
-  const double in_bytes = (double)M * S * 2.0 * 4.0;
-  return (nt_env == 2 || (nt_env == 1 && out_bytes >= 256e6 && in_bytes <= 128e6)) ? 1 : 0;
+  static const int nt_env = rato::env_int("RATO_NT_STORES", 1);
+  return rato_plan::streaming_stores(nt_env, M, S, 2, 2);
+}
+
+extern "C" int rato_car_rows_plan(int32_t M, int32_t S, int32_t cus, int32_t queue_available, const int32_t* switches,
+                                  rato_rows_plan* out) {
+  if (!out || M <= 0 || S < 2 || car_rows_lds_bytes(S) > CAR_ROWS_LDS_MAX) return RATO_EINVAL;
+  rato_plan::CarSwitches sw = car_rows_switches();
+  if (switches) sw = {switches[0], switches[1], switches[2], switches[3], switches[4]};
+  *out = rato_plan::car_rows(car_rows_geometry(S), M, S, cus > 0 ? cus : g_car_queue_pool.cus(), sw, queue_available != 0);
+  return RATO_OK;
 }
 
 extern "C" int rato_car_linearize_plan(int32_t M, int32_t S, int32_t* cols_per_thread, int32_t* tile) {
@@ -1293,96 +1302,36 @@ int car_linearize_impl(const rato_car_params* p, const float* us, const float* d
       });
       if (e != hipSuccess) return RATO_EHIP - (int)e;
     }
-    const int n_tiles = (p->M + CROWS_SAMPLES - 1) / CROWS_SAMPLES;
-    // large batches: one workgroup per slot + a global tile queue (XCD load balance, see the kernel)
-    const int cus = g_car_queue_pool.cus();
-    int per_cu = (int)(CAR_ROWS_LDS_MAX / lds);
-    if (per_cu > 32 / CROWS_NW) per_cu = 32 / CROWS_NW;
-    if (per_cu < 1) per_cu = 1;
-    static const int slots_env = [] { const char* e = getenv("RATO_CAR_SLOTS_PER_CU"); return e ? atoi(e) : 0; }();   // A/B knob
-    if (slots_env >= 1 && slots_env < per_cu) per_cu = slots_env;
-    const int slots = cus * per_cu;
-    static const int dynamic_env = [] { const char* e = getenv("RATO_ROWS_DYNAMIC"); return e ? atoi(e) : 1; }();
-    unsigned* queue = nullptr;
-    int grid_x = n_tiles;
-    if (dynamic_env && n_tiles > slots)
-      queue = g_car_queue_pool.take(st, resolve_car_tile_queues);   // per stream / per captured launch; none left: static form
-    // At most two queue workgroups per CU even where the LDS allows more (S <= 33).  Measured when the S = 40 layout still
-    // fitted three per CU: same box, alternating (tools/ab_car_slots.sh), 3 -> 2:
-    // C5 shard (M = 125,000) 0.1923-0.1938 -> 0.1846-0.1877 ms (noise read), 0.1768-0.1771 -> 0.1728-0.1734 (regenerated);
-    // M = 1e6 1.162-1.175 -> 1.158-1.163 / 1.105-1.108 -> 1.102-1.111; one per CU: +17 %.  RATO_CAR_SLOTS_PER_CU overrides.
-    // Today S = 40 takes 16,208 floats (64,832 B) per workgroup: the LDS itself allows two per CU, 512 slots on 256 CUs
-    // (tests/_car_shapes.py restates this rule; tests/test_gpu_driving_shapes.py checks the slot count on the device).
-    const int qslots = (slots_env < 1 && per_cu > 2) ? cus * 2 : slots;
-    if (queue) {
-      grid_x = qslots;
-    }
-    // small batches (fewer tiles than workgroup slots): every tile split over several workgroups (>= 4 row tasks each)
-    int split = 1;
-    static const int small_split = [] { const char* e = getenv("RATO_CAR_SMALL_SPLIT"); return e ? atoi(e) : -1; }();
-    if (!queue && n_tiles < slots) {
-      // C3 (M = 1e4: 157 tiles; 768 slots when measured, 512 with today's LDS layout: split 2 either way), same box,
-      // alternating, kern_ms: split 1 / 2 / 3 / 4 = 0.0302-0.0307 /
-      // 0.0279-0.0282 / 0.0270-0.0271 (one run 0.0411) / 0.0360-0.0361: every part rebuilds the fp64 ego tables and
-      // re-stages the noise tile, so two parts per tile is where it stops paying reliably.
-      split = small_split >= 1 ? small_split : (slots / n_tiles >= 2 ? 2 : 1);
-      const int max_split = (p->S + 3) / 4 < 1 ? 1 : (p->S + 3) / 4;
-      if (split > max_split) split = max_split;
-      if (split < 1) split = 1;
-      grid_x = n_tiles * split;
-    }
-    // statistics of Z in extra workgroups of this launch (params.stats_*)
+    // The launch geometry is rato_rows_plan.h's.  A queue (per stream / per captured launch) is taken only for a shape that
+    // wants one; when the pool has none left the shape falls back to the static form.
+    auto plan_with = [&](bool queue_available) {
+      return rato_plan::car_rows(car_rows_geometry(p->S), p->M, p->S, g_car_queue_pool.cus(), car_rows_switches(), queue_available);
+    };
+    rato_rows_plan pl = plan_with(true);
+    unsigned* queue = pl.wants_queue ? g_car_queue_pool.take(st, resolve_car_tile_queues) : nullptr;
+    if (pl.wants_queue && !queue) pl = plan_with(false);
+    // statistics of Z in extra workgroups of this launch (params.stats_*): in the launch only while the whole grid is
+    // resident at once -- no queue; otherwise behind it, below
     rato_sel::StatsTail tail = {};
     size_t lds_launch = lds;
-    int grid_launch = grid_x;
-    // (in the launch only while the whole grid is resident at once -- no queue; otherwise behind it, below)
+    int grid_launch = pl.workgroups;
     const bool stats_behind = p->stats_workspace && queue;
     if (p->stats_workspace && !stats_behind) {
-      int Gs = 0;
-      const int extra = rato_sel::stats_tail_workgroups<CROWS_NW * RATO_WAVE>(p->M, Gs);
-      if (extra < 0) return RATO_EINVAL;   // beyond the one-launch forms of the selection: use rato_risk_stats
-      tail.ws = static_cast<rato_sel::Workspace*>(p->stats_workspace);
-      tail.out = p->stats_out;
-      tail.alpha = p->stats_alpha;
-      tail.thr = p->stats_thr;
-      tail.G = Gs;
-      tail.n_prod = grid_x;
-      rato_sel::stats_rank(p->M, p->stats_alpha, tail.k, tail.var_is_max);
-      grid_launch = grid_x + extra;
-      if (lds_launch < rato_sel::rs_body_lds_bytes<CROWS_NW * RATO_WAVE>()) lds_launch = rato_sel::rs_body_lds_bytes<CROWS_NW * RATO_WAVE>();
+      const int rc = rato_sel::stats_tail_for<CROWS_NW * RATO_WAVE>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr,
+                                                                   p->M, pl.workgroups, tail, grid_launch, lds_launch);
+      if (rc != RATO_OK) return rc;   // beyond the one-launch forms of the selection: use rato_risk_stats
     }
-    dim3 grid(grid_launch), block(CROWS_NW * RATO_WAVE);
-    // streaming stores for the Jacobian when the output is far beyond the memory-side cache and the inputs fit (drone.hip):
-    // C5 shard (800 MB out, 40 MB in) -11.7 %; M = 1e6 (6.4 GB out, 320 MB in) ordinary stores (+2 % with streaming ones)
     const bool nt_stores = rato_car_rows_streaming_stores(p->M, p->S) != 0;
+#define RATO_CROWS_LAUNCH(Q, PH)                                                                                         \
+  hipLaunchKernelGGL((car_linearize_rows_kernel<Q, PH>), dim3(grid_launch), dim3(CROWS_NW * RATO_WAVE), lds_launch, st, *p, \
+                     seed, noise_scale, us, dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, pl.n_tiles, queue, \
+                     pl.split, pl.n_whole, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0))
     if (queue) {
-      // the last `tail_tiles` tiles of the queue as `tail_split` parts each (RATO_CAR_TAIL_SPLIT / RATO_CAR_TAIL_TILES).
-      // OFF by default: unlike the drone's products output it does not pay here -- C5 shard (M = 125,000, 1954 tiles
-      // on 768 slots when measured; 512 queue workgroups with today's LDS layout), same box, alternating
-      // (tools/ab_car_tail.sh), kernel ms: whole tiles 0.1813-0.1816 | halves over
-      // the last 384 / 768 tiles 0.1817-0.1823 / 0.1844-0.1856 | thirds 0.1904-0.1907 | quarters 0.1994-0.2012.
-      static const int tail_split_env = [] { const char* e = getenv("RATO_CAR_TAIL_SPLIT"); return e ? atoi(e) : 1; }();
-      static const int tail_tiles_env = [] { const char* e = getenv("RATO_CAR_TAIL_TILES"); return e ? atoi(e) : -1; }();
-      int tail_split = tail_split_env < 1 ? 1 : tail_split_env;
-      const int max_split = (p->S + 3) / 4 < 1 ? 1 : (p->S + 3) / 4;
-      if (tail_split > max_split) tail_split = max_split;
-      int tail_tiles = tail_tiles_env >= 0 ? tail_tiles_env : qslots / 2;
-      if (tail_tiles > n_tiles) tail_tiles = n_tiles;
-      const int n_whole = tail_split > 1 ? n_tiles - tail_tiles : n_tiles;
-      if (dW)
-        hipLaunchKernelGGL((car_linearize_rows_kernel<true, false>), grid, block, lds_launch, st, *p, seed, noise_scale, us,
-                           dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, n_tiles, queue, tail_split, n_whole, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0));
-      else
-        hipLaunchKernelGGL((car_linearize_rows_kernel<true, true>), grid, block, lds_launch, st, *p, seed, noise_scale, us,
-                           dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, n_tiles, queue, tail_split, n_whole, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0));
+      if (dW) RATO_CROWS_LAUNCH(true, false); else RATO_CROWS_LAUNCH(true, true);
     } else {
-      if (dW)
-        hipLaunchKernelGGL((car_linearize_rows_kernel<false, false>), grid, block, lds_launch, st, *p, seed, noise_scale, us,
-                           dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, n_tiles, queue, split, 0, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0));
-      else
-        hipLaunchKernelGGL((car_linearize_rows_kernel<false, true>), grid, block, lds_launch, st, *p, seed, noise_scale, us,
-                           dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, n_tiles, queue, split, 0, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0));
+      if (dW) RATO_CROWS_LAUNCH(false, false); else RATO_CROWS_LAUNCH(false, true);
     }
+#undef RATO_CROWS_LAUNCH
     RATO_LAUNCH_CHECK();
     if (stats_behind)
       return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace,
@@ -1416,8 +1365,6 @@ extern "C" int rato_car_linearize_philox(const rato_car_params* p, const float* 
                             final_du, final_rhs, -1, stream);
 }
 
-// Would rato_car_linearize (row-parallel kernel) with params.stats_* compute the statistics IN its launch?  (see
-// rato_drone_stats_in_launch)  1 yes, 0 no.
 namespace {
 __global__ __launch_bounds__(RATO_BLOCK) void car_tile_noise_kernel(const float* __restrict__ dW, long M, int nrows,
                                                                    float* __restrict__ out) {
@@ -1454,12 +1401,11 @@ extern "C" int rato_car_linearize_tiled(const rato_car_params* p, const float* u
                             -1, stream, 1);
 }
 
+// Would rato_car_linearize (row-parallel kernel) with params.stats_* compute the statistics IN its launch?  (see
+// rato_drone_stats_in_launch)  1 yes, 0 no.
 extern "C" int rato_car_stats_in_launch(int32_t M, int32_t S) {
   if (M <= 0 || S < 2 || car_rows_lds_bytes(S) > CAR_ROWS_LDS_MAX) return 0;
-  int per_cu = (int)(CAR_ROWS_LDS_MAX / car_rows_lds_bytes(S));
-  if (per_cu > 32 / CROWS_NW) per_cu = 32 / CROWS_NW;
-  if (per_cu < 1) per_cu = 1;
-  const int n_tiles = (M + CROWS_SAMPLES - 1) / CROWS_SAMPLES;
   int G = 0;
-  return n_tiles <= g_car_queue_pool.cus() * per_cu && rato_sel::stats_tail_workgroups<CROWS_NW * RATO_WAVE>(M, G) > 0;
+  return rato_plan::n_tiles(M) <= g_car_queue_pool.cus() * rato_plan::per_cu(car_rows_geometry(S)) &&
+         rato_sel::stats_tail_workgroups<CROWS_NW * RATO_WAVE>(M, G) > 0;
 }

@@ -16,6 +16,7 @@
 #include "philox.h"
 #include "rato_common.h"
 #include <type_traits>
+#include "rato_rows_plan.h"
 #include "rato_select.h"
 
 namespace {
@@ -945,9 +946,8 @@ __host__ __device__ inline size_t rows_lds_floats(int S) {
 // 1-D grid: workgroups [0, n_whole) own one whole tile each; after them every remaining tile is dealt out to `split`
 // workgroups that each rebuild the LDS tables (noise staging + rollout: latency, almost no bandwidth) and take the row
 // tasks congruent to their part (mod split).  Small batches (fewer tiles than workgroup slots) split every tile to
-// fill the chip.  (Large batches CAN split the tiles of the last round into smaller work units to shorten the drain
-// at the end of the launch -- RATO_TAIL_SPLIT / RATO_TAIL_PCT -- but that was measured to cost more than it returns,
-// see the launch code; off by default.)
+// fill the chip; a tile queue (tile_queue != NULL) hands the last tiles out as parts.  The launch forms and the rule that
+// picks one: rato_rows_plan.h.
 // FACT: factored output.  d g[j,t] / d u[s,a] = W[j,t,a] * Phi[t,s,a] with W = -(Q+Q^T)(p_{t+1} - o_j) (the
 // gradient of g wrt position) and Phi = d p_{t+1,a} / d u_{s,a} SHARED by the three obstacles, so the same
 // information is S(S-1) + 6S numbers per sample instead of 3S(S-1): 2.67x less HBM traffic at S = 50, for
@@ -1401,24 +1401,6 @@ int eval_tiles_max_m() {
   static const int64_t v = [] { const char* e = getenv("RATO_EVAL_TILES_MAX_M"); return e ? (int64_t)atoll(e) : EVAL_TILES_MAX_M; }();
   return (int)v;
 }
-// the statistics of Z in extra workgroups of an eval launch with `grid` producer workgroups of NT threads
-template <int NT>
-int stats_tail_for(const void* workspace, double* out, double alpha, float thr, int64_t M, int grid, rato_sel::StatsTail& tail,
-                   int& grid_launch, size_t& lds_launch) {
-  int Gs = 0;
-  const int extra = rato_sel::stats_tail_workgroups<NT>(M, Gs);
-  if (extra < 0) return RATO_EINVAL;
-  tail.ws = static_cast<rato_sel::Workspace*>(const_cast<void*>(workspace));
-  tail.out = out;
-  tail.alpha = alpha;
-  tail.thr = thr;
-  tail.G = Gs;
-  tail.n_prod = grid;
-  rato_sel::stats_rank(M, alpha, tail.k, tail.var_is_max);
-  grid_launch = grid + extra;
-  if (lds_launch < rato_sel::rs_body_lds_bytes<NT>()) lds_launch = rato_sel::rs_body_lds_bytes<NT>();
-  return RATO_OK;
-}
 }  // namespace
 
 // 1 when rato_drone_eval with params.stats_* AND RATO_STATS_IN_LAUNCH in params.stats_flags would compute the statistics in
@@ -1473,8 +1455,8 @@ int drone_eval_impl(const rato_drone_params* p, int32_t metric, const float* us,
     // producers' block size) + the hand-off took 16.  RATO_STATS_IN_LAUNCH in stats_flags asks for the one-launch form.
     const bool in_launch = p->stats_workspace && (p->stats_flags & RATO_STATS_IN_LAUNCH) && rato_drone_eval_stats_in_launch(p->M);
     if (in_launch) {
-      const int rc = stats_tail_for<RATO_BLOCK>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr, p->M, grid, tail,
-                                                grid_launch, lds);
+      const int rc = rato_sel::stats_tail_for<RATO_BLOCK>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr, p->M,
+                                                          grid, tail, grid_launch, lds);
       if (rc != RATO_OK) return rc;
     }
     const int rc = drone_eval_tiles_launch(p, metric, 1, us, dW, mass, Qsym, Z, p->ld, arg, g, tail, grid_launch, lds, n_tiles, st);
@@ -1603,7 +1585,16 @@ int launch_linearize(const rato_drone_params* p, const float* us, const float* d
 // Resolve cols_per_thread / samples_per_lane (0 = choose).  Tuned on MI355X
 // (profiles/): wide lanes once there are enough samples to fill the chip.
 size_t rows_lds_bytes(int S) { return rows_lds_floats(S) * sizeof(float); }
-constexpr size_t ROWS_LDS_MAX = 160 * 1024;
+constexpr size_t ROWS_LDS_MAX = rato_plan::LDS_MAX;
+static_assert(ROWS_SAMPLES == rato_plan::TILE, "the launch plan counts tiles of one wave");
+// the row kernel as rato_rows_plan.h sees it, and this process' A/B switches (read once)
+rato_plan::Geometry rows_geometry(int S) { return {rows_lds_bytes(S), ROWS_NW}; }
+const rato_plan::DroneSwitches& rows_switches() {
+  static const rato_plan::DroneSwitches sw = {rato::env_int("RATO_ROWS_SLOTS_PER_CU", 0), rato::env_int("RATO_SMALL_SPLIT", 0),
+                                              rato::env_int("RATO_ROWS_DYNAMIC", 1),      rato::env_int("RATO_ROWS_QSLOTS", 0),
+                                              rato::env_int("RATO_DYN_TAIL_SPLIT", 0),    rato::env_int("RATO_DYN_TAIL_TILES", 0)};
+  return sw;
+}
 
 bool plan(int32_t M, int32_t S, int32_t ld, int32_t* cpt, int32_t* spl) {
   if (M <= 0 || S <= 0 || ld < M) return false;
@@ -1728,116 +1719,33 @@ int drone_linearize_impl(const rato_drone_params* p, const float* us, const floa
       });
       if (e != hipSuccess) return RATO_EHIP - (int)e;
     }
-    // Small batches (fewer tiles than resident workgroup slots) deal each tile's row tasks out to
-    // row_split workgroups so that the chip is filled (M = 1e4, S = 50: 81 -> 72 us).  Splitting only
-    // the tiles of an incomplete last round of a large batch was measured and does not pay
-    // (M = 1e5: 0.627 -> 0.648 ms), so large batches use one workgroup per tile.
-    const int cus = device_cus();
-    int per_cu = (int)(ROWS_LDS_MAX / lds);
-    if (per_cu > 32 / ROWS_NW) per_cu = 32 / ROWS_NW;
-    if (per_cu < 1) per_cu = 1;
-    // RATO_ROWS_SLOTS_PER_CU: A/B knob -- fewer queue workgroups than the LDS allows (one per CU = 256 store streams)
-    static const int slots_env = [] { const char* e = getenv("RATO_ROWS_SLOTS_PER_CU"); return e ? atoi(e) : 0; }();
-    if (slots_env >= 1 && slots_env < per_cu) per_cu = slots_env;
-    const int slots = cus * per_cu;
-    const int n_tiles = (p->M + ROWS_SAMPLES - 1) / ROWS_SAMPLES;
-    const int max_split = (p->S + 3) / 4 < 1 ? 1 : (p->S + 3) / 4;   // keep >= 4 row tasks per workgroup
-    int split = 1, n_whole = n_tiles;
-    if (n_tiles < slots) {   // small batch: every tile split so that the chip is filled (M = 1e4, S = 50: 81 -> 72 us)
-      static const int small_split_env = [] { const char* e = getenv("RATO_SMALL_SPLIT"); return e ? atoi(e) : 0; }();   // A/B
-      // Re-measured with the tiles on 2 MiB boundaries (RATO_SMALL_SPLIT sweep, kernel ms, products / factored):
-      // M = 2000 (32 tiles): split 1 0.0439 / 0.0387, 2 0.0339 / 0.0336, 4 0.0342 / 0.0340, slots / n_tiles 0.0378 / 0.0376;
-      // M = 5000: 1 0.0456 / 0.0397, 2 0.0389 / 0.0349, 4 0.0453 / 0.0387; M = 1e4 (C2): 1 0.0609, 2 0.0645, 3 0.0653;
-      // M = 2e4: 1 0.1208 / 0.0632, 2 0.1213 / 0.0731 -> two parts while that still leaves one workgroup per CU, else none.
-      split = small_split_env > 0 ? small_split_env : (2 * n_tiles <= cus ? 2 : 1);
-      if (split > max_split) split = max_split;
-      if (split < 1) split = 1;
-      n_whole = split > 1 ? 0 : n_tiles;
-    }
-    // (Splitting the tiles of the last round of a STATIC grid was measured twice and rejected: every extra work unit
-    // spends ~15-25 us staging and rolling out in one of only 512 LDS-limited slots -- profiles/README.md.)
-    int grid = n_whole + (n_tiles - n_whole) * split, stride = 0;
-    unsigned* queue = nullptr;
-    // Large batches: a grid that fills every slot once + a global tile counter (see the kernel).  Why: with one tile
-    // per workgroup the timeline (tools/timeline.py, -DRATO_DIAG=4, M = 1e5) shows the workgroups with an even block
-    // index -- every other XCD -- running their tiles in 145-151 us and the odd ones in 174-176 us, the hardware
-    // having dealt the grid out to the XCDs in advance: the fast half of the chip is done at 500-518 us and idles
-    // until the slow half finishes at 585-590 us.  RATO_ROWS_DYNAMIC=0 switches it off (the bit-identity test's base).
-    static const int dynamic_env = [] { const char* e = getenv("RATO_ROWS_DYNAMIC"); return e ? atoi(e) : 1; }();
-    if (split == 1 && n_tiles > slots) {
-      if (dynamic_env >= 1) {
-        // Measured, same box, alternating (profiles/r02_ab_rows.txt): factored output -7 % at M = 1e5, -9 % at M = 1e6;
-        // products output -1.5 % at M = 1e5, and -- since its tiles start on 2 MiB boundaries (rato_packed_tile_stride)
-        // -- also at large batches: M = 4e5 2.148 / 2.147 ms against 2.176 / 2.213 static, M = 1e6 5.298 / 5.369 against
-        // 5.344 / 5.477 (tools/ab_big_products.sh; with the tiles back to back the queue had cost +1.3 % / +5 % there).
-        // 64 two-word queues in device memory, handed out round robin: launches that overlap on different streams get
-        // different queues; each launch leaves its queue zeroed.  (Address looked up once, outside any capture.)
-        queue = take_tile_queue(st);
-        if (queue) {
-          // Products output, four or more rounds of tiles: ONE queue workgroup per CU (256 store streams instead of
-          // 512) is as fast or faster than the two the LDS allows -- same box, alternating (tools/ab_slots.sh,
-          // ab_slots2.sh), 2 -> 1 per CU: M = 1e5 0.5600 -> 0.5605 ms (noise read) / 0.5355 -> 0.5256 (regenerated),
-          // 2e5 1.110 -> 1.102 / 1.050 -> 1.025, 1e6 5.425 -> 5.311 / 5.097 -> 5.025; at 5e4 +1.2 % / -1.2 %.
-          // The factored output needs the second workgroup (its tiles are a third as long: 0.2455 -> 0.2648 ms).
-          // RATO_ROWS_SLOTS_PER_CU overrides.
-          static const int qslots_env = [] { const char* e = getenv("RATO_ROWS_QSLOTS"); return e ? atoi(e) : 0; }();   // A/B: absolute
-          const int qslots = qslots_env > 0 ? qslots_env : ((!W && slots_env < 1 && n_tiles >= 1024) ? cus : slots);
-          grid = qslots;
-          // Products output: the LAST tiles are handed out in row-interleaved parts (round 3: quarters of the last slots / 2
-          // tiles; round 6: halves of the last `slots` tiles, below).
-          // The drain at the end of the launch is bounded per workgroup (~19 GB/s each, whatever the residency), so
-          // shorter last units shorten it; the re-staging they cost is paid while the chip is still full.  Same box,
-          // alternating, 100 steps (tools/dyn_tail_sweep.sh): 0.5543-0.5576 -> 0.5415-0.5440 ms (-2.4 %, 0.704-0.708
-          // of 8 TB/s); halves over the last 1024 tiles -1 %; thirds / sixths / eighths no better.  The factored
-          // output loses with any split (its tiles are short already) and keeps whole tiles.
-          // RATO_DYN_TAIL_SPLIT x RATO_DYN_TAIL_TILES override (split 1 = whole tiles only).
-          static const int dts = [] { const char* e = getenv("RATO_DYN_TAIL_SPLIT"); return e ? atoi(e) : 0; }();
-          static const int dtt = [] { const char* e = getenv("RATO_DYN_TAIL_TILES"); return e ? atoi(e) : 0; }();
-          // Round 6, re-measured on three boards (same board, alternating, kernel ms by events; tools/ab.sh): quarters over
-          // the last 128 tiles (the round-3 choice) 0.5139 / 0.5076 / 0.5135, whole tiles 0.5117 / 0.5036 / 0.5117, HALVES
-          // over the last 128 / 256 / 384 tiles 0.5059 / 0.4980 / 0.5004, 0.5067 / 0.5055 / 0.4986, 0.4984 / 0.5046 / 0.4969;
-          // eighths 0.523-0.538.  Since the streaming stores (round 4) a re-staged unit costs more than it did (its noise is
-          // no longer re-read from HBM by anyone else in between): halves over the last round of tiles are the default.
-          int want_split = dts > 0 ? dts : (W ? 1 : 2);
-          int want_tiles = dtt > 0 ? dtt : qslots;
-          if (want_split > max_split) want_split = max_split;
-          if (want_split > 1 && want_tiles > 0) {
-            split = want_split;
-            // (RATO_ROWS_QSLOTS above the tile count: no tail at all.  Unclamped, n_tiles - qslots < 0 pushed n_whole past
-            // n_tiles and the unit count below it: S = 90, M = 20,001 with 512 queue workgroups ran 114 of 313 tiles.)
-            const int tail_max = n_tiles > qslots ? n_tiles - qslots : 0;
-            n_whole = n_tiles - (want_tiles < tail_max ? want_tiles : tail_max);
-          }
-        }
-      }
-    }
-    // statistics of Z in extra workgroups of this launch (params.stats_*)
+    // The launch geometry is rato_rows_plan.h's.  A queue is taken only for a shape that wants one (a captured launch
+    // consumes an entry of the pool for good; launches that overlap on different streams get different queues, and each
+    // launch leaves its queue zeroed); when the pool has none left the shape falls back to the static form.
+    const bool factored = W != nullptr;
+    auto plan_with = [&](bool queue_available) {
+      return rato_plan::drone_rows(rows_geometry(p->S), p->M, p->S, factored, device_cus(), rows_switches(), queue_available);
+    };
+    rato_rows_plan pl = plan_with(true);
+    unsigned* queue = pl.wants_queue ? take_tile_queue(st) : nullptr;
+    if (pl.wants_queue && !queue) pl = plan_with(false);
+    // statistics of Z in extra workgroups of this launch (params.stats_*): in the launch only while the whole grid is
+    // resident at once -- no queue; otherwise behind it, below
     rato_sel::StatsTail tail = {};
     size_t lds_launch = lds;
-    int grid_launch = grid;
-    // (in the launch only while the whole grid is resident at once -- no queue; otherwise behind it, below)
+    int grid_launch = pl.workgroups;
     const bool stats_behind = p->stats_workspace && queue;
     if (p->stats_workspace && !stats_behind) {
-      int Gs = 0;
-      const int extra = rato_sel::stats_tail_workgroups<ROWS_NW * RATO_WAVE>(p->M, Gs);
-      if (extra < 0) return RATO_EINVAL;   // beyond the one-launch forms of the selection: use rato_risk_stats
-      tail.ws = static_cast<rato_sel::Workspace*>(p->stats_workspace);
-      tail.out = p->stats_out;
-      tail.alpha = p->stats_alpha;
-      tail.thr = p->stats_thr;
-      tail.G = Gs;
-      tail.n_prod = grid;
-      rato_sel::stats_rank(p->M, p->stats_alpha, tail.k, tail.var_is_max);
-      grid_launch = grid + extra;
-      if (lds_launch < rato_sel::rs_body_lds_bytes<ROWS_NW * RATO_WAVE>()) lds_launch = rato_sel::rs_body_lds_bytes<ROWS_NW * RATO_WAVE>();
+      const int rc = rato_sel::stats_tail_for<ROWS_NW * RATO_WAVE>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr,
+                                                                  p->M, pl.workgroups, tail, grid_launch, lds_launch);
+      if (rc != RATO_OK) return rc;   // beyond the one-launch forms of the selection: use rato_risk_stats
     }
-    // streaming stores for the Jacobian: when the output cannot stay in the 256 MB memory-side cache anyway and the batch's
-    // inputs (the noise) can -- RATO_NT_STORES=0 never / 2 always (A/B).  M = 1e5, S = 50: 3 GB out, 60 MB in: yes.
-    const bool nt_stores = rato_drone_rows_streaming_stores(p->M, p->S, W ? 1 : 0) != 0;
+    const bool nt_stores = rato_drone_rows_streaming_stores(p->M, p->S, factored) != 0;
 #define RATO_ROWS_LAUNCH(F, PH)                                                                                     \
   hipLaunchKernelGGL((drone_linearize_rows_kernel<F, PH>), dim3(grid_launch), dim3(ROWS_NW * RATO_WAVE), lds_launch, st, \
-                     *p, n_whole, split, stride, n_tiles, queue, seed, noise_scale, us, dW, mass, Qsym, G, W, A22, g_up, \
-                     Z, part, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0) | ((RATO_DIAG == 4 && getenv("RATO_DIAG_WAIT")) ? 4 : 0))
+                     *p, pl.n_whole, pl.split, /* tile_stride */ 0, pl.n_tiles, queue, seed, noise_scale, us, dW, mass, Qsym, \
+                     G, W, A22, g_up, Z, part, tail,                                                                \
+                     (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0) | ((RATO_DIAG == 4 && getenv("RATO_DIAG_WAIT")) ? 4 : 0))
     if (W) {
       if (dW) RATO_ROWS_LAUNCH(true, false); else RATO_ROWS_LAUNCH(true, true);
     } else {
@@ -1867,11 +1775,19 @@ int drone_linearize_impl(const rato_drone_params* p, const float* us, const floa
 
 // The launcher's store policy for the row-parallel kernel (1: the Jacobian goes out as streaming stores): when the output
 // cannot stay in the 256 MB memory-side cache anyway (>= 256 MB) and the batch's noise can (<= 128 MB).
+// (rato_plan::streaming_stores; per causal pair 2 factor / 6 product floats out, per step 3 noise floats in)
 extern "C" int rato_drone_rows_streaming_stores(int64_t M, int32_t S, int32_t factored) {
-  static const int nt_env = [] { const char* e = getenv("RATO_NT_STORES"); return e ? atoi(e) : 1; }();
-  const double out_bytes = (double)M * (double)rato::pair_row_offset(S) * (factored ? 2.0 : 6.0) * 4.0;
-  const double in_bytes = (double)M * S * 3.0 * 4.0;
-  return (nt_env == 2 || (nt_env == 1 && out_bytes >= 256e6 && in_bytes <= 128e6)) ? 1 : 0;
+  static const int nt_env = rato::env_int("RATO_NT_STORES", 1);
+  return rato_plan::streaming_stores(nt_env, M, S, factored ? 2 : 6, 3);
+}
+
+extern "C" int rato_drone_rows_plan(int32_t M, int32_t S, int32_t factored, int32_t cus, int32_t queue_available,
+                                    const int32_t* switches, rato_rows_plan* out) {
+  if (!out || M <= 0 || S < 2 || rows_lds_bytes(S) > ROWS_LDS_MAX) return RATO_EINVAL;
+  rato_plan::DroneSwitches sw = rows_switches();
+  if (switches) sw = {switches[0], switches[1], switches[2], switches[3], switches[4], switches[5]};
+  *out = rato_plan::drone_rows(rows_geometry(S), M, S, factored != 0, cus > 0 ? cus : device_cus(), sw, queue_available != 0);
+  return RATO_OK;
 }
 
 extern "C" int rato_drone_linearize(const rato_drone_params* p, const float* us, const float* dW,
@@ -1943,10 +1859,7 @@ extern "C" int rato_drone_linearize_tiled(const rato_drone_params* p, const floa
 // statistics of larger batches into their partial-sum launch instead.)  1 yes, 0 no.
 extern "C" int rato_drone_stats_in_launch(int32_t M, int32_t S) {
   if (M <= 0 || S < 2 || rows_lds_bytes(S) > ROWS_LDS_MAX) return 0;
-  int per_cu = (int)(ROWS_LDS_MAX / rows_lds_bytes(S));
-  if (per_cu > 32 / ROWS_NW) per_cu = 32 / ROWS_NW;
-  if (per_cu < 1) per_cu = 1;
-  const int n_tiles = (M + ROWS_SAMPLES - 1) / ROWS_SAMPLES;
   int G = 0;
-  return n_tiles <= device_cus() * per_cu && rato_sel::stats_tail_workgroups<ROWS_NW * RATO_WAVE>(M, G) > 0;
+  return rato_plan::n_tiles(M) <= device_cus() * rato_plan::per_cu(rows_geometry(S)) &&
+         rato_sel::stats_tail_workgroups<ROWS_NW * RATO_WAVE>(M, G) > 0;
 }

@@ -168,6 +168,12 @@ __device__ __forceinline__ void store_streaming(float* p, float v) {
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// an integer switch from the environment (atoi; unset = dflt): for the initialiser of a function-local static
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 static inline int nblocks_for(int32_t M) { return (M + RATO_BLOCK - 1) / RATO_BLOCK; }
 
 // Work queues of the dynamic launch forms (row-parallel linearize kernels, eval): each queue is two device words

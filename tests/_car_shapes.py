@@ -26,7 +26,7 @@ RS_SMALL_MAX, RS_COOP_KEYS, RS_COOP_MAX_WG = 12 * 1024, 16, 64   # rato_select.h
 
 
 def car_rows_lds_bytes(S):
-    """car_rows_lds_floats(S) * 4 (driving.hip:547-552)"""
+    """car_rows_lds_floats(S) * 4 (driving.hip)"""
     return 4 * (S * TILE * 6 + (S + 1) * 2 + S * 8 + S * 2 + 4 + (S + 1) * 2 + NW * 4 + (S + 1) * 6 + 2)
 
 
@@ -36,7 +36,7 @@ def _env_int(env, name, default):
 
 
 def _per_cu(S):
-    """driving.hip:1299-1301 (and rato_car_stats_in_launch, :1454-1456)"""
+    """rato_plan::per_cu (rato_rows_plan.h) for the driving kernel's geometry"""
     return max(1, min(LDS_MAX // car_rows_lds_bytes(S), 32 // NW))
 
 
@@ -48,32 +48,66 @@ def stats_tail_workgroups(M, NT=NW * 64):
     return -1 if g * NT * RS_COOP_KEYS < M else g
 
 
-def car_rows_shape(M, S, cus=CUS, env=None):
-    """The launch car_linearize_impl makes for the row kernel (driving.hip:1296-1370) under the switches in ``env``
-    (RATO_CAR_SLOTS_PER_CU, RATO_ROWS_DYNAMIC, RATO_CAR_SMALL_SPLIT, RATO_CAR_TAIL_SPLIT, RATO_CAR_TAIL_TILES; read as
-    the library reads them).  form: 'split' (every tile dealt to `split` workgroups), 'static' (one tile per
-    workgroup) or 'queue' (qslots workgroups take tiles from a global counter; the last n_tiles - n_whole tiles as
-    `split` parts each).  stats_in_launch: rato_car_stats_in_launch (:1452-1460), which ignores the switches."""
+SWITCHES = (("RATO_CAR_SLOTS_PER_CU", 0), ("RATO_CAR_SMALL_SPLIT", -1), ("RATO_ROWS_DYNAMIC", 1), ("RATO_CAR_TAIL_SPLIT", 1),
+            ("RATO_CAR_TAIL_TILES", -1))          # rato_car_rows_plan's `switches`, in its order, with the unset values
+FORMS = ("split", "static", "queue")             # RATO_ROWS_FORM_*
+PLAN_FIELDS = ("n_tiles", "per_cu", "slots", "qslots", "wants_queue", "form", "split", "n_whole", "workgroups", "n_units")
+
+
+def switch_array(env, switches):
+    """the switches of ``env`` as the int32 array the library's plan queries take"""
+    import ctypes as C
+    return (C.c_int32 * len(switches))(*[_env_int(env or {}, name, unset) for name, unset in switches])
+
+
+def plan_fields(out):
+    """a filled rato_rows_plan as a dict in the restatements' terms (form by name, wants_queue a bool)"""
+    d = {k: getattr(out, k) for k in PLAN_FIELDS}
+    d["form"], d["wants_queue"] = FORMS[d["form"]], bool(d["wants_queue"])
+    return d
+
+
+def library_plan(lib, M, S, cus=CUS, env=None, have_queue=True):
+    """rato_car_rows_plan: the rule the launcher itself runs (csrc/rato_rows_plan.h), the switches passed explicitly;
+    cus <= 0 asks the device; env = "process": the switches this process' library read from its environment"""
+    import ctypes as C
+    from riskaversetrajopt_amd import _lib
+    out = _lib.RowsPlan()
+    sw = None if env == "process" else switch_array(env, SWITCHES)
+    assert lib.rato_car_rows_plan(M, S, cus, int(have_queue), sw, C.byref(out)) == 0, (M, S)
+    return plan_fields(out)
+
+
+def car_rows_shape(M, S, cus=CUS, env=None, have_queue=True):
+    """The launch car_linearize_impl makes for the row kernel: an independent restatement of rato_plan::car_rows
+    (csrc/rato_rows_plan.h), which tests/test_car_shapes.py compares with the library's rato_car_rows_plan field by
+    field, under the switches in ``env`` (RATO_CAR_SLOTS_PER_CU, RATO_ROWS_DYNAMIC, RATO_CAR_SMALL_SPLIT,
+    RATO_CAR_TAIL_SPLIT, RATO_CAR_TAIL_TILES; read as the library reads them).  form: 'split' (every tile dealt to
+    `split` workgroups), 'static' (one tile per workgroup) or 'queue' (qslots workgroups take tiles from a global
+    counter; the last n_tiles - n_whole tiles as `split` parts each).  have_queue=False: the work-queue pool handed out
+    none, the shape keeps the static form (``queue``: the form is the queue; ``wants_queue``: it would be with one).
+    stats_in_launch: rato_car_stats_in_launch, which ignores the switches."""
     env = {} if env is None else env
     lds = car_rows_lds_bytes(S)
     if S < 2 or lds > LDS_MAX:
         raise ValueError(f"S = {S}: not the row kernel ({lds} B of LDS)")
     n_tiles = (M + TILE - 1) // TILE
     per_cu = _per_cu(S)
-    slots_env = _env_int(env, "RATO_CAR_SLOTS_PER_CU", 0)                      # :1302-1303
+    slots_env = _env_int(env, "RATO_CAR_SLOTS_PER_CU", 0)
     if 1 <= slots_env < per_cu:
         per_cu = slots_env
-    slots = cus * per_cu                                                       # :1304
-    queue = _env_int(env, "RATO_ROWS_DYNAMIC", 1) != 0 and n_tiles > slots     # :1308
-    qslots = cus * 2 if (slots_env < 1 and per_cu > 2) else slots             # :1313
-    max_split = max(1, (S + 3) // 4)                                           # :1325, :1362
-    if queue:                                                                  # :1359-1366
+    slots = cus * per_cu
+    wants_queue = _env_int(env, "RATO_ROWS_DYNAMIC", 1) != 0 and n_tiles > slots
+    queue = wants_queue and have_queue
+    qslots = cus * 2 if (slots_env < 1 and per_cu > 2) else slots             # at most two queue workgroups per CU
+    max_split = max(1, (S + 3) // 4)                                           # rato_plan::max_split
+    if queue:                                                                  # the queue and its tail parts
         split = min(max(1, _env_int(env, "RATO_CAR_TAIL_SPLIT", 1)), max_split)
         tail_env = _env_int(env, "RATO_CAR_TAIL_TILES", -1)
         tail_tiles = min(tail_env if tail_env >= 0 else qslots // 2, n_tiles)
         n_whole = n_tiles - tail_tiles if split > 1 else n_tiles
         workgroups, form = qslots, "queue"
-    else:                                                                      # :1318-1329
+    else:                                                                      # static, or every tile split
         split = 1
         if n_tiles < slots:
             small = _env_int(env, "RATO_CAR_SMALL_SPLIT", -1)
@@ -81,15 +115,15 @@ def car_rows_shape(M, S, cus=CUS, env=None):
             split = max(1, min(split, max_split))
         n_whole, workgroups = 0, n_tiles * split
         form = "split" if split > 1 else "static"
-    n_units = n_whole + (n_tiles - n_whole) * split                            # kernel :692
+    n_units = n_whole + (n_tiles - n_whole) * split                            # the kernel's unit count
     in_launch = n_tiles <= cus * _per_cu(S) and stats_tail_workgroups(M) > 0
     return dict(M=M, S=S, cus=cus, lds_bytes=lds, n_tiles=n_tiles, per_cu=per_cu, slots=slots, qslots=qslots,
-                queue=queue, form=form, split=split, n_whole=n_whole, parted_tiles=n_tiles - n_whole if split > 1 else 0,
+                wants_queue=wants_queue, queue=queue, form=form, split=split, n_whole=n_whole, parted_tiles=n_tiles - n_whole if split > 1 else 0,
                 workgroups=workgroups, n_units=n_units, stats_in_launch=in_launch)
 
 
 def units(shape):
-    """The kernel's unit -> (tile, part_id, row_split) mapping (driving.hip:706-716) for every unit of a launch"""
+    """The kernel's unit -> (tile, part_id, row_split) mapping (car_linearize_rows_kernel) for every unit of a launch"""
     out = []
     loop = shape["queue"]
     for u in range(shape["n_units"]):

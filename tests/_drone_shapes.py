@@ -18,7 +18,8 @@ import numpy as np
 
 from oracle import drone as od
 from tests import _tol as tol
-from tests._car_shapes import TILE, _check_abs, _check_rowmax, _env_int, _first_bad, sample_set, stats_tail_workgroups  # noqa: F401
+from tests._car_shapes import (PLAN_FIELDS, TILE, _check_abs, _check_rowmax, _env_int, _first_bad, plan_fields,  # noqa: F401
+                               sample_set, stats_tail_workgroups, switch_array)
 
 NW = 8                       # ROWS_NW: waves per workgroup
 LDS_MAX = 160 * 1024         # ROWS_LDS_MAX
@@ -29,61 +30,80 @@ RHS_MEAN_ATOL = 2e-5                 # rhs_sum / M (with MEAN_RTOL), as tests/te
 
 
 def rows_lds_bytes(S):
-    """rows_lds_floats(S) * 4 (drone.hip:906-909)"""
+    """rows_lds_floats(S) * 4 (drone.hip)"""
     return 4 * (S * TILE * 5 + S * 3 + 4)
 
 
 def _per_cu(S):
-    """drone.hip:1641-1643 (and rato_drone_stats_in_launch, :1848-1850)"""
+    """rato_plan::per_cu (rato_rows_plan.h) for the drone kernel's geometry"""
     return max(1, min(LDS_MAX // rows_lds_bytes(S), 32 // NW))
 
 
-def drone_rows_shape(M, S, factored, cus=CUS, env=None):
-    """The launch drone_linearize_impl makes for the row kernel (drone.hip:1640-1712) under the switches in ``env``
-    (RATO_ROWS_SLOTS_PER_CU, RATO_SMALL_SPLIT, RATO_ROWS_DYNAMIC, RATO_ROWS_QSLOTS, RATO_DYN_TAIL_SPLIT,
-    RATO_DYN_TAIL_TILES; read as the library reads them: atoi, unset = the default).  form: 'split' (every tile dealt
-    to `split` workgroups), 'static' (one tile per workgroup) or 'queue' (`workgroups` of them take units from a global
-    counter: n_whole whole tiles, then the last n_tiles - n_whole tiles as `split` row-interleaved parts each).
-    stats_in_launch: rato_drone_stats_in_launch (:1846-1854), which ignores the switches."""
+SWITCHES = (("RATO_ROWS_SLOTS_PER_CU", 0), ("RATO_SMALL_SPLIT", 0), ("RATO_ROWS_DYNAMIC", 1), ("RATO_ROWS_QSLOTS", 0),
+            ("RATO_DYN_TAIL_SPLIT", 0), ("RATO_DYN_TAIL_TILES", 0))   # rato_drone_rows_plan's `switches`, in its order, with
+                                                                      # the unset values
+
+
+def library_plan(lib, M, S, factored, cus=CUS, env=None, have_queue=True):
+    """rato_drone_rows_plan: the rule the launcher itself runs (csrc/rato_rows_plan.h), the switches passed explicitly;
+    cus <= 0 asks the device; env = "process": the switches this process' library read from its environment"""
+    import ctypes as C
+    from riskaversetrajopt_amd import _lib
+    out = _lib.RowsPlan()
+    sw = None if env == "process" else switch_array(env, SWITCHES)
+    assert lib.rato_drone_rows_plan(M, S, int(factored), cus, int(have_queue), sw, C.byref(out)) == 0, (M, S)
+    return plan_fields(out)
+
+
+def drone_rows_shape(M, S, factored, cus=CUS, env=None, have_queue=True):
+    """The launch drone_linearize_impl makes for the row kernel: an independent restatement of rato_plan::drone_rows
+    (csrc/rato_rows_plan.h), which tests/test_drone_shapes.py compares with the library's rato_drone_rows_plan field by
+    field, under the switches in ``env`` (RATO_ROWS_SLOTS_PER_CU, RATO_SMALL_SPLIT, RATO_ROWS_DYNAMIC, RATO_ROWS_QSLOTS,
+    RATO_DYN_TAIL_SPLIT, RATO_DYN_TAIL_TILES; read as the library reads them: atoi, unset = the default).  form: 'split'
+    (every tile dealt to `split` workgroups), 'static' (one tile per workgroup) or 'queue' (`workgroups` of them take
+    units from a global counter: n_whole whole tiles, then the last n_tiles - n_whole tiles as `split` row-interleaved
+    parts each).  have_queue=False: the work-queue pool handed out none, the shape keeps the static form.
+    stats_in_launch: rato_drone_stats_in_launch, which ignores the switches."""
     env = {} if env is None else env
     lds = rows_lds_bytes(S)
     if S < 2 or lds > LDS_MAX:
         raise ValueError(f"S = {S}: not the row kernel ({lds} B of LDS)")
     n_tiles = (M + TILE - 1) // TILE
     per_cu = _per_cu(S)
-    slots_env = _env_int(env, "RATO_ROWS_SLOTS_PER_CU", 0)                     # :1645-1646
+    slots_env = _env_int(env, "RATO_ROWS_SLOTS_PER_CU", 0)
     if 1 <= slots_env < per_cu:
         per_cu = slots_env
-    slots = cus * per_cu                                                       # :1647
-    max_split = max(1, (S + 3) // 4)                                           # :1649
+    slots = cus * per_cu
+    max_split = max(1, (S + 3) // 4)                                           # rato_plan::max_split
     split, n_whole, form, qslots = 1, n_tiles, "static", 0
-    if n_tiles < slots:                                                        # :1651-1661
+    if n_tiles < slots:                                                        # small batch
         small = _env_int(env, "RATO_SMALL_SPLIT", 0)
         split = small if small > 0 else (2 if 2 * n_tiles <= cus else 1)
         split = max(1, min(split, max_split))
         n_whole = 0 if split > 1 else n_tiles
         form = "split" if split > 1 else "static"
-    workgroups = n_whole + (n_tiles - n_whole) * split                         # :1664
-    if split == 1 and n_tiles > slots and _env_int(env, "RATO_ROWS_DYNAMIC", 1) >= 1:   # :1672-1673
+    workgroups = n_whole + (n_tiles - n_whole) * split
+    wants_queue = split == 1 and n_tiles > slots and _env_int(env, "RATO_ROWS_DYNAMIC", 1) >= 1
+    if wants_queue and have_queue:
         form = "queue"
-        qslots_env = _env_int(env, "RATO_ROWS_QSLOTS", 0)                      # :1688-1690
+        qslots_env = _env_int(env, "RATO_ROWS_QSLOTS", 0)
         qslots = qslots_env if qslots_env > 0 else (cus if (not factored and slots_env < 1 and n_tiles >= 1024) else slots)
         workgroups = qslots
         dts, dtt = _env_int(env, "RATO_DYN_TAIL_SPLIT", 0), _env_int(env, "RATO_DYN_TAIL_TILES", 0)
-        want_split = min(dts if dts > 0 else (1 if factored else 2), max_split)        # :1706-1708
+        want_split = min(dts if dts > 0 else (1 if factored else 2), max_split)
         want_tiles = dtt if dtt > 0 else qslots
-        if want_split > 1 and want_tiles > 0:                                  # :1709-1714
+        if want_split > 1 and want_tiles > 0:
             split = want_split
             n_whole = n_tiles - min(want_tiles, max(n_tiles - qslots, 0))       # (more workgroups than tiles: no tail)
-    n_units = n_whole + (n_tiles - n_whole) * split                            # kernel :968
+    n_units = n_whole + (n_tiles - n_whole) * split                            # the kernel's unit count
     in_launch = n_tiles <= cus * _per_cu(S) and stats_tail_workgroups(M, NW * 64) > 0
     return dict(M=M, S=S, factored=bool(factored), cus=cus, lds_bytes=lds, n_tiles=n_tiles, per_cu=per_cu, slots=slots,
-                qslots=qslots, form=form, split=split, n_whole=n_whole, workgroups=workgroups, n_units=n_units,
+                qslots=qslots, wants_queue=wants_queue, form=form, split=split, n_whole=n_whole, workgroups=workgroups, n_units=n_units,
                 stats_in_launch=in_launch)
 
 
 def unit_table(shape):
-    """the kernel's unit -> (tile, part_id, row_split) mapping (drone.hip:968-973) as three arrays over the units"""
+    """the kernel's unit -> (tile, part_id, row_split) mapping (drone_linearize_rows_kernel) as three arrays over the units"""
     u = np.arange(max(shape["n_units"], 0))
     n_whole, s = shape["n_whole"], shape["split"]
     whole = u < n_whole
@@ -93,8 +113,8 @@ def unit_table(shape):
 
 def units(shape):
     """[(tile, part_id, row_split, writes_Z, axes)] for every unit of a launch.  Part p of row_split takes the row tasks
-    t = p (mod row_split); it writes Z iff S % row_split == p (drone.hip:1166) and the rows of ``part`` of the axes a
-    with a % row_split == p (:1169-1195)."""
+    t = p (mod row_split); it writes Z iff S % row_split == p and the rows of ``part`` of the axes a with
+    a % row_split == p (drone_linearize_rows_kernel's final-state task)."""
     S = shape["S"]
     return [(int(t), int(p), int(rs), S % rs == p, tuple(a for a in range(3) if a % rs == p))
             for t, p, rs in zip(*unit_table(shape))]
@@ -115,7 +135,7 @@ def oracle_model(dW, mass, Qsym):
 
 
 def compact_final(fdu, rhs):
-    """(n, 6, 3S), (n, 6) -> (n, 6S + 6): a sample's row in the layout of ``part`` (drone.hip:1179-1194): [s][0..2] =
+    """(n, 6, 3S), (n, 6) -> (n, 6S + 6): a sample's row in the layout of ``part`` (drone_linearize_rows_kernel): [s][0..2] =
     d p_a(S) / d u_{s,a}, [s][3..5] = d v_a(S) / d u_{s,a}, then the six rhs entries"""
     n, S = fdu.shape[0], fdu.shape[2] // 3
     rows = np.empty((n, 6 * S + 6))

@@ -3,6 +3,8 @@ pinned at S = 20, 40 and 90 on 256 CUs on both sides of every edge; the checker 
 oracle and rounded to fp32 as the device stores them, and rejects each way a launch structure can deal a tile, a part
 or a row task to the wrong samples."""
 import ctypes as C
+import itertools
+import os
 
 import numpy as np
 import pytest
@@ -66,9 +68,9 @@ VARIANTS = {"default": {}, "small3": {"RATO_CAR_SMALL_SPLIT": "3"}, "small4": {"
 CASES = [(40, 10000), (40, 24577), (40, 125001), (20, 70001), (90, 12289)]
 
 
-def test_variant_forms():
-    """what the switches of the GPU bit-identity test make of its cases: every form and every tail shape is run"""
-    f = lambda env, S, M: (lambda s: (s["form"], s["workgroups"], s["split"], s["n_whole"]))(cs.car_rows_shape(M, S, env=env))
+def variant_forms(shape):
+    """shape(M, S, env=...) -> a plan: the restatement's, or the library's"""
+    f = lambda env, S, M: (lambda s: (s["form"], s["workgroups"], s["split"], s["n_whole"]))(shape(M, S, env=env))
     for S, M in CASES:
         n = (M + 63) // 64
         assert f(BASE, S, M) == ("static", n, 1, 0)
@@ -84,6 +86,11 @@ def test_variant_forms():
     assert f({}, 90, 12289) == ("static", 193, 1, 0) and f(VARIANTS["small3"], 90, 12289) == ("split", 579, 3, 0)
 
 
+def test_variant_forms():
+    """what the switches of the GPU bit-identity test make of its cases: every form and every tail shape is run"""
+    variant_forms(cs.car_rows_shape)
+
+
 @pytest.mark.parametrize("name", ["base"] + sorted(VARIANTS))
 @pytest.mark.parametrize("S,M", CASES)
 def test_units_cover_every_row_task_once(name, S, M):
@@ -95,6 +102,85 @@ def test_units_cover_every_row_task_once(name, S, M):
         rows[tile, part::rs] += 1
         zw[tile] += (S % rs) == part
     assert (rows == 1).all() and (zw == 1).all()
+
+
+# ---- the library's own plan (rato_car_rows_plan: the function the launcher calls) against the restatement -----------
+@pytest.fixture(scope="module")
+def lib():
+    from riskaversetrajopt_amd import _build, _lib
+    _build.build()
+    return _lib.load()
+
+
+def same_plan(lib, M, S, cus=cs.CUS, env=None, have_queue=True):
+    """the library's plan, having matched the restatement on every field"""
+    got = cs.library_plan(lib, M, S, cus, env, have_queue)
+    want = cs.car_rows_shape(M, S, cus, env, have_queue)
+    assert got == {k: want[k] for k in cs.PLAN_FIELDS}, (M, S, cus, env, have_queue)
+    return got
+
+
+def test_table_against_the_library(lib):
+    """the pinned tables hold for the C++ that launches, not only for the Python copy: every key of TABLE, the pinned
+    variant forms, and every (case, variant) of the bit-identity test field by field (the switches passed explicitly)"""
+    for (S, M), want in TABLE.items():
+        sh = same_plan(lib, M, S)
+        assert (sh["form"], sh["n_tiles"], sh["workgroups"], sh["split"]) == want[:4], (S, M)
+        assert lib.rato_car_stats_in_launch(M, S) == int(want[4]), (S, M)
+    variant_forms(lambda M, S, env: cs.library_plan(lib, M, S, env=env))
+    for (S, M), env in itertools.product(CASES, [BASE] + list(VARIANTS.values())):
+        same_plan(lib, M, S, env=env)
+    # switches == NULL: what this process read from its environment; outside the row kernel's range there is no plan
+    mine = {k: os.environ[k] for k, _ in cs.SWITCHES if k in os.environ}
+    assert cs.library_plan(lib, 125001, 40, env="process") == cs.library_plan(lib, 125001, 40, env=mine)
+    from riskaversetrajopt_amd._lib import RowsPlan
+    for M, S in ((1000, 1), (1000, 102), (0, 40)):
+        assert lib.rato_car_rows_plan(M, S, 256, 1, None, C.byref(RowsPlan())) == -1              # RATO_EINVAL
+
+
+SWEEP_S = (2, 4, 5, 20, 33, 34, 40, 50, 51, 90, 101)
+SWEEP_CUS = (256, 64, 304)
+
+
+@pytest.fixture(scope="module")
+def sweep(lib):
+    """[(M, S, cus, env, have_queue, the library's plan)] on both sides of every edge of the rule: library ==
+    restatement on every field, asserted here; pure calls"""
+    out = []
+    for S, cus, env in itertools.product(SWEEP_S, SWEEP_CUS, [BASE] + list(VARIANTS.values())):
+        sh = cs.car_rows_shape(1, S, cus, env)
+        slots, qslots = sh["slots"], sh["qslots"]
+        ts = {1, 2, cus // 2 - 1, cus // 2, cus // 2 + 1, slots - 1, slots, slots + 1, 1023, 1024, 1025, qslots + 1,
+              2 * slots + 1}
+        for t, have_queue in itertools.product(sorted(t for t in ts if t >= 1), (True, False)):
+            for M in (64 * t - 63, 64 * t):
+                out.append((M, S, cus, env, have_queue, same_plan(lib, M, S, cus, env, have_queue)))
+    return out
+
+
+def test_edge_sweep_library_equals_restatement(sweep):
+    forms = {(p["form"], have_queue) for *_, have_queue, p in sweep}
+    assert forms == {("split", True), ("static", True), ("queue", True), ("split", False), ("static", False)}
+    assert any(p["wants_queue"] and p["form"] == "static" for *_, p in sweep)          # the pool-exhausted fallback
+    assert any(p["form"] == "queue" and p["split"] > 1 and 0 < p["n_whole"] < p["n_tiles"] for *_, p in sweep)
+    assert len(sweep) > 10000
+
+
+def test_edge_sweep_units_cover_every_tile(sweep):
+    """n_units == n_whole + (n_tiles - n_whole) * split with 0 <= n_whole <= n_tiles, in every form"""
+    for *what, p in sweep:
+        assert 0 <= p["n_whole"] <= p["n_tiles"] and 1 <= p["split"] <= max(1, (what[1] + 3) // 4), (what, p)
+        assert p["n_units"] == p["n_whole"] + (p["n_tiles"] - p["n_whole"]) * p["split"] >= p["n_tiles"], (what, p)
+        assert p["workgroups"] == (p["qslots"] if p["form"] == "queue" else p["n_units"]), (what, p)
+
+
+def test_stats_in_launch_is_the_plans_slot_count(lib, sweep):
+    """rato_car_stats_in_launch(M, S) == the tiles fit the slots of the library's plan under default switches and the
+    statistics workgroups fit M (without a device the library assumes 256 CUs)"""
+    for M, S in sorted({(M, S) for M, S, cus, *_ in sweep if cus == 256}):
+        p = cs.library_plan(lib, M, S, 256)
+        want = p["n_tiles"] <= p["slots"] and cs.stats_tail_workgroups(M) > 0
+        assert lib.rato_car_stats_in_launch(M, S) == int(want), (M, S, p)
 
 
 # ---- the checker on synthetic outputs -------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ from the fp64 oracle and rounded to fp32 as the device stores them, and rejects 
 tile, a part or a row task to the wrong samples, naming the sample, tile and lane (or the tile of a ``part`` row)."""
 import ctypes as C
 import itertools
+import os
 
 import numpy as np
 import pytest
@@ -82,11 +83,10 @@ VARIANTS = {"default": {}, "small3": {"RATO_SMALL_SPLIT": "3"}, "small4": {"RATO
 CASES = [(50, 10000), (50, 40001), (50, 100003), (20, 70001), (36, 50001), (90, 20001)]
 
 
-def test_variant_forms():
-    """what the switches of the GPU bit-identity sweep make of its cases: every form, every band of slots, both sides
-    of 1024 tiles, whole tiles / halves / thirds of one tile / quarters of every queued tile at the end of the queue"""
+def variant_forms(shape):
+    """shape(M, S, factored, env=...) -> a plan: the restatement's, or the library's"""
     def f(name, S, M, fact=False):
-        s = ds.drone_rows_shape(M, S, fact, env=BASE if name == "base" else VARIANTS[name])
+        s = shape(M, S, fact, env=BASE if name == "base" else VARIANTS[name])
         return s["form"], s["workgroups"], s["split"], s["n_whole"]
     for S, M in CASES:
         n = (M + 63) // 64
@@ -107,7 +107,13 @@ def test_variant_forms():
     assert f("tail3_one", 50, 100003) == ("queue", 256, 3, 1562) and f("tail3_one", 90, 20001, True) == ("queue", 256, 3, 312)
     # more queue workgroups than tiles: no tail, every tile whole (unclamped, the launcher ran 114 of the 313 tiles)
     assert f("qslots_over", 90, 20001) == ("queue", 512, 2, 313) and f("qslots_over", 50, 40001) == ("queue", 512, 2, 512)
-    assert ds.drone_rows_shape(20001, 90, False, env=VARIANTS["qslots_over"])["n_units"] == 313
+    assert shape(20001, 90, False, env=VARIANTS["qslots_over"])["n_units"] == 313
+
+
+def test_variant_forms():
+    """what the switches of the GPU bit-identity sweep make of its cases: every form, every band of slots, both sides
+    of 1024 tiles, whole tiles / halves / thirds of one tile / quarters of every queued tile at the end of the queue"""
+    variant_forms(ds.drone_rows_shape)
 
 
 @pytest.mark.parametrize("name", ["base"] + sorted(VARIANTS))
@@ -151,6 +157,87 @@ def test_every_switch_setting_covers_every_tile_once():
             assert sh["split"] <= max(1, (S + 3) // 4), what
             seen.add((sh["form"], sh["split"] > 1, sh["n_whole"] == sh["n_tiles"]))
     assert {f for f, _, _ in seen} == {"split", "static", "queue"} and ("queue", True, True) in seen
+
+
+# ---- the library's own plan (rato_drone_rows_plan: the function the launcher calls) against the restatement ---------
+@pytest.fixture(scope="module")
+def lib():
+    from riskaversetrajopt_amd import _build, _lib
+    _build.build()
+    return _lib.load()
+
+
+def same_plan(lib, M, S, factored, cus=ds.CUS, env=None, have_queue=True):
+    """the library's plan, having matched the restatement on every field"""
+    got = ds.library_plan(lib, M, S, factored, cus, env, have_queue)
+    want = ds.drone_rows_shape(M, S, factored, cus, env, have_queue)
+    assert got == {k: want[k] for k in ds.PLAN_FIELDS}, (M, S, factored, cus, env, have_queue)
+    return got
+
+
+def test_table_against_the_library(lib):
+    """the pinned tables hold for the C++ that launches, not only for the Python copy: every key of TABLE, the pinned
+    variant forms, and every (case, variant) of the bit-identity sweep field by field (the switches passed explicitly)"""
+    for (S, M, factored), want in TABLE.items():
+        sh = same_plan(lib, M, S, factored)
+        assert (sh["form"], sh["n_tiles"], sh["workgroups"], sh["split"], sh["n_whole"]) == want, (S, M, factored)
+    variant_forms(lambda M, S, fact, env: ds.library_plan(lib, M, S, fact, env=env))
+    for (S, M), env, factored in itertools.product(CASES, [BASE] + list(VARIANTS.values()), (False, True)):
+        same_plan(lib, M, S, factored, env=env)
+    # switches == NULL: what this process read from its environment; outside the row kernel's range there is no plan
+    mine = {k: os.environ[k] for k, _ in ds.SWITCHES if k in os.environ}
+    assert ds.library_plan(lib, 100003, 50, False, env="process") == ds.library_plan(lib, 100003, 50, False, env=mine)
+    from riskaversetrajopt_amd._lib import RowsPlan
+    for M, S in ((1000, 1), (1000, 127), (0, 50)):
+        assert lib.rato_drone_rows_plan(M, S, 0, 256, 1, None, C.byref(RowsPlan())) == -1       # RATO_EINVAL
+
+
+SWEEP_S = (2, 4, 5, 20, 31, 32, 42, 43, 50, 63, 64, 90, 126)
+SWEEP_CUS = (256, 64, 304)
+
+
+def sweep_tiles(cus, slots, qslots):
+    ts = {1, 2, cus // 2 - 1, cus // 2, cus // 2 + 1, slots - 1, slots, slots + 1, 1023, 1024, 1025, 2 * slots + 1}
+    return sorted(t for t in ts | {q + 1 for q in qslots} if t >= 1)
+
+
+@pytest.fixture(scope="module")
+def sweep(lib):
+    """[(M, S, factored, cus, env, have_queue, the library's plan)] on both sides of every edge of the rule: library ==
+    restatement on every field, asserted here; pure calls"""
+    out = []
+    for S, cus, env in itertools.product(SWEEP_S, SWEEP_CUS, [BASE] + list(VARIANTS.values())):
+        slots = ds.drone_rows_shape(1, S, False, cus, env)["slots"]
+        qslots = {slots, cus} | ({int(env["RATO_ROWS_QSLOTS"])} if "RATO_ROWS_QSLOTS" in env else set())
+        for t, factored, have_queue in itertools.product(sweep_tiles(cus, slots, qslots), (False, True), (True, False)):
+            for M in (64 * t - 63, 64 * t):
+                out.append((M, S, factored, cus, env, have_queue, same_plan(lib, M, S, factored, cus, env, have_queue)))
+    return out
+
+
+def test_edge_sweep_library_equals_restatement(sweep):
+    forms = {(p["form"], have_queue) for *_, have_queue, p in sweep}
+    assert forms == {("split", True), ("static", True), ("queue", True), ("split", False), ("static", False)}
+    assert any(p["wants_queue"] and p["form"] == "static" for *_, p in sweep)          # the pool-exhausted fallback
+    assert len(sweep) > 30000
+
+
+def test_edge_sweep_units_cover_every_tile(sweep):
+    """n_units == n_whole + (n_tiles - n_whole) * split with 0 <= n_whole <= n_tiles: what the unclamped tail broke
+    (S = 90, M = 20,001 with 512 queue workgroups ran 114 of 313 tiles)"""
+    for *what, p in sweep:
+        assert 0 <= p["n_whole"] <= p["n_tiles"] and 1 <= p["split"] <= max(1, (what[1] + 3) // 4), (what, p)
+        assert p["n_units"] == p["n_whole"] + (p["n_tiles"] - p["n_whole"]) * p["split"] >= p["n_tiles"], (what, p)
+        assert p["workgroups"] == (p["qslots"] if p["form"] == "queue" else p["n_units"]), (what, p)
+
+
+def test_stats_in_launch_is_the_plans_slot_count(lib, sweep):
+    """rato_drone_stats_in_launch(M, S) == the tiles fit the slots of the library's plan under default switches and the
+    statistics workgroups fit M (without a device the library assumes 256 CUs)"""
+    for M, S in sorted({(M, S) for M, S, _, cus, *_ in sweep if cus == 256}):
+        p = ds.library_plan(lib, M, S, False, 256)
+        want = p["n_tiles"] <= p["slots"] and ds.stats_tail_workgroups(M, ds.NW * 64) > 0
+        assert lib.rato_drone_stats_in_launch(M, S) == int(want), (M, S, p)
 
 
 # ---- the checker on synthetic outputs -------------------------------------------------------------------------------

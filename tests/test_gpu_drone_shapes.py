@@ -73,6 +73,30 @@ def owned_finite(r, M):
 
 
 # ---- 1. the slot count on the device -----------------------------------------------------------------------------
+def bisect_slots(lib, S):
+    """the largest tile count at which rato_drone_stats_in_launch is still 1 (no launch)"""
+    lo, hi = 1, 8192                                           # in launch at lo tiles, not at hi tiles
+    assert lib.rato_drone_stats_in_launch(64 * lo, S) == 1 and lib.rato_drone_stats_in_launch(64 * hi, S) == 0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if lib.rato_drone_stats_in_launch(64 * mid, S) == 1 else (lo, mid)
+    return lo
+
+
+def test_plan_query_asks_the_device():
+    """rato_drone_rows_plan with cus <= 0 takes the device's CU count: at the shapes this file runs it is the
+    restatement at that count, field by field, and its slots are the ones the bisection finds (no launch)"""
+    from riskaversetrajopt_amd import _lib
+    lib = _lib.load()
+    n = cus()
+    shapes = sorted(TABLE) + [(S, M, f) for S, M in CASES for f in (False, True)]
+    for S, M, factored in shapes:
+        want = ds.drone_rows_shape(M, S, factored, n)
+        assert ds.library_plan(lib, M, S, factored, cus=0) == {k: want[k] for k in ds.PLAN_FIELDS}, (S, M, factored, n)
+    for S in sorted({S for S, _, _ in shapes}):
+        assert ds.library_plan(lib, 1, S, False, cus=-1)["slots"] == bisect_slots(lib, S), S
+
+
 @pytest.mark.parametrize("S", [20, 36, 50, 90])
 def test_stats_in_launch_flips_at_the_slot_count(S):
     """rato_drone_stats_in_launch(M, S) is 1 while the tiles fit the resident slots (the statistics workgroups fit up
@@ -81,11 +105,7 @@ def test_stats_in_launch_flips_at_the_slot_count(S):
     lib = _lib.load()
     n = cus()
     sh = ds.drone_rows_shape(1, S, False, n)
-    lo, hi = 1, 8192                                           # in launch at lo tiles, not at hi tiles
-    assert lib.rato_drone_stats_in_launch(64 * lo, S) == 1 and lib.rato_drone_stats_in_launch(64 * hi, S) == 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if lib.rato_drone_stats_in_launch(64 * mid, S) == 1 else (lo, mid)
+    lo = bisect_slots(lib, S)
     assert lo == sh["slots"], (f"S = {S}: the device has {lo} row-kernel slots, tests/_drone_shapes.py says "
                                f"{sh['slots']} ({n} CUs x {sh['per_cu']}): the shape table moved, the edge tests below "
                                f"no longer run the shapes they name")
