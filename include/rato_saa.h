@@ -1076,6 +1076,67 @@ int rato_car_gaussian_linearize(const rato_car_gauss_params* p, int32_t K,
                                 double* g_obs_du /* [K][S][2S] */, double* g_obs_dalpha /* [K][S] */,
                                 double* v_final /* [K][4] */, double* v_final_du /* [K][4][2S] */, void* stream);
 
+/*
+ * Drone Gaussian baseline (drone/drone_gaussian.py) -- an addition within version 12.
+ *
+ * The script hands IPOPT three callbacks in z = (u (3S), state allocations (S n_obs), obstacle allocations (n_obs)), n_obs = 3:
+ * g, jacfwd(g) and jacfwd(jacfwd(lam . g)) (:414-486), all through the S-step recursion of the mean (Euler at the nominal
+ * mass, :161-174) and of the 6x6 covariance (Sigma+ = A Sigma A^T + dt sigma sigma^T + var_m (b_dm @ b_dm.T), :176-227).  The
+ * two calls below evaluate them for K problems, fp64 throughout (csrc/drone_gaussian.hip).
+ *
+ * Layout of z, the reference's (:86-102, :356-366): us_mat[t][i] = z[3t + i]; the state allocation of obstacle i at step t
+ * (state t+1) is z[3S + t n_obs + i]; the obstacle allocation of obstacle i is z[3S + S n_obs + i].  nvar = 3S + S n_obs + n_obs.
+ *
+ * The n_nl = 6 + n_obs S + 4 (S+1) non-linear rows, in the reference's order (:351-382):
+ *   final  [6]           x_S - x_final
+ *   obs    [6 + i S + t] -( |d| - ppf(1 - a_{t,i}) sqrt(n^T Sigma_{t+1}[:2,:2] n) - r_i ),  d = p_{t+1}[:2] - obs_positions[i],
+ *                        n = d/|d|,  r_i = (obs_radii[i] + delta) - (a_obs,i / 3) 2 delta;  ppf is Wichura's AS 241 (PPND16)
+ *   high   [.. + t 2 + j]  xs[t][j] - bound_high[j],  t = 0..S, j = 0, 1
+ *   low    [.. + t 2 + j]  -xs[t][j] + bound_low[j]
+ * The script's remaining nvar + 1 rows (z itself and the sum of the allocations, :323-349) are linear with constant
+ * coefficients and no second derivative: they stay with the caller, and lam holds n_nl multipliers.
+ *
+ * Reference quirk, reproduced (there is no other mode): b_dm (:208) is 1-D, so `b_dm @ b_dm.T` is an inner product and the
+ * mass term is ONE scalar added to all 36 entries of the covariance.  |v| in the drag differentiates as sign(v) with
+ * sign(0) = 0, the convention of the reference's AD.
+ *
+ * Every constant comes from the caller (the facade fills it from drone_params): nothing is baked into the kernels. */
+typedef struct rato_drone_gauss_params {
+  int32_t S;                      /* 1..64 (one lane per control direction: 3S <= 192 lanes of one workgroup) */
+  int32_t reserved;
+  double dt;
+  double mass_nom, mass_var;      /* mass_var = (2 mass_delta)^2 / 12 */
+  double beta, drag;
+  double feedback_kp, feedback_kd; /* feedback_gain = (kp I, kd I): control_applied = u + kp p + kd v */
+  double x_init[6], x_final[6];
+  double obs_positions[3][2];
+  double obs_radii[3];
+  double obs_radii_delta;
+  double bound_high[2], bound_low[2]; /* (0.5, 0.5) and (-2, -0.5) in the script */
+} rato_drone_gauss_params;
+size_t rato_drone_gauss_params_bytes(void); /* sizeof the struct as this library was built: a binding checks its layout */
+
+/* g and its Jacobian.  Device pointers (fp64), stream ordered, no allocation.  mus / Sigmas may be NULL (not written, and
+ * the other outputs are bitwise the same either way); every other pointer is required.  jac_nl is dense row-major; its
+ * structural zeros are written as exactly 0.0: control columns of step t' > t on obstacle row t, control columns of step
+ * t' >= t and of another axis on a mean row of state t, and every allocation column but the row's own a_{t,i}
+ * (-sqrt(w) / pdf(q)) and a_obs,i (-2 delta / 3).
+ * RATO_EINVAL without a launch unless 1 <= S <= 64, K >= 1 and the required pointers are non-NULL. */
+int rato_drone_gaussian_linearize(const rato_drone_gauss_params* p, int32_t K, const double* Z /* [K][nvar] */,
+                                  double* mus /* [K][S+1][6] or NULL */, double* Sigmas /* [K][S+1][6][6] or NULL */,
+                                  double* g_nl /* [K][n_nl] */, double* jac_nl /* [K][n_nl][nvar] */, void* stream);
+
+/* The Hessian of lam . g in np.tril_indices(nvar) order, what eval_h hands to IPOPT (:480-486): the dense (u,u) block (one
+ * lane per pair of control directions), (u, a_{t,i}) = -lam_{(i,t)} (d sqrt(w) / du) / pdf(q), the diagonal of (a,a) =
+ * lam q sqrt(w) / pdf(q)^2, and exactly 0.0 everywhere else (everything involving a_obs included).
+ * The kernels keep their state in registers, so rato_drone_gaussian_hessian_workspace_bytes is 0 at every (S, K) today and
+ * workspace may then be NULL; a caller still passes what the query returns.  RATO_EINVAL without a launch unless
+ * 1 <= S <= 64, K >= 1, Z, lam and hess_tril are non-NULL and workspace_bytes covers the query. */
+size_t rato_drone_gaussian_hessian_workspace_bytes(int32_t S, int32_t K);
+int rato_drone_gaussian_hessian(const rato_drone_gauss_params* p, int32_t K, const double* Z /* [K][nvar] */,
+                                const double* lam /* [K][n_nl] */, double* hess_tril /* [K][nvar (nvar+1) / 2] */,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,15 @@ class CarGaussParams(C.Structure):
                [("mean_init", C.c_double * 8), ("ped_var_init", C.c_double * 4), ("ego_goal", C.c_double * 4)]
 
 
+class DroneGaussParams(C.Structure):
+    """rato_drone_gauss_params (include/rato_saa.h)"""
+    _fields_ = [("S", C.c_int32), ("reserved", C.c_int32)] + \
+               [(k, C.c_double) for k in ("dt", "mass_nom", "mass_var", "beta", "drag", "feedback_kp", "feedback_kd")] + \
+               [("x_init", C.c_double * 6), ("x_final", C.c_double * 6), ("obs_positions", (C.c_double * 2) * 3),
+                ("obs_radii", C.c_double * 3), ("obs_radii_delta", C.c_double), ("bound_high", C.c_double * 2),
+                ("bound_low", C.c_double * 2)]
+
+
 class RowsPlan(C.Structure):
     """rato_rows_plan (include/rato_saa.h): form 0 split, 1 static, 2 queue"""
     _fields_ = [(k, C.c_int32) for k in ("n_tiles", "per_cu", "slots", "qslots", "wants_queue", "form", "split", "n_whole",
@@ -232,6 +241,11 @@ SIGNATURES = {
     "rato_histogram": (C.c_int, [c_float_p, C.c_int64, C.c_float, C.c_float, C.c_int32, c_float_p, c_stream]),
     "rato_car_gauss_params_bytes": (C.c_size_t, []),
     "rato_car_gaussian_linearize": (C.c_int, [C.POINTER(CarGaussParams), C.c_int32] + [c_float_p] * 9 + [c_stream]),
+    "rato_drone_gauss_params_bytes": (C.c_size_t, []),
+    "rato_drone_gaussian_linearize": (C.c_int, [C.POINTER(DroneGaussParams), C.c_int32] + [c_float_p] * 5 + [c_stream]),
+    "rato_drone_gaussian_hessian_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rato_drone_gaussian_hessian": (C.c_int, [C.POINTER(DroneGaussParams), C.c_int32] + [c_float_p] * 3 +
+                                    [C.c_void_p, C.c_size_t, c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h
@@ -280,6 +294,9 @@ def load():
     if lib.rato_car_gauss_params_bytes() != C.sizeof(CarGaussParams):
         raise RatoError(f"rato_car_gauss_params is {lib.rato_car_gauss_params_bytes()} bytes in {path}, "
                         f"{C.sizeof(CarGaussParams)} in this binding")
+    if lib.rato_drone_gauss_params_bytes() != C.sizeof(DroneGaussParams):
+        raise RatoError(f"rato_drone_gauss_params is {lib.rato_drone_gauss_params_bytes()} bytes in {path}, "
+                        f"{C.sizeof(DroneGaussParams)} in this binding")
     _LIB = lib
     return lib
 

@@ -570,3 +570,101 @@ def driving_gaussian_experiment(alphas=(0.01, 0.02, 0.05, 0.1), S=None, iters=60
         for a, r in zip(alphas, results):
             save_results(os.path.join(results_dir, f"driving_gaussian_alpha={a}.npy"), r["us"], r["xs"])
     return out
+
+
+def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir='results'):
+    """The NLP of drone_gaussian.py:400-534 solved with ``scipy.optimize.minimize(method='trust-constr')`` -- the installed
+    solver that takes the Hessian of lam . g, which is the script's ``hess_lagrange_dot_g``: the non-linear rows as a
+    ``NonlinearConstraint(g, gL, gU, jac, hess)`` (6 equalities, the rest one-sided), the box on u and on the allocations as
+    ``Bounds`` (the allocations with ``keep_feasible=True``: ppf(1 - a) does not exist for a <= 0), the allocation sum as a
+    ``LinearConstraint``, gtol = 1e-8, xtol = 1e-10.  ``callbacks``: dict(linearize(Z) -> (g_nl, jac_nl), hessian(Z, lam) ->
+    tril, trajectory(Z) -> (xs, Sigmas)), by default the model's device callbacks (one launch each); g and its Jacobian at
+    the same point share one launch.  ``Z0``: the start, by default the script's (the SAA repeat-0 controls of
+    ``results_dir`` and the uniform allocation).
+    -> dict(Z, us (S, 3), alphas_risk, xs (S+1, 6), Sigmas (S+1, 6, 6), status, message, nit, nfev, constr_violation,
+    optimality, fun, callback_s, total_s)"""
+    from scipy.optimize import Bounds, LinearConstraint, NonlinearConstraint, minimize
+    from . import drone_params as P
+    cb = model.device_callbacks() if callbacks is None else callbacks
+    S, nvar, n_nl = model.S, model.nvar, model.n_nl
+    D = 3 * S
+    Z0 = model.initial_guess(results_dir) if Z0 is None else np.asarray(Z0, dtype=np.float64)
+    clock, cache = [0.0], {}
+    rows, cols = np.tril_indices(nvar)
+    curv = np.zeros(nvar)
+    curv[:D] = np.tile(4 * model.dt * np.diag(P.R), S)
+
+    def lin(x):
+        key = x.tobytes()
+        if cache.get("key") != key:
+            t0 = time.perf_counter()
+            cache["key"], cache["val"] = key, cb["linearize"](np.array(x, dtype=np.float64))
+            clock[0] += time.perf_counter() - t0
+        return cache["val"]
+
+    def hess(x, v):
+        t0 = time.perf_counter()
+        tril = cb["hessian"](np.array(x, dtype=np.float64), np.asarray(v, dtype=np.float64))
+        clock[0] += time.perf_counter() - t0
+        H = np.zeros((nvar, nvar))
+        H[rows, cols] = tril
+        H[cols, rows] = tril
+        return H
+
+    g_L = np.concatenate([np.zeros(6), np.full(n_nl - 6, -np.inf)])
+    nonlinear = NonlinearConstraint(lambda x: lin(x)[0], g_L, np.zeros(n_nl), jac=lambda x: lin(x)[1], hess=hess)
+    lo = np.concatenate([np.full(D, float(model.u_min)), np.full(nvar - D, 1e-6)])
+    hi = np.concatenate([np.full(D, float(model.u_max)), np.full(nvar - D, float(model.alpha))])
+    bounds = Bounds(lo, hi, keep_feasible=np.arange(nvar) >= D)
+    sum_row = np.concatenate([np.zeros(D), np.ones(nvar - D)])[None, :]
+    t0 = time.perf_counter()
+    res = minimize(lambda x: 0.5 * float(np.sum(curv * x * x)), Z0, method='trust-constr', jac=lambda x: curv * x,
+                   hess=lambda x: np.diag(curv), bounds=bounds,
+                   constraints=[nonlinear, LinearConstraint(sum_row, 0.0, float(model.alpha))],
+                   options=dict(gtol=1e-8, xtol=1e-10, maxiter=int(maxiter)))
+    total = time.perf_counter() - t0
+    Z = np.asarray(res.x, dtype=np.float64)
+    us = model.convert_us_vec_to_us_mat(Z[:D])
+    xs, Sigmas = cb["trajectory"](Z)
+    return {"Z": Z, "us": us, "alphas_risk": Z[D:].copy(), "xs": xs, "Sigmas": Sigmas, "status": int(res.status),
+            "message": str(res.message), "nit": int(res.nit), "nfev": int(res.nfev),
+            "constr_violation": float(res.constr_violation), "optimality": float(res.optimality), "fun": float(res.fun),
+            "callback_s": clock[0], "total_s": total}
+
+
+def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='results', M_mc=10000, seed=0, maxiter=3000,
+                              saa_iters=60, saa_M=50, device='cuda:0'):
+    """The reference's drone Gaussian baseline (drone_gaussian.py:400-534) and the third block of the drone Monte-Carlo report
+    (drone_risk.py:742-761) as one call.  The start of every alpha is the SAA repeat-0 solution
+    ``results_dir``/drone_alpha=<alpha>_repeat=0.npy, read where it exists and made by ``drone_saa_experiment`` (one repeat)
+    where it does not; each alpha is solved by ``run_drone_gaussian`` and written to drone_gaussian_alpha=<alpha>.npy as
+    (us, xs); then ONE ``eval_batch_device`` call of a fresh ``drone_risk.Model`` of M_mc samples (drawn under
+    ``np.random.seed(seed)``) over the solutions.  Per alpha percentage_safe = mean(max constraint <= 1e-6), as the block
+    computes it, and monte_carlo_cost.
+    -> dict(alphas, results [alpha] (the run_drone_gaussian dicts), status (A,), us (A, S, 3), Z (A, M_mc) [the per-sample
+    maxima], percentage_safe (A,), cost (A,), wall_s)"""
+    from . import drone_gaussian, drone_risk
+    from . import drone_params as P
+    from .drone_utils import sample_uncertain_parameters
+    alphas = [float(a) for a in alphas]
+    os.makedirs(results_dir, exist_ok=True)
+    missing = [a for a in alphas if not os.path.isfile(os.path.join(results_dir, f"drone_alpha={a}_repeat=0.npy"))]
+    if missing:
+        drone_saa_experiment(alphas=missing, num_repeats=1, M=saa_M, S=S, iters=saa_iters, seed=seed, results_dir=results_dir,
+                             device=device)
+    t0 = time.perf_counter()
+    results = []
+    for a in alphas:
+        model = drone_gaussian.Model(S, alpha=a, device=device)
+        results.append(run_drone_gaussian(model, maxiter=maxiter, results_dir=results_dir))
+        save_results(os.path.join(results_dir, f"drone_gaussian_alpha={a}.npy"), results[-1]["us"], results[-1]["xs"])
+    wall = time.perf_counter() - t0
+    us = np.stack([r["us"] for r in results])
+    np.random.seed(seed)
+    mc_model = drone_risk.Model(S, *sample_uncertain_parameters('saa', M=int(M_mc), S=S, dt=P.T / S), 'saa', alphas[0],
+                                device=device)
+    Z, _ = mc_model.eval_batch_device(us, want_stats=False)
+    Z = Z.double().cpu().numpy()[:, :int(M_mc)]
+    return {"alphas": alphas, "results": results, "status": np.array([r["status"] for r in results]), "us": us, "Z": Z,
+            "percentage_safe": np.mean(Z <= 1e-6, axis=1), "cost": np.array([mc_model.monte_carlo_cost(u) for u in us]),
+            "wall_s": wall}

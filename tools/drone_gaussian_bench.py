@@ -1,0 +1,123 @@
+"""Measures the drone Gaussian baseline on the GPU (nothing gates on it; bench.py is the flagship benchmark):
+
+  * the linearize call (rato_drone_gaussian_linearize) and the Hessian call (rato_drone_gaussian_hessian) at S = 20 and
+    S = 64 (the largest), K = 1 and K = 4: device events around `reps` back-to-back calls after a warm-up, repeated `rounds`
+    times -> median and spread per call;
+  * the same callbacks on the host by the fp64 NumPy restatement (tests/_drone_gaussian.py), and ONE torch
+    jacfwd o jacfwd Hessian of an independent torch forward (tests/test_drone_gaussian_pin.py) at S = 5 and S = 20, for scale;
+  * one full `scp.run_drone_gaussian` at S = 5 from the prototype's start point with its callback / total split, its
+    status, iterations, violation and optimality;
+  * the largest max-abs-scaled difference between the kernels and the restatement over the shapes of the GPU test
+    (tests/test_gpu_drone_gaussian.py), the Hessian per block, which sets that test's tolerance.
+
+    python tools/drone_gaussian_bench.py [--maxiter 3000] [--out profiles/drone_gaussian_bench.json]
+
+Prints one JSON line.  There is no CPU fallback: without a GPU the kernel timings fail.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def time_call(fn, reps, rounds):
+    import torch
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    per = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        per.append(e0.elapsed_time(e1) * 1e3 / reps)
+    per = np.array(per)
+    return {"median_us": float(np.median(per)), "min_us": float(per.min()), "max_us": float(per.max())}
+
+
+def scaled(a, b):
+    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), np.finfo(float).tiny))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--maxiter", type=int, default=3000)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("drone_gaussian_bench needs a GPU: nothing here is measured on the host in its place")
+    import _drone_gaussian as R
+    from riskaversetrajopt_amd import drone_gaussian as DG
+    from riskaversetrajopt_amd import scp
+
+    out = {"device": torch.cuda.get_device_name(0), "linearize": {}, "hessian": {}, "host_restatement_s": {},
+           "torch_hessian_s": {}}
+    for S in (20, DG.MAX_S):
+        m = DG.Model(S, alpha=0.1)
+        pr = R.problems(S, 4)
+        Z = torch.as_tensor(np.stack([p[0] for p in pr]), device="cuda")
+        lam = torch.as_tensor(np.stack([p[1] for p in pr]), device="cuda")
+        for K in (1, 4):
+            out["linearize"][f"S{S}_K{K}"] = time_call(lambda: m.linearize_device(Z[:K]), args.reps, args.rounds)
+            out["hessian"][f"S{S}_K{K}"] = time_call(lambda: m.hessian_device(Z[:K], lam[:K]), args.reps, args.rounds)
+        t0 = time.perf_counter()
+        R.evaluate(pr[0][0], S, [pr[0][1]])
+        out["host_restatement_s"][f"S{S}_K1"] = time.perf_counter() - t0
+
+    import test_drone_gaussian_pin as T
+    for S in (5, 20):
+        Z, lam = R.problems(S, 1)[0]
+        Zt, lt, c = torch.as_tensor(Z), torch.as_tensor(lam), R.constants(S)
+        t0 = time.perf_counter()
+        torch.func.jacfwd(torch.func.jacfwd(lambda z: torch.dot(lt, T._torch_g(z, S, c))))(Zt)
+        out["torch_hessian_s"][f"S{S}"] = time.perf_counter() - t0
+
+    worst = {"linearize": 0.0, "hess_uu": 0.0, "hess_ua": 0.0, "hess_aa": 0.0}
+    for S in (1, 2, 3, 5, 20, 22, DG.MAX_S):
+        m = DG.Model(S, alpha=0.1)
+        pr = R.problems(S, 4)
+        Z, lam = np.stack([p[0] for p in pr]), np.stack([p[1] for p in pr])
+        got = {k: v.cpu().numpy() for k, v in m.linearize_device(Z, want_trajectory=True).items()}
+        hess = m.hessian_device(Z, lam).cpu().numpy()
+        nvar = R.sizes(S)[0]
+        for k in range(4):
+            ref = R.evaluate(Z[k], S, [lam[k]])
+            for key, g in got.items():
+                worst["linearize"] = max(worst["linearize"], scaled(g[k], ref[key]))
+            H = np.zeros((nvar, nvar))
+            H[np.tril_indices(nvar)] = hess[k]
+            H = H + np.tril(H, -1).T
+            for name, a, b in zip(("hess_uu", "hess_ua", "hess_aa"), R.hess_blocks(H, S), R.hess_blocks(ref["hess"][0], S)):
+                worst[name] = max(worst[name], scaled(a, b))
+    out["kernel_vs_restatement_max_scaled_difference"] = worst
+
+    S = 5
+    m = DG.Model(S, alpha=0.1)
+    scp.run_drone_gaussian(m, Z0=R.start_point(S, 0.1), maxiter=3)       # warm-up: code objects, allocator
+    res = scp.run_drone_gaussian(m, Z0=R.start_point(S, 0.1), maxiter=args.maxiter)
+    out["solve_S5"] = {k: res[k] for k in ("status", "message", "nit", "nfev", "constr_violation", "optimality", "fun",
+                                           "callback_s", "total_s")}
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
