@@ -1137,6 +1137,68 @@ int rato_drone_gaussian_hessian(const rato_drone_gauss_params* p, int32_t K, con
                                 const double* lam /* [K][n_nl] */, double* hess_tril /* [K][nvar (nvar+1) / 2] */,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Hopper NLP (hopper/hopper.py:491-514, :569-580) -- an addition within version 12.
+ *
+ * The script hands IPOPT g, jacrev(g) and hessian(lam . g) in z = (x_0 .. x_S (8 each), u_0 .. u_{S-1} (4 each), ys (M), slack,
+ * t_risk): x_t = z[8t .. 8t+8), u_t = z[8(S+1) + 4t ..) (:105-132); nvar = 8(S+1) + 4S + M + 2.  The rows that carry the
+ * sample axis are rato_hopper_slip* above.  The calls below evaluate every other non-linear row for K problems, fp64
+ * throughout (csrc/hopper_nlp.hip), as per-step LOCAL quantities: they are phase-agnostic, and the caller owns the contact /
+ * flight masks (time_jump, time_land), the constant unit coefficients and the placement in the script's row order.
+ *
+ * Every constant comes from the caller (the facade fills it from the script's values): nothing is baked into the kernels.
+ * state_initial / state_final and the phase times travel with the struct for the caller's rows (x_0 - state_initial,
+ * x_S[4:6] - state_final[4:6], the masks); the kernels validate the phase times and read neither state. */
+typedef struct rato_hopper_nlp_params {
+  int32_t S;                      /* >= 1 */
+  int32_t time_jump, time_land;   /* 0 <= time_jump <= time_land <= S */
+  int32_t reserved;
+  double dt;
+  double mass_body, mass_leg;
+  double inertia_body, inertia_leg;
+  double gravity;
+  double state_initial[8], state_final[8];
+} rato_hopper_nlp_params;
+size_t rato_hopper_nlp_params_bytes(void); /* sizeof the struct as this library was built: a binding checks its layout */
+
+/* The RK4 defect (:240-248) of every step and the two state rows of every state, with their first derivatives.  Device pointers
+ * (fp64), stream ordered, no allocation.  Z is [K][ldz] with ldz >= 8(S+1) + 4S (the tail of a problem's z is not read).
+ *   defect   [K][S][8]       x_{t+1} - (x_t + dt/6 (k1 + 2 k2 + 2 k3 + k4))
+ *   d_defect [K][S][8][12]   its derivative with respect to (x_t, u_t); the x_{t+1} coefficient is the identity and stays
+ *                            with the caller
+ *   rows     [K][S+1][2]     [0] the no-slip value J_T q_dot = x4 + x3 cos(x2) x6 + sin(x2) x7 (:288-293),
+ *                            [1] the end-effector height x1 - x3 cos(x2) (:166-171), at every state
+ *   d_rows   [K][S+1][2][4]  their derivatives with respect to (x2, x3, x6, x7); the unit coefficients on x4 and x1 stay with
+ *                            the caller
+ * Any output may be NULL (not written; the others are bitwise the same either way).  One lane per (problem, state, direction);
+ * nothing depends on S fitting a workgroup.  RATO_EINVAL without a launch unless S >= 1, K >= 1, ldz >= 8(S+1) + 4S,
+ * 0 <= time_jump <= time_land <= S, Z is non-NULL and K (S+1) 12 lanes fit the grid's index range. */
+int rato_hopper_nlp_linearize(const rato_hopper_nlp_params* p, int32_t K, const double* Z /* [K][ldz] */, int64_t ldz,
+                              double* defect, double* d_defect, double* rows, double* d_rows, void* stream);
+
+/* The Hessian of lam . g over the rows above, which is block diagonal over the steps: block t on (x_t (8), u_t (4)), t = 0..S,
+ * as the lower triangle in np.tril_indices(12) order (78 entries); the u part of block S is exactly 0.0.
+ *   lam_dyn     [K][S][8]     multipliers of the defect rows
+ *   lam_rows    [K][S+1][2]   per-state weights of the two state rows (the caller folds the no-slip, contact and leg-over-ground
+ *                             (sign -1) multipliers into them by phase)
+ *   add         [K][S+1][78]  or NULL: blocks added to the output (the slip part and obj_factor hess_f)
+ *   hess_blocks [K][S+1][78]
+ * Second-order tangents are carried through the four RK4 stages, one lane per (problem, block, pair of directions); pairs that
+ * hold x0, x1, x4 or x5 carry no second derivative and only forward `add`.  RATO_EINVAL without a launch as above, and when
+ * lam_dyn, lam_rows or hess_blocks is NULL. */
+int rato_hopper_nlp_hessian(const rato_hopper_nlp_params* p, int32_t K, const double* Z /* [K][ldz] */, int64_t ldz,
+                            const double* lam_dyn, const double* lam_rows, const double* add, double* hess_blocks,
+                            void* stream);
+
+/* Emission: dst[k][map[i]] = scale[i] src[k][i] for i < n, k < K (scale NULL: 1).  map is a device array of int64; an entry
+ * outside [0, n_dst) is not emitted.  The caller zeroes (or pre-fills) dst once: what the map does not point at is left alone.
+ * Places the local blocks into the CSC value array of the Jacobian and into the tril-packed dense Hessian.
+ * RATO_EINVAL without a launch unless 1 <= K <= 65535, n >= 1, ld_src >= n, n_dst >= 1, ld_dst >= n_dst and src, map, dst are
+ * non-NULL. */
+int rato_scatter_f64(int32_t K, int64_t n, const double* src /* [K][ld_src] */, int64_t ld_src, const int64_t* map /* [n] */,
+                     const double* scale /* [n] or NULL */, double* dst /* [K][ld_dst] */, int64_t ld_dst, int64_t n_dst,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

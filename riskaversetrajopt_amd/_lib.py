@@ -52,6 +52,13 @@ class DroneGaussParams(C.Structure):
                 ("bound_low", C.c_double * 2)]
 
 
+class HopperNlpParams(C.Structure):
+    """rato_hopper_nlp_params (include/rato_saa.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("S", "time_jump", "time_land", "reserved")] + \
+               [(k, C.c_double) for k in ("dt", "mass_body", "mass_leg", "inertia_body", "inertia_leg", "gravity")] + \
+               [("state_initial", C.c_double * 8), ("state_final", C.c_double * 8)]
+
+
 class RowsPlan(C.Structure):
     """rato_rows_plan (include/rato_saa.h): form 0 split, 1 static, 2 queue"""
     _fields_ = [(k, C.c_int32) for k in ("n_tiles", "per_cu", "slots", "qslots", "wants_queue", "form", "split", "n_whole",
@@ -246,6 +253,13 @@ SIGNATURES = {
     "rato_drone_gaussian_hessian_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rato_drone_gaussian_hessian": (C.c_int, [C.POINTER(DroneGaussParams), C.c_int32] + [c_float_p] * 3 +
                                     [C.c_void_p, C.c_size_t, c_stream]),
+    "rato_hopper_nlp_params_bytes": (C.c_size_t, []),
+    "rato_hopper_nlp_linearize": (C.c_int, [C.POINTER(HopperNlpParams), C.c_int32, c_float_p, C.c_int64] + [c_float_p] * 4 +
+                                  [c_stream]),
+    "rato_hopper_nlp_hessian": (C.c_int, [C.POINTER(HopperNlpParams), C.c_int32, c_float_p, C.c_int64] + [c_float_p] * 4 +
+                                [c_stream]),
+    "rato_scatter_f64": (C.c_int, [C.c_int32, C.c_int64, c_float_p, C.c_int64, c_float_p, c_float_p, c_float_p, C.c_int64,
+                                   C.c_int64, c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h
@@ -297,6 +311,9 @@ def load():
     if lib.rato_drone_gauss_params_bytes() != C.sizeof(DroneGaussParams):
         raise RatoError(f"rato_drone_gauss_params is {lib.rato_drone_gauss_params_bytes()} bytes in {path}, "
                         f"{C.sizeof(DroneGaussParams)} in this binding")
+    if lib.rato_hopper_nlp_params_bytes() != C.sizeof(HopperNlpParams):
+        raise RatoError(f"rato_hopper_nlp_params is {lib.rato_hopper_nlp_params_bytes()} bytes in {path}, "
+                        f"{C.sizeof(HopperNlpParams)} in this binding")
     _LIB = lib
     return lib
 

@@ -1,7 +1,15 @@
-"""Hopper uncertain-friction SAA constraint — the sample-dependent part of the
-reference's ``class Model`` (hopper/hopper.py:68-81,90-171,300-367,901-958) on
-the MI355X.  The sample-independent NLP rows and the IPOPT glue stay on the
-host and are out of scope."""
+"""Hopper uncertain-friction NLP -- the reference's ``class Model`` (hopper/hopper.py:90-453) and the callbacks its solve block
+hands to IPOPT (:486-640) on the MI355X.
+
+  * The sample-dependent part (:68-81, :300-367, :901-958): the slip rows, their Jacobian and Hessian slices and the Monte-Carlo
+    check, fp32 over the sample axis (csrc/hopper.hip).
+  * The rest of the NLP (:239-298, :369-453): the RK4 defect of the 8-state leg, the no-slip and end-effector rows, their
+    derivatives and the Hessian of lam . g as one 12 x 12 block per step, fp64, for K problems per call
+    (rato_hopper_nlp_linearize / rato_hopper_nlp_hessian, csrc/hopper_nlp.hip); rato_scatter_f64 places the local blocks
+    into the CSC values of the Jacobian and into the tril-packed Hessian.  The kernels are phase-agnostic: the contact /
+    flight masks, the constant unit coefficients and the script's row order live here.
+  * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
+There is no solver driver: IPOPT is the caller's."""
 import ctypes as C
 
 import numpy as np
@@ -18,6 +26,16 @@ n_x = 8
 n_u = 4
 mu_nom = 0.10
 num_mu_features = 30
+# hopper.py:60-66, :83-89
+u_max = 1000.0
+mass_body, mass_leg = 3.0, 0.3
+inertia_body, inertia_leg = 0.75, 0.075
+gravity = 9.81
+max_contact_force = 1000.0
+state_initial = np.array([1e-6, 1.0, -1e-6, 1.0, 0., 0., 0., 0.]) + 2e-7
+state_final = np.array([0.15, 1., -1e-6, 1., 0., 0., 0., 0.]) + 2e-7
+n_l = n_x + n_u                      # local variables (x_t, u_t) of a step block
+n_pairs = n_l * (n_l + 1) // 2       # 78: the lower triangle of a block in np.tril_indices(12) order
 
 
 def phase_times(S):
@@ -48,16 +66,90 @@ def sample_friction_fields_device(M, seed=1, device='cuda:0'):
     return a, th, tau
 
 
+# ---- the deterministic NLP rows: device-level calls (include/rato_saa.h, csrc/hopper_nlp.hip) ---------------------------------
+def nlp_params(S, time_jump=None, time_land=None, dt=None):
+    """rato_hopper_nlp_params from the script's constants (:44-89)"""
+    tj, tl = phase_times(S)
+    p = _lib.HopperNlpParams()
+    p.S, p.reserved = int(S), 0
+    p.time_jump, p.time_land = int(tj if time_jump is None else time_jump), int(tl if time_land is None else time_land)
+    p.dt = float(T / S if dt is None else dt)
+    p.mass_body, p.mass_leg, p.inertia_body, p.inertia_leg = mass_body, mass_leg, inertia_body, inertia_leg
+    p.gravity = gravity
+    for i in range(n_x):
+        p.state_initial[i], p.state_final[i] = float(state_initial[i]), float(state_final[i])
+    return p
+
+
+def _rows_of(Z, nmin):
+    """(K, ldz) of a device fp64 tensor [K][ldz] whose rows are contiguous"""
+    if Z.dim() != 2 or Z.dtype != torch.float64 or not Z.is_cuda or Z.stride(1) != 1 or Z.shape[1] < nmin or Z.shape[0] < 1:
+        raise ValueError(f"Z must be a device float64 tensor (K >= 1, >= {nmin}) with contiguous rows, got {tuple(Z.shape)}")
+    return Z.shape[0], (Z.stride(0) if Z.shape[0] > 1 else max(Z.stride(0), Z.shape[1]))
+
+
+def nlp_linearize_device(params, Z, want=("defect", "d_defect", "rows", "d_rows")):
+    """rato_hopper_nlp_linearize on a device tensor Z [K][ldz] (a row-strided view is fine) -> dict of the fp64 device tensors
+    named in ``want``: defect (K, S, 8), d_defect (K, S, 8, 12), rows (K, S+1, 2), d_rows (K, S+1, 2, 4)"""
+    S = params.S
+    K, ldz = _rows_of(Z, n_x * (S + 1) + n_u * S)
+    shapes = {"defect": (K, S, n_x), "d_defect": (K, S, n_x, n_l), "rows": (K, S + 1, 2), "d_rows": (K, S + 1, 2, 4)}
+    out = {k: torch.empty(shapes[k], dtype=torch.float64, device=Z.device) for k in want}
+    with torch.cuda.device(Z.device):
+        _lib.check(_lib.load().rato_hopper_nlp_linearize(
+            C.byref(params), K, _lib.ptr(Z), ldz, *(_lib.ptr(out.get(k)) for k in ("defect", "d_defect", "rows", "d_rows")),
+            _lib.current_stream()), "rato_hopper_nlp_linearize")
+    return out
+
+
+def nlp_hessian_device(params, Z, lam_dyn, lam_rows, add=None):
+    """rato_hopper_nlp_hessian: Z [K][ldz], lam_dyn (K, S, 8), lam_rows (K, S+1, 2), add (K, S+1, 78) or None, all device fp64
+    -> hess_blocks (K, S+1, 78)"""
+    S = params.S
+    K, ldz = _rows_of(Z, n_x * (S + 1) + n_u * S)
+    for t, shape, name in ((lam_dyn, (K, S, n_x), "lam_dyn"), (lam_rows, (K, S + 1, 2), "lam_rows"), (add, (K, S + 1, n_pairs), "add")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != Z.device):
+            raise ValueError(f"{name} must be a contiguous device float64 tensor of shape {shape}")
+    out = torch.empty((K, S + 1, n_pairs), dtype=torch.float64, device=Z.device)
+    with torch.cuda.device(Z.device):
+        _lib.check(_lib.load().rato_hopper_nlp_hessian(
+            C.byref(params), K, _lib.ptr(Z), ldz, _lib.ptr(lam_dyn), _lib.ptr(lam_rows), _lib.ptr(add), _lib.ptr(out),
+            _lib.current_stream()), "rato_hopper_nlp_hessian")
+    return out
+
+
+def scatter_f64(src, index_map, dst, scale=None):
+    """rato_scatter_f64: dst[k][map[i]] = scale[i] src[k][i]; src (K, n), dst (K, n_dst) device fp64, map (n,) device int64
+    (entries outside [0, n_dst) are not emitted), scale (n,) device fp64 or None"""
+    K, n = src.shape
+    if dst.shape[0] != K or index_map.shape != (n,) or index_map.dtype != torch.int64 or src.dtype != torch.float64 or \
+            dst.dtype != torch.float64 or not (src.is_contiguous() and dst.is_contiguous() and index_map.is_contiguous()):
+        raise ValueError("scatter_f64: src (K, n) and dst (K, n_dst) float64, map (n,) int64, all contiguous")
+    if scale is not None and (scale.shape != (n,) or scale.dtype != torch.float64 or not scale.is_contiguous()):
+        raise ValueError("scatter_f64: scale must be (n,) float64")
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.load().rato_scatter_f64(K, n, _lib.ptr(src), n, _lib.ptr(index_map), _lib.ptr(scale), _lib.ptr(dst),
+                                                dst.shape[1], dst.shape[1], _lib.current_stream()), "rato_scatter_f64")
+    return dst
+
+
+def block_variables(S, t):
+    """indices in z of the local variables (x_t (8), u_t (4)) of step block t; the u part of block S does not exist (-1)"""
+    u = n_x * (S + 1) + n_u * t + np.arange(n_u) if t < S else -np.ones(n_u, dtype=np.int64)
+    return np.concatenate([n_x * t + np.arange(n_x), u]).astype(np.int64)
+
+
 class Model:
     def __init__(self, M, method='baseline', alpha=0.1, S=S, fields=None, device='cuda:0', rng=None,
-                 verbose=False):
+                 verbose=False, phases=None):
         # hopper.py:91-104
         if verbose:
             print("Initializing Model with")
             print("> method =", method)
             print("> alpha  =", alpha)
         self.method, self.alpha, self.S, self.M = method, alpha, S, M
-        self.time_jump, self.time_land = phase_times(S)
+        self.time_jump, self.time_land = phase_times(S) if phases is None else (int(phases[0]), int(phases[1]))
+        self.dt = T / S
         self.device = torch.device(device)
         self._lib = _lib.load()
         self.num_vars = (S + 1) * n_x + S * n_u + M + 2
@@ -348,3 +440,363 @@ class Model:
         return stats.risk_stats(Z, self.alpha if alpha is None else alpha)
 
     avar = staticmethod(stats.monte_carlo_avar)
+
+    # ---- the whole NLP (hopper.py:441-453, :491-562, :569-640) -------------------------------------------------------------
+    @classmethod
+    def host_only(cls, M, method='saa', alpha=0.1, S=S, phases=None):
+        """a Model without friction fields or a device: for the members that compute on the host alone (nlp_layout, gL_gU,
+        x_bounds, f, grad_f, fold_multipliers); every device call on it fails"""
+        self = cls(M, method, alpha, S=S, fields='device', device='cpu', phases=phases)
+        self._a = self._th = self._tau = torch.empty((num_mu_features, M), dtype=torch.float32)
+        return self
+
+    def nlp_layout(self):
+        """Host-only description of g in the script's order (:503-513), built once: the offsets of the ten groups, the fixed
+        structural pattern of jac_g in CSC order and the index maps the device emission uses.
+          off        offsets of dyn, x0, xf, slip, contact, over, risk, control, slack, len; ncon; C (contact steps)
+          det_*      the deterministic rows' CSC (every row but the risk group's): indices, indptr, constant values
+          map_defect [S][8][12] / map_rows [S+1][2][4] -> position in the deterministic CSC values (-1: not emitted),
+          scale_rows -1 on the leg-over-ground rows
+          map_hess   [S+1][78] -> position in np.tril_indices(nvar) order (-1: the u part of the last block)
+          lam_rows_index / lam_rows_sign  [S+1][2]: which multiplier of g weighs the state row (-1: none), and its sign
+          jac_indices / jac_indptr / pos_det / pos_slip   the full pattern and where the two value arrays go in it"""
+        lay = getattr(self, "_nlp_layout", None)
+        if lay is not None:
+            return lay
+        S, M, tj, tl, nvar = self.S, self.M, self.time_jump, self.time_land, self.num_vars
+        if not 0 <= tj <= tl <= S:
+            raise ValueError(f"phase times must satisfy 0 <= time_jump <= time_land <= S, got {tj}, {tl}, {S}")
+        saa = self.method != 'baseline'
+        Cn = tj + (S - tl)
+        n_state = tj + (S + 1 - tl)
+        n_risk = (1 + M + M * Cn + 1) if saa else M * Cn
+        names = ("dyn", "x0", "xf", "slip", "contact", "over", "risk", "control", "slack", "len")
+        counts = (n_x * S, n_x, 2, n_state, n_state, tl - tj, n_risk, n_u * S, 1, 3 * S)
+        off, o = {}, 0
+        for name, k in zip(names, counts):
+            off[name] = o
+            o += k
+        ncon = o
+        nX = n_x * (S + 1)
+        states = np.concatenate([np.arange(0, tj), np.arange(tl, S + 1)]).astype(np.int64)
+        rows, cols, consts, src = [], [], [], []        # src: ('d', flat index) / ('r', flat index) / None for a constant
+
+        def put(r, c, v=0.0, s=None):
+            rows.append(int(r)), cols.append(int(c)), consts.append(float(v)), src.append(s)
+        for t in range(S):
+            v = block_variables(S, t)
+            for i in range(n_x):
+                for j in range(n_l):
+                    put(n_x * t + i, v[j], s=('d', (t * n_x + i) * n_l + j))
+                put(n_x * t + i, n_x * (t + 1) + i, 1.0)                         # the x_{t+1} coefficient
+        for i in range(n_x):
+            put(off["x0"] + i, i, 1.0)
+        for j in range(2):
+            put(off["xf"] + j, n_x * S + 4 + j, 1.0)
+        xsel = (2, 3, 6, 7)
+        lam_index = -np.ones((S + 1, 2), dtype=np.int64)
+        lam_sign = np.zeros((S + 1, 2))
+        for i, t in enumerate(states):
+            for j in range(4):
+                put(off["slip"] + i, n_x * t + xsel[j], s=('r', (t * 2 + 0) * 4 + j))
+            put(off["slip"] + i, n_x * t + 4, 1.0)
+            for j in range(2):
+                put(off["contact"] + i, n_x * t + xsel[j], s=('r', (t * 2 + 1) * 4 + j))
+            put(off["contact"] + i, n_x * t + 1, 1.0)
+            lam_index[t] = off["slip"] + i, off["contact"] + i
+            lam_sign[t] = 1.0, 1.0
+        scale_rows = np.ones((S + 1) * 8)
+        for i, t in enumerate(range(tj, tl)):
+            for j in range(2):
+                put(off["over"] + i, n_x * t + xsel[j], s=('r', (t * 2 + 1) * 4 + j))
+                scale_rows[(t * 2 + 1) * 4 + j] = -1.0
+            put(off["over"] + i, n_x * t + 1, -1.0)
+            lam_index[t, 1], lam_sign[t, 1] = off["over"] + i, -1.0
+        for k in range(n_u * S):
+            put(off["control"] + k, nX + k, 1.0)
+        put(off["slack"], nvar - 2, 1.0)
+        for j, comp in enumerate((3, 7, 6)):
+            for t in range(S):
+                put(off["len"] + j * S + t, n_x * (t + 1) + comp, 1.0)
+        rows, cols, consts = np.array(rows, dtype=np.int64), np.array(cols, dtype=np.int64), np.array(consts)
+        order = np.lexsort((rows, cols))
+        where = np.empty_like(order)
+        where[order] = np.arange(order.size)
+        map_defect = -np.ones(S * n_x * n_l, dtype=np.int64)
+        map_rows = -np.ones((S + 1) * 8, dtype=np.int64)
+        for e, s in enumerate(src):
+            if s is not None:
+                (map_defect if s[0] == 'd' else map_rows)[s[1]] = where[e]
+        det_indices = rows[order]
+        det_indptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=nvar))]).astype(np.int64)
+        # the tril-packed Hessian: entry e of block t is (v[r], v[c]) of np.tril_indices(nvar); x indices lie below u indices
+        tr, tc = np.tril_indices(n_l)
+        map_hess = -np.ones((S + 1, n_pairs), dtype=np.int64)
+        for t in range(S + 1):
+            v = block_variables(S, t)
+            gr, gc = v[tr], v[tc]
+            ok = (gr >= 0) & (gc >= 0)
+            map_hess[t, ok] = gr[ok] * (gr[ok] + 1) // 2 + gc[ok]
+        lay = dict(off=off, ncon=ncon, nvar=nvar, C=Cn, n_state=n_state, n_risk=n_risk, states=states, det_indices=det_indices,
+                   det_indptr=det_indptr, det_const=consts[order], map_defect=map_defect, map_rows=map_rows,
+                   scale_rows=scale_rows, map_hess=map_hess, lam_rows_index=lam_index, lam_rows_sign=lam_sign)
+        # the full pattern: the deterministic entries and the risk group's (the slip Jacobian's own pattern), column by column
+        if Cn > 0:
+            s_idx, s_ptr = self._jacobian_pattern(Cn)
+        else:
+            s_idx, s_ptr = np.zeros(0, dtype=np.int64), np.zeros(nvar + 1, dtype=np.int64)
+        s_cols = np.repeat(np.arange(nvar), np.diff(s_ptr))
+        d_cols = np.repeat(np.arange(nvar), np.diff(det_indptr))
+        all_rows = np.concatenate([det_indices, off["risk"] + np.asarray(s_idx, dtype=np.int64)])
+        all_cols = np.concatenate([d_cols, s_cols])
+        order = np.lexsort((all_rows, all_cols))
+        where = np.empty_like(order)
+        where[order] = np.arange(order.size)
+        lay.update(jac_indices=all_rows[order].astype(np.int32),
+                   jac_indptr=np.concatenate([[0], np.cumsum(np.bincount(all_cols, minlength=nvar))]).astype(np.int64),
+                   pos_det=where[:det_indices.size], pos_slip=where[det_indices.size:])
+        self._nlp_layout = lay
+        return lay
+
+    def f(self, Z):
+        """:441-453"""
+        Z = np.asarray(Z, dtype=np.float64)
+        xs, us = self.convert_z_to_xs_us_mats(Z)
+        R = 1.0
+        return float(np.sum(R * (us[:, 0] * us[:, 0]) + R * (us[:, 1] * us[:, 1])) - 10000 * xs[-1, 0] + 10000000 * Z[-2])
+
+    def grad_f(self, Z):
+        Z = np.asarray(Z, dtype=np.float64)
+        g = np.zeros(self.num_vars)
+        nX = n_x * (self.S + 1)
+        ui = nX + n_u * np.arange(self.S)
+        g[ui], g[ui + 1] = 2.0 * Z[ui], 2.0 * Z[ui + 1]
+        g[n_x * self.S] = -10000.0
+        g[-2] = 10000000.0
+        return g
+
+    def gL_gU(self):
+        """:515-562"""
+        lay = self.nlp_layout()
+        off, S, tj, tl = lay["off"], self.S, self.time_jump, self.time_land
+        g_L, g_U = np.zeros(lay["ncon"]), np.zeros(lay["ncon"])
+        g_L[off["over"]:] = -1e15
+        cl, cu = np.zeros((S, n_u)), np.zeros((S, n_u))
+        cl[:, :2], cu[:, :2] = -u_max, u_max                     # :401-406
+        cu[:tj, 2:] = max_contact_force                          # :409-427: zero in flight
+        cu[tl:, 2:] = max_contact_force
+        g_L[off["control"]:off["slack"]], g_U[off["control"]:off["slack"]] = cl.reshape(-1), cu.reshape(-1)
+        g_L[off["slack"]], g_U[off["slack"]] = 0.0, 1e6          # :430-438
+        g_L[off["len"]:] = np.concatenate([0.25 * np.ones(S), -4.0 * np.ones(S), -2.5 * np.ones(S)])   # :369-390
+        g_U[off["len"]:] = np.concatenate([1.0 * np.ones(S), 4.0 * np.ones(S), 2.5 * np.ones(S)])
+        return g_L, g_U
+
+    def x_bounds(self):
+        """:599-620"""
+        x_L, x_U = -np.ones(self.num_vars) * 1000.0, np.ones(self.num_vars) * 1000.0
+        lo = np.array([-3, 0.5, -np.pi / 2, 0.1, -500, -500, -500, -500])
+        hi = np.array([3, 10, np.pi / 2, 3, 500, 500, 500, 500])
+        x_L[:n_x * (self.S + 1)] = np.tile(lo, self.S + 1)
+        x_U[:n_x * (self.S + 1)] = np.tile(hi, self.S + 1)
+        return x_L, x_U
+
+    def _nlp_state(self, K):
+        """device-side constants of the emission: the maps (uploaded once) and, per K, the destinations zeroed / pre-filled once"""
+        st = getattr(self, "_nlp_dev", None)
+        if st is None:
+            lay = self.nlp_layout()
+            up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=self.device)
+            st = dict(params=nlp_params(self.S, self.time_jump, self.time_land, self.dt), map_defect=up(lay["map_defect"]),
+                      map_rows=up(lay["map_rows"]), scale_rows=up(lay["scale_rows"]), map_hess=up(lay["map_hess"].reshape(-1)),
+                      det_const=up(lay["det_const"]), templates={})
+            self._nlp_dev = st
+        if K not in st["templates"]:
+            n_tril = self.num_vars * (self.num_vars + 1) // 2
+            st["templates"][K] = (st["det_const"][None].repeat(K, 1).contiguous(),
+                                  torch.zeros((K, n_tril), dtype=torch.float64, device=self.device))
+        return st
+
+    def fold_multipliers(self, lams):
+        """(K, ncon) multipliers of g -> lam_dyn (K, S, 8), lam_rows (K, S+1, 2): the no-slip and contact multipliers on the
+        contact states and minus the leg-over-ground multiplier on the flight states (host arrays)"""
+        lay = self.nlp_layout()
+        lams = np.atleast_2d(np.asarray(lams, dtype=np.float64))
+        if lams.shape[1] != lay["ncon"]:
+            raise ValueError(f"lams must be (K, {lay['ncon']}), got {lams.shape}")
+        idx, sign = lay["lam_rows_index"], lay["lam_rows_sign"]
+        lam_rows = np.where(idx >= 0, lams[:, np.maximum(idx, 0)], 0.0) * sign
+        return np.ascontiguousarray(lams[:, :n_x * self.S]).reshape(-1, self.S, n_x), np.ascontiguousarray(lam_rows)
+
+    def nlp_device(self, Zs, lams=None, add=None):
+        """K problems per call.  Zs (K, nvar) host array or device fp64 tensor (rows may be strided: ldz >= nvar); lams
+        (K, ncon) multipliers of g or None; add (K, S+1, 78) blocks added to the Hessian or None.  -> dict of fp64 DEVICE tensors:
+        defect (K, S, 8), d_defect (K, S, 8, 12), rows (K, S+1, 2), d_rows (K, S+1, 2, 4), jac_values (K, nnz): the CSC values of
+        the deterministic rows' Jacobian in ``nlp_layout()``'s det_indices / det_indptr order; and with lams: hess_blocks
+        (K, S+1, 78), hess_tril (K, nvar (nvar+1)/2) in np.tril_indices(nvar) order.  Four launches without lams, six with."""
+        dev = self.device
+        if not isinstance(Zs, torch.Tensor):
+            Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=dev)
+        if Zs.dim() != 2 or Zs.shape[1] < self.num_vars:
+            raise ValueError(f"Zs must be (K, >= {self.num_vars}), got {tuple(Zs.shape)}")
+        K = Zs.shape[0]
+        st = self._nlp_state(K)
+        jac_t, hess_t = st["templates"][K]
+        out = nlp_linearize_device(st["params"], Zs)
+        jac = jac_t.clone()
+        scatter_f64(out["d_defect"].view(K, -1), st["map_defect"], jac)
+        scatter_f64(out["d_rows"].view(K, -1), st["map_rows"], jac, st["scale_rows"])
+        out["jac_values"] = jac
+        if lams is not None:
+            lam_dyn, lam_rows = self.fold_multipliers(lams.cpu().numpy() if isinstance(lams, torch.Tensor) else lams)
+            if lam_dyn.shape[0] != K:
+                raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")
+            if add is not None and not isinstance(add, torch.Tensor):
+                add = torch.as_tensor(np.ascontiguousarray(add, dtype=np.float64), device=dev)
+            blocks = nlp_hessian_device(st["params"], Zs, torch.as_tensor(lam_dyn, device=dev),
+                                        torch.as_tensor(lam_rows, device=dev), add)
+            tril = hess_t.clone()
+            scatter_f64(blocks.view(K, -1), st["map_hess"], tril)
+            out["hess_blocks"], out["hess_tril"] = blocks, tril
+        return out
+
+    def g(self, Z, _lin=None):
+        """:491-514: all ten groups in the script's order (float64); the risk group is ``slip_risk_constraints`` (fp32 path)"""
+        Z = np.asarray(Z, dtype=np.float64)
+        lay = self.nlp_layout()
+        r = _lin if _lin is not None else self.nlp_device(Z[None])
+        defect, rows = r["defect"][0].cpu().numpy(), r["rows"][0].cpu().numpy()
+        xs, us = self.convert_z_to_xs_us_mats(Z)
+        st, tj, tl = lay["states"], self.time_jump, self.time_land
+        risk = self.slip_risk_constraints(Z) if lay["C"] > 0 else self._risk_without_contacts(Z)
+        return np.concatenate([defect.reshape(-1), xs[0] - state_initial, (xs[-1] - state_final)[4:6], rows[st, 0], rows[st, 1],
+                               -rows[tj:tl, 1], risk, us.reshape(-1), [Z[-2]], xs[1:, 3], xs[1:, 7], xs[1:, 6]])
+
+    def _risk_without_contacts(self, Z):
+        """the risk group when no step is in contact (:339-367 with num_contacts = 0)"""
+        if self.method == 'baseline':
+            return np.zeros(0)
+        _, _, ys, _, t_risk = self.convert_z_to_variables(Z)
+        return np.concatenate([[(self.M * self.alpha) * t_risk + np.sum(ys)], -ys, [0.0]])
+
+    def jac_g(self, Z, _lin=None):
+        """jacrev(g)(Z) (:569) as a scipy CSC (ncon, nvar) in the script's row and column order, with a FIXED structural
+        pattern (``nlp_layout()``: jac_indices / jac_indptr), exact zeros stored: the device-written deterministic values
+        stacked with the ``slip_jacobian_device`` values.  ``.toarray()`` is what grad_g_jax returns."""
+        import scipy.sparse as sp
+        Z = np.asarray(Z, dtype=np.float64)
+        lay = self.nlp_layout()
+        r = _lin if _lin is not None else self.nlp_device(Z[None])
+        data = np.zeros(lay["jac_indices"].size)
+        data[lay["pos_det"]] = r["jac_values"][0].cpu().numpy()
+        if lay["C"] > 0:
+            vals, _, indptr, _ = self.slip_jacobian_device(Z)
+            slip = vals.double().cpu().numpy()
+            if self.method != 'baseline':
+                slip[indptr[-2]] = self._a.shape[1] * self.alpha   # row 0 of the t_risk column: M alpha in fp64, as slip_jacobian
+            data[lay["pos_slip"]] = slip
+        return sp.csc_matrix((data, lay["jac_indices"], lay["jac_indptr"]), shape=(lay["ncon"], lay["nvar"]))
+
+    def slip_hessian_blocks(self, Z, lam):
+        """the risk group's share of hess(lam . g) as step blocks (S+1, 78), computed as ``slip_hessian`` computes it: per
+        contact the 3 x 3 block on (x0, x2, x3) of its step and the mixed entries with fz (local 0, 2, 3 and 11)"""
+        lay = self.nlp_layout()
+        blocks = np.zeros((self.S + 1, n_l, n_l))
+        Cn, M = lay["C"], self._a.shape[1]
+        if Cn > 0:
+            r0 = lay["off"]["risk"] + (1 + M if self.method != 'baseline' else 0)
+            lam_s = np.asarray(lam, dtype=np.float64)[r0:r0 + M * Cn].reshape(M, Cn)
+            px, forces = self.contact_inputs(Z)
+            D = self.slip_hessian_sums3(px, forces, lam_s)
+            Jee, Hee = self.contact_chain(Z)
+            blk = D[:, 1, None, None] * Jee[:, :, None] * Jee[:, None, :] + D[:, 2, None, None] * Hee
+            mixed = D[:, 0, None] * Jee
+            steps, loc = self.contact_steps(), np.array([0, 2, 3])
+            blocks[steps[:, None, None], loc[None, :, None], loc[None, None, :]] = blk
+            blocks[steps[:, None], 11, loc[None, :]] = mixed
+            blocks[steps[:, None], loc[None, :], 11] = mixed
+        tr, tc = np.tril_indices(n_l)
+        return blocks[:, tr, tc]
+
+    def _hess_add(self, Z, lam, obj_factor):
+        add = self.slip_hessian_blocks(Z, lam)
+        tr, tc = np.tril_indices(n_l)
+        diag_u = np.flatnonzero((tr == tc) & ((tr == n_x) | (tr == n_x + 1)))
+        add[:self.S, diag_u] += 2.0 * float(obj_factor)          # hess_f: 2 R on u0 and u1, R = 1 (:443-448)
+        return add
+
+    def _hess_device(self, Z, lam, obj_factor):
+        Z = np.asarray(Z, dtype=np.float64)
+        lam = np.asarray(lam, dtype=np.float64)
+        return self.nlp_device(Z[None], lam[None], add=self._hess_add(Z, lam, obj_factor)[None])
+
+    def hess_lagrangian(self, Z, lam, obj_factor=1.0):
+        """obj_factor hess_f + hess(lam . g) as the tril-packed vector eval_h writes (:622-628)"""
+        return self._hess_device(Z, lam, obj_factor)["hess_tril"][0].cpu().numpy()
+
+    def hess_lagrangian_blocks(self, Z, lam, obj_factor=1.0):
+        """the same Hessian as its S + 1 step blocks (S+1, 12, 12) on (x_t, u_t); nothing lies outside them"""
+        v = self._hess_device(Z, lam, obj_factor)["hess_blocks"][0].cpu().numpy()
+        tr, tc = np.tril_indices(n_l)
+        B = np.zeros((self.S + 1, n_l, n_l))
+        B[:, tr, tc] = v
+        B[:, tc, tr] = v
+        return B
+
+    def ipopt_callbacks(self, sparse=False):
+        """-> dict(eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h, g_L, g_U, x_L, x_U, eval_jac_g_sparsity_indices,
+        eval_h_sparsity_indices, nvar, ncon): the arguments of the script's ``ipyopt.Problem(...)`` call (:646-661), same
+        signatures (the callbacks write into ``out``).  sparse=False: the script's dense row-major Jacobian and tril Hessian
+        (:633-640).  sparse=True: the index pairs are the structural patterns (CSC order of ``jac_g``; the step blocks of the
+        Hessian) and ``out`` holds only those entries.  eval_g and eval_jac_g at the same x share one evaluation."""
+        lay = self.nlp_layout()
+        nvar, ncon, S = lay["nvar"], lay["ncon"], self.S
+        cache = {}
+
+        def lin(x):
+            x = np.asarray(x, dtype=np.float64)
+            key = x.tobytes()
+            if cache.get("key") != key:
+                cache["key"], cache["val"] = key, self.nlp_device(x[None])
+            return cache["val"]
+
+        def eval_f(x):
+            return self.f(x)
+
+        def eval_grad_f(x, out):
+            out[:] = self.grad_f(x)
+            return out
+
+        def eval_g(x, out):
+            out[:] = self.g(x, _lin=lin(x))
+            return out
+        g_L, g_U = self.gL_gU()
+        x_L, x_U = self.x_bounds()
+        if not sparse:
+            def eval_jac_g(x, out):
+                out[:] = self.jac_g(x, _lin=lin(x)).toarray().reshape(-1)
+                return out
+
+            def eval_h(x, lagrange, obj_factor, out):
+                out[:] = self.hess_lagrangian(x, lagrange, obj_factor)
+                return out
+            i1, i2 = np.indices((ncon, nvar))
+            jac_idx = (i1.flatten(), i2.flatten())
+            r, c = np.tril_indices(nvar)
+            h_idx = (r.flatten(), c.flatten())
+        else:
+            keep = np.flatnonzero(lay["map_hess"].reshape(-1) >= 0)
+            tr, tc = np.tril_indices(n_l)
+            hr = np.concatenate([block_variables(S, t)[tr] for t in range(S + 1)])[keep]
+            hc = np.concatenate([block_variables(S, t)[tc] for t in range(S + 1)])[keep]
+
+            def eval_jac_g(x, out):
+                out[:] = self.jac_g(x, _lin=lin(x)).data
+                return out
+
+            def eval_h(x, lagrange, obj_factor, out):
+                out[:] = self._hess_device(x, lagrange, obj_factor)["hess_blocks"][0].cpu().numpy().reshape(-1)[keep]
+                return out
+            jac_idx = (lay["jac_indices"].astype(np.int64), np.repeat(np.arange(nvar), np.diff(lay["jac_indptr"])))
+            h_idx = (hr, hc)
+        return dict(eval_f=eval_f, eval_grad_f=eval_grad_f, eval_g=eval_g, eval_jac_g=eval_jac_g, eval_h=eval_h, g_L=g_L, g_U=g_U,
+                    x_L=x_L, x_U=x_U, eval_jac_g_sparsity_indices=jac_idx, eval_h_sparsity_indices=h_idx, nvar=nvar, ncon=ncon)
