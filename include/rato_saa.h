@@ -545,6 +545,10 @@ int rato_drone_linearize_generators(const rato_drone_params* p, const float* us,
  * sample; it is a valid cut under ANY linearization,
  *     CVaR(m(x)) >= (1/(alpha M)) sum_i w_i [(G_i x)_{r_i} + sign base_{i,r_i}],
  * tight at the x it was computed for under the linearization it was computed with.
+ * lambda is formed in fp64 from the record and then carried as a FLOAT, in every tail-rows form and in rato_kkt_sums
+ * (the products and sums are fp64): a sum differs from the fp64 rule by at most |float(lambda) - lambda| sum_ties |entry|
+ * <= 2^-24 lambda sum_ties |entry| -- nothing where lambda is 0, 1 or dyadic (tests/test_gpu_cut_tails.py holds the
+ * kernels to that term).
  * K cuts kept in rings  m_base [slot][M], arg_base [slot][M], stats_base [slot][stats_stride >= 11 doubles]  are
  * evaluated in one launch (slots: device array of K ring slots; NULL: K = 1, the pointers are the slot):
  *   part[blk][k][0 .. 2(S-1))  block sums of w_i G_i[r_i, (s,g)]      (doubles)
