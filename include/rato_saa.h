@@ -477,8 +477,9 @@ int rato_hopper_emit_jacobian_values(int32_t M, int32_t C, int32_t saa, double a
  * tile-blocked Jacobian of the linearize calls (tile = its TILE, n_g = 2,
  * R = 3 drone / 1 driving).  scale = the reference's MULTIPLIER (0.01 drone, 1
  * driving), times 1e-7 while scp_iter < 2 (drone_risk.py:413-415).
- * The transposition is staged through 64 (R (S-1) + 1) floats of LDS: RATO_EINVAL when that exceeds 160 KB
- * (S > 213 for the drone, S > 639 for driving) -- the facades then assemble on the host from the untiled Jacobian
+ * The transposition is staged through 64 (R (S-1) + 1) floats of LDS: RATO_EINVAL when that exceeds 160 KiB = 163,840 B
+ * (S > 214 for the drone, S > 640 for driving; S = 214 / 640 take exactly 163,840 B and are accepted) -- the facades then
+ * assemble on the host from the untiled Jacobian
  * (Model.get_constraints_coeffs_host), same pattern and values.
  */
 int rato_emit_csc_values(const float* G, const float* W /* NULL, or the factor of a factored G */,

@@ -60,7 +60,7 @@ extern "C" int rato_emit_csc_values(const float* G, const float* W, int64_t ld, 
   RATO_CLEAR_ERROR();
   if (!G || !out || M <= 0 || S < 2 || n_g <= 0 || R <= 0 || (tile != 64 && tile != 256)) return RATO_EINVAL;
   const size_t lds = (size_t)64 * ((size_t)R * (S - 1) + 1) * sizeof(float);
-  if (lds > 160 * 1024) return RATO_EINVAL;  // S <= 213 (drone, R = 3) / 639 (driving, R = 1): beyond, assemble on the host
+  if (lds > 160 * 1024) return RATO_EINVAL;  // S <= 214 (drone, R = 3) / 640 (driving, R = 1), both exactly 160 KiB: beyond, assemble on the host
   static rato::DynamicLdsLimit lds_limit;   // per device
   {
     const hipError_t e = lds_limit.ensure(lds, [](size_t) {
