@@ -689,6 +689,12 @@ class CvarCutSolver:
         return info
 
 
+def _check_record_size(struct, n_lib):
+    """RatoError unless the library lays a per-iteration record out as the ctypes struct the loops below read it with"""
+    if _lib.C.sizeof(struct) != n_lib:
+        raise _lib.RatoError(f"{struct.__name__} is {_lib.C.sizeof(struct)} bytes here, {n_lib} in the library (stale build?)")
+
+
 def scp_run(lib, cs, us0, iters, run, what, check_finite):
     """The native SCP loop of ONE problem behind ``drone_risk.Model.scp_run_native`` / ``driving.Model.scp_run_native``: runs
     it on the solver's native handle and lets the solver's Python-side state follow the native one.
@@ -703,7 +709,7 @@ def scp_run(lib, cs, us0, iters, run, what, check_finite):
         raise ValueError(f"us0 must be ({S},{n_u}), got {us0.shape}")
     h = cs._native_solver()
     out = cs._keep_arrays()
-    assert C.sizeof(_lib.ScpIter) == lib.rato_scp_iter_bytes()
+    _check_record_size(_lib.ScpIter, lib.rato_scp_iter_bytes())
     rec = (_lib.ScpIter * max(iters, 1))()
     us_hist = np.zeros((max(iters, 1), S, n_u))
     done = C.c_int32(0)
@@ -800,8 +806,8 @@ def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, che
         n_keep[k] = len(cs.keep)
         keep[k, :len(cs.keep)] = cs.keep
         idle[k, :len(cs.keep)] = [cs.idle.get(sl, 0) for sl in cs.keep]
-    assert C.sizeof(_lib.ScpIter) == lib.rato_scp_iter_bytes()
-    assert C.sizeof(_lib.ScpBatchIter) == lib.rato_scp_batch_iter_bytes()
+    _check_record_size(_lib.ScpIter, lib.rato_scp_iter_bytes())
+    _check_record_size(_lib.ScpBatchIter, lib.rato_scp_batch_iter_bytes())
     n_it = max(int(iters), 1)
     rec = (_lib.ScpIter * (K * n_it))()
     brec = (_lib.ScpBatchIter * n_it)()
@@ -830,3 +836,19 @@ def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, che
             "done": done.copy(), "rounds": int(rounds.value), "define_s": g("define_s"), "oracle_s": g("oracle_s"),
             "master_s": g("master_s"), "total_s": g("total_s"), "rounds_per_iter": g("rounds").astype(np.int64),
             "active": g("active").astype(np.int64)}
+
+
+def scp_run_native_batch(models, check, us0, n_u, entry, lead, loop_args, n_threads, check_finite):
+    """``drone_risk.scp_run_native_batch`` / ``driving.scp_run_native_batch``: ``check(models)`` (the module's ``_check_batch``),
+    the solvers of ``scp_batch_inputs``, then ``scp_batch_run`` on the library's ``entry`` (rato_scp_batch_run_*).  ``lead(model)``
+    -> the fp64 arrays the entry takes between us0 and ``loop_args`` = (iters, first_cvar, tol, max_cuts, final_cut_above)."""
+    models = list(models)
+    check(models)
+    us0, solvers = scp_batch_inputs(models, us0, n_u)
+    lib = models[0]._lib
+    arrays = lead(models[0])
+    iters, first_cvar, tol, max_cuts, final_cut_above = loop_args
+    run = lambda h, *tail: getattr(lib, entry)(
+        h, us0.ctypes.data, *[a.ctypes.data for a in arrays], int(iters), int(first_cvar), float(tol), int(max_cuts),
+        float(final_cut_above), int(bool(check_finite)), *tail)
+    return scp_batch_run(lib, models[0].device, solvers, us0, iters, run, entry, n_threads=n_threads, check_finite=check_finite)

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib, assemble, cvar_cuts, qp, stats
 from . import driving_params as P
+from ._saa_model import SaaModel
 from .scp import L2_error_us  # noqa: F401  (the reference's module-level name, driving.py:459-464)
 
 n_x, n_u = P.n_x, P.n_u
@@ -75,7 +76,10 @@ def to_soa_inputs(states_init, omegas_speed, omegas_repulsive, DWs, device):
     return dW, x0_ped, ws, wr
 
 
-class Model:
+class Model(SaaModel):
+    N_U, N_NOISE, PARAMS, RCOST = n_u, 2, _lib.CarParams, P.R     # (KAPPA, CUT_ROWS, CUT_RHS0: the base's 1.0, 1, 0.0)
+    SLACK_PENALTY = 1000.0      # driving.py:387-388
+
     # scp.run_drone_reduced takes the native SCP loop by default only where a Model says so: the driving loop's native form
     # (rato_scp_run_car) computes its final rows natively, to rounding the NumPy ones -- it is asked for explicitly
     # (scp.run_driving_reduced(native_loop=True)), so that the default results stay what they were to the bit
@@ -85,6 +89,7 @@ class Model:
     def __init__(self, M, method='saa', alpha=0.05, S=P.S, device='cuda:0', rng=None,
                  samples=None, verbose=False, check_finite=False):
         self.check_finite = check_finite        # scan every linearization for NaN/Inf -> RatoNonFiniteError (scp.py)
+        self._init_state()
         if verbose:
             print("Initializing Model with")
             print("> method =", method)
@@ -125,30 +130,23 @@ class Model:
         return self
 
     # ---- layout helpers (driving.py:122-143) -------------------------------
-    def convert_us_vec_to_us_mat(self, us_vec):
-        return np.reshape(np.asarray(us_vec), (n_u, self.S), 'F').T.copy()
-
-    def convert_us_mat_to_us_jaxvec(self, us_mat):
-        return np.reshape(np.asarray(us_mat), (self.S * n_u), 'C')
-
     def initial_guess_us_mat(self):
         return np.zeros((self.S, n_u)) + (self.u_max + self.u_min) / 2.0 + 1e-2
 
     # ---- plumbing ----------------------------------------------------------
-    def _params(self, M):
-        """a fresh rato_car_params (a copy of a template built once per (M, S, dt, beta, ego state): see drone_risk)"""
-        key = (M, self.S, self.dt, self.beta, tuple(float(v) for v in self._ego_init))
-        cache = self.__dict__.setdefault("_params_cache", {})
-        t = cache.get(key)
-        if t is None:
-            if len(cache) > 64:
-                cache.clear()
-            t = cache[key] = self._params_build(M)
-        return _lib.CarParams.from_buffer_copy(t)
+    def _batch_shape(self, inputs=None):
+        """-> (M, row stride) of ``inputs`` (default: the model's batch); the driving arrays carry no padding"""
+        M = (inputs[2] if inputs is not None else self._ws).numel()
+        return M, M
 
-    def _params_build(self, M):
+    def _params_key(self, M, rows_out=0):
+        """what the template of ``_params(M[, rows_out])`` depends on"""
+        return (M, int(rows_out), self.S, self.dt, self.beta, tuple(float(v) for v in self._ego_init))
+
+    def _params_build(self, M, rows_out=0):
         p = _lib.CarParams()
         p.M, p.S, p.dt, p.beta = M, self.S, self.dt, self.beta
+        p.rows_out = int(rows_out)      # 1: g_up receives g itself (base of the cut oracle's delta form, cvar_cuts.py)
         p.speed_ped_des = P.speed_ped_des
         p.d_min = float(P.min_separation_distance)
         p.tol = OSQP_TOL
@@ -161,18 +159,6 @@ class Model:
         p.speed_ped_des64, p.d_min64 = float(P.speed_ped_des), float(P.min_separation_distance)
         return p
 
-    def _us_device(self, us_mat):
-        if isinstance(us_mat, torch.Tensor) and us_mat.is_cuda:
-            us = us_mat.float().contiguous()
-        else:
-            us = torch.as_tensor(np.ascontiguousarray(np.asarray(us_mat), dtype=np.float32), device=self.device)
-        if tuple(us.shape) != (self.S, n_u):
-            raise ValueError(f"us_mat must be ({self.S},{n_u}), got {tuple(us.shape)}")
-        return us
-
-    def _empty(self, *shape):
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
-
     # ---- rollout + separation distances (K3) -------------------------------
     def eval_device(self, us_mat, want_xs=False, want_g=False, inputs=None, out=None, stats_request=None):
         """-> (Z [M], xs [S+1][8][M] or None, g [S][M] or None), device tensors.  ``out``: a dict whose ``_Z`` / ``_g``
@@ -183,23 +169,15 @@ class Model:
         M = ws.numel()
         us = self._us_device(us_mat)
         o = out if out is not None else {}
-
-        def reuse(key, shape):
-            t = o.get(key)
-            if t is not None and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t
-            return self._empty(*shape)
-
-        Z = reuse("_Z", (M,))
+        Z = self._reuse(o, "_Z", (M,))
         xs = self._empty(self.S + 1, n_x, M) if want_xs else None
-        g = reuse("_g", (self.S, M)) if want_g else None
+        g = self._reuse(o, "_g", (self.S, M)) if want_g else None
         o["_Z"] = Z
         if g is not None:                                # (a call without g keeps the reusable g buffer of an earlier one)
             o["_g"] = g
         p = self._params(M)
-        if stats_request is not None:        # (workspace, record, alpha[, in_launch])
-            stats.request_in_launch(p, *stats_request[:3], flags=(stats.STATS_IN_LAUNCH if (len(stats_request) > 3 and
-                                                                                             stats_request[3]) else 0))
+        if stats_request is not None:
+            self._request_stats(p, stats_request)
         if dW is None:                                   # noise regenerated in the kernel (Philox, csrc/philox.h)
             _lib.check(self._lib.rato_car_eval_philox(C.byref(p), _lib.ptr(us), self._noise_seed, float(self.dt),
                                                       _lib.ptr(x0), _lib.ptr(ws), _lib.ptr(wr),
@@ -214,19 +192,6 @@ class Model:
                                            _lib.ptr(g), _lib.current_stream()), "rato_car_eval")
         return Z, xs, g
 
-    def mc_step_device(self, us_mat, alpha=None, out=None, workspace=None, stats_out=None, inputs=None, in_launch=False):
-        """One Monte-Carlo validation step on the device (driving.py:630-671: rollout -> max_t(-distance) -> fraction
-        satisfied / VaR / AVaR) as ONE library call -- for small batches one launch (ego tables, tiled rollout and the
-        exact selection).  -> (Z [M], record double[N_STATS]), device tensors."""
-        alpha = self.alpha if alpha is None else alpha
-        M = (inputs[2] if inputs is not None else self._ws).numel()
-        if workspace is None:
-            workspace = stats.new_workspace(M, self.device)
-        if stats_out is None:
-            stats_out = torch.empty(stats.N_STATS, dtype=torch.float64, device=self.device)
-        Z, _, _ = self.eval_device(us_mat, inputs=inputs, out=out, stats_request=(workspace, stats_out, alpha, in_launch))
-        return Z, stats_out
-
     def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None):
         """K control sequences on the model's batch in ONE call (rato_car_eval_batch; the reference's Monte-Carlo report,
         driving.py:675-740, evaluates its 4 alpha x 30 repeats one at a time).  ``us_batch`` (K, S, n_u) ->
@@ -237,30 +202,13 @@ class Model:
             raise _lib.RatoError("eval_batch_device reads a materialised dW (this Model regenerates its noise)")
         alpha = self.alpha if alpha is None else alpha
         M = ws.numel()
-        if isinstance(us_batch, torch.Tensor) and us_batch.is_cuda:
-            us = us_batch.float().contiguous()
-        else:
-            us = torch.as_tensor(np.ascontiguousarray(np.asarray(us_batch), dtype=np.float32), device=self.device)
-        if us.dim() != 3 or tuple(us.shape[1:]) != (self.S, n_u):
-            raise ValueError(f"us_batch must be (K,{self.S},{n_u}), got {tuple(us.shape)}")
+        us = self._us_batch_device(us_batch)
         K = us.shape[0]
-        o = out if out is not None else {}
-        Z = o.get("_Zb")
-        if Z is None or tuple(Z.shape) != (K, M):
-            Z = self._empty(K, M)
-        rec = workspace_ = None
-        if want_stats:
-            rec = o.get("_recb")
-            if rec is None or tuple(rec.shape) != (K, stats.N_STATS):
-                rec = torch.empty((K, stats.N_STATS), dtype=torch.float64, device=self.device)
-            workspace_ = workspace if workspace is not None else o.get("_wsb")
-            if workspace_ is None:
-                workspace_ = stats.new_workspace(M, self.device)
-        o["_Zb"], o["_recb"], o["_wsb"] = Z, rec, workspace_
+        Z, rec, workspace = self._batch_buffers(out if out is not None else {}, K, M, M, want_stats, workspace)
         p = self._params(M)
         _lib.check(self._lib.rato_car_eval_batch(
             C.byref(p), K, _lib.ptr(us), _lib.ptr(dW), _lib.ptr(x0), _lib.ptr(ws), _lib.ptr(wr), _lib.ptr(Z), M, float(alpha),
-            float(stats.SATISFIED_THRESHOLD), _lib.ptr(workspace_), workspace_.numel() if workspace_ is not None else 0,
+            float(stats.SATISFIED_THRESHOLD), _lib.ptr(workspace), workspace.numel() if workspace is not None else 0,
             _lib.ptr(rec), _lib.current_stream()), "rato_car_eval_batch")
         return Z, rec
 
@@ -307,36 +255,12 @@ class Model:
         return -g.t().double().cpu().numpy()
 
     # ---- linearization (K4) ------------------------------------------------
-    TILED_NOISE = True        # (class-level switch for A/B runs and the equality test)
-
-    def _tiled_noise(self, dW, M):
-        """The [tile][2S][64] copy of the MODEL'S OWN noise that the row-parallel kernel reads; made once, kept with
-        the source tensor itself (compared by identity, never by address).  A caller's ``inputs`` are not cached
-        (``None``: they go through the kernel that reads dW as it lies); an in-place refill of ``self._dW`` through raw
-        pointers needs ``set_noise`` / ``invalidate_noise``."""
-        if dW is not self._dW:
-            return None
-        c = getattr(self, "_dW_tiled_cache", None)
-        if c is None or c[0] is not dW or c[1] != dW._version or c[3] != (M, self.S):
-            n = int(self._lib.rato_car_tiled_noise_floats(M, self.S))
-            t = torch.empty(n, dtype=torch.float32, device=dW.device)
-            _lib.check(self._lib.rato_car_tile_noise(_lib.ptr(dW), M, self.S, _lib.ptr(t), _lib.current_stream()),
-                       "rato_car_tile_noise")
-            c = (dW, dW._version, t, (M, self.S))
-            self._dW_tiled_cache = c
-        return c[2]
-
-    def invalidate_noise(self):
-        """Forget every copy derived from ``self._dW`` (after an in-place refill of the noise array)."""
-        self._dW_tiled_cache = None
-
-    def set_noise(self, dW):
-        """Replace the batch's Brownian increments (kernel layout [S][2][M], fp32, on the model's device)."""
-        dW = _lib.require_f32_device(dW, "dW")
-        if tuple(dW.shape) != (self.S, 2, int(self._ws.numel())):
-            raise ValueError(f"dW must be ({self.S}, 2, {int(self._ws.numel())}), got {tuple(dW.shape)}")
-        self._dW = dW
-        self.invalidate_noise()
+    def _tile_noise(self, dW, M, ld):
+        """dW [S][2][M] -> its [tile][2S][64] copy (``_tiled_noise`` keeps it)"""
+        t = torch.empty(int(self._lib.rato_car_tiled_noise_floats(M, self.S)), dtype=torch.float32, device=dW.device)
+        _lib.check(self._lib.rato_car_tile_noise(_lib.ptr(dW), M, self.S, _lib.ptr(t), _lib.current_stream()),
+                   "rato_car_tile_noise")
+        return t
 
     def linearize_device(self, us_mat, inputs=None, cols_per_thread=0, out=None, want_Z=True, rows_out=0, stats_request=None):
         """-> dict: G [n_tiles][n_pairs][2][TILE], g_up [S][M], Z [M], final_du [4][2S], final_rhs [4]
@@ -352,23 +276,15 @@ class Model:
         if dW is None and cols_per_thread != -1:
             raise _lib.RatoError("a Model that regenerates its noise linearizes with the row-parallel kernel only "
                                  "(cols_per_thread=-1); the column kernel reads a materialised dW")
-        def reuse(key, shape):
-            """a buffer of an earlier call is reused only if it has exactly the shape this launch writes"""
-            t = o.get(key)
-            if t is not None and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t
-            return self._empty(*shape)
-
         g_shape = (num_tiles(M, tile), max(num_pairs(S), 1), 2, tile)
         G = o.get("G")               # packed Jacobian: tiles of >= 1 MiB start on 2 MiB boundaries (_lib.packed_buffer)
         if not (_lib.is_packed_layout(G, g_shape) and G.dtype == torch.float32):
             G = _lib.packed_buffer(g_shape, self.device)
-        g_up = reuse("g_up", (S, M))
-        Z = reuse("Z", (M,)) if want_Z else None
-        final_du = reuse("final_du", (4, n_u * S))
-        final_rhs = reuse("final_rhs", (4,))
-        p = self._params(M)
-        p.rows_out = int(rows_out)      # 1: g_up receives g itself (base of the cut oracle's delta form, cvar_cuts.py)
+        g_up = self._reuse(o, "g_up", (S, M))
+        Z = self._reuse(o, "Z", (M,)) if want_Z else None
+        final_du = self._reuse(o, "final_du", (4, n_u * S))
+        final_rhs = self._reuse(o, "final_rhs", (4,))
+        p = self._params(M, rows_out)
         if stats_request is not None:   # (workspace, out, alpha): the launch also computes the statistics of its Z
             stats.request_in_launch(p, *stats_request)
         tiled = self._tiled_noise(dW, M) if (dW is not None and cols_per_thread == -1 and self.TILED_NOISE) else None
@@ -405,12 +321,7 @@ class Model:
         cpt, tile = C.c_int32(int(kw.get("cols_per_thread", 0))), C.c_int32(0)
         self._lib.rato_car_linearize_plan(M, self.S, C.byref(cpt), C.byref(tile))
         if fused and cpt.value == -1 and self._lib.rato_car_stats_in_launch(M, self.S):
-            if workspace is None:
-                workspace = stats.new_workspace(M, self.device)
-            if stats_out is None:
-                stats_out = torch.empty(stats.N_STATS, dtype=torch.float64, device=self.device)
-            r = self.linearize_device(us_mat, out=out, stats_request=(workspace, stats_out, alpha), **kw)
-            return r, stats_out
+            return self._fused_step(us_mat, alpha, M, workspace, stats_out, out=out, **kw)
         r = self.linearize_device(us_mat, out=out, **kw)
         return r, stats.risk_stats_device(r["Z"], alpha, workspace=workspace, out=stats_out)
 
@@ -454,8 +365,6 @@ class Model:
                 r["g_up"].t().double().cpu().numpy())
 
     # ---- L3: sparse QP assembly (driving.py:243-258, 301-421) --------------
-    SLACK_PENALTY = 1000.0      # driving.py:387-388
-
     def _assemble(self, us_mat, relax):
         r = self.linearize_device(us_mat)
         M = r["M"]
@@ -477,7 +386,7 @@ class Model:
         treats like the l = u = 0 used here."""
         if scp_iter < 1:                            # pattern differs (zeroed rows are dropped): host path
             return self._assemble(us_mat, ('zero', n_x))
-        fast = getattr(self, "_fast", None)
+        fast = self._fast
         if fast is None:
             A0, l0, u0 = self._assemble(us_mat, None)
             fast = assemble.FastAssembler(A0, l0, u0, n_c=4, n_u=n_u, n_g=2, R=1, S=self.S, M=self.M,
@@ -520,31 +429,9 @@ class Model:
         return True
 
     def solve(self, verbose=False):
-        S = self.S
-        self.res = self.osqp_prob.solve()
-        if self.res.info.status != 'solved':
-            print("[solve]: Problem infeasible.")
-        us_sol = self.convert_us_vec_to_us_mat(self.res.x[:(n_u * S)])
-        ys, t_risk_sol = self.res.x[(n_u * S):-2], self.res.x[-1]
-        if verbose:
-            print("y_min =", np.min(ys))
-            print("slack_var =", self.res.x[-2])
-        return us_sol, t_risk_sol
+        return self._solve(verbose)
 
     # ---- L4 at large M: reduced (u, slack) problem with device CVaR cuts ----------------------
-    def shard(self, group=None):
-        """This Model is one shard of a sample-sharded batch (see drone_risk.Model.shard): the cutting-plane oracle
-        of ``solve_reduced`` then runs across the ranks.  (The final rows are sample independent: nothing else to merge.)"""
-        import torch.distributed as tdist
-        from . import dist as rdist
-        rdist.check_equal_shards(self.M, group)          # raises on every rank if the shards differ
-        rdist.check_equal_shards(self.S, group, what="horizons S")   # (... the lengths of every exchanged buffer)
-        self._group, self._world = group, tdist.get_world_size(group)
-        # buffers a single-process solve_reduced may have left behind are single-process shaped (pinned HOST sums that
-        # the partial-sum kernel writes into directly): a sharded solve must not inherit them
-        self._cut_solver = self._gen_buffers = self._lin_buffers = self._define_host = None
-        return self
-
     def ego_final_rows(self, us_mat):
         """The final-state rows of the ego in double precision -> (final_du (4, 2S), final_rhs (4,)):  the ego carries no
         noise, so x_S[0:4] and its control Jacobian are sample independent (the mean of driving.py:311 is a no-op) and
@@ -583,17 +470,6 @@ class Model:
                                                      final_rhs.ctypes.data), "rato_car_ego_final_rows")
         return final_du, final_rhs
 
-    def _reduced_cut_solver(self, M):
-        cs = getattr(self, "_cut_solver", None)
-        if cs is None:
-            cs = cvar_cuts.CvarCutSolver(self._lib, self.device, n_u=n_u, S=self.S, M=M, ld=M, R=1, alpha=self.alpha,
-                                         dt=self.dt, Rcost=P.R, slack_penalty=self.SLACK_PENALTY,
-                                         u_min=self.u_min, u_max=self.u_max,
-                                         group=getattr(self, "_group", None), world=getattr(self, "_world", 1),
-                                         mode=self.method, rhs0=0.0)
-            self._cut_solver = cs
-        return cs
-
     def solve_reduced(self, us_mat_p, scp_iter=1, tol=1e-9, verbose=False, delta=True, rollout=None, final_rows='numpy'):
         """One SCP iteration without the O(M) QP (see cvar_cuts.py / drone_risk.Model.solve_reduced).
         scp_iter < 1 zeroes every separation row (driving.py:411-415), i.e. no CVaR constraint.
@@ -626,16 +502,16 @@ class Model:
                 raise _lib.RatoNonFiniteError("driving final rows: non-finite values (RATO_ENONFINITE)")
             # unconditionally: the upload of u_k to the device happens only while cs.rollout is set, so a table-form call
             # at the same u before this one must not leave the rollout kernels reading a stale uk_dev
-            cs.begin(u_lin, scp_iter >= 1 and getattr(self, "_world", 1) == 1)
+            cs.begin(u_lin, scp_iter >= 1 and self._world == 1)
             info = cs.solve(None, None, 0, None, final_du, final_rhs, u_lin=u_lin, with_cvar=(scp_iter >= 1), tol=tol,
                             verbose=verbose)
             info["final_du"], info["final_rhs"] = final_du, final_rhs    # (the equality rows: certificate.certify)
             return info["us"], info["t_risk"], info
         cs.rollout = None
-        r = self.linearize_device(us_mat_p, out=getattr(self, "_lin_buffers", None), rows_out=1 if delta else 0)
+        r = self.linearize_device(us_mat_p, out=self._lin_buffers, rows_out=1 if delta else 0)
         self._lin_buffers = r
         cs.set_linearization_point(u_lin)
-        if scp_iter >= 1 and getattr(self, "_world", 1) == 1:
+        if scp_iter >= 1 and self._world == 1:
             cs.enqueue_relinearize(r["G"], None, r["tile"], r["g_up"])      # one device round trip with the read-backs below
         info = cs.solve(r["G"], None, r["tile"], r["g_up"], r["final_du"].double().cpu().numpy(),
                         r["final_rhs"].double().cpu().numpy(), u_lin=u_lin,
@@ -646,7 +522,7 @@ class Model:
         """the cut solver of the native SCP loop with its table-free oracle attached, or None where that loop does not
         apply (no materialised dW, sharded, S < 2)"""
         dW, x0, ws, wr = self._dW, self._x0, self._ws, self._wr
-        if dW is None or getattr(self, "_world", 1) != 1 or self.S < 2:
+        if dW is None or self._world != 1 or self.S < 2:
             return None
         M = int(ws.numel())
         cs = self._reduced_cut_solver(M)
@@ -669,25 +545,13 @@ class Model:
             float(final_cut_above), int(bool(self.check_finite)), *tail)
         return cvar_cuts.scp_run(self._lib, cs, us0, iters, run, ("rato_scp_run_car", "final rows"), self.check_finite)
 
-    def certify_reduced(self, info):
-        """Matrix-free KKT certificate of the last ``solve_reduced`` (table-free oracle, an iteration with the CVaR rows)
-        against the reference's full QP (driving.py:330-373): certificate.py."""
-        from . import certificate
-        return certificate.certify(self._cut_solver, info, info["final_du"], info["final_rhs"], kappa=1.0)
-
     # ---- Monte-Carlo validation (driving.py:623-671) -----------------------
     def monte_carlo_cost(self, us_mat):
         # driving.py:623-629: the script has ONE dt (driving_params.py:14, dt = T / S), shared with the rollout
         us = np.asarray(us_mat)
         return self.dt * float(np.sum(np.diag(P.R)[None, :] * us * us))
 
-    def monte_carlo_separation_constraints_verification(self, us_mat):
-        Z, _, _ = self.eval_device(us_mat)
-        Zh = Z.double().cpu().numpy()
-        return Zh <= 1e-6, Zh
-
-    monte_carlo_statistics = stats.monte_carlo_statistics
-    monte_carlo_avar = staticmethod(stats.monte_carlo_avar)
+    monte_carlo_separation_constraints_verification = SaaModel._monte_carlo_verification      # driving.py:630-638
 
 
 def _check_batch(models):
@@ -704,13 +568,5 @@ def scp_run_native_batch(models, us0, iters, first_cvar=1, tol=1e-9, max_cuts=40
     kept cuts of all problems in one launch, then rounds of one batched oracle round trip for every problem still cutting.
     Each Model brings its own cut solver and leaves it as ``scp_run_native`` would; ``us0`` [K][S][2].  ValueError (before any
     device work) for what the batch does not cover.  -> the dict of ``cvar_cuts.scp_batch_run``."""
-    models = list(models)
-    _check_batch(models)
-    us0, solvers = cvar_cuts.scp_batch_inputs(models, us0, n_u)
-    lib = models[0]._lib
-    goal = models[0]._goal64()
-    run = lambda h, *tail: lib.rato_scp_batch_run_car(
-        h, us0.ctypes.data, goal.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
-        int(bool(check_finite)), *tail)
-    return cvar_cuts.scp_batch_run(lib, models[0].device, solvers, us0, iters, run, "rato_scp_batch_run_car",
-                                   n_threads=n_threads, check_finite=check_finite)
+    return cvar_cuts.scp_run_native_batch(models, _check_batch, us0, n_u, "rato_scp_batch_run_car", lambda m: (m._goal64(),),
+                                          (iters, first_cvar, tol, max_cuts, final_cut_above), n_threads, check_finite)

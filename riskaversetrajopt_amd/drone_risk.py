@@ -15,6 +15,7 @@ import torch
 
 from . import _lib, assemble, cvar_cuts, qp, stats
 from . import drone_params as P
+from ._saa_model import SaaModel
 from .scp import L2_error_us  # noqa: F401  (the reference's module-level name, drone_risk.py:471-476)
 
 n_x, n_u, n_obs = P.n_x, P.n_u, P.n_obs
@@ -66,13 +67,19 @@ def to_soa_inputs(DWs, masses, obs_Qs, device):
     return dW, mass, Qsym, M
 
 
-class Model:
+class Model(SaaModel):
+    N_U, N_NOISE, PARAMS, RCOST = n_u, 3, _lib.DroneParams, P.R
+    MULTIPLIER = 0.01           # drone_risk.py:307,353: constraint rows are scaled by 0.01
+    SLACK_PENALTY = 10000.0     # :389-390
+    KAPPA, CUT_ROWS, CUT_RHS0 = MULTIPLIER, n_obs, -1e-3 / MULTIPLIER
+
     def __init__(self, S, DWs, masses, obs_Qs, method='saa', alpha=0.1, device='cuda:0',
                  verbose=False, check_finite=False):
         # drone_risk.py:71-93
         # check_finite: scan g_up / Z / partial sums of every linearization for NaN/Inf and raise
         # RatoNonFiniteError (the SCP drivers of scp.py switch it on; off in throughput runs: it costs a sync)
         self.check_finite = check_finite
+        self._init_state()
         if verbose:
             print("Initializing Model with")
             print("> method =", method)
@@ -114,12 +121,6 @@ class Model:
         return self
 
     # ---- layout helpers (drone_risk.py:95-120) -----------------------------
-    def convert_us_vec_to_us_mat(self, us_vec):
-        return np.reshape(np.asarray(us_vec), (n_u, self.S), 'F').T.copy()
-
-    def convert_us_mat_to_us_jaxvec(self, us_mat):
-        return np.reshape(np.asarray(us_mat), (self.S * n_u), 'C')
-
     def initial_guess_us_mat(self, all_axes=False):
         """drone_risk.py:119 offsets the first two controls by 1e-2; ``all_axes=True`` is the main-plot script's guess,
         which offsets all three (drone_main_plot.py:137-148)."""
@@ -131,17 +132,14 @@ class Model:
     def _inputs(self, inputs):
         return inputs if inputs is not None else (self._dW, self._mass, self._Qsym, self.M)
 
-    def _params(self, M, ld, rows_out=0):
-        """a fresh rato_drone_params for this Model (callers set the stats_* fields on it): a copy of a template built once
-        per (M, ld, rows_out, S, dt, beta, drag) -- ~40 ctypes field stores cost 15-20 us, more than a small kernel"""
-        key = (M, ld, int(rows_out), self.S, self.dt, self.beta, self.drag_coefficient)
-        cache = self.__dict__.setdefault("_params_cache", {})
-        t = cache.get(key)
-        if t is None:
-            if len(cache) > 64:
-                cache.clear()
-            t = cache[key] = self._params_build(M, ld, rows_out)
-        return _lib.DroneParams.from_buffer_copy(t)
+    def _batch_shape(self, inputs=None):
+        """-> (M, row stride ld) of ``inputs`` (default: the model's batch)"""
+        _, mass, _, M = self._inputs(inputs)
+        return M, mass.numel()
+
+    def _params_key(self, M, ld, rows_out=0):
+        """what the template of ``_params(M, ld[, rows_out])`` depends on"""
+        return (M, ld, int(rows_out), self.S, self.dt, self.beta, self.drag_coefficient)
 
     def _params_build(self, M, ld, rows_out=0):
         p = _lib.DroneParams()
@@ -166,18 +164,6 @@ class Model:
             p.obs_xy64[j][0] = float(P.obs_positions[j, 0])
             p.obs_xy64[j][1] = float(P.obs_positions[j, 1])
         return p
-
-    def _us_device(self, us_mat):
-        if isinstance(us_mat, torch.Tensor) and us_mat.is_cuda:
-            us = us_mat.float().contiguous()
-        else:
-            us = torch.as_tensor(np.ascontiguousarray(np.asarray(us_mat), dtype=np.float32), device=self.device)
-        if tuple(us.shape) != (self.S, n_u):
-            raise ValueError(f"us_mat must be ({self.S},{n_u}), got {tuple(us.shape)}")
-        return us
-
-    def _empty(self, *shape):
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
 
     def _rows(self, *shape, M):
         """[..][ld] output rows: the kernels never write the ld - M padding lanes, so they are zeroed once here
@@ -208,25 +194,17 @@ class Model:
         ld = mass.numel()
         us = self._us_device(us_mat)
         o = out if out is not None else {}
-
-        def reuse(key, shape):
-            t = o.get(key)
-            if t is not None and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t
-            return self._empty(*shape)
-
-        Z = reuse("_Z", (ld,))
+        Z = self._reuse(o, "_Z", (ld,))
         xs = self._empty(self.S + 1, n_x, ld) if want_xs else None
-        g = reuse("_g", (n_obs, self.S, ld)) if want_g else None
+        g = self._reuse(o, "_g", (n_obs, self.S, ld)) if want_g else None
         o["_Z"] = Z
         if g is not None:                                # (a call without g keeps the reusable g buffer of an earlier one)
             o["_g"] = g
         p = self._params(M, ld)
         if tol is not None:
             p.tol, p.tol64 = float(tol), float(tol)
-        if stats_request is not None:        # (workspace, record, alpha[, in_launch])
-            stats.request_in_launch(p, *stats_request[:3], flags=(stats.STATS_IN_LAUNCH if (len(stats_request) > 3 and
-                                                                                             stats_request[3]) else 0))
+        if stats_request is not None:
+            self._request_stats(p, stats_request)
         metric_id = self._metric(metric)
         if metric_id or want_arg:
             if dW is None:
@@ -251,20 +229,6 @@ class Model:
                                              _lib.current_stream()), "rato_drone_eval")
         return Z[:M], (xs[..., :M] if want_xs else None), (g[..., :M] if want_g else None)
 
-    def mc_step_device(self, us_mat, alpha=None, out=None, workspace=None, stats_out=None, inputs=None, in_launch=False):
-        """One Monte-Carlo validation step on the device (drone_risk.py:711-714: rollout -> max over (obstacle, t) ->
-        fraction satisfied / VaR / AVaR) as ONE library call -- for small batches one launch.
-        -> (Z [M], record double[N_STATS]), device tensors; ``out`` / ``workspace`` / ``stats_out`` are reused when given
-        (a captured step must pass them)."""
-        alpha = self.alpha if alpha is None else alpha
-        M = self._inputs(inputs)[3]
-        if workspace is None:
-            workspace = stats.new_workspace(M, self.device)
-        if stats_out is None:
-            stats_out = torch.empty(stats.N_STATS, dtype=torch.float64, device=self.device)
-        Z, _, _ = self.eval_device(us_mat, inputs=inputs, out=out, stats_request=(workspace, stats_out, alpha, in_launch))
-        return Z, stats_out
-
     def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None, metric='quadratic',
                           want_arg=False, tol=None):
         """K control sequences on the model's batch in ONE call (rato_drone_eval_batch): what the reference's Monte-Carlo
@@ -279,27 +243,9 @@ class Model:
                 raise ValueError("metric='euclidean' / want_arg=True read a materialised dW (this Model regenerates its noise)")
             raise _lib.RatoError("eval_batch_device reads a materialised dW (this Model regenerates its noise)")
         alpha = self.alpha if alpha is None else alpha
-        if isinstance(us_batch, torch.Tensor) and us_batch.is_cuda:
-            us = us_batch.float().contiguous()
-        else:
-            us = torch.as_tensor(np.ascontiguousarray(np.asarray(us_batch), dtype=np.float32), device=self.device)
-        if us.dim() != 3 or tuple(us.shape[1:]) != (self.S, n_u):
-            raise ValueError(f"us_batch must be (K,{self.S},{n_u}), got {tuple(us.shape)}")
+        us = self._us_batch_device(us_batch)
         K, ld = us.shape[0], mass.numel()
-        o = out if out is not None else {}
-        Z = o.get("_Zb")
-        if Z is None or tuple(Z.shape) != (K, ld):
-            Z = self._empty(K, ld)
-        rec = None
-        if want_stats:
-            rec = o.get("_recb")
-            if rec is None or tuple(rec.shape) != (K, stats.N_STATS):
-                rec = torch.empty((K, stats.N_STATS), dtype=torch.float64, device=self.device)
-            if workspace is None:
-                workspace = o.get("_wsb")
-            if workspace is None:
-                workspace = stats.new_workspace(M, self.device)
-        o["_Zb"], o["_recb"], o["_wsb"] = Z, rec, workspace
+        Z, rec, workspace = self._batch_buffers(out if out is not None else {}, K, M, ld, want_stats, workspace)
         p = self._params(M, ld)
         if tol is not None:
             p.tol, p.tol64 = float(tol), float(tol)
@@ -373,37 +319,12 @@ class Model:
                                  f"samples_per_lane={samples_per_lane}, ld={ld}")
         return nblk, cpt.value, spl.value, tile.value
 
-    TILED_NOISE = True        # (class-level switch for A/B runs and the equality test)
-
-    def _tiled_noise(self, dW, M, ld):
-        """The [tile][3S][64] copy of the MODEL'S OWN noise that the row-parallel kernel reads; made once, kept with
-        the source tensor itself (compared by identity: an address can be recycled by the allocator, a live tensor
-        cannot).  A caller's ``inputs`` are never cached -- ``None`` sends them through the kernel that reads dW as it
-        lies.  Whoever rewrites ``self._dW`` in place through raw pointers (the library's samplers do not bump a
-        tensor's version counter) must call ``set_noise`` / ``invalidate_noise``."""
-        if dW is not self._dW:
-            return None
-        c = getattr(self, "_dW_tiled_cache", None)
-        if c is None or c[0] is not dW or c[1] != dW._version or c[3] != (M, ld, self.S):
-            n = int(self._lib.rato_drone_tiled_noise_floats(M, self.S))
-            t = torch.empty(n, dtype=torch.float32, device=dW.device)
-            _lib.check(self._lib.rato_drone_tile_noise(_lib.ptr(dW), M, ld, self.S, _lib.ptr(t), _lib.current_stream()),
-                       "rato_drone_tile_noise")
-            c = (dW, dW._version, t, (M, ld, self.S))
-            self._dW_tiled_cache = c
-        return c[2]
-
-    def invalidate_noise(self):
-        """Forget every copy derived from ``self._dW`` (after an in-place refill of the noise array)."""
-        self._dW_tiled_cache = None
-
-    def set_noise(self, dW):
-        """Replace the batch's Brownian increments (kernel layout [S][3][ld], fp32, on the model's device)."""
-        dW = _lib.require_f32_device(dW, "dW")
-        if tuple(dW.shape) != (self.S, 3, self._mass.numel()):
-            raise ValueError(f"dW must be ({self.S}, 3, {self._mass.numel()}), got {tuple(dW.shape)}")
-        self._dW = dW
-        self.invalidate_noise()
+    def _tile_noise(self, dW, M, ld):
+        """dW [S][3][ld] -> its [tile][3S][64] copy (``_tiled_noise`` keeps it)"""
+        t = torch.empty(int(self._lib.rato_drone_tiled_noise_floats(M, self.S)), dtype=torch.float32, device=dW.device)
+        _lib.check(self._lib.rato_drone_tile_noise(_lib.ptr(dW), M, ld, self.S, _lib.ptr(t), _lib.current_stream()),
+                   "rato_drone_tile_noise")
+        return t
 
     def linearize_device(self, us_mat, inputs=None, cols_per_thread=0, samples_per_lane=0, out=None,
                          want_Z=True, events=None, factored=None, want_A22=False, reduce=True, rows_out=0, stats_request=None):
@@ -443,30 +364,21 @@ class Model:
         o = out if out is not None else {}
         g_shape = (num_tiles(M, tile), max(num_pairs(S), 1), 2, tile) if factored else \
             (num_tiles(M, tile), max(num_pairs(S), 1), 2, n_obs, tile)
-
-        def reuse(key, shape, alloc):
-            """a buffer of an earlier call is reused only if it has exactly the shape this launch writes (``out`` may
-            come from another batch size or S: the kernels would write past a smaller buffer)"""
-            t = o.get(key)
-            if t is not None and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t
-            return alloc()
-
         # the packed Jacobian: tiles of >= 1 MiB start on 2 MiB boundaries (a strided view; _lib.packed_buffer)
         G = o.get("G")
         if not (_lib.is_packed_layout(G, g_shape) and G.dtype == torch.float32):
             G = _lib.packed_buffer(g_shape, self.device)
         Wf = None
         if factored:
-            Wf = reuse("_W", (n_obs, S, 2, ld), lambda: self._empty(n_obs, S, 2, ld))
+            Wf = self._reuse(o, "_W", (n_obs, S, 2, ld))
         A22 = None
         if want_A22:
             if not factored:
                 raise _lib.RatoError("A22 goes with the factored output (row-parallel kernel)")
-            A22 = reuse("_A22", (S, 2, ld), lambda: self._empty(S, 2, ld))
-        g_up = reuse("_g_up", (n_obs, S, ld), lambda: self._rows(n_obs, S, ld, M=M))
-        Z = reuse("_Z", (ld,), lambda: self._rows(ld, M=M)) if want_Z else None
-        part = reuse("part", (nblk, 6 * S + 6), lambda: self._empty(nblk, 6 * S + 6))
+            A22 = self._reuse(o, "_A22", (S, 2, ld))
+        g_up = self._reuse(o, "_g_up", (n_obs, S, ld), lambda: self._rows(n_obs, S, ld, M=M))
+        Z = self._reuse(o, "_Z", (ld,), lambda: self._rows(ld, M=M)) if want_Z else None
+        part = self._reuse(o, "part", (nblk, 6 * S + 6))
         if o.get("sums") is not None and (o["sums"].numel() != 6 * S + 6 or o["sums"].dtype != torch.float64):
             o = dict(o, sums=None)
         p = self._params(M, ld, rows_out)
@@ -524,18 +436,12 @@ class Model:
         us = self._us_device(us_mat)
         o = out if out is not None else {}
 
-        def reuse(key, shape, alloc):
-            t = o.get(key)
-            if t is not None and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_contiguous():
-                return t
-            return alloc()
-
-        A22 = reuse("_A22", (S, 3, ld), lambda: self._empty(S, 3, ld))
-        Wf = reuse("_W", (n_obs, S, 2, ld), lambda: self._empty(n_obs, S, 2, ld)) if tables else None
-        g_up = reuse("_g_up", (n_obs, S, ld), lambda: self._rows(n_obs, S, ld, M=M)) if tables else None
-        Z = reuse("_Z", (ld,), lambda: self._rows(ld, M=M))
+        A22 = self._reuse(o, "_A22", (S, 3, ld))
+        Wf = self._reuse(o, "_W", (n_obs, S, 2, ld)) if tables else None
+        g_up = self._reuse(o, "_g_up", (n_obs, S, ld), lambda: self._rows(n_obs, S, ld, M=M)) if tables else None
+        Z = self._reuse(o, "_Z", (ld,), lambda: self._rows(ld, M=M))
         nblk = (M + 255) // 256
-        part = reuse("part", (nblk, 6 * S + 6), lambda: self._empty(nblk, 6 * S + 6))
+        part = self._reuse(o, "part", (nblk, 6 * S + 6))
         if o.get("sums") is not None and (o["sums"].numel() != 6 * S + 6 or o["sums"].dtype != torch.float64):
             o = dict(o, sums=None)
         p = self._params(M, ld, rows_out)
@@ -633,13 +539,7 @@ class Model:
         _, mass, _, M = self._inputs(kw.get("inputs"))
         if fused and self._lib.rato_drone_stats_in_launch(M, self.S) and \
                 self.linearize_plan(M, mass.numel(), kw.get("cols_per_thread", 0), kw.get("samples_per_lane", 0))[1] == -1:
-            if workspace is None:
-                workspace = stats.new_workspace(M, self.device)
-            if stats_out is None:
-                stats_out = torch.empty(stats.N_STATS, dtype=torch.float64, device=self.device)
-            r = self.linearize_device(us_mat, out=out, events=events, reduce=True,
-                                      stats_request=(workspace, stats_out, alpha), **kw)
-            return r, stats_out
+            return self._fused_step(us_mat, alpha, M, workspace, stats_out, out=out, events=events, reduce=True, **kw)
         r = self.linearize_device(us_mat, out=out, events=events, reduce=False, **kw)
         _, st = stats.sums_and_risk_stats_device(r["part"], r["Z"], alpha, workspace=workspace, sums_out=r["sums"],
                                                  out=stats_out)
@@ -670,9 +570,6 @@ class Model:
         return sg
 
     # ---- L3: sparse QP assembly (drone_risk.py:221-237, 282-423) -----------
-    MULTIPLIER = 0.01           # drone_risk.py:307,353: constraint rows are scaled by 0.01
-    SLACK_PENALTY = 10000.0     # :389-390
-
     def _host_linearization(self, us_mat):
         r = self.linearize_device(us_mat)
         M = r["M"]
@@ -706,7 +603,7 @@ class Model:
         After the first call the sparsity pattern is cached and an iteration only moves the value block
         that the device wrote in CSC order (rato_emit_csc_values)."""
         relax = ('scale', n_x, 1e-7, -0.1, 0.1) if scp_iter < 2 else None
-        fast = getattr(self, "_fast", None)
+        fast = self._fast
         if fast is None:
             A0, l0, u0 = self._assemble(us_mat, None)
             saa = self.method == 'saa'
@@ -755,32 +652,9 @@ class Model:
         return True
 
     def solve(self, verbose=True):
-        S = self.S
-        self.res = self.osqp_prob.solve()
-        if self.res.info.status != 'solved':
-            print("[solve]: Problem infeasible.")
-        us_sol = self.convert_us_vec_to_us_mat(self.res.x[:(n_u * S)])
-        ys, t_risk_sol = self.res.x[(n_u * S):-2], self.res.x[-1]
-        if verbose:
-            print("y_min =", np.min(ys))
-            print("slack_var =", self.res.x[-2])
-        return us_sol, t_risk_sol
+        return self._solve(verbose)
 
     # ---- L4 at large M: reduced (u, slack) problem with device CVaR cuts ----------------------
-    def shard(self, group=None):
-        """Declare this Model one shard of a sample-sharded batch (one process per GPU, torch.distributed already
-        initialised, equal shard sizes): ``solve_reduced`` then merges the sample means and runs the cutting-plane
-        oracle across the ranks (cvar_cuts.py); every rank returns the same iterate."""
-        import torch.distributed as tdist
-        from . import dist as rdist
-        rdist.check_equal_shards(self.M, group)          # raises on every rank if the shards differ
-        rdist.check_equal_shards(self.S, group, what="horizons S")   # (... the lengths of every exchanged buffer)
-        self._group, self._world = group, tdist.get_world_size(group)
-        # buffers a single-process solve_reduced may have left behind are single-process shaped (pinned HOST sums that
-        # the partial-sum kernel writes into directly): a sharded solve must not inherit them
-        self._cut_solver = self._gen_buffers = self._lin_buffers = self._define_host = None
-        return self
-
     def solve_reduced(self, us_mat_p, scp_iter=2, tol=1e-9, verbose=False, implicit=True, generators_only=None,
                       delta=True, factored=None, rollout=None):
         """One SCP iteration without the O(M) QP: linearize at ``us_mat_p`` on the device, eliminate the
@@ -809,18 +683,19 @@ class Model:
             rollout = bool(implicit and generators_only and delta and dW is not None)
         if rollout and not (implicit and delta and dW is not None):
             raise ValueError("the rollout form of the oracle needs implicit=True, delta=True and a materialised dW")
-        world = getattr(self, "_world", 1)
+        world = self._world
         if rollout and world == 1 and not verbose:
             # the benchmarked configuration: define (rato_cut_define_drone) and solve (rato_cut_solve) are one native call each
             cs = self._native_loop_solver(min_S=1)       # (the SCP loops need S >= 2; one define + solve runs at S = 1 too)
-            assert cs is not None                        # rollout: dW is materialised; world == 1; S >= 1
+            if cs is None:                               # rollout: dW is materialised; world == 1; S >= 1
+                raise _lib.RatoError("solve_reduced: no native cut solver for a table-free oracle on one GPU")
             cs.check_finite = False
             if cs.native_loop_applies():
                 return self._solve_reduced_native(cs, us_mat_p, scp_iter, tol)
         if generators_only:
             # (the table-free oracle reads neither W nor g: only Z and the sample sums are produced then)
-            bufs = getattr(self, "_gen_buffers", None)
-            if bufs is None and getattr(self, "_world", 1) == 1:
+            bufs = self._gen_buffers
+            if bufs is None and world == 1:
                 # single GPU: the sample sums are consumed on the host only, so the partial-sum kernel writes them straight
                 # into pinned host memory (visible after the synchronisation below) -- no read-back copy to issue
                 bufs = {"sums": torch.zeros(6 * self.S + 6, dtype=torch.float64).pin_memory()}
@@ -828,7 +703,7 @@ class Model:
                                                  defer_check=True)
             self._gen_buffers = r
         else:
-            r = self.linearize_device(us_mat_p, out=getattr(self, "_lin_buffers", None), want_A22=implicit,
+            r = self.linearize_device(us_mat_p, out=self._lin_buffers, want_A22=implicit,
                                       rows_out=rows_out, factored=factored)
             self._lin_buffers = r
         M, S = r["M"], self.S
@@ -845,9 +720,9 @@ class Model:
         sums = r["sums"]
         if world > 1:                                     # sample means over ALL shards, summed in rank order
             from . import dist as rdist
-            sums = rdist.sum_in_rank_order(sums, getattr(self, "_group", None), agreed=True)   # 6S + 6 numbers: S agreed in shard()
+            sums = rdist.sum_in_rank_order(sums, self._group, agreed=True)   # 6S + 6 numbers: S agreed in shard()
         # ONE synchronisation for the sample sums, the non-finite count and (enqueued above) the kept cuts
-        host = getattr(self, "_define_host", None)
+        host = self._define_host
         if host is None or host[0].numel() != sums.numel():
             host = (torch.zeros(sums.numel(), dtype=torch.float64).pin_memory(), torch.zeros(1, dtype=torch.int32).pin_memory())
             self._define_host = host
@@ -868,17 +743,6 @@ class Model:
                         with_cvar=(scp_iter >= 2), tol=tol, verbose=verbose)
         info["final_du"], info["final_rhs"] = final_du, final_rhs        # (the equality rows: certificate.certify)
         return info["us"], info["t_risk"], info
-
-    def _reduced_cut_solver(self, M, ld):
-        cs = getattr(self, "_cut_solver", None)
-        if cs is None:
-            cs = cvar_cuts.CvarCutSolver(self._lib, self.device, n_u=n_u, S=self.S, M=M, ld=ld,
-                                         R=n_obs, alpha=self.alpha, dt=self.dt, Rcost=P.R,
-                                         slack_penalty=self.SLACK_PENALTY, u_min=self.u_min, u_max=self.u_max,
-                                         group=getattr(self, "_group", None), world=getattr(self, "_world", 1),
-                                         mode=self.method, rhs0=-1e-3 / self.MULTIPLIER)
-            self._cut_solver = cs
-        return cs
 
     def _solve_reduced_native(self, cs, us_mat_p, scp_iter, tol):
         """``solve_reduced`` for the benchmarked configuration (table-free oracle, one GPU) as TWO library calls:
@@ -914,7 +778,7 @@ class Model:
     def _native_define_buffers(self, cs):
         """the device / pinned buffers rato_cut_define_drone and rato_scp_run_drone work in (made once per shape)"""
         S, M, ld = self.S, cs.M, self._mass.numel()
-        b = getattr(self, "_native_define", None)
+        b = self._native_define
         if b is None or b["key"] != (S, M, ld):
             e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=self.device)
             b = {"key": (S, M, ld), "us_host": torch.zeros((S, n_u), dtype=torch.float32).pin_memory(), "us_dev": e(S, n_u),
@@ -946,32 +810,22 @@ class Model:
         """the cut solver with its table-free oracle attached -- the one place that does so -- or None where the native loops
         do not apply (no materialised dW, sharded, S < ``min_S``: 2 for the SCP loops, 1 for a single define + solve)"""
         dW, mass, Qsym, M = self._inputs(None)
-        if dW is None or getattr(self, "_world", 1) != 1 or self.S < min_S:
+        if dW is None or self._world != 1 or self.S < min_S:
             return None
         cs = self._reduced_cut_solver(int(M), mass.numel())
         cs.implicit = None
-        rp = getattr(self, "_rollout_params", None)      # (built once: ~20 us of ctypes field stores per call otherwise)
+        rp = self._rollout_params      # (built once: ~20 us of ctypes field stores per call otherwise)
         if rp is None or rp[0] != (cs.M, mass.numel()):
             rp = self._rollout_params = ((cs.M, mass.numel()), self._params(cs.M, mass.numel()))
         cs.rollout = ("drone", rp[1], dW, mass, Qsym)
         return cs
-
-    def certify_reduced(self, info):
-        """Matrix-free KKT certificate of the last ``solve_reduced`` (its ``info``; an iteration with the CVaR rows,
-        before any other solve) against the reference's full QP (drone_risk.py:327-368): certificate.py."""
-        from . import certificate
-        return certificate.certify(self._cut_solver, info, info["final_du"], info["final_rhs"], kappa=self.MULTIPLIER)
 
     # ---- Monte-Carlo validation (drone_risk.py:649-695) --------------------
     def monte_carlo_cost(self, us_mat):
         us = np.asarray(us_mat)
         return P.dt * float(np.sum(np.diag(P.R)[None, :] * us * us))
 
-    def monte_carlo_no_collisions_constraint_verification(self, us_mat):
-        """vmap of drone_risk.py:656-662 -> (B_satisfied (M,) bool, max_constraint (M,))."""
-        Z, _, _ = self.eval_device(us_mat)
-        Zh = Z.double().cpu().numpy()
-        return Zh <= 1e-6, Zh
+    monte_carlo_no_collisions_constraint_verification = SaaModel._monte_carlo_verification     # drone_risk.py:656-662
 
     def monte_carlo_no_collisions_constraint_verification_euclidean(self, us_mat):
         """vmap of the main-plot script's closure (drone_main_plot.py:633-639) -> (xs (M,S+1,n_x), B_satisfied (M,) bool,
@@ -979,10 +833,6 @@ class Model:
         Z, xs, _ = self.eval_device(us_mat, want_xs=True, metric='euclidean', tol=0.0)
         Zh = Z.double().cpu().numpy()
         return xs.permute(2, 0, 1).double().cpu().numpy(), Zh <= OSQP_TOL + 1e-6, Zh
-
-    monte_carlo_statistics = stats.monte_carlo_statistics
-    monte_carlo_avar = staticmethod(stats.monte_carlo_avar)
-    monte_carlo_var = staticmethod(stats.monte_carlo_var)
 
 
 class StepGraph:
@@ -1012,12 +862,5 @@ def scp_run_native_batch(models, us0, iters, first_cvar=2, tol=1e-9, max_cuts=40
     to ``n_threads`` threads.  Each Model brings its own cut solver (its samples, alpha, rings and kept cuts) and leaves it as
     ``scp_run_native`` would; ``us0`` [K][S][3].  ValueError (before any device work) for what the batch does not cover.
     -> the dict of ``cvar_cuts.scp_batch_run``."""
-    models = list(models)
-    _check_batch(models)
-    us0, solvers = cvar_cuts.scp_batch_inputs(models, us0, n_u)
-    lib = models[0]._lib
-    run = lambda h, *tail: lib.rato_scp_batch_run_drone(
-        h, us0.ctypes.data, int(iters), int(first_cvar), float(tol), int(max_cuts), float(final_cut_above),
-        int(bool(check_finite)), *tail)
-    return cvar_cuts.scp_batch_run(lib, models[0].device, solvers, us0, iters, run, "rato_scp_batch_run_drone",
-                                   n_threads=n_threads, check_finite=check_finite)
+    return cvar_cuts.scp_run_native_batch(models, _check_batch, us0, n_u, "rato_scp_batch_run_drone", lambda m: (),
+                                          (iters, first_cvar, tol, max_cuts, final_cut_above), n_threads, check_finite)

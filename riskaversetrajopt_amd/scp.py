@@ -43,13 +43,20 @@ def run_drone(model, num_scp_iters_max=60, warmup_iters=5, verbose=False, check_
     for scp_iter in range(warmup_iters):
         model.update_problem(us_prev, scp_iter, verbose=False)
         us_prev, _ = model.solve(verbose=False)
+    return _timed_qp_loop(model, model.update_problem, num_scp_iters_max, verbose)
+
+
+def _timed_qp_loop(model, define, n_iters, verbose):
+    """The timed loop of run_drone / run_driving (drone_risk.py:519-532, driving.py:486-513): from the initial guess, a fixed
+    number of ``define(us_prev, scp_iter, verbose=False)`` / ``model.solve`` iterations with the wall-clock of each half.
+    -> dict(us, t_risk, define_s, solve_s, cumulative_s, L2_error)"""
     us_prev = model.initial_guess_us_mat()
     define_s, solve_s, err = [], [], []
     t_risk = None
-    for scp_iter in range(num_scp_iters_max):
+    for scp_iter in range(n_iters):
         _sync()
         t0 = time.perf_counter()
-        model.update_problem(us_prev, scp_iter, verbose=False)
+        define(us_prev, scp_iter, verbose=False)
         _sync()
         t1 = time.perf_counter()
         us, t_risk = model.solve(verbose=False)
@@ -337,26 +344,7 @@ def run_driving(model, num_scp_iters_max=15, verbose=False, check_finite=True):
     us, _ = model.solve()
     model.define_problem(us, 1, verbose=False)
     us, _ = model.solve()
-    us_prev = model.initial_guess_us_mat()
-    define_s, solve_s, err = [], [], []
-    t_risk = None
-    for scp_iter in range(num_scp_iters_max):
-        _sync()
-        t0 = time.perf_counter()
-        model.define_problem(us_prev, scp_iter, verbose=False)
-        _sync()
-        t1 = time.perf_counter()
-        us, t_risk = model.solve()
-        t2 = time.perf_counter()
-        define_s.append(t1 - t0)
-        solve_s.append(t2 - t1)
-        err.append(L2_error_us(us, us_prev))
-        us_prev = us
-        if verbose:
-            print(f"scp {scp_iter:3d}  define {t1 - t0:.4f}s  solve {t2 - t1:.4f}s  L2 {err[-1]:.3e}")
-    define_s, solve_s = np.array(define_s), np.array(solve_s)
-    return {"us": us_prev, "t_risk": t_risk, "define_s": define_s, "solve_s": solve_s,
-            "cumulative_s": np.cumsum(define_s + solve_s), "L2_error": np.array(err)}
+    return _timed_qp_loop(model, model.define_problem, num_scp_iters_max, verbose)
 
 
 def save_results(path, *arrays):
