@@ -577,7 +577,11 @@ __device__ __forceinline__ void drone_rowmax_rollout_block(const rato_drone_para
       bv = best[j];
       bi = j * S + best_t[j];
     }
-  m_out[m] = (float)bv;
+  // a NaN row loses every comparison above (and v_max_f64 returns its other operand): as in the driving kernel it is
+  // reported, not dropped.  A row is a function of p and dp after its step, and a NaN stays in either to the last step
+  // (p' = p + dt v, dp' = dp + dt dv), so the state after the loop tells whether a row was NaN: no test per step.
+  const bool bad = (p[0] != p[0]) | (p[1] != p[1]) | (dp[0] != dp[0]) | (dp[1] != dp[1]);
+  m_out[m] = bad ? __builtin_nanf("") : (float)bv;
   arg_out[m] = bi;
 }
 

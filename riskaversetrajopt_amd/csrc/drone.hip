@@ -1629,7 +1629,7 @@ extern "C" int rato_drone_linearize_generators(const rato_drone_params* p, const
   if (!params_ok(p) || !params64_ok(p) || !us || !dW || !mass || !Qsym || !A22 || (!W != !g_up) || !part) return RATO_EINVAL;
   dim3 grid(rato::nblocks_for(p->M)), block(RATO_BLOCK);
   const size_t lds = (size_t)(RATO_BLOCK / RATO_WAVE) * ((size_t)(p->S + 1) * 6 + (RATO_GEN_LDS_REDUCE ? 24 * 65 : 0)) * sizeof(double);
-  if (lds > 160 * 1024) return RATO_EINVAL;   // S <= 570
+  if (lds > 160 * 1024) return RATO_EINVAL;   // S <= 592: 32 (6 (S + 1) + 1560) bytes (S = 592: 163776, S = 593: 163968)
   static rato::DynamicLdsLimit gen_lds_limit;
   {
     const hipError_t e = gen_lds_limit.ensure(lds, [](size_t bytes) {
