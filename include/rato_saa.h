@@ -96,7 +96,8 @@ extern "C" {
  * rato_hopper_jacobian_nnz / rato_hopper_emit_jacobian_values -- the hopper's jacrev / Lagrangian Hessian in the reference's
  * layout; rato_scp_run_drone / rato_scp_iter -- the reduced SCP loop as one call; rato_car_ego_final_rows, rato_scp_run_car,
  * rato_scp_batch_run_car -- additions within version 12: the same for the driving problem; rato_drone_rows_plan /
- * rato_car_rows_plan -- a further addition within version 12: the row kernels' launch geometry as a query).
+ * rato_car_rows_plan -- a further addition within version 12: the row kernels' launch geometry as a query;
+ * rato_hopper_slip_f64 / rato_hopper_slip_f64_nblocks / rato_hopper_slip_hess_blocks_f64 -- likewise: the hopper's slip rows in fp64).
  * The Python binding refuses a library that reports another version. */
 #define RATO_ABI_VERSION 12
 #define RATO_STATS_IN_LAUNCH 1   /* params.stats_flags */
@@ -1203,6 +1204,48 @@ int rato_hopper_nlp_hessian(const rato_hopper_nlp_params* p, int32_t K, const do
 int rato_scatter_f64(int32_t K, int64_t n, const double* src /* [K][ld_src] */, int64_t ld_src, const int64_t* map /* [n] */,
                      const double* scale /* [n] or NULL */, double* dst /* [K][ld_dst] */, int64_t ld_dst, int64_t n_dst,
                      void* stream);
+
+/*
+ * Hopper slip rows in fp64 (hopper/hopper.py:68-81, :300-367, :569-580) -- a further addition within version 12.
+ *
+ * The risk group of the NLP above at the precision of its other rows: h_ic = fx_c - mu_i(p_c) fz_c for problem k, sample i and
+ * contact c on step t_c of [0, time_jump) U [time_land, S) (C = time_jump + S - time_land contacts), computed from Z on the
+ * device: x_t = Z[k][8t ..), (fx, fz) = Z[k][8(S+1) + 4t + 2 ..), p = x0 + x3 sin x2, chain J = (1, x3 cos x2, sin x2),
+ * mu_i(p) = mu_nom + sum_k a_ik cos(theta_ik p + tau_ik) with fp64 sin / cos (csrc/hopper_slip64.hip; the per-lane arithmetic
+ * is csrc/rato_hopper_slip64.h).  rato_hopper_slip* above (fp32) stays the Monte-Carlo / large-M throughput path.
+ *
+ * Device pointers (fp64), stream ordered, no allocation.  p supplies S and the phase times (nothing else of it is read);
+ * mu_nom comes from the caller.  a, theta, tau are [30][M].  Outputs, any of which may be NULL (not written; the others are
+ * bitwise the same either way):
+ *   h      [K][C][M]      fx - mu fz
+ *   dh_dfz [K][C][M]      -mu
+ *   dh_dx  [K][C][3][M]   dh/d(x0, x2, x3) = -mu' fz J, the chain applied: the x3 entry is 0.0 where sin x2 is
+ *   Zmax   [K][M]         max over the contacts of h
+ * lam (or NULL) is the caller's multiplier array [K][ldlam] read in place at lam[k][lam_r0 + i C + c] (the risk rows' own
+ * order; ldlam >= lam_r0 + M C).  With lam:
+ *   part   workspace, double[rato_hopper_slip_f64_nblocks(M)][K][C][3]: per-workgroup sums over the samples of a tile
+ *   D      [K][C][3]      (D1, D2, D0) = sum_i lam (d2h/(dp dfz), d2h/dp2, dh/dp) = sum_i lam (-mu', -mu'' fz, -mu' fz)
+ * The sums are fp64 in a fixed order (a tree inside the workgroup, then rato_sum_partials_f64 over the tiles), without atomics:
+ * two calls on the same inputs are bitwise equal, and row k of a K-problem call is bitwise what the K = 1 call gives.
+ * One launch for K problems, two with lam.  A workgroup is a tile of TI samples x 256 / TI contacts, TI the smallest power of
+ * two >= M, at most 256 (rato_hopper_slip_f64_nblocks(M) = ceil(M / TI) tiles).
+ * RATO_EINVAL without a launch unless S >= 1, 1 <= K <= 65535, M >= 1, ldz >= 8(S+1) + 4S, 0 <= time_jump <= time_land <= S,
+ * Z and the fields are non-NULL and, with lam, part and D are non-NULL, lam_r0 >= 0 and ldlam >= lam_r0 + M C.  C = 0 is valid
+ * and launches nothing.
+ */
+int rato_hopper_slip_f64_nblocks(int32_t M);
+int rato_hopper_slip_f64(const rato_hopper_nlp_params* p, double mu_nom, int32_t K, int32_t M,
+                         const double* Z /* [K][ldz] */, int64_t ldz, const double* a, const double* theta, const double* tau,
+                         const double* lam /* [K][ldlam] or NULL */, int64_t ldlam, int64_t lam_r0, double* h, double* dh_dfz,
+                         double* dh_dx, double* Zmax, double* part, double* D, void* stream);
+
+/* The slip rows' share of hess(lam . g), added IN PLACE into add [K][S+1][78] (the `add` of rato_hopper_nlp_hessian, zeroed or
+ * pre-filled by the caller) at the np.tril_indices(12) positions of step t_c: local indices 0, 2, 3 (x0, x2, x3) and 11 (fz),
+ * nine entries per contact -- the block D2 J J' + D0 H with H the curvature of p (H11 = -x3 sin x2, H12 = H21 = cos x2) and
+ * the mixed entries D1 J.  D [K][C][3] is rato_hopper_slip_f64's.  One lane per (problem, contact, entry); contacts sit on
+ * distinct steps, so every entry has one writer.  RATO_EINVAL as above, and when Z, D or add is NULL; C = 0 launches nothing. */
+int rato_hopper_slip_hess_blocks_f64(const rato_hopper_nlp_params* p, int32_t K, const double* Z /* [K][ldz] */, int64_t ldz,
+                                     const double* D, double* add, void* stream);
 
 #ifdef __cplusplus
 }

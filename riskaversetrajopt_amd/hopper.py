@@ -8,6 +8,9 @@ hands to IPOPT (:486-640) on the MI355X.
     (rato_hopper_nlp_linearize / rato_hopper_nlp_hessian, csrc/hopper_nlp.hip); rato_scatter_f64 places the local blocks
     into the CSC values of the Jacobian and into the tril-packed Hessian.  The kernels are phase-agnostic: the contact /
     flight masks, the constant unit coefficients and the script's row order live here.
+  * ``Model(..., precision='f64')``: the sample-dependent part at the precision of the rest, from Z on the device for K problems
+    per call (rato_hopper_slip_f64 / rato_hopper_slip_hess_blocks_f64, csrc/hopper_slip64.hip); 'f32' stays the default and
+    the Monte-Carlo / large-M path.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
 There is no solver driver: IPOPT is the caller's."""
 import ctypes as C
@@ -141,8 +144,14 @@ def block_variables(S, t):
 
 class Model:
     def __init__(self, M, method='baseline', alpha=0.1, S=S, fields=None, device='cuda:0', rng=None,
-                 verbose=False, phases=None):
+                 verbose=False, phases=None, precision='f32'):
+        """precision: 'f32' -- the risk group (the slip rows, their Jacobian and Hessian share) from the fp32 throughput kernel
+        (csrc/hopper.hip), gathered on the host one problem per call; 'f64' -- from the fp64 kernels of csrc/hopper_slip64.hip,
+        computed from Z on the device for K problems per call, like every other row of the NLP."""
         # hopper.py:91-104
+        if precision not in ('f32', 'f64'):
+            raise ValueError(f"precision must be 'f32' or 'f64', got {precision!r}")
+        self.precision = precision
         if verbose:
             print("Initializing Model with")
             print("> method =", method)
@@ -161,13 +170,25 @@ class Model:
             self._a, self._th, self._tau = (
                 torch.as_tensor(f, device=self.device).t().contiguous().float()
                 for f in (self.intensities, self.thetas, self.taus))
+            if precision == 'f64':
+                self._fields64 = tuple(torch.as_tensor(np.ascontiguousarray(f.T), device=self.device)
+                                       for f in (self.intensities, self.thetas, self.taus))
 
     @classmethod
-    def from_device(cls, a, theta, tau, method='saa', alpha=0.1, S=S):
-        self = cls(a.shape[1], method, alpha, S=S, fields='device', device=a.device)
+    def from_device(cls, a, theta, tau, method='saa', alpha=0.1, S=S, precision='f32'):
+        self = cls(a.shape[1], method, alpha, S=S, fields='device', device=a.device, precision=precision)
         self._a, self._th, self._tau = (_lib.require_f32_device(t, n) for t, n in
                                         ((a, "a"), (theta, "theta"), (tau, "tau")))
         return self
+
+    def fields_f64(self):
+        """the friction fields [30][M] as fp64 device tensors: from the host fp64 arrays, or upcast once from the fp32 device
+        arrays (from_device / fields='device')"""
+        f = getattr(self, "_fields64", None)
+        if f is None:
+            f = self._fields64 = tuple(_lib.require_f32_device(t, n).double() for t, n in
+                                       ((self._a, "a"), (self._th, "theta"), (self._tau, "tau")))
+        return f
 
     # ---- variable layout (hopper.py:105-132) -------------------------------
     def convert_z_to_variables(self, z):
@@ -284,6 +305,9 @@ class Model:
     def slip_risk_constraints(self, Z):
         """hopper.py:300-367 -> gs (1 + M + M*C + 1,) ['saa'] or (M*C,) ['baseline']."""
         Z = np.asarray(Z, dtype=np.float64)
+        if self.precision == 'f64':
+            h = self.slip_device_f64(Z[None], want=("h",))["h"][0].cpu().numpy()          # (C,M)
+            return self._risk_rows(Z, np.ascontiguousarray(h.T).reshape(-1))
         _, _, ys, slack_var, t_risk = self.convert_z_to_variables(Z)
         px, forces = self.contact_inputs(Z)
         h = self.slip_device(px, forces, want_Z=False)["h"].t().double().cpu().numpy()   # (M,C)
@@ -350,8 +374,16 @@ class Model:
         """-> (values [nnz] fp32 device tensor, indices, indptr, shape): ``jacrev(slip_risk_constraints)(Z)`` of the
         reference (hopper.py:569 on the rows of :300-367), rows and columns in its order, as CSC with every structural entry
         present; the values are written on the device (rato_hopper_emit_jacobian_values) from the slip kernel's partials and
-        the end-effector chain factors.  ``out``: the value tensor of an earlier call (its constant part is kept)."""
+        the end-effector chain factors.  ``out``: the value tensor of an earlier call (its constant part is kept).
+        precision='f64': the values are fp64, computed from Z on the device (rato_hopper_slip_f64) and placed by
+        rato_scatter_f64; ``out`` is not used."""
         Z = np.asarray(Z, dtype=np.float64)
+        if self.precision == 'f64':
+            lay = self.nlp_layout()
+            saa = self.method != 'baseline'
+            indices, indptr = self._jacobian_pattern(lay["C"])
+            n_rows = (1 + self.M + self.M * lay["C"] + 1) if saa else self.M * lay["C"]
+            return self._slip_f64(Z[None])["slip_jac_values"][0], indices, indptr, (n_rows, self.num_vars)
         px, forces = self.contact_inputs(Z)
         Cn, M = px.shape[0], self._a.shape[1]
         r = self.slip_device(px, forces, want_Z=False, want_h=False, want_deriv=True)
@@ -393,6 +425,11 @@ class Model:
         come from ONE launch (rato_hopper_slip_hessian); the 15 entries per contact are placed on the host."""
         import scipy.sparse as sp
         Z = np.asarray(Z, dtype=np.float64)
+        if self.precision == 'f64':
+            ncon, r0 = self.risk_rows_offset()
+            full = np.zeros(ncon)
+            full[r0:r0 + np.size(lam)] = np.asarray(lam, dtype=np.float64).reshape(-1)
+            return self._blocks_to_csc(self.slip_hessian_blocks(Z, full))
         px, forces = self.contact_inputs(Z)
         D = self.slip_hessian_sums3(px, forces, lam)
         Jee, Hee = self.contact_chain(Z)
@@ -430,6 +467,132 @@ class Model:
             None, None, _lib.ptr(part), _lib.current_stream()), "rato_hopper_slip_hessian")
         return stats.sum_partials(part).cpu().numpy().reshape(Cn, 3)
 
+    # ---- the fp64 path (precision='f64'): from Z on the device, K problems per call (csrc/hopper_slip64.hip) -----------------
+    def risk_rows_offset(self):
+        """(ncon, r0): the length of g and the index in g of the slip row of sample 0, contact 0 (row r0 + i C + c), by
+        arithmetic alone (no layout is built: M may be large)"""
+        S, M, tj, tl = self.S, self.M, self.time_jump, self.time_land
+        saa = self.method != 'baseline'
+        Cn, n_state = tj + (S - tl), tj + (S + 1 - tl)
+        risk = n_x * S + n_x + 2 + 2 * n_state + (tl - tj)
+        n_risk = (1 + M + M * Cn + 1) if saa else M * Cn
+        return risk + n_risk + n_u * S + 1 + 3 * S, risk + (1 + M if saa else 0)
+
+    def _slip_params(self):
+        p = getattr(self, "_slip_p", None)
+        if p is None:
+            p = self._slip_p = nlp_params(self.S, self.time_jump, self.time_land, self.dt)
+        return p
+
+    def _device_rows(self, Zs):
+        if not isinstance(Zs, torch.Tensor):
+            Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=self.device)
+        return Zs
+
+    def slip_device_f64(self, Zs, lams=None, want=("h", "dh_dfz", "dh_dx", "Zmax")):
+        """rato_hopper_slip_f64 for K problems.  Zs (K, >= 8(S+1) + 4S) host array or device fp64 tensor (rows may be strided);
+        lams (K, ncon) multipliers of g (host array or device fp64 tensor, read in place at the risk rows) or None.
+        -> dict of fp64 device tensors, those named in ``want``: h (K, C, M), dh_dfz (K, C, M), dh_dx (K, C, 3, M) = dh/d(x0, x2,
+        x3) with the end-effector chain applied, Zmax (K, M); and D (K, C, 3) = (D1, D2, D0), the lambda-weighted sample sums of
+        d2h/(dp dfz), d2h/dp2 and dh/dp (None without lams).  One launch, two with lams."""
+        S, M, dev = self.S, self.M, self.device
+        if not 0 <= self.time_jump <= self.time_land <= S:
+            raise ValueError(f"phase times must satisfy 0 <= time_jump <= time_land <= S, got {self.time_jump}, {self.time_land}")
+        Zs = self._device_rows(Zs)
+        K, ldz = _rows_of(Zs, n_x * (S + 1) + n_u * S)
+        Cn = self.time_jump + (S - self.time_land)
+        params = self._slip_params()
+        shapes = {"h": (K, Cn, M), "dh_dfz": (K, Cn, M), "dh_dx": (K, Cn, 3, M), "Zmax": (K, M)}
+        e = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
+        out = {k: e(*shapes[k]) for k in want}
+        if Cn == 0 and "Zmax" in out:
+            out["Zmax"].fill_(-np.inf)                            # the maximum over no contact; nothing is launched
+        lamd = part = D = None
+        ldlam = r0 = 0
+        if lams is not None:
+            ncon, r0 = self.risk_rows_offset()
+            lamd = lams if isinstance(lams, torch.Tensor) else \
+                torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(lams, dtype=np.float64))), device=dev)
+            if tuple(lamd.shape) != (K, ncon) or lamd.dtype != torch.float64 or lamd.device != Zs.device or lamd.stride(1) != 1:
+                raise ValueError(f"lams must be (K, ncon) = ({K}, {ncon}) float64 with contiguous rows, got {tuple(lamd.shape)}")
+            ldlam = lamd.stride(0) if K > 1 else max(lamd.stride(0), ncon)
+            part = e(self._lib.rato_hopper_slip_f64_nblocks(M), K, Cn, 3)
+            D = e(K, Cn, 3)
+        a, th, tau = self.fields_f64()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.rato_hopper_slip_f64(
+                C.byref(params), mu_nom, K, M, _lib.ptr(Zs), ldz, _lib.ptr(a), _lib.ptr(th), _lib.ptr(tau), _lib.ptr(lamd), ldlam,
+                r0, *(_lib.ptr(out.get(k)) for k in ("h", "dh_dfz", "dh_dx", "Zmax")), _lib.ptr(part), _lib.ptr(D),
+                _lib.current_stream()), "rato_hopper_slip_f64")
+        out["D"] = D
+        return out
+
+    def slip_hess_blocks_device_f64(self, Zs, D, add):
+        """rato_hopper_slip_hess_blocks_f64: adds the slip rows' share of hess(lam . g) into add (K, S+1, 78), in place"""
+        Zs = self._device_rows(Zs)
+        K, ldz = _rows_of(Zs, n_x * (self.S + 1) + n_u * self.S)
+        if tuple(add.shape) != (K, self.S + 1, n_pairs) or add.dtype != torch.float64 or not add.is_contiguous() or \
+                tuple(D.shape[:1] + D.shape[2:]) != (K, 3) or not D.is_contiguous():
+            raise ValueError(f"add must be a contiguous device float64 tensor ({K}, {self.S + 1}, {n_pairs}) and D (K, C, 3)")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rato_hopper_slip_hess_blocks_f64(
+                C.byref(self._slip_params()), K, _lib.ptr(Zs), ldz, _lib.ptr(D), _lib.ptr(add), _lib.current_stream()),
+                "rato_hopper_slip_hess_blocks_f64")
+        return add
+
+    def _slip_f64(self, Zs, lams=None):
+        """one evaluation of the slip kernel and its emission: slip_h (K, C, M), slip_rows (K, M C): h in the risk rows' order
+        i C + c, slip_jac_values (K, nnz_slip): the CSC values of ``_jacobian_pattern`` with the constant part in place, D"""
+        lay = self.nlp_layout()
+        Cn, M = lay["C"], self.M
+        r = self.slip_device_f64(Zs, lams, want=("h", "dh_dfz", "dh_dx"))
+        K = r["h"].shape[0]
+        st = getattr(self, "_slip_dev", None)
+        if st is None:
+            up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=self.device)
+            st = self._slip_dev = dict(const=up(lay["slip_const"]), map_dx=up(lay["map_slip_dx"]), map_dfz=up(lay["map_slip_dfz"]),
+                                       map_h=up(lay["map_slip_h"]))
+        vals = st["const"][None].repeat(K, 1)
+        rows = torch.empty((K, M * Cn), dtype=torch.float64, device=self.device)
+        if Cn > 0:
+            scatter_f64(r["dh_dx"].view(K, -1), st["map_dx"], vals)
+            scatter_f64(r["dh_dfz"].view(K, -1), st["map_dfz"], vals)
+            scatter_f64(r["h"].view(K, -1), st["map_h"], rows)
+        return dict(slip_h=r["h"], slip_rows=rows, slip_jac_values=vals, D=r["D"])
+
+    def _risk_rows(self, Z, h_rows):
+        """the risk group from the slip values in row order i C + c (:339-367)"""
+        _, _, ys, slack_var, t_risk = self.convert_z_to_variables(Z)
+        M = self.M
+        Cn = h_rows.size // M
+        h = h_rows.reshape(M, Cn)
+        if self.method == 'baseline':
+            return (h - slack_var).reshape(M * Cn)
+        gs = np.zeros(1 + M + M * Cn + 1)
+        gs[0] = (M * self.alpha) * t_risk + np.sum(ys)
+        gs[1:1 + M] = -ys
+        gs[1 + M:1 + M + M * Cn] = (h - t_risk - ys[:, None] - slack_var).reshape(M * Cn)
+        return gs
+
+    def _blocks_to_csc(self, blocks):
+        """step blocks (S+1, 78) -> the symmetric scipy CSC (num_vars x num_vars), exact zeros dropped"""
+        import scipy.sparse as sp
+        tr, tc = np.tril_indices(n_l)
+        I, J, V = [], [], []
+        for t in np.flatnonzero(np.any(blocks != 0.0, axis=1)):
+            v = block_variables(self.S, t)
+            gr, gc, val = v[tr], v[tc], blocks[t]
+            ok = (gr >= 0) & (gc >= 0)
+            off = ok & (gr != gc)
+            I += [gr[ok], gc[off]]
+            J += [gc[ok], gr[off]]
+            V += [val[ok], val[off]]
+        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
+        H = sp.coo_matrix((cat(V, np.float64), (cat(I, np.int64), cat(J, np.int64))), shape=(self.num_vars, self.num_vars)).tocsc()
+        H.eliminate_zeros()
+        H.sort_indices()
+        return H
+
     # ---- Monte-Carlo validation (hopper.py:901-958) ------------------------
     def no_slip_constraints_verification(self, px, forces):
         Zh = self.slip_device(px, forces, want_h=False)["Z"].double().cpu().numpy()
@@ -459,7 +622,8 @@ class Model:
           scale_rows -1 on the leg-over-ground rows
           map_hess   [S+1][78] -> position in np.tril_indices(nvar) order (-1: the u part of the last block)
           lam_rows_index / lam_rows_sign  [S+1][2]: which multiplier of g weighs the state row (-1: none), and its sign
-          jac_indices / jac_indptr / pos_det / pos_slip   the full pattern and where the two value arrays go in it"""
+          jac_indices / jac_indptr / pos_det / pos_slip   the full pattern and where the two value arrays go in it
+          nnz_slip, slip_const, map_slip_dx / map_slip_dfz / map_slip_h   the fp64 slip path's emission (precision='f64')"""
         lay = getattr(self, "_nlp_layout", None)
         if lay is not None:
             return lay
@@ -555,6 +719,26 @@ class Model:
         lay.update(jac_indices=all_rows[order].astype(np.int32),
                    jac_indptr=np.concatenate([[0], np.cumsum(np.bincount(all_cols, minlength=nvar))]).astype(np.int64),
                    pos_det=where[:det_indices.size], pos_slip=where[det_indices.size:])
+        # the fp64 slip path (csrc/hopper_slip64.hip): where dh_dx [C][3][M], dh_dfz [C][M] and h [C][M] go -- positions in the
+        # slip Jacobian's own CSC values (``_jacobian_pattern`` order) and in the risk rows' order i C + c -- and the constant
+        # entries of those values (M alpha in fp64)
+        CM = Cn * M
+        ci, ii = np.divmod(np.arange(CM, dtype=np.int64), M)
+        slip_const = np.zeros(len(s_idx))
+        if Cn > 0:
+            slip_const[3 * CM:5 * CM].reshape(Cn, 2, M)[:, 0, :] = 1.0                   # d/dfx
+            o = 5 * CM
+            if saa:
+                slip_const[o:o + M * (2 + Cn)] = np.tile(np.concatenate([[1.0, -1.0], -np.ones(Cn)]), M)   # the y_i columns
+                o += M * (2 + Cn)
+            slip_const[o:o + CM] = -1.0                                                  # slack
+            o += CM
+            if saa:
+                slip_const[o], slip_const[o + 1:o + 1 + CM] = M * self.alpha, -1.0       # t_risk
+                o += 1 + CM
+            assert o == slip_const.size
+        lay.update(nnz_slip=slip_const.size, slip_const=slip_const, map_slip_dx=np.arange(3 * CM, dtype=np.int64),
+                   map_slip_dfz=3 * CM + ci * (2 * M) + M + ii, map_slip_h=ii * Cn + ci)
         self._nlp_layout = lay
         return lay
 
@@ -632,7 +816,11 @@ class Model:
         (K, ncon) multipliers of g or None; add (K, S+1, 78) blocks added to the Hessian or None.  -> dict of fp64 DEVICE tensors:
         defect (K, S, 8), d_defect (K, S, 8, 12), rows (K, S+1, 2), d_rows (K, S+1, 2, 4), jac_values (K, nnz): the CSC values of
         the deterministic rows' Jacobian in ``nlp_layout()``'s det_indices / det_indptr order; and with lams: hess_blocks
-        (K, S+1, 78), hess_tril (K, nvar (nvar+1)/2) in np.tril_indices(nvar) order.  Four launches without lams, six with."""
+        (K, S+1, 78), hess_tril (K, nvar (nvar+1)/2) in np.tril_indices(nvar) order.  Four launches without lams, six with.
+        precision='f64' adds the risk group, from the same Z on the device (no host gather): slip_h (K, C, M), slip_rows
+        (K, M C) = h in the risk rows' order i C + c, slip_jac_values (K, nnz_slip) in ``_jacobian_pattern`` order with the
+        constant entries in place; with lams the slip rows' share is inside hess_blocks / hess_tril (the multipliers are read
+        where they lie).  Four more launches, seven with lams."""
         dev = self.device
         if not isinstance(Zs, torch.Tensor):
             Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=dev)
@@ -646,12 +834,21 @@ class Model:
         scatter_f64(out["d_defect"].view(K, -1), st["map_defect"], jac)
         scatter_f64(out["d_rows"].view(K, -1), st["map_rows"], jac, st["scale_rows"])
         out["jac_values"] = jac
+        f64 = self.precision == 'f64'
+        if f64:                                                   # the risk group from the same Z, on the device
+            if lams is not None and not isinstance(lams, torch.Tensor):
+                lams = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(lams, dtype=np.float64))), device=dev)
+            slip = self._slip_f64(Zs, lams)
+            out.update(slip_h=slip["slip_h"], slip_rows=slip["slip_rows"], slip_jac_values=slip["slip_jac_values"])
         if lams is not None:
             lam_dyn, lam_rows = self.fold_multipliers(lams.cpu().numpy() if isinstance(lams, torch.Tensor) else lams)
             if lam_dyn.shape[0] != K:
                 raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")
             if add is not None and not isinstance(add, torch.Tensor):
                 add = torch.as_tensor(np.ascontiguousarray(add, dtype=np.float64), device=dev)
+            if f64 and self.nlp_layout()["C"] > 0:                # the caller's add is left as it is
+                add = torch.zeros((K, self.S + 1, n_pairs), dtype=torch.float64, device=dev) if add is None else add.clone()
+                self.slip_hess_blocks_device_f64(Zs, slip["D"], add)
             blocks = nlp_hessian_device(st["params"], Zs, torch.as_tensor(lam_dyn, device=dev),
                                         torch.as_tensor(lam_rows, device=dev), add)
             tril = hess_t.clone()
@@ -660,14 +857,20 @@ class Model:
         return out
 
     def g(self, Z, _lin=None):
-        """:491-514: all ten groups in the script's order (float64); the risk group is ``slip_risk_constraints`` (fp32 path)"""
+        """:491-514: all ten groups in the script's order (float64); the risk group is ``slip_risk_constraints`` (fp32 path), or with
+        precision='f64' the fp64 slip rows of the same ``nlp_device`` call"""
         Z = np.asarray(Z, dtype=np.float64)
         lay = self.nlp_layout()
         r = _lin if _lin is not None else self.nlp_device(Z[None])
         defect, rows = r["defect"][0].cpu().numpy(), r["rows"][0].cpu().numpy()
         xs, us = self.convert_z_to_xs_us_mats(Z)
         st, tj, tl = lay["states"], self.time_jump, self.time_land
-        risk = self.slip_risk_constraints(Z) if lay["C"] > 0 else self._risk_without_contacts(Z)
+        if lay["C"] == 0:
+            risk = self._risk_without_contacts(Z)
+        elif self.precision == 'f64':
+            risk = self._risk_rows(Z, r["slip_rows"][0].cpu().numpy())
+        else:
+            risk = self.slip_risk_constraints(Z)
         return np.concatenate([defect.reshape(-1), xs[0] - state_initial, (xs[-1] - state_final)[4:6], rows[st, 0], rows[st, 1],
                                -rows[tj:tl, 1], risk, us.reshape(-1), [Z[-2]], xs[1:, 3], xs[1:, 7], xs[1:, 6]])
 
@@ -688,7 +891,9 @@ class Model:
         r = _lin if _lin is not None else self.nlp_device(Z[None])
         data = np.zeros(lay["jac_indices"].size)
         data[lay["pos_det"]] = r["jac_values"][0].cpu().numpy()
-        if lay["C"] > 0:
+        if lay["C"] > 0 and self.precision == 'f64':
+            data[lay["pos_slip"]] = r["slip_jac_values"][0].cpu().numpy()
+        elif lay["C"] > 0:
             vals, _, indptr, _ = self.slip_jacobian_device(Z)
             slip = vals.double().cpu().numpy()
             if self.method != 'baseline':
@@ -700,6 +905,13 @@ class Model:
         """the risk group's share of hess(lam . g) as step blocks (S+1, 78), computed as ``slip_hessian`` computes it: per
         contact the 3 x 3 block on (x0, x2, x3) of its step and the mixed entries with fz (local 0, 2, 3 and 11)"""
         lay = self.nlp_layout()
+        if self.precision == 'f64':
+            Zd = self._device_rows(np.asarray(Z, dtype=np.float64)[None])
+            add = torch.zeros((1, self.S + 1, n_pairs), dtype=torch.float64, device=self.device)
+            if lay["C"] > 0:
+                D = self.slip_device_f64(Zd, np.asarray(lam, dtype=np.float64)[None], want=())["D"]
+                self.slip_hess_blocks_device_f64(Zd, D, add)
+            return add[0].cpu().numpy()
         blocks = np.zeros((self.S + 1, n_l, n_l))
         Cn, M = lay["C"], self._a.shape[1]
         if Cn > 0:
@@ -718,7 +930,8 @@ class Model:
         return blocks[:, tr, tc]
 
     def _hess_add(self, Z, lam, obj_factor):
-        add = self.slip_hessian_blocks(Z, lam)
+        # precision='f64': nlp_device adds the slip share on the device
+        add = self.slip_hessian_blocks(Z, lam) if self.precision != 'f64' else np.zeros((self.S + 1, n_pairs))
         tr, tc = np.tril_indices(n_l)
         diag_u = np.flatnonzero((tr == tc) & ((tr == n_x) | (tr == n_x + 1)))
         add[:self.S, diag_u] += 2.0 * float(obj_factor)          # hess_f: 2 R on u0 and u1, R = 1 (:443-448)
@@ -747,7 +960,8 @@ class Model:
         eval_h_sparsity_indices, nvar, ncon): the arguments of the script's ``ipyopt.Problem(...)`` call (:646-661), same
         signatures (the callbacks write into ``out``).  sparse=False: the script's dense row-major Jacobian and tril Hessian
         (:633-640).  sparse=True: the index pairs are the structural patterns (CSC order of ``jac_g``; the step blocks of the
-        Hessian) and ``out`` holds only those entries.  eval_g and eval_jac_g at the same x share one evaluation."""
+        Hessian) and ``out`` holds only those entries.  eval_g and eval_jac_g at the same x share one evaluation; with
+        precision='f64' that one evaluation holds the slip kernel's too (one rato_hopper_slip_f64 call for both)."""
         lay = self.nlp_layout()
         nvar, ncon, S = lay["nvar"], lay["ncon"], self.S
         cache = {}
