@@ -1247,6 +1247,54 @@ int rato_hopper_slip_f64(const rato_hopper_nlp_params* p, double mu_nom, int32_t
 int rato_hopper_slip_hess_blocks_f64(const rato_hopper_nlp_params* p, int32_t K, const double* Z /* [K][ldz] */, int64_t ldz,
                                      const double* D, double* add, void* stream);
 
+/*
+ * The Newton step of the hopper's interior-point solver (riskaversetrajopt_amd/hopper_ipm.py; csrc/hopper_ipm.hip) -- a further
+ * addition within version 12.  fp64 throughout, K problems per launch, device pointers, stream ordered, no allocation.  No
+ * floating-point atomics: every output entry has one owner that sums in a fixed order, so two calls are bitwise equal and
+ * problem k of a batch is bitwise its K = 1 call.
+ *
+ * The Jacobian J (ncon x n) is given by its values on a FIXED pattern, as one or two arrays per problem: value index i is
+ * vals0[k][i] for i < n0 and vals1[k][i - n0] otherwise (n1 = 0: vals1 is not read).  For the hopper these are nlp_device's
+ * jac_values and slip_jac_values where they lie; the index lists below are built once on the host in that numbering.
+ *
+ * rato_normal_matrix_f64:  Kc[k] = J' diag(d[k]) J + W[k] + diag(diag[k]), the lower triangle (b <= a) of a row-major n x n
+ * array with leading dimension lda >= n, Kc[k][a][b] at Kc[(k n + a) lda + b]; the strict upper triangle and the padding are
+ * not touched.  One lane per (a, b):
+ *   ent_of   [n][n] int32   the structural entry of (a, b), or -1: the lane writes 0.0
+ *   ptr      [n_ent + 1]    the entry's segment of the product map
+ *   tri_a, tri_b, tri_r     per triple the value indices of J_ra and J_rb and the row r, sorted by r inside a segment; the
+ *                           lane sums (J_ra d_r) J_rb in that order
+ *   hess_src [n_ent] int32  where the entry lies in hess[k] (-1: nowhere); hess [K][n_hess] (the step blocks, or NULL) is
+ *                           added after the sum, diag [K][n] (or NULL) after that on a == b
+ * rato_csc_matvec_f64 / rato_csc_tmatvec_f64:  out[k] = J v[k] (one lane per row, through the row list row_ptr / row_idx /
+ * row_col) and out[k] = J' w[k] (one lane per column: col_ptr is the CSC indptr in the same numbering, col_idx the value
+ * index, col_row the row).
+ * RATO_EINVAL without a launch on a NULL or undersized argument, K outside [1, 65535] or n > 32768.  The lists are trusted:
+ * their indices must lie inside the arrays they address.
+ */
+int rato_normal_matrix_f64(int32_t K, int32_t n, int64_t lda, const double* vals0, int64_t ld0, int64_t n0, const double* vals1,
+                           int64_t ld1, int64_t n1, const double* d /* [K][ncon] */, int64_t ncon, const double* hess,
+                           int64_t n_hess, const double* diag, const int32_t* ent_of, const int64_t* ptr, const int32_t* tri_a,
+                           const int32_t* tri_b, const int32_t* tri_r, const int32_t* hess_src, double* Kc, void* stream);
+int rato_csc_matvec_f64(int32_t K, int64_t ncon, int64_t n, const double* vals0, int64_t ld0, int64_t n0, const double* vals1,
+                        int64_t ld1, int64_t n1, const int64_t* row_ptr, const int32_t* row_idx, const int32_t* row_col,
+                        const double* v /* [K][ldv] */, int64_t ldv, double* out /* [K][ldo] */, int64_t ldo, void* stream);
+int rato_csc_tmatvec_f64(int32_t K, int64_t ncon, int64_t n, const double* vals0, int64_t ld0, int64_t n0, const double* vals1,
+                         int64_t ld1, int64_t n1, const int64_t* col_ptr, const int32_t* col_idx, const int32_t* col_row,
+                         const double* w /* [K][ldw] */, int64_t ldw, double* out /* [K][ldo] */, int64_t ldo, void* stream);
+
+/* In-place blocked Cholesky A = L L' of K row-major matrices A[k] (n x n, leading dimension lda >= n), lower triangle: only
+ * entries with b <= a < n are read or written, so the strict upper triangle and the padding may hold anything (NaN included).
+ * One workgroup per problem, panels of rato_chol_panel_width() columns.  info[k] = 0, or j + 1 for the first pivot j that is
+ * not a positive finite number: that problem stops there (its matrix is left partly factored), the others are not affected and
+ * the call still returns RATO_OK -- an indefinite matrix is an answer (the solver's inertia test), not an error.
+ * rato_chol_solve_batch_f64 solves L L' x = b in place for nrhs right-hand sides per problem, B[k][r] at B[(k nrhs + r) ldb],
+ * ldb >= n, n <= 8000.  RATO_EINVAL without a launch on NULL pointers, n < 1, lda < n, ldb < n or K outside [1, 65535]. */
+int rato_chol_panel_width(void);
+int rato_chol_factor_batch_f64(double* A, int32_t n, int64_t lda, int32_t K, int32_t* info, void* stream);
+int rato_chol_solve_batch_f64(const double* L, int32_t n, int64_t lda, int32_t K, double* B, int32_t nrhs, int64_t ldb,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,18 @@ SIGNATURES = {
                              [c_float_p] * 4 + [C.c_int64, C.c_int64] + [c_float_p] * 6 + [c_stream]),
     "rato_hopper_slip_hess_blocks_f64": (C.c_int, [C.POINTER(HopperNlpParams), C.c_int32, c_float_p, C.c_int64, c_float_p,
                                                    c_float_p, c_stream]),
+    "rato_normal_matrix_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64,
+                                         C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_int64] + [c_float_p] * 8 + [c_stream]),
+    "rato_csc_matvec_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64,
+                                      C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int64, c_float_p, C.c_int64,
+                                      c_stream]),
+    "rato_csc_tmatvec_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64,
+                                       C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int64, c_float_p, C.c_int64,
+                                       c_stream]),
+    "rato_chol_panel_width": (C.c_int, []),
+    "rato_chol_factor_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, c_stream]),
+    "rato_chol_solve_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int64,
+                                            c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h

@@ -12,7 +12,8 @@ hands to IPOPT (:486-640) on the MI355X.
     per call (rato_hopper_slip_f64 / rato_hopper_slip_hess_blocks_f64, csrc/hopper_slip64.hip); 'f32' stays the default and
     the Monte-Carlo / large-M path.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
-There is no solver driver: IPOPT is the caller's."""
+  * ``Model.initial_guess()`` and ``Model.solve()``: the script's start and its solve (:136-164, :642-669) with the batched
+    interior-point method of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip) in IPOPT's place."""
 import ctypes as C
 
 import numpy as np
@@ -783,6 +784,25 @@ class Model:
         x_L[:n_x * (self.S + 1)] = np.tile(lo, self.S + 1)
         x_U[:n_x * (self.S + 1)] = np.tile(hi, self.S + 1)
         return x_L, x_U
+
+    def initial_guess(self):
+        """:136-164: the initial state until landing and the final state after it, the weight carried by u1 and fz in contact"""
+        S, tj, tl = self.S, self.time_jump, self.time_land
+        Zp = np.zeros(self.num_vars)
+        xs = Zp[:n_x * (S + 1)].reshape(S + 1, n_x)
+        us = Zp[n_x * (S + 1):n_x * (S + 1) + n_u * S].reshape(S, n_u)
+        xs[:tl], xs[tl:] = state_initial, state_final
+        nominal_force = (mass_body + mass_leg) * gravity
+        for sl in (slice(0, tj), slice(tl, S)):
+            us[sl, 1] = us[sl, 3] = nominal_force
+        return Zp
+
+    def solve(self, Z0=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False):
+        """The script's solve (:642-669, its options tol = 1e-3, max_iter = 3000) with the batched interior-point method of
+        ``hopper_ipm`` in place of IPOPT -> (Z, info); info["status"] is 'converged' only if the final error shows it."""
+        from . import hopper_ipm
+        return hopper_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter, backend=backend,
+                                      callbacks=None if callbacks is None else [callbacks], verbose=verbose)[0]
 
     def _nlp_state(self, K):
         """device-side constants of the emission: the maps (uploaded once) and, per K, the destinations zeroed / pre-filled once"""

@@ -656,3 +656,72 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
     return {"alphas": alphas, "results": results, "status": np.array([r["status"] for r in results]), "us": us, "Z": Z,
             "percentage_safe": np.mean(Z <= 1e-6, axis=1), "cost": np.array([mc_model.monte_carlo_cost(u) for u in us]),
             "wall_s": wall}
+
+
+def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device'):
+    """The hopper script's solve block (hopper.py:642-670) for one model: ``hopper_ipm.solve_batch`` in IPOPT's place, from
+    ``Z0`` (default ``model.initial_guess()``) -> dict(Z, xs (S+1, 8), us (S, 4), status, info, total_s).  status is
+    'converged' only if the final error E_0 <= tol shows it."""
+    t0 = time.perf_counter()
+    Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend)
+    xs, us = model.convert_z_to_xs_us_mats(Z)
+    return {"Z": Z, "xs": xs, "us": us, "status": info["status"], "info": info, "total_s": time.perf_counter() - t0}
+
+
+def hopper_result_path(results_dir, method, alpha=None):
+    """hopper.py:672-680: hopper_base_results.npy / hopper_saa_alpha=<alpha>_results.npy"""
+    name = "hopper_base_results.npy" if method == 'baseline' else f"hopper_saa_alpha={alpha}_results.npy"
+    return os.path.join(results_dir, name)
+
+
+def save_hopper_result(results_dir, model, Z):
+    """xs then us in one file, as the script writes them (:672-680) -> the path"""
+    os.makedirs(results_dir, exist_ok=True)
+    path = hopper_result_path(results_dir, model.method, model.alpha)
+    xs, us = model.convert_z_to_xs_us_mats(Z)
+    save_results(path, xs, us)
+    return path
+
+
+def hopper_saa_start(model, xs, us):
+    """the script's SAA start (:470-479): the baseline's states and controls, ys = slack = t_risk = 0"""
+    from . import hopper
+    Z0 = np.zeros(model.num_vars)
+    nX = hopper.n_x * (model.S + 1)
+    Z0[:nX] = np.asarray(xs, dtype=np.float64).reshape(-1)
+    Z0[nX:nX + hopper.n_u * model.S] = np.asarray(us, dtype=np.float64).reshape(-1)
+    return Z0
+
+
+def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=1, results_dir=None, tol=1e-3, max_iter=3000,
+                      backend='device', device='cuda:0', clocks=None):
+    """The hopper script's two runs (hopper.py:455-680) as one call: the friction fields under ``RandomState(seed)`` (:70-74),
+    the baseline from ``initial_guess()``, then every alpha of the SAA problem in ONE lockstep batch from the baseline's
+    solution (:465-479).  With ``results_dir`` the files hopper_base_results.npy and hopper_saa_alpha=<a>_results.npy are
+    written (xs then us, ``save_results``), whatever the status.
+    -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)"""
+    from . import hopper, hopper_ipm
+    alphas = [float(a) for a in alphas]
+    fields = hopper.sample_friction_fields(M, np.random.RandomState(seed))
+    t0 = time.perf_counter()
+    base_model = hopper.Model(M, 'baseline', S=S, fields=fields, device=device, precision='f64')
+    c0 = {}
+    (Zb, ib), = hopper_ipm.solve_batch([base_model], tol=tol, max_iter=max_iter, backend=backend, clocks=c0)
+    xs, us = base_model.convert_z_to_xs_us_mats(Zb)
+    base = {"Z": Zb, "xs": xs, "us": us, "status": ib["status"], "info": ib}
+    models = [hopper.Model(M, 'saa', a, S=S, fields=fields, device=device, precision='f64') for a in alphas]
+    c1 = {}
+    sols = hopper_ipm.solve_batch(models, [hopper_saa_start(m, xs, us) for m in models], tol=tol, max_iter=max_iter,
+                                  backend=backend, clocks=c1) if models else []
+    results = []
+    for m, (Z, info) in zip(models, sols):
+        x, u = m.convert_z_to_xs_us_mats(Z)
+        results.append({"Z": Z, "xs": x, "us": u, "status": info["status"], "info": info})
+    if clocks is not None:
+        clocks["base"], clocks["saa"] = c0, c1
+    if results_dir is not None:
+        save_hopper_result(results_dir, base_model, Zb)
+        for m, r in zip(models, results):
+            save_hopper_result(results_dir, m, r["Z"])
+    return {"alphas": alphas, "base": base, "results": results, "status": np.array([r["status"] for r in results]),
+            "wall_s": time.perf_counter() - t0}
