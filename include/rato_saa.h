@@ -1295,6 +1295,36 @@ int rato_chol_factor_batch_f64(double* A, int32_t n, int64_t lda, int32_t K, int
 int rato_chol_solve_batch_f64(const double* L, int32_t n, int64_t lda, int32_t K, double* B, int32_t nrhs, int64_t ldb,
                               void* stream);
 
+/* ---- Batched dense convex QP solve, fp64 (csrc/qp_ipm.hip): the QPs of the driving Gaussian baseline's SCP
+ * (car/driving_gaussian.py:428-456, n = 3S + 1 and m = 4S + 5 before the host presolve), which the reference hands to OSQP.
+ * ABI: additive (RATO_ABI_VERSION stays 12).
+ *
+ * Problem k:  min 1/2 z'P z + q'z  s.t.  l <= A z <= u.  P [k] n x n row-major, symmetric positive semi-definite (its lower
+ * triangle and its columns are read), at P + k strideP; q [k] at q + k strideq; a stride of 0 shares P or q across the batch.
+ * A [k] m x n row-major with leading dimension lda >= n at A + k strideA (the padding is never read); l, u [k] at
+ * l + k stridelu, u + k stridelu: +-inf = that side is absent, l == u = an equality.  m = 0 is allowed (A, l, u may be NULL).
+ *
+ * ONE launch solves all K problems to completion, one workgroup per problem, by a Mehrotra predictor-corrector interior-point
+ * method (cold start from z = 0; the method and its constants: riskaversetrajopt_amd/qp_ipm.py, whose solve_numpy is the same
+ * algorithm on the host).  tol <= 0 means 1e-8, max_iter <= 0 means 100; the loop is capped at 200 iterations and 12 retries
+ * per factorization whatever the arguments say.  Outputs, all fully written whatever the status: z [k] (n) at z + k stridez,
+ * y [k] (m, OSQP's sign: y > 0 on an active upper side, y < 0 on an active lower side) at y + k stridey, and
+ * info [k][8] = {status, iterations, factorizations, primal residual, dual residual, mu, last delta_w, largest
+ * complementarity product max_i(lam_l |A z - l|, lam_u |u - A z|)_i} with status
+ * 0 solved, 1 max_iter, 2 numerical (the factorization failed through the whole retry ladder, or a residual or step went
+ * non-finite: z, y are the last finite iterate), 3 invalid (NaN or inf in P, q, A, NaN in l or u, l > u, l = +inf or
+ * u = -inf on a row: z, y are NaN).  No floating-point atomics and fixed summation orders: problem k of a batch is bitwise its
+ * K = 1 run.
+ *
+ * workspace: rato_qp_ipm_workspace_bytes(K, n, m) bytes of device memory, 8-byte aligned (the condensed matrices; nothing is
+ * read from it before it is written).  Stream-ordered, no allocation.  RATO_EINVAL without a launch on NULL pointers, n < 1 or
+ * n > 256, m < 0 or m > 384, lda < n, a stride too small for its array, a workspace too small, or K outside [1, 65535]. */
+size_t rato_qp_ipm_workspace_bytes(int32_t K, int32_t n, int32_t m);
+int rato_qp_ipm_batch_f64(int32_t K, int32_t n, int32_t m, const double* P, int64_t strideP, const double* q, int64_t strideq,
+                          const double* A, int64_t lda, int64_t strideA, const double* l, const double* u, int64_t stridelu,
+                          double tol, int32_t max_iter, double* z, int64_t stridez, double* y, int64_t stridey,
+                          double* info /* [K][8] */, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

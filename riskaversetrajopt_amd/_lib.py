@@ -277,6 +277,10 @@ SIGNATURES = {
     "rato_chol_factor_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, c_stream]),
     "rato_chol_solve_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int64,
                                             c_stream]),
+    "rato_qp_ipm_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rato_qp_ipm_batch_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_int64, c_float_p,
+                                        C.c_int64, C.c_int64, c_float_p, c_float_p, C.c_int64, C.c_double, C.c_int32, c_float_p,
+                                        C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_void_p, C.c_size_t, c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h

@@ -13,13 +13,14 @@ import ctypes as C
 import numpy as np
 import scipy.sparse as sp
 
-from . import _lib, qp
+from . import _lib, qp, qp_ipm
 from . import driving_params as P
 
 n_x, n_u = P.n_x, P.n_u
 OSQP_TOL = 1e-8                                                  # driving_gaussian.py:27 (not driving_params.OSQP_TOL)
 BETA = 3e-2                                                      # :77
 MAX_S = 64                                                       # rato_car_gaussian_linearize: 2S lanes in one workgroup
+SOLVERS = ('osqp', 'ipm')
 
 
 def gauss_params(S, outer_product=False):
@@ -131,8 +132,14 @@ def objective_coeffs(S, dt):
 
 
 class Model:
-    def __init__(self, method='gaussian', alpha=0.1, S=P.S, device='cuda:0', outer_product=False, verbose=False):
+    def __init__(self, method='gaussian', alpha=0.1, S=P.S, device='cuda:0', outer_product=False, verbose=False,
+                 solver='osqp'):
+        """``solver``: 'osqp' (``qp.OSQP`` with the reference's arguments) or 'ipm' (``qp_ipm.IPM``: the batched interior-point
+        solver on the device, tol = OSQP_TOL, every solve a cold start)"""
         import torch
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        self.solver = solver
         if not 1 <= S <= MAX_S:
             raise ValueError(f"S must be in 1..{MAX_S} (one lane per control direction), got {S}")
         if verbose:
@@ -248,7 +255,14 @@ class Model:
         """``lin``: this problem's slice of a K-problem ``linearize_device`` call (host arrays), else one launch here."""
         self.P, self.q = self.get_objective_coeffs()
         self.A, self.l, self.u = self.get_constraints_coeffs(us_mat_p, alphas_risk_p, scp_iter, lin)
-        if scp_iter == 0 or scp_iter == 1:
+        if self.solver == 'ipm':
+            if scp_iter == 0 or scp_iter == 1:
+                self.osqp_prob = qp_ipm.IPM(device=str(self.device))
+                self.osqp_prob.setup(self.P, self.q, self.A, self.l, self.u, tol=OSQP_TOL)
+            else:
+                self.osqp_prob.update(l=self.l, u=self.u)
+                self.osqp_prob.update(Ax=self.A.data)
+        elif scp_iter == 0 or scp_iter == 1:
             self.osqp_prob = qp.OSQP()
             self.osqp_prob.setup(self.P, self.q, self.A, self.l, self.u, eps_abs=OSQP_TOL, eps_rel=OSQP_TOL,
                                  linsys_solver="qdldl", warm_start=True, verbose=verbose, polish=P.OSQP_POLISH)
@@ -258,8 +272,12 @@ class Model:
         return True
 
     def solve(self, verbose=False):
-        S = self.S
         self.res = self.osqp_prob.solve()
+        return self.solution(verbose)
+
+    def solution(self, verbose=False):
+        """(us, alphas_risk) of ``self.res`` (left by ``solve``, or by a batched solve of several models' problems)"""
+        S = self.S
         if self.res.info.status != 'solved' and verbose:
             print("[solve]: Problem infeasible.")
         us_sol = self.convert_us_vec_to_us_mat(self.res.x[:(n_u * S)])

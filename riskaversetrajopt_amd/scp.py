@@ -470,15 +470,23 @@ def driving_gaussian_tol():
 
 def _gaussian_solve_all(models, us_list, alphas_list, scp_iter, clocks=None):
     """One lockstep SCP iteration of K driving Gaussian problems: ONE K-problem linearize launch (models[0] launches: the
-    kernel's parameters do not depend on alpha), then K host QPs.  -> ([us], [alphas_risk], [status])"""
+    kernel's parameters do not depend on alpha), then K host QPs -- or, when the models' solver is 'ipm', ONE
+    ``qp_ipm.solve_batch`` launch for the K QPs.  -> ([us], [alphas_risk], [status])"""
+    batched = models[0].solver == 'ipm'
     t0 = time.perf_counter()
     lin = models[0].linearize_device(np.stack(us_list), np.stack(alphas_list))
     lin = {k: v.cpu().numpy() for k, v in lin.items()}             # (the copy waits for the launch)
     t1 = time.perf_counter()
-    us_out, al_out, status = [], [], []
+    us_out, al_out, status, sols = [], [], [], []
     for k, m in enumerate(models):
         m.define_problem(us_list[k], alphas_list[k], scp_iter, lin={key: v[k] for key, v in lin.items()})
-        us, al = m.solve()
+        if not batched:
+            sols.append(m.solve())
+    if batched:
+        _gaussian_solve_ipm(models)
+        sols = [m.solution() for m in models]
+    for k, m in enumerate(models):
+        us, al = sols[k]
         if not (np.all(np.isfinite(us)) and np.all(np.isfinite(al))):
             # a solve that hands back no point (qp.OSQP: 'primal infeasible' -> nan): the reference prints and carries the
             # nan on (:451-452); here the problem keeps its iterate, and the status list says so
@@ -496,12 +504,32 @@ def _gaussian_solve_all(models, us_list, alphas_list, scp_iter, clocks=None):
     return us_out, al_out, status
 
 
-def run_driving_gaussian_batch(models, num_scp_iters_max=60):
+def _gaussian_solve_ipm(models):
+    """the K defined problems in one ``qp_ipm.solve_batch`` call (P and q do not depend on alpha: shared); leaves ``m.res``"""
+    from . import qp_ipm
+    data = [m.osqp_prob.data() for m in models]
+    _, _, info = res = qp_ipm.solve_batch(data[0][0], data[0][1], np.stack([d[2] for d in data]), np.stack([d[3] for d in data]),
+                                          np.stack([d[4] for d in data]), models[0].osqp_prob.tol, models[0].osqp_prob.max_iter,
+                                          backend=models[0].osqp_prob.backend, device=models[0].osqp_prob.device)
+    for k, m in enumerate(models):
+        m.res = m.osqp_prob.result(res[0][k], res[1][k], info["status"][k], int(info["iterations"][k]))
+
+
+def run_driving_gaussian_batch(models, num_scp_iters_max=60, solver=None):
     """``run_driving_gaussian`` for K ``driving_gaussian.Model``s of one S in lockstep (the reference's four alphas,
-    driving_gaussian.py:469-498): per iteration one K-problem launch and K host QPs.  -> list of the result dicts."""
+    driving_gaussian.py:469-498): per iteration one K-problem launch and K host QPs ('osqp') or one K-problem QP launch ('ipm').
+    ``solver``: None = the models' own (which must agree), else it is set on every model.  -> list of the result dicts."""
     S, outer = models[0].S, models[0].outer_product
     if any(m.S != S or m.outer_product != outer for m in models):
         raise ValueError("the models of a lockstep batch share S and outer_product")
+    if solver is not None:
+        from . import driving_gaussian
+        if solver not in driving_gaussian.SOLVERS:
+            raise ValueError(f"solver must be one of {driving_gaussian.SOLVERS}, got {solver!r}")
+        for m in models:
+            m.solver = solver
+    if any(m.solver != models[0].solver for m in models):
+        raise ValueError("the models of a lockstep batch share their solver")
     K = len(models)
     us_prev = [m.initial_guess_us_mat() for m in models]           # the two warm-up solves (:472-479)
     al_prev = [m.initial_guess_alphas_risk() for m in models]
@@ -522,20 +550,21 @@ def run_driving_gaussian_batch(models, num_scp_iters_max=60):
              "status": [st[k] for st in statuses], "define_s": define_s, "solve_s": solve_s} for k in range(K)]
 
 
-def run_driving_gaussian(model, num_scp_iters_max=60):
+def run_driving_gaussian(model, num_scp_iters_max=60, solver=None):
     """driving_gaussian.py:471-492: two warm-up solves (scp_iter 0 and 1), restart from the initial guess, then a fixed number
     of define_problem / solve iterations with the risk allocation carried from one iteration to the next.  -> dict(us (S, 2),
     alphas_risk (S,), xs (S+1, 8) [the mean trajectory of us], L2_error per iteration, status per solve, define_s, solve_s)"""
-    return run_driving_gaussian_batch([model], num_scp_iters_max)[0]
+    return run_driving_gaussian_batch([model], num_scp_iters_max, solver)[0]
 
 
 def driving_gaussian_experiment(alphas=(0.01, 0.02, 0.05, 0.1), S=None, iters=60, M_mc=10000, seed=0, results_dir=None,
-                                device='cuda:0'):
+                                device='cuda:0', solver='osqp'):
     """The reference's driving Gaussian baseline (driving_gaussian.py:466-498) and its Monte-Carlo report (driving.py:719-739)
     as one call: the problems of all alphas in lockstep (``run_driving_gaussian_batch``), then ONE ``eval_batch_device`` call of
     a fresh ``driving.Model(M_mc)`` (drawn under ``np.random.seed(seed)``) over the solutions.  Per alpha
     percentage_safe = mean(max_t(-distance) - OSQP_TOL <= 1e-6) with the SAA model's OSQP_TOL, as the block computes it, and
-    monte_carlo_cost.  With ``results_dir``: driving_gaussian_alpha=<alpha>.npy holding (us, xs).
+    monte_carlo_cost.  With ``results_dir``: driving_gaussian_alpha=<alpha>.npy holding (us, xs).  ``solver``: 'osqp' or 'ipm'
+    (``driving_gaussian.Model``).
     -> dict(alphas, results [alpha], us (A, S, 2), Z (A, M_mc) [max_t(-distance) - OSQP_TOL per sample], percentage_safe (A,),
     cost (A,), wall_s)"""
     from . import driving, driving_gaussian
@@ -543,7 +572,7 @@ def driving_gaussian_experiment(alphas=(0.01, 0.02, 0.05, 0.1), S=None, iters=60
     S = P.S if S is None else int(S)
     alphas = [float(a) for a in alphas]
     t0 = time.perf_counter()
-    models = [driving_gaussian.Model(alpha=a, S=S, device=device) for a in alphas]
+    models = [driving_gaussian.Model(alpha=a, S=S, device=device, solver=solver) for a in alphas]
     results = run_driving_gaussian_batch(models, iters)
     wall = time.perf_counter() - t0
     us = np.stack([r["us"] for r in results])
