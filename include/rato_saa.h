@@ -1325,6 +1325,39 @@ int rato_qp_ipm_batch_f64(int32_t K, int32_t n, int32_t m, const double* P, int6
                           double tol, int32_t max_iter, double* z, int64_t stridez, double* y, int64_t stridey,
                           double* info /* [K][8] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Dense Newton-step arithmetic, fp64 (csrc/drone_gaussian_ipm.hip): what the interior-point solve of the drone Gaussian
+ * baseline (riskaversetrajopt_amd/drone_gaussian_ipm.py) does on the values rato_drone_gaussian_linearize /
+ * rato_drone_gaussian_hessian leave on the device.  ABI: additive (RATO_ABI_VERSION stays 12).  K problems per launch, device
+ * pointers, stream ordered, no allocation, no workspace.  No floating-point atomics: every output entry has one owner that
+ * sums in a fixed order, so two calls are bitwise equal and problem k of a batch is bitwise its K = 1 call.
+ *
+ * The kernels are generic.  The constraint matrix J (m x n, m = m0 + m1) is given as two dense row-major row blocks:
+ *   J0 [K][m0][ld0], ld0 >= n, m0 >= 1                    one block per problem
+ *   J1 [m1][ld1] at J1 + k stride1, ld1 >= n, m1 >= 0     stride1 = 0: shared by the batch (m1 = 0: J1 is not read)
+ * Padding columns (>= n) are never read.  Vectors over the rows (d, w, the matvec's out) have length m0 + m1, J0's rows first.
+ *
+ * rato_dense_normal_matrix_f64:  Kc[k] = unpack(hess_tril[k]) + diag(diag[k]) + J' diag(d[k]) J, the lower triangle of a
+ *   row-major n x n array with leading dimension lda >= n (what rato_chol_factor_batch_f64 reads): only entries b <= a < n are
+ *   written, the strict upper triangle and the padding are never touched.  hess_tril [K][n (n + 1) / 2] in np.tril_indices
+ *   order (entry (a, b) at a (a + 1) / 2 + b) or NULL; diag [K][n] or NULL.  Every entry is one accumulator that takes
+ *   (J_ra d_r) J_rb for r ascending, then hess_tril, then diag: the order depends on neither K, nor the tile of
+ *   rato_dense_tile_width() columns the entry falls in, nor n's relation to that width.
+ * rato_dense_matvec_f64:   out[k] = J x[k]  (x [K][ldx >= n], out [K][ldo >= m]); a row is one wave's fixed-order reduction.
+ * rato_dense_tmatvec_f64:  out[k] = J' w[k] (w [K][ldw >= m], out [K][ldo >= n]); one lane per column, rows ascending.
+ * rato_tril_symv_f64:      out[k] = H[k] x[k] for the symmetric H given tril-packed as above.
+ * RATO_EINVAL without a launch on NULL pointers, n < 1 or n > 32768, lda < n, a leading dimension below the length it serves,
+ * m0 < 1, m1 < 0, 0 < stride1 < (m1 - 1) ld1 + n, or K outside [1, 65535]. */
+int rato_dense_tile_width(void);
+int rato_dense_normal_matrix_f64(int32_t K, int32_t n, int64_t lda, const double* J0, int32_t m0, int64_t ld0, const double* J1,
+                                 int32_t m1, int64_t ld1, int64_t stride1, const double* d /* [K][ldd] */, int64_t ldd,
+                                 const double* hess_tril, const double* diag, double* Kc, void* stream);
+int rato_dense_matvec_f64(int32_t K, int32_t n, const double* J0, int32_t m0, int64_t ld0, const double* J1, int32_t m1,
+                          int64_t ld1, int64_t stride1, const double* x, int64_t ldx, double* out, int64_t ldo, void* stream);
+int rato_dense_tmatvec_f64(int32_t K, int32_t n, const double* J0, int32_t m0, int64_t ld0, const double* J1, int32_t m1,
+                           int64_t ld1, int64_t stride1, const double* w, int64_t ldw, double* out, int64_t ldo, void* stream);
+int rato_tril_symv_f64(int32_t K, int32_t n, const double* hess_tril, const double* x, int64_t ldx, double* out, int64_t ldo,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

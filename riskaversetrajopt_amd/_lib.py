@@ -281,6 +281,15 @@ SIGNATURES = {
     "rato_qp_ipm_batch_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_int64, c_float_p,
                                         C.c_int64, C.c_int64, c_float_p, c_float_p, C.c_int64, C.c_double, C.c_int32, c_float_p,
                                         C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_void_p, C.c_size_t, c_stream]),
+    "rato_dense_tile_width": (C.c_int, []),
+    "rato_dense_normal_matrix_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_float_p, C.c_int32, C.c_int64, c_float_p,
+                                               C.c_int32, C.c_int64, C.c_int64, c_float_p, C.c_int64, c_float_p, c_float_p,
+                                               c_float_p, c_stream]),
+    "rato_dense_matvec_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, C.c_int32, C.c_int64, c_float_p, C.c_int32, C.c_int64,
+                                        C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
+    "rato_dense_tmatvec_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, C.c_int32, C.c_int64, c_float_p, C.c_int32, C.c_int64,
+                                         C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
+    "rato_tril_symv_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h

@@ -6,7 +6,10 @@ z = (u (3S), state allocations (S n_obs), obstacle allocations (n_obs)) in the r
 device evaluates the n_nl = 6 + n_obs S + 4 (S+1) non-linear rows; the nvar + 1 linear rows (z itself and the sum of the
 allocations, :323-349) and the objective's constant Hessian are filled once on the host (``ipopt_callbacks``).  The
 reference fixes S as a module constant; here it is the constructor's argument and dt = T / S (as its Model does).
-``scp.run_drone_gaussian`` solves the NLP with scipy's trust-constr on these callbacks.
+``scp.run_drone_gaussian`` solves the NLP with scipy's trust-constr on these callbacks, one alpha after the other through the
+host (``solver='trust-constr'``, the default), or with the batched interior-point method of ``drone_gaussian_ipm``
+(``solver='ipm'``; ``Model.solve``): K problems in lockstep, the Newton step on the device on jac_nl and the packed Hessian where
+these kernels leave them.
 """
 import ctypes as C
 import os
@@ -207,6 +210,14 @@ class Model:
         g_L[6:] = -1e15
         g_L[self.n_nl:], g_U[self.n_nl:] = gs_l, gs_u
         return g_L, g_U
+
+    def solve(self, Z0=None, tol=1e-8, max_iter=3000, backend='device', results_dir='results'):
+        """the NLP by ``drone_gaussian_ipm.solve_batch`` (a batch of one) from ``Z0`` (default: the script's start,
+        ``initial_guess(results_dir)``) -> (Z, info)"""
+        from . import drone_gaussian_ipm
+        (Z, info), = drone_gaussian_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter,
+                                                    backend=backend, results_dir=results_dir)
+        return Z, info
 
     # ---- the script's IPOPT callbacks (:409-498) -----------------------------------------------------------------------------
     def ipopt_callbacks(self, host=None):

@@ -1,0 +1,432 @@
+"""Batched interior-point solve of the drone Gaussian baseline's NLP (drone/drone_gaussian.py:400-534: what the script hands
+to IPOPT), on the driver of ``hopper_ipm`` (``Problem``, ``newton_steps``, ``_solve_group``: DESIGN §7.ad, §7.ae).
+
+Formulation.  The script's g is (the n_nl non-linear rows, z itself, the allocation sum).  The nvar identity rows are bounds on
+z, intersected with x_L / x_U = -+1000:  u in [u_min, u_max], allocations in [1e-6, alpha] -- the same feasible set, and every
+trial point keeps its allocations strictly inside (0, alpha), where ppf(1 - a) exists.  That leaves m = n_nl + 1 rows: 6
+equalities, n_nl - 6 rows bounded above by 0, the sum row in [0, alpha].  f = sum 2 dt R_ii u^2 has a diagonal Hessian, which
+the host folds into the diagonal term of the condensed matrix and adds to W x.
+
+The constraint matrix is dense: J = [jac_nl; the sum row] (m x nvar).  Two backends do the step:
+  'device'  one ``linearize_device`` and one ``hessian_device`` call per iteration for the active problems, then
+            rato_dense_normal_matrix_f64 / rato_chol_factor_batch_f64 / rato_chol_solve_batch_f64 / rato_dense_matvec_f64 /
+            rato_dense_tmatvec_f64 / rato_tril_symv_f64 (csrc/drone_gaussian_ipm.hip, csrc/hopper_ipm.hip) on jac_nl and the
+            packed Hessian where they lie.  Up go the points, the multipliers (K, n_nl), d, the diagonals and the vectors;
+            down come g_nl, the matvec results, the factorization's info and the solutions.  jac_nl, the packed Hessian and
+            Kc / L never leave the device.
+  'numpy'   the whole step on the host on injected (or the model's) callbacks dict(linearize, hessian).
+alpha enters only the host-side bounds, so the problems of one S form a group whatever their alpha.
+"""
+import time
+
+import numpy as np
+
+from . import drone_params as P
+from . import hopper_ipm as _ipm
+
+STATUSES = _ipm.STATUSES
+X_BOUND = 1000.0                                                 # the script's x_L / x_U (:446-447)
+
+
+class Nlp:
+    """what ``hopper_ipm.Problem`` reads of a model: num_vars, gL_gU() on the m = n_nl + 1 rows, x_bounds(), f, grad_f"""
+
+    def __init__(self, model):
+        from . import drone_gaussian as dg
+        self.model, self.S, self.alpha = model, model.S, float(model.alpha)
+        self.num_vars, self.n_nl, self.D = model.nvar, model.n_nl, dg.n_u * model.S
+        self.curv = np.zeros(model.nvar)
+        self.curv[:self.D] = np.tile(4 * model.dt * np.diag(P.R), model.S)          # f = 1/2 sum curv z^2 = sum 2 dt R_ii u^2
+        self.alpha_min = dg.ALPHA_MIN
+
+    def f(self, Z):
+        Z = np.asarray(Z, dtype=np.float64)
+        return 0.5 * float(np.sum(self.curv * Z * Z))
+
+    def grad_f(self, Z):
+        return self.curv * np.asarray(Z, dtype=np.float64)
+
+    def gL_gU(self):
+        gL = np.concatenate([np.zeros(6), np.full(self.n_nl - 6, -1e15), [0.0]])
+        gU = np.concatenate([np.zeros(self.n_nl), [self.alpha]])
+        return gL, gU
+
+    def x_bounds(self):
+        n, D = self.num_vars, self.D
+        lo = np.concatenate([np.full(D, float(self.model.u_min)), np.full(n - D, self.alpha_min)])
+        hi = np.concatenate([np.full(D, float(self.model.u_max)), np.full(n - D, self.alpha)])
+        return np.maximum(lo, -X_BOUND), np.minimum(hi, X_BOUND)
+
+    def g(self, Z, g_nl):
+        return np.concatenate([g_nl, [np.sum(np.asarray(Z)[self.D:])]])
+
+    def sum_row(self):
+        return np.concatenate([np.zeros(self.D), np.ones(self.num_vars - self.D)])
+
+
+def unpack_tril(tril, n):
+    r, c = np.tril_indices(n)
+    H = np.zeros((n, n))
+    H[r, c] = tril
+    H[c, r] = tril
+    return H
+
+
+def normal_matrix_host(J, d, hess_tril=None, diag=None):
+    """the NumPy twin of rato_dense_normal_matrix_f64: unpack(hess_tril) + diag(diag) + J' diag(d) J, J (m, n) -> (n, n)"""
+    J = np.asarray(J, dtype=np.float64)
+    Kc = (J.T * np.asarray(d, dtype=np.float64)) @ J             # the factorization reads the lower triangle alone
+    if hess_tril is not None:
+        Kc = Kc + unpack_tril(hess_tril, J.shape[1])
+    if diag is not None:
+        Kc = Kc + np.diag(np.asarray(diag, dtype=np.float64))
+    return Kc
+
+
+# ---- backends ----------------------------------------------------------------------------------------------------------------
+def _new_clock():
+    return dict(callbacks=0.0, normal=0.0, factor=0.0, solve=0.0, matvec=0.0)
+
+
+class NumpyBackend:
+    """the whole step on the host.  ``callbacks[i]`` serves nlps[i]: dict(linearize(Z) -> (g_nl, jac_nl), hessian(Z, lam) -> tril)"""
+    name = "numpy"
+
+    def __init__(self, nlps, callbacks=None):
+        self.nlps = nlps
+        self.cb = [p.model.device_callbacks() for p in nlps] if callbacks is None else list(callbacks)
+        self.st = None
+        self.J, self.hess, self.sf, self.L = {}, {}, {}, {}
+        self.clock = _new_clock()
+
+    def eval_full(self, idx, Zs, lams, sfs):
+        t0 = time.perf_counter()
+        out = []
+        for i, Z, lam, sf in zip(idx, Zs, lams, sfs):
+            nlp = self.nlps[i]
+            g_nl, jac_nl = self.cb[i]["linearize"](np.asarray(Z, dtype=np.float64))
+            self.J[i] = np.vstack([np.asarray(jac_nl, dtype=np.float64), nlp.sum_row()[None, :]])
+            self.hess[i] = np.asarray(self.cb[i]["hessian"](np.asarray(Z, dtype=np.float64),
+                                                            np.asarray(lam, dtype=np.float64)[:nlp.n_nl]), dtype=np.float64)
+            self.sf[i] = float(sf)
+            out.append(nlp.g(Z, np.asarray(g_nl, dtype=np.float64)))
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def eval_g(self, idx, Zs):
+        t0 = time.perf_counter()
+        out = [self.nlps[i].g(Z, np.asarray(self.cb[i]["linearize"](np.asarray(Z, dtype=np.float64))[0], dtype=np.float64))
+               for i, Z in zip(idx, Zs)]
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def set_values(self, J, hess, sfs):
+        """install dense J (K, m, n), packed Hessians (K, n (n + 1) / 2) and objective scales as the current evaluation of
+        problems 0 .. K-1 (what eval_full leaves)"""
+        for i, (j, h, sf) in enumerate(zip(J, hess, sfs)):
+            self.J[i], self.hess[i], self.sf[i] = np.asarray(j, dtype=np.float64), np.asarray(h, dtype=np.float64), float(sf)
+
+    def hess_apply(self, idx, X):
+        return [unpack_tril(self.hess[i], x.size) @ x + self.sf[i] * self.nlps[i].curv * x for i, x in zip(idx, X)]
+
+    def matvec(self, idx, X):
+        t0 = time.perf_counter()
+        out = [self.J[i] @ x for i, x in zip(idx, X)]
+        self.clock["matvec"] += time.perf_counter() - t0
+        return out
+
+    def tmatvec(self, idx, W):
+        t0 = time.perf_counter()
+        out = [self.J[i].T @ w for i, w in zip(idx, W)]
+        self.clock["matvec"] += time.perf_counter() - t0
+        return out
+
+    def factor(self, idx, D, diags):
+        info = []
+        for i, d, dg in zip(idx, D, diags):
+            t0 = time.perf_counter()
+            Kc = normal_matrix_host(self.J[i], d, self.hess[i], dg + self.sf[i] * self.nlps[i].curv)
+            t1 = time.perf_counter()
+            ok = bool(np.all(np.isfinite(Kc)))
+            if ok:
+                try:
+                    self.L[i] = np.linalg.cholesky(Kc)
+                except np.linalg.LinAlgError:
+                    ok = False
+            self.clock["normal"] += t1 - t0
+            self.clock["factor"] += time.perf_counter() - t1
+            info.append(0 if ok else 1)
+        return info
+
+    def solve(self, idx, B):
+        from scipy.linalg import solve_triangular
+        t0 = time.perf_counter()
+        out = [solve_triangular(self.L[i], solve_triangular(self.L[i], b, lower=True), lower=True, trans='T')
+               for i, b in zip(idx, B)]
+        self.clock["solve"] += time.perf_counter() - t0
+        return out
+
+
+def _check(t, name, dims=None):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or \
+            (dims is not None and t.dim() != dims):
+        raise ValueError(f"{name} must be a contiguous device float64 tensor" + (f" of {dims} dimensions" if dims else ""))
+    return t
+
+
+def dense_tile_width():
+    from . import _lib
+    return int(_lib.load().rato_dense_tile_width())
+
+
+def _blocks(J0, J1, n):
+    """the two row blocks as the ABI takes them: J0 (K, m0, ld0), J1 None | (m1, ld1) shared | (K, m1, ld1) per problem"""
+    from . import _lib
+    _check(J0, "J0", 3)
+    K, m0, ld0 = J0.shape
+    if J1 is None:
+        return K, (_lib.ptr(J0), m0, ld0, None, 0, n, 0), m0
+    _check(J1, "J1")
+    if J1.dim() == 2:
+        m1, ld1, stride1 = J1.shape[0], J1.shape[1], 0
+    elif J1.dim() == 3 and J1.shape[0] == K:
+        m1, ld1, stride1 = J1.shape[1], J1.shape[2], J1.shape[1] * J1.shape[2]
+    else:
+        raise ValueError("J1 must be (m1, ld1) or (K, m1, ld1)")
+    return K, (_lib.ptr(J0), m0, ld0, _lib.ptr(J1) if m1 else None, m1, ld1, stride1), m0 + m1
+
+
+def dense_normal_matrix(n, J0, J1, d, hess_tril=None, diag=None, out=None):
+    """rato_dense_normal_matrix_f64 on device fp64 tensors: J0 (K, m0, ld0 >= n), J1 as ``_blocks`` takes it, d (K, ldd >= m),
+    hess_tril (K, n (n + 1) / 2) or None, diag (K, n) or None -> Kc (K, n, lda) (``out``, or a fresh (K, n, n) tensor whose strict
+    upper triangle is not written)"""
+    import torch
+    from . import _lib
+    K, blk, m = _blocks(J0, J1, n)
+    _check(d, "d", 2)
+    if hess_tril is not None and tuple(_check(hess_tril, "hess_tril", 2).shape) != (K, n * (n + 1) // 2):
+        raise ValueError("hess_tril must be (K, n (n + 1) / 2)")
+    if diag is not None and tuple(_check(diag, "diag", 2).shape) != (K, n):
+        raise ValueError("diag must be (K, n)")
+    Kc = torch.empty((K, n, n), dtype=torch.float64, device=J0.device) if out is None else _check(out, "out", 3)
+    if d.shape[0] != K or tuple(Kc.shape[:2]) != (K, n):
+        raise ValueError("d must be (K, ldd) and out (K, n, lda)")
+    with torch.cuda.device(J0.device):
+        _lib.check(_lib.load().rato_dense_normal_matrix_f64(K, n, Kc.shape[2], *blk, _lib.ptr(d), d.shape[1], _lib.ptr(hess_tril),
+                                                            _lib.ptr(diag), _lib.ptr(Kc), _lib.current_stream()),
+                   "rato_dense_normal_matrix_f64")
+    return Kc
+
+
+def _mv(name, n, J0, J1, x, n_out_of):
+    import torch
+    from . import _lib
+    K, blk, m = _blocks(J0, J1, n)
+    _check(x, "x", 2)
+    if x.shape[0] != K:
+        raise ValueError("the vector must be (K, ld)")
+    out = torch.empty((K, n_out_of(m)), dtype=torch.float64, device=J0.device)
+    with torch.cuda.device(J0.device):
+        _lib.check(getattr(_lib.load(), name)(K, n, *blk, _lib.ptr(x), x.shape[1], _lib.ptr(out), out.shape[1],
+                                              _lib.current_stream()), name)
+    return out
+
+
+def dense_matvec(n, J0, J1, x):
+    """rato_dense_matvec_f64: x (K, ldx >= n) -> J x (K, m)"""
+    return _mv("rato_dense_matvec_f64", n, J0, J1, x, lambda m: m)
+
+
+def dense_tmatvec(n, J0, J1, w):
+    """rato_dense_tmatvec_f64: w (K, ldw >= m) -> J' w (K, n)"""
+    return _mv("rato_dense_tmatvec_f64", n, J0, J1, w, lambda m: n)
+
+
+def tril_symv(n, hess_tril, x):
+    """rato_tril_symv_f64: hess_tril (K, n (n + 1) / 2), x (K, ldx >= n) -> H x (K, n)"""
+    import torch
+    from . import _lib
+    _check(hess_tril, "hess_tril", 2), _check(x, "x", 2)
+    K = x.shape[0]
+    if tuple(hess_tril.shape) != (K, n * (n + 1) // 2):
+        raise ValueError("hess_tril must be (K, n (n + 1) / 2)")
+    out = torch.empty((K, n), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rato_tril_symv_f64(K, n, _lib.ptr(hess_tril), _lib.ptr(x), x.shape[1], _lib.ptr(out), n,
+                                                  _lib.current_stream()), "rato_tril_symv_f64")
+    return out
+
+
+class DeviceBackend:
+    """the step on the MI355X for the problems of one group (same S; alpha may differ).  Every call serves the listed problems
+    in ONE launch each; nothing a kernel computes for a problem depends on the others."""
+    name = "device"
+
+    def __init__(self, nlps):
+        import torch
+        self.torch = torch
+        self.nlps = nlps
+        self.m0 = nlps[0].model
+        self.m0._handle()
+        self.dev = self.m0.device
+        self.n, self.n_nl = nlps[0].num_vars, nlps[0].n_nl
+        self.st = None
+        self.sum_row = torch.as_tensor(nlps[0].sum_row()[None, :].copy(), device=self.dev)
+        self.slot, self.sf = {}, {}
+        self.jac = self.hess = self.L = None
+        self.clock = _new_clock()
+
+    def _sync(self):
+        self.torch.cuda.synchronize(self.dev)
+
+    def _up(self, rows):
+        return self.torch.as_tensor(np.ascontiguousarray(np.stack(rows), dtype=np.float64), device=self.dev)
+
+    def _g(self, idx, Zs, g_nl):
+        g_nl = g_nl.cpu().numpy()
+        return [self.nlps[i].g(Z, g_nl[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
+
+    def eval_full(self, idx, Zs, lams, sfs):
+        t0 = time.perf_counter()
+        with self.torch.cuda.device(self.dev):
+            Zd = self._up(Zs)
+            r = self.m0.linearize_device(Zd)
+            self.hess = self.m0.hessian_device(Zd, self._up([np.asarray(l)[:self.n_nl] for l in lams]))
+        self.jac = r["jac_nl"]
+        self.slot = {i: k for k, i in enumerate(idx)}
+        for i, sf in zip(idx, sfs):
+            self.sf[i] = float(sf)
+        out = self._g(idx, Zs, r["g_nl"])
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def eval_g(self, idx, Zs):
+        t0 = time.perf_counter()
+        with self.torch.cuda.device(self.dev):
+            out = self._g(idx, Zs, self.m0.linearize_device(self._up(Zs))["g_nl"])
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def set_values(self, J, hess, sfs):
+        """install dense J (K, m, n) (its last row is the sum row), packed Hessians (K, n (n + 1) / 2) and objective scales as
+        the current evaluation of problems 0 .. K-1 (what eval_full leaves)"""
+        J = np.asarray(J, dtype=np.float64)
+        self.jac, self.hess = self._up(list(J[:, :self.n_nl])), self._up(list(hess))
+        self.slot = {i: i for i in range(J.shape[0])}
+        self.sf = {i: float(sf) for i, sf in enumerate(sfs)}
+
+    def _sel(self, idx):
+        """the value arrays of the listed problems, in place when they are all of them in order"""
+        rows = [self.slot[i] for i in idx]
+        if rows == list(range(self.jac.shape[0])):
+            return self.jac, self.hess
+        sel = self.torch.as_tensor(rows, device=self.dev)
+        return self.jac.index_select(0, sel).contiguous(), self.hess.index_select(0, sel).contiguous()
+
+    def hess_apply(self, idx, X):
+        t0 = time.perf_counter()
+        out = tril_symv(self.n, self._sel(idx)[1], self._up(X)).cpu().numpy()
+        self.clock["matvec"] += time.perf_counter() - t0
+        return [o + self.sf[i] * self.nlps[i].curv * x for i, o, x in zip(idx, out, X)]
+
+    def matvec(self, idx, X):
+        t0 = time.perf_counter()
+        out = list(dense_matvec(self.n, self._sel(idx)[0], self.sum_row, self._up(X)).cpu().numpy())
+        self.clock["matvec"] += time.perf_counter() - t0
+        return out
+
+    def tmatvec(self, idx, W):
+        t0 = time.perf_counter()
+        out = list(dense_tmatvec(self.n, self._sel(idx)[0], self.sum_row, self._up(W)).cpu().numpy())
+        self.clock["matvec"] += time.perf_counter() - t0
+        return out
+
+    def normal_matrix(self, idx, D, diags, out=None):
+        """-> Kc (K, n, lda) device tensor, the objective's curvature folded into the diagonal"""
+        jac, hess = self._sel(idx)
+        dg = self._up([g + self.sf[i] * self.nlps[i].curv for i, g in zip(idx, diags)])
+        return dense_normal_matrix(self.n, jac, self.sum_row, self._up(D), hess, dg, out=out)
+
+    def factor(self, idx, D, diags):
+        torch = self.torch
+        t0 = time.perf_counter()
+        Kc = self.normal_matrix(idx, D, diags)
+        self._sync()
+        t1 = time.perf_counter()
+        info = _ipm.chol_factor(Kc)
+        if self.L is None:
+            self.L = torch.empty((len(self.nlps),) + tuple(Kc.shape[1:]), dtype=torch.float64, device=self.dev)
+        self.L[torch.as_tensor(list(idx), device=self.dev)] = Kc
+        info = info.cpu().numpy()
+        self.clock["normal"] += t1 - t0
+        self.clock["factor"] += time.perf_counter() - t1
+        return [int(v) for v in info]
+
+    def solve(self, idx, B):
+        t0 = time.perf_counter()
+        L = self.L.index_select(0, self.torch.as_tensor(list(idx), device=self.dev))
+        b = self._up(B)[:, None, :].contiguous()
+        _ipm.chol_solve(L, b)
+        out = list(b[:, 0].cpu().numpy())
+        self.clock["solve"] += time.perf_counter() - t0
+        return out
+
+
+# ---- the solve -------------------------------------------------------------------------------------------------------------
+def lagrange(nlp, info):
+    """the multipliers in the script's row order (ncon): the non-linear rows' y, zu_j - zl_j for the identity row j, the sum
+    row's y.  With J_script = ``ipopt_callbacks()``'s Jacobian: sf grad f + J_script' lagrange is the dual residual."""
+    n, n_nl = nlp.num_vars, nlp.n_nl
+    return np.concatenate([info["y"][:n_nl], info["zu"][:n] - info["zl"][:n], info["y"][n_nl:]])
+
+
+def make_backend(nlps, backend, callbacks=None):
+    return DeviceBackend(nlps) if backend == 'device' else NumpyBackend(nlps, callbacks)
+
+
+def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
+                results_dir='results'):
+    """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  Models of one S form a group that moves
+    through the K-problem kernels together (alpha may differ inside it: it enters only the host-side bounds), the groups one
+    after the other.  A problem that has ended leaves the launches, a failed factorization is redone for the failed problems
+    alone, and a problem's Z is bitwise what its own K = 1 run returns.
+      Z0s        starting points (default: ``model.initial_guess(results_dir)``, the script's)
+      backend    'device' (csrc/drone_gaussian_ipm.hip) or 'numpy' (the step on the host)
+      callbacks  backend='numpy' only: one dict(linearize, hessian) per model, as ``run_drone_gaussian(callbacks=...)`` takes
+      clocks     a dict that receives the seconds spent in callbacks / normal / factor / solve / matvec, the wall clock and
+                 host = the rest (the driver's vector algebra and line-search bookkeeping)
+    info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
+    dual_infeasibility, f, mu, sf (the objective scale), the final multipliers y (m = n_nl + 1), zl, zu (nvar + the slacks), the
+    slacks s, and lagrange (ncon) in the script's row order."""
+    if backend not in ('device', 'numpy'):
+        raise ValueError(f"backend must be 'device' or 'numpy', got {backend!r}")
+    if callbacks is not None and backend != 'numpy':
+        raise ValueError("callbacks are the numpy backend's")
+    models = list(models)
+    if callbacks is not None and len(callbacks) != len(models):
+        raise ValueError("callbacks must hold one dict(linearize, hessian) per model")
+    Z0s = [m.initial_guess(results_dir) for m in models] if Z0s is None else [np.asarray(Z, dtype=np.float64) for Z in Z0s]
+    if len(Z0s) != len(models) or any(Z.shape != (m.nvar,) for Z, m in zip(Z0s, models)):
+        raise ValueError("Z0s must hold one (nvar,) vector per model")
+    groups = {}
+    for i, m in enumerate(models):
+        groups.setdefault((m.S, str(m.device)) if backend == 'device' else (m.S,), []).append(i)
+    out = [None] * len(models)
+    t0 = time.perf_counter()
+    spent = 0.0
+    for members in groups.values():
+        nlps = [Nlp(models[i]) for i in members]
+        be = make_backend(nlps, backend, None if callbacks is None else [callbacks[i] for i in members])
+        for i, nlp, (Z, info) in zip(members, nlps, _ipm._solve_group(nlps, [Z0s[i] for i in members], tol, max_iter, be, verbose)):
+            info["lagrange"] = lagrange(nlp, info)
+            out[i] = (Z, info)
+        if clocks is not None:
+            for k, v in be.clock.items():
+                clocks[k] = clocks.get(k, 0.0) + v
+                spent += v
+    if clocks is not None:
+        wall = time.perf_counter() - t0
+        clocks["wall"] = clocks.get("wall", 0.0) + wall
+        clocks["host"] = clocks.get("host", 0.0) + wall - spent
+    return out

@@ -20,6 +20,10 @@ rato_chol_solve_batch_f64, rato_csc_matvec_f64 / rato_csc_tmatvec_f64 on the val
 problems per launch) and 'numpy' (the whole step on the host, callbacks injected or taken one problem at a time from the
 Model): the driver, the line search and the O(n + m) vector algebra are shared and run on the host per problem, so a problem's
 iterates do not depend on what else is in the batch.
+
+The driver (``Problem``, ``newton_steps``, ``_solve_group``) knows a model through num_vars, gL_gU(), x_bounds(), f, grad_f and a
+backend through eval_full / eval_g / matvec / tmatvec / factor / solve / hess_apply(idx, X) -> [W x]: ``drone_gaussian_ipm`` runs
+it on dense backends of its own.
 """
 import time
 
@@ -185,6 +189,9 @@ class NumpyBackend:
     def hess_blocks(self, i):
         return self.hess[i]
 
+    def hess_apply(self, idx, X):
+        return [_hess_apply(self.st, self.hess[i], x) for i, x in zip(idx, X)]
+
     def matvec(self, idx, X):
         st = self.st
         return [np.bincount(st["rows"], weights=self.vals[i] * x[st["cols"]], minlength=st["ncon"]) for i, x in zip(idx, X)]
@@ -303,6 +310,9 @@ class DeviceBackend:
 
     def hess_blocks(self, i):
         return self.hess_host[self.slot[i]]
+
+    def hess_apply(self, idx, X):
+        return [_hess_apply(self.st, self.hess_host[self.slot[i]], x) for i, x in zip(idx, X)]
 
     def _sel(self, idx):
         """the value arrays of the listed problems, in place when they are all of them in order"""
@@ -502,7 +512,6 @@ class Problem:
 def newton_steps(be, idx, ps, refine=2):
     """the condensed Newton step of the listed problems (``Problem.prepare_step`` done) on backend ``be``: fills p.dv (n + nI)
     and p.dy (m).  A failed factorization is redone with the next delta_w; returns False for a problem where none succeeded."""
-    st = be.st
     JTw = be.tmatvec(idx, [p.w for p in ps])
     for p, t in zip(ps, JTw):
         p.rhs = -(p.rz + t)
@@ -545,7 +554,8 @@ def newton_steps(be, idx, ps, refine=2):
             q[p.E] = p.dyE - p.r2 / p.dc
             Q.append(q)
         JTq = be.tmatvec(gi, Q)
-        R = [-(p.rz + _hess_apply(st, be.hess_blocks(i), p.dz) + (p.Sigma[:p.n] + p.dw) * p.dz + t) for i, p, t in zip(gi, gp, JTq)]
+        Wdz = be.hess_apply(gi, [p.dz for p in gp])
+        R = [-(p.rz + h + (p.Sigma[:p.n] + p.dw) * p.dz + t) for p, h, t in zip(gp, Wdz, JTq)]
         ez = be.solve(gi, R)
         Jez = be.matvec(gi, ez)
         for p, e, je in zip(gp, ez, Jez):
@@ -616,6 +626,8 @@ def _solve_group(models, Z0s, tol, max_iter, be, verbose):
         idx, act = [i for i, _ in pairs], [p for _, p in pairs]
         ok = newton_steps(be, idx, act)
         search = []
+        gi = [i for i, good in zip(idx, ok) if good]
+        Wdv = dict(zip(gi, be.hess_apply(gi, [p.dv[:p.n] for p, good in zip(act, ok) if good]))) if gi else {}
         for i, p, good in zip(idx, act, ok):
             if not good:
                 p.done, p.status = True, "line_search"
@@ -631,7 +643,7 @@ def _solve_group(models, Z0s, tol, max_iter, be, verbose):
             p.a_dual = min(_max_step(p.zl, p.dzl, p.hasL, tau), _max_step(p.zu, p.dzu, p.hasU, tau))
             c1 = float(np.sum(np.abs(p.c)))
             Dbar = float(p.gradf @ dv[:n] + p.gbar @ dv)
-            quad = float(dv[:n] @ _hess_apply(be.st, be.hess_blocks(i), dv[:n]) + np.sum(p.Sigma * dv * dv) + p.dw * (dv[:n] @ dv[:n]))
+            quad = float(dv[:n] @ Wdv[i] + np.sum(p.Sigma * dv * dv) + p.dw * (dv[:n] @ dv[:n]))
             if c1 > 0.0:
                 nu_trial = (Dbar + 0.5 * max(quad, 0.0)) / (0.9 * c1)
                 if p.nu < nu_trial:

@@ -589,7 +589,19 @@ def driving_gaussian_experiment(alphas=(0.01, 0.02, 0.05, 0.1), S=None, iters=60
     return out
 
 
-def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir='results'):
+def _drone_gaussian_ipm_result(model, Z, info, trajectory, callback_s, total_s):
+    """the ``run_drone_gaussian`` dictionary of one ``drone_gaussian_ipm.solve_batch`` result"""
+    D = 3 * model.S
+    xs, Sigmas = trajectory(Z)
+    return {"Z": Z, "us": model.convert_us_vec_to_us_mat(Z[:D]), "alphas_risk": Z[D:].copy(), "xs": xs, "Sigmas": Sigmas,
+            "status": info["status"], "message": "interior point: " + info["status"], "nit": int(info["iterations"]),
+            "nfev": int(info["factorizations"]), "constr_violation": float(info["primal_infeasibility"]),
+            "optimality": float(info["dual_infeasibility"]), "fun": float(info["f"]), "callback_s": float(callback_s),
+            "total_s": float(total_s), "info": info}
+
+
+def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir='results', solver='trust-constr', tol=1e-8,
+                       backend=None):
     """The NLP of drone_gaussian.py:400-534 solved with ``scipy.optimize.minimize(method='trust-constr')`` -- the installed
     solver that takes the Hessian of lam . g, which is the script's ``hess_lagrange_dot_g``: the non-linear rows as a
     ``NonlinearConstraint(g, gL, gU, jac, hess)`` (6 equalities, the rest one-sided), the box on u and on the allocations as
@@ -599,7 +611,24 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
     the same point share one launch.  ``Z0``: the start, by default the script's (the SAA repeat-0 controls of
     ``results_dir`` and the uniform allocation).
     -> dict(Z, us (S, 3), alphas_risk, xs (S+1, 6), Sigmas (S+1, 6, 6), status, message, nit, nfev, constr_violation,
-    optimality, fun, callback_s, total_s)"""
+    optimality, fun, callback_s, total_s)
+    ``solver='ipm'``: the same NLP by ``drone_gaussian_ipm.solve_batch`` (a batch of one; ``backend`` 'device', or
+    'numpy', the default when ``callbacks`` are given; ``tol``: its E_0 tolerance) -> the same keys with status one of
+    'converged' | 'max_iter' | 'line_search', nit = iterations, nfev = factorizations, constr_violation / optimality = the
+    primal / dual parts of the final E_0, and ``info`` (``solve_batch``'s, with the multipliers)."""
+    if solver not in ('trust-constr', 'ipm'):
+        raise ValueError(f"solver must be 'trust-constr' or 'ipm', got {solver!r}")
+    if solver == 'ipm':
+        from . import drone_gaussian_ipm
+        backend = ('device' if callbacks is None else 'numpy') if backend is None else backend
+        Z0 = model.initial_guess(results_dir) if Z0 is None else np.asarray(Z0, dtype=np.float64)
+        clocks = {}
+        t0 = time.perf_counter()
+        (Z, info), = drone_gaussian_ipm.solve_batch([model], [Z0], tol=tol, max_iter=int(maxiter), backend=backend,
+                                                    callbacks=None if callbacks is None else [callbacks], clocks=clocks)
+        total = time.perf_counter() - t0
+        trajectory = (model.device_callbacks() if callbacks is None else callbacks)["trajectory"]
+        return _drone_gaussian_ipm_result(model, Z, info, trajectory, clocks["callbacks"], total)
     from scipy.optimize import Bounds, LinearConstraint, NonlinearConstraint, minimize
     from . import drone_params as P
     cb = model.device_callbacks() if callbacks is None else callbacks
@@ -650,11 +679,12 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
 
 
 def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='results', M_mc=10000, seed=0, maxiter=3000,
-                              saa_iters=60, saa_M=50, device='cuda:0'):
+                              saa_iters=60, saa_M=50, device='cuda:0', solver='trust-constr', tol=1e-8, clocks=None):
     """The reference's drone Gaussian baseline (drone_gaussian.py:400-534) and the third block of the drone Monte-Carlo report
     (drone_risk.py:742-761) as one call.  The start of every alpha is the SAA repeat-0 solution
     ``results_dir``/drone_alpha=<alpha>_repeat=0.npy, read where it exists and made by ``drone_saa_experiment`` (one repeat)
-    where it does not; each alpha is solved by ``run_drone_gaussian`` and written to drone_gaussian_alpha=<alpha>.npy as
+    where it does not; each alpha is solved by ``run_drone_gaussian`` (``solver='ipm'``: all alphas in ONE
+    ``drone_gaussian_ipm.solve_batch`` call on the device, whose clocks ``clocks`` receives) and written to drone_gaussian_alpha=<alpha>.npy as
     (us, xs); then ONE ``eval_batch_device`` call of a fresh ``drone_risk.Model`` of M_mc samples (drawn under
     ``np.random.seed(seed)``) over the solutions.  Per alpha percentage_safe = mean(max constraint <= 1e-6), as the block
     computes it, and monte_carlo_cost.
@@ -670,11 +700,24 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
         drone_saa_experiment(alphas=missing, num_repeats=1, M=saa_M, S=S, iters=saa_iters, seed=seed, results_dir=results_dir,
                              device=device)
     t0 = time.perf_counter()
+    if solver not in ('trust-constr', 'ipm'):
+        raise ValueError(f"solver must be 'trust-constr' or 'ipm', got {solver!r}")
     results = []
-    for a in alphas:
-        model = drone_gaussian.Model(S, alpha=a, device=device)
-        results.append(run_drone_gaussian(model, maxiter=maxiter, results_dir=results_dir))
-        save_results(os.path.join(results_dir, f"drone_gaussian_alpha={a}.npy"), results[-1]["us"], results[-1]["xs"])
+    if solver == 'ipm':
+        from . import drone_gaussian_ipm
+        models = [drone_gaussian.Model(S, alpha=a, device=device) for a in alphas]
+        ck = {} if clocks is None else clocks
+        sols = drone_gaussian_ipm.solve_batch(models, tol=tol, max_iter=int(maxiter), backend='device', clocks=ck,
+                                              results_dir=results_dir)
+        for m, (Z, info) in zip(models, sols):
+            results.append(_drone_gaussian_ipm_result(m, Z, info, m.device_callbacks()["trajectory"],
+                                                      ck["callbacks"] / len(models), ck["wall"] / len(models)))
+    else:
+        for a in alphas:
+            model = drone_gaussian.Model(S, alpha=a, device=device)
+            results.append(run_drone_gaussian(model, maxiter=maxiter, results_dir=results_dir))
+    for a, r in zip(alphas, results):
+        save_results(os.path.join(results_dir, f"drone_gaussian_alpha={a}.npy"), r["us"], r["xs"])
     wall = time.perf_counter() - t0
     us = np.stack([r["us"] for r in results])
     np.random.seed(seed)

@@ -1,0 +1,247 @@
+"""GPU: the dense kernels of csrc/drone_gaussian_ipm.hip on designed buffers, one Newton step and the whole solve of
+``drone_gaussian_ipm``'s device backend.
+
+Bounds.  Any order of summing k terms t_i in fp64 (sequential, a tree, with or without fused multiply-adds) has
+|computed - exact| <= gamma_k sum |t_i|, gamma_k = k u / (1 - k u), u = 2^-53 (Higham, Accuracy and Stability of Numerical
+Algorithms, §3.1, §4.2).  A normal-matrix entry sums m products of three factors (one extra rounding: J_ra d_r), the packed
+Hessian and the diagonal: gamma_(m+3) sum |terms|.  A matvec entry sums len products: gamma_(len+1) sum |terms|.  The left
+sides are evaluated in np.longdouble.
+
+Measured on an MI355X, the figures the two gates below are set from:
+  one Newton step, relative residual in the uncondensed KKT system, NumPy / device backend:
+      S = 2: 1.9e-14 / 1.4e-14     S = 5: 1.3e-14 / 1.1e-14     (gate: device <= 100 x NumPy)
+  end to end, |f_device - f_numpy| at alphas (0.05, 0.3) of S = 3 and (0.1, 0.3) of S = 5: 4.4e-16, 0, 4.4e-16, 0
+      (gate: 10 x the largest, floored at 1e-12)"""
+import numpy as np
+import pytest
+
+import _drone_gaussian as R
+import _drone_gaussian_ipm as T
+
+pytestmark = pytest.mark.gpu
+LD = np.longdouble
+DEV = "cuda:0"
+K = 3
+F_GAP_MEASURED = 4.441e-16                                       # the largest of the four measured gaps above
+F_GATE = max(10.0 * F_GAP_MEASURED, 1e-12)
+
+
+def ipm():
+    from riskaversetrajopt_amd import drone_gaussian_ipm
+    return drone_gaussian_ipm
+
+
+def TW():
+    return ipm().dense_tile_width()
+
+
+M1_MODES = [(0, False), (1, False), (3, False), (1, True), (3, True)]   # (m1, per problem)
+
+
+def kernel_cases():
+    """(n, m0, m1, per_problem, pad, with_hess): every small n with every m1 form, padding and Hessian form; the two large
+    shapes (the drone's nvar at S = 20 and S = 64) with the m1 forms in turn.  T = 32 is asserted against the kernel's."""
+    t = 32
+    out = []
+    for n, m0 in ((1, 1), (2, 7), (t - 1, 7), (t, 1), (t + 1, 274), (2 * t + 1, 7)):
+        for m1, per in M1_MODES:
+            for pad in (0, 3):
+                for with_hess in (True, False):
+                    out.append((n, m0, m1, per, pad, with_hess))
+    for i, (m1, per) in enumerate(M1_MODES):
+        out.append((123, 274, m1, per, 3 * (i % 2), i % 2 == 0))
+    out.append((387, 458, 1, False, 0, True))
+    out.append((387, 458, 1, False, 3, False))
+    return out
+
+
+def up(a):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=DEV)
+
+
+def device_buffers(des, n, pad):
+    """the designed values in padded device buffers, NaN in every padding column"""
+    J1 = None if des["J1"] is None else up(T.padded(des["J1"], n + pad))
+    return dict(J0=up(T.padded(des["J0"], n + pad)), J1=J1, d=up(T.padded(des["d"], des["m"] + pad)), hess=up(des["hess"]),
+                diag=up(des["diag"]), x=up(T.padded(des["x"], n + pad)), w=up(T.padded(des["w"], des["m"] + pad)))
+
+
+def one(b, k, per):
+    """problem k alone"""
+    sl = lambda t: None if t is None else t[k:k + 1].contiguous()
+    return dict(J0=sl(b["J0"]), J1=sl(b["J1"]) if per else b["J1"], d=sl(b["d"]), hess=sl(b["hess"]), diag=sl(b["diag"]),
+                x=sl(b["x"]), w=sl(b["w"]))
+
+
+def same(a, b):
+    return a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("n,m0,m1,per,pad,with_hess", kernel_cases())
+def test_dense_normal_matrix(n, m0, m1, per, pad, with_hess):
+    import torch
+    m = ipm()
+    assert TW() == 32
+    des = T.designed(n, m0, m1, per)
+    b = device_buffers(des, n, pad)
+    run = lambda q, out: m.dense_normal_matrix(n, q["J0"], q["J1"], q["d"], q["hess"] if with_hess else None, q["diag"], out=out)
+    sentinel = lambda k: torch.full((k, n, n + pad), float("nan"), dtype=torch.float64, device=DEV)
+    Kc = run(b, sentinel(K))
+    assert same(Kc, run(b, sentinel(K)))                                  # two runs
+    got = Kc.cpu().numpy()
+    r, c = np.tril_indices(n)
+    ur, uc = np.triu_indices(n, 1)
+    assert np.all(np.isnan(got[:, ur, uc])) and np.all(np.isnan(got[:, :, n:])), "sentinels outside b <= a < n were written"
+    assert not np.any(np.isnan(got[:, r, c]))
+    for k in range(K):
+        ref, bound = T.normal_reference(n, m0, m1, per, k, with_hess)
+        err = np.abs(got[k][:, :n].astype(LD) - ref)[r, c]
+        assert np.all(err <= bound[r, c]), (k, float(np.max(err / bound[r, c])))
+        assert same(run(one(b, k, per), sentinel(1))[0], Kc[k]), f"problem {k} differs from its K = 1 launch"
+
+
+@pytest.mark.parametrize("n,m0,m1,per,pad,with_hess", [c for c in kernel_cases() if c[5]])
+def test_matvec_tmatvec_symv(n, m0, m1, per, pad, with_hess):
+    m = ipm()
+    des = T.designed(n, m0, m1, per)
+    b = device_buffers(des, n, pad)
+    mm = des["m"]
+    calls = dict(matvec=lambda q: m.dense_matvec(n, q["J0"], q["J1"], q["x"]),
+                 tmatvec=lambda q: m.dense_tmatvec(n, q["J0"], q["J1"], q["w"]),
+                 symv=lambda q: m.tril_symv(n, q["hess"], q["x"]))
+    for name, call in calls.items():
+        out = call(b)
+        assert same(out, call(b)), name
+        got = out.cpu().numpy()
+        assert got.shape == (K, mm if name == "matvec" else n) and not np.any(np.isnan(got)), name
+        for k in range(K):
+            Jl = des["J"][k].astype(LD)
+            if name == "matvec":
+                A, v = Jl, des["x"][k].astype(LD)
+            elif name == "tmatvec":
+                A, v = Jl.T, des["w"][k].astype(LD)
+            else:
+                A, v = T.unpack(des["hess"][k].astype(LD), n), des["x"][k].astype(LD)
+            ref, bound = A @ v, T.gamma(A.shape[1] + 1) * (np.abs(A) @ np.abs(v))
+            err = np.abs(got[k].astype(LD) - ref)
+            assert np.all(err <= bound), (name, k, float(np.max(err / bound)))
+            assert same(call(one(b, k, per))[0], out[k]), f"{name}: problem {k} differs from its K = 1 launch"
+
+
+def test_argument_errors():
+    import torch
+    from riskaversetrajopt_amd import _lib
+    lib = _lib.load()
+    n, m0, m1 = 5, 4, 2
+    new = lambda *s: torch.zeros(s, dtype=torch.float64, device=DEV)
+    J0, J1, d, h, g, Kc, x, w, on, om = new(2, m0, n), new(m1, n), new(2, m0 + m1), new(2, 15), new(2, n), new(2, n, n), new(2, n), \
+        new(2, m0 + m1), new(2, n), new(2, m0 + m1)
+    P, st = _lib.ptr, _lib.current_stream()
+
+    def normal(K=2, n=n, lda=n, J0=J0, m0=m0, ld0=n, J1=J1, m1=m1, ld1=n, s1=0, d=d, ldd=m0 + m1, Kc=Kc):
+        return lib.rato_dense_normal_matrix_f64(K, n, lda, P(J0), m0, ld0, P(J1), m1, ld1, s1, P(d), ldd, P(h), P(g), P(Kc), st)
+
+    def mv(fn, vec, out, ldv, ldo, K=2, n=n, J0=J0, ld0=n, J1=J1, ld1=n):
+        return fn(K, n, P(J0), m0, ld0, P(J1), m1, ld1, 0, P(vec), ldv, P(out), ldo, st)
+
+    def symv(K=2, n=n, h=h, x=x, ldx=n, out=on, ldo=n):
+        return lib.rato_tril_symv_f64(K, n, P(h), P(x), ldx, P(out), ldo, st)
+    assert normal() == 0 and mv(lib.rato_dense_matvec_f64, x, om, n, m0 + m1) == 0 and \
+        mv(lib.rato_dense_tmatvec_f64, w, on, m0 + m1, n) == 0 and symv() == 0
+    bad = [normal(K=0), normal(K=65536), normal(n=0), normal(lda=n - 1), normal(ld0=n - 1), normal(ld1=n - 1), normal(J0=None),
+           normal(J1=None), normal(d=None), normal(Kc=None), normal(ldd=m0 + m1 - 1), normal(m0=0), normal(m1=-1), normal(s1=1)]
+    for fn, vec, out, ldv, ldo in ((lib.rato_dense_matvec_f64, x, om, n, m0 + m1), (lib.rato_dense_tmatvec_f64, w, on, m0 + m1, n)):
+        bad += [mv(fn, vec, out, ldv, ldo, K=0), mv(fn, vec, out, ldv, ldo, K=65536), mv(fn, vec, out, ldv, ldo, n=0),
+                mv(fn, vec, out, ldv, ldo, ld0=n - 1), mv(fn, vec, out, ldv, ldo, ld1=n - 1), mv(fn, vec, out, ldv, ldo, J0=None),
+                mv(fn, vec, out, ldv, ldo, J1=None), mv(fn, None, out, ldv, ldo), mv(fn, vec, None, ldv, ldo),
+                mv(fn, vec, out, ldv - 1, ldo), mv(fn, vec, out, ldv, ldo - 1)]
+    bad += [symv(K=0), symv(K=65536), symv(n=0), symv(h=None), symv(x=None), symv(out=None), symv(ldx=n - 1), symv(ldo=n - 1)]
+    assert all(v == -1 for v in bad), bad                                 # RATO_EINVAL
+    torch.cuda.synchronize()
+
+
+# ---- one Newton step ---------------------------------------------------------------------------------------------------------
+def newton_residuals(S, alpha=0.1):
+    """One Newton step of both backends from the same ``Problem`` state: the designed interior point
+    ``_drone_gaussian.problems(S, 1)``, seeded multipliers of mixed sign, mu = 0.1.  -> (NumPy, device) relative residuals in
+    the uncondensed regularised KKT system built from the restatement's dense J and W"""
+    from riskaversetrajopt_amd import drone_gaussian as dg, hopper_ipm
+    m = ipm()
+    model = dg.Model(S, alpha=alpha, device=DEV)
+    nlp = m.Nlp(model)
+    Z0 = R.problems(S, 1, alpha)[0][0]
+    be_np, be_dev = m.NumpyBackend([nlp], [R.callbacks(S, alpha)]), m.DeviceBackend([nlp])
+    g0 = be_np.eval_g([0], [Z0])[0]
+    out = []
+    for be in (be_np, be_dev):
+        p = hopper_ipm.Problem(nlp, Z0, g0, T.TOL)
+        rng = np.random.RandomState(400 + S)
+        p.y = rng.uniform(-1, 1, p.m)
+        p.zl, p.zu = p.zl * rng.uniform(0.5, 2.0, p.zl.size), p.zu * rng.uniform(0.5, 2.0, p.zu.size)
+        g, = be.eval_full([0], [p.z.copy()], [p.y], [p.sf])
+        p.residuals(g, be.tmatvec([0], [p.y])[0])
+        p.prepare_step()
+        assert hopper_ipm.newton_steps(be, [0], [p]) == [True]
+        ev = R.evaluate(p.z, S, [p.y[:nlp.n_nl]])
+        J = np.vstack([ev["jac_nl"], nlp.sum_row()[None, :]])
+        W = ev["hess"][0] + np.diag(p.sf * nlp.curv)
+        out.append(hopper_ipm.kkt_residual(p, J, W))
+    return out
+
+
+@pytest.mark.parametrize("S", [2, 5])
+def test_one_newton_step_device_against_numpy(S):
+    res_np, res_dev = newton_residuals(S)
+    print(f"newton step S={S}: numpy {res_np:.3e} device {res_dev:.3e}")
+    assert np.isfinite(res_dev) and res_dev <= 100.0 * res_np, (res_np, res_dev)
+
+
+# ---- end to end --------------------------------------------------------------------------------------------------------------
+_DEVICE = {}
+
+
+def device_solutions(S):
+    """the device backend on the real device callbacks, the batch of T.CASES[S] (computed once; do not modify)"""
+    if S not in _DEVICE:
+        from riskaversetrajopt_amd import drone_gaussian as dg
+        a = T.CASES[S]
+        _DEVICE[S] = ipm().solve_batch([dg.Model(S, alpha=x, device=DEV) for x in a], T.starts(S, a), tol=T.TOL, max_iter=300,
+                                       backend='device')
+    return _DEVICE[S]
+
+
+@pytest.mark.parametrize("S", sorted(T.CASES))
+def test_end_to_end_device_batch(S):
+    for k, (a, (Z, info)) in enumerate(zip(T.CASES[S], device_solutions(S))):
+        assert info["status"] == "converged" and info["backend"] == "device", (a, info["status"])
+        T.check_solution(S, a, Z, info)
+        f_np = T.numpy_solutions(S)[k][1]["f"]
+        gap = abs(info["f"] - f_np)
+        print(f"end to end S={S} alpha={a}: iterations {info['iterations']} f_device {info['f']:.12f} |f_device - f_numpy| {gap:.3e}")
+        assert gap <= F_GATE, (a, gap)
+
+
+@pytest.mark.parametrize("S", sorted(T.CASES))
+def test_device_batch_is_bitwise_the_solo_runs(S):
+    from riskaversetrajopt_amd import drone_gaussian as dg
+    for a, (Zb, ib) in zip(T.CASES[S], device_solutions(S)):
+        (Z1, i1), = ipm().solve_batch([dg.Model(S, alpha=a, device=DEV)], T.starts(S, [a]), tol=T.TOL, max_iter=300, backend='device')
+        assert Z1.tobytes() == Zb.tobytes(), a
+        assert (i1["iterations"], i1["factorizations"]) == (ib["iterations"], ib["factorizations"])
+        for key in ("y", "zl", "zu", "s"):
+            assert i1[key].tobytes() == ib[key].tobytes(), (a, key)
+
+
+def test_driver_and_model_entry_points_agree_with_solve_batch():
+    from riskaversetrajopt_amd import drone_gaussian as dg, scp
+    S, a = 5, 0.1
+    Zb, ib = device_solutions(S)[0]
+    Z0 = R.start_point(S, a)
+    r = scp.run_drone_gaussian(dg.Model(S, alpha=a, device=DEV), Z0=Z0, maxiter=300, solver='ipm')
+    assert r["status"] == ib["status"] == "converged" and r["Z"].tobytes() == Zb.tobytes()
+    assert r["nit"] == ib["iterations"] and r["fun"] == ib["f"]
+    assert r["xs"].shape == (S + 1, 6) and r["Sigmas"].shape == (S + 1, 6, 6)
+    Z, info = dg.Model(S, alpha=a, device=DEV).solve(Z0, max_iter=300)
+    assert Z.tobytes() == Zb.tobytes() and info["status"] == "converged"
+    assert info["lagrange"].shape == (dg.sizes(S)[2],)

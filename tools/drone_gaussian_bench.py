@@ -12,6 +12,18 @@
 
     python tools/drone_gaussian_bench.py [--maxiter 3000] [--out profiles/drone_gaussian_bench.json]
 
+With ``--solver {trust-constr,ipm,both}`` it measures the SOLVE instead and writes profiles/drone_gaussian_solve.json: the
+script's experiment (S = 20, alpha in 0.05, 0.1, 0.2, 0.3, every alpha from its SAA repeat-0 solution, made first where
+``--results-dir`` does not hold it) through ``scp.drone_gaussian_experiment`` with scipy's trust-constr (one alpha after the
+other) and / or the batched interior-point method (``drone_gaussian_ipm``: all alphas in one ``solve_batch`` call), in the same
+process.  Per alpha and solver: status, iterations, factorizations (ipm) or evaluations (trust-constr), E_0 (ipm) or
+constraint violation and optimality (trust-constr), f, percentage_safe of the 10,000-sample Monte-Carlo block and the wall
+clock; for the batch the split of its wall clock into callbacks / normal matrix / factor / solves / matvecs / host, in total
+and per lockstep iteration.  Nothing is tuned towards an outcome: an alpha that ends in 'line_search' or 'max_iter' is
+reported as that.
+
+    python tools/drone_gaussian_bench.py --solver both [--results-dir results] [--out profiles/drone_gaussian_solve.json]
+
 Prints one JSON line.  There is no CPU fallback: without a GPU the kernel timings fail.
 """
 import argparse
@@ -49,17 +61,69 @@ def scaled(a, b):
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), np.finfo(float).tiny))
 
 
+def write(out, path):
+    line = json.dumps(out)
+    print(line, flush=True)
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(line + "\n")
+
+
+def solve_bench(args):
+    """the S = 20 experiment with one or both solvers -> the dictionary written to profiles/drone_gaussian_solve.json"""
+    import torch
+    import _drone_gaussian as R
+    from riskaversetrajopt_amd import drone_gaussian as DG
+    from riskaversetrajopt_amd import drone_gaussian_ipm, scp
+    S, alphas = 20, (0.05, 0.1, 0.2, 0.3)
+    path = args.out or os.path.join(ROOT, "profiles", "drone_gaussian_solve.json")
+    out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": list(alphas), "tol": args.tol, "maxiter": args.maxiter,
+           "start": "SAA repeat 0 (drone_saa_experiment, M = 50, 60 iterations, seed 0)", "M_mc": 10000}
+    # warm-up: code objects, allocator, the SAA starts
+    drone_gaussian_ipm.solve_batch([DG.Model(5, alpha=0.1)], [R.start_point(5, 0.1)], max_iter=3)
+    scp.run_drone_gaussian(DG.Model(5, alpha=0.1), Z0=R.start_point(5, 0.1), maxiter=3)
+    if args.solver in ("ipm", "both"):
+        clocks = {}
+        r = scp.drone_gaussian_experiment(alphas, S=S, results_dir=args.results_dir, maxiter=args.maxiter, solver='ipm',
+                                          tol=args.tol, clocks=clocks)
+        rounds = max(1, max(x["info"]["iterations"] for x in r["results"]))
+        out["ipm"] = {"wall_s": r["wall_s"], "clocks_s": clocks, "lockstep_iterations": rounds,
+                      "per_iteration_ms": {k: 1e3 * v / rounds for k, v in clocks.items()},
+                      "per_alpha": [{"alpha": a, "status": x["status"], "iterations": x["info"]["iterations"],
+                                     "factorizations": x["info"]["factorizations"], "E0": x["info"]["E0"],
+                                     "primal_infeasibility": x["info"]["primal_infeasibility"],
+                                     "dual_infeasibility": x["info"]["dual_infeasibility"], "f": x["fun"],
+                                     "percentage_safe": float(s), "cost": float(c)}
+                                    for a, x, s, c in zip(alphas, r["results"], r["percentage_safe"], r["cost"])]}
+        write(out, path)
+    if args.solver in ("trust-constr", "both"):
+        r = scp.drone_gaussian_experiment(alphas, S=S, results_dir=args.results_dir, maxiter=args.maxiter)
+        out["trust_constr"] = {"wall_s": r["wall_s"],
+                               "per_alpha": [{"alpha": a, "status": x["status"], "message": x["message"], "iterations": x["nit"],
+                                              "evaluations": x["nfev"], "constr_violation": x["constr_violation"],
+                                              "optimality": x["optimality"], "f": x["fun"], "callback_s": x["callback_s"],
+                                              "wall_s": x["total_s"], "percentage_safe": float(s), "cost": float(c)}
+                                             for a, x, s, c in zip(alphas, r["results"], r["percentage_safe"], r["cost"])]}
+        write(out, path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maxiter", type=int, default=3000)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--solver", choices=("trust-constr", "ipm", "both"), default=None)
+    ap.add_argument("--tol", type=float, default=1e-8)
+    ap.add_argument("--results-dir", default="results")
     args = ap.parse_args()
 
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("drone_gaussian_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.solver is not None:
+        return solve_bench(args)
     import _drone_gaussian as R
     from riskaversetrajopt_amd import drone_gaussian as DG
     from riskaversetrajopt_amd import scp
@@ -111,12 +175,7 @@ def main():
     res = scp.run_drone_gaussian(m, Z0=R.start_point(S, 0.1), maxiter=args.maxiter)
     out["solve_S5"] = {k: res[k] for k in ("status", "message", "nit", "nfev", "constr_violation", "optimality", "fun",
                                            "callback_s", "total_s")}
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    write(out, args.out)
 
 
 if __name__ == "__main__":
