@@ -1358,6 +1358,58 @@ int rato_dense_tmatvec_f64(int32_t K, int32_t n, const double* J0, int32_t m0, i
 int rato_tril_symv_f64(int32_t K, int32_t n, const double* hess_tril, const double* x, int64_t ldx, double* out, int64_t ldo,
                        void* stream);
 
+/* ---- Arrowhead Newton step of the hopper's interior-point solve at large M, fp64 (csrc/hopper_arrow.hip; hopper_ipm.py,
+ * newton='arrow').  ABI: additive (RATO_ABI_VERSION stays 12).  K problems per launch, device pointers, stream ordered, no
+ * allocation.  No floating-point atomics: every output has one owner that sums in a fixed order, so two calls are bitwise equal
+ * and problem k of a batch is bitwise its K = 1 call.
+ *
+ * The M variables ys enter the condensed matrix only through E = diag(e) + d_0 1 1' and one row each of B = B_s + beta 1 e_t',
+ * so they are eliminated exactly; these entry points do the work over the sample axis.  Inputs shared by all of them:
+ *   dh_dx [K][C][3][M], dh_dfz [K][C][M]   the partials rato_hopper_slip_f64 leaves; with them
+ *                                          g_ic = (dh/dx0, dh/dx2, dh/dx3, 1 on fx, dh/dfz) and grad h_ic = (g_ic, -1 on slack,
+ *                                          -1 on t_risk [saa only])
+ *   d [K][ldd], r0, saa                    row weights read in place: the slip row of sample i, contact c at r0 + i C + c; with
+ *                                          saa != 0 the row -y_i at r0 - M + i and the sum row at r0 - M - 1
+ *   touched columns                        q = 5C + 2: contact c owns 5c .. 5c + 4 (x0, x2, x3, fx, fz), then slack, then t_risk
+ * Samples are cut into chunks of rato_hopper_arrow_chunk(); a chunk sums its samples ascending into part
+ * [rato_hopper_arrow_nchunks(M)][K][n_part], a second launch sums the chunks ascending into red [K][n_part].
+ *
+ * rato_hopper_arrow_reduce_f64: with b_i = -sum_c d_ic grad h_ic (never stored in memory), e_i = ydiag_i (+ d_(1+i) + sum_c d_ic
+ *   with saa) is written to e [K][M], and with u = 1 / e, n_part = rato_hopper_arrow_npart(C) values per problem in this order:
+ *   G = sum u_i b_i b_i' (lower triangle, entry (p, r <= p) at p (p + 1) / 2 + r), w = sum u_i b_i (q), a = sum b_i (q),
+ *   s = sum u_i (1), P_c = sum_i d_ic g_ic g_ic' (per contact the 15 entries of its lower triangle).
+ * rato_hopper_arrow_assemble_f64: adds into the row-major lower triangle Sh [K][nc][lda] (what rato_normal_matrix_f64 left for
+ *   the deterministic rows on the core columns) at (qcol[p], qcol[r]) the slip rows' share (P_c, a) and, with saa,
+ *   - [G + beta (w e_t' + e_t w') + beta^2 s e_t e_t'] + k v v' + d_0 malpha^2 e_t e_t', beta = d_0 malpha[k],
+ *   k = d_0 / (1 + d_0 s), v = w + beta s e_t.  Nothing else of Sh is read or written.
+ * rato_hopper_arrow_cols_f64: red [K][5C + 1] = per (c, j) sum_i omega_ic g_ic[j]; mode 0: omega_ic = w[r0 + i C + c], and yout
+ *   [K][M] (may be NULL) takes w_0 - w_(1+i) - sum_c omega_ic (0 without saa): J_risk' w.  mode 1: omega_ic = -t_i w[r0 + i C + c]
+ *   (pass d as w), slot 5C takes sum_i t_i: B_s' t.
+ * rato_hopper_arrow_rows_f64: mode 0: out[k][r0 + i C + c] = g_ic . xq_c - xq_slack - xq_t - xy_i, and with saa out[k][r0 - M + i]
+ *   = -xy_i and red[k] = sum_i xy_i (xq [K][q], xy [K][M]): J_risk v but for the sum row's M alpha v_t.  mode 1: out[k][i] =
+ *   sum_c -d_ic (g_ic . xq_c - xq_slack - xq_t) + addc[k]: B x_c; with xy != NULL, xy_i minus that: r_y - B x_c.
+ * rato_hopper_arrow_edot_f64: red[k] = sum_i (1 / e_i) v_i.  rato_hopper_arrow_eapply_f64: out_i = (1 / e_i) (v_i - kappa[k]).
+ * RATO_EINVAL without a launch on a NULL or undersized argument, K outside [1, 65535], M < 1, C outside [1, 50], a mode other
+ * than 0 or 1, or r0 too small for the rows in front of it. */
+int rato_hopper_arrow_nchunks(int64_t M);
+int rato_hopper_arrow_chunk(void);
+int64_t rato_hopper_arrow_npart(int32_t C);
+int rato_hopper_arrow_reduce_f64(int32_t K, int64_t M, int32_t C, int32_t saa, const double* dh_dx, const double* dh_dfz,
+                                 const double* d, int64_t ldd, int64_t r0, const double* ydiag /* [K][M] */, double* e,
+                                 double* part, double* red, void* stream);
+int rato_hopper_arrow_assemble_f64(int32_t K, int64_t M, int32_t C, int32_t saa, int32_t nc, int64_t lda, const int32_t* qcol,
+                                   const double* red, const double* d, int64_t ldd, int64_t r0, const double* malpha /* [K] */,
+                                   double* Sh, void* stream);
+int rato_hopper_arrow_cols_f64(int32_t K, int64_t M, int32_t C, int32_t saa, int32_t mode, const double* dh_dx,
+                               const double* dh_dfz, const double* w, int64_t ldw, int64_t r0, const double* t, double* yout,
+                               double* part, double* red, void* stream);
+int rato_hopper_arrow_rows_f64(int32_t K, int64_t M, int32_t C, int32_t saa, int32_t mode, const double* dh_dx,
+                               const double* dh_dfz, const double* xq, const double* xy, const double* d, int64_t ldd, int64_t r0,
+                               const double* addc, double* out, int64_t ldo, double* part, double* red, void* stream);
+int rato_hopper_arrow_edot_f64(int32_t K, int64_t M, const double* e, const double* v, double* part, double* red, void* stream);
+int rato_hopper_arrow_eapply_f64(int32_t K, int64_t M, const double* e, const double* v, const double* kappa, double* out,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,20 @@ SIGNATURES = {
     "rato_dense_tmatvec_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, C.c_int32, C.c_int64, c_float_p, C.c_int32, C.c_int64,
                                          C.c_int64, c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
     "rato_tril_symv_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
+    "rato_hopper_arrow_nchunks": (C.c_int, [C.c_int64]),
+    "rato_hopper_arrow_chunk": (C.c_int, []),
+    "rato_hopper_arrow_npart": (C.c_int64, [C.c_int32]),
+    "rato_hopper_arrow_reduce_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_float_p, c_float_p, c_float_p,
+                                               C.c_int64, C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_assemble_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, c_float_p,
+                                                 c_float_p, c_float_p, C.c_int64, C.c_int64, c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_cols_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p,
+                                             c_float_p, C.c_int64, C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_rows_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p,
+                                             c_float_p, c_float_p, c_float_p, C.c_int64, C.c_int64, c_float_p, c_float_p, C.c_int64,
+                                             c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_edot_f64": (C.c_int, [C.c_int32, C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_eapply_f64": (C.c_int, [C.c_int32, C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h

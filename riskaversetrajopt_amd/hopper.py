@@ -797,12 +797,13 @@ class Model:
             us[sl, 1] = us[sl, 3] = nominal_force
         return Zp
 
-    def solve(self, Z0=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False):
+    def solve(self, Z0=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, newton='dense'):
         """The script's solve (:642-669, its options tol = 1e-3, max_iter = 3000) with the batched interior-point method of
-        ``hopper_ipm`` in place of IPOPT -> (Z, info); info["status"] is 'converged' only if the final error shows it."""
+        ``hopper_ipm`` in place of IPOPT -> (Z, info); info["status"] is 'converged' only if the final error shows it.
+        newton='arrow' eliminates the M sample variables from the Newton step (the path that scales with M)."""
         from . import hopper_ipm
         return hopper_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter, backend=backend,
-                                      callbacks=None if callbacks is None else [callbacks], verbose=verbose)[0]
+                                      callbacks=None if callbacks is None else [callbacks], verbose=verbose, newton=newton)[0]
 
     def _nlp_state(self, K):
         """device-side constants of the emission: the maps (uploaded once) and, per K, the destinations zeroed / pre-filled once"""

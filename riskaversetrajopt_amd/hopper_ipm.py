@@ -21,6 +21,11 @@ problems per launch) and 'numpy' (the whole step on the host, callbacks injected
 Model): the driver, the line search and the O(n + m) vector algebra are shared and run on the host per problem, so a problem's
 iterates do not depend on what else is in the batch.
 
+newton='arrow'  is the same step for any M: the M variables ys enter Kc only through E = diag(e) + d_0 1 1' and one
+row each of B, so they are eliminated exactly and the Cholesky factors the core's Schur complement (8(S+1) + 4S + 2 columns)
+-- the same inertia test, since e > 0.  ``ArrowDeviceBackend`` does the work over the samples with csrc/hopper_arrow.hip on the
+partials rato_hopper_slip_f64 leaves, ``ArrowNumpyBackend`` is its host twin; newton='dense' (the default) is the step above.
+
 The driver (``Problem``, ``newton_steps``, ``_solve_group``) knows a model through num_vars, gL_gU(), x_bounds(), f, grad_f and a
 backend through eval_full / eval_g / matvec / tmatvec / factor / solve / hess_apply(idx, X) -> [W x]: ``drone_gaussian_ipm`` runs
 it on dense backends of its own.
@@ -50,9 +55,19 @@ def structure(model):
     if st is not None:
         return st
     lay = model.nlp_layout()
-    n, ncon, S = lay["nvar"], lay["ncon"], model.S
-    rows = np.asarray(lay["jac_indices"], dtype=np.int64)
-    indptr = np.asarray(lay["jac_indptr"], dtype=np.int64)
+    st = _pattern_maps(lay["jac_indices"], lay["jac_indptr"], lay["nvar"], lay["ncon"], model.S)
+    to_cat = np.empty(st["nnz"], dtype=np.int64)
+    to_cat[lay["pos_det"]] = np.arange(lay["pos_det"].size)
+    to_cat[lay["pos_slip"]] = lay["pos_det"].size + np.arange(lay["pos_slip"].size)
+    st.update(to_cat=to_cat, n_det=int(lay["pos_det"].size), n_slip=int(lay["pos_slip"].size))
+    model._ipm_structure = st
+    return st
+
+
+def _pattern_maps(jac_indices, jac_indptr, n, ncon, S):
+    """the index lists of ``structure`` for a CSC pattern with n columns whose first 8(S+1) + 4S are the step blocks' variables"""
+    rows = np.asarray(jac_indices, dtype=np.int64)
+    indptr = np.asarray(jac_indptr, dtype=np.int64)
     cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
     nnz = rows.size
     order = np.lexsort((cols, rows))
@@ -85,15 +100,9 @@ def structure(model):
     hess_src[np.searchsorted(ent_keys, hkeys)] = hsrc
     ent_of = -np.ones(n * n, dtype=np.int64)
     ent_of[ent_keys] = np.arange(ent_keys.size)
-    to_cat = np.empty(nnz, dtype=np.int64)
-    to_cat[lay["pos_det"]] = np.arange(lay["pos_det"].size)
-    to_cat[lay["pos_slip"]] = lay["pos_det"].size + np.arange(lay["pos_slip"].size)
-    st = dict(n=n, ncon=ncon, nnz=nnz, rows=rows, cols=cols, indptr=indptr, row_ptr=row_ptr, row_idx=row_idx, row_col=row_col,
-              ent_keys=ent_keys, ent_of=ent_of, ptr=ptr, tri_a=IA, tri_b=IB, tri_r=R, tri_ent=tri_ent, hess_src=hess_src,
-              diag_ent=np.searchsorted(ent_keys, dkeys), to_cat=to_cat, n_det=int(lay["pos_det"].size),
-              n_slip=int(lay["pos_slip"].size), block_vars=np.where(bv >= 0, bv, n))
-    model._ipm_structure = st
-    return st
+    return dict(n=n, ncon=ncon, nnz=nnz, rows=rows, cols=cols, indptr=indptr, row_ptr=row_ptr, row_idx=row_idx, row_col=row_col,
+                ent_keys=ent_keys, ent_of=ent_of, ptr=ptr, tri_a=IA, tri_b=IB, tri_r=R, tri_ent=tri_ent, hess_src=hess_src,
+                diag_ent=np.searchsorted(ent_keys, dkeys), block_vars=np.where(bv >= 0, bv, n))
 
 
 def product_map(model):
@@ -416,6 +425,489 @@ def chol_solve(L, B):
     return B
 
 
+# ---- the arrowhead step: ys eliminated exactly (newton='arrow') ------------------------------------------------
+def arrow_structure(model):
+    """Host-only index lists of the arrowhead step; nothing in it grows faster than O(M C).  z = (core, y): the core
+    c = (xs, us, slack, t_risk) has n_c = 8(S+1) + 4S + 2 columns, y = ys has M.
+      n, nc, ncon, M, C, saa, q = 5C + 2, r0 (g index of the slip row of sample 0, contact 0), rr (the sum row; -1: baseline)
+      core_z (nc,)       z index of a core column;  y0: z index of y_0
+      qcol (q,), qz (q,) core / z index of the touched columns: per contact (x0, x2, x3, fx, fz) of its step, then slack, t_risk
+      det                ``_pattern_maps`` of the deterministic rows on the core columns (value index = position in
+                         ``nlp_layout()``'s det values; ent_of is n_c x n_c whatever M is)
+      det_rows, det_cols_z   the deterministic pattern as coordinate lists in z numbering
+      pos_det, pos_slip  where the two value arrays lie in the full pattern (the NumPy twin splits injected values with them)"""
+    st = getattr(model, "_ipm_arrow", None)
+    if st is not None:
+        return st
+    lay = model.nlp_layout()
+    S, M, Cn, n, ncon = model.S, model.M, lay["C"], lay["nvar"], lay["ncon"]
+    if Cn < 1:
+        raise ValueError("newton='arrow' needs at least one contact step; use newton='dense'")
+    saa = model.method != 'baseline'
+    nXU = _h.n_x * (S + 1) + _h.n_u * S
+    nc = nXU + 2
+    det_indptr = np.asarray(lay["det_indptr"], dtype=np.int64)
+    assert det_indptr[nXU] == det_indptr[n - 2]                    # no deterministic row touches a y column
+    det = _pattern_maps(lay["det_indices"], np.concatenate([det_indptr[:nXU], det_indptr[n - 2:]]), nc, ncon, S)
+    core_z = np.concatenate([np.arange(nXU), [n - 2, n - 1]]).astype(np.int64)
+    steps = model.contact_steps()
+    nX = _h.n_x * (S + 1)
+    qcol = np.concatenate([np.stack([_h.n_x * steps, _h.n_x * steps + 2, _h.n_x * steps + 3, nX + _h.n_u * steps + 2,
+                                     nX + _h.n_u * steps + 3], axis=1).reshape(-1), [nc - 2, nc - 1]]).astype(np.int64)
+    r_ncon, r0 = model.risk_rows_offset()
+    assert r_ncon == ncon
+    st = dict(n=n, nc=nc, ncon=ncon, M=M, C=Cn, saa=saa, q=5 * Cn + 2, r0=int(r0), rr=int(r0 - M - 1) if saa else -1, y0=nXU,
+              core_z=core_z, qcol=qcol, qz=core_z[qcol], det=det, det_rows=np.asarray(lay["det_indices"], dtype=np.int64),
+              det_cols_z=np.repeat(np.arange(n, dtype=np.int64), np.diff(det_indptr)), det_indptr_z=det_indptr,
+              pos_det=np.asarray(lay["pos_det"]), pos_slip=np.asarray(lay["pos_slip"]),
+              hess=dict(n=n, block_vars=det["block_vars"].copy()))
+    st["hess"]["block_vars"][st["hess"]["block_vars"] == nc] = n
+    model._ipm_arrow = st
+    return st
+
+
+ArrowStructure = arrow_structure
+
+
+def arrow_terms(st, dx, dfz, d, ydiag, malpha):
+    """The sample block of one problem on the host.  dx (C, 3, M), dfz (C, M) the slip partials, d (ncon,), ydiag (M,) = Sigma_y +
+    delta_w, malpha = M alpha.  -> dict(e (M,), Bq (M, q) = B_s on the touched columns, A (q, q) the slip rows' own share, T (q, q)
+    what is added to the core's matrix, d0, beta, k, s): E = diag(e) + d0 1 1', B = B_s + beta 1 e_t'."""
+    M, Cn, q, r0, saa = st["M"], st["C"], st["q"], st["r0"], st["saa"]
+    dic = d[r0:r0 + M * Cn].reshape(M, Cn)
+    g = np.stack([dx[:, 0].T, dx[:, 1].T, dx[:, 2].T, np.ones((M, Cn)), dfz.T], axis=2)            # (M, C, 5)
+    dsum = dic.sum(axis=1)
+    Bq = np.zeros((M, q))
+    Bq[:, :5 * Cn] = (-dic[:, :, None] * g).reshape(M, 5 * Cn)
+    Bq[:, 5 * Cn] = dsum
+    A = np.zeros((q, q))
+    tq = 5 * Cn + 1
+    for c in range(Cn):
+        N = np.zeros((M, q))
+        N[:, 5 * c:5 * c + 5] = g[:, c]
+        N[:, 5 * Cn] = -1.0
+        if saa:
+            N[:, tq] = -1.0
+        A += N.T @ (dic[:, c, None] * N)
+    if not saa:
+        return dict(e=ydiag.copy(), Bq=None, A=A, T=A, d0=0.0, beta=0.0, k=0.0, s=0.0)
+    Bq[:, tq] = dsum
+    e = ydiag + d[st["rr"] + 1:st["rr"] + 1 + M] + dsum
+    u = 1.0 / e
+    d0 = float(d[st["rr"]])
+    beta = d0 * malpha
+    G, w, s = Bq.T @ (u[:, None] * Bq), Bq.T @ u, float(np.sum(u))
+    k = d0 / (1.0 + d0 * s)
+    et = np.zeros(q)
+    et[tq] = 1.0
+    v = w + beta * s * et
+    T = A - (G + beta * (np.outer(w, et) + np.outer(et, w)) + beta * beta * s * np.outer(et, et)) + k * np.outer(v, v)
+    T[tq, tq] += d0 * malpha * malpha
+    return dict(e=e, Bq=Bq, A=A, T=T, d0=d0, beta=beta, k=k, s=s)
+
+
+def _risk_matvec(st, dx, dfz, malpha, x, out):
+    """out[risk rows] = J_risk x from the partials (x in z numbering)"""
+    M, Cn, r0 = st["M"], st["C"], st["r0"]
+    xq = x[st["qz"]]
+    h = np.einsum("cjm,cj->mc", dx, xq[:5 * Cn].reshape(Cn, 5)[:, :3]) + xq[3:5 * Cn:5][None, :] + dfz.T * xq[4:5 * Cn:5][None, :]
+    h = h - xq[5 * Cn]
+    if st["saa"]:
+        xy = x[st["y0"]:st["y0"] + M]
+        h = h - xq[5 * Cn + 1] - xy[:, None]
+        out[st["rr"]] = malpha * xq[5 * Cn + 1] + np.sum(xy)
+        out[st["rr"] + 1:st["rr"] + 1 + M] = -xy
+    out[r0:r0 + M * Cn] = h.reshape(-1)
+    return out
+
+
+def _risk_tmatvec(st, dx, dfz, malpha, w, out):
+    """out += J_risk' w from the partials (out in z numbering)"""
+    M, Cn, r0 = st["M"], st["C"], st["r0"]
+    wic = w[r0:r0 + M * Cn].reshape(M, Cn)
+    cols = np.empty((Cn, 5))
+    cols[:, :3] = np.einsum("cjm,mc->cj", dx, wic)
+    cols[:, 3] = wic.sum(axis=0)
+    cols[:, 4] = np.einsum("cm,mc->c", dfz, wic)
+    tot = -np.sum(cols[:, 3])
+    add = np.concatenate([cols.reshape(-1), [tot, 0.0]])
+    if st["saa"]:
+        add[5 * Cn + 1] = malpha * w[st["rr"]] + tot
+        out[st["y0"]:st["y0"] + M] = w[st["rr"]] - w[st["rr"] + 1:st["rr"] + 1 + M] - wic.sum(axis=1)
+    out[st["qz"]] += add
+    return out
+
+
+class ArrowNumpyBackend:
+    """The arrowhead step on the host: the same elimination as ``ArrowDeviceBackend``, from injected callbacks (or the Model's,
+    one problem at a time).  ``callbacks[i]`` as for ``NumpyBackend``; of jac_values only the deterministic values and the slip
+    partials dh/d(x0, x2, x3), dh/dfz are kept.  After ``factor``, ``parts[i]`` holds Shat (nc, nc) with ``arrow_terms``' pieces."""
+    name, newton = "numpy", "arrow"
+
+    def __init__(self, models, callbacks=None):
+        self.models = models
+        self.cb = [ModelCallbacks(m) for m in models] if callbacks is None else list(callbacks)
+        self.st = arrow_structure(models[0])
+        self.det, self.dx, self.dfz, self.hess, self.parts, self.L = {}, {}, {}, {}, {}, {}
+        self.clock = dict(callbacks=0.0, normal=0.0, factor=0.0, solve=0.0)
+
+    def _malpha(self, i):
+        return self.st["M"] * float(self.models[i].alpha)
+
+    def set_values(self, i, vals, hess):
+        """install Jacobian values on the full CSC pattern and step blocks as problem i's current evaluation"""
+        st = self.st
+        M, Cn = st["M"], st["C"]
+        vals = np.asarray(vals, dtype=np.float64)
+        slip = vals[st["pos_slip"]]
+        self.det[i] = vals[st["pos_det"]]
+        self.dx[i] = slip[:3 * Cn * M].reshape(Cn, 3, M).copy()
+        self.dfz[i] = slip[3 * Cn * M:5 * Cn * M].reshape(Cn, 2, M)[:, 1].copy()
+        self.hess[i] = np.asarray(hess, dtype=np.float64)
+
+    def eval_full(self, idx, Zs, lams, sfs):
+        t0 = time.perf_counter()
+        out = []
+        for i, Z, lam, sf in zip(idx, Zs, lams, sfs):
+            self.set_values(i, self.cb[i].jac_values(Z), self.cb[i].hess_blocks(Z, lam, sf))
+            out.append(np.asarray(self.cb[i].g(Z), dtype=np.float64))
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def eval_g(self, idx, Zs):
+        t0 = time.perf_counter()
+        out = [np.asarray(self.cb[i].g(Z), dtype=np.float64) for i, Z in zip(idx, Zs)]
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def hess_apply(self, idx, X):
+        return [_hess_apply(self.st["hess"], self.hess[i], x) for i, x in zip(idx, X)]
+
+    def matvec(self, idx, X):
+        st = self.st
+        out = []
+        for i, x in zip(idx, X):
+            o = np.bincount(st["det_rows"], weights=self.det[i] * x[st["det_cols_z"]], minlength=st["ncon"])
+            out.append(_risk_matvec(st, self.dx[i], self.dfz[i], self._malpha(i), x, o))
+        return out
+
+    def tmatvec(self, idx, W):
+        st = self.st
+        out = []
+        for i, w in zip(idx, W):
+            o = np.bincount(st["det_cols_z"], weights=self.det[i] * w[st["det_rows"]], minlength=st["n"])
+            out.append(_risk_tmatvec(st, self.dx[i], self.dfz[i], self._malpha(i), w, o))
+        return out
+
+    def factor(self, idx, D, diags):
+        st = self.st
+        info = []
+        for i, d, dg in zip(idx, D, diags):
+            t0 = time.perf_counter()
+            Sh = normal_matrix_host(st["det"], self.det[i], d, self.hess[i], dg[st["core_z"]])
+            P = arrow_terms(st, self.dx[i], self.dfz[i], d, dg[st["y0"]:st["y0"] + st["M"]], self._malpha(i))
+            Sh[np.ix_(st["qcol"], st["qcol"])] += P["T"]
+            P["Shat"] = Sh
+            self.parts[i] = P
+            t1 = time.perf_counter()
+            ok = bool(np.all(np.isfinite(Sh))) and bool(np.all(P["e"] > 0.0))
+            if ok:
+                try:
+                    self.L[i] = np.linalg.cholesky(Sh)
+                except np.linalg.LinAlgError:
+                    ok = False
+            self.clock["normal"] += t1 - t0
+            self.clock["factor"] += time.perf_counter() - t1
+            info.append(0 if ok else 1)
+        return info
+
+    def solve(self, idx, B):
+        from scipy.linalg import solve_triangular
+        st = self.st
+        t0 = time.perf_counter()
+        out = []
+        for i, b in zip(idx, B):
+            P, L = self.parts[i], self.L[i]
+            u = 1.0 / P["e"]
+            einv = (lambda v: u * (v - P["k"] * (u @ v))) if st["saa"] else (lambda v: u * v)
+            rc, ry = b[st["core_z"]].copy(), b[st["y0"]:st["y0"] + st["M"]]
+            t = einv(ry)
+            if st["saa"]:
+                bt = P["Bq"].T @ t
+                bt[-1] += P["beta"] * np.sum(t)
+                rc[st["qcol"]] -= bt
+            xc = solve_triangular(L, solve_triangular(L, rc, lower=True), lower=True, trans='T')
+            if st["saa"]:
+                ry = ry - (P["Bq"] @ xc[st["qcol"]] + P["beta"] * xc[-1])
+            x = np.empty(st["n"])
+            x[st["core_z"]] = xc
+            x[st["y0"]:st["y0"] + st["M"]] = einv(ry)
+            out.append(x)
+        self.clock["solve"] += time.perf_counter() - t0
+        return out
+
+
+class ArrowDeviceBackend:
+    """The arrowhead step on the MI355X for the problems of one group (csrc/hopper_arrow.hip on the partials rato_hopper_slip_f64
+    leaves in HBM; the core through rato_normal_matrix_f64 on the deterministic pattern and the Cholesky of ``DeviceBackend``).
+    eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels to the
+    host per call is the vectors the driver works on and O(q) sums."""
+    name, newton = "device", "arrow"
+
+    def __init__(self, models):
+        import torch
+        from . import _lib
+        self.torch, self._lib, self.lib = torch, _lib, _lib.load()
+        self.models = models
+        m0 = self.m0 = models[0]
+        if any(m.precision != 'f64' for m in models):
+            raise ValueError("the device backend needs Model(..., precision='f64')")
+        self.dev = m0.device
+        st = self.st = arrow_structure(m0)
+        det, lay = st["det"], m0.nlp_layout()
+        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
+        self.maps = dict(ent_of=up(det["ent_of"], np.int32), ptr=up(det["ptr"], np.int64), tri_a=up(det["tri_a"], np.int32),
+                         tri_b=up(det["tri_b"], np.int32), tri_r=up(det["tri_r"], np.int32), hess_src=up(det["hess_src"], np.int32),
+                         row_ptr=up(det["row_ptr"], np.int64), row_idx=up(det["row_idx"], np.int32),
+                         row_col=up(st["core_z"][det["row_col"]], np.int32), col_ptr=up(st["det_indptr_z"], np.int64),
+                         col_idx=up(np.arange(det["nnz"]), np.int32), col_row=up(st["det_rows"], np.int32),
+                         qcol=up(st["qcol"], np.int32), map_defect=up(lay["map_defect"], np.int64),
+                         map_rows=up(lay["map_rows"], np.int64), scale_rows=up(lay["scale_rows"], np.float64),
+                         det_const=up(lay["det_const"], np.float64))
+        self.params = _h.nlp_params(m0.S, m0.time_jump, m0.time_land, m0.dt)
+        self.nch = int(self.lib.rato_hopper_arrow_nchunks(st["M"]))
+        self.npart = int(self.lib.rato_hopper_arrow_npart(st["C"]))
+        if self.nch < 1 or self.npart < 1:
+            raise ValueError(f"newton='arrow' on the device serves 1 <= C <= 50 contact steps, got C = {st['C']}")
+        self.slot = {}
+        self.vals0 = self.dx = self.dfz = self.hessd = self.hess_host = None
+        n_all = len(models)
+        e = lambda *s: torch.empty(s, dtype=torch.float64, device=self.dev)
+        self.L, self.e, self.d = e(n_all, st["nc"], st["nc"]), e(n_all, st["M"]), e(n_all, st["ncon"])
+        self.kk, self.beta = np.zeros(n_all), np.zeros(n_all)
+        self.clock = dict(callbacks=0.0, normal=0.0, factor=0.0, solve=0.0, reduction=0.0, assembly=0.0, products=0.0)
+
+    def _sync(self):
+        self.torch.cuda.synchronize(self.dev)
+
+    def _up(self, rows):
+        return self.torch.as_tensor(np.ascontiguousarray(np.stack(rows), dtype=np.float64), device=self.dev)
+
+    def _empty(self, *shape):
+        return self.torch.empty(shape, dtype=self.torch.float64, device=self.dev)
+
+    def _malpha(self, idx):
+        return np.array([self.st["M"] * float(self.models[i].alpha) for i in idx])
+
+    def _g_rows(self, idx, Zs, lin, h):
+        defect, rows = lin["defect"].cpu().numpy(), lin["rows"].cpu().numpy()
+        slip = np.ascontiguousarray(h.cpu().numpy().transpose(0, 2, 1)).reshape(len(idx), -1)          # row order i C + c
+        return [assemble_g(self.models[i], np.asarray(Z), defect[k], rows[k], slip[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
+
+    def eval_full(self, idx, Zs, lams, sfs):
+        t0 = time.perf_counter()
+        m0, mp, K = self.m0, self.maps, len(idx)
+        Zd, lamd = self._up(Zs), self._up(lams)
+        lin = _h.nlp_linearize_device(self.params, Zd)
+        jac = mp["det_const"][None].repeat(K, 1).contiguous()
+        _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
+        _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
+        slip = m0.slip_device_f64(Zd, lamd, want=("h", "dh_dfz", "dh_dx"))
+        add = self._up([_obj_add(m0, sf) for sf in sfs])
+        m0.slip_hess_blocks_device_f64(Zd, slip["D"], add)
+        lam_dyn, lam_rows = m0.fold_multipliers(np.stack(lams))
+        self.hessd = _h.nlp_hessian_device(self.params, Zd, self._up(list(lam_dyn)), self._up(list(lam_rows)), add)
+        self.vals0, self.dx, self.dfz = jac, slip["dh_dx"], slip["dh_dfz"]
+        self.slot = {i: k for k, i in enumerate(idx)}
+        self.hess_host = self.hessd.cpu().numpy()
+        out = self._g_rows(idx, Zs, lin, slip["h"])
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def eval_g(self, idx, Zs):
+        t0 = time.perf_counter()
+        Zd = self._up(Zs)
+        lin = _h.nlp_linearize_device(self.params, Zd, want=("defect", "rows"))
+        out = self._g_rows(idx, Zs, lin, self.m0.slip_device_f64(Zd, want=("h",))["h"])
+        self.clock["callbacks"] += time.perf_counter() - t0
+        return out
+
+    def hess_apply(self, idx, X):
+        return [_hess_apply(self.st["hess"], self.hess_host[self.slot[i]], x) for i, x in zip(idx, X)]
+
+    def _sel(self, idx):
+        rows = [self.slot[i] for i in idx]
+        if rows == list(range(self.vals0.shape[0])):
+            return self.vals0, self.dx, self.dfz, self.hessd
+        sel = self.torch.as_tensor(rows, device=self.dev)
+        return tuple(t.index_select(0, sel).contiguous() for t in (self.vals0, self.dx, self.dfz, self.hessd))
+
+    def _call(self, name, *args):
+        with self.torch.cuda.device(self.dev):
+            self._lib.check(getattr(self.lib, name)(*args, self._lib.current_stream()), name)
+
+    def _det_matvec(self, name, v0, x, n_out, ptr, lidx, other):
+        st, p = self.st, self._lib.ptr
+        K = x.shape[0]
+        out = self._empty(K, n_out)
+        self._call(name, K, st["ncon"], st["n"], p(v0), v0.shape[1], v0.shape[1], None, 0, 0, p(self.maps[ptr]),
+                   p(self.maps[lidx]), p(self.maps[other]), p(x), x.shape[1], p(out), n_out)
+        return out
+
+    def matvec(self, idx, X):
+        t0 = time.perf_counter()
+        st, p = self.st, self._lib.ptr
+        M, Cn, K = st["M"], st["C"], len(idx)
+        v0, dx, dfz, _ = self._sel(idx)
+        xh = np.stack(X)
+        x = self._up(X)
+        out = self._det_matvec("rato_csc_matvec_f64", v0, x, st["ncon"], "row_ptr", "row_idx", "row_col")
+        xq, xy = self._up(list(xh[:, st["qz"]])), x[:, st["y0"]:st["y0"] + M].contiguous()
+        part, red = self._empty(self.nch, K), self._empty(K)
+        self._call("rato_hopper_arrow_rows_f64", K, M, Cn, int(st["saa"]), 0, p(dx), p(dfz), p(xq), p(xy), None, 0, st["r0"], None,
+                   p(out), st["ncon"], p(part), p(red))
+        o = out.cpu().numpy()
+        if st["saa"]:
+            o[:, st["rr"]] = self._malpha(idx) * xh[:, st["n"] - 1] + red.cpu().numpy()
+        self.clock["products"] += time.perf_counter() - t0
+        return list(o)
+
+    def _cols(self, mode, dx, dfz, w, t, yout):
+        """rato_hopper_arrow_cols_f64 -> (K, 5C + 1) host"""
+        st, p = self.st, self._lib.ptr
+        K = w.shape[0]
+        part, red = self._empty(self.nch, K, 5 * st["C"] + 1), self._empty(K, 5 * st["C"] + 1)
+        self._call("rato_hopper_arrow_cols_f64", K, st["M"], st["C"], int(st["saa"]), mode, p(dx), p(dfz), p(w), w.shape[1], st["r0"],
+                   p(t), p(yout), p(part), p(red))
+        return red.cpu().numpy()
+
+    def _minus_fx_total(self, red):
+        """-sum_c of the fx column sums (the slack and t_risk columns hold -1 in every slip row), contacts ascending one
+        problem-wise addition at a time: np.sum over an axis of a (K, C) array picks its order by K"""
+        tot = np.zeros(red.shape[0])
+        for c in range(self.st["C"]):
+            tot -= red[:, 5 * c + 3]
+        return tot
+
+    def tmatvec(self, idx, W):
+        t0 = time.perf_counter()
+        st = self.st
+        M, Cn, K = st["M"], st["C"], len(idx)
+        v0, dx, dfz, _ = self._sel(idx)
+        wh = np.stack(W)
+        w = self._up(W)
+        out = self._det_matvec("rato_csc_tmatvec_f64", v0, w, st["n"], "col_ptr", "col_idx", "col_row")
+        yout = self._empty(K, M)
+        red = self._cols(0, dx, dfz, w, None, yout)
+        o = out.cpu().numpy()
+        tot = self._minus_fx_total(red)
+        o[:, st["qz"][:5 * Cn]] += red[:, :5 * Cn]
+        o[:, st["n"] - 2] += tot
+        if st["saa"]:
+            o[:, st["n"] - 1] += self._malpha(idx) * wh[:, st["rr"]] + tot
+            o[:, st["y0"]:st["y0"] + M] = yout.cpu().numpy()
+        self.clock["products"] += time.perf_counter() - t0
+        return list(o)
+
+    def schur(self, idx, D, diags, out=None):
+        """-> (Shat (K, nc, lda) device tensor, lower triangle; e (K, M) and d (K, ncon) device; red (K, n_part) and d on the
+        host): the core's Schur complement of the listed problems (``out``: a contiguous (K, nc, lda >= nc) tensor to write into)"""
+        st, torch, mp, p = self.st, self.torch, self.maps, self._lib.ptr
+        M, Cn, nc, K = st["M"], st["C"], st["nc"], len(idx)
+        v0, dx, dfz, hs = self._sel(idx)
+        dh = np.stack(D)
+        d, dgh = self._up(D), np.stack(diags)
+        dg, yd = self._up(list(dgh[:, st["core_z"]])), self._up(list(dgh[:, st["y0"]:st["y0"] + M]))
+        Sh = self._empty(K, nc, nc) if out is None else out
+        if tuple(Sh.shape[:2]) != (K, nc) or Sh.shape[2] < nc or Sh.dtype != torch.float64 or not Sh.is_contiguous():
+            raise ValueError(f"out must be a contiguous device float64 tensor ({K}, {nc}, >= {nc})")
+        t0 = time.perf_counter()
+        self._call("rato_normal_matrix_f64", K, nc, Sh.shape[2], p(v0), v0.shape[1], v0.shape[1], None, 0, 0, p(d), st["ncon"], p(hs),
+                   hs.shape[1] * hs.shape[2], p(dg), p(mp["ent_of"]), p(mp["ptr"]), p(mp["tri_a"]), p(mp["tri_b"]), p(mp["tri_r"]),
+                   p(mp["hess_src"]), p(Sh))
+        self._sync()
+        t1 = time.perf_counter()
+        e, part, red = self._empty(K, M), self._empty(self.nch, K, self.npart), self._empty(K, self.npart)
+        self._call("rato_hopper_arrow_reduce_f64", K, M, Cn, int(st["saa"]), p(dx), p(dfz), p(d), st["ncon"], st["r0"], p(yd), p(e),
+                   p(part), p(red))
+        self._sync()
+        t2 = time.perf_counter()
+        ma = self._up([self._malpha(idx)])[0].contiguous()
+        self._call("rato_hopper_arrow_assemble_f64", K, M, Cn, int(st["saa"]), nc, Sh.shape[2], p(mp["qcol"]), p(red), p(d),
+                   st["ncon"], st["r0"], p(ma), p(Sh))
+        self._sync()
+        t3 = time.perf_counter()
+        self.clock["normal"] += t1 - t0
+        self.clock["reduction"] += t2 - t1
+        self.clock["assembly"] += t3 - t2
+        return Sh, e, d, red.cpu().numpy(), dh
+
+    def factor(self, idx, D, diags):
+        torch, st = self.torch, self.st
+        Sh, e, d, red, dh = self.schur(idx, D, diags)
+        t1 = time.perf_counter()
+        info = chol_factor(Sh).cpu().numpy()
+        sel = torch.as_tensor(list(idx), device=self.dev)
+        self.L[sel], self.e[sel], self.d[sel] = Sh, e, d
+        if st["saa"]:
+            q = st["q"]
+            s = red[:, q * (q + 1) // 2 + 2 * q]
+            d0 = dh[:, st["rr"]]
+            self.kk[list(idx)] = d0 / (1.0 + d0 * s)
+            self.beta[list(idx)] = d0 * self._malpha(idx)
+        self.clock["factor"] += time.perf_counter() - t1
+        return [int(v) for v in info]
+
+    def _einv(self, e, v, kk):
+        """E^-1 v for (K, M) device tensors: u o (v - k (u'v))"""
+        p = self._lib.ptr
+        K, M = v.shape
+        kappa = np.zeros(K)
+        if self.st["saa"]:
+            part, red = self._empty(self.nch, K), self._empty(K)
+            self._call("rato_hopper_arrow_edot_f64", K, M, p(e), p(v), p(part), p(red))
+            kappa = kk * red.cpu().numpy()
+        out, kap = self._empty(K, M), self._up([kappa])[0].contiguous()   # kap stays referenced until the launch is queued
+        self._call("rato_hopper_arrow_eapply_f64", K, M, p(e), p(v), p(kap), p(out))
+        return out
+
+    def solve(self, idx, B):
+        t0 = time.perf_counter()
+        st, p = self.st, self._lib.ptr
+        M, Cn, K, q = st["M"], st["C"], len(idx), st["q"]
+        rows = [self.slot[i] for i in idx]
+        sel = self.torch.as_tensor(list(idx), device=self.dev)
+        ssel = self.torch.as_tensor(rows, device=self.dev)
+        L, e, d = (t.index_select(0, sel) for t in (self.L, self.e, self.d))
+        dx, dfz = self.dx.index_select(0, ssel), self.dfz.index_select(0, ssel)
+        kk, beta = self.kk[list(idx)], self.beta[list(idx)]
+        bh = np.stack(B)
+        rc = bh[:, st["core_z"]].copy()
+        ry = self._up(list(bh[:, st["y0"]:st["y0"] + M]))
+        if st["saa"]:
+            t = self._einv(e, ry, kk)
+            red = self._cols(1, dx, dfz, d, t, None)
+            tot = self._minus_fx_total(red)
+            rc[:, st["qcol"][:5 * Cn]] -= red[:, :5 * Cn]
+            rc[:, -2] -= tot
+            rc[:, -1] -= tot + beta * red[:, 5 * Cn]
+        xc = self._up(list(rc))[:, None, :].contiguous()
+        chol_solve(L, xc)
+        xch = xc[:, 0].cpu().numpy()
+        if st["saa"]:
+            rem = self._empty(K, M)                                    # r_y - B x_c
+            xq, addc = self._up(list(xch[:, st["qcol"]])), self._up([beta * xch[:, -1]])[0].contiguous()
+            self._call("rato_hopper_arrow_rows_f64", K, M, Cn, 1, 1, p(dx), p(dfz), p(xq), p(ry), p(d), st["ncon"], st["r0"], p(addc),
+                       p(rem), M, None, None)
+            ry = rem
+        ry = self._einv(e, ry, kk)
+        out = np.empty((K, st["n"]))
+        out[:, st["core_z"]] = xch
+        out[:, st["y0"]:st["y0"] + M] = ry.cpu().numpy()
+        self.clock["solve"] += time.perf_counter() - t0
+        return list(out)
+
+
 # ---- the method ------------------------------------------------------------------------------------------------------------
 class Problem:
     """one problem's iterate and constants (host, fp64)"""
@@ -695,7 +1187,8 @@ def _group_key(m):
     return (m.method, m.S, m.M, m.time_jump, m.time_land, f)
 
 
-def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None):
+def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
+                newton='dense'):
     """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  The K problems share S, M and the phases;
     problems of one method and one set of friction fields (alpha may differ) form a group that moves through the K-problem
     kernels together, the groups one after the other.  A problem that has ended stops changing and leaves the launches; its Z is
@@ -704,10 +1197,15 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
       backend    'device' (csrc/hopper_ipm.hip) or 'numpy' (the step on the host)
       callbacks  backend='numpy' only: one object per model with g(Z), jac_values(Z), hess_blocks(Z, lam, obj_factor)
       clocks     a dict that receives the seconds spent in callbacks / normal / factor / solve and the wall clock
+      newton     'dense': the condensed matrix over all n = 8(S+1) + 4S + M + 2 variables (the default; n^2 memory, right at the
+                 script's M = 30); 'arrow': the M sample variables ys are eliminated exactly and the 8(S+1) + 4S + 2 core is
+                 factored (``ArrowDeviceBackend`` / ``ArrowNumpyBackend``): memory and work are O(M C), for any M
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
     dual_infeasibility, f, and the final multipliers y, zl, zu with the slacks s and the objective scale sf."""
     if backend not in ('device', 'numpy'):
         raise ValueError(f"backend must be 'device' or 'numpy', got {backend!r}")
+    if newton not in ('dense', 'arrow'):
+        raise ValueError(f"newton must be 'dense' or 'arrow', got {newton!r}")
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
@@ -723,8 +1221,11 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
     t0 = time.perf_counter()
     for members in groups.values():
         ms = [models[i] for i in members]
-        be = DeviceBackend(ms) if backend == 'device' else \
-            NumpyBackend(ms, None if callbacks is None else [callbacks[i] for i in members])
+        cbs = None if callbacks is None else [callbacks[i] for i in members]
+        if newton == 'arrow':
+            be = ArrowDeviceBackend(ms) if backend == 'device' else ArrowNumpyBackend(ms, cbs)
+        else:
+            be = DeviceBackend(ms) if backend == 'device' else NumpyBackend(ms, cbs)
         for i, r in zip(members, _solve_group(ms, [Z0s[i] for i in members], tol, max_iter, be, verbose)):
             out[i] = r
         if clocks is not None:

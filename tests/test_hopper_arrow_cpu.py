@@ -1,0 +1,219 @@
+"""The arrowhead Newton step of ``hopper_ipm`` (newton='arrow') on the host: the exact elimination of the M sample variables
+against the dense condensed matrix, the inertia test, the structured products, and the solver end to end on the fp64 restatement
+(tests/_hopper_nlp.py + oracle/hopper.py).  Bounds are gamma_k sum |terms| against np.longdouble, gamma_k = k u / (1 - k u),
+u = 2^-53, and "100 x what the dense twin reaches" for solves.
+
+Where the values come from.  With the script's phases (S = 6: C = 4) the Jacobian values and Hessian blocks are the
+restatement's at a perturbed point.  The restatement knows no other phases, so the C = 1 cases (phases (1, 6)) take designed
+values on the same fixed pattern: random partials dh/d(x0, x2, x3) and dh/dfz and random deterministic values, the structural
+constants of the risk group (1 on fx, -1 on slack, t_risk and y_i, M alpha) where the pattern has them, random step blocks."""
+import numpy as np
+import pytest
+
+from riskaversetrajopt_amd import hopper, hopper_ipm
+import _hopper_ipm as H
+import _hopper_nlp as R
+from _hopper_ipm import gamma
+
+LD = np.longdouble
+S6 = 6
+
+
+def designed_problem(M, method, phases, seed, alpha=0.2, lam_scale=1e-3):
+    """-> (model, vals (nnz,) on the full pattern, hess (S+1, 78), fields or None)"""
+    model = hopper.Model.host_only(M, method=method, alpha=alpha, S=S6, phases=phases)
+    rng = np.random.RandomState(seed)
+    if phases is None:
+        flds = H.fields(M)
+        cb = H.RestatementCallbacks(model, flds)
+        Z = R.problem(S6, M, seed)
+        lam = lam_scale * rng.randn(model.nlp_layout()["ncon"])
+        return model, cb.jac_values(Z), cb.hess_blocks(Z, lam, 0.3), flds
+    lay = model.nlp_layout()
+    Cn = lay["C"]
+    vals = np.empty(lay["jac_indices"].size)
+    det = np.where(lay["det_const"] != 0.0, lay["det_const"], rng.uniform(-2, 2, lay["det_const"].size))
+    slip = lay["slip_const"].copy()
+    slip[:3 * Cn * M] = rng.uniform(-2, 2, 3 * Cn * M)
+    slip[lay["map_slip_dfz"]] = rng.uniform(-1, 1, Cn * M)
+    vals[lay["pos_det"]], vals[lay["pos_slip"]] = det, slip
+    return model, vals, lam_scale * rng.randn(S6 + 1, hopper.n_pairs), None
+
+
+def graded(rng, size, decades=12):
+    return 10.0 ** rng.uniform(-decades / 2, decades / 2, size)
+
+
+def expand(be, i, st):
+    """the arrow backend's Shat, E and B put back together as the full matrix in z numbering, in extended precision, and the
+    sum of the magnitudes of the terms that Shat's own computation and the expansion add up"""
+    P = be.parts[i]
+    n, nc, M, y0 = st["n"], st["nc"], st["M"], st["y0"]
+    e = P["e"].astype(LD)
+    B = np.zeros((M, nc), dtype=LD)
+    if st["saa"]:
+        B[:, st["qcol"]] = P["Bq"]
+        B[:, nc - 1] += LD(P["beta"])
+    u = 1 / e
+    Einv = np.diag(u) - LD(P["k"]) * np.outer(u, u)
+    E = np.diag(e) + LD(P["d0"]) * np.ones((M, M), dtype=LD)
+    A = P["Shat"].astype(LD) + B.T @ Einv @ B
+    full = np.zeros((n, n), dtype=LD)
+    cz, yz = st["core_z"], np.arange(y0, y0 + M)
+    full[np.ix_(cz, cz)], full[np.ix_(yz, cz)], full[np.ix_(cz, yz)], full[np.ix_(yz, yz)] = A, B, B.T, E
+    mag = np.zeros((n, n), dtype=LD)
+    mag[np.ix_(cz, cz)] = np.abs(B).T @ np.abs(Einv) @ np.abs(B)
+    return full, mag
+
+
+CASES = [(M, method, phases, dw) for M in (1, 4, 65) for method in ('baseline', 'saa') for phases in (None, (1, 6))
+         for dw in (0.0, 1e-4)]
+
+
+@pytest.mark.parametrize("M,method,phases,dw", CASES)
+def test_elimination_is_the_dense_matrix_and_solves_as_well(M, method, phases, dw):
+    """Shat, E and B expanded = ``normal_matrix_host`` entrywise within gamma_(ncon + 3) sum |terms|: an entry sums at most
+    M C + M + 2 + (its deterministic rows) < ncon - 8 S products, each with at most C + 8 roundings of its own (b_i, 1 / e_i with
+    e_i a sum of C + 2 terms, k), so ncon + 3 roundings bound every chain; the terms are those of J' D J + W + diag and, on the
+    core, twice those of B' E^-1 B (once inside Shat, once in the expansion).  Then factor + solve: the relative residual in the
+    DENSE Kc is at most 100 x that of np.linalg.cholesky + triangular solves on the same Kc."""
+    from scipy.linalg import solve_triangular
+    model, vals, hess, _ = designed_problem(M, method, phases, 11 + M)
+    assert model.nlp_layout()["C"] == (4 if phases is None else 1)
+    st, ast = hopper_ipm.structure(model), hopper_ipm.arrow_structure(model)
+    rng = np.random.RandomState(5 + M)
+    d = graded(rng, st["ncon"])
+    diag = rng.uniform(0.5, 2.0, st["n"]) + dw
+    Kc = hopper_ipm.normal_matrix_host(st, vals, d, hess, diag)
+    be = hopper_ipm.ArrowNumpyBackend([model], [None])
+    be.set_values(0, vals, hess)
+    info = be.factor([0], [d], [diag])
+    full, mag_b = expand(be, 0, ast)
+    J = np.zeros((st["ncon"], st["n"]), dtype=LD)
+    J[st["rows"], st["cols"]] = vals
+    W = hopper_ipm.normal_matrix_host(st, np.zeros(st["nnz"]), np.zeros(st["ncon"]), hess)
+    mag = np.abs(J).T @ (d.astype(LD)[:, None] * np.abs(J)) + np.abs(W) + np.diag(diag) + 2 * mag_b
+    err = np.abs(full - Kc.astype(LD))
+    print("M=%d %s C=%d dw=%g: max err / bound = %.3g" % (M, method, ast["C"], dw, float(np.max(err / (gamma(st["ncon"] + 3) * mag + 1e-300)))))
+    assert np.all(err <= gamma(st["ncon"] + 3) * mag)
+    assert info == [0]
+    L = np.linalg.cholesky(Kc)
+    for b in rng.randn(3, st["n"]) * graded(rng, (3, st["n"]), 4):
+        x_ref = solve_triangular(L, solve_triangular(L, b, lower=True), lower=True, trans='T')
+        x, = be.solve([0], [b])
+        res = lambda x: float(np.max(np.abs(Kc.astype(LD) @ x.astype(LD) - b)) / np.max(np.abs(b)))
+        print("   residual arrow %.3e dense %.3e" % (res(x), res(x_ref)))
+        assert res(x) <= 100.0 * res(x_ref)
+
+
+@pytest.mark.parametrize("M,method,phases", [(4, 'saa', None), (4, 'baseline', None), (65, 'saa', (1, 6))])
+def test_inertia_is_what_the_dense_twin_reports(M, method, phases):
+    """W = -1e8 on (u0, u0) of every step: a clear negative direction in the core.  delta_w = 0: both twins report a failed
+    factorization; delta_w = 1e9: both succeed."""
+    model, vals, hess, _ = designed_problem(M, method, phases, 3)
+    tr, tc = np.tril_indices(hopper.n_l)
+    hess = np.zeros_like(hess)
+    hess[:S6, np.flatnonzero((tr == hopper.n_x) & (tc == hopper.n_x))[0]] = -1e8
+    st = hopper_ipm.structure(model)
+    rng = np.random.RandomState(9)
+    d = 10.0 ** rng.uniform(-2, 2, st["ncon"])
+    sigma = rng.uniform(0.5, 2.0, st["n"])
+    arrow, dense = hopper_ipm.ArrowNumpyBackend([model], [None]), hopper_ipm.NumpyBackend([model], [None])
+    arrow.set_values(0, vals, hess)
+    dense.vals[0], dense.hess[0] = vals, hess
+    for dw, good in ((0.0, False), (1e9, True)):
+        ia, idn = arrow.factor([0], [d], [sigma + dw]), dense.factor([0], [d], [sigma + dw])
+        assert (ia == [0]) == good and (idn == [0]) == good, (dw, ia, idn)
+
+
+@pytest.mark.parametrize("M,method,phases", [(1, 'saa', None), (65, 'saa', None), (65, 'baseline', None), (4, 'saa', (1, 6)),
+                                             (65, 'baseline', (1, 6))])
+def test_structured_products_are_the_dense_patterns(M, method, phases):
+    """J v and J' w of the arrow backend (deterministic rows through the pattern, risk rows from the partials) within
+    gamma_(len + 1) |J| |x| of extended precision, len = the entries of the row / column, as the dense pattern's products are"""
+    model, vals, hess, _ = designed_problem(M, method, phases, 21)
+    st = hopper_ipm.structure(model)
+    arrow, dense = hopper_ipm.ArrowNumpyBackend([model], [None]), hopper_ipm.NumpyBackend([model], [None])
+    arrow.set_values(0, vals, hess)
+    dense.vals[0] = vals
+    J = np.zeros((st["ncon"], st["n"]), dtype=LD)
+    J[st["rows"], st["cols"]] = vals
+    rng = np.random.RandomState(M)
+    x, w = rng.randn(st["n"]) * graded(rng, st["n"], 6), rng.randn(st["ncon"]) * graded(rng, st["ncon"], 6)
+    gr = np.array([gamma(int(t) + 1) for t in np.diff(st["row_ptr"])], dtype=LD)
+    gc = np.array([gamma(int(t) + 1) for t in np.diff(st["indptr"])], dtype=LD)
+    for be in (arrow, dense):
+        Jx, JTw = be.matvec([0], [x])[0], be.tmatvec([0], [w])[0]
+        assert np.all(np.abs(Jx - J @ x) <= gr * (np.abs(J) @ np.abs(x)))
+        assert np.all(np.abs(JTw - J.T @ w) <= gc * (np.abs(J).T @ np.abs(w)))
+    hx = arrow.hess_apply([0], [x])[0]
+    assert np.array_equal(hx, hopper_ipm._hess_apply(st, hess, x))
+
+
+# ---- end to end on the restatement -------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def arrow_runs():
+    flds = H.fields(H.M_SMALL)
+    models = [H.host_model('baseline', 0.1), H.host_model('saa', 0.1), H.host_model('saa', 0.3)]
+    cbs = [H.RestatementCallbacks(m, flds) for m in models]
+    kw = dict(backend='numpy', tol=H.TOL, max_iter=3000)
+    (Zb, ib), = hopper_ipm.solve_batch(models[:1], callbacks=cbs[:1], newton='arrow', **kw)
+    Z0s = [models[0].initial_guess(), H.warm_start(models[1], Zb), H.warm_start(models[2], Zb)]
+    batch = hopper_ipm.solve_batch(models, Z0s, callbacks=cbs, newton='arrow', **kw)
+    return dict(fields=flds, models=models, cbs=cbs, Z0s=Z0s, base=(Zb, ib), batch=batch, kw=kw)
+
+
+@pytest.mark.parametrize("k", [0, 1, 2], ids=["baseline", "saa0.1", "saa0.3"])
+def test_arrow_converges_and_the_batch_is_bitwise_the_solo_runs(arrow_runs, k):
+    r = arrow_runs
+    Z, info = r["batch"][k]
+    assert info["status"] == "converged" and info["backend"] == "numpy"
+    H.check_solution(r["models"][k], r["fields"], Z, info)
+    if k == 0:
+        Z1, i1 = r["base"]
+    else:
+        (Z1, i1), = hopper_ipm.solve_batch([r["models"][k]], [r["Z0s"][k]], callbacks=[r["cbs"][k]], newton='arrow', **r["kw"])
+    assert Z.tobytes() == Z1.tobytes() and (info["iterations"], info["factorizations"]) == (i1["iterations"], i1["factorizations"])
+    (Zd, idn), = hopper_ipm.solve_batch([r["models"][k]], [r["Z0s"][k]], callbacks=[r["cbs"][k]], newton='dense', **r["kw"])
+    print("S=6 M=4 %s: arrow %d it / %d fact, dense %d it / %d fact, |f_arrow - f_dense| = %.3e" %
+          (("baseline", "saa0.1", "saa0.3")[k], info["iterations"], info["factorizations"], idn["iterations"], idn["factorizations"],
+           abs(info["f"] - idn["f"])))
+
+
+def test_arrow_at_M_200(arrow_runs):
+    """one alpha at S = 6, M = 200 (n = 278 dense, 78 in the core), from the small baseline's states and controls"""
+    M = 200
+    flds = H.fields(M)
+    model = H.host_model('saa', 0.1, S6, M)
+    cb = H.RestatementCallbacks(model, flds)
+    Z0 = H.warm_start(model, arrow_runs["base"][0])
+    (Z, info), = hopper_ipm.solve_batch([model], [Z0], callbacks=[cb], newton='arrow', **arrow_runs["kw"])
+    print("S=6 M=200 saa0.1: arrow %s %d it / %d fact, f = %.6f" % (info["status"], info["iterations"], info["factorizations"], info["f"]))
+    assert info["status"] == "converged"
+    H.check_solution(model, flds, Z, info)
+
+
+def test_newton_keyword_is_checked():
+    with pytest.raises(ValueError):
+        hopper_ipm.solve_batch([H.host_model('baseline', 0.1)], backend='numpy', newton='sparse')
+
+
+def test_arrow_structure_scales_with_M_times_C():
+    """M = 20 000 at S = 6: the dense structure's ent_of alone would be 20 086^2 entries; every array of the arrow structure
+    stays within 8 (ncon + 7 M C) elements"""
+    M = 20000
+    model = hopper.Model.host_only(M, 'saa', S=S6)
+    st = hopper_ipm.arrow_structure(model)
+    ncon, _ = model.risk_rows_offset()
+    limit = 8 * (ncon + 7 * M * st["C"])
+    seen = []
+
+    def walk(x):
+        if isinstance(x, dict):
+            for v in x.values():
+                walk(v)
+        elif isinstance(x, np.ndarray):
+            seen.append(x.size)
+    walk(st)
+    assert seen and max(seen) <= limit, (max(seen), limit)
+    assert st["nc"] == 8 * (S6 + 1) + 4 * S6 + 2 and st["det"]["ent_of"].size == st["nc"] ** 2

@@ -11,6 +11,14 @@ bench.py is the flagship benchmark):
 
     python tools/hopper_solve_bench.py [--out profiles/hopper_solve.json] [--S 30 --M 30]
 
+``--newton arrow --M 30,1000,10000`` measures the arrowhead Newton step (``hopper_ipm``, newton='arrow') instead,
+into profiles/hopper_solve_large_m.json: per M the same two runs (one run after a warm-up, the same call capped at three
+iterations), the training fields being the script's 30 of ``RandomState(1)`` extended to M by further draws of the same stream;
+per problem the record above; the per-iteration split callbacks / reduction / assembly / factor / solves / products / host;
+every solution's safe fraction and AVaR on the script's 10 000 validation fields (the draws that follow the 30 training fields
+on the same stream, hopper.py:974-979); and at M = 30 the dense step in the same process.  The file is rewritten after every M,
+and a later call with other M adds them to it.
+
 Prints one JSON line.  There is no CPU fallback: without a GPU nothing is measured.
 """
 import argparse
@@ -51,16 +59,92 @@ def run(backend, args):
             "saa_split": split(clocks["saa"], max([r["iterations"] for r in saa.values()] + [0]))}
 
 
+def arrow_split(clock, iters):
+    wall = clock["wall"]
+    parts = {"callbacks": clock.get("callbacks", 0.0), "reduction": clock.get("reduction", 0.0),
+             "assembly": clock.get("normal", 0.0) + clock.get("assembly", 0.0), "factor": clock.get("factor", 0.0),
+             "solves": clock.get("solve", 0.0), "products": clock.get("products", 0.0)}
+    parts["host"] = wall - sum(parts.values())
+    return {"wall_s": wall, "batch_iterations": iters, "seconds": parts,
+            "ms_per_iteration": {k: 1e3 * v / max(iters, 1) for k, v in parts.items()}}
+
+
+def script_fields(M_max):
+    """-> (training fields (M_max, 30) x 3: the script's 30 then further draws, validation fields (10000, 30) x 3)"""
+    from riskaversetrajopt_amd import hopper
+    rng = np.random.RandomState(1)
+    first = hopper.sample_friction_fields(30, rng)
+    val = hopper.sample_friction_fields(10000, rng)
+    more = hopper.sample_friction_fields(max(M_max - 30, 1), rng)
+    return tuple(np.concatenate([a, b])[:M_max] for a, b in zip(first, more)), val
+
+
+def run_arrow(M, newton, args, train, val_model, max_iter=3000):
+    from riskaversetrajopt_amd import scp
+    clocks = {}
+    fields = tuple(f[:M] for f in train)
+    out = scp.hopper_experiment(alphas=args.alphas, M=M, S=args.S, tol=1e-3, max_iter=max_iter, clocks=clocks, newton=newton,
+                                fields=fields)
+
+    def record(r, alpha):
+        rec = problem_record(r, args.S)
+        st = val_model.monte_carlo_statistics(*val_model.contact_inputs(r["Z"]), alpha=alpha if alpha else 0.5)
+        rec["validation_safe_fraction"] = float(st["frac_satisfied"])
+        if alpha:
+            rec["validation_avar"] = float(st["cvar"])
+        return rec
+    base = record(out["base"], None)
+    saa = {str(a): record(r, a) for a, r in zip(out["alphas"], out["results"])}
+    split_of = arrow_split if newton == 'arrow' else split
+    return {"baseline": base, "saa": saa, "wall_s": out["wall_s"], "baseline_split": split_of(clocks["base"], base["iterations"]),
+            "saa_split": split_of(clocks["saa"], max([r["iterations"] for r in saa.values()] + [0]))}
+
+
+def main_arrow(args):
+    import torch
+    from riskaversetrajopt_amd import hopper
+    Ms = [int(m) for m in str(args.M).split(",")]
+    train, val = script_fields(max(Ms))
+    val_model = hopper.Model(10000, 'saa', 0.1, S=args.S, fields=val)
+    out = {"device": torch.cuda.get_device_name(0), "S": args.S, "tol": 1e-3, "max_iter": 3000, "newton": "arrow",
+           "validation_fields": 10000, "runs": {}}
+    if args.out and os.path.exists(args.out):                        # a later call adds its M to the file of an earlier one
+        with open(args.out) as f:
+            old = json.loads(f.readline())
+        if all(old.get(k) == out[k] for k in ("device", "S", "tol", "max_iter", "newton")):
+            out["runs"] = old.get("runs", {})
+    for M in Ms:
+        run_arrow(M, 'arrow', args, train, val_model, max_iter=3)       # warm-up: library, maps, allocator
+        rec = {"arrow": run_arrow(M, 'arrow', args, train, val_model)}
+        if M == 30:
+            run_arrow(M, 'dense', args, train, val_model, max_iter=3)
+            rec["dense"] = run_arrow(M, 'dense', args, train, val_model)
+        out["runs"][str(M)] = rec
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out) + "\n")
+        print("M = %d done: baseline %s, saa %s, wall %.2f s" % (M, rec["arrow"]["baseline"]["status"],
+              [r["status"] for r in rec["arrow"]["saa"].values()], rec["arrow"]["wall_s"]), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--S", type=int, default=30)
-    ap.add_argument("--M", type=int, default=30)
+    ap.add_argument("--M", default="30", help="with --newton arrow: a comma-separated list")
+    ap.add_argument("--newton", choices=("dense", "arrow"), default="dense")
     ap.add_argument("--alphas", type=float, nargs="*", default=[0.05, 0.1, 0.2, 0.3, 0.5, 0.75])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hopper_solve.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("hopper_solve_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "hopper_solve_large_m.json" if args.newton == "arrow" else "hopper_solve.json")
+    if args.newton == "arrow":
+        return main_arrow(args)
+    args.M = int(args.M)
     run("device", args)                                              # warm-up: library load, maps, allocator
     out = {"device": torch.cuda.get_device_name(0), "S": args.S, "M": args.M, "tol": 1e-3, "max_iter": 3000,
            "backend_device": run("device", args), "backend_numpy": run("numpy", args)}
