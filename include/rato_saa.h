@@ -1283,7 +1283,8 @@ int rato_csc_tmatvec_f64(int32_t K, int64_t ncon, int64_t n, const double* vals0
                          int64_t ld1, int64_t n1, const int64_t* col_ptr, const int32_t* col_idx, const int32_t* col_row,
                          const double* w /* [K][ldw] */, int64_t ldw, double* out /* [K][ldo] */, int64_t ldo, void* stream);
 
-/* In-place blocked Cholesky A = L L' of K row-major matrices A[k] (n x n, leading dimension lda >= n), lower triangle: only
+/* ---- Batched Cholesky, fp64 (csrc/chol.hip, on the workgroup functions of csrc/rato_chol.h; riskaversetrajopt_amd/ipm.py).
+ * In-place blocked Cholesky A = L L' of K row-major matrices A[k] (n x n, leading dimension lda >= n), lower triangle: only
  * entries with b <= a < n are read or written, so the strict upper triangle and the padding may hold anything (NaN included).
  * One workgroup per problem, panels of rato_chol_panel_width() columns.  info[k] = 0, or j + 1 for the first pivot j that is
  * not a positive finite number: that problem stops there (its matrix is left partly factored), the others are not affected and
@@ -1358,7 +1359,7 @@ int rato_dense_tmatvec_f64(int32_t K, int32_t n, const double* J0, int32_t m0, i
 int rato_tril_symv_f64(int32_t K, int32_t n, const double* hess_tril, const double* x, int64_t ldx, double* out, int64_t ldo,
                        void* stream);
 
-/* ---- Arrowhead Newton step of the hopper's interior-point solve at large M, fp64 (csrc/hopper_arrow.hip; hopper_ipm.py,
+/* ---- Arrowhead Newton step of the hopper's interior-point solve at large M, fp64 (csrc/hopper_arrow.hip; hopper_arrow.py,
  * newton='arrow').  ABI: additive (RATO_ABI_VERSION stays 12).  K problems per launch, device pointers, stream ordered, no
  * allocation.  No floating-point atomics: every output has one owner that sums in a fixed order, so two calls are bitwise equal
  * and problem k of a batch is bitwise its K = 1 call.

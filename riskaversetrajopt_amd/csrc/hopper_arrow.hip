@@ -1,4 +1,4 @@
-// Arrowhead Newton step of the hopper's interior-point solver at large M (riskaversetrajopt_amd/hopper_ipm.py, newton='arrow';
+// Arrowhead Newton step of the hopper's interior-point solver at large M (riskaversetrajopt_amd/hopper_arrow.py, newton='arrow';
 // DESIGN §7.af), fp64, K problems per launch.
 //
 // The M variables ys enter the condensed matrix Kc only through E = diag(e) + d_0 1 1', so they are eliminated exactly and what

@@ -16,19 +16,15 @@
 // butterfly of its wave, then the four waves in order), and nothing a workgroup computes depends on K or on its neighbours, so
 // problem k of a batch is bitwise its K = 1 run.
 //
-// The Cholesky and the triangular solves follow csrc/hopper_ipm.hip (right-looking, panels of QP_NB = 32 columns: the diagonal
-// block in wave 0's registers, the rows below one lane per row, the trailing matrix in 64 x 64 tiles with the panel slices staged
-// in LDS); they are device functions of this kernel because a solve must not leave the workgroup.
-#include "rato_common.h"
+// The Cholesky and the triangular solves are the workgroup functions of csrc/rato_chol.h, the ones csrc/chol.hip launches on
+// their own: called here because a solve must not leave the workgroup.
+#include "rato_chol.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int QP_BLOCK = 256;
-constexpr int QP_NB = 32;             // panel width
-constexpr int QP_TILE = 64;           // trailing-update tile
-constexpr int QP_LD = QP_NB + 1;      // LDS row stride of a staged slice
 constexpr int QP_MAX_N = 256, QP_MAX_M = 384;
 constexpr int QP_HARD_CAP = 200;      // iterations, whatever max_iter says
 constexpr int QP_MAX_RETRIES = 12;    // of one factorization
@@ -43,10 +39,11 @@ enum { HAS_L = 1, HAS_U = 2, IS_EQ = 4 };
 __host__ __device__ constexpr int even(int x) { return (x + 1) & ~1; }
 // doubles of dynamic LDS: the Cholesky's three staging tiles, the vectors, 8 words of reduction scratch; then 4 int32
 __host__ __device__ constexpr size_t lds_bytes(int n, int m) {
-  return sizeof(double) * ((size_t)QP_NB * QP_LD + 2 * (size_t)QP_TILE * QP_LD + (size_t)QP_M_VECS * even(m) +
-                           (size_t)QP_N_VECS * even(n) + 8) + 16;
+  return sizeof(double) * ((size_t)rato::CHOL_LDS_DOUBLES + (size_t)QP_M_VECS * even(m) + (size_t)QP_N_VECS * even(n) + 8) + 16;
 }
-static_assert((QP_NB * QP_LD) % 2 == 0 && (QP_TILE * QP_LD) % 2 == 0, "every carve offset is a multiple of 16 bytes");
+static_assert((rato::CHOL_NB * rato::CHOL_LD) % 2 == 0 && (rato::CHOL_TILE * rato::CHOL_LD) % 2 == 0,
+              "every carve offset is a multiple of 16 bytes");
+static_assert(QP_BLOCK == rato::CHOL_BLOCK, "the Cholesky's workgroup");
 static_assert(lds_bytes(QP_MAX_N, QP_MAX_M) <= 160 * 1024, "one workgroup's LDS");
 
 __device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }   // false for NaN
@@ -93,160 +90,6 @@ __device__ __forceinline__ void rows_matvec(const Ctx& c, const double* __restri
   }
 }
 
-// ---- Cholesky of the lower triangle of Kc (n x n, leading dimension ld), in place; -> 1 when every pivot was positive --------
-__device__ __forceinline__ int chol_factor(const Ctx& c, double* A, int ld, double* Ld, double* Li, double* Lj) {
-  const int tid = c.tid, n = c.n;
-  int32_t* bad = c.word + 1;
-  if (tid == 0) *bad = 0;
-  __syncthreads();
-  for (int j0 = 0; j0 < n; j0 += QP_NB) {
-    const int nb = min(QP_NB, n - j0);
-    // 1. the diagonal block, wave 0, registers; rows and columns past n act as the identity
-    if (tid < RATO_WAVE) {
-      const int r = tid;
-      double row[QP_NB];
-#pragma unroll
-      for (int cc = 0; cc < QP_NB; ++cc)
-        row[cc] = (r < nb && cc <= r && cc < nb) ? A[(int64_t)(j0 + r) * ld + j0 + cc] : ((r == cc) ? 1.0 : 0.0);
-      int fail = 0;
-#pragma unroll
-      for (int j = 0; j < QP_NB; ++j) {
-        const double piv = __shfl(row[j], j, RATO_WAVE);
-        if (!fail && !(piv > 0.0 && piv <= 1.79769313486231570815e308)) fail = 1;   // wave-uniform
-        const double dj = sqrt(piv);
-        if (r == j) row[j] = dj;
-        else if (r > j) row[j] = row[j] / dj;
-#pragma unroll
-        for (int cc = j + 1; cc < QP_NB; ++cc) {
-          const double lcj = __shfl(row[j], cc, RATO_WAVE);
-          if (r >= cc) row[cc] -= row[j] * lcj;
-        }
-        __builtin_amdgcn_sched_barrier(0);   // keeps the next column's shuffles from being hoisted (no scratch)
-      }
-      if (fail) {
-        if (tid == 0) *bad = 1;
-      } else if (r < QP_NB) {
-#pragma unroll
-        for (int cc = 0; cc < QP_NB; ++cc) {
-          Ld[r * QP_LD + cc] = row[cc];
-          if (r < nb && cc <= r) A[(int64_t)(j0 + r) * ld + j0 + cc] = row[cc];
-        }
-      }
-    }
-    __syncthreads();
-    if (*bad) break;                               // every lane reads the same word after the barrier
-    const int i0 = j0 + QP_NB;                     // first row below the block
-    if (i0 >= n) break;
-    // 2. rows below: x L11' = a, one lane per row
-    for (int i = i0 + tid; i < n; i += QP_BLOCK) {
-      double* a = A + (int64_t)i * ld + j0;
-      double x[QP_NB];
-#pragma unroll
-      for (int cc = 0; cc < QP_NB; ++cc) x[cc] = a[cc];
-#pragma unroll
-      for (int cc = 0; cc < QP_NB; ++cc) {
-        double s = x[cc];
-#pragma unroll
-        for (int p = 0; p < cc; ++p) s -= x[p] * Ld[cc * QP_LD + p];
-        x[cc] = s / Ld[cc * QP_LD + cc];
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int cc = 0; cc < QP_NB; ++cc) a[cc] = x[cc];
-    }
-    __syncthreads();
-    // 3. trailing update, 64 x 64 tiles of the lower triangle
-    const int tx = tid & 15, ty = tid >> 4;
-    for (int ti = i0; ti < n; ti += QP_TILE) {
-      for (int tj = i0; tj <= ti; tj += QP_TILE) {
-        for (int e = tid; e < QP_TILE * QP_NB; e += QP_BLOCK) {
-          const int r = e / QP_NB, cc = e - r * QP_NB;
-          Li[r * QP_LD + cc] = (ti + r < n) ? A[(int64_t)(ti + r) * ld + j0 + cc] : 0.0;
-          Lj[r * QP_LD + cc] = (tj + r < n) ? A[(int64_t)(tj + r) * ld + j0 + cc] : 0.0;
-        }
-        __syncthreads();
-        double acc[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
-#pragma unroll 4
-        for (int p = 0; p < QP_NB; ++p) {
-          double li[4], lj[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            li[u] = Li[(ty + 16 * u) * QP_LD + p];
-            lj[u] = Lj[(tx + 16 * u) * QP_LD + p];
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[u][v] += li[u] * lj[v];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int i = ti + ty + 16 * u, j = tj + tx + 16 * v;
-            if (i < n && j <= i) A[(int64_t)i * ld + j] -= acc[u][v];
-          }
-        __syncthreads();
-      }
-    }
-  }
-  __syncthreads();
-  const int ok = *bad == 0;
-  __syncthreads();                                 // nobody resets the word before everyone has read it
-  return ok;
-}
-
-// L L' x = b in place on xs (LDS, n doubles); ends behind a barrier
-__device__ __forceinline__ void chol_solve(const Ctx& c, const double* L, int ld, double* xs) {
-  const int tid = c.tid, n = c.n;
-  __syncthreads();
-  for (int j0 = 0; j0 < n; j0 += QP_NB) {          // L y = b
-    const int nb = min(QP_NB, n - j0);
-    if (tid < RATO_WAVE) {                         // the diagonal block, wave 0: lane r owns row j0 + r
-      const int r = tid;
-      double x = (r < nb) ? xs[j0 + r] : 0.0;
-      for (int cc = 0; cc < nb; ++cc) {
-        if (r == cc) x = x / L[(int64_t)(j0 + cc) * ld + j0 + cc];
-        const double xc = __shfl(x, cc, RATO_WAVE);
-        if (r > cc && r < nb) x -= L[(int64_t)(j0 + r) * ld + j0 + cc] * xc;
-      }
-      if (r < nb) xs[j0 + r] = x;
-    }
-    __syncthreads();
-    for (int i = j0 + QP_NB + tid; i < n; i += QP_BLOCK) {   // rows below: contiguous reads of their own row
-      const double* l = L + (int64_t)i * ld + j0;
-      double s = xs[i];
-      for (int p = 0; p < QP_NB; ++p) s -= l[p] * xs[j0 + p];
-      xs[i] = s;
-    }
-    __syncthreads();
-  }
-  for (int j0 = ((n - 1) / QP_NB) * QP_NB; j0 >= 0; j0 -= QP_NB) {   // L' x = y, blocks from the end
-    const int nb = min(QP_NB, n - j0);
-    if (tid < RATO_WAVE) {
-      const int r = tid;
-      double x = (r < nb) ? xs[j0 + r] : 0.0;
-      for (int cc = nb - 1; cc >= 0; --cc) {
-        if (r == cc) x = x / L[(int64_t)(j0 + cc) * ld + j0 + cc];
-        const double xc = __shfl(x, cc, RATO_WAVE);
-        if (r < cc) x -= L[(int64_t)(j0 + cc) * ld + j0 + r] * xc;
-      }
-      if (r < nb) xs[j0 + r] = x;
-    }
-    __syncthreads();
-    for (int i = tid; i < j0; i += QP_BLOCK) {     // rows above: column i of the block's rows, consecutive across lanes
-      double s = xs[i];
-      for (int p = 0; p < nb; ++p) s -= L[(int64_t)(j0 + p) * ld + i] * xs[j0 + p];
-      xs[i] = s;
-    }
-    __syncthreads();
-  }
-}
-
 struct Vecs {
   double *lo, *up, *sl, *su, *ll, *lu, *rl, *ru, *D, *t, *dsl, *dsu, *dll, *dlu, *cl, *cu;   // m
   double *z, *dz, *rhs, *rd, *diag, *tv;                                                      // n
@@ -281,7 +124,7 @@ __device__ __forceinline__ void newton_step(const Ctx& c, const Vecs& v, const d
       }
       v.tv[a] = s;
     }
-    chol_solve(c, Kc, n, v.tv);
+    rato::chol_solve(Kc, n, n, v.tv);
     for (int a = tid; a < n; a += QP_BLOCK) v.dz[a] = rep > 0 ? v.dz[a] + v.tv[a] : v.tv[a];
     __syncthreads();
   }
@@ -345,9 +188,9 @@ __global__ __launch_bounds__(QP_BLOCK) void qp_ipm_kernel(
 
   double* base = reinterpret_cast<double*>(smem);
   double* Ld = base;
-  double* Li = Ld + QP_NB * QP_LD;
-  double* Lj = Li + QP_TILE * QP_LD;
-  double* mv = Lj + QP_TILE * QP_LD;
+  double* Li = Ld + rato::CHOL_NB * rato::CHOL_LD;
+  double* Lj = Li + rato::CHOL_TILE * rato::CHOL_LD;
+  double* mv = Ld + rato::CHOL_LDS_DOUBLES;
   const int mp = even(m), np = even(n);
   Vecs v;
   v.lo = mv, v.up = mv + mp, v.sl = mv + 2 * mp, v.su = mv + 3 * mp, v.ll = mv + 4 * mp, v.lu = mv + 5 * mp, v.rl = mv + 6 * mp;
@@ -519,7 +362,7 @@ __global__ __launch_bounds__(QP_BLOCK) void qp_ipm_kernel(
         else if (b == a) Kc[(int64_t)a * n + a] = v.diag[a] + dw;
       }
       __syncthreads();
-      ok = chol_factor(c, Kc, n, Ld, Li, Lj);       // the same in every lane
+      ok = rato::chol_factor(Kc, n, n, Ld, Li, Lj, c.word + 1) == 0;   // the same in every lane
       ++nfact;
       dw_last = dw;
       if (ok) break;

@@ -1,5 +1,5 @@
 """Batched interior-point solve of the drone Gaussian baseline's NLP (drone/drone_gaussian.py:400-534: what the script hands
-to IPOPT), on the driver of ``hopper_ipm`` (``Problem``, ``newton_steps``, ``_solve_group``: DESIGN §7.ad, §7.ae).
+to IPOPT), by the method of ``ipm`` (``Problem``, ``newton_steps``, ``solve_group``: DESIGN §7.ad, §7.ae).
 
 Formulation.  The script's g is (the n_nl non-linear rows, z itself, the allocation sum).  The nvar identity rows are bounds on
 z, intersected with x_L / x_U = -+1000:  u in [u_min, u_max], allocations in [1e-6, alpha] -- the same feasible set, and every
@@ -10,26 +10,24 @@ the host folds into the diagonal term of the condensed matrix and adds to W x.
 The constraint matrix is dense: J = [jac_nl; the sum row] (m x nvar).  Two backends do the step:
   'device'  one ``linearize_device`` and one ``hessian_device`` call per iteration for the active problems, then
             rato_dense_normal_matrix_f64 / rato_chol_factor_batch_f64 / rato_chol_solve_batch_f64 / rato_dense_matvec_f64 /
-            rato_dense_tmatvec_f64 / rato_tril_symv_f64 (csrc/drone_gaussian_ipm.hip, csrc/hopper_ipm.hip) on jac_nl and the
+            rato_dense_tmatvec_f64 / rato_tril_symv_f64 (csrc/drone_gaussian_ipm.hip, csrc/chol.hip) on jac_nl and the
             packed Hessian where they lie.  Up go the points, the multipliers (K, n_nl), d, the diagonals and the vectors;
             down come g_nl, the matvec results, the factorization's info and the solutions.  jac_nl, the packed Hessian and
             Kc / L never leave the device.
   'numpy'   the whole step on the host on injected (or the model's) callbacks dict(linearize, hessian).
 alpha enters only the host-side bounds, so the problems of one S form a group whatever their alpha.
 """
-import time
-
 import numpy as np
 
 from . import drone_params as P
-from . import hopper_ipm as _ipm
+from . import ipm as _ipm
 
 STATUSES = _ipm.STATUSES
 X_BOUND = 1000.0                                                 # the script's x_L / x_U (:446-447)
 
 
 class Nlp:
-    """what ``hopper_ipm.Problem`` reads of a model: num_vars, gL_gU() on the m = n_nl + 1 rows, x_bounds(), f, grad_f"""
+    """what ``ipm.Problem`` reads of a model: num_vars, gL_gU() on the m = n_nl + 1 rows, x_bounds(), f, grad_f"""
 
     def __init__(self, model):
         from . import drone_gaussian as dg
@@ -84,40 +82,34 @@ def normal_matrix_host(J, d, hess_tril=None, diag=None):
 
 
 # ---- backends ----------------------------------------------------------------------------------------------------------------
-def _new_clock():
-    return dict(callbacks=0.0, normal=0.0, factor=0.0, solve=0.0, matvec=0.0)
-
-
-class NumpyBackend:
+class NumpyBackend(_ipm.Backend):
     """the whole step on the host.  ``callbacks[i]`` serves nlps[i]: dict(linearize(Z) -> (g_nl, jac_nl), hessian(Z, lam) -> tril)"""
     name = "numpy"
 
     def __init__(self, nlps, callbacks=None):
+        super().__init__("matvec")
         self.nlps = nlps
         self.cb = [p.model.device_callbacks() for p in nlps] if callbacks is None else list(callbacks)
         self.st = None
-        self.J, self.hess, self.sf, self.L = {}, {}, {}, {}
-        self.clock = _new_clock()
+        self.J, self.hess, self.sf = {}, {}, {}
 
     def eval_full(self, idx, Zs, lams, sfs):
-        t0 = time.perf_counter()
-        out = []
-        for i, Z, lam, sf in zip(idx, Zs, lams, sfs):
-            nlp = self.nlps[i]
-            g_nl, jac_nl = self.cb[i]["linearize"](np.asarray(Z, dtype=np.float64))
-            self.J[i] = np.vstack([np.asarray(jac_nl, dtype=np.float64), nlp.sum_row()[None, :]])
-            self.hess[i] = np.asarray(self.cb[i]["hessian"](np.asarray(Z, dtype=np.float64),
-                                                            np.asarray(lam, dtype=np.float64)[:nlp.n_nl]), dtype=np.float64)
-            self.sf[i] = float(sf)
-            out.append(nlp.g(Z, np.asarray(g_nl, dtype=np.float64)))
-        self.clock["callbacks"] += time.perf_counter() - t0
+        with self.timed("callbacks"):
+            out = []
+            for i, Z, lam, sf in zip(idx, Zs, lams, sfs):
+                nlp = self.nlps[i]
+                g_nl, jac_nl = self.cb[i]["linearize"](np.asarray(Z, dtype=np.float64))
+                self.J[i] = np.vstack([np.asarray(jac_nl, dtype=np.float64), nlp.sum_row()[None, :]])
+                self.hess[i] = np.asarray(self.cb[i]["hessian"](np.asarray(Z, dtype=np.float64),
+                                                                np.asarray(lam, dtype=np.float64)[:nlp.n_nl]), dtype=np.float64)
+                self.sf[i] = float(sf)
+                out.append(nlp.g(Z, np.asarray(g_nl, dtype=np.float64)))
         return out
 
     def eval_g(self, idx, Zs):
-        t0 = time.perf_counter()
-        out = [self.nlps[i].g(Z, np.asarray(self.cb[i]["linearize"](np.asarray(Z, dtype=np.float64))[0], dtype=np.float64))
-               for i, Z in zip(idx, Zs)]
-        self.clock["callbacks"] += time.perf_counter() - t0
+        with self.timed("callbacks"):
+            out = [self.nlps[i].g(Z, np.asarray(self.cb[i]["linearize"](np.asarray(Z, dtype=np.float64))[0], dtype=np.float64))
+                   for i, Z in zip(idx, Zs)]
         return out
 
     def set_values(self, J, hess, sfs):
@@ -130,41 +122,27 @@ class NumpyBackend:
         return [unpack_tril(self.hess[i], x.size) @ x + self.sf[i] * self.nlps[i].curv * x for i, x in zip(idx, X)]
 
     def matvec(self, idx, X):
-        t0 = time.perf_counter()
-        out = [self.J[i] @ x for i, x in zip(idx, X)]
-        self.clock["matvec"] += time.perf_counter() - t0
+        with self.timed("matvec"):
+            out = [self.J[i] @ x for i, x in zip(idx, X)]
         return out
 
     def tmatvec(self, idx, W):
-        t0 = time.perf_counter()
-        out = [self.J[i].T @ w for i, w in zip(idx, W)]
-        self.clock["matvec"] += time.perf_counter() - t0
+        with self.timed("matvec"):
+            out = [self.J[i].T @ w for i, w in zip(idx, W)]
         return out
 
     def factor(self, idx, D, diags):
         info = []
         for i, d, dg in zip(idx, D, diags):
-            t0 = time.perf_counter()
-            Kc = normal_matrix_host(self.J[i], d, self.hess[i], dg + self.sf[i] * self.nlps[i].curv)
-            t1 = time.perf_counter()
-            ok = bool(np.all(np.isfinite(Kc)))
-            if ok:
-                try:
-                    self.L[i] = np.linalg.cholesky(Kc)
-                except np.linalg.LinAlgError:
-                    ok = False
-            self.clock["normal"] += t1 - t0
-            self.clock["factor"] += time.perf_counter() - t1
-            info.append(0 if ok else 1)
+            with self.timed("normal"):
+                Kc = normal_matrix_host(self.J[i], d, self.hess[i], dg + self.sf[i] * self.nlps[i].curv)
+            with self.timed("factor"):
+                info.append(self.factor_host(i, Kc))
         return info
 
     def solve(self, idx, B):
-        from scipy.linalg import solve_triangular
-        t0 = time.perf_counter()
-        out = [solve_triangular(self.L[i], solve_triangular(self.L[i], b, lower=True), lower=True, trans='T')
-               for i, b in zip(idx, B)]
-        self.clock["solve"] += time.perf_counter() - t0
-        return out
+        with self.timed("solve"):
+            return [self.solve_host(i, b) for i, b in zip(idx, B)]
 
 
 def _check(t, name, dims=None):
@@ -258,54 +236,43 @@ def tril_symv(n, hess_tril, x):
     return out
 
 
-class DeviceBackend:
+class DeviceBackend(_ipm.DeviceBase):
     """the step on the MI355X for the problems of one group (same S; alpha may differ).  Every call serves the listed problems
     in ONE launch each; nothing a kernel computes for a problem depends on the others."""
     name = "device"
 
     def __init__(self, nlps):
-        import torch
-        self.torch = torch
         self.nlps = nlps
         self.m0 = nlps[0].model
         self.m0._handle()
-        self.dev = self.m0.device
+        super().__init__(self.m0.device, len(nlps), "matvec")
         self.n, self.n_nl = nlps[0].num_vars, nlps[0].n_nl
         self.st = None
-        self.sum_row = torch.as_tensor(nlps[0].sum_row()[None, :].copy(), device=self.dev)
-        self.slot, self.sf = {}, {}
-        self.jac = self.hess = self.L = None
-        self.clock = _new_clock()
-
-    def _sync(self):
-        self.torch.cuda.synchronize(self.dev)
-
-    def _up(self, rows):
-        return self.torch.as_tensor(np.ascontiguousarray(np.stack(rows), dtype=np.float64), device=self.dev)
+        self.sum_row = self.torch.as_tensor(nlps[0].sum_row()[None, :].copy(), device=self.dev)
+        self.sf = {}
+        self.jac = self.hess = None
 
     def _g(self, idx, Zs, g_nl):
         g_nl = g_nl.cpu().numpy()
         return [self.nlps[i].g(Z, g_nl[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
 
     def eval_full(self, idx, Zs, lams, sfs):
-        t0 = time.perf_counter()
-        with self.torch.cuda.device(self.dev):
-            Zd = self._up(Zs)
-            r = self.m0.linearize_device(Zd)
-            self.hess = self.m0.hessian_device(Zd, self._up([np.asarray(l)[:self.n_nl] for l in lams]))
-        self.jac = r["jac_nl"]
-        self.slot = {i: k for k, i in enumerate(idx)}
-        for i, sf in zip(idx, sfs):
-            self.sf[i] = float(sf)
-        out = self._g(idx, Zs, r["g_nl"])
-        self.clock["callbacks"] += time.perf_counter() - t0
+        with self.timed("callbacks"):
+            with self.torch.cuda.device(self.dev):
+                Zd = self._up(Zs)
+                r = self.m0.linearize_device(Zd)
+                self.hess = self.m0.hessian_device(Zd, self._up([np.asarray(l)[:self.n_nl] for l in lams]))
+            self.jac = r["jac_nl"]
+            self.slot = {i: k for k, i in enumerate(idx)}
+            for i, sf in zip(idx, sfs):
+                self.sf[i] = float(sf)
+            out = self._g(idx, Zs, r["g_nl"])
         return out
 
     def eval_g(self, idx, Zs):
-        t0 = time.perf_counter()
-        with self.torch.cuda.device(self.dev):
-            out = self._g(idx, Zs, self.m0.linearize_device(self._up(Zs))["g_nl"])
-        self.clock["callbacks"] += time.perf_counter() - t0
+        with self.timed("callbacks"):
+            with self.torch.cuda.device(self.dev):
+                out = self._g(idx, Zs, self.m0.linearize_device(self._up(Zs))["g_nl"])
         return out
 
     def set_values(self, J, hess, sfs):
@@ -317,29 +284,21 @@ class DeviceBackend:
         self.sf = {i: float(sf) for i, sf in enumerate(sfs)}
 
     def _sel(self, idx):
-        """the value arrays of the listed problems, in place when they are all of them in order"""
-        rows = [self.slot[i] for i in idx]
-        if rows == list(range(self.jac.shape[0])):
-            return self.jac, self.hess
-        sel = self.torch.as_tensor(rows, device=self.dev)
-        return self.jac.index_select(0, sel).contiguous(), self.hess.index_select(0, sel).contiguous()
+        return self._rows(idx, self.jac, self.hess)
 
     def hess_apply(self, idx, X):
-        t0 = time.perf_counter()
-        out = tril_symv(self.n, self._sel(idx)[1], self._up(X)).cpu().numpy()
-        self.clock["matvec"] += time.perf_counter() - t0
+        with self.timed("matvec"):
+            out = tril_symv(self.n, self._sel(idx)[1], self._up(X)).cpu().numpy()
         return [o + self.sf[i] * self.nlps[i].curv * x for i, o, x in zip(idx, out, X)]
 
     def matvec(self, idx, X):
-        t0 = time.perf_counter()
-        out = list(dense_matvec(self.n, self._sel(idx)[0], self.sum_row, self._up(X)).cpu().numpy())
-        self.clock["matvec"] += time.perf_counter() - t0
+        with self.timed("matvec"):
+            out = list(dense_matvec(self.n, self._sel(idx)[0], self.sum_row, self._up(X)).cpu().numpy())
         return out
 
     def tmatvec(self, idx, W):
-        t0 = time.perf_counter()
-        out = list(dense_tmatvec(self.n, self._sel(idx)[0], self.sum_row, self._up(W)).cpu().numpy())
-        self.clock["matvec"] += time.perf_counter() - t0
+        with self.timed("matvec"):
+            out = list(dense_tmatvec(self.n, self._sel(idx)[0], self.sum_row, self._up(W)).cpu().numpy())
         return out
 
     def normal_matrix(self, idx, D, diags, out=None):
@@ -349,28 +308,15 @@ class DeviceBackend:
         return dense_normal_matrix(self.n, jac, self.sum_row, self._up(D), hess, dg, out=out)
 
     def factor(self, idx, D, diags):
-        torch = self.torch
-        t0 = time.perf_counter()
-        Kc = self.normal_matrix(idx, D, diags)
-        self._sync()
-        t1 = time.perf_counter()
-        info = _ipm.chol_factor(Kc)
-        if self.L is None:
-            self.L = torch.empty((len(self.nlps),) + tuple(Kc.shape[1:]), dtype=torch.float64, device=self.dev)
-        self.L[torch.as_tensor(list(idx), device=self.dev)] = Kc
-        info = info.cpu().numpy()
-        self.clock["normal"] += t1 - t0
-        self.clock["factor"] += time.perf_counter() - t1
-        return [int(v) for v in info]
+        with self.timed("normal"):
+            Kc = self.normal_matrix(idx, D, diags)
+            self._sync()
+        with self.timed("factor"):
+            return self.factor_device(idx, Kc)
 
     def solve(self, idx, B):
-        t0 = time.perf_counter()
-        L = self.L.index_select(0, self.torch.as_tensor(list(idx), device=self.dev))
-        b = self._up(B)[:, None, :].contiguous()
-        _ipm.chol_solve(L, b)
-        out = list(b[:, 0].cpu().numpy())
-        self.clock["solve"] += time.perf_counter() - t0
-        return out
+        with self.timed("solve"):
+            return list(self.solve_device(idx, B))
 
 
 # ---- the solve -------------------------------------------------------------------------------------------------------------
@@ -412,21 +358,19 @@ def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', cal
     groups = {}
     for i, m in enumerate(models):
         groups.setdefault((m.S, str(m.device)) if backend == 'device' else (m.S,), []).append(i)
-    out = [None] * len(models)
-    t0 = time.perf_counter()
-    spent = 0.0
-    for members in groups.values():
-        nlps = [Nlp(models[i]) for i in members]
-        be = make_backend(nlps, backend, None if callbacks is None else [callbacks[i] for i in members])
-        for i, nlp, (Z, info) in zip(members, nlps, _ipm._solve_group(nlps, [Z0s[i] for i in members], tol, max_iter, be, verbose)):
-            info["lagrange"] = lagrange(nlp, info)
-            out[i] = (Z, info)
-        if clocks is not None:
-            for k, v in be.clock.items():
-                clocks[k] = clocks.get(k, 0.0) + v
-                spent += v
+    nlps = {}
+
+    def setup(members):
+        group = [Nlp(models[i]) for i in members]
+        nlps.update(zip(members, group))
+        return group, make_backend(group, backend, None if callbacks is None else [callbacks[i] for i in members])
+
+    spent = None if clocks is None else {}
+    out = _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, spent)
+    for i, (Z, info) in enumerate(out):
+        info["lagrange"] = lagrange(nlps[i], info)
     if clocks is not None:
-        wall = time.perf_counter() - t0
-        clocks["wall"] = clocks.get("wall", 0.0) + wall
-        clocks["host"] = clocks.get("host", 0.0) + wall - spent
+        spent["host"] = spent["wall"] - sum(v for k, v in spent.items() if k != "wall")
+        for k, v in spent.items():
+            clocks[k] = clocks.get(k, 0.0) + v
     return out

@@ -13,7 +13,8 @@ hands to IPOPT (:486-640) on the MI355X.
     the Monte-Carlo / large-M path.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
   * ``Model.initial_guess()`` and ``Model.solve()``: the script's start and its solve (:136-164, :642-669) with the batched
-    interior-point method of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip) in IPOPT's place."""
+    interior-point method of ``ipm`` on the backends of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip, csrc/chol.hip) in
+    IPOPT's place."""
 import ctypes as C
 
 import numpy as np

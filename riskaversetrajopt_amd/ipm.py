@@ -1,0 +1,426 @@
+"""The lockstep primal-dual interior-point method, model-independent: ``hopper_ipm`` and ``drone_gaussian_ipm``
+run it on backends of their own.
+
+  min f(z)  s.t.  gL <= g(z) <= gU,  xL <= z <= xU
+
+Rows with gL == gU are equalities E; every other row I gets a slack, g_I(z) - s = 0, gL_I <= s <= gU_I.  v = (z, s).  A bound
+with |b| >= 1e14 is absent; present bounds are relaxed outward by 1e-8 max(1, |b|) (IPOPT's bound_relax_factor).  The objective
+is scaled by sf = min(1, 100 / max |grad f(Z0)|).
+
+Newton step, condensed.  With Sigma = zl / (v - vL) + zu / (vU - v), eliminating s and y_I:
+  Kc = W + diag(Sigma_z) + delta_w I + J_I' diag(Sigma_s) J_I + (1 / delta_c) J_E' J_E
+  Kc dz = -r_z - J' w,   w = d c + (r_s on I, 0 on E),   d = (Sigma_s on I, 1 / delta_c on E)
+  dy_E = (J_E dz + c_E) / delta_c,   ds = J_I dz + c_I,   dy_I = Sigma_s ds + r_s
+delta_c = 1e-8 mu^(1/4) is always on (it tolerates redundant rows); delta_w = 0, 1e-4, then x 8 until the Cholesky of Kc
+succeeds: Kc positive definite <=> the regularised KKT matrix has the right inertia, so the factorization is the inertia test.
+Two steps of iterative refinement follow against the system with the equality block NOT condensed (unknowns dz, dy_E),
+re-using the factor.
+
+The driver (``Problem``, ``newton_steps``, ``solve_group``, ``solve_groups``) knows a model through num_vars, gL_gU(),
+x_bounds(), f, grad_f and a backend through name, clock, eval_full / eval_g / matvec / tmatvec / factor / solve /
+hess_apply(idx, X) -> [W x].  It, the line search and the O(n + m) vector algebra run on the host per problem, so a problem's
+iterates do not depend on what else is in the batch.  ``Backend`` / ``DeviceBase`` hold what the backends have in common: the
+clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_solve``: csrc/chol.hip), uploads and row selection.
+"""
+import contextlib
+import time
+
+import numpy as np
+
+ABSENT = 1e14
+STATUSES = ("converged", "max_iter", "line_search")
+
+
+# ---- the Cholesky (csrc/chol.hip) --------------------------------------------------------------------------------------------
+def chol_panel_width():
+    from . import _lib
+    return int(_lib.load().rato_chol_panel_width())
+
+
+def chol_factor(A):
+    """rato_chol_factor_batch_f64 in place on a device fp64 tensor A (K, n, lda) (row-major lower triangle; lda >= n)
+    -> info (K,) int32 device tensor: 0, or j + 1 for the first pivot j that is not positive and finite"""
+    import torch
+    from . import _lib
+    if A.dim() != 3 or A.dtype != torch.float64 or not A.is_cuda or not A.is_contiguous() or A.shape[2] < A.shape[1] or A.shape[1] < 1:
+        raise ValueError(f"A must be a contiguous device float64 tensor (K, n, lda >= n), got {tuple(A.shape)}")
+    info = torch.empty(A.shape[0], dtype=torch.int32, device=A.device)
+    with torch.cuda.device(A.device):
+        _lib.check(_lib.load().rato_chol_factor_batch_f64(_lib.ptr(A), A.shape[1], A.shape[2], A.shape[0], _lib.ptr(info),
+                                                          _lib.current_stream()), "rato_chol_factor_batch_f64")
+    return info
+
+
+def chol_solve(L, B):
+    """rato_chol_solve_batch_f64: L (K, n, lda) as chol_factor leaves it, B (K, nrhs, ldb >= n) device fp64, solved in place"""
+    import torch
+    from . import _lib
+    if L.dim() != 3 or B.dim() != 3 or L.dtype != torch.float64 or B.dtype != torch.float64 or not (L.is_contiguous() and B.is_contiguous()) \
+            or B.shape[0] != L.shape[0] or B.shape[2] < L.shape[1] or L.shape[2] < L.shape[1] or L.device != B.device or not L.is_cuda:
+        raise ValueError("chol_solve: L (K, n, lda >= n) and B (K, nrhs, ldb >= n) contiguous device float64 tensors")
+    with torch.cuda.device(L.device):
+        _lib.check(_lib.load().rato_chol_solve_batch_f64(_lib.ptr(L), L.shape[1], L.shape[2], L.shape[0], _lib.ptr(B), B.shape[1],
+                                                         B.shape[2], _lib.current_stream()), "rato_chol_solve_batch_f64")
+    return B
+
+
+# ---- what every backend repeats ------------------------------------------------------------------------------------------------
+class Backend:
+    """the clocks of a backend, and the host's Cholesky: factors kept per problem in ``self.L``"""
+
+    def __init__(self, *more_clocks):
+        self.clock = dict.fromkeys(("callbacks", "normal", "factor", "solve") + more_clocks, 0.0)
+        self.L = {}
+
+    @contextlib.contextmanager
+    def timed(self, key):
+        """adds the seconds spent in the block to clock[key]"""
+        t0 = time.perf_counter()
+        yield
+        self.clock[key] += time.perf_counter() - t0
+
+    def factor_host(self, i, Kc, ok=True):
+        """the Cholesky factor of Kc as problem i's L -> 0, or 1 when ``ok`` is false or Kc is not finite and positive definite"""
+        ok = ok and bool(np.all(np.isfinite(Kc)))
+        if ok:
+            try:
+                self.L[i] = np.linalg.cholesky(Kc)
+            except np.linalg.LinAlgError:
+                ok = False
+        return 0 if ok else 1
+
+    def solve_host(self, i, b):
+        from scipy.linalg import solve_triangular
+        return solve_triangular(self.L[i], solve_triangular(self.L[i], b, lower=True), lower=True, trans='T')
+
+
+class DeviceBase(Backend):
+    """what the device backends share: the uploads, ``slot`` (problem -> row of the current value arrays) and the Cholesky on
+    the device with the factors of all ``n_all`` problems of the group kept in one tensor"""
+
+    def __init__(self, dev, n_all, *more_clocks):
+        import torch
+        super().__init__(*more_clocks)
+        self.torch, self.dev, self.n_all = torch, dev, n_all
+        self.slot, self.L = {}, None
+
+    def _sync(self):
+        self.torch.cuda.synchronize(self.dev)
+
+    def _up(self, rows):
+        return self.torch.as_tensor(np.ascontiguousarray(np.stack(rows), dtype=np.float64), device=self.dev)
+
+    def _rows(self, idx, *tensors):
+        """the rows of the value arrays that hold the listed problems, in place when they are all of them in order"""
+        rows = [self.slot[i] for i in idx]
+        if rows == list(range(tensors[0].shape[0])):
+            return tensors
+        sel = self.torch.as_tensor(rows, device=self.dev)
+        return tuple(t.index_select(0, sel).contiguous() for t in tensors)
+
+    def factor_device(self, idx, Kc):
+        """factors Kc (K, n, lda) in place and keeps it as the listed problems' L -> info as a list"""
+        torch = self.torch
+        info = chol_factor(Kc)
+        if self.L is None:
+            self.L = torch.empty((self.n_all,) + tuple(Kc.shape[1:]), dtype=torch.float64, device=self.dev)
+        self.L[torch.as_tensor(list(idx), device=self.dev)] = Kc
+        return [int(v) for v in info.cpu().numpy()]
+
+    def solve_device(self, idx, B):
+        """L L' x = b for the listed problems from their kept factors, B host vectors -> (K, n) host array"""
+        L = self.L.index_select(0, self.torch.as_tensor(list(idx), device=self.dev))
+        b = self._up(B)[:, None, :].contiguous()
+        chol_solve(L, b)
+        return b[:, 0].cpu().numpy()
+
+
+# ---- the method ------------------------------------------------------------------------------------------------------------
+class Problem:
+    """one problem's iterate and constants (host, fp64)"""
+
+    def __init__(self, model, Z0, g0, tol):
+        self.model, self.tol = model, float(tol)
+        n = self.n = model.num_vars
+        gL, gU = model.gL_gU()
+        xL, xU = model.x_bounds()
+        self.m = gL.size
+        self.E = gL == gU
+        self.I = ~self.E
+        self.gE = gL[self.E]
+        vL, vU = np.concatenate([xL, gL[self.I]]), np.concatenate([xU, gU[self.I]])
+        self.hasL, self.hasU = np.abs(vL) < ABSENT, np.abs(vU) < ABSENT
+        vL = np.where(self.hasL, vL - 1e-8 * np.maximum(1.0, np.abs(vL)), -np.inf)
+        vU = np.where(self.hasU, vU + 1e-8 * np.maximum(1.0, np.abs(vU)), np.inf)
+        self.vL, self.vU = vL, vU
+        v = np.concatenate([np.asarray(Z0, dtype=np.float64), g0[self.I]])
+        with np.errstate(invalid='ignore'):
+            width = np.where(self.hasL & self.hasU, 1e-2 * (vU - vL), np.inf)
+        fin = lambda b, has: np.where(has, b, 0.0)
+        pL = np.minimum(1e-2 * np.maximum(1.0, np.abs(fin(vL, self.hasL))), width)
+        pU = np.minimum(1e-2 * np.maximum(1.0, np.abs(fin(vU, self.hasU))), width)
+        v = np.where(self.hasL, np.maximum(v, fin(vL, self.hasL) + pL), v)
+        v = np.where(self.hasU, np.minimum(v, fin(vU, self.hasU) - pU), v)
+        self.v = v
+        self.zl, self.zu = self.hasL.astype(np.float64), self.hasU.astype(np.float64)
+        self.y = np.zeros(self.m)
+        self.mu, self.nu, self.dw = 0.1, 0.0, 0.0
+        gf = model.grad_f(Z0)
+        self.sf = min(1.0, 100.0 / max(np.max(np.abs(gf)), 1e-300))
+        self.done, self.status = False, None
+        self.iterations = self.factorizations = 0
+        self.E0 = self.prim = self.dual = np.inf
+
+    @property
+    def z(self):
+        return self.v[:self.n]
+
+    def residuals(self, g, JTy):
+        """c (m,), the dual residual of (z, s), and E_mu as a function of mu"""
+        n = self.n
+        c = np.empty(self.m)
+        c[self.E] = g[self.E] - self.gE
+        c[self.I] = g[self.I] - self.v[n:]
+        self.gradf = self.sf * self.model.grad_f(self.z)
+        rz = self.gradf + JTy - self.zl[:n] + self.zu[:n]
+        rs = -self.y[self.I] - self.zl[n:] + self.zu[n:]
+        self.c, self.JTy = c, JTy
+        self.dual = max(np.max(np.abs(rz)), np.max(np.abs(rs)) if rs.size else 0.0)
+        self.prim = np.max(np.abs(c))
+        with np.errstate(invalid='ignore'):
+            self.dL, self.dU = self.v - self.vL, self.vU - self.v
+        self.cl = np.where(self.hasL, self.zl * np.where(self.hasL, self.dL, 0.0), 0.0)
+        self.cu = np.where(self.hasU, self.zu * np.where(self.hasU, self.dU, 0.0), 0.0)
+
+    def error(self, mu):
+        comp = 0.0
+        if np.any(self.hasL):
+            comp = max(comp, np.max(np.abs(self.cl[self.hasL] - mu)))
+        if np.any(self.hasU):
+            comp = max(comp, np.max(np.abs(self.cu[self.hasU] - mu)))
+        return max(self.dual, self.prim, comp)
+
+    def barrier(self, v):
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return -self.mu * (np.sum(np.log((v - self.vL)[self.hasL])) + np.sum(np.log((self.vU - v)[self.hasU])))
+
+    def c_of(self, g, v):
+        c = np.empty(self.m)
+        c[self.E] = g[self.E] - self.gE
+        c[self.I] = g[self.I] - v[self.n:]
+        return c
+
+    def prepare_step(self):
+        """Sigma, the barrier gradient, the row weights d and the vector w of the condensed right-hand side"""
+        n, mu = self.n, self.mu
+        iL, iU = 1.0 / np.where(self.hasL, self.dL, np.inf), 1.0 / np.where(self.hasU, self.dU, np.inf)
+        self.Sigma = self.zl * iL + self.zu * iU
+        self.gbar = -mu * iL + mu * iU                               # the barrier's gradient in v
+        self.rz = self.gradf + self.JTy + self.gbar[:n]
+        self.rs = -self.y[self.I] + self.gbar[n:]
+        self.dc = 1e-8 * mu ** 0.25
+        d = np.empty(self.m)
+        d[self.E] = 1.0 / self.dc
+        d[self.I] = self.Sigma[n:]
+        self.d = d
+        w = d * self.c
+        w[self.I] += self.rs
+        self.w = w
+
+
+def newton_steps(be, idx, ps, refine=2):
+    """the condensed Newton step of the listed problems (``Problem.prepare_step`` done) on backend ``be``: fills p.dv (n + nI)
+    and p.dy (m).  A failed factorization is redone with the next delta_w; returns False for a problem where none succeeded."""
+    JTw = be.tmatvec(idx, [p.w for p in ps])
+    for p, t in zip(ps, JTw):
+        p.rhs = -(p.rz + t)
+        p.dw, p.fact_ok = 0.0, False
+    todo = list(range(len(ps)))
+    for _ in range(60):
+        info = be.factor([idx[k] for k in todo], [ps[k].d for k in todo], [ps[k].Sigma[:ps[k].n] + ps[k].dw for k in todo])
+        nxt = []
+        for k, bad in zip(todo, info):
+            ps[k].factorizations += 1
+            if bad:
+                ps[k].dw = 1e-4 if ps[k].dw == 0.0 else 8.0 * ps[k].dw
+                nxt.append(k)
+            else:
+                ps[k].fact_ok = True
+        todo = nxt
+        if not todo:
+            break
+    good = [k for k in range(len(ps)) if ps[k].fact_ok]
+    if not good:
+        return [False] * len(ps)
+    gi, gp = [idx[k] for k in good], [ps[k] for k in good]
+    for p, x in zip(gp, be.solve(gi, [p.rhs for p in gp])):
+        p.dz = x
+    for it in range(refine + 1):
+        Jdz = be.matvec(gi, [p.dz for p in gp])
+        for p, jd in zip(gp, Jdz):
+            p.Jdz = jd
+            lin = jd + p.c
+            if it == 0:
+                p.dyE = lin[p.E] / p.dc
+        if it == refine:
+            break
+        Q = []
+        for p in gp:
+            lin = p.Jdz + p.c
+            p.r2 = -lin[p.E] + p.dc * p.dyE                        # the equality block's residual, kept apart from dz's
+            q = np.empty(p.m)
+            q[p.I] = p.Sigma[p.n:] * lin[p.I] + p.rs
+            q[p.E] = p.dyE - p.r2 / p.dc
+            Q.append(q)
+        JTq = be.tmatvec(gi, Q)
+        Wdz = be.hess_apply(gi, [p.dz for p in gp])
+        R = [-(p.rz + h + (p.Sigma[:p.n] + p.dw) * p.dz + t) for p, h, t in zip(gp, Wdz, JTq)]
+        ez = be.solve(gi, R)
+        Jez = be.matvec(gi, ez)
+        for p, e, je in zip(gp, ez, Jez):
+            p.dz = p.dz + e
+            p.dyE = p.dyE + (je[p.E] - p.r2) / p.dc
+    for p in gp:
+        ds = p.Jdz[p.I] + p.c[p.I]
+        p.dv = np.concatenate([p.dz, ds])
+        dy = np.empty(p.m)
+        dy[p.E] = p.dyE
+        dy[p.I] = p.Sigma[p.n:] * ds + p.rs
+        p.dy = dy
+    return [p.fact_ok for p in ps]
+
+
+def kkt_residual(p, J, W):
+    """relative residual of (p.dv, p.dy) in the UNCONDENSED regularised KKT system (unknowns dz, ds, dy_E, dy_I) with dense J
+    (m, n) and W (n, n):  max |K x - b| / max |b|"""
+    n = p.n
+    dz, ds, dy = p.dv[:n], p.dv[n:], p.dy
+    JE, JI = J[p.E], J[p.I]
+    r1 = (W @ dz + (p.Sigma[:n] + p.dw) * dz + JE.T @ dy[p.E] + JI.T @ dy[p.I]) + p.rz
+    r2 = p.Sigma[n:] * ds - dy[p.I] + p.rs
+    r3 = JE @ dz - p.dc * dy[p.E] + p.c[p.E]
+    r4 = JI @ dz - ds + p.c[p.I]
+    b = np.concatenate([p.rz, p.rs, p.c[p.E], p.c[p.I]])
+    return float(np.max(np.abs(np.concatenate([r1, r2, r3, r4]))) / np.max(np.abs(b)))
+
+
+def _max_step(x, dx, has, tau):
+    """largest alpha in (0, 1] with x + alpha dx >= (1 - tau) x (x: distances to a bound or multipliers, all positive)"""
+    m = has & (dx < 0)
+    if not np.any(m):
+        return 1.0
+    return float(min(1.0, np.min(-tau * x[m] / dx[m])))
+
+
+def solve_group(models, Z0s, tol, max_iter, be, verbose):
+    K = len(models)
+    all_idx = list(range(K))
+    g0 = be.eval_g(all_idx, [np.asarray(Z, dtype=np.float64) for Z in Z0s])
+    ps = [Problem(m, Z, g, tol) for m, Z, g in zip(models, Z0s, g0)]
+    for it in range(max_iter + 1):
+        idx = [i for i in all_idx if not ps[i].done]
+        if not idx:
+            break
+        act = [ps[i] for i in idx]
+        G = be.eval_full(idx, [p.z.copy() for p in act], [p.y for p in act], [p.sf for p in act])
+        JTy = be.tmatvec(idx, [p.y for p in act])
+        for p, g, t in zip(act, G, JTy):
+            p.g = g
+            p.residuals(g, t)
+            p.E0 = p.error(0.0)
+            if not np.isfinite(p.E0):
+                p.done, p.status = True, "line_search"
+            elif p.E0 <= tol:
+                p.done, p.status = True, "converged"
+            elif it == max_iter:
+                p.done, p.status = True, "max_iter"
+            else:
+                while p.error(p.mu) <= 10.0 * p.mu and p.mu > tol / 10.0:
+                    p.mu = max(tol / 10.0, min(0.2 * p.mu, p.mu ** 1.5))
+                    p.nu = 0.0
+                p.prepare_step()
+        pairs = [(i, p) for i, p in zip(idx, act) if not p.done]
+        if not pairs:
+            continue
+        idx, act = [i for i, _ in pairs], [p for _, p in pairs]
+        ok = newton_steps(be, idx, act)
+        search = []
+        gi = [i for i, good in zip(idx, ok) if good]
+        Wdv = dict(zip(gi, be.hess_apply(gi, [p.dv[:p.n] for p, good in zip(act, ok) if good]))) if gi else {}
+        for i, p, good in zip(idx, act, ok):
+            if not good:
+                p.done, p.status = True, "line_search"
+                continue
+            n, mu = p.n, p.mu
+            tau = max(0.99, 1.0 - mu)
+            dv = p.dv
+            iL, iU = 1.0 / np.where(p.hasL, p.dL, np.inf), 1.0 / np.where(p.hasU, p.dU, np.inf)
+            p.dzl = np.where(p.hasL, mu * iL - p.zl - p.zl * iL * dv, 0.0)
+            p.dzu = np.where(p.hasU, mu * iU - p.zu + p.zu * iU * dv, 0.0)
+            p.a_max = min(_max_step(np.where(p.hasL, p.dL, 1.0), dv, p.hasL, tau),
+                          _max_step(np.where(p.hasU, p.dU, 1.0), -dv, p.hasU, tau))
+            p.a_dual = min(_max_step(p.zl, p.dzl, p.hasL, tau), _max_step(p.zu, p.dzu, p.hasU, tau))
+            c1 = float(np.sum(np.abs(p.c)))
+            Dbar = float(p.gradf @ dv[:n] + p.gbar @ dv)
+            quad = float(dv[:n] @ Wdv[i] + np.sum(p.Sigma * dv * dv) + p.dw * (dv[:n] @ dv[:n]))
+            if c1 > 0.0:
+                nu_trial = (Dbar + 0.5 * max(quad, 0.0)) / (0.9 * c1)
+                if p.nu < nu_trial:
+                    p.nu = nu_trial + 1.0
+            p.Dphi = min(Dbar - p.nu * c1, 0.0)
+            p.phi = p.sf * p.model.f(p.z) + p.barrier(p.v) + p.nu * c1
+            p.alpha, p.trials, p.accepted = p.a_max, 0, False
+            search.append((i, p))
+        while search:
+            trial_v = [p.v + p.alpha * p.dv for _, p in search]
+            Gt = be.eval_g([i for i, _ in search], [v[:p.n].copy() for v, (_, p) in zip(trial_v, search)])
+            nxt = []
+            for (i, p), v, g in zip(search, trial_v, Gt):
+                phi_t = p.sf * p.model.f(v[:p.n]) + p.barrier(v) + p.nu * float(np.sum(np.abs(p.c_of(g, v))))
+                p.trials += 1
+                if np.isfinite(phi_t) and phi_t <= p.phi + 1e-8 * p.alpha * p.Dphi + 10.0 * np.finfo(float).eps * abs(p.phi):
+                    p.v = v
+                    p.y = p.y + p.alpha * p.dy
+                    p.zl = p.zl + p.a_dual * p.dzl
+                    p.zu = p.zu + p.a_dual * p.dzu
+                    with np.errstate(invalid='ignore'):
+                        dL, dU = np.where(p.hasL, p.v - p.vL, 1.0), np.where(p.hasU, p.vU - p.v, 1.0)
+                    p.zl = np.where(p.hasL, np.clip(p.zl, p.mu / dL / 1e10, 1e10 * p.mu / dL), 0.0)   # kappa_Sigma
+                    p.zu = np.where(p.hasU, np.clip(p.zu, p.mu / dU / 1e10, 1e10 * p.mu / dU), 0.0)
+                    p.iterations += 1
+                elif p.trials >= 40:
+                    p.done, p.status = True, "line_search"
+                else:
+                    p.alpha *= 0.5
+                    nxt.append((i, p))
+            search = nxt
+        if verbose:
+            print("it %4d " % it + " | ".join("mu %.1e E0 %.2e pr %.1e du %.1e a %.1e dw %.0e" %
+                                               (p.mu, p.E0, p.prim, p.dual, getattr(p, "alpha", 0.0), p.dw) for p in act))
+    out = []
+    for p in ps:
+        if p.status is None:
+            p.status = "max_iter"
+        info = dict(status=p.status, iterations=p.iterations, factorizations=p.factorizations, E0=float(p.E0),
+                    primal_infeasibility=float(p.prim), dual_infeasibility=float(p.dual), f=p.model.f(p.z), mu=p.mu, sf=p.sf,
+                    y=p.y.copy(), zl=p.zl.copy(), zu=p.zu.copy(), s=p.v[p.n:].copy(), backend=be.name)
+        out.append((p.z.copy(), info))
+    return out
+
+
+def solve_groups(groups, setup, Z0s, tol, max_iter, verbose, clocks):
+    """what a ``solve_batch`` ends with: the groups (lists of problem numbers) one after the other, each by ``solve_group`` on
+    the (models, backend) ``setup(members)`` makes -> [(Z, info)] in the problems' order.  ``clocks`` (a dict, or None) receives
+    the sums of the backends' clocks and the wall clock."""
+    out = [None] * sum(len(members) for members in groups)
+    t0 = time.perf_counter()
+    for members in groups:
+        models, be = setup(members)
+        for i, r in zip(members, solve_group(models, [Z0s[i] for i in members], tol, max_iter, be, verbose)):
+            out[i] = r
+        if clocks is not None:
+            for k, v in be.clock.items():
+                clocks[k] = clocks.get(k, 0.0) + v
+    if clocks is not None:
+        clocks["wall"] = clocks.get("wall", 0.0) + time.perf_counter() - t0
+    return out

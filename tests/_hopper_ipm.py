@@ -79,19 +79,19 @@ def newton_residual(be, model, flds, S, M, seed=0):
     """One Newton step of backend ``be`` (holding ``model`` as its problem 0) at a designed interior iterate: the perturbed
     point ``_hopper_nlp.problem(S, M, seed)`` pushed inside the bounds, seeded multipliers of mixed sign, mu = 0.1.
     -> (relative residual in the uncondensed regularised KKT system built from the restatement's dense J and W, delta_w)"""
-    from riskaversetrajopt_amd import hopper_ipm
+    from riskaversetrajopt_amd import ipm
     Z0 = R.problem(S, M, seed)
-    p = hopper_ipm.Problem(model, Z0, be.eval_g([0], [Z0])[0], TOL)
+    p = ipm.Problem(model, Z0, be.eval_g([0], [Z0])[0], TOL)
     rng = np.random.RandomState(400 + S)
     p.y = rng.uniform(-1, 1, p.m)
     p.zl, p.zu = p.zl * rng.uniform(0.5, 2.0, p.zl.size), p.zu * rng.uniform(0.5, 2.0, p.zu.size)
     g, = be.eval_full([0], [p.z.copy()], [p.y], [p.sf])
     p.residuals(g, be.tmatvec([0], [p.y])[0])
     p.prepare_step()
-    assert hopper_ipm.newton_steps(be, [0], [p]) == [True]
+    assert ipm.newton_steps(be, [0], [p]) == [True]
     J = R.jac_dense(p.z, S, M, model.method, model.alpha, flds)
     W = R.dense_from_blocks(R.hess_blocks_full(p.z, p.y, S, M, model.method, model.alpha, flds, obj_factor=p.sf), S, p.n)
-    return hopper_ipm.kkt_residual(p, J, W), p.dw
+    return ipm.kkt_residual(p, J, W), p.dw
 
 
 def warm_start(model, Zbase):

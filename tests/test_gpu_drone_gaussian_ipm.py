@@ -166,7 +166,7 @@ def newton_residuals(S, alpha=0.1):
     """One Newton step of both backends from the same ``Problem`` state: the designed interior point
     ``_drone_gaussian.problems(S, 1)``, seeded multipliers of mixed sign, mu = 0.1.  -> (NumPy, device) relative residuals in
     the uncondensed regularised KKT system built from the restatement's dense J and W"""
-    from riskaversetrajopt_amd import drone_gaussian as dg, hopper_ipm
+    from riskaversetrajopt_amd import drone_gaussian as dg, ipm as method
     m = ipm()
     model = dg.Model(S, alpha=alpha, device=DEV)
     nlp = m.Nlp(model)
@@ -175,18 +175,18 @@ def newton_residuals(S, alpha=0.1):
     g0 = be_np.eval_g([0], [Z0])[0]
     out = []
     for be in (be_np, be_dev):
-        p = hopper_ipm.Problem(nlp, Z0, g0, T.TOL)
+        p = method.Problem(nlp, Z0, g0, T.TOL)
         rng = np.random.RandomState(400 + S)
         p.y = rng.uniform(-1, 1, p.m)
         p.zl, p.zu = p.zl * rng.uniform(0.5, 2.0, p.zl.size), p.zu * rng.uniform(0.5, 2.0, p.zu.size)
         g, = be.eval_full([0], [p.z.copy()], [p.y], [p.sf])
         p.residuals(g, be.tmatvec([0], [p.y])[0])
         p.prepare_step()
-        assert hopper_ipm.newton_steps(be, [0], [p]) == [True]
+        assert method.newton_steps(be, [0], [p]) == [True]
         ev = R.evaluate(p.z, S, [p.y[:nlp.n_nl]])
         J = np.vstack([ev["jac_nl"], nlp.sum_row()[None, :]])
         W = ev["hess"][0] + np.diag(p.sf * nlp.curv)
-        out.append(hopper_ipm.kkt_residual(p, J, W))
+        out.append(method.kkt_residual(p, J, W))
     return out
 
 

@@ -1,5 +1,5 @@
 """GPU: the kernels of csrc/hopper_arrow.hip on designed buffers, and the device backend of the arrowhead Newton step
-(``hopper_ipm.ArrowDeviceBackend``, newton='arrow').
+(``hopper_arrow.ArrowDeviceBackend``, newton='arrow').
 
 Kernel bounds: |device - np.longdouble| <= gamma_(len + 1) sum |terms|, gamma_k = k u / (1 - k u), u = 2^-53, where len counts
 the terms of the sum plus the roundings inside one term (b_i = -d_ic g_ic, the slack entry of b_i a sum over C contacts, u_i =
@@ -20,6 +20,11 @@ K3 = 3
 def ipm():
     from riskaversetrajopt_amd import hopper_ipm
     return hopper_ipm
+
+
+def arrow():
+    from riskaversetrajopt_amd import hopper_arrow
+    return hopper_arrow
 
 
 def lib():
@@ -317,7 +322,7 @@ def device_model(S, M, method, alpha=0.2, flds=None):
 def test_one_newton_step_residual(S, M):
     """the device arrow step's relative residual in the UNCONDENSED regularised KKT system (the restatement's dense J and W) is at
     most 100 x the NumPy arrow backend's at the same designed interior iterate"""
-    m = ipm()
+    m = arrow()
     flds = H.fields(M)
     host = H.host_model('saa', 0.2, S, M)
     r_np, dw_np = H.newton_residual(m.ArrowNumpyBackend([host], [H.RestatementCallbacks(host, flds)]), host, flds, S, M)

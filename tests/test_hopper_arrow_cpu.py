@@ -1,4 +1,4 @@
-"""The arrowhead Newton step of ``hopper_ipm`` (newton='arrow') on the host: the exact elimination of the M sample variables
+"""The arrowhead Newton step of ``hopper_arrow`` (``hopper_ipm``, newton='arrow') on the host: the exact elimination of the M sample variables
 against the dense condensed matrix, the inertia test, the structured products, and the solver end to end on the fp64 restatement
 (tests/_hopper_nlp.py + oracle/hopper.py).  Bounds are gamma_k sum |terms| against np.longdouble, gamma_k = k u / (1 - k u),
 u = 2^-53, and "100 x what the dense twin reaches" for solves.
@@ -10,7 +10,7 @@ constants of the risk group (1 on fx, -1 on slack, t_risk and y_i, M alpha) wher
 import numpy as np
 import pytest
 
-from riskaversetrajopt_amd import hopper, hopper_ipm
+from riskaversetrajopt_amd import hopper, hopper_arrow, hopper_ipm
 import _hopper_ipm as H
 import _hopper_nlp as R
 from _hopper_ipm import gamma
@@ -80,12 +80,12 @@ def test_elimination_is_the_dense_matrix_and_solves_as_well(M, method, phases, d
     from scipy.linalg import solve_triangular
     model, vals, hess, _ = designed_problem(M, method, phases, 11 + M)
     assert model.nlp_layout()["C"] == (4 if phases is None else 1)
-    st, ast = hopper_ipm.structure(model), hopper_ipm.arrow_structure(model)
+    st, ast = hopper_ipm.structure(model), hopper_arrow.arrow_structure(model)
     rng = np.random.RandomState(5 + M)
     d = graded(rng, st["ncon"])
     diag = rng.uniform(0.5, 2.0, st["n"]) + dw
     Kc = hopper_ipm.normal_matrix_host(st, vals, d, hess, diag)
-    be = hopper_ipm.ArrowNumpyBackend([model], [None])
+    be = hopper_arrow.ArrowNumpyBackend([model], [None])
     be.set_values(0, vals, hess)
     info = be.factor([0], [d], [diag])
     full, mag_b = expand(be, 0, ast)
@@ -118,7 +118,7 @@ def test_inertia_is_what_the_dense_twin_reports(M, method, phases):
     rng = np.random.RandomState(9)
     d = 10.0 ** rng.uniform(-2, 2, st["ncon"])
     sigma = rng.uniform(0.5, 2.0, st["n"])
-    arrow, dense = hopper_ipm.ArrowNumpyBackend([model], [None]), hopper_ipm.NumpyBackend([model], [None])
+    arrow, dense = hopper_arrow.ArrowNumpyBackend([model], [None]), hopper_ipm.NumpyBackend([model], [None])
     arrow.set_values(0, vals, hess)
     dense.vals[0], dense.hess[0] = vals, hess
     for dw, good in ((0.0, False), (1e9, True)):
@@ -133,7 +133,7 @@ def test_structured_products_are_the_dense_patterns(M, method, phases):
     gamma_(len + 1) |J| |x| of extended precision, len = the entries of the row / column, as the dense pattern's products are"""
     model, vals, hess, _ = designed_problem(M, method, phases, 21)
     st = hopper_ipm.structure(model)
-    arrow, dense = hopper_ipm.ArrowNumpyBackend([model], [None]), hopper_ipm.NumpyBackend([model], [None])
+    arrow, dense = hopper_arrow.ArrowNumpyBackend([model], [None]), hopper_ipm.NumpyBackend([model], [None])
     arrow.set_values(0, vals, hess)
     dense.vals[0] = vals
     J = np.zeros((st["ncon"], st["n"]), dtype=LD)
@@ -203,7 +203,7 @@ def test_arrow_structure_scales_with_M_times_C():
     stays within 8 (ncon + 7 M C) elements"""
     M = 20000
     model = hopper.Model.host_only(M, 'saa', S=S6)
-    st = hopper_ipm.arrow_structure(model)
+    st = hopper_arrow.arrow_structure(model)
     ncon, _ = model.risk_rows_offset()
     limit = 8 * (ncon + 7 * M * st["C"])
     seen = []

@@ -5,7 +5,7 @@ bookkeeping, the lockstep batch against solo runs, the product map of J' D J aga
 import numpy as np
 import pytest
 
-from riskaversetrajopt_amd import hopper, hopper_ipm, scp
+from riskaversetrajopt_amd import hopper, hopper_ipm, ipm, scp
 import _hopper_ipm as H
 from _hopper_ipm import dense_reference, designed_values, gamma, map_cases
 
@@ -55,10 +55,10 @@ def test_batch_of_three_is_bitwise_the_solo_runs(small_runs, k):
 def test_status_strings_when_max_iter_is_3(small_runs):
     r = small_runs
     (Z, info), = hopper_ipm.solve_batch([r["models"][0]], backend='numpy', callbacks=[r["cbs"][0]], tol=H.TOL, max_iter=3)
-    assert info["status"] == "max_iter" and info["status"] in hopper_ipm.STATUSES
+    assert info["status"] == "max_iter" and info["status"] in ipm.STATUSES
     assert info["iterations"] == 3 and info["E0"] > H.TOL          # nothing claims convergence that E_0 does not show
-    assert set(s for _, i in r["batch"] for s in [i["status"]]) <= set(hopper_ipm.STATUSES)
-    assert hopper_ipm.STATUSES == ("converged", "max_iter", "line_search")
+    assert set(s for _, i in r["batch"] for s in [i["status"]]) <= set(ipm.STATUSES)
+    assert ipm.STATUSES == ("converged", "max_iter", "line_search")
     with pytest.raises(ValueError):
         hopper_ipm.solve_batch([r["models"][0]], backend='eager')
 

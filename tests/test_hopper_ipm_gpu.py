@@ -1,4 +1,5 @@
-"""GPU: the kernels of csrc/hopper_ipm.hip and the device backend of ``hopper_ipm``.
+"""GPU: the kernels of csrc/hopper_ipm.hip and csrc/chol.hip (``ipm.chol_factor`` / ``chol_solve``) and the device backend of
+``hopper_ipm``.
 
 The Cholesky and its solve are held to the textbook elementwise backward-error bounds (Higham, Accuracy and Stability of
 Numerical Algorithms, Thm 10.3 / 10.4), which hold for any summation order: |L L' - A| <= gamma_(n+1) |L| |L'| and
@@ -19,8 +20,13 @@ def ipm():
     return hopper_ipm
 
 
+def chol():
+    from riskaversetrajopt_amd import ipm as method
+    return method
+
+
 def NB():
-    return ipm().chol_panel_width()
+    return chol().chol_panel_width()
 
 
 def spd(kind, n, seed):
@@ -53,8 +59,8 @@ def untouched(out, n):
 
 
 def sizes():
-    nb = 32                                                           # asserted against the kernel's in the test
-    return [1, 2, nb - 1, nb, nb + 1, 2 * nb + 1, 130]
+    nb = 32                              # asserted against the kernel's in the test; 3 nb: the trailing tiles' first edge
+    return [1, 2, nb - 1, nb, nb + 1, 2 * nb, 2 * nb + 1, 3 * nb, 3 * nb + 1, 130]
 
 
 @pytest.mark.parametrize("kind", ["bbt", "graded"])
@@ -62,7 +68,7 @@ def sizes():
 @pytest.mark.parametrize("n", sizes())
 def test_cholesky_and_solve_backward_error(n, pad, kind):
     import torch
-    m = ipm()
+    m = chol()
     assert NB() == 32
     K, lda = 3, n + pad
     As = [spd(kind, n, 10 * n + k) for k in range(K)]
@@ -110,7 +116,7 @@ def test_cholesky_and_solve_backward_error(n, pad, kind):
 @pytest.mark.parametrize("jname", ["0", "NB-1", "NB", "n-1"])
 def test_indefinite_input_is_reported_not_faulted(jname, what):
     """what the solver meets on every delta_w retry: info = j + 1, the neighbours bitwise unaffected, the call returns 0"""
-    m = ipm()
+    m = chol()
     n = 70
     j = {"0": 0, "NB-1": NB() - 1, "NB": NB(), "n-1": n - 1}[jname]
     rng = np.random.RandomState(j)

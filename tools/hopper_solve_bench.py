@@ -11,7 +11,7 @@ bench.py is the flagship benchmark):
 
     python tools/hopper_solve_bench.py [--out profiles/hopper_solve.json] [--S 30 --M 30]
 
-``--newton arrow --M 30,1000,10000`` measures the arrowhead Newton step (``hopper_ipm``, newton='arrow') instead,
+``--newton arrow --M 30,1000,10000`` measures the arrowhead Newton step (``hopper_arrow``, newton='arrow') instead,
 into profiles/hopper_solve_large_m.json: per M the same two runs (one run after a warm-up, the same call capped at three
 iterations), the training fields being the script's 30 of ``RandomState(1)`` extended to M by further draws of the same stream;
 per problem the record above; the per-iteration split callbacks / reduction / assembly / factor / solves / products / host;
