@@ -106,6 +106,67 @@ def constructed_bound(P, A, z, tol=TOL):
     return (b + np.sqrt(b * b + 4.0 * LAMBDA_MIN * c)) / (2.0 * LAMBDA_MIN)
 
 
+# ---- designs that reach the retry ladder (delta_w x 100 while a pivot fails) ------------------------------------------------------
+RUNGS = {1e-11: 2, 1e-7: 4, 1e-3: 6, 1e13: qp_ipm.MAX_RETRIES + 1}   # saddle's c -> factorization attempts per iteration
+
+
+def rung(k):
+    """delta_w of attempt k (0-based) as both backends compute it: 1e-12 multiplied k times by 100.0 in fp64"""
+    dw = qp_ipm.DELTA_W0
+    for _ in range(k):
+        dw *= qp_ipm.DELTA_W_GROWTH
+    return dw
+
+
+def saddle(n, m, j, c, seed):
+    """``constructed(n - 1, m, seed)`` on every variable but j, and variable j decoupled with negative curvature: P[j, j] = -c,
+    the rest of row and column j of P zero, q[j] = 0, A[:, j] = 0.  Pivot j of Kc0 + delta_w I has only exact zeros to subtract,
+    so it is exactly -c + delta_w in any summation order, with or without FMA: the factorization fails at pivot j on every rung
+    with delta_w <= c and the number of attempts per iteration is RUNGS[c] by design.  Row j of every right-hand side is
+    c z_j = 0, so dz_j and z_j stay exactly 0 and the other variables see ``constructed``'s QP (plus delta_w, which the
+    refinement removes).  Non-convex, so outside the solver's contract, not outside its handling.
+    -> P, q, A, l, u, z* (z*[j] = 0), y*, keep (the n - 1 indices of the constructed part)"""
+    P0, q0, A0, l, u, z0, y = constructed(n - 1, m, seed)
+    keep = np.delete(np.arange(n), j)
+    P, q, A, z = np.zeros((n, n)), np.zeros(n), np.zeros((m, n)), np.zeros(n)
+    P[np.ix_(keep, keep)] = P0
+    P[j, j] = -c
+    q[keep], A[:, keep], z[keep] = q0, A0, z0
+    return P, q, A, l, u, z, y, keep
+
+
+DEFICIENT = [(33, 10, 20, 1.0), (65, 20, 40, 1e4), (70, 35, 50, 1e6)]          # (n, r, m, scale); seed = n
+
+
+def deficient(n, r, m, seed, scale=1.0):
+    """P = scale B B' with B (n, r) and A = C B': Kc0 = B (scale I + C'D C) B' has rank r exactly, and its n - r surplus pivots
+    are rounding noise of either sign, of the order eps scale (and eps |D| late in the solve) against delta_w = 1e-12: the
+    ladder is reached by rounding.  z* is feasible, about r / 2 rows are active with multipliers |y*| >= Y_MIN, the others keep a
+    margin >= MARGIN, q = -P z* - A'y* (in the range of B, so the QP is bounded).  The solution is NOT unique (z* + null(B') is
+    optimal): judge a result by ``assert_kkt`` only.  -> P, q, A, l, u"""
+    rng = np.random.RandomState(seed)
+    B = rng.uniform(-1.0, 1.0, (n, r)) / np.sqrt(r)
+    C = rng.uniform(-1.0, 1.0, (m, r))
+    P = scale * (B @ B.T)
+    P = (P + P.T) / 2
+    A = C @ B.T
+    z = rng.uniform(-1.0, 1.0, n)
+    n_act = min(m, max(r // 2, 1))
+    act = rng.permutation(m)[:n_act]
+    y = np.zeros(m)
+    y[act] = rng.uniform(Y_MIN, 2.0, n_act) * rng.choice([-1.0, 1.0], n_act)
+    Az = A @ z
+    l, u = Az - rng.uniform(MARGIN, 1.0, m), Az + rng.uniform(MARGIN, 1.0, m)
+    u[act] = np.where(y[act] > 0, Az[act], u[act])
+    l[act] = np.where(y[act] < 0, Az[act], l[act])
+    return P, -P @ z - A.T @ y, A, l, u
+
+
+# An input that runs into the iteration cap: a tolerance below what fp64 residuals can reach (the dual residual stalls near
+# 1e-10, the primal near 1e-15) on a QP whose iterates stay finite for 200 iterations, so the only exit left is max_iter.
+CAP_QP, CAP_TOL = (33, 65, 33065), 1e-17
+
+
 def box_qp(n, seed):
     """separable: diagonal P >= 1, A = I, some coordinates active below, some above, some free: z* = clip(-q / p, l, u)"""
     rng = np.random.RandomState(seed)

@@ -136,6 +136,150 @@ def test_indefinite_input_is_reported_not_faulted(jname, what):
     assert untouched(buf, n)
 
 
+# ---- the Cholesky at the workload's sizes ---------------------------------------------------------------------------------------
+# n = 400 is the hopper's dense step at S = M = 30, 370 its arrow core, 387 the drone at S = 64.  With 256 lanes the three
+# one-lane-per-row loops (step 2 of chol_factor, "rows below" and "rows above" of chol_solve) take a second trip from n = 289
+# on (row 32 + 256), which the sizes above never reach.
+def lower(Lh, n):
+    L = np.zeros((n, n))
+    r, c = np.tril_indices(n)
+    L[r, c] = Lh[r, c]
+    return L
+
+
+@pytest.mark.parametrize("kind", ["bbt", "graded"])
+@pytest.mark.parametrize("pad", [0, 3])
+@pytest.mark.parametrize("n", [288, 289, 321, 400])
+def test_cholesky_and_solve_backward_error_at_the_workloads_sizes(n, pad, kind):
+    """the assertions of test_cholesky_and_solve_backward_error with K = 2: 288 is the last size of one trip, 289 the first of
+    two in all three loops, 321 one panel more, 400 the workload's"""
+    import torch
+    m = chol()
+    assert NB() == 32
+    K, lda = 2, n + pad
+    As = [spd(kind, n, 10 * n + k) for k in range(K)]
+    A0 = padded(As, lda)
+    L1, L2 = A0.clone(), A0.clone()
+    info = m.chol_factor(L1)
+    m.chol_factor(L2)
+    assert info.cpu().tolist() == [0] * K
+    assert L1.cpu().numpy().tobytes() == L2.cpu().numpy().tobytes()  # two calls are bitwise equal
+    assert untouched(L1, n)
+    Lh = L1.cpu().numpy()
+    Ls = [lower(Lh[k], n) for k in range(K)]
+    LLs = [np.abs(L) @ np.abs(L).T for L in Ls]
+    for k in range(K):
+        err = np.abs(Ls[k].astype(LD) @ Ls[k].T.astype(LD) - As[k].astype(LD))
+        assert np.all(err <= gamma(n + 1) * LLs[k].astype(LD)), (k, float(err.max()))
+        single = A0[k:k + 1].clone()                                 # problem k of the batch is bitwise its K = 1 call
+        assert m.chol_factor(single).cpu().tolist() == [0]
+        assert single.cpu().numpy().tobytes() == Lh[k:k + 1].tobytes()
+    rng = np.random.RandomState(n)
+    for nrhs in (1, 3):
+        ldb = n + 2
+        bh = np.full((K, nrhs, ldb), np.nan)
+        bh[:, :, :n] = rng.uniform(-1, 1, (K, nrhs, n))
+        X1, X2 = torch.as_tensor(bh, device="cuda:0"), torch.as_tensor(bh, device="cuda:0")
+        m.chol_solve(L1, X1)
+        m.chol_solve(L1, X2)
+        xh = X1.cpu().numpy()
+        assert xh.tobytes() == X2.cpu().numpy().tobytes() and np.all(np.isnan(xh[:, :, n:]))
+        for k in range(K):
+            for j in range(nrhs):
+                x = xh[k, j, :n]
+                res = np.abs(bh[k, j, :n].astype(LD) - As[k].astype(LD) @ x.astype(LD))
+                assert np.all(res <= gamma(3 * n + 1) * (LLs[k] @ np.abs(x)).astype(LD)), (k, j, float(res.max()))
+            one = torch.as_tensor(bh[k:k + 1], device="cuda:0")
+            m.chol_solve(L1[k:k + 1].contiguous(), one)
+            assert one.cpu().numpy().tobytes() == xh[k:k + 1].tobytes()
+
+
+@pytest.mark.parametrize("what", ["negative", "nan"])
+@pytest.mark.parametrize("j", [288, 300, 329])
+def test_indefinite_input_behind_a_second_trip_row(j, what):
+    """n = 330: the failing pivot sits in a row that only a second-trip lane of step 2 has solved (row >= 32 + 256);
+    info = j + 1, the neighbours bitwise unaffected"""
+    m = chol()
+    n = 330
+    rng = np.random.RandomState(j)
+    As = []
+    for k in range(3):
+        A = rng.uniform(-1, 1, (n, n))
+        As.append((A + A.T) / 2 + n * np.eye(n))                     # diagonally dominant
+    As[1][j, j] = -1.0 if what == "negative" else np.nan
+    buf = padded(As, n + 3)
+    ref = [buf[k:k + 1].clone() for k in (0, 2)]
+    info = m.chol_factor(buf)
+    assert info.cpu().tolist() == [0, j + 1, 0]
+    for k, single in zip((0, 2), ref):
+        assert m.chol_factor(single).cpu().tolist() == [0]
+        assert single.cpu().numpy().tobytes() == buf[k:k + 1].cpu().numpy().tobytes()
+    assert untouched(buf, n)
+
+
+def test_more_workgroups_than_compute_units():
+    """K = 300 problems in one launch (256 compute units): every info word 0, problems 0, 150 and 299 bitwise their K = 1 calls,
+    and their factors within the bound"""
+    m = chol()
+    K, n = 300, 33
+    rng = np.random.RandomState(300)
+    As = []
+    for k in range(K):
+        B = rng.uniform(-1, 1, (n, n))
+        A = B @ B.T + np.eye(n)
+        As.append((A + A.T) / 2)
+    A0 = padded(As, n + 3)
+    L = A0.clone()
+    assert m.chol_factor(L).cpu().tolist() == [0] * K
+    assert untouched(L, n)
+    Lh = L.cpu().numpy()
+    for k in (0, 150, 299):
+        single = A0[k:k + 1].clone()
+        assert m.chol_factor(single).cpu().tolist() == [0]
+        assert single.cpu().numpy().tobytes() == Lh[k:k + 1].tobytes()
+        Lk = lower(Lh[k], n)
+        err = np.abs(Lk.astype(LD) @ Lk.T.astype(LD) - As[k].astype(LD))
+        assert np.all(err <= gamma(n + 1) * (np.abs(Lk) @ np.abs(Lk).T).astype(LD)), (k, float(err.max()))
+
+
+def test_device_base_scatters_a_retry_and_gathers_a_subset():
+    """``ipm.DeviceBase`` on its own (no model): all four problems factored, problem 2 factored again with another matrix as a
+    delta_w retry does, then a solve for problems 0, 2, 3 -- row 2 must come from the SECOND factor, problem 1's factor must
+    survive the scatter"""
+    import torch
+    m = chol()
+    n_all, n = 4, 65
+    lda = n + 3
+    As = [spd("bbt", n, 650 + k) for k in range(n_all)]
+    A2 = spd("graded", n, 659)
+    first, second = padded(As, lda), padded([A2], lda)
+    Lref, Lref2 = first.clone(), second.clone()
+    assert m.chol_factor(Lref).cpu().tolist() == [0] * n_all and m.chol_factor(Lref2).cpu().tolist() == [0]
+    be = m.DeviceBase(torch.device("cuda:0"), n_all)
+    assert be.factor_device([0, 1, 2, 3], first) == [0] * n_all
+    assert be.L.shape == (n_all, n, lda) and be.L.cpu().numpy().tobytes() == Lref.cpu().numpy().tobytes()
+    keep1 = be.L[1].cpu().numpy().tobytes()
+    assert be.factor_device([2], second) == [0]
+    Lh = be.L.cpu().numpy()
+    assert Lh[1].tobytes() == keep1                                   # untouched by the scatter
+    assert Lh[2].tobytes() == Lref2[0].cpu().numpy().tobytes()
+    assert Lh[0].tobytes() == Lref[0].cpu().numpy().tobytes() and Lh[3].tobytes() == Lref[3].cpu().numpy().tobytes()
+    rng = np.random.RandomState(65)
+    B = [rng.uniform(-1, 1, n) for _ in range(3)]
+    X = be.solve_device([0, 2, 3], B)
+    assert X.shape == (3, n)
+
+    def within_bound(A, Ldev, b, x):                                  # |b - A x| <= gamma_(3n+1) |L| |L'| |x| for factor Ldev of A
+        Lk = lower(Ldev.cpu().numpy(), n)
+        res = np.abs(b.astype(LD) - A.astype(LD) @ x.astype(LD))
+        return bool(np.all(res <= gamma(3 * n + 1) * ((np.abs(Lk) @ np.abs(Lk).T) @ np.abs(x)).astype(LD)))
+    for row, (Ldev, A) in enumerate(((Lref[0:1], As[0]), (Lref2, A2), (Lref[3:4], As[3]))):
+        b = torch.as_tensor(B[row][None, None, :].copy(), device="cuda:0")
+        m.chol_solve(Ldev.contiguous(), b)
+        assert b[0, 0].cpu().numpy().tobytes() == X[row].tobytes(), row
+        assert within_bound(A, Ldev[0], B[row], X[row]), row          # row 1: the retry's matrix, not the first one
+
+
 def device_model(S, M, method, phases, alpha=0.2):
     from riskaversetrajopt_amd import hopper
     return hopper.Model(M, method, alpha, S=S, fields=H.fields(M), phases=phases, precision='f64')

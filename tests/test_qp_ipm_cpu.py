@@ -77,6 +77,87 @@ def test_constructed_qp_recovers_the_designed_solution(n, m, seed):
     assert np.all(np.sign(y[np.abs(ys) > 0]) == np.sign(ys[np.abs(ys) > 0]))
 
 
+# ---- designs that reach the retry ladder ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", [1e-11, 1e-7, 1e-3])
+@pytest.mark.parametrize("n,m,j", [(70, 85, 0), (70, 85, 31), (70, 85, 32), (70, 85, 69), (33, 40, 32), (130, 85, 96)])
+def test_saddle_takes_the_designed_number_of_rungs(n, m, j, c):
+    """``_qp_ipm.saddle``: pivot j is exactly -c + delta_w, so every iteration factors RUNGS[c] times -- a count the design fixes,
+    not rounding.  z_j stays exactly 0 and the other variables solve ``constructed``'s QP.  Here (70 x 85): 13 to 16 iterations."""
+    P, q, A, l, u, zs, _, keep = H.saddle(n, m, j, c, 1000 * n + 10 * m + j)
+    z, y, info = qp_ipm.solve_numpy(P, q, A, l, u, TOL, 100)            # past the presolve, as the device test goes
+    print(f"saddle n={n} m={m} j={j} c={c}: {info['status']} in {info['iterations']} iterations, {info['factorizations']} factorizations")
+    assert info["status"] == "solved" and 0 < info["iterations"] <= H.ITER_CAP
+    assert info["factorizations"] == H.RUNGS[c] * info["iterations"]
+    assert z[j] == 0.0
+    H.assert_kkt(P, q, A, l, u, z, y, what=f"saddle n={n} m={m} j={j} c={c}")
+    assert np.max(np.abs(z[keep] - zs[keep])) <= H.constructed_bound(P[np.ix_(keep, keep)], A[:, keep], zs[keep])
+    pre = qp_ipm.presolve(P, q, A, l, u)                                # the presolve would drop nothing here
+    assert pre["cols"].size == n and pre["rows"].size == m
+
+
+@pytest.mark.parametrize("j", [0, 31, 32, 69])
+def test_saddle_beyond_the_last_rung_exhausts_the_ladder(j):
+    """c = 1e13 is above the 13th rung (1e-12 x 100^12 ~ 1e12): 'numerical' with 0 iterations, 13 factorizations, z the start"""
+    P, q, A, l, u, _, _, _ = H.saddle(70, 85, j, 1e13, 1000 * 70 + 10 * 85 + j)
+    z, y, info = qp_ipm.solve_numpy(P, q, A, l, u, TOL, 100)
+    assert H.rung(qp_ipm.MAX_RETRIES) < 1e13
+    assert info["status"] == "numerical" and info["iterations"] == 0 and info["factorizations"] == qp_ipm.MAX_RETRIES + 1 == 13
+    assert np.all(z == 0.0) and np.all(np.isfinite(y))
+
+
+def test_rungs_are_what_the_design_says():
+    """RUNGS[c] counts the attempts up to the first whose pivot -c + delta_w is positive (all 13 when none is), for the deltas
+    both backends compute (1e-12 multiplied by 100.0 in fp64); no rung lies within a factor 2 of c, so rounding cannot decide"""
+    attempts = qp_ipm.MAX_RETRIES + 1
+    for c, rungs in H.RUNGS.items():
+        failing = sum(not (-c + H.rung(k) > 0.0) for k in range(attempts))
+        assert min(failing + 1, attempts) == rungs
+        assert all(not (0.5 < H.rung(k) / c < 2.0) for k in range(attempts))
+
+
+@pytest.mark.parametrize("n,r,m,scale", H.DEFICIENT)
+def test_deficient_reaches_the_ladder_by_rounding(n, r, m, scale):
+    """``_qp_ipm.deficient``: Kc0 has rank r, the n - r surplus pivots are rounding noise.  The solution is not unique, so the
+    KKT residuals judge it.  Here: 18 factorizations in 11 iterations (33, 10, 20, 1), 48 in 17 (65, 20, 40, 1e4), 72 in 20
+    (70, 35, 50, 1e6)."""
+    P, q, A, l, u = H.deficient(n, r, m, n, scale)
+    assert np.linalg.matrix_rank(P) == r
+    z, y, info = qp_ipm.solve_numpy(P, q, A, l, u, TOL, 100)
+    print(f"deficient n={n} r={r} m={m} scale={scale:g}: {info['status']}, {info['factorizations']} factorizations in "
+          f"{info['iterations']} iterations")
+    assert info["status"] == "solved" and info["iterations"] <= H.ITER_CAP
+    H.assert_kkt(P, q, A, l, u, z, y, what=f"deficient n={n} r={r}")
+    assert info["factorizations"] > info["iterations"]
+    if scale > 1.0:
+        assert info["factorizations"] >= 2 * info["iterations"]
+
+
+@pytest.mark.parametrize("k", [0, 1])
+@pytest.mark.parametrize("n,m", [(256, 384), (255, 383), (256, 0), (1, 384)])
+def test_constructed_qp_at_the_entry_points_largest_shapes(n, m, k):
+    """the shapes tests/test_gpu_qp_ipm_paths.py runs on the device, both seeds: 18, 19, 1 and 9 iterations here at k = 0,
+    18, 17, 1 and 6 at k = 1"""
+    P, q, A, l, u, zs, _ = H.constructed(n, m, 1000 * n + 10 * m + k)
+    z, y, info = qp_ipm.solve_numpy(P, q, A.reshape(m, n), l, u, TOL, 100)
+    print(f"n={n} m={m} k={k}: {info['status']} in {info['iterations']} iterations, {info['factorizations']} factorizations")
+    assert info["status"] == "solved" and info["iterations"] <= H.ITER_CAP
+    H.assert_kkt(P, q, A.reshape(m, n), l, u, z, y, what=f"constructed n={n} m={m}")
+    assert np.max(np.abs(z - zs)) <= H.constructed_bound(P, A.reshape(m, n), zs)
+
+
+def test_unreachable_tolerance_runs_into_max_iter_and_the_hard_cap():
+    """``_qp_ipm.CAP_QP`` at tol = 1e-17: the iterates stay finite and the stop rule is never met, so the solve ends 'max_iter'
+    at exactly max_iter iterations -- 150 for 150, 200 for 200, and 200 again for 10**6 (HARD_CAP), with the bytes of 200"""
+    P, q, A, l, u, _, _ = H.constructed(*H.CAP_QP)
+    runs = {mi: qp_ipm.solve_numpy(P, q, A, l, u, H.CAP_TOL, mi) for mi in (150, 200, 10 ** 6)}
+    for mi, (z, y, info) in runs.items():
+        print(f"max_iter={mi}: {info['status']} in {info['iterations']} iterations, {info['factorizations']} factorizations")
+        assert info["status"] == "max_iter" and info["iterations"] == min(mi, qp_ipm.HARD_CAP) and np.all(np.isfinite(z))
+    assert qp_ipm.HARD_CAP == 200
+    assert runs[10 ** 6][0].tobytes() == runs[200][0].tobytes() and runs[10 ** 6][1].tobytes() == runs[200][1].tobytes()
+    assert runs[150][0].tobytes() != runs[200][0].tobytes()          # the last 50 iterations move the point: the cap is what binds
+
+
 # ---- the driving Gaussian QPs ------------------------------------------------------------------------------------------------------
 def driving_cases():
     cases = [(20, 0.05, name) for name in ("scp_iter0", "warmup1")]            # the warm-up pair at S = 20
