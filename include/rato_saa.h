@@ -950,6 +950,8 @@ int rato_nnls_warm(const double* A, int32_t m, int32_t n, const double* b, uint8
  * O(n m_eq); a solve is one warm-started rato_nnls_warm on the rows so far.
  *   rato_master_solve -> 1: z (n doubles) and lam (one multiplier >= 0 per row);  0: NNLS did not converge;
  *                        RATO_EINFEASIBLE.
+ * A row that vanishes in the null space of the equalities (a combination of rows of A_eq, or all zero) is constant on the
+ * feasible set and is decided when it is added: it holds (multiplier 0) or every later solve returns RATO_EINFEASIBLE.
  */
 typedef struct rato_master rato_master;
 int rato_master_create(rato_master** out, int32_t n, const double* p_diag, const double* q, int32_t m_eq,

@@ -12,7 +12,12 @@
 //   * the problem in v (z = x0 + N (v - c)) is a least-distance problem  min |v|  s.t.  G v >= h, solved through NNLS
 //     (Lawson & Hanson ch. 23) on [G' ; h'/sigma] with the passive set of the previous solve as the start AND its thin QR
 //     factor kept (rato_nnls.h; round 6); sigma ~ |v| (within a factor 4) keeps the KKT tolerance of the NNLS meaningful
-//     for optima far out.
+//     for optima far out;
+//   * two kinds of rows never reach the NNLS's tolerance ("Rows the master decides without the NNLS"): a row that
+//     VANISHES in the null space of the equalities (|a N| <= VANISH_REL |a D^-1/2|: a combination of equality rows, or all
+//     zero) is the constant  a x0 <= b  on every feasible point -- decided when it is added (vacuous, or the problem is
+//     infeasible); and the column of a LOOSE row (h / sigma < -LOOSE_REL: inactive unless |v| >= LOOSE_REL sigma) is left out
+//     of a1, the column norm that scales the KKT tolerance of every other column.
 // The reference hands the whole subproblem to OSQP (drone_risk.py:433-457).
 #include <math.h>
 #include <stdint.h>
@@ -43,7 +48,8 @@ struct rato_master {
   rato_nnls::ThinQR qr;
   bool factor_ready = false;
   int an_cols = 0, changes = 0;       // columns of An in place; updates + downdates since the factor was last built
-  double sigma = 0.0, a1 = 0.0;      // the scale An was built with; max column 1-norm of An
+  double sigma = 0.0, a1 = 0.0;      // the scale An was built with; max column 1-norm of An (loose columns left out)
+  bool infeasible = false;           // a vanishing row  a x0 <= b  does not hold: no feasible point, whatever else is added
   std::vector<double> nn_s, nn_resid, bn;
   std::vector<uint8_t> nn_banned;
 
@@ -149,13 +155,20 @@ extern "C" int32_t rato_master_rows(const rato_master* M) { return M ? M->nrows 
 extern "C" int rato_master_add_rows(rato_master* M, int32_t k, const double* A, const double* b) {
   if (!M || k < 0 || (k > 0 && (!A || !b))) return RATO_EINVAL;
   const int n = M->n, m = M->m, nk = M->nk;
+  // |a N| <= VANISH_REL |a D^-1/2|: what is left of the row in the null space is the rounding of the m reflectors (a few
+  // n eps); the same ratio rato_master_create uses for the rank of the equalities
+  constexpr double VANISH_REL = 1e-10, VANISH_SLACK = 1e-9;
   for (int j = 0; j < k; ++j) {
     const double* a = A + (size_t)j * n;
     double* t = M->work.data();
-    double ax0 = 0.0;
+    double ax0 = 0.0, tn = 0.0, ax0_abs = 0.0;
     for (int i = 0; i < n; ++i) {
       t[i] = a[i] * M->d[i];
       ax0 += a[i] * M->x0[i];
+    }
+    for (int i = 0; i < n; ++i) {
+      tn += t[i] * t[i];
+      ax0_abs += fabs(a[i] * M->x0[i]);
     }
     M->apply_Qt(t);                       // E = a N = t[m:]
     double ec = 0.0, nrm = 0.0;
@@ -163,10 +176,21 @@ extern "C" int rato_master_add_rows(rato_master* M, int32_t k, const double* A, 
       ec += t[m + i] * M->c[i];
       nrm += t[m + i] * t[m + i];
     }
-    const double f = b[j] - ax0 + ec;
-    const double s = fmax(sqrt(nrm), 1e-300);
     const size_t at = M->rows.size();
     M->rows.resize(at + nk + 1);
+    if (sqrt(nrm) <= VANISH_REL * sqrt(tn)) {   // (a NaN row is not decided here: it goes on as before)
+      // the row is constant on the feasible set: a z = a x0.  It holds (a placeholder  0 . v >= -1  keeps the row count and
+      // the multipliers' layout: its column [0; -1/sigma] never has a positive dual) or nothing is feasible.
+      if (b[j] - ax0 < -VANISH_SLACK * (ax0_abs + fabs(b[j]))) M->infeasible = true;
+      for (int i = 0; i < nk; ++i) M->rows[at + i] = 0.0;
+      M->rows[at + nk] = -1.0;
+      M->sc.push_back(1.0);
+      M->passive.push_back(0);
+      ++M->nrows;
+      continue;
+    }
+    const double f = b[j] - ax0 + ec;
+    const double s = fmax(sqrt(nrm), 1e-300);
     for (int i = 0; i < nk; ++i) M->rows[at + i] = -(t[m + i] / s);
     M->rows[at + nk] = -(f / s);
     M->sc.push_back(s);
@@ -182,8 +206,13 @@ extern "C" int rato_master_solve(rato_master* M, double* z, double* lam) {
   if (!M || !z || (M->nrows > 0 && !lam)) return RATO_EINVAL;
   const int n = M->n, m = M->m, nk = M->nk, r = M->nrows;
   std::vector<double> v(nk, 0.0);
+  if (M->infeasible) return RATO_EINFEASIBLE;
   if (r > 0) {
     constexpr int FACTOR_REFRESH = 96;
+    // a column whose last entry h / sigma is below -LOOSE_REL belongs to a row that is inactive unless |v| >= LOOSE_REL sigma:
+    // it stays in the NNLS (its dual is still tested), but its norm does not scale the tolerance of the other columns --
+    // with a1 ~ 1e13 that tolerance exceeded every dual and the NNLS "converged" at y = 0
+    constexpr double LOOSE_REL = 1e6;
     // sigma sticks while |v| stays within a factor SIGMA_STICK of it.  Not wider: near convergence the cuts are nearly
     // parallel and differ mostly in h; a sigma 3x too large (left over from an earlier, larger |v|) shrank those differences
     // until the NNLS cycled between near-dependent columns (found on tests/test_gpu_scp.py's M = 40 case with a factor 4).
@@ -211,7 +240,7 @@ extern "C" int rato_master_solve(rato_master* M, double* z, double* lam) {
         }
         col[nk] = row[nk] / M->sigma;
         sj += fabs(col[nk]);
-        if (sj > M->a1) M->a1 = sj;
+        if (sj > M->a1 && !(col[nk] < -LOOSE_REL)) M->a1 = sj;
       }
       M->an_cols = r;
     };

@@ -784,7 +784,8 @@ def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, che
     lets every solver's Python-side state follow its native one (a later solve_reduced continues from there).
     ``run(handle, keep, idle, n_keep, us_hist, rec, brec, status, done, rounds, stream)`` -> status: the system's
     rato_scp_batch_run_* with its own leading arguments bound; ``what``: its name, for error messages.
-    -> dict(us_hist (K, iters, S, n_u), cuts / t_risk / slack / iter_status / master_s_problem (K, iters), status (K) (RATO_*
+    -> dict(us_hist (K, iters, S, n_u), cuts / t_risk / slack / iter_status / recycled (the kept cuts an iteration started
+    with) / master_s_problem (K, iters), status (K) (RATO_*
     per problem), done (K), rounds, and the batch-level clocks define_s / oracle_s / master_s / total_s / rounds_per_iter
     (iters))"""
     C = _lib.C
@@ -832,7 +833,8 @@ def scp_batch_run(lib, device, solvers, us0, iters, run, what, n_threads=16, che
     f = lambda key: np.array([[getattr(rec[k * n_it + i], key) for i in range(it)] for k in range(K)]).reshape(K, it)
     g = lambda key: np.array([getattr(brec[i], key) for i in range(it)])
     return {"us_hist": us_hist[:, :it], "cuts": f("cuts").astype(np.int64), "t_risk": f("t_risk"), "slack": f("slack"),
-            "iter_status": f("status").astype(np.int64), "master_s_problem": f("master_s"), "status": status.copy(),
+            "iter_status": f("status").astype(np.int64), "recycled": f("recycled").astype(np.int64),
+            "master_s_problem": f("master_s"), "status": status.copy(),
             "done": done.copy(), "rounds": int(rounds.value), "define_s": g("define_s"), "oracle_s": g("oracle_s"),
             "master_s": g("master_s"), "total_s": g("total_s"), "rounds_per_iter": g("rounds").astype(np.int64),
             "active": g("active").astype(np.int64)}

@@ -251,7 +251,11 @@ class MasterNative:
 
 
 class MasterPy:
-    """NumPy form of ``Master`` (general Hessian; also the reference the native one is tested against)."""
+    """NumPy form of ``Master`` (general Hessian; also the reference the native one is tested against).  The two kinds of
+    rows the native master keeps away from the tolerance of its NNLS are treated the same way here: a row that vanishes in
+    the null space of the equalities is decided when it is added (vacuous, or infeasible), and a loose row (h / sigma <
+    -LOOSE_REL) is left out of the NNLS, with the solution checked against it afterwards."""
+    VANISH_REL, VANISH_SLACK, LOOSE_REL = 1e-10, 1e-9, 1e6        # (csrc/master.hip)
 
     def __init__(self, P, q, A_eq, b_eq):
         P = np.asarray(P, dtype=np.float64)
@@ -273,6 +277,7 @@ class MasterPy:
             self.L = None
             self.Linv_c = self.N.T @ (P @ self.x0 + q)                           # H = I
             self.NLinvT = self.N
+            self._whiten = lambda A: A * d[None, :]
         else:
             if self.N is None:
                 self.N = _null_space(A_eq)
@@ -281,6 +286,9 @@ class MasterPy:
             self.L = np.linalg.cholesky(H)
             self.Linv_c = sla.solve_triangular(self.L, c, lower=True)
             self.NLinvT = sla.solve_triangular(self.L, self.N.T, lower=True).T      # N L^-T  (n x k)
+            Lp = np.linalg.cholesky(P)
+            self._whiten = lambda A: sla.solve_triangular(Lp, A.T, lower=True).T    # rows of A P^-1/2 (up to a rotation)
+        self.infeasible = False
         self.G = np.zeros((0, self.N.shape[1]))
         self.h = np.zeros(0)
         self.sc = np.zeros(0)
@@ -294,11 +302,21 @@ class MasterPy:
         E = A_in @ self.NLinvT
         f = b_in - A_in @ self.x0 + E @ self.Linv_c
         sc = np.maximum(np.linalg.norm(E, axis=1), 1e-300)
-        self.G = np.vstack([self.G, -(E / sc[:, None])])
-        self.h = np.concatenate([self.h, -(f / sc)])
+        G, h = -(E / sc[:, None]), -(f / sc)
+        # rows that vanish in the null space of the equalities: constant on the feasible set, a z = a x0
+        gone = np.linalg.norm(E, axis=1) <= self.VANISH_REL * np.linalg.norm(self._whiten(A_in), axis=1)
+        if gone.any():
+            f0 = b_in - A_in @ self.x0
+            if np.any(gone & (f0 < -self.VANISH_SLACK * (np.abs(A_in) @ np.abs(self.x0) + np.abs(b_in)))):
+                self.infeasible = True
+            G[gone], h[gone], sc[gone] = 0.0, -1.0, 1.0            # the placeholder 0 . v >= -1
+        self.G = np.vstack([self.G, G])
+        self.h = np.concatenate([self.h, h])
         self.sc = np.concatenate([self.sc, sc])
 
     def solve(self):
+        if self.infeasible:
+            raise InfeasibleError("master QP infeasible")
         if self.G.shape[0] == 0:
             v = np.zeros(self.N.shape[1])
             lam = np.zeros(0)
@@ -307,21 +325,34 @@ class MasterPy:
             # slack) the KKT tolerance of the NNLS would accept constraint violations of tol (1 + |v|^2).  Solve for
             # v / sigma instead, sigma ~ |v| (previous solve, or the lower bound max_j h_j: rows are unit vectors).
             sigma = max(1.0, self.vnorm, float(self.h.max(initial=0.0)))
-            A_n = np.vstack([self.G.T, (self.h / sigma)[None, :]])
-            b_n = np.zeros(A_n.shape[0])
+            A_all = np.vstack([self.G.T, (self.h / sigma)[None, :]])
+            b_n = np.zeros(A_all.shape[0])
             b_n[-1] = 1.0
-            ok = False
-            if self.warm:
-                y, P, ok = nnls_warm(A_n, b_n, self.passive)
-                if ok:
-                    self.passive = P
-            if not ok:                               # cold fallback: scipy's Lawson-Hanson
-                y, _ = nnls(A_n, b_n, maxiter=20 * A_n.shape[1])
-                self.passive = y > 0.0
-            r = A_n @ y - b_n
-            if abs(r[-1]) < 1e-14:
-                raise InfeasibleError("master QP infeasible")
-            v = -sigma * r[:-1] / r[-1]
+            # loose rows (inactive unless |v| >= LOOSE_REL sigma) stay out of the NNLS: the 1-norm of their columns would
+            # scale its KKT tolerance beyond every dual.  The solution is checked against them; one that does reach such a
+            # row (an optimum far beyond sigma) is solved again with every column.
+            use = A_all[-1] >= -self.LOOSE_REL
+            while True:
+                A_n = A_all[:, use]
+                passive0 = np.zeros(A_all.shape[1], dtype=bool)
+                passive0[:len(self.passive)] = self.passive
+                ok = False
+                if self.warm:
+                    yu, P, ok = nnls_warm(A_n, b_n, passive0[use])
+                if not ok:                           # cold fallback: scipy's Lawson-Hanson
+                    yu, _ = nnls(A_n, b_n, maxiter=20 * A_n.shape[1])
+                    P = yu > 0.0
+                y = np.zeros(A_all.shape[1])
+                y[use] = yu
+                r = A_all @ y - b_n
+                if abs(r[-1]) < 1e-14:
+                    raise InfeasibleError("master QP infeasible")
+                v = -sigma * r[:-1] / r[-1]
+                if use.all() or np.all(self.G[~use] @ v >= self.h[~use]):
+                    break
+                use = np.ones_like(use)
+            self.passive = np.zeros(A_all.shape[1], dtype=bool)
+            self.passive[use] = P
             lam = sigma * (y / (-r[-1])) / self.sc
             self.vnorm = float(np.linalg.norm(v))
         return self.x0 + self.NLinvT @ (v - self.Linv_c), lam

@@ -161,7 +161,8 @@ def run_drone_reduced_batch(models, num_scp_iters_max=60, tol=None, n_threads=No
     with its own samples and alpha); anything else is a ValueError.
     -> one dict per Model with the keys of run_drone_reduced (us, us_hist, t_risk, cuts, L2_error, loop), where define_s /
     solve_s / cumulative_s are the BATCH's per-iteration clocks (lockstep has no per-problem clock), plus ``rounds`` (the
-    batched oracle round trips of the whole run).  A problem the native loop hands back (rank-deficient master, a selection
+    batched oracle round trips of the whole run), ``rounds_per_iter``, and per iteration of the problem ``recycled`` (the kept
+    cuts it started with) and ``slack`` (the master's slack: t_risk = VaR of the last evaluation + slack).  A problem the native loop hands back (rank-deficient master, a selection
     that gave up) is re-run alone through run_drone_reduced from the initial guess with a fresh cut solver (cold; tagged in
     ``loop``).  A problem that fails (non-finite values, infeasible master) leaves the batch while the others finish; then
     the exception class of the solo path is raised, naming the problem -- or, with on_error="return", its dict is
@@ -220,7 +221,9 @@ def _run_reduced_batch(system, entry, solo, rerun, models, num_scp_iters_max, to
         err = np.array([L2_error_us(u, p) for u, p in zip(hist, prev)])
         out.append({"us": hist[-1], "t_risk": float(r["t_risk"][k, -1]), "define_s": define_s, "solve_s": solve_s,
                     "cumulative_s": cumulative, "L2_error": err, "cuts": r["cuts"][k], "us_hist": hist,
-                    "rounds": r["rounds"], "loop": "native batch (%s)" % entry})
+                    "rounds": r["rounds"], "rounds_per_iter": r["rounds_per_iter"], "recycled": r["recycled"][k],
+                    "slack": r["slack"][k],
+                    "loop": "native batch (%s)" % entry})
     if failed and on_error == "raise":
         raise failed[0][1]
     return out
