@@ -1413,6 +1413,78 @@ int rato_hopper_arrow_edot_f64(int32_t K, int64_t M, const double* e, const doub
 int rato_hopper_arrow_eapply_f64(int32_t K, int64_t M, const double* e, const double* v, const double* kappa, double* out,
                                  void* stream);
 
+/* ---- The interior-point driver's O(n + m) algebra on a state that stays on the device, fp64 (csrc/ipm_driver.hip): what
+ * riskaversetrajopt_amd/ipm.py (Problem, newton_steps, solve_group) does on the host between the launches of a Newton step,
+ * restated phase by phase.  ABI: additive (RATO_ABI_VERSION stays 12).  Model independent.  K problems per
+ * launch, one workgroup of 256 lanes per problem, device pointers, stream ordered, no allocation, no workspace, no
+ * floating-point atomics.  Every loop is lane-strided over ascending indices; a max is exact; a sum takes the per-lane
+ * partials in ascending order, the wave's fixed tree and then the four waves in order: two calls are bitwise equal and problem
+ * k of a batch is bitwise its K = 1 call.
+ *
+ * The state.  v = (z, s), nv = n + nI; rows of [K][ldv] arrays hold vectors of length nv or n, rows of [K][ldm] arrays
+ * vectors over the m constraint rows; padding is never read or written.  vL / vU: -inf / +inf where a bound is absent.
+ * row_slack [m] (shared): the slack number in [0, nI) of an inequality row, -1 for an equality row (whose value is gL).
+ * The objective is f = 1/2 sf sum curv z^2.  rec [K][RATO_IPM_REC] is the record of scalars the host reads back; status is
+ * RATO_IPM_RUNNING or the index into ('converged', 'max_iter', 'line_search').  A problem whose status is not
+ * RATO_IPM_RUNNING is left untouched by every call, and so is one that is not searching by _trial and _accept. */
+#define RATO_IPM_REC 32
+#define RATO_IPM_RUNNING (-1)
+enum {
+  RATO_IPM_MU = 0, RATO_IPM_NU, RATO_IPM_DW, RATO_IPM_DC, RATO_IPM_TOL, RATO_IPM_E0, RATO_IPM_PRIM, RATO_IPM_DUAL,
+  RATO_IPM_A_MAX, RATO_IPM_A_DUAL, RATO_IPM_C1, RATO_IPM_DBAR, RATO_IPM_QUAD, RATO_IPM_PHI, RATO_IPM_DPHI, RATO_IPM_ALPHA,
+  RATO_IPM_TRIALS, RATO_IPM_ITERATIONS, RATO_IPM_STATUS, RATO_IPM_SF, RATO_IPM_MU_PASSES, RATO_IPM_SEARCHING,
+  RATO_IPM_PHI_T, RATO_IPM_BARRIER, RATO_IPM_OBJECTIVE, RATO_IPM_ACCEPTED
+};
+typedef struct rato_ipm_state {
+  int32_t K, n, nI, m;
+  int64_t ldv, ldm;
+  const int32_t* row_slack;          /* [m] */
+  double *v, *zl, *zu;               /* [K][ldv] the iterate and the bound multipliers */
+  const double *vL, *vU, *curv;      /* [K][ldv] bounds (nv), objective curvature (n) */
+  double* y;                         /* [K][ldm] */
+  const double* gL;                  /* [K][ldm] read on equality rows */
+  double* rec;                       /* [K][RATO_IPM_REC] */
+  double *Sigma, *gbar, *dv, *dzl, *dzu, *vt;      /* [K][ldv] work, length nv */
+  double *gradf, *rz, *dz, *ez;                    /* [K][ldv] work, length n */
+  double* diag;                                    /* [K][n]: what rato_dense_normal_matrix_f64 takes */
+  double *c, *d, *w, *rs, *dyE, *r2, *q, *dy;      /* [K][ldm] work; rs on inequality rows, dyE and r2 on equality rows */
+} rato_ipm_state;
+size_t rato_ipm_state_bytes(void);
+/* rato_ipm_g_rows_f64: g[k] = (g0[k] (m0 entries), J1 z[k] (m1 rows of the shared block J1 [m1][ld1 >= n])), g [K][ldg >= m0 + m1].
+ * rato_ipm_residuals_f64 (Problem.residuals, error, the status and mu logic of solve_group, prepare_step): from g [K][ldg >= m]
+ *   and JTy [K][ldj >= n] -> c, gradf, prim, dual, E0; status 'line_search' (E0 not finite) | 'converged' (E0 <= tol) |
+ *   'max_iter' (last != 0); otherwise the mu loop (mu <- max(tol / 10, min(0.2 mu, mu sqrt(mu))), nu <- 0 while E_mu <= 10 mu and
+ *   mu > tol / 10; mu_passes counts), then Sigma, gbar, rz, rs, dc = 1e-8 sqrt(sqrt(mu)), d, w, dw = 0, diag = Sigma_z + dw + sf curv.
+ * rato_ipm_newton_f64 (newton_steps), by phase, a / b [K][ld >= the length read]:
+ *   RHS     a = J'w                  dz <- -(rz + a)                 (the right-hand side; the solve turns it into dz in place)
+ *   LADDER  info [K] int32, attempt  where info != 0: dw <- 1e-4 or 8 dw and diag again; status 'line_search' once attempt >= 60
+ *   Q       a = J dz, first          dyE <- (a + c)_E / dc if first; r2, q
+ *   R       a = W dz, b = J'q        ez <- -(rz + (a + sf curv dz) + (Sigma_z + dw) dz + b)      (solved in place into ez)
+ *   UPDATE  a = J ez                 dz += ez, dyE += (a_E - r2) / dc
+ *   FINISH  a = J dz                 ds, dv, dy
+ * rato_ipm_step_setup_f64 (solve_group's step setup): Hdv = W dv_z [K][ldh >= n] -> dzl, dzu, a_max, a_dual, c1, Dbar, quad, the
+ *   nu rule, Dphi, phi = objective + barrier + nu c1, alpha = a_max, trials = 0, searching = 1.
+ * rato_ipm_trial_f64: vt <- v + alpha dv for the searching problems.
+ * rato_ipm_accept_f64: gt = g(vt_z) [K][ldg >= m] -> phi_t and the Armijo test; accepted: v, y, zl, zu (the kappa_Sigma clip),
+ *   iterations + 1, searching = 0; else alpha / 2, or status 'line_search' at 40 trials.
+ * RATO_EINVAL without a launch on a NULL pointer, K outside [1, 65535], n < 1, nI < 0, m < 1, nI > m, ldv < n + nI, ldm < m, a
+ * leading dimension below the length it serves, or an unknown phase. */
+#define RATO_IPM_PHASE_RHS 0
+#define RATO_IPM_PHASE_LADDER 1
+#define RATO_IPM_PHASE_Q 2
+#define RATO_IPM_PHASE_R 3
+#define RATO_IPM_PHASE_UPDATE 4
+#define RATO_IPM_PHASE_FINISH 5
+int rato_ipm_g_rows_f64(int32_t K, int32_t n, const double* g0, int32_t m0, int64_t ldg0, const double* J1, int32_t m1, int64_t ld1,
+                        const double* z, int64_t ldz, double* g, int64_t ldg, void* stream);
+int rato_ipm_residuals_f64(const rato_ipm_state* st, const double* g, int64_t ldg, const double* JTy, int64_t ldj, int32_t last,
+                           void* stream);
+int rato_ipm_newton_f64(const rato_ipm_state* st, int32_t phase, const double* a, int64_t lda, const double* b, int64_t ldb,
+                        const int32_t* info, int32_t flag, void* stream);
+int rato_ipm_step_setup_f64(const rato_ipm_state* st, const double* Hdv, int64_t ldh, void* stream);
+int rato_ipm_trial_f64(const rato_ipm_state* st, void* stream);
+int rato_ipm_accept_f64(const rato_ipm_state* st, const double* gt, int64_t ldg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

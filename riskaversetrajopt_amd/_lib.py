@@ -99,8 +99,33 @@ class ScpBatchIter(C.Structure):
                [(k, C.c_int32) for k in ("rounds", "active", "reserved0", "reserved1")]
 
 
+class IpmState(C.Structure):
+    """rato_ipm_state (include/rato_saa.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("K", "n", "nI", "m")] + [("ldv", C.c_int64), ("ldm", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("row_slack", "v", "zl", "zu", "vL", "vU", "curv", "y", "gL", "rec",
+                                          "Sigma", "gbar", "dv", "dzl", "dzu", "vt", "gradf", "rz", "dz", "ez", "diag",
+                                          "c", "d", "w", "rs", "dyE", "r2", "q", "dy")]
+
+
+IPM_REC = 32                 # RATO_IPM_REC; the enum of include/rato_saa.h in its order:
+IPM_FIELDS = ("mu", "nu", "dw", "dc", "tol", "E0", "prim", "dual", "a_max", "a_dual", "c1", "Dbar", "quad", "phi", "Dphi",
+              "alpha", "trials", "iterations", "status", "sf", "mu_passes", "searching", "phi_t", "barrier", "objective",
+              "accepted")
+IPM_RUNNING = -1
+IPM_PHASES = {"rhs": 0, "ladder": 1, "q": 2, "r": 3, "update": 4, "finish": 5}   # RATO_IPM_PHASE_*
+
+
 # name -> (restype, argtypes); mirrors include/rato_saa.h one to one
 SIGNATURES = {
+    "rato_ipm_state_bytes": (C.c_size_t, []),
+    "rato_ipm_g_rows_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, C.c_int32, C.c_int64, c_float_p, C.c_int32, C.c_int64,
+                                      c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
+    "rato_ipm_residuals_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_float_p, C.c_int64, C.c_int32, c_stream]),
+    "rato_ipm_newton_f64": (C.c_int, [C.POINTER(IpmState), C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_int64, c_float_p,
+                                      C.c_int32, c_stream]),
+    "rato_ipm_step_setup_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_stream]),
+    "rato_ipm_trial_f64": (C.c_int, [C.POINTER(IpmState), c_stream]),
+    "rato_ipm_accept_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_stream]),
     "rato_abi_version": (C.c_int, []),
     "rato_packed_tile_stride": (C.c_size_t, [C.c_size_t]),
     "rato_packed_buffer_floats": (C.c_size_t, [C.c_size_t, C.c_size_t]),
@@ -358,6 +383,8 @@ def load():
     if lib.rato_hopper_nlp_params_bytes() != C.sizeof(HopperNlpParams):
         raise RatoError(f"rato_hopper_nlp_params is {lib.rato_hopper_nlp_params_bytes()} bytes in {path}, "
                         f"{C.sizeof(HopperNlpParams)} in this binding")
+    if lib.rato_ipm_state_bytes() != C.sizeof(IpmState):
+        raise RatoError(f"rato_ipm_state is {lib.rato_ipm_state_bytes()} bytes in {path}, {C.sizeof(IpmState)} in this binding")
     _LIB = lib
     return lib
 

@@ -250,7 +250,7 @@ class DeviceBackend(_ipm.DeviceBase):
         self.st = None
         self.sum_row = self.torch.as_tensor(nlps[0].sum_row()[None, :].copy(), device=self.dev)
         self.sf = {}
-        self.jac = self.hess = None
+        self.jac = self.hess = self.Kc = None
 
     def _g(self, idx, Zs, g_nl):
         g_nl = g_nl.cpu().numpy()
@@ -318,6 +318,41 @@ class DeviceBackend(_ipm.DeviceBase):
         with self.timed("solve"):
             return list(self.solve_device(idx, B))
 
+    # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group, takes and returns
+    # (K, ld) tensors and waits for nothing.  ``solve_t`` is DeviceBase's.
+    def eval_full_t(self, Z, Y):
+        """Z (K, n) and the multipliers Y (K, ld >= m) -> g (K, m); leaves jac_nl and the packed Hessian of Y . g for the calls below"""
+        with self.torch.cuda.device(self.dev):
+            r = self.m0.linearize_device(Z)
+            self.hess = self.m0.hessian_device(Z, Y[:, :self.n_nl].contiguous())
+        self.jac = r["jac_nl"]
+        self.slot = {i: i for i in range(Z.shape[0])}
+        return _ipm.g_rows(self.n, r["g_nl"], self.sum_row, Z)
+
+    def eval_g_t(self, Z):
+        with self.torch.cuda.device(self.dev):
+            g_nl = self.m0.linearize_device(Z)["g_nl"]
+        return _ipm.g_rows(self.n, g_nl, self.sum_row, Z)
+
+    def matvec_t(self, X):
+        return dense_matvec(self.n, self.jac, self.sum_row, X)
+
+    def tmatvec_t(self, W):
+        return dense_tmatvec(self.n, self.jac, self.sum_row, W)
+
+    def hess_apply_t(self, X):
+        """W x of the constraints' part alone: the objective's sf curv x is added where the result is used (csrc/ipm_driver.hip)"""
+        return tril_symv(self.n, self.hess, X)
+
+    def normal_matrix_t(self, d, diag, out=None):
+        """d (K, ld >= m), diag (K, n) with the objective's curvature already in it -> Kc (K, n, lda)"""
+        return dense_normal_matrix(self.n, self.jac, self.sum_row, d, self.hess, diag, out=out)
+
+    def factor_t(self, d, diag):
+        with self.timed_t("normal"):
+            self.Kc = self.normal_matrix_t(d, diag, out=self.Kc)
+        return self.factor_all(self.Kc)
+
 
 # ---- the solve -------------------------------------------------------------------------------------------------------------
 def lagrange(nlp, info):
@@ -332,7 +367,7 @@ def make_backend(nlps, backend, callbacks=None):
 
 
 def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
-                results_dir='results'):
+                results_dir='results', driver='host'):
     """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  Models of one S form a group that moves
     through the K-problem kernels together (alpha may differ inside it: it enters only the host-side bounds), the groups one
     after the other.  A problem that has ended leaves the launches, a failed factorization is redone for the failed problems
@@ -342,11 +377,15 @@ def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', cal
       callbacks  backend='numpy' only: one dict(linearize, hessian) per model, as ``run_drone_gaussian(callbacks=...)`` takes
       clocks     a dict that receives the seconds spent in callbacks / normal / factor / solve / matvec, the wall clock and
                  host = the rest (the driver's vector algebra and line-search bookkeeping)
+      driver     'host' (``ipm.solve_group``: the iterate and the vector algebra on the host) or 'device'
+                 (``ipm.solve_group_device``, backend='device' only: the iterate stays on the device, csrc/ipm_driver.hip, and
+                 the clocks hold the time to launch; info["driver"] = 'device')
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
     dual_infeasibility, f, mu, sf (the objective scale), the final multipliers y (m = n_nl + 1), zl, zu (nvar + the slacks), the
     slacks s, and lagrange (ncon) in the script's row order."""
     if backend not in ('device', 'numpy'):
         raise ValueError(f"backend must be 'device' or 'numpy', got {backend!r}")
+    _ipm.check_driver(driver, backend)
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
@@ -366,7 +405,7 @@ def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', cal
         return group, make_backend(group, backend, None if callbacks is None else [callbacks[i] for i in members])
 
     spent = None if clocks is None else {}
-    out = _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, spent)
+    out = _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, spent, driver=driver)
     for i, (Z, info) in enumerate(out):
         info["lagrange"] = lagrange(nlps[i], info)
     if clocks is not None:

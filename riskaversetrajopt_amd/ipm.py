@@ -21,6 +21,10 @@ x_bounds(), f, grad_f and a backend through name, clock, eval_full / eval_g / ma
 hess_apply(idx, X) -> [W x].  It, the line search and the O(n + m) vector algebra run on the host per problem, so a problem's
 iterates do not depend on what else is in the batch.  ``Backend`` / ``DeviceBase`` hold what the backends have in common: the
 clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_solve``: csrc/chol.hip), uploads and row selection.
+
+``solve_group_device`` (``driver='device'``) is the same method with the iterate on the device: ``DeviceState``
+holds the state of the K problems in HBM, the vector algebra above is csrc/ipm_driver.hip, and the host keeps the branches
+it needs a read-back for: who is still running, the delta_w ladder, who is still searching.
 """
 import contextlib
 import time
@@ -133,6 +137,32 @@ class DeviceBase(Backend):
         b = self._up(B)[:, None, :].contiguous()
         chol_solve(L, b)
         return b[:, 0].cpu().numpy()
+
+    # ---- for the driver on the device (``solve_group_device``): launches are not waited for
+    sync_clocks = False
+
+    @contextlib.contextmanager
+    def timed_t(self, key):
+        """``timed`` around asynchronous launches: the clock holds the time to launch, or, with ``sync_clocks`` set (the
+        per-iteration split of a measurement), the time until the device has finished the block"""
+        t0 = time.perf_counter()
+        yield
+        if self.sync_clocks:
+            self._sync()
+        self.clock[key] = self.clock.get(key, 0.0) + time.perf_counter() - t0
+
+    def factor_all(self, Kc):
+        """factors Kc (K, n, lda) of the whole group in place and keeps it as L -> info (K,) int32 device tensor"""
+        with self.timed_t("factor"):
+            info = chol_factor(Kc)
+            self.L = Kc
+        return info
+
+    def solve_t(self, B):
+        """L L' x = b in place on B (K, ld >= n), a device tensor, from the factors ``factor_all`` kept"""
+        with self.timed_t("solve"):
+            chol_solve(self.L, B[:, None, :])
+        return B
 
 
 # ---- the method ------------------------------------------------------------------------------------------------------------
@@ -408,15 +438,255 @@ def solve_group(models, Z0s, tol, max_iter, be, verbose):
     return out
 
 
-def solve_groups(groups, setup, Z0s, tol, max_iter, verbose, clocks):
-    """what a ``solve_batch`` ends with: the groups (lists of problem numbers) one after the other, each by ``solve_group`` on
-    the (models, backend) ``setup(members)`` makes -> [(Z, info)] in the problems' order.  ``clocks`` (a dict, or None) receives
-    the sums of the backends' clocks and the wall clock."""
+# ---- the driver on the device (csrc/ipm_driver.hip) -----------------------------------------------------------------
+DRIVERS = ("host", "device")
+
+
+def check_driver(driver, backend):
+    if driver not in DRIVERS:
+        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
+    if driver == 'device' and backend != 'device':
+        raise ValueError(f"driver='device' keeps the iterate on the device: it needs backend='device', got {backend!r}")
+
+
+def g_rows(n, g0, J1, z, out=None):
+    """rato_ipm_g_rows_f64 on device fp64 tensors: g0 (K, m0), the shared block J1 (m1, ld1 >= n), z (K, ldz >= n)
+    -> g (K, m0 + m1) = (g0, J1 z)"""
+    import torch
+    from . import _lib
+    K, m0, m1 = z.shape[0], g0.shape[1], J1.shape[0]
+    g = torch.empty((K, m0 + m1), dtype=torch.float64, device=z.device) if out is None else out
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.load().rato_ipm_g_rows_f64(K, n, _lib.ptr(g0), m0, g0.shape[1], _lib.ptr(J1), m1, J1.shape[1], _lib.ptr(z),
+                                                   z.shape[1], _lib.ptr(g), g.shape[1], _lib.current_stream()), "rato_ipm_g_rows_f64")
+    return g
+
+
+class DeviceState:
+    """The iterates, constants and work vectors of K problems of one shape as rows of device arrays (rato_ipm_state of
+    include/rato_saa.h), built from host ``Problem``s and downloadable back into them.  Vectors of length nv = n + nI or n lie in
+    (K, ldv) arrays, vectors over the m rows in (K, ldm) arrays; ``rs`` / ``dyE`` / ``r2``, which the host keeps packed over the
+    inequality / equality rows, are spread over the rows.  Whatever of a Problem's work vectors exists is uploaded too, so a
+    phase can be run from any host state.  ``fill`` is what the padding and the work vectors that do not exist yet hold.
+    The methods are the kernels: ``residuals``, ``newton``, ``step_setup``, ``trial``, ``accept``; ``record()`` reads the
+    (K, RATO_IPM_REC) scalars back -- the only read-back an iteration needs."""
+    NV = ("v", "zl", "zu", "vL", "vU", "Sigma", "gbar", "dv", "dzl", "dzu", "vt")
+    N = ("curv", "gradf", "rz", "dz", "ez")
+    M = ("y", "gL", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")
+    SCALARS = ("mu", "nu", "dw", "dc", "tol", "E0", "prim", "dual", "a_max", "a_dual", "Dphi", "phi", "alpha", "sf")
+
+    def __init__(self, ps, dev, ldv=None, ldm=None, fill=np.nan):
+        import torch
+        from . import _lib
+        p0 = ps[0]
+        self.K, self.n, self.m, self.nI = len(ps), p0.n, p0.m, int(np.sum(p0.I))
+        self.nv = self.n + self.nI
+        if any(p.n != p0.n or p.m != p0.m or not np.array_equal(p.E, p0.E) for p in ps):
+            raise ValueError("the problems of a DeviceState share n, m and the equality rows")
+        self.ldv, self.ldm = self.nv if ldv is None else int(ldv), self.m if ldm is None else int(ldm)
+        if self.ldv < self.nv or self.ldm < self.m:
+            raise ValueError("ldv >= n + nI and ldm >= m")
+        self.torch, self.dev, self.lib = torch, torch.device(dev), _lib
+        self.E, self.I = p0.E.copy(), p0.I.copy()
+        slack = np.full(self.m, -1, dtype=np.int32)
+        slack[self.I] = np.arange(self.nI, dtype=np.int32)
+        self.row_slack = torch.as_tensor(slack, device=self.dev)
+        host = {k: np.full((self.K, self.ldv), fill) for k in self.NV + self.N}
+        host.update({k: np.full((self.K, self.ldm), fill) for k in self.M})
+        rec = np.zeros((self.K, _lib.IPM_REC))
+        F = {k: i for i, k in enumerate(_lib.IPM_FIELDS)}
+        for k, p in enumerate(ps):
+            for name in self.NV + self.N + self.M:
+                a = self._host_vector(p, name)
+                if a is not None:
+                    host[name][k, :a.size] = a
+            for name in self.SCALARS:
+                if hasattr(p, name):
+                    rec[k, F[name]] = float(getattr(p, name))
+            rec[k, F["iterations"]] = p.iterations
+            rec[k, F["trials"]] = getattr(p, "trials", 0)
+            rec[k, F["status"]] = STATUSES.index(p.status) if p.done else _lib.IPM_RUNNING
+        for name, a in host.items():
+            setattr(self, name, torch.as_tensor(a, device=self.dev))
+        self.diag = torch.full((self.K, self.n), float(fill), dtype=torch.float64, device=self.dev)
+        self.rec = torch.as_tensor(rec, device=self.dev)
+        self.F = F
+        ptr = lambda t: t.data_ptr()
+        self.c_state = _lib.IpmState(self.K, self.n, self.nI, self.m, self.ldv, self.ldm, ptr(self.row_slack),
+                                     *[ptr(getattr(self, k)) for k in ("v", "zl", "zu", "vL", "vU", "curv", "y", "gL", "rec", "Sigma",
+                                                                      "gbar", "dv", "dzl", "dzu", "vt", "gradf", "rz", "dz", "ez",
+                                                                      "diag", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")])
+
+    def _host_vector(self, p, name):
+        """what a Problem holds of the named device vector, in the device's layout, or None"""
+        if name == "curv":
+            return np.asarray(p.model.curv, dtype=np.float64)
+        if name == "gL":
+            return np.asarray(p.model.gL_gU()[0], dtype=np.float64)
+        a = getattr(p, name, None)
+        if a is None:
+            return None
+        a = np.asarray(a, dtype=np.float64)
+        if name in ("rs", "dyE", "r2"):
+            full = np.zeros(self.m)
+            full[self.I if name == "rs" else self.E] = a
+            return full
+        return a
+
+    def download(self, ps):
+        """the device's state into the host Problems: the iterate, the scalars and every work vector"""
+        rec = self.record()
+        get = {k: getattr(self, k).cpu().numpy() for k in self.NV + self.N + self.M if k not in ("curv", "gL", "vL", "vU")}
+        for k, p in enumerate(ps):
+            for name, a in get.items():
+                length = self.nv if name in self.NV else self.n if name in self.N else self.m
+                a = a[k, :length].copy()
+                if name in ("rs", "dyE", "r2"):
+                    a = a[self.I if name == "rs" else self.E]
+                setattr(p, name, a)
+            for name in self.lib.IPM_FIELDS:
+                if name not in ("status", "iterations", "trials", "tol", "sf"):
+                    setattr(p, name, float(rec[k, self.F[name]]))
+            p.iterations, p.trials = int(rec[k, self.F["iterations"]]), int(rec[k, self.F["trials"]])
+            code = int(rec[k, self.F["status"]])
+            p.done, p.status = code != self.lib.IPM_RUNNING, None if code == self.lib.IPM_RUNNING else STATUSES[code]
+            with np.errstate(invalid='ignore'):
+                p.dL, p.dU = p.v - p.vL, p.vU - p.v
+
+    def record(self):
+        return self.rec.cpu().numpy()
+
+    def z(self, of="v"):
+        """the z part of ``v`` (or ``vt``) as a contiguous (K, n) tensor (a copy on the device)"""
+        return getattr(self, of)[:, :self.n].contiguous()
+
+    def _call(self, name, *args):
+        lib = self.lib
+        with self.torch.cuda.device(self.dev):
+            return getattr(lib.load(), name)(self.c_state, *args, lib.current_stream())
+
+    def _ld(self, t):
+        return 0 if t is None else t.shape[1]
+
+    def residuals(self, g, JTy, last=False):
+        self.lib.check(self._call("rato_ipm_residuals_f64", self.lib.ptr(g), self._ld(g), self.lib.ptr(JTy), self._ld(JTy), int(last)),
+                       "rato_ipm_residuals_f64")
+
+    def newton(self, phase, a=None, b=None, info=None, flag=0):
+        lib = self.lib
+        lib.check(self._call("rato_ipm_newton_f64", lib.IPM_PHASES[phase], lib.ptr(a), self._ld(a), lib.ptr(b), self._ld(b),
+                             lib.ptr(info), int(flag)), "rato_ipm_newton_f64")
+
+    def step_setup(self, Hdv):
+        self.lib.check(self._call("rato_ipm_step_setup_f64", self.lib.ptr(Hdv), self._ld(Hdv)), "rato_ipm_step_setup_f64")
+
+    def trial(self):
+        self.lib.check(self._call("rato_ipm_trial_f64"), "rato_ipm_trial_f64")
+
+    def accept(self, gt):
+        self.lib.check(self._call("rato_ipm_accept_f64", self.lib.ptr(gt), self._ld(gt)), "rato_ipm_accept_f64")
+
+
+def newton_steps_device(be, st, run, fact, refine=2):
+    """``newton_steps`` on a DeviceState for the running problems (``run``: their numbers); every launch serves the whole batch
+    and a problem that is not running is skipped inside it.  The delta_w ladder stays the host's decision on the
+    factorization's info; ``fact`` counts a problem's factorizations.  -> the problems that are still running"""
+    with be.timed_t("matvec"):
+        st.newton("rhs", be.tmatvec_t(st.w))
+    todo = list(run)
+    for attempt in range(60):
+        info = be.factor_t(st.d, st.diag)
+        with be.timed_t("factor"):
+            bad = info.cpu().numpy()
+        for k in todo:
+            fact[k] += 1
+        todo = [k for k in todo if bad[k]]
+        if not todo:
+            break
+        st.newton("ladder", info=info, flag=attempt + 1)              # the 60th failure ends the problem: 'line_search'
+    run = [k for k in run if k not in todo]
+    if not run:
+        return run
+    be.solve_t(st.dz)
+    for it in range(refine + 1):
+        with be.timed_t("matvec"):
+            Jdz = be.matvec_t(st.dz)
+            if it == refine:
+                break
+            st.newton("q", Jdz, flag=it == 0)
+            JTq, Wdz = be.tmatvec_t(st.q), be.hess_apply_t(st.dz)
+            st.newton("r", Wdz, JTq)
+        be.solve_t(st.ez)
+        with be.timed_t("matvec"):
+            st.newton("update", be.matvec_t(st.ez))
+    st.newton("finish", Jdz)
+    return run
+
+
+def solve_group_device(models, Z0s, tol, max_iter, be, verbose):
+    """``solve_group`` with the iterate on the device: the Problems are made on the host once (bound relaxation, the push into
+    the interior, sf), uploaded as a ``DeviceState``, and every lockstep iteration is a chain of K-problem launches; the host
+    reads back the scalar record after the residual phase and after each line-search trial, and the info of each
+    factorization.  A problem that has ended stays in the launches and is skipped inside them.  ``be`` serves device tensors:
+    eval_full_t / eval_g_t / matvec_t / tmatvec_t / hess_apply_t / factor_t / solve_t.  -> [(Z, info)] as ``solve_group``'s,
+    with info["driver"] = 'device'."""
+    from . import _lib
+    K = len(models)
+    g0 = be.eval_g(list(range(K)), [np.asarray(Z, dtype=np.float64) for Z in Z0s])
+    ps = [Problem(m, Z, g, tol) for m, Z, g in zip(models, Z0s, g0)]
+    st = DeviceState(ps, be.dev)
+    fact = [0] * K
+    STATUS, SEARCHING = st.F["status"], st.F["searching"]
+    for it in range(max_iter + 1):
+        with be.timed_t("callbacks"):
+            g = be.eval_full_t(st.z(), st.y)
+        with be.timed_t("matvec"):
+            JTy = be.tmatvec_t(st.y)
+        st.residuals(g, JTy, it == max_iter)
+        with be.timed_t("readback"):
+            rec = st.record()
+        run = [k for k in range(K) if rec[k, STATUS] == _lib.IPM_RUNNING]
+        if run:
+            run = newton_steps_device(be, st, run, fact)
+        if run:
+            with be.timed_t("matvec"):
+                st.step_setup(be.hess_apply_t(st.dv))
+            while True:
+                st.trial()
+                with be.timed_t("callbacks"):
+                    gt = be.eval_g_t(st.z("vt"))
+                st.accept(gt)
+                with be.timed_t("readback"):
+                    rec = st.record()
+                if not np.any((rec[:, STATUS] == _lib.IPM_RUNNING) & (rec[:, SEARCHING] == 1.0)):
+                    break
+        if verbose:
+            print("it %4d " % it + " | ".join("mu %.1e E0 %.2e pr %.1e du %.1e a %.1e dw %.0e" % tuple(
+                rec[k, st.F[f]] for f in ("mu", "E0", "prim", "dual", "alpha", "dw")) for k in range(K)))
+        if not np.any(rec[:, STATUS] == _lib.IPM_RUNNING):
+            break
+    st.download(ps)
+    out = []
+    for p, nf in zip(ps, fact):
+        if p.status is None:
+            p.status = "max_iter"
+        info = dict(status=p.status, iterations=p.iterations, factorizations=nf, E0=float(p.E0),
+                    primal_infeasibility=float(p.prim), dual_infeasibility=float(p.dual), f=p.model.f(p.z), mu=p.mu, sf=p.sf,
+                    y=p.y.copy(), zl=p.zl.copy(), zu=p.zu.copy(), s=p.v[p.n:].copy(), backend=be.name, driver='device')
+        out.append((p.z.copy(), info))
+    return out
+
+
+def solve_groups(groups, setup, Z0s, tol, max_iter, verbose, clocks, driver='host'):
+    """what a ``solve_batch`` ends with: the groups (lists of problem numbers) one after the other, each by ``solve_group``
+    (``driver='device'``: ``solve_group_device``) on the (models, backend) ``setup(members)`` makes -> [(Z, info)] in the
+    problems' order.  ``clocks`` (a dict, or None) receives the sums of the backends' clocks and the wall clock."""
     out = [None] * sum(len(members) for members in groups)
     t0 = time.perf_counter()
+    run = solve_group_device if driver == 'device' else solve_group
     for members in groups:
         models, be = setup(members)
-        for i, r in zip(members, solve_group(models, [Z0s[i] for i in members], tol, max_iter, be, verbose)):
+        for i, r in zip(members, run(models, [Z0s[i] for i in members], tol, max_iter, be, verbose)):
             out[i] = r
         if clocks is not None:
             for k, v in be.clock.items():

@@ -604,7 +604,7 @@ def _drone_gaussian_ipm_result(model, Z, info, trajectory, callback_s, total_s):
 
 
 def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir='results', solver='trust-constr', tol=1e-8,
-                       backend=None):
+                       backend=None, driver='host'):
     """The NLP of drone_gaussian.py:400-534 solved with ``scipy.optimize.minimize(method='trust-constr')`` -- the installed
     solver that takes the Hessian of lam . g, which is the script's ``hess_lagrange_dot_g``: the non-linear rows as a
     ``NonlinearConstraint(g, gL, gU, jac, hess)`` (6 equalities, the rest one-sided), the box on u and on the allocations as
@@ -618,9 +618,14 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
     ``solver='ipm'``: the same NLP by ``drone_gaussian_ipm.solve_batch`` (a batch of one; ``backend`` 'device', or
     'numpy', the default when ``callbacks`` are given; ``tol``: its E_0 tolerance) -> the same keys with status one of
     'converged' | 'max_iter' | 'line_search', nit = iterations, nfev = factorizations, constr_violation / optimality = the
-    primal / dual parts of the final E_0, and ``info`` (``solve_batch``'s, with the multipliers)."""
+    primal / dual parts of the final E_0, and ``info`` (``solve_batch``'s, with the multipliers).  ``driver``: 'host' or 'device'
+    (``solver='ipm'`` only: where ``solve_batch`` keeps the iterate)."""
+    if driver not in ('host', 'device'):
+        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
     if solver not in ('trust-constr', 'ipm'):
         raise ValueError(f"solver must be 'trust-constr' or 'ipm', got {solver!r}")
+    if driver == 'device' and solver != 'ipm':
+        raise ValueError("driver='device' is the interior-point method's: it needs solver='ipm'")
     if solver == 'ipm':
         from . import drone_gaussian_ipm
         backend = ('device' if callbacks is None else 'numpy') if backend is None else backend
@@ -628,7 +633,8 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
         clocks = {}
         t0 = time.perf_counter()
         (Z, info), = drone_gaussian_ipm.solve_batch([model], [Z0], tol=tol, max_iter=int(maxiter), backend=backend,
-                                                    callbacks=None if callbacks is None else [callbacks], clocks=clocks)
+                                                    callbacks=None if callbacks is None else [callbacks], clocks=clocks,
+                                                    driver=driver)
         total = time.perf_counter() - t0
         trajectory = (model.device_callbacks() if callbacks is None else callbacks)["trajectory"]
         return _drone_gaussian_ipm_result(model, Z, info, trajectory, clocks["callbacks"], total)
@@ -682,12 +688,14 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
 
 
 def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='results', M_mc=10000, seed=0, maxiter=3000,
-                              saa_iters=60, saa_M=50, device='cuda:0', solver='trust-constr', tol=1e-8, clocks=None):
+                              saa_iters=60, saa_M=50, device='cuda:0', solver='trust-constr', tol=1e-8, clocks=None,
+                              driver='host'):
     """The reference's drone Gaussian baseline (drone_gaussian.py:400-534) and the third block of the drone Monte-Carlo report
     (drone_risk.py:742-761) as one call.  The start of every alpha is the SAA repeat-0 solution
     ``results_dir``/drone_alpha=<alpha>_repeat=0.npy, read where it exists and made by ``drone_saa_experiment`` (one repeat)
     where it does not; each alpha is solved by ``run_drone_gaussian`` (``solver='ipm'``: all alphas in ONE
-    ``drone_gaussian_ipm.solve_batch`` call on the device, whose clocks ``clocks`` receives) and written to drone_gaussian_alpha=<alpha>.npy as
+    ``drone_gaussian_ipm.solve_batch`` call on the device, whose clocks ``clocks`` receives and whose ``driver`` is 'host' or
+    'device') and written to drone_gaussian_alpha=<alpha>.npy as
     (us, xs); then ONE ``eval_batch_device`` call of a fresh ``drone_risk.Model`` of M_mc samples (drawn under
     ``np.random.seed(seed)``) over the solutions.  Per alpha percentage_safe = mean(max constraint <= 1e-6), as the block
     computes it, and monte_carlo_cost.
@@ -697,6 +705,10 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
     from . import drone_params as P
     from .drone_utils import sample_uncertain_parameters
     alphas = [float(a) for a in alphas]
+    if driver not in ('host', 'device'):
+        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
+    if driver == 'device' and solver != 'ipm':
+        raise ValueError("driver='device' is the interior-point method's: it needs solver='ipm'")
     os.makedirs(results_dir, exist_ok=True)
     missing = [a for a in alphas if not os.path.isfile(os.path.join(results_dir, f"drone_alpha={a}_repeat=0.npy"))]
     if missing:
@@ -711,7 +723,7 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
         models = [drone_gaussian.Model(S, alpha=a, device=device) for a in alphas]
         ck = {} if clocks is None else clocks
         sols = drone_gaussian_ipm.solve_batch(models, tol=tol, max_iter=int(maxiter), backend='device', clocks=ck,
-                                              results_dir=results_dir)
+                                              results_dir=results_dir, driver=driver)
         for m, (Z, info) in zip(models, sols):
             results.append(_drone_gaussian_ipm_result(m, Z, info, m.device_callbacks()["trajectory"],
                                                       ck["callbacks"] / len(models), ck["wall"] / len(models)))

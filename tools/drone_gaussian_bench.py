@@ -24,6 +24,14 @@ reported as that.
 
     python tools/drone_gaussian_bench.py --solver both [--results-dir results] [--out profiles/drone_gaussian_solve.json]
 
+With ``--solver ipm --driver {host,device,both}`` it measures the interior-point solve under one or both drivers (DESIGN
+§7.ag: the iterate on the host or on the device) and writes profiles/drone_gaussian_solve_device_driver.json: the same
+batch of four alphas from their SAA starts, both drivers in this process on one board, each after a warm-up solve, the
+median of ``--solves`` solves, the iterations per alpha, and from one more solve with a device-wide wait behind every block
+the split of a lockstep iteration.
+
+    python tools/drone_gaussian_bench.py --solver ipm --driver both [--solves 7]
+
 Prints one JSON line.  There is no CPU fallback: without a GPU the kernel timings fail.
 """
 import argparse
@@ -108,6 +116,49 @@ def solve_bench(args):
         write(out, path)
 
 
+def driver_bench(args):
+    """the S = 20 batch under the host and / or the device driver -> profiles/drone_gaussian_solve_device_driver.json"""
+    import torch
+    from riskaversetrajopt_amd import drone_gaussian as DG
+    from riskaversetrajopt_amd import drone_gaussian_ipm, scp
+    S, alphas = 20, (0.05, 0.1, 0.2, 0.3)
+    path = args.out or os.path.join(ROOT, "profiles", "drone_gaussian_solve_device_driver.json")
+    out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": list(alphas), "tol": args.tol, "maxiter": args.maxiter,
+           "start": "SAA repeat 0 (drone_saa_experiment, M = 50, 60 iterations, seed 0)", "solves": args.solves, "drivers": {}}
+    drivers = ("host", "device") if args.driver == "both" else (args.driver,)
+    # the SAA starts where they are missing (and the code objects of everything around the solve)
+    scp.drone_gaussian_experiment(alphas, S=S, results_dir=args.results_dir, maxiter=3, solver='ipm', tol=args.tol)
+    models = [DG.Model(S, alpha=a) for a in alphas]
+    Z0s = [m.initial_guess(args.results_dir) for m in models]
+    solve = lambda d, ck=None: drone_gaussian_ipm.solve_batch(models, Z0s, tol=args.tol, max_iter=args.maxiter, driver=d, clocks=ck)
+    for d in drivers:
+        solve(d)                                                     # warm-up: code objects, allocator
+        torch.cuda.synchronize()
+        walls = []
+        for _ in range(args.solves):
+            t0 = time.perf_counter()
+            sols = solve(d)
+            walls.append(time.perf_counter() - t0)
+        rounds = max(1, max(info["iterations"] for _, info in sols))
+        drone_gaussian_ipm.DeviceBackend.sync_clocks = True          # one more solve, a device-wide wait behind every block
+        try:
+            clocks = {}
+            solve(d, clocks)
+        finally:
+            drone_gaussian_ipm.DeviceBackend.sync_clocks = False
+        out["drivers"][d] = {"wall_ms": [1e3 * w for w in walls], "median_wall_ms": 1e3 * float(np.median(walls)),
+                             "lockstep_iterations": rounds, "median_ms_per_iteration": 1e3 * float(np.median(walls)) / rounds,
+                             "per_alpha": [{"alpha": a, "status": info["status"], "iterations": info["iterations"],
+                                            "factorizations": info["factorizations"], "E0": info["E0"], "f": info["f"]}
+                                           for a, (_, info) in zip(alphas, sols)],
+                             "split_solve_wall_ms": 1e3 * clocks["wall"],
+                             "split_ms_per_iteration": {k: 1e3 * v / rounds for k, v in clocks.items()}}
+    if len(drivers) == 2:
+        h, dv = out["drivers"]["host"], out["drivers"]["device"]
+        out["host_over_device"] = h["median_wall_ms"] / dv["median_wall_ms"]
+    write(out, path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maxiter", type=int, default=3000)
@@ -117,11 +168,17 @@ def main():
     ap.add_argument("--solver", choices=("trust-constr", "ipm", "both"), default=None)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--results-dir", default="results")
+    ap.add_argument("--driver", choices=("host", "device", "both"), default=None)
+    ap.add_argument("--solves", type=int, default=7)
     args = ap.parse_args()
+    if args.driver is not None and args.solver != "ipm":
+        raise SystemExit("--driver measures the interior-point solve: use it with --solver ipm")
 
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("drone_gaussian_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.driver is not None:
+        return driver_bench(args)
     if args.solver is not None:
         return solve_bench(args)
     import _drone_gaussian as R
