@@ -1598,7 +1598,7 @@ size_t tail_rows_lds(int S, int& c_tab) {
   const size_t lds = (size_t)(2 * (S - 1) + 1) * sizeof(double) + (size_t)S * 2 * RATO_WAVE * sizeof(float);
   c_tab = 0;
   if (lds + 4096 > 160 * 1024) return 0;   // S <= 300 (4 KB: the static lists of the tail compaction)
-  static const int ctab_env = [] { const char* e = getenv("RATO_TAIL_CTAB"); return e ? atoi(e) : 1; }();
+  static const int ctab_env = rato::env_int("RATO_TAIL_CTAB", 1);
   const size_t lds_c = lds + tail_ctab_doubles(S) * sizeof(double);
   c_tab = (ctab_env && lds_c + 4096 <= 80 * 1024) ? 1 : 0;
   return c_tab ? lds_c : lds;
@@ -1607,7 +1607,7 @@ size_t tail_rows_lds(int S, int& c_tab) {
 
 namespace rato {
 bool drone_tail_union_form(int S, int K) {
-  static const int union_env = [] { const char* e = getenv("RATO_TAIL_UNION"); return e ? atoi(e) : 1; }();
+  static const int union_env = rato::env_int("RATO_TAIL_UNION", 1);
   return K > 1 && union_env && tail_union_lds_bytes(S, K < TRU_KMAX ? K : TRU_KMAX) + 4096 <= 160 * 1024;
 }
 }  // namespace rato

@@ -18,8 +18,7 @@
 
 #include "philox.h"
 #include "rato_common.h"
-#include "rato_rows_plan.h"
-#include "rato_select.h"
+#include "rato_sample_launch.h"
 
 namespace {
 
@@ -1096,7 +1095,7 @@ namespace {
 //  per cent faster: M = 1e7 0.614 against 0.650 ms; the driving noise has no unused row to skip)
 constexpr int64_t CAR_EVAL_TILES_MAX_M = 1 << 20, CAR_EVAL_STATS_IN_LAUNCH_MAX_M = 65536;
 int car_eval_tiles_max_m() {
-  static const int64_t v = [] { const char* e = getenv("RATO_EVAL_TILES_MAX_M"); return e ? (int64_t)atoll(e) : CAR_EVAL_TILES_MAX_M; }();
+  static const int64_t v = rato::env_int64("RATO_EVAL_TILES_MAX_M", CAR_EVAL_TILES_MAX_M);
   return (int)v;
 }
 }  // namespace
@@ -1128,38 +1127,26 @@ extern "C" int rato_car_eval(const rato_car_params* p, const float* us, const fl
                              float* g, void* stream) {
   RATO_CLEAR_ERROR();
   if (!params_ok(p) || !us || !dW || !x0_ped || !w_speed || !w_rep || !ego_scratch) return RATO_EINVAL;
-  if (p->stats_workspace && (!Z || !p->stats_out || !(p->stats_alpha > 0.0) || !(p->stats_alpha <= 1.0))) return RATO_EINVAL;
+  const rato::StatsRequest rq = rato::stats_request(p);
+  if (!rq.ok(Z)) return RATO_EINVAL;
   hipStream_t st = rato::as_stream(stream);
   if (!xs && car_eval_tiles_ok(p)) {
     // no trajectories wanted: ONE launch for the rollout (ego tables in every workgroup, tiled rollout); the statistics
     // behind it (in the launch only on request: see rato_drone_eval)
     const int n_tiles = (int)((p->M + RATO_WAVE - 1) / RATO_WAVE);
-    const int grid = (n_tiles + CEV_NW - 1) / CEV_NW;
-    rato_sel::StatsTail tail = {};
-    int grid_launch = grid;
-    size_t lds = car_eval_tiles_lds_bytes(p->S);
-    const bool in_launch = p->stats_workspace && (p->stats_flags & RATO_STATS_IN_LAUNCH) && rato_car_eval_stats_in_launch(p->M);
-    if (in_launch) {
-      const int rc = rato_sel::stats_tail_for<RATO_BLOCK>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr, p->M,
-                                                          grid, tail, grid_launch, lds);
-      if (rc != RATO_OK) return rc;
-    }
-    const int rc = car_eval_tiles_launch(p, 1, us, dW, x0_ped, w_speed, w_rep, Z, p->M, g, tail, grid_launch, lds, n_tiles, st);
+    rato::StatsPlacement sp;
+    int rc = rato::place_stats<RATO_BLOCK>(rq, p->M, (n_tiles + CEV_NW - 1) / CEV_NW, car_eval_tiles_lds_bytes(p->S),
+                                           (rq.flags & RATO_STATS_IN_LAUNCH) && rato_car_eval_stats_in_launch(p->M), sp);
     if (rc != RATO_OK) return rc;
-    if (p->stats_workspace && !in_launch)
-      return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace,
-                             rato_risk_stats_workspace_bytes(p->M), p->stats_out, stream);
-    return RATO_OK;
+    rc = car_eval_tiles_launch(p, 1, us, dW, x0_ped, w_speed, w_rep, Z, p->M, g, sp.tail, sp.grid, sp.lds, n_tiles, st);
+    return rc != RATO_OK ? rc : rato::stats_behind(rq, sp.behind, Z, p->M, stream);
   }
   hipLaunchKernelGGL(car_ego_kernel, dim3(1), dim3(RATO_BLOCK), ego_lds_bytes(p->S), st, *p, us, ego_scratch,
                      (float*)nullptr, (float*)nullptr, 0);
   hipLaunchKernelGGL(car_eval_kernel<false>, dim3(rato::nblocks_for(p->M)), dim3(RATO_BLOCK), 0, st, *p, dW,
                      (uint64_t)0, 0.0f, x0_ped, w_speed, w_rep, ego_scratch, Z, xs, g);
   RATO_LAUNCH_CHECK();
-  if (p->stats_workspace)
-    return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace, rato_risk_stats_workspace_bytes(p->M),
-                           p->stats_out, stream);
-  return RATO_OK;
+  return rato::stats_behind(rq, rq.workspace != nullptr, Z, p->M, stream);
 }
 
 // K control sequences against ONE resident batch in one call: us [K][S][2] -> Z [K][ldz] (+ stats_out [K][RATO_N_STATS]).
@@ -1279,8 +1266,8 @@ int car_linearize_impl(const rato_car_params* p, const float* us, const float* d
   if (rato_car_linearize_plan(p->M, p->S, &spt, &tile) < 0) return RATO_EINVAL;
   if (!dW && spt != -1) return RATO_EINVAL;
   if (noise_tiled && (spt != -1 || !dW)) return RATO_EINVAL;   // the tiled noise layout: row-parallel kernel only
-  if (p->stats_workspace && (spt != -1 || !Z || !p->stats_out || !(p->stats_alpha > 0.0) || !(p->stats_alpha <= 1.0)))
-    return RATO_EINVAL;   // statistics in the same launch: row-parallel kernel, Z requested
+  const rato::StatsRequest rq = rato::stats_request(p);
+  if (!rq.ok(Z) || (rq.workspace && spt != -1)) return RATO_EINVAL;   // statistics: row-parallel kernel, Z requested
   // the ego prologue (trajectory + per-step tangents Epos, Eu) serves the forward/column kernel; the row-parallel
   // kernel builds its ego tables itself, under the latency of its noise loads
   if (spt != -1)
@@ -1289,54 +1276,30 @@ int car_linearize_impl(const rato_car_params* p, const float* us, const float* d
   if (spt == -1) {
     const size_t lds = car_rows_lds_bytes(p->S);
     static rato::DynamicLdsLimit lds_limit;   // per device; cached: capture-safe after the first call
-    {
-      const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
-        hipError_t err = hipSuccess;
-        const void* kernels[4] = {reinterpret_cast<const void*>(car_linearize_rows_kernel<false, false>),
-                                  reinterpret_cast<const void*>(car_linearize_rows_kernel<true, false>),
-                                  reinterpret_cast<const void*>(car_linearize_rows_kernel<false, true>),
-                                  reinterpret_cast<const void*>(car_linearize_rows_kernel<true, true>)};
-        for (int i = 0; i < 4 && err == hipSuccess; ++i)
-          err = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        return err;
-      });
-      if (e != hipSuccess) return RATO_EHIP - (int)e;
-    }
-    // The launch geometry is rato_rows_plan.h's.  A queue (per stream / per captured launch) is taken only for a shape that
-    // wants one; when the pool has none left the shape falls back to the static form.
-    auto plan_with = [&](bool queue_available) {
-      return rato_plan::car_rows(car_rows_geometry(p->S), p->M, p->S, g_car_queue_pool.cus(), car_rows_switches(), queue_available);
-    };
-    rato_rows_plan pl = plan_with(true);
-    unsigned* queue = pl.wants_queue ? g_car_queue_pool.take(st, resolve_car_tile_queues) : nullptr;
-    if (pl.wants_queue && !queue) pl = plan_with(false);
-    // statistics of Z in extra workgroups of this launch (params.stats_*): in the launch only while the whole grid is
-    // resident at once -- no queue; otherwise behind it, below
-    rato_sel::StatsTail tail = {};
-    size_t lds_launch = lds;
-    int grid_launch = pl.workgroups;
-    const bool stats_behind = p->stats_workspace && queue;
-    if (p->stats_workspace && !stats_behind) {
-      const int rc = rato_sel::stats_tail_for<CROWS_NW * RATO_WAVE>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr,
-                                                                   p->M, pl.workgroups, tail, grid_launch, lds_launch);
-      if (rc != RATO_OK) return rc;   // beyond the one-launch forms of the selection: use rato_risk_stats
-    }
+    const hipError_t e = lds_limit.raise(lds, car_linearize_rows_kernel<false, false>, car_linearize_rows_kernel<true, false>,
+                                         car_linearize_rows_kernel<false, true>, car_linearize_rows_kernel<true, true>);
+    if (e != hipSuccess) return RATO_EHIP - (int)e;
+    // plan, queue (or the fallback to the static form) and the place of the statistics: rato_sample_launch.h
+    rato::RowsLaunch rl;
+    const int rc = rato::prepare_rows_launch<CROWS_NW * RATO_WAVE>(
+        [&](bool queue_available) {
+          return rato_plan::car_rows(car_rows_geometry(p->S), p->M, p->S, g_car_queue_pool.cus(), car_rows_switches(), queue_available);
+        },
+        g_car_queue_pool, resolve_car_tile_queues, st, rq, p->M, lds, rl);
+    if (rc != RATO_OK) return rc;   // beyond the one-launch forms of the selection: use rato_risk_stats
     const bool nt_stores = rato_car_rows_streaming_stores(p->M, p->S) != 0;
-#define RATO_CROWS_LAUNCH(Q, PH)                                                                                         \
-  hipLaunchKernelGGL((car_linearize_rows_kernel<Q, PH>), dim3(grid_launch), dim3(CROWS_NW * RATO_WAVE), lds_launch, st, *p, \
-                     seed, noise_scale, us, dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, pl.n_tiles, queue, \
-                     pl.split, pl.n_whole, tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0))
-    if (queue) {
+#define RATO_CROWS_LAUNCH(Q, PH)                                                                                              \
+  hipLaunchKernelGGL((car_linearize_rows_kernel<Q, PH>), dim3(rl.stats.grid), dim3(CROWS_NW * RATO_WAVE), rl.stats.lds, st, *p, \
+                     seed, noise_scale, us, dW, x0_ped, w_speed, w_rep, final_du, final_rhs, G, g_up, Z, rl.plan.n_tiles,     \
+                     rl.queue, rl.plan.split, rl.plan.n_whole, rl.stats.tail, (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0))
+    if (rl.queue) {
       if (dW) RATO_CROWS_LAUNCH(true, false); else RATO_CROWS_LAUNCH(true, true);
     } else {
       if (dW) RATO_CROWS_LAUNCH(false, false); else RATO_CROWS_LAUNCH(false, true);
     }
 #undef RATO_CROWS_LAUNCH
     RATO_LAUNCH_CHECK();
-    if (stats_behind)
-      return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace,
-                             rato_risk_stats_workspace_bytes(p->M), p->stats_out, stream);
-    return RATO_OK;
+    return rato::stats_behind(rq, rl.stats.behind, Z, p->M, stream);
   }
   switch (spt) {
     case 4: return launch_car_linearize<4>(p, dW, x0_ped, w_speed, w_rep, ego_scratch, G, g_up, Z, st);
@@ -1365,33 +1328,10 @@ extern "C" int rato_car_linearize_philox(const rato_car_params* p, const float* 
                             final_du, final_rhs, -1, stream);
 }
 
-namespace {
-__global__ __launch_bounds__(RATO_BLOCK) void car_tile_noise_kernel(const float* __restrict__ dW, long M, int nrows,
-                                                                   float* __restrict__ out) {
-  const long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x;        // over [tile][row][lane]
-  const long n_tiles = (M + CROWS_SAMPLES - 1) / CROWS_SAMPLES;
-  if (i >= n_tiles * nrows * CROWS_SAMPLES) return;
-  // a tile's block is the image the row kernel keeps in LDS: [S][64] (xi_0, xi_1) pairs
-  const long tile = i / ((long)nrows * CROWS_SAMPLES);
-  const int o = (int)(i - tile * (long)nrows * CROWS_SAMPLES);
-  const int t = o / (2 * CROWS_SAMPLES), lane = (o % (2 * CROWS_SAMPLES)) / 2, a = o & 1;
-  const long m = tile * CROWS_SAMPLES + lane;
-  out[i] = (m < M) ? dW[(size_t)(t * 2 + a) * M + m] : 0.0f;
-}
-}  // namespace
-
-extern "C" size_t rato_car_tiled_noise_floats(int64_t M, int32_t S) {
-  return (M > 0 && S > 0) ? (size_t)((M + CROWS_SAMPLES - 1) / CROWS_SAMPLES) * (size_t)(2 * S) * CROWS_SAMPLES : 0;
-}
+extern "C" size_t rato_car_tiled_noise_floats(int64_t M, int32_t S) { return rato::tiled_noise_floats(M, S, 2); }
 
 extern "C" int rato_car_tile_noise(const float* dW, int64_t M, int32_t S, float* dW_tiled, void* stream) {
-  RATO_CLEAR_ERROR();
-  if (!dW || !dW_tiled || M <= 0 || S <= 0) return RATO_EINVAL;
-  const size_t n = rato_car_tiled_noise_floats(M, S);
-  hipLaunchKernelGGL(car_tile_noise_kernel, dim3((unsigned)((n + RATO_BLOCK - 1) / RATO_BLOCK)), dim3(RATO_BLOCK), 0,
-                     rato::as_stream(stream), dW, (long)M, 2 * S, dW_tiled);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return rato::launch_tile_noise(dW, M, M, S, 2, dW_tiled, rato::as_stream(stream));
 }
 
 extern "C" int rato_car_linearize_tiled(const rato_car_params* p, const float* us, const float* dW_tiled,

@@ -16,14 +16,13 @@
 #include "philox.h"
 #include "rato_common.h"
 #include <type_traits>
-#include "rato_rows_plan.h"
-#include "rato_select.h"
+#include "rato_sample_launch.h"
 
 namespace {
 
 constexpr int NOBS = RATO_DRONE_NOBS;
 
-// work queues of the dynamic launch forms (row-parallel linearize, eval): {next tile, workgroups gone}; zero at load,
+// work queues of the dynamic launch form (row-parallel linearize): {next tile, workgroups gone}; zero at load,
 // every launch leaves its queue zeroed again; handed out by rato::TileQueuePool (per stream / per captured launch)
 __device__ unsigned g_tile_queues[RATO_QUEUES_TOTAL * 2];
 
@@ -166,34 +165,12 @@ __device__ __forceinline__ void drone_eval_block(
   if constexpr (WANT_ARG) arg[m] = amax;
 }
 
-// tile_queue != NULL (large batches): 8 workgroups per CU, each taking 256-sample blocks from a global counter until
-// none is left -- the hardware deals a plain grid out to the XCDs up front and every other XCD streams slower (see
-// drone_linearize_rows_kernel), so with one block per workgroup half the chip idles at the end of the launch.
 template <bool PHILOX, int METRIC = RATO_DRONE_METRIC_QUADRATIC, bool WANT_ARG = false>
 __global__ __launch_bounds__(RATO_BLOCK) void drone_eval_kernel(
     rato_drone_params P, const float* __restrict__ us, const float* __restrict__ dW, uint64_t seed,
     float noise_scale, const float* __restrict__ mass, const float* __restrict__ Qsym, float* __restrict__ Z,
-    float* __restrict__ xs, float* __restrict__ g, unsigned* __restrict__ tile_queue, int nblk, int32_t* __restrict__ arg) {
-  if (!tile_queue) {
-    drone_eval_block<PHILOX, METRIC, WANT_ARG>(P, blockIdx.x, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g, arg);
-    return;
-  }
-  __shared__ int next_blk;
-  for (int blk = blockIdx.x; blk < nblk;) {
-    drone_eval_block<PHILOX, METRIC, WANT_ARG>(P, (size_t)blk, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g, arg);
-    __syncthreads();
-    if (threadIdx.x == 0)
-      next_blk = (int)gridDim.x + (int)__hip_atomic_fetch_add(tile_queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    blk = next_blk;
-  }
-  if (threadIdx.x == 0) {
-    const unsigned gone = __hip_atomic_fetch_add(tile_queue + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (gone == gridDim.x - 1) {
-      __hip_atomic_store(tile_queue, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(tile_queue + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+    float* __restrict__ xs, float* __restrict__ g, int32_t* __restrict__ arg) {
+  drone_eval_block<PHILOX, METRIC, WANT_ARG>(P, blockIdx.x, us, dW, seed, noise_scale, mass, Qsym, Z, xs, g, arg);
 }
 
 // Monte-Carlo validation batches (drone_risk.py:643-725: M = 1e4) are LATENCY bound: drone_eval_kernel at C2 runs 40
@@ -1377,8 +1354,6 @@ unsigned* resolve_tile_queues() {
 }
 rato::TileQueuePool g_queue_pool;
 
-unsigned* take_tile_queue(hipStream_t stream) { return g_queue_pool.take(stream, resolve_tile_queues); }
-
 int device_cus() { return g_queue_pool.cus(); }
 
 bool params_ok(const rato_drone_params* p) {
@@ -1398,7 +1373,7 @@ namespace {
 // RATO_EVAL_TILES_MAX_M overrides (A/B).
 constexpr int64_t EVAL_TILES_MAX_M = 0x7fffffff, EVAL_STATS_IN_LAUNCH_MAX_M = 65536;
 int eval_tiles_max_m() {
-  static const int64_t v = [] { const char* e = getenv("RATO_EVAL_TILES_MAX_M"); return e ? (int64_t)atoll(e) : EVAL_TILES_MAX_M; }();
+  static const int64_t v = rato::env_int64("RATO_EVAL_TILES_MAX_M", EVAL_TILES_MAX_M);
   return (int)v;
 }
 }  // namespace
@@ -1442,51 +1417,31 @@ int drone_eval_impl(const rato_drone_params* p, int32_t metric, const float* us,
                     const float* Qsym, float* Z, int32_t* arg, float* xs, float* g, void* stream) {
   RATO_CLEAR_ERROR();
   if (!params_ok(p) || !metric_ok(metric) || !us || !dW || !mass || !Qsym) return RATO_EINVAL;
-  if (p->stats_workspace && (!Z || !p->stats_out || !(p->stats_alpha > 0.0) || !(p->stats_alpha <= 1.0))) return RATO_EINVAL;
+  const rato::StatsRequest rq = rato::stats_request(p);
+  if (!rq.ok(Z)) return RATO_EINVAL;
   hipStream_t st = rato::as_stream(stream);
   if (!xs && p->M <= eval_tiles_max_m()) {
     const int n_tiles = (int)((p->M + RATO_WAVE - 1) / RATO_WAVE);
-    const int grid = (n_tiles + EV_NW - 1) / EV_NW;
-    rato_sel::StatsTail tail = {};
-    int grid_launch = grid;
-    size_t lds = 0;
     // The statistics behind the kernel by default: measured (profiles/r05_*_mc_step.txt) a second node costs 3.4 us of a
     // replayed graph and rs_small (1024 threads) 3.8, while the selection as ONE 256-thread workgroup of this launch (the
     // producers' block size) + the hand-off took 16.  RATO_STATS_IN_LAUNCH in stats_flags asks for the one-launch form.
-    const bool in_launch = p->stats_workspace && (p->stats_flags & RATO_STATS_IN_LAUNCH) && rato_drone_eval_stats_in_launch(p->M);
-    if (in_launch) {
-      const int rc = rato_sel::stats_tail_for<RATO_BLOCK>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr, p->M,
-                                                          grid, tail, grid_launch, lds);
-      if (rc != RATO_OK) return rc;
-    }
-    const int rc = drone_eval_tiles_launch(p, metric, 1, us, dW, mass, Qsym, Z, p->ld, arg, g, tail, grid_launch, lds, n_tiles, st);
+    rato::StatsPlacement sp;
+    int rc = rato::place_stats<RATO_BLOCK>(rq, p->M, (n_tiles + EV_NW - 1) / EV_NW, 0,
+                                           (rq.flags & RATO_STATS_IN_LAUNCH) && rato_drone_eval_stats_in_launch(p->M), sp);
     if (rc != RATO_OK) return rc;
-    if (p->stats_workspace && !in_launch)
-      return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace,
-                             rato_risk_stats_workspace_bytes(p->M), p->stats_out, stream);
-    return RATO_OK;
+    rc = drone_eval_tiles_launch(p, metric, 1, us, dW, mass, Qsym, Z, p->ld, arg, g, sp.tail, sp.grid, sp.lds, n_tiles, st);
+    return rc != RATO_OK ? rc : rato::stats_behind(rq, sp.behind, Z, p->M, stream);
   }
-  const int nblk = rato::nblocks_for(p->M);
-  // The block queue buys the READ-bound eval kernel nothing (same box, alternating, M = 1e6 / 1e7: 0.1264-0.1281 /
-  // 1.159-1.168 ms without, 0.1257-0.1276 / 1.153-1.165 ms with): the XCD asymmetry that the row kernels' queue
-  // removes belongs to the store stream.  Off by default (RATO_EVAL_DYNAMIC=1 for A/B runs).
-  static const int eval_dyn = [] { const char* e = getenv("RATO_EVAL_DYNAMIC"); return e ? atoi(e) : 0; }();
-  unsigned* queue = nullptr;
-  int grid_x = nblk;
-  if (eval_dyn && nblk > 4 * 8 * device_cus()) {   // more than four rounds of 8 workgroups per CU
-    queue = take_tile_queue(st);
-    if (queue) grid_x = 8 * device_cus();
-  }
-  dim3 grid(grid_x), block(RATO_BLOCK);
+  // One block per workgroup, no block queue: it buys the READ-bound eval kernel nothing (same box, alternating, M = 1e6 /
+  // 1e7: 0.1264-0.1281 / 1.159-1.168 ms without, 0.1257-0.1276 / 1.153-1.165 ms with): the XCD asymmetry that the row
+  // kernels' queue removes belongs to the store stream.
+  dim3 grid(rato::nblocks_for(p->M)), block(RATO_BLOCK);
   with_metric(metric, arg != nullptr, [&](auto mt, auto wa) {
     hipLaunchKernelGGL((drone_eval_kernel<false, decltype(mt)::value, decltype(wa)::value>), grid, block, 0, st, *p, us, dW,
-                       (uint64_t)0, 0.0f, mass, Qsym, Z, xs, g, queue, nblk, arg);
+                       (uint64_t)0, 0.0f, mass, Qsym, Z, xs, g, arg);
   });
   RATO_LAUNCH_CHECK();
-  if (p->stats_workspace)
-    return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace, rato_risk_stats_workspace_bytes(p->M),
-                           p->stats_out, stream);
-  return RATO_OK;
+  return rato::stats_behind(rq, rq.workspace != nullptr, Z, p->M, stream);
 }
 
 int drone_eval_batch_impl(const rato_drone_params* p, int32_t metric, int32_t K, const float* us, const float* dW,
@@ -1542,7 +1497,7 @@ extern "C" int rato_drone_eval_philox(const rato_drone_params* p, const float* u
   if (!params_ok(p) || !us || !mass || !Qsym || !(sampler_dt >= 0.0f) || p->S > 65535) return RATO_EINVAL;
   dim3 grid(rato::nblocks_for(p->M)), block(RATO_BLOCK);
   hipLaunchKernelGGL(drone_eval_kernel<true>, grid, block, 0, rato::as_stream(stream), *p, us, (const float*)nullptr,
-                     seed, sqrtf(sampler_dt), mass, Qsym, Z, xs, g, (unsigned*)nullptr, 0, (int32_t*)nullptr);
+                     seed, sqrtf(sampler_dt), mass, Qsym, Z, xs, g, (int32_t*)nullptr);
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }
@@ -1631,18 +1586,10 @@ extern "C" int rato_drone_linearize_generators(const rato_drone_params* p, const
   const size_t lds = (size_t)(RATO_BLOCK / RATO_WAVE) * ((size_t)(p->S + 1) * 6 + (RATO_GEN_LDS_REDUCE ? 24 * 65 : 0)) * sizeof(double);
   if (lds > 160 * 1024) return RATO_EINVAL;   // S <= 592: 32 (6 (S + 1) + 1560) bytes (S = 592: 163776, S = 593: 163968)
   static rato::DynamicLdsLimit gen_lds_limit;
-  {
-    const hipError_t e = gen_lds_limit.ensure(lds, [](size_t bytes) {
-      const void* kernels[3] = {reinterpret_cast<const void*>(drone_linearize_generators_kernel<true, true>),
-                                reinterpret_cast<const void*>(drone_linearize_generators_kernel<false, true>),
-                                reinterpret_cast<const void*>(drone_linearize_generators_kernel<false, false>)};
-      hipError_t err = hipSuccess;
-      for (int i = 0; i < 3 && err == hipSuccess; ++i)
-        err = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      return err;
-    });
-    if (e != hipSuccess) return RATO_EHIP - (int)e;
-  }
+  const hipError_t e = gen_lds_limit.raise(lds, drone_linearize_generators_kernel<true, true>,
+                                           drone_linearize_generators_kernel<false, true>,
+                                           drone_linearize_generators_kernel<false, false>);
+  if (e != hipSuccess) return RATO_EHIP - (int)e;
   if (W)
     hipLaunchKernelGGL((drone_linearize_generators_kernel<true, true>), grid, block, lds, rato::as_stream(stream), *p, us,
                        dW, mass, Qsym, A22, W, g_up, Z, part);
@@ -1663,15 +1610,8 @@ int launch_drone_linearize_generators_batch(const rato_drone_params* p, const Ba
   const size_t lds = (size_t)(RATO_BLOCK / RATO_WAVE) * ((size_t)(p->S + 1) * 6 + (RATO_GEN_LDS_REDUCE ? 24 * 65 : 0)) * sizeof(double);
   if (lds > 160 * 1024) return RATO_EINVAL;
   static rato::DynamicLdsLimit lds_limit;
-  const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(drone_linearize_generators_batch_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
-  if (e != hipSuccess) return RATO_EHIP - (int)e;
-  hipLaunchKernelGGL(drone_linearize_generators_batch_kernel, dim3(rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), lds, st,
-                     *p, tab);
-  RATO_LAUNCH_CHECK();
-  return RATO_OK;
+  return launch_dynamic_lds(drone_linearize_generators_batch_kernel, lds_limit, lds, lds,
+                            dim3(rato::nblocks_for(p->M), (unsigned)n), dim3(RATO_BLOCK), st, *p, tab);
 }
 }  // namespace rato
 
@@ -1697,8 +1637,8 @@ int drone_linearize_impl(const rato_drone_params* p, const float* us, const floa
   if (!dW && cpt != -1) return RATO_EINVAL;
   if (noise_tiled && (cpt != -1 || !dW)) return RATO_EINVAL;   // the tiled noise layout: row-parallel kernel only
   if (W && cpt != -1) return RATO_EINVAL;  // the factored output exists for the row-parallel kernel only
-  if (p->stats_workspace && (cpt != -1 || !Z || !p->stats_out || !(p->stats_alpha > 0.0) || !(p->stats_alpha <= 1.0)))
-    return RATO_EINVAL;   // statistics in the same launch: row-parallel kernel, Z requested
+  const rato::StatsRequest rq = rato::stats_request(p);
+  if (!rq.ok(Z) || (rq.workspace && cpt != -1)) return RATO_EINVAL;   // statistics: row-parallel kernel, Z requested
   if (A22 && !W) return RATO_EINVAL;       // the step-Jacobian table goes with the factored output
   hipStream_t st = rato::as_stream(stream);
   if (cpt == -1) {
@@ -1706,45 +1646,23 @@ int drone_linearize_impl(const rato_drone_params* p, const float* us, const floa
     // Device properties are cached so that a launch inside a hipGraph capture makes no non-stream
     // runtime call (the first, uncaptured call sets them).
     static rato::DynamicLdsLimit lds_limit;   // per device
-    {
-      const hipError_t e = lds_limit.ensure(lds, [](size_t bytes) {
-        hipError_t err = hipSuccess;
-        const void* kernels[4] = {reinterpret_cast<const void*>(drone_linearize_rows_kernel<true, false>),
-                                  reinterpret_cast<const void*>(drone_linearize_rows_kernel<false, false>),
-                                  reinterpret_cast<const void*>(drone_linearize_rows_kernel<true, true>),
-                                  reinterpret_cast<const void*>(drone_linearize_rows_kernel<false, true>)};
-        for (int i = 0; i < 4 && err == hipSuccess; ++i)
-          err = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        return err;
-      });
-      if (e != hipSuccess) return RATO_EHIP - (int)e;
-    }
-    // The launch geometry is rato_rows_plan.h's.  A queue is taken only for a shape that wants one (a captured launch
-    // consumes an entry of the pool for good; launches that overlap on different streams get different queues, and each
-    // launch leaves its queue zeroed); when the pool has none left the shape falls back to the static form.
+    const hipError_t e = lds_limit.raise(lds, drone_linearize_rows_kernel<true, false>, drone_linearize_rows_kernel<false, false>,
+                                         drone_linearize_rows_kernel<true, true>, drone_linearize_rows_kernel<false, true>);
+    if (e != hipSuccess) return RATO_EHIP - (int)e;
+    // plan, queue (or the fallback to the static form) and the place of the statistics: rato_sample_launch.h
     const bool factored = W != nullptr;
-    auto plan_with = [&](bool queue_available) {
-      return rato_plan::drone_rows(rows_geometry(p->S), p->M, p->S, factored, device_cus(), rows_switches(), queue_available);
-    };
-    rato_rows_plan pl = plan_with(true);
-    unsigned* queue = pl.wants_queue ? take_tile_queue(st) : nullptr;
-    if (pl.wants_queue && !queue) pl = plan_with(false);
-    // statistics of Z in extra workgroups of this launch (params.stats_*): in the launch only while the whole grid is
-    // resident at once -- no queue; otherwise behind it, below
-    rato_sel::StatsTail tail = {};
-    size_t lds_launch = lds;
-    int grid_launch = pl.workgroups;
-    const bool stats_behind = p->stats_workspace && queue;
-    if (p->stats_workspace && !stats_behind) {
-      const int rc = rato_sel::stats_tail_for<ROWS_NW * RATO_WAVE>(p->stats_workspace, p->stats_out, p->stats_alpha, p->stats_thr,
-                                                                  p->M, pl.workgroups, tail, grid_launch, lds_launch);
-      if (rc != RATO_OK) return rc;   // beyond the one-launch forms of the selection: use rato_risk_stats
-    }
+    rato::RowsLaunch rl;
+    const int rc = rato::prepare_rows_launch<ROWS_NW * RATO_WAVE>(
+        [&](bool queue_available) {
+          return rato_plan::drone_rows(rows_geometry(p->S), p->M, p->S, factored, device_cus(), rows_switches(), queue_available);
+        },
+        g_queue_pool, resolve_tile_queues, st, rq, p->M, lds, rl);
+    if (rc != RATO_OK) return rc;   // beyond the one-launch forms of the selection: use rato_risk_stats
     const bool nt_stores = rato_drone_rows_streaming_stores(p->M, p->S, factored) != 0;
-#define RATO_ROWS_LAUNCH(F, PH)                                                                                     \
-  hipLaunchKernelGGL((drone_linearize_rows_kernel<F, PH>), dim3(grid_launch), dim3(ROWS_NW * RATO_WAVE), lds_launch, st, \
-                     *p, pl.n_whole, pl.split, /* tile_stride */ 0, pl.n_tiles, queue, seed, noise_scale, us, dW, mass, Qsym, \
-                     G, W, A22, g_up, Z, part, tail,                                                                \
+#define RATO_ROWS_LAUNCH(F, PH)                                                                                            \
+  hipLaunchKernelGGL((drone_linearize_rows_kernel<F, PH>), dim3(rl.stats.grid), dim3(ROWS_NW * RATO_WAVE), rl.stats.lds, st, *p, \
+                     rl.plan.n_whole, rl.plan.split, /* tile_stride */ 0, rl.plan.n_tiles, rl.queue, seed, noise_scale, us, dW, \
+                     mass, Qsym, G, W, A22, g_up, Z, part, rl.stats.tail,                                                  \
                      (noise_tiled ? 1 : 0) | (nt_stores ? 2 : 0) | ((RATO_DIAG == 4 && getenv("RATO_DIAG_WAIT")) ? 4 : 0))
     if (W) {
       if (dW) RATO_ROWS_LAUNCH(true, false); else RATO_ROWS_LAUNCH(true, true);
@@ -1753,10 +1671,7 @@ int drone_linearize_impl(const rato_drone_params* p, const float* us, const floa
     }
 #undef RATO_ROWS_LAUNCH
     RATO_LAUNCH_CHECK();
-    if (stats_behind)
-      return rato_risk_stats(Z, p->M, p->stats_alpha, p->stats_thr, p->stats_workspace,
-                             rato_risk_stats_workspace_bytes(p->M), p->stats_out, stream);
-    return RATO_OK;
+    return rato::stats_behind(rq, rl.stats.behind, Z, p->M, stream);
   }
 #define RATO_CASE(C, L) \
   if (cpt == C && spl == L) return launch_linearize<C, L>(p, us, dW, mass, Qsym, G, g_up, Z, part, st)
@@ -1808,43 +1723,44 @@ extern "C" int rato_drone_linearize_philox(const rato_drone_params* p, const flo
 }
 
 namespace {
-__global__ __launch_bounds__(RATO_BLOCK) void drone_tile_noise_kernel(const float* __restrict__ dW, long M, long ld, int nrows,
-                                                                     float* __restrict__ out) {
+// the layout: rato_common.h (launch_tile_noise); one thread per output word
+static_assert(ROWS_SAMPLES == RATO_WAVE, "a tile of the row kernels is one wave of samples");
+__global__ __launch_bounds__(RATO_BLOCK) void tile_noise_kernel(const float* __restrict__ dW, long M, long ld, int S, int n_axes,
+                                                               float* __restrict__ out) {
   const long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x;        // over [tile][row][lane]
-  const long n_tiles = (M + ROWS_SAMPLES - 1) / ROWS_SAMPLES;
-  if (i >= n_tiles * nrows * ROWS_SAMPLES) return;
-  // a tile's block is the image the row kernel keeps in LDS: [S][64] (xi_x, xi_y) pairs, then [S][64] xi_z
-  const int S = nrows / 3;
-  const long tile = i / ((long)nrows * ROWS_SAMPLES);
-  const int o = (int)(i - tile * (long)nrows * ROWS_SAMPLES);
+  const long block = (long)n_axes * S * RATO_WAVE, n_tiles = (M + RATO_WAVE - 1) / RATO_WAVE;
+  if (i >= n_tiles * block) return;
+  const long tile = i / block;
+  const int o = (int)(i - tile * block), planar = o - S * 2 * RATO_WAVE;
   int t, lane, a;
-  if (o < S * 2 * ROWS_SAMPLES) {
-    t = o / (2 * ROWS_SAMPLES);
-    lane = (o % (2 * ROWS_SAMPLES)) / 2;
+  if (planar < 0) {
+    t = o / (2 * RATO_WAVE);
+    lane = (o % (2 * RATO_WAVE)) / 2;
     a = o & 1;
   } else {
-    const int o2 = o - S * 2 * ROWS_SAMPLES;
-    t = o2 / ROWS_SAMPLES;
-    lane = o2 % ROWS_SAMPLES;
-    a = 2;
+    a = 2 + planar / (S * RATO_WAVE);
+    t = (planar % (S * RATO_WAVE)) / RATO_WAVE;
+    lane = planar % RATO_WAVE;
   }
-  const long m = tile * ROWS_SAMPLES + lane;
-  out[i] = (m < M) ? dW[(size_t)(t * 3 + a) * ld + m] : 0.0f;
+  const long m = tile * RATO_WAVE + lane;
+  out[i] = (m < M) ? dW[(size_t)(t * n_axes + a) * ld + m] : 0.0f;
 }
 }  // namespace
 
-extern "C" size_t rato_drone_tiled_noise_floats(int64_t M, int32_t S) {
-  return (M > 0 && S > 0) ? (size_t)((M + ROWS_SAMPLES - 1) / ROWS_SAMPLES) * (size_t)(3 * S) * ROWS_SAMPLES : 0;
-}
-
-extern "C" int rato_drone_tile_noise(const float* dW, int64_t M, int64_t ld, int32_t S, float* dW_tiled, void* stream) {
+int rato::launch_tile_noise(const float* dW, int64_t M, int64_t ld, int32_t S, int n_axes, float* out, hipStream_t st) {
   RATO_CLEAR_ERROR();
-  if (!dW || !dW_tiled || M <= 0 || ld < M || S <= 0) return RATO_EINVAL;
-  const size_t n = rato_drone_tiled_noise_floats(M, S);
-  hipLaunchKernelGGL(drone_tile_noise_kernel, dim3((unsigned)((n + RATO_BLOCK - 1) / RATO_BLOCK)), dim3(RATO_BLOCK), 0,
-                     rato::as_stream(stream), dW, (long)M, (long)ld, 3 * S, dW_tiled);
+  if (!dW || !out || M <= 0 || ld < M || S <= 0) return RATO_EINVAL;
+  const size_t n = tiled_noise_floats(M, S, n_axes);
+  hipLaunchKernelGGL(tile_noise_kernel, dim3((unsigned)((n + RATO_BLOCK - 1) / RATO_BLOCK)), dim3(RATO_BLOCK), 0, st, dW, (long)M,
+                     (long)ld, S, n_axes, out);
   RATO_LAUNCH_CHECK();
   return RATO_OK;
+}
+
+extern "C" size_t rato_drone_tiled_noise_floats(int64_t M, int32_t S) { return rato::tiled_noise_floats(M, S, 3); }
+
+extern "C" int rato_drone_tile_noise(const float* dW, int64_t M, int64_t ld, int32_t S, float* dW_tiled, void* stream) {
+  return rato::launch_tile_noise(dW, M, ld, S, 3, dW_tiled, rato::as_stream(stream));
 }
 
 extern "C" int rato_drone_linearize_tiled(const rato_drone_params* p, const float* us, const float* dW_tiled,

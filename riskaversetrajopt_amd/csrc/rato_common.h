@@ -174,9 +174,14 @@ static inline int env_int(const char* name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
+static inline int64_t env_int64(const char* name, int64_t dflt) {   // the same for a value that may not fit an int (atoll)
+  const char* e = getenv(name);
+  return e ? (int64_t)atoll(e) : dflt;
+}
+
 static inline int nblocks_for(int32_t M) { return (M + RATO_BLOCK - 1) / RATO_BLOCK; }
 
-// Work queues of the dynamic launch forms (row-parallel linearize kernels, eval): each queue is two device words
+// Work queues of the dynamic launch forms (row-parallel linearize kernels): each queue is two device words
 // {next tile, workgroups gone}, zero at load, and every launch leaves its queue zeroed.  One pool per kernel file and
 // per DEVICE (a __device__ array has its own copy -- and its own address -- on every device of the process):
 //   * an eager launch takes the queue bound to its STREAM: launches on one stream are ordered and may share it,
@@ -305,6 +310,14 @@ int launch_kept_sums_batch(const BatchProb* tab, int n, int nblocks, int nc, int
 // drone.hip (the generators-only linearization without tables or Z, as rato_cut_define_drone runs it)
 int launch_drone_linearize_generators_batch(const rato_drone_params* p, const BatchProb* tab, int n, hipStream_t st);
 
+// The re-tiled noise copy the row-parallel linearize kernels read (rato_*_tile_noise, rato_saa.h): dW [S][n_axes][ld] ->
+// out [ceil(M / 64)] blocks of n_axes * S * 64 floats, each the image its kernel keeps in LDS: [S][64] (xi_0, xi_1) pairs,
+// then [S][64] xi_a for every further axis a (drone n_axes = 3, driving 2); the lanes beyond M hold 0.
+inline size_t tiled_noise_floats(int64_t M, int32_t S, int n_axes) {
+  return (M > 0 && S > 0) ? (size_t)((M + RATO_WAVE - 1) / RATO_WAVE) * (size_t)(n_axes * S) * RATO_WAVE : 0;
+}
+int launch_tile_noise(const float* dW, int64_t M, int64_t ld, int32_t S, int n_axes, float* out, hipStream_t st);   // drone.hip
+
 // Read-back of a few doubles that a kernel writes into PINNED, device-visible host memory: the host pre-sets every word
 // to a NaN payload no arithmetic produces (arm) and then watches the words arrive (wait) instead of asking the runtime
 // for the end of the stream -- hipStreamSynchronize / hipEventSynchronize enqueue a completion packet behind the last
@@ -313,7 +326,7 @@ int launch_drone_linearize_generators_batch(const rato_drone_params* p, const Ba
 // asked after all (a failed launch never writes: the error comes out there).  RATO_CUT_POLL=0: always ask the runtime.
 constexpr uint64_t READBACK_PENDING = 0x7ff8dead5a5abeefull;
 inline bool readback_poll_enabled() {
-  static const int v = [] { const char* e = getenv("RATO_CUT_POLL"); return e ? atoi(e) : 1; }();
+  static const int v = env_int("RATO_CUT_POLL", 1);
   return v != 0;
 }
 inline void readback_arm(double* host, int n) {
@@ -365,6 +378,15 @@ class DynamicLdsLimit {
     if (e == hipSuccess) set_[dev] = bytes;
     return e;
   }
+  template <class... Kernel>   // the launch site's kernels, named: raises each of them to `bytes`
+  hipError_t raise(size_t bytes, Kernel*... kernels) {
+    return ensure(bytes, [=](size_t b) {
+      hipError_t err = hipSuccess;
+      for (const void* k : {reinterpret_cast<const void*>(kernels)...})
+        if (err == hipSuccess) err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+      return err;
+    });
+  }
 
  private:
   static constexpr int kMaxDev = 32;
@@ -378,9 +400,7 @@ class DynamicLdsLimit {
 template <class... Params, class... Args>
 int launch_dynamic_lds(void (*kernel)(Params...), DynamicLdsLimit& limit, size_t raise_to, size_t lds, dim3 grid, dim3 block,
                        hipStream_t st, Args&&... args) {
-  const hipError_t e = limit.ensure(raise_to, [kernel](size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
+  const hipError_t e = limit.raise(raise_to, kernel);
   if (e != hipSuccess) return RATO_EHIP - (int)e;
   hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<Args&&>(args)...);
   RATO_LAUNCH_CHECK();

@@ -645,26 +645,7 @@ __device__ __forceinline__ void stats_tail_run(const StatsTail& t, const float* 
 template <int NT>
 constexpr size_t rs_body_lds_bytes() { return sizeof(unsigned) * B1 + sizeof(double) * 6 * (NT / RATO_WAVE) + sizeof(float) * (NT / RATO_WAVE); }
 
-// The launcher's side: the statistics of Z in extra workgroups of a launch with `grid` producer workgroups of NT threads.
-// Fills `tail`, adds the extra workgroups to grid_launch and raises lds_launch to what the bodies need.  RATO_EINVAL: M is
-// beyond the one-launch forms of the selection (use rato_risk_stats behind the kernel).
-template <int NT>
-int stats_tail_for(const void* workspace, double* out, double alpha, float thr, int64_t M, int grid, StatsTail& tail,
-                   int& grid_launch, size_t& lds_launch) {
-  int Gs = 0;
-  const int extra = stats_tail_workgroups<NT>(M, Gs);
-  if (extra < 0) return RATO_EINVAL;
-  tail.ws = static_cast<Workspace*>(const_cast<void*>(workspace));
-  tail.out = out;
-  tail.alpha = alpha;
-  tail.thr = thr;
-  tail.G = Gs;
-  tail.n_prod = grid;
-  stats_rank(M, alpha, tail.k, tail.var_is_max);
-  grid_launch = grid + extra;
-  if (lds_launch < rs_body_lds_bytes<NT>()) lds_launch = rs_body_lds_bytes<NT>();
-  return RATO_OK;
-}
+// (the launcher's side -- fill a StatsTail, add the extra workgroups, raise the LDS: rato::place_stats, rato_sample_launch.h)
 
 }  // namespace rato_sel
 #endif

@@ -1,8 +1,9 @@
 """Launch shapes of the driving row kernel (car_linearize_rows_kernel) and a dense checker of its outputs against the
 fp64 oracle: plain Python / NumPy, no GPU.
 
-``car_rows_shape`` restates the launcher's rule (csrc/driving.hip, car_linearize_impl: LDS per workgroup, workgroups per
-CU, the tile queue, small-batch split, queue tail parts), so that a GPU test can name the form it means to run and
+``car_rows_shape`` restates the launcher's rule (csrc/rato_rows_plan.h as csrc/driving.hip, car_linearize_impl, calls it
+through prepare_rows_launch of csrc/rato_sample_launch.h, which holds the queue fallback: LDS per workgroup, workgroups
+per CU, the tile queue, small-batch split, queue tail parts), so that a GPU test can name the form it means to run and
 ``rato_car_stats_in_launch`` on the device can tell when the table has moved.  ``units`` restates the kernel's
 unit -> (tile, part) mapping.
 

@@ -1,7 +1,8 @@
 """Launch shapes of the drone row kernel (drone_linearize_rows_kernel) and a dense checker of its outputs against the
 fp64 oracle: plain Python / NumPy, no GPU (the digest runs on whatever device its tensor is on).
 
-``drone_rows_shape`` restates the launcher's rule (csrc/drone.hip, drone_linearize_impl: LDS per workgroup, workgroups
+``drone_rows_shape`` restates the launcher's rule (csrc/rato_rows_plan.h as csrc/drone.hip, drone_linearize_impl, calls it
+through prepare_rows_launch of csrc/rato_sample_launch.h, which holds the queue fallback: LDS per workgroup, workgroups
 per CU, small-batch split, the tile queue, its grid and its tail parts), so that a GPU test can name the form it means
 to run and ``rato_drone_stats_in_launch`` on the device can tell when the table has moved.  ``units`` restates the
 kernel's unit -> (tile, part) mapping and which part writes Z and each axis' rows of ``part``.
