@@ -1285,6 +1285,32 @@ int rato_csc_tmatvec_f64(int32_t K, int64_t ncon, int64_t n, const double* vals0
                          int64_t ld1, int64_t n1, const int64_t* col_ptr, const int32_t* col_idx, const int32_t* col_row,
                          const double* w /* [K][ldw] */, int64_t ldw, double* out /* [K][ldo] */, int64_t ldo, void* stream);
 
+/* ---- What the interior-point driver on the device needs of the hopper between those launches (csrc/hopper_g.hip)
+ * -- a further addition within version 12.  fp64, K problems per launch, device pointers, stream ordered, no allocation, no
+ * workspace, no atomics: two calls are bitwise equal and problem k of a batch is bitwise its K = 1 call.
+ *
+ * rato_hopper_g_f64: g [K][ldg >= ncon] in the script's row order (:491-514; hopper.Model.nlp_layout()["off"]): the defect, x_0 -
+ *   state_initial, (x_S - state_final)[4:6], the no-slip and contact rows on the contact states, minus the end-effector height on
+ *   the flight steps, the risk group, the controls, the slack and the three leg rows -- from Z [K][ldz >= nvar = 8(S+1) + 4S + M +
+ *   2], defect [K][S][8] and rows [K][S+1][2] (rato_hopper_nlp_linearize's) and the slip values h of rato_hopper_slip_f64, problem
+ *   k at h + k M C, sample i and contact c at i h_stride_sample + c h_stride_contact: (C, 1) reads the rows' order i C + c, (1, M)
+ *   reads [C][M] as the slip kernel leaves it.  saa != 0: the risk group is (malpha[k] t + sum ys, -ys_i, ((h_ic - t) - ys_i) -
+ *   slack, 0), malpha [K] = M alpha per problem; saa == 0: h_ic - slack.  C = 0 (no contact step) is valid: h is not read.
+ *   p supplies S, the phase times and the two states.  One lane per row; every row but the sum row is bitwise the host's
+ *   (hopper_ipm.assemble_g) from the same pieces.  The sum row has one owner, a workgroup that adds ys lane-strided ascending,
+ *   the wave's fixed tree, then the four waves in order: the order depends on M alone.  Padding is never written.
+ * rato_hopper_block_symv_f64: out[k] = W x[k] (x [K][ldx >= n], out [K][ldo >= n]) with W given as the step blocks [K][S+1][78] of
+ *   rato_hopper_nlp_hessian: one lane per (problem, block, local row) sums its 12 products with the column ascending (8 in
+ *   block S, whose u part does not exist); the n - 8(S+1) - 4S entries behind the blocks' variables (ys, slack, t_risk) are
+ *   written +0.
+ * RATO_EINVAL without a launch on a NULL or undersized argument, K outside [1, 65535], S < 1, M < 1, phase times outside
+ * 0 <= time_jump <= time_land <= S, h strides below 1 or reaching past M C values, n < 8(S+1) + 4S. */
+int rato_hopper_g_f64(const rato_hopper_nlp_params* p, int32_t K, int64_t M, int32_t saa, const double* Z /* [K][ldz] */,
+                      int64_t ldz, const double* defect, const double* rows, const double* h, int64_t h_stride_sample,
+                      int64_t h_stride_contact, const double* malpha /* [K], saa only */, double* g, int64_t ldg, void* stream);
+int rato_hopper_block_symv_f64(int32_t K, int32_t S, int64_t n, const double* blocks, const double* x, int64_t ldx, double* out,
+                               int64_t ldo, void* stream);
+
 /* ---- Batched Cholesky, fp64 (csrc/chol.hip, on the workgroup functions of csrc/rato_chol.h; riskaversetrajopt_amd/ipm.py).
  * In-place blocked Cholesky A = L L' of K row-major matrices A[k] (n x n, leading dimension lda >= n), lower triangle: only
  * entries with b <= a < n are read or written, so the strict upper triangle and the padding may hold anything (NaN included).
@@ -1424,7 +1450,10 @@ int rato_hopper_arrow_eapply_f64(int32_t K, int64_t M, const double* e, const do
  * The state.  v = (z, s), nv = n + nI; rows of [K][ldv] arrays hold vectors of length nv or n, rows of [K][ldm] arrays
  * vectors over the m constraint rows; padding is never read or written.  vL / vU: -inf / +inf where a bound is absent.
  * row_slack [m] (shared): the slack number in [0, nI) of an inequality row, -1 for an equality row (whose value is gL).
- * The objective is f = 1/2 sf sum curv z^2.  rec [K][RATO_IPM_REC] is the record of scalars the host reads back; status is
+ * The objective is f = sf (1/2 sum curv_j z_j^2 + sum lin_j z_j); lin is mandatory like every pointer of the struct (a model
+ * without a linear part passes zeros) and enters gradf = sf (curv z + lin) -- hence rz, dual, E0 and Dbar -- and the objective
+ * values of _step_setup and _accept; diag, phase R and quad know curv alone.  The struct grew by lin within version 12:
+ * RATO_ABI_VERSION stays 12 and rato_ipm_state_bytes() against the binding's sizeof is the guard.  rec [K][RATO_IPM_REC] is the record of scalars the host reads back; status is
  * RATO_IPM_RUNNING or the index into ('converged', 'max_iter', 'line_search').  A problem whose status is not
  * RATO_IPM_RUNNING is left untouched by every call, and so is one that is not searching by _trial and _accept. */
 #define RATO_IPM_REC 32
@@ -1440,7 +1469,7 @@ typedef struct rato_ipm_state {
   int64_t ldv, ldm;
   const int32_t* row_slack;          /* [m] */
   double *v, *zl, *zu;               /* [K][ldv] the iterate and the bound multipliers */
-  const double *vL, *vU, *curv;      /* [K][ldv] bounds (nv), objective curvature (n) */
+  const double *vL, *vU, *curv, *lin; /* [K][ldv] bounds (nv), the objective's curvature and linear term (n) */
   double* y;                         /* [K][ldm] */
   const double* gL;                  /* [K][ldm] read on equality rows */
   double* rec;                       /* [K][RATO_IPM_REC] */

@@ -102,7 +102,7 @@ class ScpBatchIter(C.Structure):
 class IpmState(C.Structure):
     """rato_ipm_state (include/rato_saa.h)"""
     _fields_ = [(k, C.c_int32) for k in ("K", "n", "nI", "m")] + [("ldv", C.c_int64), ("ldm", C.c_int64)] + \
-               [(k, C.c_void_p) for k in ("row_slack", "v", "zl", "zu", "vL", "vU", "curv", "y", "gL", "rec",
+               [(k, C.c_void_p) for k in ("row_slack", "v", "zl", "zu", "vL", "vU", "curv", "lin", "y", "gL", "rec",
                                           "Sigma", "gbar", "dv", "dzl", "dzu", "vt", "gradf", "rz", "dz", "ez", "diag",
                                           "c", "d", "w", "rs", "dyE", "r2", "q", "dy")]
 
@@ -298,6 +298,10 @@ SIGNATURES = {
     "rato_csc_tmatvec_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64,
                                        C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, C.c_int64, c_float_p, C.c_int64,
                                        c_stream]),
+    "rato_hopper_g_f64": (C.c_int, [C.POINTER(HopperNlpParams), C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int64, c_float_p,
+                                    c_float_p, c_float_p, C.c_int64, C.c_int64, c_float_p, c_float_p, C.c_int64, c_stream]),
+    "rato_hopper_block_symv_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_float_p, c_float_p, C.c_int64, c_float_p,
+                                             C.c_int64, c_stream]),
     "rato_chol_panel_width": (C.c_int, []),
     "rato_chol_factor_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, c_stream]),
     "rato_chol_solve_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int64,

@@ -1,6 +1,8 @@
 // The interior-point driver's O(n + m) algebra on a state that stays on the device (riskaversetrajopt_amd/ipm.py:
-// DeviceState, solve_group_device), fp64, K problems per launch.  Nothing here knows a model: the objective is
-// 1/2 sf sum curv z^2, the constraints arrive as values (g, J'y, J dz, W dz, ...) that other kernels leave on the device.
+// DeviceState, solve_group_device), fp64, K problems per launch.  Nothing here knows a model: the objective
+// is sf (1/2 sum curv z^2 + sum lin z), the constraints arrive as values (g, J'y, J dz, W dz, ...) that other kernels leave on
+// the device.  lin enters the gradient (gradf, hence rz, dual, E0 and Dbar) and the two objective values (the record of the step
+// setup, phi_t); the second-order places (diag, phase R, quad) know curv alone.
 //
 // Each kernel restates one piece of the host driver (ipm.Problem, ipm.newton_steps, ipm.solve_group) and nothing else:
 //   ipm_residuals_kernel   Problem.residuals, error, the status and mu logic, prepare_step
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_residuals_kernel(rato_ipm_state 
     mx[0] = nanmax(mx[0], fabs(cr));
   }
   for (int j = t; j < n; j += ID_BLOCK) {
-    const double gf = sf * (st.curv[w.ov + j] * st.v[w.ov + j]);
+    const double gf = sf * (st.curv[w.ov + j] * st.v[w.ov + j] + st.lin[w.ov + j]);
     st.gradf[w.ov + j] = gf;
     mx[2] = nanmax(mx[2], fabs(gf + jk[j] - st.zl[w.ov + j] + st.zu[w.ov + j]));
   }
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_newton_kernel(rato_ipm_state st,
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_setup_kernel(rato_ipm_state st, const double* __restrict__ Hdv, int64_t ldh) {
-  __shared__ double sh[9][ID_WAVES];
+  __shared__ double sh[10][ID_WAVES];
   const View w = view(st);
   if (w.rec[RATO_IPM_STATUS] != (double)RATO_IPM_RUNNING) return;
   const int t = threadIdx.x, n = w.n;
@@ -288,8 +290,9 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_setup_kernel(rato_ipm_state st, 
   double nu = w.rec[RATO_IPM_NU];
   const double tau = pymax(0.99, 1.0 - mu);
   const double* hk = Hdv + (int64_t)blockIdx.x * ldh;
-  // sums: gradf . dv_z, gbar . dv, dv_z . W dv_z, sum Sigma dv^2, dv_z . dv_z, the two barrier sums, sum curv z^2, sum |c|
-  double s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  // sums: gradf . dv_z, gbar . dv, dv_z . W dv_z, sum Sigma dv^2, dv_z . dv_z, the two barrier sums, sum curv z^2, sum |c|,
+  // sum lin z
+  double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double mn[2] = {INFINITY, INFINITY};                           // the primal and the dual step to the boundary
   for (int i = t; i < w.nv; i += ID_BLOCK) {
     const double vi = st.v[w.ov + i], dvi = st.dv[w.ov + i], zl = st.zl[w.ov + i], zu = st.zu[w.ov + i];
@@ -312,6 +315,7 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_setup_kernel(rato_ipm_state st, 
       s[2] += dvi * (hk[i] + (sf * cv) * dvi);
       s[4] += dvi * dvi;
       s[7] += cv * vi * vi;
+      s[9] += st.lin[w.ov + i] * vi;
     }
   }
   for (int r = t; r < w.m; r += ID_BLOCK) s[8] += fabs(st.c[w.om + r]);
@@ -324,7 +328,7 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_setup_kernel(rato_ipm_state st, 
     if (nu < nu_trial) nu = __dadd_rn(nu_trial, 1.0);
   }
   const double Dphi = pymin(__dadd_rn(Dbar, -__dmul_rn(nu, c1)), 0.0);
-  const double objective = 0.5 * s[7], barrier = -mu * (s[5] + s[6]);
+  const double objective = 0.5 * s[7] + s[9], barrier = -mu * (s[5] + s[6]);
   const double phi = __dadd_rn(__dadd_rn(__dmul_rn(sf, objective), barrier), __dmul_rn(nu, c1));
   if (t == 0) {
     w.rec[RATO_IPM_A_MAX] = a_max;
@@ -356,7 +360,7 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_trial_kernel(rato_ipm_state st) 
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_accept_kernel(rato_ipm_state st, const double* __restrict__ gt, int64_t ldg) {
-  __shared__ double sh[4][ID_WAVES];
+  __shared__ double sh[5][ID_WAVES];
   const View w = view(st);
   if (!searching(w.rec)) return;
   const int t = threadIdx.x, n = w.n;
@@ -364,20 +368,23 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_accept_kernel(rato_ipm_state st,
   const double Dphi = w.rec[RATO_IPM_DPHI], alpha = w.rec[RATO_IPM_ALPHA], a_dual = w.rec[RATO_IPM_A_DUAL];
   const int trials = (int)w.rec[RATO_IPM_TRIALS] + 1, iterations = (int)w.rec[RATO_IPM_ITERATIONS];
   const double* gk = gt + (int64_t)blockIdx.x * ldg;
-  double s[4] = {0.0, 0.0, 0.0, 0.0};                            // the two barrier sums, sum curv z^2, sum |c|
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};                       // the two barrier sums, sum curv z^2, sum |c|, sum lin z
   for (int i = t; i < w.nv; i += ID_BLOCK) {
     const double vi = st.vt[w.ov + i];
     const Dist b = dist(vi, st.vL[w.ov + i], st.vU[w.ov + i]);
     if (b.hasL) s[0] += log(b.dL);
     if (b.hasU) s[1] += log(b.dU);
-    if (i < n) s[2] += st.curv[w.ov + i] * vi * vi;
+    if (i < n) {
+      s[2] += st.curv[w.ov + i] * vi * vi;
+      s[4] += st.lin[w.ov + i] * vi;
+    }
   }
   for (int r = t; r < w.m; r += ID_BLOCK) {
     const int sl = st.row_slack[r];
     s[3] += fabs(sl < 0 ? gk[r] - st.gL[w.om + r] : gk[r] - st.vt[w.ov + n + sl]);
   }
   block_sum(s, sh);
-  const double phi_t = __dadd_rn(__dadd_rn(__dmul_rn(sf, 0.5 * s[2]), -mu * (s[0] + s[1])), __dmul_rn(nu, s[3]));
+  const double phi_t = __dadd_rn(__dadd_rn(__dmul_rn(sf, 0.5 * s[2] + s[4]), -mu * (s[0] + s[1])), __dmul_rn(nu, s[3]));
   const double bound = __dadd_rn(__dadd_rn(phi, __dmul_rn(__dmul_rn(1e-8, alpha), Dphi)),
                                  __dmul_rn(10.0 * 2.220446049250313e-16, fabs(phi)));
   const bool accept = isfinite(phi_t) && phi_t <= bound;
@@ -430,7 +437,7 @@ bool state_ok(const rato_ipm_state* st) {
   if (!st || st->K < 1 || st->K > 65535 || st->n < 1 || st->nI < 0 || st->m < 1 || st->nI > st->m ||
       st->ldv < (int64_t)st->n + st->nI || st->ldm < st->m)
     return false;
-  const void* p[] = {st->row_slack, st->v, st->zl, st->zu, st->vL, st->vU, st->curv, st->y, st->gL, st->rec, st->Sigma, st->gbar,
+  const void* p[] = {st->row_slack, st->v, st->zl, st->zu, st->vL, st->vU, st->curv, st->lin, st->y, st->gL, st->rec, st->Sigma, st->gbar,
                      st->dv, st->dzl, st->dzu, st->vt, st->gradf, st->rz, st->dz, st->ez, st->diag, st->c, st->d, st->w, st->rs,
                      st->dyE, st->r2, st->q, st->dy};
   for (const void* q : p)

@@ -14,7 +14,9 @@ hands to IPOPT (:486-640) on the MI355X.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
   * ``Model.initial_guess()`` and ``Model.solve()``: the script's start and its solve (:136-164, :642-669) with the batched
     interior-point method of ``ipm`` on the backends of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip, csrc/chol.hip) in
-    IPOPT's place."""
+    IPOPT's place.  ``solve(driver='device')`` keeps the iterate on the device: the objective as ``curv`` / ``lin``,
+    g assembled by rato_hopper_g_f64 and W x by rato_hopper_block_symv_f64 (csrc/hopper_g.hip), the multipliers folded where
+    they lie (``fold_multipliers_device``)."""
 import ctypes as C
 
 import numpy as np
@@ -136,6 +138,52 @@ def scatter_f64(src, index_map, dst, scale=None):
         _lib.check(_lib.load().rato_scatter_f64(K, n, _lib.ptr(src), n, _lib.ptr(index_map), _lib.ptr(scale), _lib.ptr(dst),
                                                 dst.shape[1], dst.shape[1], _lib.current_stream()), "rato_scatter_f64")
     return dst
+
+
+def g_device(params, M, saa, Z, defect, rows, h, h_strides, malpha, out=None):
+    """rato_hopper_g_f64 (csrc/hopper_g.hip): g (K, ncon) in the script's row order from device fp64 tensors -- Z (K, ldz >= nvar),
+    defect (K, S, 8) and rows (K, S+1, 2) of ``nlp_linearize_device``, the slip values ``h`` of K x M x C entries (None when no
+    step is in contact) read with ``h_strides`` = (sample, contact): (C, 1) for slip_rows, (1, M) for slip_h -- and malpha (K,)
+    = M alpha per problem (saa only).  ``out``: a (K, ldg >= ncon) tensor to write into; its padding is left as it is."""
+    S = params.S
+    Cn = params.time_jump + (S - params.time_land)
+    n_state = params.time_jump + (S + 1 - params.time_land)
+    ncon = n_x * S + n_x + 2 + 2 * n_state + (params.time_land - params.time_jump) + \
+        ((1 + M + M * Cn + 1) if saa else M * Cn) + n_u * S + 1 + 3 * S
+    K, ldz = _rows_of(Z, n_x * (S + 1) + n_u * S + M + 2)
+    for t, shape, name in ((defect, (K, S, n_x), "defect"), (rows, (K, S + 1, 2), "rows")):
+        if tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != Z.device:
+            raise ValueError(f"{name} must be a contiguous device float64 tensor of shape {shape}")
+    if Cn > 0 and (h is None or h.numel() != K * M * Cn or h.dtype != torch.float64 or not h.is_contiguous() or h.device != Z.device):
+        raise ValueError(f"h must be a contiguous device float64 tensor of K M C = {K * M * Cn} entries")
+    if saa and (malpha is None or tuple(malpha.shape) != (K,) or malpha.dtype != torch.float64 or malpha.device != Z.device):
+        raise ValueError(f"malpha must be a device float64 tensor ({K},)")
+    g = torch.empty((K, ncon), dtype=torch.float64, device=Z.device) if out is None else out
+    if g.dim() != 2 or g.shape[0] != K or g.shape[1] < ncon or g.dtype != torch.float64 or not g.is_contiguous() or g.device != Z.device:
+        raise ValueError(f"out must be a contiguous device float64 tensor ({K}, >= {ncon})")
+    with torch.cuda.device(Z.device):
+        _lib.check(_lib.load().rato_hopper_g_f64(
+            C.byref(params), K, M, int(bool(saa)), _lib.ptr(Z), ldz, _lib.ptr(defect), _lib.ptr(rows), _lib.ptr(h if Cn > 0 else None),
+            int(h_strides[0]), int(h_strides[1]), _lib.ptr(malpha if saa else None), _lib.ptr(g), g.shape[1],
+            _lib.current_stream()), "rato_hopper_g_f64")
+    return g
+
+
+def block_symv(S, blocks, x, n=None, out=None):
+    """rato_hopper_block_symv_f64 (csrc/hopper_g.hip): W x for W given as its step blocks (K, S+1, 78); x (K, ldx >= n) device
+    fp64 -> (K, n) (``out``: a (K, ldo >= n) tensor to write into); the entries behind the blocks' variables are +0"""
+    K = blocks.shape[0]
+    n = x.shape[1] if n is None else int(n)
+    if tuple(blocks.shape) != (K, S + 1, n_pairs) or blocks.dtype != torch.float64 or not blocks.is_contiguous() or \
+            x.dim() != 2 or x.shape[0] != K or x.shape[1] < n or x.dtype != torch.float64 or not x.is_contiguous() or x.device != blocks.device:
+        raise ValueError(f"blocks must be a contiguous device float64 tensor (K, {S + 1}, {n_pairs}) and x (K, >= {n})")
+    o = torch.empty((K, n), dtype=torch.float64, device=x.device) if out is None else out
+    if o.dim() != 2 or o.shape[0] != K or o.shape[1] < n or o.dtype != torch.float64 or not o.is_contiguous() or o.device != x.device:
+        raise ValueError(f"out must be a contiguous device float64 tensor ({K}, >= {n})")
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rato_hopper_block_symv_f64(K, S, n, _lib.ptr(blocks), _lib.ptr(x), x.shape[1], _lib.ptr(o), o.shape[1],
+                                                          _lib.current_stream()), "rato_hopper_block_symv_f64")
+    return o
 
 
 def block_variables(S, t):
@@ -751,6 +799,29 @@ class Model:
         R = 1.0
         return float(np.sum(R * (us[:, 0] * us[:, 0]) + R * (us[:, 1] * us[:, 1])) - 10000 * xs[-1, 0] + 10000000 * Z[-2])
 
+    def _objective_terms(self):
+        """(curv, lin) with f = 1/2 sum curv z^2 + lin . z: host-only, read-only, built once"""
+        cl = getattr(self, "_curv_lin", None)
+        if cl is None:
+            curv, lin = np.zeros(self.num_vars), np.zeros(self.num_vars)
+            ui = n_x * (self.S + 1) + n_u * np.arange(self.S)
+            curv[ui] = curv[ui + 1] = 2.0                            # R (u0^2 + u1^2), R = 1
+            lin[n_x * self.S], lin[-2] = -10000.0, 10000000.0        # -10000 x_S[0] + 1e7 slack
+            curv.flags.writeable = lin.flags.writeable = False
+            cl = self._curv_lin = (curv, lin)
+        return cl
+
+    @property
+    def curv(self):
+        """the objective's diagonal curvature (num_vars,): 2 on u0 and u1 of every step.  grad_f(Z) == curv * Z + lin bitwise
+        (the supports are disjoint); what ``ipm.DeviceState`` uploads for the driver on the device"""
+        return self._objective_terms()[0]
+
+    @property
+    def lin(self):
+        """the objective's linear term (num_vars,): -10000 at x_S[0], 1e7 at the slack"""
+        return self._objective_terms()[1]
+
     def grad_f(self, Z):
         Z = np.asarray(Z, dtype=np.float64)
         g = np.zeros(self.num_vars)
@@ -798,13 +869,17 @@ class Model:
             us[sl, 1] = us[sl, 3] = nominal_force
         return Zp
 
-    def solve(self, Z0=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, newton='dense'):
+    def solve(self, Z0=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, newton='dense',
+              driver='host'):
         """The script's solve (:642-669, its options tol = 1e-3, max_iter = 3000) with the batched interior-point method of
         ``hopper_ipm`` in place of IPOPT -> (Z, info); info["status"] is 'converged' only if the final error shows it.
-        newton='arrow' eliminates the M sample variables from the Newton step (the path that scales with M)."""
+        newton='arrow' eliminates the M sample variables from the Newton step (the path that scales with M).
+        driver='device' (backend='device', newton='dense' only): the iterate stays on the device (``ipm.solve_group_device``,
+        csrc/ipm_driver.hip); info["driver"] = 'device'."""
         from . import hopper_ipm
         return hopper_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter, backend=backend,
-                                      callbacks=None if callbacks is None else [callbacks], verbose=verbose, newton=newton)[0]
+                                      callbacks=None if callbacks is None else [callbacks], verbose=verbose, newton=newton,
+                                      driver=driver)[0]
 
     def _nlp_state(self, K):
         """device-side constants of the emission: the maps (uploaded once) and, per K, the destinations zeroed / pre-filled once"""
@@ -833,7 +908,43 @@ class Model:
         lam_rows = np.where(idx >= 0, lams[:, np.maximum(idx, 0)], 0.0) * sign
         return np.ascontiguousarray(lams[:, :n_x * self.S]).reshape(-1, self.S, n_x), np.ascontiguousarray(lam_rows)
 
-    def nlp_device(self, Zs, lams=None, add=None):
+    def fold_map(self):
+        """the inverse of ``nlp_layout()``'s lam_rows_index, host-only, built once: (index (ncon,) int64, scale (ncon,)) with
+        lam_rows.reshape(-1)[index[r]] = scale[r] lams[r] for the rows r with index[r] >= 0 (the no-slip, contact and
+        leg-over-ground rows; scale is lam_rows_sign) and index[r] = -1 for every other row: what rato_scatter_f64 takes to
+        fold the multipliers where they lie"""
+        fm = getattr(self, "_fold_map", None)
+        if fm is None:
+            lay = self.nlp_layout()
+            idx, sign = lay["lam_rows_index"].reshape(-1), lay["lam_rows_sign"].reshape(-1)
+            used = np.flatnonzero(idx >= 0)
+            assert np.unique(idx[used]).size == used.size, "lam_rows_index must be one-to-one on its non-negative entries"
+            index, scale = -np.ones(lay["ncon"], dtype=np.int64), np.zeros(lay["ncon"])
+            index[idx[used]], scale[idx[used]] = used, sign[used]
+            fm = self._fold_map = (index, scale)
+        return fm
+
+    def fold_multipliers_device(self, lams):
+        """``fold_multipliers`` on a device fp64 tensor lams (K, ld >= ncon) with contiguous rows, without a read-back:
+        lam_rows by rato_scatter_f64 through ``fold_map()`` into a zeroed (K, S+1, 2), lam_dyn the contiguous copy of
+        lams[:, :8 S] -> (lam_dyn (K, S, 8), lam_rows (K, S+1, 2)) device tensors, bitwise the host's"""
+        ncon, S = self.nlp_layout()["ncon"], self.S
+        if not isinstance(lams, torch.Tensor) or lams.dim() != 2 or lams.shape[1] < ncon or lams.dtype != torch.float64 or \
+                not lams.is_cuda or lams.stride(1) != 1:
+            raise ValueError(f"lams must be a device float64 tensor (K, >= {ncon}) with contiguous rows")
+        K = lams.shape[0]
+        fd = getattr(self, "_fold_dev", None)
+        if fd is None:
+            index, scale = self.fold_map()
+            fd = self._fold_dev = (torch.as_tensor(index, device=self.device), torch.as_tensor(scale, device=self.device))
+        lam_rows = torch.zeros((K, S + 1, 2), dtype=torch.float64, device=lams.device)
+        ld = lams.stride(0) if K > 1 else max(lams.stride(0), ncon)
+        with torch.cuda.device(lams.device):
+            _lib.check(self._lib.rato_scatter_f64(K, ncon, _lib.ptr(lams), ld, _lib.ptr(fd[0]), _lib.ptr(fd[1]), _lib.ptr(lam_rows),
+                                                  2 * (S + 1), 2 * (S + 1), _lib.current_stream()), "rato_scatter_f64")
+        return lams[:, :n_x * S].contiguous().view(K, S, n_x), lam_rows
+
+    def nlp_device(self, Zs, lams=None, add=None, fold='host'):
         """K problems per call.  Zs (K, nvar) host array or device fp64 tensor (rows may be strided: ldz >= nvar); lams
         (K, ncon) multipliers of g or None; add (K, S+1, 78) blocks added to the Hessian or None.  -> dict of fp64 DEVICE tensors:
         defect (K, S, 8), d_defect (K, S, 8, 12), rows (K, S+1, 2), d_rows (K, S+1, 2, 4), jac_values (K, nnz): the CSC values of
@@ -842,7 +953,11 @@ class Model:
         precision='f64' adds the risk group, from the same Z on the device (no host gather): slip_h (K, C, M), slip_rows
         (K, M C) = h in the risk rows' order i C + c, slip_jac_values (K, nnz_slip) in ``_jacobian_pattern`` order with the
         constant entries in place; with lams the slip rows' share is inside hess_blocks / hess_tril (the multipliers are read
-        where they lie).  Four more launches, seven with lams."""
+        where they lie).  Four more launches, seven with lams.
+        fold='device' (lams a device tensor (K, ld >= ncon)): the multipliers are folded by ``fold_multipliers_device`` and
+        nothing of them is read back; hess_tril is not built (the solver reads the blocks)."""
+        if fold not in ('host', 'device'):
+            raise ValueError(f"fold must be 'host' or 'device', got {fold!r}")
         dev = self.device
         if not isinstance(Zs, torch.Tensor):
             Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=dev)
@@ -860,9 +975,17 @@ class Model:
         if f64:                                                   # the risk group from the same Z, on the device
             if lams is not None and not isinstance(lams, torch.Tensor):
                 lams = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(lams, dtype=np.float64))), device=dev)
-            slip = self._slip_f64(Zs, lams)
+            slip = self._slip_f64(Zs, lams if lams is None or fold == 'host' else lams[:, :self.nlp_layout()["ncon"]])
             out.update(slip_h=slip["slip_h"], slip_rows=slip["slip_rows"], slip_jac_values=slip["slip_jac_values"])
-        if lams is not None:
+        if lams is not None and fold == 'device':
+            lam_dyn, lam_rows = self.fold_multipliers_device(lams)
+            if lam_dyn.shape[0] != K:
+                raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")
+            if f64 and self.nlp_layout()["C"] > 0:
+                add = torch.zeros((K, self.S + 1, n_pairs), dtype=torch.float64, device=dev) if add is None else add.clone()
+                self.slip_hess_blocks_device_f64(Zs, slip["D"], add)
+            out["hess_blocks"] = nlp_hessian_device(st["params"], Zs, lam_dyn, lam_rows, add)
+        elif lams is not None:
             lam_dyn, lam_rows = self.fold_multipliers(lams.cpu().numpy() if isinstance(lams, torch.Tensor) else lams)
             if lam_dyn.shape[0] != K:
                 raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")

@@ -7,6 +7,11 @@ redundant rows.)
 on the values ``Model.nlp_device`` leaves in HBM, K problems per launch; 'numpy' does the whole step on the host, callbacks
 injected or taken one problem at a time from the Model.
 
+driver='device' (``ipm.solve_group_device``) keeps the iterate in HBM: the device backend then serves device
+tensors (eval_full_t ... factor_t below), g is assembled by rato_hopper_g_f64, W x is rato_hopper_block_symv_f64 and the
+multipliers are folded by rato_scatter_f64 (csrc/hopper_g.hip, ``Model.fold_multipliers_device``); nothing but the scalar
+record and the factorization's info comes back during an iteration.
+
 newton='arrow' (``hopper_arrow``) is the same step for any M: the M variables ys are eliminated exactly and the
 Cholesky factors the core's Schur complement; newton='dense' (the default) is the step over all variables.
 """
@@ -230,6 +235,9 @@ class DeviceBackend(_ipm.DeviceBase):
         self.saa = m0.method != 'baseline' and lay["C"] > 0
         self.alpha_pos = int(lay["nnz_slip"] - 1 - m0.M * lay["C"]) if self.saa else -1
         self.vals0 = self.vals1 = self.hessd = self.hess_host = None
+        # for the driver on the device: M alpha per problem (the sum row of g, and the Jacobian entry above), uploaded once
+        self.malpha = up([m0.M * float(m.alpha) for m in models], np.float64) if m0.method != 'baseline' else None
+        self.Kc = None
 
     def _g_rows(self, idx, Zs, r):
         defect, rows = r["defect"].cpu().numpy(), r["rows"].cpu().numpy()
@@ -317,6 +325,79 @@ class DeviceBackend(_ipm.DeviceBase):
         with self.timed("solve"):
             return list(self.solve_device(idx, B))
 
+    # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group, takes and returns
+    # (K, ld) tensors, waits for nothing and moves nothing to the host.  ``solve_t`` is DeviceBase's.
+    def _g_t(self, Z, r):
+        m0 = self.m0
+        Cn = m0.nlp_layout()["C"]
+        return _h.g_device(m0._slip_params(), m0.M, m0.method != 'baseline', Z, r["defect"], r["rows"],
+                           r["slip_rows"] if Cn > 0 else None, (Cn, 1), self.malpha)
+
+    def eval_full_t(self, Z, Y):
+        """Z (K, n) and the multipliers Y (K, ld >= ncon) -> g (K, ncon); leaves the Jacobian's values and the step blocks of
+        hess(Y . g) for the calls below.  The objective's curvature is NOT in the blocks: the driver's diagonal carries it."""
+        r = self.m0.nlp_device(Z, Y, fold='device')
+        self.vals0, self.vals1, self.hessd = r["jac_values"], r["slip_jac_values"], r["hess_blocks"]
+        if self.saa:
+            self.vals1[:, self.alpha_pos] = self.malpha
+        self.slot = {i: i for i in range(Z.shape[0])}
+        return self._g_t(Z, r)
+
+    def eval_g_t(self, Z):
+        return self._g_t(Z, self.m0.nlp_device(Z))
+
+    def _matvec_t(self, entry, name, x, n_in, n_out, ptr, lidx, other):
+        _lib, st, torch = self._lib, self.st, self.torch
+        v0, v1 = self.vals0, self.vals1
+        K = v0.shape[0]
+        if x.dim() != 2 or x.shape[0] != K or x.shape[1] < n_in or x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError(f"{name}: the vector must be a contiguous device float64 tensor ({K}, >= {n_in})")
+        out = torch.empty((K, n_out), dtype=torch.float64, device=self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(entry(K, st["ncon"], st["n"], _lib.ptr(v0), v0.shape[1], st["n_det"], _lib.ptr(v1), v1.shape[1],
+                             st["n_slip"], _lib.ptr(self.maps[ptr]), _lib.ptr(self.maps[lidx]), _lib.ptr(self.maps[other]),
+                             _lib.ptr(x), x.shape[1], _lib.ptr(out), n_out, _lib.current_stream()), name)
+        return out
+
+    def matvec_t(self, X):
+        """X (K, ld >= n) -> J x (K, ncon)"""
+        return self._matvec_t(self.lib.rato_csc_matvec_f64, "rato_csc_matvec_f64", X, self.st["n"], self.st["ncon"], "row_ptr",
+                              "row_idx", "row_col")
+
+    def tmatvec_t(self, W):
+        """W (K, ld >= ncon) -> J' w (K, n)"""
+        return self._matvec_t(self.lib.rato_csc_tmatvec_f64, "rato_csc_tmatvec_f64", W, self.st["ncon"], self.st["n"], "col_ptr",
+                              "col_idx", "col_row")
+
+    def hess_apply_t(self, X):
+        """W x of the constraints' part alone (K, n): the objective's sf curv x is added where the result is used
+        (csrc/ipm_driver.hip)"""
+        return _h.block_symv(self.m0.S, self.hessd, X, self.st["n"])
+
+    def normal_matrix_t(self, d, diag, out=None):
+        """d (K, ld >= ncon), diag (K, n) with the objective's curvature already in it -> Kc (K, n, lda)"""
+        _lib, st, torch, mp = self._lib, self.st, self.torch, self.maps
+        v0, v1, hs = self.vals0, self.vals1, self.hessd
+        K, n = v0.shape[0], st["n"]
+        if d.dim() != 2 or d.shape[0] != K or d.shape[1] < st["ncon"] or not d.is_contiguous() or tuple(diag.shape) != (K, n) or \
+                not diag.is_contiguous() or d.dtype != torch.float64 or diag.dtype != torch.float64:
+            raise ValueError(f"d must be a contiguous device float64 tensor ({K}, >= {st['ncon']}) and diag ({K}, {n})")
+        Kc = torch.empty((K, n, n), dtype=torch.float64, device=self.dev) if out is None else out
+        if tuple(Kc.shape[:2]) != (K, n) or Kc.shape[2] < n or Kc.dtype != torch.float64 or not Kc.is_contiguous():
+            raise ValueError(f"out must be a contiguous device float64 tensor ({K}, {n}, >= {n})")
+        with torch.cuda.device(self.dev):
+            _lib.check(self.lib.rato_normal_matrix_f64(
+                K, n, Kc.shape[2], _lib.ptr(v0), v0.shape[1], st["n_det"], _lib.ptr(v1), v1.shape[1], st["n_slip"], _lib.ptr(d),
+                d.shape[1], _lib.ptr(hs), hs.shape[1] * hs.shape[2], _lib.ptr(diag), _lib.ptr(mp["ent_of"]), _lib.ptr(mp["ptr"]),
+                _lib.ptr(mp["tri_a"]), _lib.ptr(mp["tri_b"]), _lib.ptr(mp["tri_r"]), _lib.ptr(mp["hess_src"]), _lib.ptr(Kc),
+                _lib.current_stream()), "rato_normal_matrix_f64")
+        return Kc
+
+    def factor_t(self, d, diag):
+        with self.timed_t("normal"):
+            self.Kc = self.normal_matrix_t(d, diag, out=self.Kc)
+        return self.factor_all(self.Kc)
+
 
 def _group_key(m):
     f = tuple(np.asarray(x).tobytes() for x in (getattr(m, "intensities", None), getattr(m, "thetas", None), getattr(m, "taus", None))
@@ -325,7 +406,7 @@ def _group_key(m):
 
 
 def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
-                newton='dense'):
+                newton='dense', driver='host'):
     """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  The K problems share S, M and the phases;
     problems of one method and one set of friction fields (alpha may differ) form a group that moves through the K-problem
     kernels together, the groups one after the other.  A problem that has ended stops changing and leaves the launches; its Z is
@@ -337,12 +418,18 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
       newton     'dense': the condensed matrix over all n = 8(S+1) + 4S + M + 2 variables (the default; n^2 memory, right at the
                  script's M = 30); 'arrow': the M sample variables ys are eliminated exactly and the 8(S+1) + 4S + 2 core is
                  factored (``hopper_arrow``): memory and work are O(M C), for any M
+      driver     'host' (``ipm.solve_group``: the iterate and the vector algebra on the host) or 'device'
+                 (``ipm.solve_group_device``, backend='device' and newton='dense' only: the iterate stays on the device,
+                 csrc/ipm_driver.hip and csrc/hopper_g.hip, and the clocks hold the time to launch; info["driver"] = 'device')
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
     dual_infeasibility, f, and the final multipliers y, zl, zu with the slacks s and the objective scale sf."""
     if backend not in ('device', 'numpy'):
         raise ValueError(f"backend must be 'device' or 'numpy', got {backend!r}")
     if newton not in ('dense', 'arrow'):
         raise ValueError(f"newton must be 'dense' or 'arrow', got {newton!r}")
+    _ipm.check_driver(driver, backend)
+    if driver == 'device' and newton == 'arrow':
+        raise ValueError("driver='device' serves the dense Newton step: the arrow backend (newton='arrow') is not yet served")
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
@@ -365,7 +452,7 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
         cbs = None if callbacks is None else [callbacks[i] for i in members]
         return ms, (on_device(ms) if backend == 'device' else on_host(ms, cbs))
 
-    return _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, clocks)
+    return _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, clocks, driver=driver)
 
 
 # ---- former homes.  Code written against the module before it was split (the previous revision's tests among it) reaches

@@ -24,7 +24,8 @@ clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_sol
 
 ``solve_group_device`` (``driver='device'``) is the same method with the iterate on the device: ``DeviceState``
 holds the state of the K problems in HBM, the vector algebra above is csrc/ipm_driver.hip, and the host keeps the branches
-it needs a read-back for: who is still running, the delta_w ladder, who is still searching.
+it needs a read-back for: who is still running, the delta_w ladder, who is still searching.  There the objective is
+sf (1/2 sum curv z^2 + lin . z): the model gives ``curv`` and, if it has a linear part, ``lin`` (both (n,)).
 """
 import contextlib
 import time
@@ -471,7 +472,7 @@ class DeviceState:
     The methods are the kernels: ``residuals``, ``newton``, ``step_setup``, ``trial``, ``accept``; ``record()`` reads the
     (K, RATO_IPM_REC) scalars back -- the only read-back an iteration needs."""
     NV = ("v", "zl", "zu", "vL", "vU", "Sigma", "gbar", "dv", "dzl", "dzu", "vt")
-    N = ("curv", "gradf", "rz", "dz", "ez")
+    N = ("curv", "lin", "gradf", "rz", "dz", "ez")
     M = ("y", "gL", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")
     SCALARS = ("mu", "nu", "dw", "dc", "tol", "E0", "prim", "dual", "a_max", "a_dual", "Dphi", "phi", "alpha", "sf")
 
@@ -513,14 +514,17 @@ class DeviceState:
         self.F = F
         ptr = lambda t: t.data_ptr()
         self.c_state = _lib.IpmState(self.K, self.n, self.nI, self.m, self.ldv, self.ldm, ptr(self.row_slack),
-                                     *[ptr(getattr(self, k)) for k in ("v", "zl", "zu", "vL", "vU", "curv", "y", "gL", "rec", "Sigma",
-                                                                      "gbar", "dv", "dzl", "dzu", "vt", "gradf", "rz", "dz", "ez",
-                                                                      "diag", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")])
+                                     *[ptr(getattr(self, k)) for k in ("v", "zl", "zu", "vL", "vU", "curv", "lin", "y", "gL", "rec",
+                                                                      "Sigma", "gbar", "dv", "dzl", "dzu", "vt", "gradf", "rz", "dz",
+                                                                      "ez", "diag", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")])
 
     def _host_vector(self, p, name):
         """what a Problem holds of the named device vector, in the device's layout, or None"""
         if name == "curv":
             return np.asarray(p.model.curv, dtype=np.float64)
+        if name == "lin":                                            # f = sf (1/2 sum curv z^2 + lin . z); a model without one: zeros
+            lin = getattr(p.model, "lin", None)
+            return np.zeros(self.n) if lin is None else np.asarray(lin, dtype=np.float64)
         if name == "gL":
             return np.asarray(p.model.gL_gU()[0], dtype=np.float64)
         a = getattr(p, name, None)
@@ -536,7 +540,8 @@ class DeviceState:
     def download(self, ps):
         """the device's state into the host Problems: the iterate, the scalars and every work vector"""
         rec = self.record()
-        get = {k: getattr(self, k).cpu().numpy() for k in self.NV + self.N + self.M if k not in ("curv", "gL", "vL", "vU")}
+        const = ("curv", "lin", "gL", "vL", "vU")
+        get = {k: getattr(self, k).cpu().numpy() for k in self.NV + self.N + self.M if k not in const}
         for k, p in enumerate(ps):
             for name, a in get.items():
                 length = self.nv if name in self.NV else self.n if name in self.N else self.m

@@ -745,12 +745,14 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
             "wall_s": wall}
 
 
-def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device', newton='dense'):
+def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device', newton='dense', driver='host'):
     """The hopper script's solve block (hopper.py:642-670) for one model: ``hopper_ipm.solve_batch`` in IPOPT's place, from
     ``Z0`` (default ``model.initial_guess()``) -> dict(Z, xs (S+1, 8), us (S, 4), status, info, total_s).  status is
-    'converged' only if the final error E_0 <= tol shows it.  newton: 'dense' or 'arrow' (``hopper_ipm.solve_batch``)."""
+    'converged' only if the final error E_0 <= tol shows it.  newton: 'dense' or 'arrow' (``hopper_ipm.solve_batch``).
+    ``driver``: 'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device',
+    newton='dense')."""
     t0 = time.perf_counter()
-    Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend, newton=newton)
+    Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend, newton=newton, driver=driver)
     xs, us = model.convert_z_to_xs_us_mats(Z)
     return {"Z": Z, "xs": xs, "us": us, "status": info["status"], "info": info, "total_s": time.perf_counter() - t0}
 
@@ -781,12 +783,13 @@ def hopper_saa_start(model, xs, us):
 
 
 def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=1, results_dir=None, tol=1e-3, max_iter=3000,
-                      backend='device', device='cuda:0', clocks=None, newton='dense', fields=None):
+                      backend='device', device='cuda:0', clocks=None, newton='dense', fields=None, driver='host'):
     """The hopper script's two runs (hopper.py:455-680) as one call: the friction fields under ``RandomState(seed)`` (:70-74),
     the baseline from ``initial_guess()``, then every alpha of the SAA problem in ONE lockstep batch from the baseline's
     solution (:465-479).  With ``results_dir`` the files hopper_base_results.npy and hopper_saa_alpha=<a>_results.npy are
     written (xs then us, ``save_results``), whatever the status.  ``fields``: (intensities, thetas, taus), each (M, 30), in place
-    of the draw; ``newton``: 'dense' or 'arrow' (``hopper_ipm.solve_batch``: 'arrow' is the one that scales with M).
+    of the draw; ``newton``: 'dense' or 'arrow' (``hopper_ipm.solve_batch``: 'arrow' is the one that scales with M); ``driver``:
+    'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', newton='dense').
     -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)"""
     from . import hopper, hopper_ipm
     alphas = [float(a) for a in alphas]
@@ -796,13 +799,13 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
     base_model = hopper.Model(M, 'baseline', S=S, fields=fields, device=device, precision='f64')
     c0 = {}
     (Zb, ib), = hopper_ipm.solve_batch([base_model], tol=tol, max_iter=max_iter, backend=backend, clocks=c0,
-                                        newton=newton)
+                                        newton=newton, driver=driver)
     xs, us = base_model.convert_z_to_xs_us_mats(Zb)
     base = {"Z": Zb, "xs": xs, "us": us, "status": ib["status"], "info": ib}
     models = [hopper.Model(M, 'saa', a, S=S, fields=fields, device=device, precision='f64') for a in alphas]
     c1 = {}
     sols = hopper_ipm.solve_batch(models, [hopper_saa_start(m, xs, us) for m in models], tol=tol, max_iter=max_iter,
-                                  backend=backend, clocks=c1, newton=newton) if models else []
+                                  backend=backend, clocks=c1, newton=newton, driver=driver) if models else []
     results = []
     for m, (Z, info) in zip(models, sols):
         x, u = m.convert_z_to_xs_us_mats(Z)
