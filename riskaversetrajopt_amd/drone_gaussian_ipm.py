@@ -15,7 +15,9 @@ The constraint matrix is dense: J = [jac_nl; the sum row] (m x nvar).  Two backe
             down come g_nl, the matvec results, the factorization's info and the solutions.  jac_nl, the packed Hessian and
             Kc / L never leave the device.
   'numpy'   the whole step on the host on injected (or the model's) callbacks dict(linearize, hessian).
-alpha enters only the host-side bounds, so the problems of one S form a group whatever their alpha.
+alpha enters only the host-side bounds, so the problems of one S form a group whatever their alpha.  A backend here is its
+callbacks, its products and its normal matrix (``normal_matrix_host``; ``normal_matrix`` / ``normal_matrix_t`` on the device):
+factor and solve, on lists and on tensors, are ``ipm.Backend``'s / ``ipm.DeviceBase``'s.
 """
 import numpy as np
 
@@ -131,18 +133,8 @@ class NumpyBackend(_ipm.Backend):
             out = [self.J[i].T @ w for i, w in zip(idx, W)]
         return out
 
-    def factor(self, idx, D, diags):
-        info = []
-        for i, d, dg in zip(idx, D, diags):
-            with self.timed("normal"):
-                Kc = normal_matrix_host(self.J[i], d, self.hess[i], dg + self.sf[i] * self.nlps[i].curv)
-            with self.timed("factor"):
-                info.append(self.factor_host(i, Kc))
-        return info
-
-    def solve(self, idx, B):
-        with self.timed("solve"):
-            return [self.solve_host(i, b) for i, b in zip(idx, B)]
+    def normal_matrix_host(self, i, d, diag):
+        return normal_matrix_host(self.J[i], d, self.hess[i], diag + self.sf[i] * self.nlps[i].curv)
 
 
 def _check(t, name, dims=None):
@@ -250,7 +242,7 @@ class DeviceBackend(_ipm.DeviceBase):
         self.st = None
         self.sum_row = self.torch.as_tensor(nlps[0].sum_row()[None, :].copy(), device=self.dev)
         self.sf = {}
-        self.jac = self.hess = self.Kc = None
+        self.jac = self.hess = None
 
     def _g(self, idx, Zs, g_nl):
         g_nl = g_nl.cpu().numpy()
@@ -307,19 +299,8 @@ class DeviceBackend(_ipm.DeviceBase):
         dg = self._up([g + self.sf[i] * self.nlps[i].curv for i, g in zip(idx, diags)])
         return dense_normal_matrix(self.n, jac, self.sum_row, self._up(D), hess, dg, out=out)
 
-    def factor(self, idx, D, diags):
-        with self.timed("normal"):
-            Kc = self.normal_matrix(idx, D, diags)
-            self._sync()
-        with self.timed("factor"):
-            return self.factor_device(idx, Kc)
-
-    def solve(self, idx, B):
-        with self.timed("solve"):
-            return list(self.solve_device(idx, B))
-
     # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group, takes and returns
-    # (K, ld) tensors and waits for nothing.  ``solve_t`` is DeviceBase's.
+    # (K, ld) tensors and waits for nothing.  ``factor_t`` and ``solve_t`` are DeviceBase's, as are ``factor`` and ``solve``.
     def eval_full_t(self, Z, Y):
         """Z (K, n) and the multipliers Y (K, ld >= m) -> g (K, m); leaves jac_nl and the packed Hessian of Y . g for the calls below"""
         with self.torch.cuda.device(self.dev):
@@ -347,11 +328,6 @@ class DeviceBackend(_ipm.DeviceBase):
     def normal_matrix_t(self, d, diag, out=None):
         """d (K, ld >= m), diag (K, n) with the objective's curvature already in it -> Kc (K, n, lda)"""
         return dense_normal_matrix(self.n, self.jac, self.sum_row, d, self.hess, diag, out=out)
-
-    def factor_t(self, d, diag):
-        with self.timed_t("normal"):
-            self.Kc = self.normal_matrix_t(d, diag, out=self.Kc)
-        return self.factor_all(self.Kc)
 
 
 # ---- the solve -------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 same step as the dense one for any M.  The M variables ys enter Kc only through E = diag(e) + d_0 1 1' and one row each of B, so
 they are eliminated exactly and the Cholesky factors the core's Schur complement (8(S+1) + 4S + 2 columns) -- the same inertia
 test, since e > 0.  ``ArrowDeviceBackend`` does the work over the samples with csrc/hopper_arrow.hip on the partials
-rato_hopper_slip_f64 leaves, ``ArrowNumpyBackend`` is its host twin.
+rato_hopper_slip_f64 leaves and the deterministic rows with ``hopper_ipm``'s ``normal_matrix`` / ``csc_matvec`` / ``csc_tmatvec`` on
+the core's pattern; ``ArrowNumpyBackend`` is its host twin.  Both keep their own factor and solve (the elimination).
 """
 import time
 
@@ -10,7 +11,8 @@ import numpy as np
 
 from . import hopper as _h
 from . import ipm as _ipm
-from .hopper_ipm import ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, assemble_g, normal_matrix_host
+from .hopper_ipm import (ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, assemble_g, csc_matvec, csc_tmatvec, normal_matrix,
+                         normal_matrix_host, upload_maps)
 
 
 def arrow_structure(model):
@@ -220,7 +222,7 @@ class ArrowNumpyBackend(_ipm.Backend):
 
 class ArrowDeviceBackend(_ipm.DeviceBase):
     """The arrowhead step on the MI355X for the problems of one group (csrc/hopper_arrow.hip on the partials rato_hopper_slip_f64
-    leaves in HBM; the core through rato_normal_matrix_f64 on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).
+    leaves in HBM; the core through ``hopper_ipm.normal_matrix`` on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).
     eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels to the
     host per call is the vectors the driver works on and O(q) sums."""
     name, newton = "device", "arrow"
@@ -235,14 +237,10 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
             raise ValueError("the device backend needs Model(..., precision='f64')")
         super().__init__(m0.device, len(models), "reduction", "assembly", "products")
         st = self.st = arrow_structure(m0)
-        det, lay = st["det"], m0.nlp_layout()
+        lay = m0.nlp_layout()
         up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
-        self.maps = dict(ent_of=up(det["ent_of"], np.int32), ptr=up(det["ptr"], np.int64), tri_a=up(det["tri_a"], np.int32),
-                         tri_b=up(det["tri_b"], np.int32), tri_r=up(det["tri_r"], np.int32), hess_src=up(det["hess_src"], np.int32),
-                         row_ptr=up(det["row_ptr"], np.int64), row_idx=up(det["row_idx"], np.int32),
-                         row_col=up(st["core_z"][det["row_col"]], np.int32), col_ptr=up(st["det_indptr_z"], np.int64),
-                         col_idx=up(np.arange(det["nnz"]), np.int32), col_row=up(st["det_rows"], np.int32),
-                         qcol=up(st["qcol"], np.int32), map_defect=up(lay["map_defect"], np.int64),
+        self.maps = upload_maps(st["det"], self.dev, to_col=st["core_z"], col_ptr=st["det_indptr_z"])     # x and J'w in z numbering
+        self.maps.update(qcol=up(st["qcol"], np.int32), map_defect=up(lay["map_defect"], np.int64),
                          map_rows=up(lay["map_rows"], np.int64), scale_rows=up(lay["scale_rows"], np.float64),
                          det_const=up(lay["det_const"], np.float64))
         self.params = _h.nlp_params(m0.S, m0.time_jump, m0.time_land, m0.dt)
@@ -302,14 +300,6 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         with self.torch.cuda.device(self.dev):
             self._lib.check(getattr(self.lib, name)(*args, self._lib.current_stream()), name)
 
-    def _det_matvec(self, name, v0, x, n_out, ptr, lidx, other):
-        st, p = self.st, self._lib.ptr
-        K = x.shape[0]
-        out = self._empty(K, n_out)
-        self._call(name, K, st["ncon"], st["n"], p(v0), v0.shape[1], v0.shape[1], None, 0, 0, p(self.maps[ptr]),
-                   p(self.maps[lidx]), p(self.maps[other]), p(x), x.shape[1], p(out), n_out)
-        return out
-
     def matvec(self, idx, X):
         with self.timed("products"):
             st, p = self.st, self._lib.ptr
@@ -317,7 +307,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
             v0, dx, dfz, _ = self._sel(idx)
             xh = np.stack(X)
             x = self._up(X)
-            out = self._det_matvec("rato_csc_matvec_f64", v0, x, st["ncon"], "row_ptr", "row_idx", "row_col")
+            out = csc_matvec(st, self.maps, v0, None, x)                # the deterministic rows; the risk rows below
             xq, xy = self._up(list(xh[:, st["qz"]])), x[:, st["y0"]:st["y0"] + M].contiguous()
             part, red = self._empty(self.nch, K), self._empty(K)
             self._call("rato_hopper_arrow_rows_f64", K, M, Cn, int(st["saa"]), 0, p(dx), p(dfz), p(xq), p(xy), None, 0, st["r0"],
@@ -351,7 +341,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
             v0, dx, dfz, _ = self._sel(idx)
             wh = np.stack(W)
             w = self._up(W)
-            out = self._det_matvec("rato_csc_tmatvec_f64", v0, w, st["n"], "col_ptr", "col_idx", "col_row")
+            out = csc_tmatvec(st, self.maps, v0, None, w)
             yout = self._empty(K, M)
             red = self._cols(0, dx, dfz, w, None, yout)
             o = out.cpu().numpy()
@@ -366,19 +356,14 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     def schur(self, idx, D, diags, out=None):
         """-> (Shat (K, nc, lda) device tensor, lower triangle; e (K, M) and d (K, ncon) device; red (K, n_part) and d on the
         host): the core's Schur complement of the listed problems (``out``: a contiguous (K, nc, lda >= nc) tensor to write into)"""
-        st, torch, mp, p = self.st, self.torch, self.maps, self._lib.ptr
+        st, mp, p = self.st, self.maps, self._lib.ptr
         M, Cn, nc, K = st["M"], st["C"], st["nc"], len(idx)
         v0, dx, dfz, hs = self._sel(idx)
         dh = np.stack(D)
         d, dgh = self._up(D), np.stack(diags)
         dg, yd = self._up(list(dgh[:, st["core_z"]])), self._up(list(dgh[:, st["y0"]:st["y0"] + M]))
-        Sh = self._empty(K, nc, nc) if out is None else out
-        if tuple(Sh.shape[:2]) != (K, nc) or Sh.shape[2] < nc or Sh.dtype != torch.float64 or not Sh.is_contiguous():
-            raise ValueError(f"out must be a contiguous device float64 tensor ({K}, {nc}, >= {nc})")
         t0 = time.perf_counter()
-        self._call("rato_normal_matrix_f64", K, nc, Sh.shape[2], p(v0), v0.shape[1], v0.shape[1], None, 0, 0, p(d), st["ncon"], p(hs),
-                   hs.shape[1] * hs.shape[2], p(dg), p(mp["ent_of"]), p(mp["ptr"]), p(mp["tri_a"]), p(mp["tri_b"]), p(mp["tri_r"]),
-                   p(mp["hess_src"]), p(Sh))
+        Sh = normal_matrix(nc, st["ncon"], mp, v0, None, d, hs, dg, out=out)       # the deterministic rows' J'DJ + W + the diagonal
         self._sync()
         t1 = time.perf_counter()
         e, part, red = self._empty(K, M), self._empty(self.nch, K, self.npart), self._empty(K, self.npart)

@@ -3,12 +3,14 @@ interior-point method of ``ipm``: the fixed sparse structure of 
 (Relaxing the bounds outward makes the constant row ``0 <= 0`` of the SAA group harmless; delta_c tolerates the script's
 redundant rows.)
 
-'device' works with csrc/hopper_ipm.hip (rato_normal_matrix_f64, rato_csc_matvec_f64 / rato_csc_tmatvec_f64) and csrc/chol.hip
-on the values ``Model.nlp_device`` leaves in HBM, K problems per launch; 'numpy' does the whole step on the host, callbacks
-injected or taken one problem at a time from the Model.
+'device' works with csrc/hopper_ipm.hip and csrc/chol.hip on the values ``Model.nlp_device`` leaves in HBM, K problems per
+launch; 'numpy' does the whole step on the host, callbacks injected or taken one problem at a time from the Model.  The three
+kernels of csrc/hopper_ipm.hip are bound once, as ``normal_matrix``, ``csc_matvec`` and ``csc_tmatvec`` on device tensors (with
+``upload_maps`` for their index lists): both hopper device backends, on lists and on tensors, are adapters over them, and
+``ipm.Backend`` / ``ipm.DeviceBase`` supply factor and solve.
 
 driver='device' (``ipm.solve_group_device``) keeps the iterate in HBM: the device backend then serves device
-tensors (eval_full_t ... factor_t below), g is assembled by rato_hopper_g_f64, W x is rato_hopper_block_symv_f64 and the
+tensors (eval_full_t ... normal_matrix_t below), g is assembled by rato_hopper_g_f64, W x is rato_hopper_block_symv_f64 and the
 multipliers are folded by rato_scatter_f64 (csrc/hopper_g.hip, ``Model.fold_multipliers_device``); nothing but the scalar
 record and the factorization's info comes back during an iteration.
 
@@ -16,7 +18,9 @@ newton='arrow' (``hopper_arrow``) is the same step for any M: the
 Cholesky factors the core's Schur complement; newton='dense' (the default) is the step over all variables.
 """
 import numpy as np
+import torch
 
+from . import _lib
 from . import hopper as _h
 from . import ipm as _ipm
 
@@ -184,18 +188,8 @@ class NumpyBackend(_ipm.Backend):
         st = self.st
         return [np.bincount(st["cols"], weights=self.vals[i] * w[st["rows"]], minlength=st["n"]) for i, w in zip(idx, W)]
 
-    def factor(self, idx, D, diags):
-        info = []
-        for i, d, dg in zip(idx, D, diags):
-            with self.timed("normal"):
-                Kc = normal_matrix_host(self.st, self.vals[i], d, self.hess[i], dg)
-            with self.timed("factor"):
-                info.append(self.factor_host(i, Kc))
-        return info
-
-    def solve(self, idx, B):
-        with self.timed("solve"):
-            return [self.solve_host(i, b) for i, b in zip(idx, B)]
+    def normal_matrix_host(self, i, d, diag):
+        return normal_matrix_host(self.st, self.vals[i], d, self.hess[i], diag)
 
 
 def assemble_g(model, Z, defect, rows, slip_rows):
@@ -208,15 +202,83 @@ def assemble_g(model, Z, defect, rows, slip_rows):
                            -rows[tj:tl, 1], risk, us.reshape(-1), [Z[-2]], xs[1:, 3], xs[1:, 7], xs[1:, 6]])
 
 
+# ---- the kernels of csrc/hopper_ipm.hip on device fp64 tensors: each entry point is called here and nowhere else ----------------
+def upload_maps(pm, dev, to_value=None, to_col=None, col_ptr=None):
+    """the index lists of a ``_pattern_maps`` dict as the device tensors the three kernels read.  ``to_value`` translates the
+    pattern's value index into the index in the value arrays (None: the same), ``to_col`` the pattern's column into the column
+    of x (None: the same), and ``col_ptr`` is the column list's pointer over the columns of J'w (None: the pattern's indptr)."""
+    up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=dev)
+    val = (lambda a: a) if to_value is None else (lambda a: to_value[a])
+    return dict(ent_of=up(pm["ent_of"], np.int32), ptr=up(pm["ptr"], np.int64), tri_a=up(val(pm["tri_a"]), np.int32),
+                tri_b=up(val(pm["tri_b"]), np.int32), tri_r=up(pm["tri_r"], np.int32), hess_src=up(pm["hess_src"], np.int32),
+                row_ptr=up(pm["row_ptr"], np.int64), row_idx=up(val(pm["row_idx"]), np.int32),
+                row_col=up(pm["row_col"] if to_col is None else to_col[pm["row_col"]], np.int32),
+                col_ptr=up(pm["indptr"] if col_ptr is None else col_ptr, np.int64),
+                col_idx=up(val(np.arange(pm["nnz"])), np.int32), col_row=up(pm["rows"], np.int32))
+
+
+def _bad(t, K, ld):
+    return t.dim() != 2 or t.shape[0] != K or t.shape[1] < ld or t.dtype != torch.float64 or not t.is_contiguous()
+
+
+def _values(v0, v1):
+    """the value arrays as the kernels take them: pointer, ld and count of the deterministic rows' values v0 (K, n_det) and of
+    the slip rows' v1 (K, n_slip); v1 None: the arrow backend's deterministic block alone"""
+    if v1 is None:
+        return _lib.ptr(v0), v0.shape[1], v0.shape[1], None, 0, 0
+    return _lib.ptr(v0), v0.shape[1], v0.shape[1], _lib.ptr(v1), v1.shape[1], v1.shape[1]
+
+
+def _csc(name, st, maps, lists, v0, v1, x, n_in, n_out):
+    K = v0.shape[0]
+    if _bad(x, K, n_in):
+        raise ValueError(f"{name}: the vector must be a contiguous device float64 tensor ({K}, >= {n_in})")
+    if v1 is not None and (v0.shape[1] != st["n_det"] or v1.shape != (K, st["n_slip"])):
+        raise ValueError(f"{name}: the values must be ({K}, {st['n_det']}) and ({K}, {st['n_slip']})")
+    out = torch.empty((K, n_out), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(getattr(_lib.load(), name)(K, st["ncon"], st["n"], *_values(v0, v1), _lib.ptr(maps[lists[0]]),
+                                              _lib.ptr(maps[lists[1]]), _lib.ptr(maps[lists[2]]), _lib.ptr(x), x.shape[1],
+                                              _lib.ptr(out), n_out, _lib.current_stream()), name)
+    return out
+
+
+def csc_matvec(st, maps, v0, v1, x):
+    """rato_csc_matvec_f64: x (K, ld >= n) -> J x (K, ncon), J's values in v0 and v1 as ``_values`` takes them"""
+    return _csc("rato_csc_matvec_f64", st, maps, ("row_ptr", "row_idx", "row_col"), v0, v1, x, st["n"], st["ncon"])
+
+
+def csc_tmatvec(st, maps, v0, v1, w):
+    """rato_csc_tmatvec_f64: w (K, ld >= ncon) -> J' w (K, n)"""
+    return _csc("rato_csc_tmatvec_f64", st, maps, ("col_ptr", "col_idx", "col_row"), v0, v1, w, st["ncon"], st["n"])
+
+
+def normal_matrix(n, ncon, maps, v0, v1, d, hess, diag, out=None):
+    """rato_normal_matrix_f64: values as ``_values`` takes them, d (K, ldd >= ncon), hess (K, S+1, 78) step blocks or None, diag
+    (K, n) or None -> Kc (K, n, lda), lower triangle (``out``: a contiguous (K, n, lda >= n) tensor to write into)"""
+    K = v0.shape[0]
+    if _bad(d, K, ncon) or (diag is not None and (_bad(diag, K, n) or diag.shape[1] != n)):
+        raise ValueError(f"d must be a contiguous device float64 tensor ({K}, >= {ncon}) and diag ({K}, {n})")
+    if hess is not None and (hess.dim() != 3 or hess.shape[0] != K or hess.dtype != torch.float64 or not hess.is_contiguous()):
+        raise ValueError(f"hess must be a contiguous device float64 tensor ({K}, S + 1, 78)")
+    Kc = torch.empty((K, n, n), dtype=torch.float64, device=d.device) if out is None else out
+    if tuple(Kc.shape[:2]) != (K, n) or Kc.shape[2] < n or Kc.dtype != torch.float64 or not Kc.is_contiguous():
+        raise ValueError(f"out must be a contiguous device float64 tensor ({K}, {n}, >= {n})")
+    with torch.cuda.device(d.device):
+        _lib.check(_lib.load().rato_normal_matrix_f64(
+            K, n, Kc.shape[2], *_values(v0, v1), _lib.ptr(d), d.shape[1], _lib.ptr(hess),
+            0 if hess is None else hess.shape[1] * hess.shape[2], _lib.ptr(diag), _lib.ptr(maps["ent_of"]), _lib.ptr(maps["ptr"]),
+            _lib.ptr(maps["tri_a"]), _lib.ptr(maps["tri_b"]), _lib.ptr(maps["tri_r"]), _lib.ptr(maps["hess_src"]), _lib.ptr(Kc),
+            _lib.current_stream()), "rato_normal_matrix_f64")
+    return Kc
+
+
 class DeviceBackend(_ipm.DeviceBase):
     """the step on the MI355X for the problems of one group (same S, M, phases, method and friction fields; alpha may differ).
     Every call serves the listed problems in ONE launch each; nothing a kernel computes for a problem depends on the others."""
     name = "device"
 
     def __init__(self, models):
-        import torch
-        from . import _lib
-        self._lib, self.lib = _lib, _lib.load()
         self.models = models
         m0 = self.m0 = models[0]
         if any(m.precision != 'f64' for m in models):
@@ -224,20 +286,14 @@ class DeviceBackend(_ipm.DeviceBase):
         super().__init__(m0.device, len(models))
         st = self.st = structure(m0)
         lay = m0.nlp_layout()
-        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
-        tc = st["to_cat"]
-        self.maps = dict(ent_of=up(st["ent_of"], np.int32), ptr=up(st["ptr"], np.int64), tri_a=up(tc[st["tri_a"]], np.int32),
-                         tri_b=up(tc[st["tri_b"]], np.int32), tri_r=up(st["tri_r"], np.int32),
-                         hess_src=up(st["hess_src"], np.int32), row_ptr=up(st["row_ptr"], np.int64),
-                         row_idx=up(tc[st["row_idx"]], np.int32), row_col=up(st["row_col"], np.int32),
-                         col_ptr=up(st["indptr"], np.int64), col_idx=up(tc, np.int32), col_row=up(st["rows"], np.int32))
+        self.maps = upload_maps(st, self.dev, to_value=st["to_cat"])
         # the one Jacobian value that depends on alpha (row 0 of the t_risk column): patched per problem after the group's call
         self.saa = m0.method != 'baseline' and lay["C"] > 0
         self.alpha_pos = int(lay["nnz_slip"] - 1 - m0.M * lay["C"]) if self.saa else -1
         self.vals0 = self.vals1 = self.hessd = self.hess_host = None
         # for the driver on the device: M alpha per problem (the sum row of g, and the Jacobian entry above), uploaded once
-        self.malpha = up([m0.M * float(m.alpha) for m in models], np.float64) if m0.method != 'baseline' else None
-        self.Kc = None
+        self.malpha = torch.as_tensor([m0.M * float(m.alpha) for m in models], dtype=torch.float64, device=self.dev) \
+            if m0.method != 'baseline' else None
 
     def _g_rows(self, idx, Zs, r):
         defect, rows = r["defect"].cpu().numpy(), r["rows"].cpu().numpy()
@@ -277,56 +333,22 @@ class DeviceBackend(_ipm.DeviceBase):
     def _sel(self, idx):
         return self._rows(idx, self.vals0, self.vals1, self.hessd)
 
-    def _list_matvec(self, entry, name, idx, X, n_out, ptr, lidx, other):
-        _lib, st = self._lib, self.st
-        v0, v1, _ = self._sel(idx)
-        x = self._up(X)
-        K = x.shape[0]
-        out = self.torch.empty((K, n_out), dtype=self.torch.float64, device=self.dev)
-        with self.torch.cuda.device(self.dev):
-            _lib.check(entry(K, st["ncon"], st["n"], _lib.ptr(v0), v0.shape[1], st["n_det"], _lib.ptr(v1), v1.shape[1],
-                             st["n_slip"], _lib.ptr(self.maps[ptr]), _lib.ptr(self.maps[lidx]), _lib.ptr(self.maps[other]),
-                             _lib.ptr(x), x.shape[1], _lib.ptr(out), n_out, _lib.current_stream()), name)
-        return list(out.cpu().numpy())
-
     def matvec(self, idx, X):
-        return self._list_matvec(self.lib.rato_csc_matvec_f64, "rato_csc_matvec_f64", idx, X, self.st["ncon"], "row_ptr", "row_idx",
-                                 "row_col")
+        v0, v1, _ = self._sel(idx)
+        return list(csc_matvec(self.st, self.maps, v0, v1, self._up(X)).cpu().numpy())
 
     def tmatvec(self, idx, W):
-        return self._list_matvec(self.lib.rato_csc_tmatvec_f64, "rato_csc_tmatvec_f64", idx, W, self.st["n"], "col_ptr", "col_idx",
-                                 "col_row")
+        v0, v1, _ = self._sel(idx)
+        return list(csc_tmatvec(self.st, self.maps, v0, v1, self._up(W)).cpu().numpy())
 
     def normal_matrix(self, idx, D, diags, with_hess=True, out=None):
         """-> Kc (K, n, lda) device tensor (lower triangle; ``out``: a contiguous (K, n, lda >= n) tensor to write into)"""
-        _lib, st, torch, mp = self._lib, self.st, self.torch, self.maps
         v0, v1, hs = self._sel(idx)
         d, dg = self._up(D), (self._up(diags) if diags is not None else None)
-        K, n = d.shape[0], st["n"]
-        Kc = torch.empty((K, n, n), dtype=torch.float64, device=self.dev) if out is None else out
-        if tuple(Kc.shape[:2]) != (K, n) or Kc.shape[2] < n or Kc.dtype != torch.float64 or not Kc.is_contiguous():
-            raise ValueError(f"out must be a contiguous device float64 tensor ({K}, {n}, >= {n})")
-        with torch.cuda.device(self.dev):
-            _lib.check(self.lib.rato_normal_matrix_f64(
-                K, n, Kc.shape[2], _lib.ptr(v0), v0.shape[1], st["n_det"], _lib.ptr(v1), v1.shape[1], st["n_slip"], _lib.ptr(d), st["ncon"],
-                _lib.ptr(hs if with_hess else None), hs.shape[1] * hs.shape[2], _lib.ptr(dg), _lib.ptr(mp["ent_of"]),
-                _lib.ptr(mp["ptr"]), _lib.ptr(mp["tri_a"]), _lib.ptr(mp["tri_b"]), _lib.ptr(mp["tri_r"]), _lib.ptr(mp["hess_src"]),
-                _lib.ptr(Kc), _lib.current_stream()), "rato_normal_matrix_f64")
-        return Kc
-
-    def factor(self, idx, D, diags):
-        with self.timed("normal"):
-            Kc = self.normal_matrix(idx, D, diags)
-            self._sync()
-        with self.timed("factor"):
-            return self.factor_device(idx, Kc)
-
-    def solve(self, idx, B):
-        with self.timed("solve"):
-            return list(self.solve_device(idx, B))
+        return normal_matrix(self.st["n"], self.st["ncon"], self.maps, v0, v1, d, hs if with_hess else None, dg, out=out)
 
     # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group, takes and returns
-    # (K, ld) tensors, waits for nothing and moves nothing to the host.  ``solve_t`` is DeviceBase's.
+    # (K, ld) tensors, waits for nothing and moves nothing to the host.  ``factor_t`` and ``solve_t`` are DeviceBase's.
     def _g_t(self, Z, r):
         m0 = self.m0
         Cn = m0.nlp_layout()["C"]
@@ -346,28 +368,13 @@ class DeviceBackend(_ipm.DeviceBase):
     def eval_g_t(self, Z):
         return self._g_t(Z, self.m0.nlp_device(Z))
 
-    def _matvec_t(self, entry, name, x, n_in, n_out, ptr, lidx, other):
-        _lib, st, torch = self._lib, self.st, self.torch
-        v0, v1 = self.vals0, self.vals1
-        K = v0.shape[0]
-        if x.dim() != 2 or x.shape[0] != K or x.shape[1] < n_in or x.dtype != torch.float64 or not x.is_contiguous():
-            raise ValueError(f"{name}: the vector must be a contiguous device float64 tensor ({K}, >= {n_in})")
-        out = torch.empty((K, n_out), dtype=torch.float64, device=self.dev)
-        with torch.cuda.device(self.dev):
-            _lib.check(entry(K, st["ncon"], st["n"], _lib.ptr(v0), v0.shape[1], st["n_det"], _lib.ptr(v1), v1.shape[1],
-                             st["n_slip"], _lib.ptr(self.maps[ptr]), _lib.ptr(self.maps[lidx]), _lib.ptr(self.maps[other]),
-                             _lib.ptr(x), x.shape[1], _lib.ptr(out), n_out, _lib.current_stream()), name)
-        return out
-
     def matvec_t(self, X):
         """X (K, ld >= n) -> J x (K, ncon)"""
-        return self._matvec_t(self.lib.rato_csc_matvec_f64, "rato_csc_matvec_f64", X, self.st["n"], self.st["ncon"], "row_ptr",
-                              "row_idx", "row_col")
+        return csc_matvec(self.st, self.maps, self.vals0, self.vals1, X)
 
     def tmatvec_t(self, W):
         """W (K, ld >= ncon) -> J' w (K, n)"""
-        return self._matvec_t(self.lib.rato_csc_tmatvec_f64, "rato_csc_tmatvec_f64", W, self.st["ncon"], self.st["n"], "col_ptr",
-                              "col_idx", "col_row")
+        return csc_tmatvec(self.st, self.maps, self.vals0, self.vals1, W)
 
     def hess_apply_t(self, X):
         """W x of the constraints' part alone (K, n): the objective's sf curv x is added where the result is used
@@ -376,27 +383,7 @@ class DeviceBackend(_ipm.DeviceBase):
 
     def normal_matrix_t(self, d, diag, out=None):
         """d (K, ld >= ncon), diag (K, n) with the objective's curvature already in it -> Kc (K, n, lda)"""
-        _lib, st, torch, mp = self._lib, self.st, self.torch, self.maps
-        v0, v1, hs = self.vals0, self.vals1, self.hessd
-        K, n = v0.shape[0], st["n"]
-        if d.dim() != 2 or d.shape[0] != K or d.shape[1] < st["ncon"] or not d.is_contiguous() or tuple(diag.shape) != (K, n) or \
-                not diag.is_contiguous() or d.dtype != torch.float64 or diag.dtype != torch.float64:
-            raise ValueError(f"d must be a contiguous device float64 tensor ({K}, >= {st['ncon']}) and diag ({K}, {n})")
-        Kc = torch.empty((K, n, n), dtype=torch.float64, device=self.dev) if out is None else out
-        if tuple(Kc.shape[:2]) != (K, n) or Kc.shape[2] < n or Kc.dtype != torch.float64 or not Kc.is_contiguous():
-            raise ValueError(f"out must be a contiguous device float64 tensor ({K}, {n}, >= {n})")
-        with torch.cuda.device(self.dev):
-            _lib.check(self.lib.rato_normal_matrix_f64(
-                K, n, Kc.shape[2], _lib.ptr(v0), v0.shape[1], st["n_det"], _lib.ptr(v1), v1.shape[1], st["n_slip"], _lib.ptr(d),
-                d.shape[1], _lib.ptr(hs), hs.shape[1] * hs.shape[2], _lib.ptr(diag), _lib.ptr(mp["ent_of"]), _lib.ptr(mp["ptr"]),
-                _lib.ptr(mp["tri_a"]), _lib.ptr(mp["tri_b"]), _lib.ptr(mp["tri_r"]), _lib.ptr(mp["hess_src"]), _lib.ptr(Kc),
-                _lib.current_stream()), "rato_normal_matrix_f64")
-        return Kc
-
-    def factor_t(self, d, diag):
-        with self.timed_t("normal"):
-            self.Kc = self.normal_matrix_t(d, diag, out=self.Kc)
-        return self.factor_all(self.Kc)
+        return normal_matrix(self.st["n"], self.st["ncon"], self.maps, self.vals0, self.vals1, d, self.hessd, diag, out=out)
 
 
 def _group_key(m):
@@ -454,15 +441,3 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
 
     return _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, clocks, driver=driver)
 
-
-# ---- former homes.  Code written against the module before it was split (the previous revision's tests among it) reaches
-# these names here; nothing in this tree does.  To be dropped together with the last such caller. -------------------------------
-from .ipm import (STATUSES, Problem, chol_factor, chol_panel_width, chol_solve, kkt_residual,   # noqa: E402,F401
-                  newton_steps)
-
-
-def __getattr__(name):
-    if name in ("arrow_structure", "arrow_terms", "ArrowNumpyBackend", "ArrowDeviceBackend"):   # on demand: it imports this module
-        from . import hopper_arrow
-        return getattr(hopper_arrow, name)
-    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -20,7 +20,9 @@ The driver (``Problem``, ``newton_steps``, ``solve_group``, ``solve_groups``) kn
 x_bounds(), f, grad_f and a backend through name, clock, eval_full / eval_g / matvec / tmatvec / factor / solve /
 hess_apply(idx, X) -> [W x].  It, the line search and the O(n + m) vector algebra run on the host per problem, so a problem's
 iterates do not depend on what else is in the batch.  ``Backend`` / ``DeviceBase`` hold what the backends have in common: the
-clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_solve``: csrc/chol.hip), uploads and row selection.
+clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_solve``: csrc/chol.hip), uploads and row selection,
+and ``factor`` / ``solve`` (``DeviceBase``: ``factor_t`` / ``solve_t`` too) on the normal matrix a subclass provides:
+``normal_matrix_host(i, d, diag)`` on the host, ``normal_matrix(idx, D, diags)`` / ``normal_matrix_t(d, diag, out=)`` on the device.
 
 ``solve_group_device`` (``driver='device'``) is the same method with the iterate on the device: ``DeviceState``
 holds the state of the K problems in HBM, the vector algebra above is csrc/ipm_driver.hip, and the host keeps the branches
@@ -98,16 +100,31 @@ class Backend:
         from scipy.linalg import solve_triangular
         return solve_triangular(self.L[i], solve_triangular(self.L[i], b, lower=True), lower=True, trans='T')
 
+    def factor(self, idx, D, diags):
+        """one problem after the other: ``normal_matrix_host(i, d, diag)`` -> Kc (n, n), the subclass's, then its Cholesky"""
+        info = []
+        for i, d, dg in zip(idx, D, diags):
+            with self.timed("normal"):
+                Kc = self.normal_matrix_host(i, d, dg)
+            with self.timed("factor"):
+                info.append(self.factor_host(i, Kc))
+        return info
+
+    def solve(self, idx, B):
+        with self.timed("solve"):
+            return [self.solve_host(i, b) for i, b in zip(idx, B)]
+
 
 class DeviceBase(Backend):
     """what the device backends share: the uploads, ``slot`` (problem -> row of the current value arrays) and the Cholesky on
-    the device with the factors of all ``n_all`` problems of the group kept in one tensor"""
+    the device with the factors of all ``n_all`` problems of the group kept in one tensor.  ``factor`` / ``solve`` / ``factor_t``
+    stand on the subclass's ``normal_matrix(idx, D, diags)`` and ``normal_matrix_t(d, diag, out=)`` -> Kc (K, n, lda)."""
 
     def __init__(self, dev, n_all, *more_clocks):
         import torch
         super().__init__(*more_clocks)
         self.torch, self.dev, self.n_all = torch, dev, n_all
-        self.slot, self.L = {}, None
+        self.slot, self.L, self.Kc = {}, None, None
 
     def _sync(self):
         self.torch.cuda.synchronize(self.dev)
@@ -139,6 +156,17 @@ class DeviceBase(Backend):
         chol_solve(L, b)
         return b[:, 0].cpu().numpy()
 
+    def factor(self, idx, D, diags):
+        with self.timed("normal"):
+            Kc = self.normal_matrix(idx, D, diags)
+            self._sync()
+        with self.timed("factor"):
+            return self.factor_device(idx, Kc)
+
+    def solve(self, idx, B):
+        with self.timed("solve"):
+            return list(self.solve_device(idx, B))
+
     # ---- for the driver on the device (``solve_group_device``): launches are not waited for
     sync_clocks = False
 
@@ -158,6 +186,12 @@ class DeviceBase(Backend):
             info = chol_factor(Kc)
             self.L = Kc
         return info
+
+    def factor_t(self, d, diag):
+        """the normal matrix of the whole group into the kept ``self.Kc``, factored in place -> info (K,) device tensor"""
+        with self.timed_t("normal"):
+            self.Kc = self.normal_matrix_t(d, diag, out=self.Kc)
+        return self.factor_all(self.Kc)
 
     def solve_t(self, B):
         """L L' x = b in place on B (K, ld >= n), a device tensor, from the factors ``factor_all`` kept"""
@@ -343,6 +377,24 @@ def _max_step(x, dx, has, tau):
     return float(min(1.0, np.min(-tau * x[m] / dx[m])))
 
 
+def _print_iteration(it, rows):
+    """the verbose line of both drivers; a row: (mu, E0, prim, dual, alpha, dw) of one problem"""
+    print("it %4d " % it + " | ".join("mu %.1e E0 %.2e pr %.1e du %.1e a %.1e dw %.0e" % tuple(r) for r in rows))
+
+
+def _results(ps, be, **more):
+    """what both drivers return: [(Z, info)] of the ended Problems; one that never ended ran out of iterations"""
+    out = []
+    for p in ps:
+        if p.status is None:
+            p.status = "max_iter"
+        info = dict(status=p.status, iterations=p.iterations, factorizations=p.factorizations, E0=float(p.E0),
+                    primal_infeasibility=float(p.prim), dual_infeasibility=float(p.dual), f=p.model.f(p.z), mu=p.mu, sf=p.sf,
+                    y=p.y.copy(), zl=p.zl.copy(), zu=p.zu.copy(), s=p.v[p.n:].copy(), backend=be.name, **more)
+        out.append((p.z.copy(), info))
+    return out
+
+
 def solve_group(models, Z0s, tol, max_iter, be, verbose):
     K = len(models)
     all_idx = list(range(K))
@@ -426,17 +478,8 @@ def solve_group(models, Z0s, tol, max_iter, be, verbose):
                     nxt.append((i, p))
             search = nxt
         if verbose:
-            print("it %4d " % it + " | ".join("mu %.1e E0 %.2e pr %.1e du %.1e a %.1e dw %.0e" %
-                                               (p.mu, p.E0, p.prim, p.dual, getattr(p, "alpha", 0.0), p.dw) for p in act))
-    out = []
-    for p in ps:
-        if p.status is None:
-            p.status = "max_iter"
-        info = dict(status=p.status, iterations=p.iterations, factorizations=p.factorizations, E0=float(p.E0),
-                    primal_infeasibility=float(p.prim), dual_infeasibility=float(p.dual), f=p.model.f(p.z), mu=p.mu, sf=p.sf,
-                    y=p.y.copy(), zl=p.zl.copy(), zu=p.zu.copy(), s=p.v[p.n:].copy(), backend=be.name)
-        out.append((p.z.copy(), info))
-    return out
+            _print_iteration(it, [(p.mu, p.E0, p.prim, p.dual, getattr(p, "alpha", 0.0), p.dw) for p in act])
+    return _results(ps, be)
 
 
 # ---- the driver on the device (csrc/ipm_driver.hip) -----------------------------------------------------------------
@@ -512,11 +555,9 @@ class DeviceState:
         self.diag = torch.full((self.K, self.n), float(fill), dtype=torch.float64, device=self.dev)
         self.rec = torch.as_tensor(rec, device=self.dev)
         self.F = F
-        ptr = lambda t: t.data_ptr()
-        self.c_state = _lib.IpmState(self.K, self.n, self.nI, self.m, self.ldv, self.ldm, ptr(self.row_slack),
-                                     *[ptr(getattr(self, k)) for k in ("v", "zl", "zu", "vL", "vU", "curv", "lin", "y", "gL", "rec",
-                                                                      "Sigma", "gbar", "dv", "dzl", "dzu", "vt", "gradf", "rz", "dz",
-                                                                      "ez", "diag", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")])
+        fields = [k for k, _ in _lib.IpmState._fields_]              # the struct's pointers follow ldm, named as the tensors are
+        self.c_state = _lib.IpmState(self.K, self.n, self.nI, self.m, self.ldv, self.ldm,
+                                     *[getattr(self, k).data_ptr() for k in fields[fields.index("ldm") + 1:]])
 
     def _host_vector(self, p, name):
         """what a Problem holds of the named device vector, in the device's layout, or None"""
@@ -666,20 +707,13 @@ def solve_group_device(models, Z0s, tol, max_iter, be, verbose):
                 if not np.any((rec[:, STATUS] == _lib.IPM_RUNNING) & (rec[:, SEARCHING] == 1.0)):
                     break
         if verbose:
-            print("it %4d " % it + " | ".join("mu %.1e E0 %.2e pr %.1e du %.1e a %.1e dw %.0e" % tuple(
-                rec[k, st.F[f]] for f in ("mu", "E0", "prim", "dual", "alpha", "dw")) for k in range(K)))
+            _print_iteration(it, rec[:, [st.F[f] for f in ("mu", "E0", "prim", "dual", "alpha", "dw")]])
         if not np.any(rec[:, STATUS] == _lib.IPM_RUNNING):
             break
     st.download(ps)
-    out = []
     for p, nf in zip(ps, fact):
-        if p.status is None:
-            p.status = "max_iter"
-        info = dict(status=p.status, iterations=p.iterations, factorizations=nf, E0=float(p.E0),
-                    primal_infeasibility=float(p.prim), dual_infeasibility=float(p.dual), f=p.model.f(p.z), mu=p.mu, sf=p.sf,
-                    y=p.y.copy(), zl=p.zl.copy(), zu=p.zu.copy(), s=p.v[p.n:].copy(), backend=be.name, driver='device')
-        out.append((p.z.copy(), info))
-    return out
+        p.factorizations = nf                                        # the device's record does not count them: the host did
+    return _results(ps, be, driver='device')
 
 
 def solve_groups(groups, setup, Z0s, tol, max_iter, verbose, clocks, driver='host'):

@@ -333,6 +333,44 @@ def test_one_newton_step_residual(S, M):
     assert r_dev <= 100.0 * r_np
 
 
+@pytest.mark.parametrize("S,M", [(2, 4), (2, 65)])
+def test_list_methods_on_a_subset_of_the_group(S, M):
+    """"nothing a kernel computes for a problem depends on the others": after one eval_full of the K = 3 problems of a group
+    (alphas differ) at the designed interior iterates of ``_hopper_ipm.newton_residual``, matvec, tmatvec and schur for
+    idx = [2, 0] are bitwise rows 2 and 0 of the calls for idx = [0, 1, 2].  M = 65 crosses one chunk boundary of the sample
+    reduction (32 samples a chunk, two chunks' partials summed), M = 4 stays under it."""
+    import _hopper_nlp as R
+    from riskaversetrajopt_amd import ipm as method
+    m = arrow()
+    flds = H.fields(M)
+    models = [device_model(S, M, 'saa', a, flds) for a in (0.1, 0.2, 0.3)]
+    be = m.ArrowDeviceBackend(models)
+    everyone, sub = list(range(K3)), [2, 0]
+    Z0s = [R.problem(S, M, k) for k in everyone]
+    ps = [method.Problem(mm, Z0, g0, H.TOL) for mm, Z0, g0 in zip(models, Z0s, be.eval_g(everyone, Z0s))]
+    rng = np.random.RandomState(500 + S + M)
+    n, ncon, nc = ps[0].n, ps[0].m, be.st["nc"]
+    lams = list(rng.uniform(-1, 1, (K3, ncon)))
+    be.eval_full(everyone, [p.z.copy() for p in ps], lams, [p.sf for p in ps])
+    X, W = list(rng.randn(K3, n)), list(rng.randn(K3, ncon))
+    D, diags = list(10.0 ** rng.uniform(-3, 3, (K3, ncon))), list(10.0 ** rng.uniform(-3, 3, (K3, n)))
+    pick = lambda rows: [rows[i] for i in sub]
+    low = np.tril(np.ones((nc, nc), dtype=bool))
+
+    def schur(idx, d, dg):
+        Sh, e, _, red, _ = be.schur(idx, d, dg)
+        return np.where(low, Sh.cpu().numpy(), 0.0), e.cpu().numpy(), red
+
+    full = dict(matvec=(np.stack(be.matvec(everyone, X)),), tmatvec=(np.stack(be.tmatvec(everyone, W)),), schur=schur(everyone, D, diags))
+    part = dict(matvec=(np.stack(be.matvec(sub, pick(X))),), tmatvec=(np.stack(be.tmatvec(sub, pick(W))),),
+                schur=schur(sub, pick(D), pick(diags)))
+    assert full["matvec"][0].shape == (K3, ncon) and full["tmatvec"][0].shape == (K3, n) and full["schur"][0].shape == (K3, nc, nc)
+    for name in full:
+        for a, b in zip(full[name], part[name]):
+            assert np.all(np.isfinite(a)), name
+            assert np.ascontiguousarray(a[sub]).tobytes() == b.tobytes(), name
+
+
 @pytest.fixture(scope="module")
 def baseline_small():
     """the S = 6, M = 4 baseline by the device arrow step, and the largest |f_device - f_numpy| of the DENSE step over the
