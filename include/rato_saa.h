@@ -1439,6 +1439,38 @@ int rato_hopper_arrow_edot_f64(int32_t K, int64_t M, const double* e, const doub
 int rato_hopper_arrow_eapply_f64(int32_t K, int64_t M, const double* e, const double* v, const double* kappa, double* out,
                                  void* stream);
 
+/* The fix-ups between the launches above, for the step under the interior-point driver on the device (hopper_arrow.py,
+ * ArrowDeviceBackend's *_t methods): what the list methods do on the host, operation by operation in the host's order (every
+ * product that feeds a sum is rounded on its own), so each output is bitwise the host's line.  ABI: additive.  One lane per
+ * output, no sums over K, no scratch; vectors in z / row / core numbering come with their leading dimension and their padding
+ * is neither read nor written; red is what the named launch left, [K][ldr].
+ * rato_hopper_arrow_scale_f64: out[k][ocol] = a[k] x[k][col] (+ add[k] unless add is NULL).  With a = malpha, col = n - 1, add =
+ *   the red of rows mode 0, ocol = the sum row: the sum row of J x; with a = beta, col = nc - 1: addc of rows mode 1.
+ * rato_hopper_arrow_tfix_f64: after cols mode 0, with tot = -(red[3] + red[8] + ... ) summed contacts ascending from 0:
+ *   out[k][qz[j]] += red[k][j] (j < 5C; qz [5C] the z index of the touched columns, an entry outside [0, n - 2 - M) is skipped),
+ *   out[k][n - 2] += tot, and with saa out[k][n - 1] += malpha[k] w[k][rr] + tot and out[k][n - 2 - M + i] = yout[k][i]
+ *   (yout [K][M] as cols leaves it): J' w in z numbering, n the number of variables, rr the sum row.
+ * rato_hopper_arrow_kkbeta_f64: after reduce, kk[k] = d0 / (1 + d0 s), beta[k] = d0 malpha[k] with d0 = d[k][rr] and s =
+ *   red[k][q (q + 1) / 2 + 2 q] (ldr >= rato_hopper_arrow_npart(C)).
+ * rato_hopper_arrow_einv_f64: out[k][i] = (1 / e[k][i]) (v[k][i] - kk[k] red[k]), red [K] the result of edot; kk NULL: the
+ *   baseline's (1 / e) v.  e [K][M] as reduce leaves it.
+ * rato_hopper_arrow_rhsfix_f64: after cols mode 1, on rc [K][ldrc >= nc] in core numbering: rc[qcol[j]] -= red[j] (j < 5C; an
+ *   entry outside [0, nc - 2) is skipped), rc[nc - 2] -= tot, rc[nc - 1] -= tot + beta[k] red[5C].
+ * RATO_EINVAL without a launch on a NULL or undersized argument, a column outside its array, K outside [1, 65535], M < 1 or C
+ * outside [1, 50]. */
+int rato_hopper_arrow_scale_f64(int32_t K, const double* a /* [K] */, const double* x /* [K][ldx] */, int64_t ldx, int64_t col,
+                                const double* add /* [K] or NULL */, double* out /* [K][ldo] */, int64_t ldo, int64_t ocol,
+                                void* stream);
+int rato_hopper_arrow_tfix_f64(int32_t K, int64_t M, int32_t C, int32_t saa, int64_t n, const int32_t* qz, const double* red,
+                               int64_t ldr, const double* malpha, const double* w, int64_t ldw, int64_t rr, const double* yout,
+                               double* out, int64_t ldo, void* stream);
+int rato_hopper_arrow_kkbeta_f64(int32_t K, int32_t C, const double* d, int64_t ldd, int64_t rr, const double* red, int64_t ldr,
+                                 const double* malpha, double* kk, double* beta, void* stream);
+int rato_hopper_arrow_einv_f64(int32_t K, int64_t M, const double* e, const double* v, int64_t ldv, const double* kk,
+                               const double* red, double* out, int64_t ldo, void* stream);
+int rato_hopper_arrow_rhsfix_f64(int32_t K, int32_t C, int32_t nc, const int32_t* qcol, const double* red, int64_t ldr,
+                                 const double* beta, double* rc, int64_t ldrc, void* stream);
+
 /* ---- The interior-point driver's O(n + m) algebra on a state that stays on the device, fp64 (csrc/ipm_driver.hip): what
  * riskaversetrajopt_amd/ipm.py (Problem, newton_steps, solve_group) does on the host between the launches of a Newton step,
  * restated phase by phase.  ABI: additive (RATO_ABI_VERSION stays 12).  Model independent.  K problems per

@@ -333,6 +333,17 @@ SIGNATURES = {
                                              c_float_p, c_float_p, c_stream]),
     "rato_hopper_arrow_edot_f64": (C.c_int, [C.c_int32, C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
     "rato_hopper_arrow_eapply_f64": (C.c_int, [C.c_int32, C.c_int64, c_float_p, c_float_p, c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_scale_f64": (C.c_int, [C.c_int32, c_float_p, c_float_p, C.c_int64, C.c_int64, c_float_p, c_float_p,
+                                              C.c_int64, C.c_int64, c_stream]),
+    "rato_hopper_arrow_tfix_f64": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, c_float_p, c_float_p,
+                                             C.c_int64, c_float_p, c_float_p, C.c_int64, C.c_int64, c_float_p, c_float_p, C.c_int64,
+                                             c_stream]),
+    "rato_hopper_arrow_kkbeta_f64": (C.c_int, [C.c_int32, C.c_int32, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64,
+                                               c_float_p, c_float_p, c_float_p, c_stream]),
+    "rato_hopper_arrow_einv_f64": (C.c_int, [C.c_int32, C.c_int64, c_float_p, c_float_p, C.c_int64, c_float_p, c_float_p,
+                                             c_float_p, C.c_int64, c_stream]),
+    "rato_hopper_arrow_rhsfix_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p, C.c_int64, c_float_p,
+                                               c_float_p, C.c_int64, c_stream]),
 }
 
 DRONE_METRICS = {"quadratic": 0, "euclidean": 1}     # RATO_DRONE_METRIC_* of include/rato_saa.h

@@ -10,6 +10,8 @@
 //   rato_hopper_arrow_cols_f64      sum_i omega_ic grad_c h_ic: J_risk' w (omega = w) and B_s' t (omega = -t_i d_ic)
 //   rato_hopper_arrow_rows_f64      J_risk v on the risk rows, and B_s x
 //   rato_hopper_arrow_edot_f64 / rato_hopper_arrow_eapply_f64   (1/e)' v and (1/e) o (v - kappa): E^-1 by Sherman-Morrison
+//   rato_hopper_arrow_scale_f64 / _tfix_f64 / _kkbeta_f64 / _einv_f64 / _rhsfix_f64   the O(q + M) fix-ups between those launches
+//                                   on device arrays, for the driver on the device
 //
 // Samples are cut into chunks of AR_CHUNK; a chunk sums its samples ascending into the caller's partials buffer
 // [nchunks][K][n_part], a second launch sums the chunks ascending.  No floating-point atomics, every output has one owner and
@@ -250,6 +252,101 @@ __global__ __launch_bounds__(AR_BLOCK) void arrow_eapply_kernel(int64_t M, const
   out[(int64_t)k * M + i] = (1.0 / e[(int64_t)k * M + i]) * (v[(int64_t)k * M + i] - kappa[k]);
 }
 
+// ---- the sample-axis fix-ups of the step under the driver on the device (ipm.solve_group_device): what ArrowDeviceBackend's list
+// methods do on the host between the launches above, operation by operation in the host's order (__dmul_rn / __dadd_rn /
+// __ddiv_rn wherever a product feeds a sum: the library is built with contraction on).  One lane per output.
+
+// -ffp-contract=fast lets the back end fuse an inlined __dmul_rn into the add that follows it: a product that must stay a
+// product goes through an empty asm statement, which hides where it came from (``unfused`` of driving.hip)
+__device__ __forceinline__ double product(double a, double b) {
+  double x = __dmul_rn(a, b);
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// -sum_c of the fx column sums, contacts ascending
+__device__ __forceinline__ double minus_fx_total(const double* __restrict__ R, int C) {
+  double tot = 0.0;
+  for (int c = 0; c < C; ++c) tot -= R[5 * c + 3];
+  return tot;
+}
+
+// out[k][ocol] = a[k] x[k][col] (+ add[k])
+__global__ __launch_bounds__(AR_BLOCK) void arrow_scale_kernel(int32_t K, const double* __restrict__ a, const double* __restrict__ x,
+                                                               int64_t ldx, int64_t col, const double* __restrict__ add,
+                                                               double* __restrict__ out, int64_t ldo, int64_t ocol) {
+  const int k = blockIdx.x * AR_BLOCK + threadIdx.x;
+  if (k >= K) return;
+  const double prod = product(a[k], x[(int64_t)k * ldx + col]);
+  out[(int64_t)k * ldo + ocol] = add ? __dadd_rn(prod, add[k]) : prod;
+}
+
+// J' w in z numbering after cols mode 0: the touched columns, slack, t_risk and (saa) the y block
+__global__ __launch_bounds__(AR_BLOCK) void arrow_tfix_kernel(int64_t M, int32_t C, int32_t saa, int64_t n,
+                                                              const int32_t* __restrict__ qz, const double* __restrict__ red,
+                                                              int64_t ldr, const double* __restrict__ malpha,
+                                                              const double* __restrict__ w, int64_t ldw, int64_t rr,
+                                                              const double* __restrict__ yout, double* __restrict__ out,
+                                                              int64_t ldo) {
+  const int64_t x = (int64_t)blockIdx.x * AR_BLOCK + threadIdx.x;
+  const int k = blockIdx.y;
+  const int64_t y0 = n - 2 - M;
+  const double* R = red + (int64_t)k * ldr;
+  double* o = out + (int64_t)k * ldo;
+  if (x < 5 * C) {
+    const int64_t z = qz[x];
+    if (z >= 0 && z < y0) o[z] += R[x];
+  } else if (x == 5 * C) {
+    o[n - 2] += minus_fx_total(R, C);
+  } else if (x == 5 * C + 1 && saa) {
+    o[n - 1] += __dadd_rn(product(malpha[k], w[(int64_t)k * ldw + rr]), minus_fx_total(R, C));
+  }
+  if (saa && x < M) o[y0 + x] = yout[(int64_t)k * M + x];
+}
+
+__global__ __launch_bounds__(AR_BLOCK) void arrow_kkbeta_kernel(int32_t K, int32_t C, const double* __restrict__ d, int64_t ldd,
+                                                                int64_t rr, const double* __restrict__ red, int64_t ldr,
+                                                                const double* __restrict__ malpha, double* __restrict__ kk,
+                                                                double* __restrict__ beta) {
+  const int k = blockIdx.x * AR_BLOCK + threadIdx.x;
+  if (k >= K) return;
+  const int q = 5 * C + 2;
+  const double d0 = d[(int64_t)k * ldd + rr], s = red[(int64_t)k * ldr + q * (q + 1) / 2 + 2 * q];
+  kk[k] = __ddiv_rn(d0, __dadd_rn(1.0, product(d0, s)));
+  beta[k] = __dmul_rn(d0, malpha[k]);
+}
+
+// out_i = (1 / e_i) (v_i - kk[k] red[k]); kk NULL: (1 / e_i) v_i
+__global__ __launch_bounds__(AR_BLOCK) void arrow_einv_kernel(int64_t M, const double* __restrict__ e, const double* __restrict__ v,
+                                                              int64_t ldv, const double* __restrict__ kk,
+                                                              const double* __restrict__ red, double* __restrict__ out,
+                                                              int64_t ldo) {
+  const int64_t i = (int64_t)blockIdx.x * AR_BLOCK + threadIdx.x;
+  if (i >= M) return;
+  const int k = blockIdx.y;
+  const double kappa = kk ? product(kk[k], red[k]) : 0.0;
+  out[(int64_t)k * ldo + i] = __dmul_rn(__ddiv_rn(1.0, e[(int64_t)k * M + i]), v[(int64_t)k * ldv + i] - kappa);
+}
+
+// r_c -= B' t after cols mode 1 (core numbering); one workgroup per problem, q <= AR_BLOCK
+static_assert(5 * AR_MAX_C + 2 <= AR_BLOCK, "one lane per touched column");
+__global__ __launch_bounds__(AR_BLOCK) void arrow_rhsfix_kernel(int32_t C, int32_t nc, const int32_t* __restrict__ qcol,
+                                                                const double* __restrict__ red, int64_t ldr,
+                                                                const double* __restrict__ beta, double* __restrict__ rc,
+                                                                int64_t ldrc) {
+  const int x = threadIdx.x, k = blockIdx.x;
+  const double* R = red + (int64_t)k * ldr;
+  double* r = rc + (int64_t)k * ldrc;
+  if (x < 5 * C) {
+    const int col = qcol[x];
+    if (col >= 0 && col < nc - 2) r[col] -= R[x];
+  } else if (x == 5 * C) {
+    r[nc - 2] -= minus_fx_total(R, C);
+  } else if (x == 5 * C + 1) {
+    r[nc - 1] -= __dadd_rn(minus_fx_total(R, C), product(beta[k], R[5 * C]));
+  }
+}
+
 int64_t chunks_of(int64_t M) { return (M + AR_CHUNK - 1) / AR_CHUNK; }
 
 bool shape_ok(int32_t K, int64_t M, int32_t C) {
@@ -352,6 +449,61 @@ extern "C" int rato_hopper_arrow_eapply_f64(int32_t K, int64_t M, const double* 
   RATO_CLEAR_ERROR();
   hipLaunchKernelGGL(arrow_eapply_kernel, dim3((unsigned)((M + AR_BLOCK - 1) / AR_BLOCK), (unsigned)K), dim3(AR_BLOCK), 0,
                      (hipStream_t)stream, M, e, v, kappa, out);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+extern "C" int rato_hopper_arrow_scale_f64(int32_t K, const double* a, const double* x, int64_t ldx, int64_t col, const double* add,
+                                           double* out, int64_t ldo, int64_t ocol, void* stream) {
+  if (K < 1 || K > 65535 || !a || !x || !out || col < 0 || col >= ldx || ocol < 0 || ocol >= ldo) return RATO_EINVAL;
+  RATO_CLEAR_ERROR();
+  hipLaunchKernelGGL(arrow_scale_kernel, dim3((unsigned)((K + AR_BLOCK - 1) / AR_BLOCK)), dim3(AR_BLOCK), 0, (hipStream_t)stream, K, a,
+                     x, ldx, col, add, out, ldo, ocol);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+extern "C" int rato_hopper_arrow_tfix_f64(int32_t K, int64_t M, int32_t C, int32_t saa, int64_t n, const int32_t* qz,
+                                          const double* red, int64_t ldr, const double* malpha, const double* w, int64_t ldw,
+                                          int64_t rr, const double* yout, double* out, int64_t ldo, void* stream) {
+  if (!shape_ok(K, M, C) || n < M + 2 || ldo < n || !qz || !red || ldr < 5 * (int64_t)C + 1 || !out) return RATO_EINVAL;
+  if (saa && (!malpha || !w || !yout || rr < 0 || rr >= ldw)) return RATO_EINVAL;
+  const int64_t work = max((int64_t)5 * C + 2, saa ? M : (int64_t)0);
+  RATO_CLEAR_ERROR();
+  hipLaunchKernelGGL(arrow_tfix_kernel, dim3((unsigned)((work + AR_BLOCK - 1) / AR_BLOCK), (unsigned)K), dim3(AR_BLOCK), 0,
+                     (hipStream_t)stream, M, C, saa ? 1 : 0, n, qz, red, ldr, malpha, w, ldw, rr, yout, out, ldo);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+extern "C" int rato_hopper_arrow_kkbeta_f64(int32_t K, int32_t C, const double* d, int64_t ldd, int64_t rr, const double* red,
+                                            int64_t ldr, const double* malpha, double* kk, double* beta, void* stream) {
+  if (!shape_ok(K, 1, C) || !d || rr < 0 || rr >= ldd || !red || ldr < rato_hopper_arrow_npart(C) || !malpha || !kk || !beta)
+    return RATO_EINVAL;
+  RATO_CLEAR_ERROR();
+  hipLaunchKernelGGL(arrow_kkbeta_kernel, dim3((unsigned)((K + AR_BLOCK - 1) / AR_BLOCK)), dim3(AR_BLOCK), 0, (hipStream_t)stream, K,
+                     C, d, ldd, rr, red, ldr, malpha, kk, beta);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+extern "C" int rato_hopper_arrow_einv_f64(int32_t K, int64_t M, const double* e, const double* v, int64_t ldv, const double* kk,
+                                          const double* red, double* out, int64_t ldo, void* stream) {
+  if (!shape_ok(K, M, 1) || !e || !v || ldv < M || (kk && !red) || !out || ldo < M) return RATO_EINVAL;
+  RATO_CLEAR_ERROR();
+  hipLaunchKernelGGL(arrow_einv_kernel, dim3((unsigned)((M + AR_BLOCK - 1) / AR_BLOCK), (unsigned)K), dim3(AR_BLOCK), 0,
+                     (hipStream_t)stream, M, e, v, ldv, kk, red, out, ldo);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+
+extern "C" int rato_hopper_arrow_rhsfix_f64(int32_t K, int32_t C, int32_t nc, const int32_t* qcol, const double* red, int64_t ldr,
+                                            const double* beta, double* rc, int64_t ldrc, void* stream) {
+  if (!shape_ok(K, 1, C) || nc < 5 * C + 2 || !qcol || !red || ldr < 5 * (int64_t)C + 1 || !beta || !rc || ldrc < nc)
+    return RATO_EINVAL;
+  RATO_CLEAR_ERROR();
+  hipLaunchKernelGGL(arrow_rhsfix_kernel, dim3((unsigned)K), dim3(AR_BLOCK), 0, (hipStream_t)stream, C, nc, qcol, red, ldr, beta, rc,
+                     ldrc);
   RATO_LAUNCH_CHECK();
   return RATO_OK;
 }

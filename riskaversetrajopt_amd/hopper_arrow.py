@@ -4,6 +4,8 @@ they are eliminated exactly and the Cholesky factors the core's Schur complement
 test, since e > 0.  ``ArrowDeviceBackend`` does the work over the samples with csrc/hopper_arrow.hip on the partials
 rato_hopper_slip_f64 leaves and the deterministic rows with ``hopper_ipm``'s ``normal_matrix`` / ``csc_matvec`` / ``csc_tmatvec`` on
 the core's pattern; ``ArrowNumpyBackend`` is its host twin.  Both keep their own factor and solve (the elimination).
+Under ``driver='device'`` ``ArrowDeviceBackend`` serves device tensors: its ``*_t`` methods do the same step
+without a read-back, the host-side fix-ups of the list methods being kernels of csrc/hopper_arrow.hip.
 """
 import time
 
@@ -11,8 +13,9 @@ import numpy as np
 
 from . import hopper as _h
 from . import ipm as _ipm
-from .hopper_ipm import (ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, assemble_g, csc_matvec, csc_tmatvec, normal_matrix,
-                         normal_matrix_host, upload_maps)
+from .hopper_ipm import (ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, arrow_einv, arrow_kkbeta, arrow_rhsfix, arrow_scale,
+                         arrow_tfix, assemble_g, csc_matvec, csc_tmatvec, normal_matrix, normal_matrix_host, scatter_rows,
+                         upload_maps)
 
 
 def arrow_structure(model):
@@ -24,7 +27,9 @@ def arrow_structure(model):
       det                ``_pattern_maps`` of the deterministic rows on the core columns (value index = position in
                          ``nlp_layout()``'s det values; ent_of is n_c x n_c whatever M is)
       det_rows, det_cols_z   the deterministic pattern as coordinate lists in z numbering
-      pos_det, pos_slip  where the two value arrays lie in the full pattern (the NumPy twin splits injected values with them)"""
+      pos_det, pos_slip  where the two value arrays lie in the full pattern (the NumPy twin splits injected values with them)
+      inv_qz (n,), inv_core_z (n,), inv_qcol (nc,)   the inverse maps of qz, core_z and qcol (-1: the column has no target): what
+                         rato_scatter_f64 takes to gather x[qz], z[core_z] and xc[qcol] on the device"""
     st = getattr(model, "_ipm_arrow", None)
     if st is not None:
         return st
@@ -51,6 +56,11 @@ def arrow_structure(model):
               pos_det=np.asarray(lay["pos_det"]), pos_slip=np.asarray(lay["pos_slip"]),
               hess=dict(n=n, block_vars=det["block_vars"].copy()))
     st["hess"]["block_vars"][st["hess"]["block_vars"] == nc] = n
+    for name, fwd, size in (("inv_qz", st["qz"], n), ("inv_core_z", core_z, n), ("inv_qcol", qcol, nc)):
+        assert np.unique(fwd).size == fwd.size
+        inv = -np.ones(size, dtype=np.int64)
+        inv[fwd] = np.arange(fwd.size)
+        st[name] = inv
     model._ipm_arrow = st
     return st
 
@@ -224,7 +234,8 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     """The arrowhead step on the MI355X for the problems of one group (csrc/hopper_arrow.hip on the partials rato_hopper_slip_f64
     leaves in HBM; the core through ``hopper_ipm.normal_matrix`` on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).
     eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels to the
-    host per call is the vectors the driver works on and O(q) sums."""
+    host per call of a list method is the vectors the driver works on and O(q) sums; the ``*_t`` methods (the driver on the
+    device) move nothing."""
     name, newton = "device", "arrow"
 
     def __init__(self, models):
@@ -442,3 +453,134 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
             out[:, st["core_z"]] = xch
             out[:, st["y0"]:st["y0"] + M] = ry.cpu().numpy()
         return list(out)
+
+    # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group, takes and
+    # returns (K, ld) tensors, waits for nothing and moves nothing to the host.  What the list methods fix up on the host is done
+    # by the ``arrow_*`` bindings of ``hopper_ipm`` (bitwise the host's lines); gathers and scatters between z numbering, core
+    # numbering and the touched columns go through rato_scatter_f64 with the maps of ``arrow_structure``.
+    def _work(self):
+        """the work buffers of the group and the uploaded maps, made once"""
+        w = getattr(self, "_w", None)
+        if w is None:
+            st, K, torch = self.st, self.n_all, self.torch
+            M, q, nc = st["M"], st["q"], st["nc"]
+            up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
+            w = self._w = dict(
+                xq=self._empty(K, q), xy=self._empty(K, M), yout=self._empty(K, M), dg=self._empty(K, nc), yd=self._empty(K, M),
+                rc=self._empty(K, nc), ry=self._empty(K, M), t=self._empty(K, M), rem=self._empty(K, M), addc=self._empty(K),
+                part1=self._empty(self.nch, K), red1=self._empty(K), partc=self._empty(self.nch, K, 5 * st["C"] + 1),
+                redc=self._empty(K, 5 * st["C"] + 1), partr=self._empty(self.nch, K, self.npart), redr=self._empty(K, self.npart),
+                kk=self._empty(K), beta=self._empty(K), malpha=self._up([self._malpha(range(K))])[0].contiguous(),
+                add=self._empty(K, self.m0.S + 1, _h.n_pairs), qz=up(st["qz"], np.int32), core_z=up(st["core_z"], np.int64),
+                inv_qz=up(st["inv_qz"], np.int64), inv_core_z=up(st["inv_core_z"], np.int64), inv_qcol=up(st["inv_qcol"], np.int64))
+        return w
+
+    def _g_t(self, Z, lin, h):
+        m0, st = self.m0, self.st
+        return _h.g_device(m0._slip_params(), st["M"], st["saa"], Z, lin["defect"], lin["rows"], h, (1, st["M"]),
+                           self._work()["malpha"])
+
+    def eval_full_t(self, Z, Y):
+        """Z (K, n) and the multipliers Y (K, ld >= ncon), read where they lie -> g (K, ncon); leaves the deterministic rows'
+        values, the slip partials and the step blocks of hess(Y . g) for the calls below.  The objective's curvature is NOT in the
+        blocks: the driver's diagonal carries it."""
+        m0, mp, w, K = self.m0, self.maps, self._work(), Z.shape[0]
+        lin = _h.nlp_linearize_device(self.params, Z)
+        jac = mp["det_const"][None].repeat(K, 1).contiguous()
+        _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
+        _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
+        slip = m0.slip_device_f64(Z, Y[:, :self.st["ncon"]], want=("h", "dh_dfz", "dh_dx"))
+        add = w["add"].zero_()
+        m0.slip_hess_blocks_device_f64(Z, slip["D"], add)
+        lam_dyn, lam_rows = m0.fold_multipliers_device(Y)
+        self.hessd = _h.nlp_hessian_device(self.params, Z, lam_dyn, lam_rows, add)
+        self.vals0, self.dx, self.dfz = jac, slip["dh_dx"], slip["dh_dfz"]
+        self.slot = {i: i for i in range(K)}
+        return self._g_t(Z, lin, slip["h"])
+
+    def eval_g_t(self, Z):
+        lin = _h.nlp_linearize_device(self.params, Z, want=("defect", "rows"))
+        return self._g_t(Z, lin, self.m0.slip_device_f64(Z, want=("h",))["h"])
+
+    def hess_apply_t(self, X):
+        """W x of the constraints' part alone (K, n)"""
+        return _h.block_symv(self.m0.S, self.hessd, X, self.st["n"])
+
+    def matvec_t(self, X):
+        """X (K, ld >= n) -> J x (K, ncon)"""
+        with self.timed_t("products"):
+            st, w, p = self.st, self._work(), self._lib.ptr
+            M, Cn, n, K = st["M"], st["C"], st["n"], X.shape[0]
+            out = csc_matvec(st, self.maps, self.vals0, None, X)
+            xq = scatter_rows(X, n, w["inv_qz"], w["xq"], st["q"])
+            xy = w["xy"].copy_(X[:, st["y0"]:st["y0"] + M])
+            self._call("rato_hopper_arrow_rows_f64", K, M, Cn, int(st["saa"]), 0, p(self.dx), p(self.dfz), p(xq), p(xy), None, 0,
+                       st["r0"], None, p(out), st["ncon"], p(w["part1"]), p(w["red1"]))
+            if st["saa"]:
+                arrow_scale(w["malpha"], X, n - 1, w["red1"], out, st["rr"])
+        return out
+
+    def tmatvec_t(self, W):
+        """W (K, ld >= ncon) -> J' w (K, n)"""
+        with self.timed_t("products"):
+            st, w, p = self.st, self._work(), self._lib.ptr
+            M, Cn, K = st["M"], st["C"], W.shape[0]
+            out = csc_tmatvec(st, self.maps, self.vals0, None, W)
+            self._call("rato_hopper_arrow_cols_f64", K, M, Cn, int(st["saa"]), 0, p(self.dx), p(self.dfz), p(W), W.shape[1], st["r0"],
+                       None, p(w["yout"]), p(w["partc"]), p(w["redc"]))
+            arrow_tfix(M, Cn, st["saa"], st["n"], w["qz"], w["redc"], w["malpha"], W, st["rr"], w["yout"], out)
+        return out
+
+    def factor_t(self, d, diag):
+        """d (K, ld >= ncon) and diag (K, n) with the objective's curvature already in it: the core's Schur complement into the
+        kept ``self.Kc`` (normal_matrix on the core pattern, reduce, assemble), factored in place -> info (K,) int32 device tensor.
+        e, kk and beta stay on the device; ``d`` is kept by reference for ``solve_t``."""
+        st, mp, w, p = self.st, self.maps, self._work(), self._lib.ptr
+        M, Cn, nc, K = st["M"], st["C"], st["nc"], d.shape[0]
+        with self.timed_t("normal"):
+            dg = scatter_rows(diag, st["n"], w["inv_core_z"], w["dg"], nc)
+            yd = w["yd"].copy_(diag[:, st["y0"]:st["y0"] + M])
+            self.Kc = normal_matrix(nc, st["ncon"], mp, self.vals0, None, d, self.hessd, dg, out=self.Kc)
+        with self.timed_t("reduction"):
+            self._call("rato_hopper_arrow_reduce_f64", K, M, Cn, int(st["saa"]), p(self.dx), p(self.dfz), p(d), d.shape[1], st["r0"],
+                       p(yd), p(self.e), p(w["partr"]), p(w["redr"]))
+        with self.timed_t("assembly"):
+            self._call("rato_hopper_arrow_assemble_f64", K, M, Cn, int(st["saa"]), nc, self.Kc.shape[2], p(mp["qcol"]), p(w["redr"]),
+                       p(d), d.shape[1], st["r0"], p(w["malpha"]), p(self.Kc))
+            if st["saa"]:
+                arrow_kkbeta(Cn, d, st["rr"], w["redr"], w["malpha"], w["kk"], w["beta"])
+            self.d_t = d
+        return self.factor_all(self.Kc)
+
+    def _einv_t(self, v, out):
+        """E^-1 v for (K, >= M) device tensors into ``out``: kappa is formed on the device"""
+        w, p = self._work(), self._lib.ptr
+        K, M = v.shape[0], self.st["M"]
+        if not self.st["saa"]:
+            return arrow_einv(self.e, v, None, None, out)
+        self._call("rato_hopper_arrow_edot_f64", K, M, p(self.e), p(v), p(w["part1"]), p(w["red1"]))
+        return arrow_einv(self.e, v, w["kk"], w["red1"], out)
+
+    def solve_t(self, B):
+        """the elimination in place on B (K, ld >= n) in z numbering, from what ``factor_t`` kept"""
+        with self.timed_t("solve"):
+            st, w, p = self.st, self._work(), self._lib.ptr
+            M, Cn, nc, n, K, y0 = st["M"], st["C"], st["nc"], st["n"], B.shape[0], st["y0"]
+            d = self.d_t
+            rc = scatter_rows(B, n, w["inv_core_z"], w["rc"], nc)
+            ry = w["ry"].copy_(B[:, y0:y0 + M])
+            if st["saa"]:
+                t = self._einv_t(ry, w["t"])
+                self._call("rato_hopper_arrow_cols_f64", K, M, Cn, 1, 1, p(self.dx), p(self.dfz), p(d), d.shape[1], st["r0"], p(t),
+                           None, p(w["partc"]), p(w["redc"]))
+                arrow_rhsfix(Cn, nc, self.maps["qcol"], w["redc"], w["beta"], rc)
+            _ipm.chol_solve(self.L, rc[:, None, :])
+            if st["saa"]:
+                xq = scatter_rows(rc, nc, w["inv_qcol"], w["xq"], st["q"])
+                arrow_scale(w["beta"], rc, nc - 1, None, w["addc"], 0)
+                self._call("rato_hopper_arrow_rows_f64", K, M, Cn, 1, 1, p(self.dx), p(self.dfz), p(xq), p(ry), p(d), d.shape[1],
+                           st["r0"], p(w["addc"]), p(w["rem"]), M, None, None)
+                ry = w["rem"]
+            self._einv_t(ry, B[:, y0:y0 + M])
+            scatter_rows(rc, nc, w["core_z"], B, n)
+        return B

@@ -12,7 +12,8 @@ kernels of csrc/hopper_ipm.hip are bound once, as ``normal_matrix``, ``csc_matve
 driver='device' (``ipm.solve_group_device``) keeps the iterate in HBM: the device backend then serves device
 tensors (eval_full_t ... normal_matrix_t below), g is assembled by rato_hopper_g_f64, W x is rato_hopper_block_symv_f64 and the
 multipliers are folded by rato_scatter_f64 (csrc/hopper_g.hip, ``Model.fold_multipliers_device``); nothing but the scalar
-record and the factorization's info comes back during an iteration.
+record and the factorization's info comes back during an iteration.  Both Newton steps are served: the arrow backend's
+host-side fix-ups are the ``arrow_*`` bindings below.
 
 newton='arrow' (``hopper_arrow``) is the same step for any M: the M variables ys are eliminated exactly and the
 Cholesky factors the core's Schur complement; newton='dense' (the default) is the step over all variables.
@@ -273,6 +274,108 @@ def normal_matrix(n, ncon, maps, v0, v1, d, hess, diag, out=None):
     return Kc
 
 
+# ---- the fix-up kernels of csrc/hopper_arrow.hip on device fp64 tensors (``hopper_arrow.ArrowDeviceBackend`` on tensors): a 2-D
+# argument is (K, >= cols) with contiguous rows -- a column range of a wider tensor is fine, its row stride is the ld
+def _rows_ld(t, K, cols, name, dtype=torch.float64):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != K or t.shape[1] < cols or t.dtype != dtype or not t.is_cuda \
+            or t.stride(1) != 1 or (K > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name} must be a device {str(dtype).split('.')[-1]} tensor ({K}, >= {cols}) with contiguous rows")
+    return t.stride(0) if K > 1 else max(t.stride(0), t.shape[1])
+
+
+def _per_problem(K, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (K,) or t.dtype != torch.float64 or not t.is_cuda
+                              or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous device float64 tensor ({K},)")
+
+
+def _index_list(t, length, name, dtype=torch.int32):
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.shape[0] < length or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous device {str(dtype).split('.')[-1]} tensor (>= {length},)")
+
+
+def _launch(dev, name, *args):
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.load(), name)(*args, _lib.current_stream()), name)
+
+
+def scatter_rows(src, n, index_map, dst, n_dst):
+    """rato_scatter_f64 between padded tensors: dst[k][map[i]] = src[k][i] for i < n; map (n,) device int64, an entry outside
+    [0, n_dst) is not emitted (a gather takes the inverse map, -1 where a column has no target).  What the map does not point at
+    is left alone."""
+    K = src.shape[0]
+    ld_src, ld_dst = _rows_ld(src, K, n, "src"), _rows_ld(dst, K, n_dst, "dst")
+    _index_list(index_map, n, "map", torch.int64)
+    if index_map.shape[0] != n:
+        raise ValueError(f"map must hold {n} entries")
+    _launch(src.device, "rato_scatter_f64", K, n, _lib.ptr(src), ld_src, _lib.ptr(index_map), None, _lib.ptr(dst), ld_dst, n_dst)
+    return dst
+
+
+def arrow_scale(a, x, col, add, out, ocol):
+    """rato_hopper_arrow_scale_f64: out[k][ocol] = a[k] x[k][col] (+ add[k]); out 1-D (K,): out[k]"""
+    K = a.shape[0]
+    _per_problem(K, a=a, add=add)
+    o2 = out[:, None] if out.dim() == 1 else out
+    ldx, ldo = _rows_ld(x, K, col + 1, "x"), _rows_ld(o2, K, ocol + 1, "out")
+    if col < 0 or ocol < 0:
+        raise ValueError("col and ocol must not be negative")
+    _launch(x.device, "rato_hopper_arrow_scale_f64", K, _lib.ptr(a), _lib.ptr(x), ldx, col, _lib.ptr(add), _lib.ptr(o2), ldo, ocol)
+    return out
+
+
+def arrow_tfix(M, Cn, saa, n, qz, red, malpha, w, rr, yout, out):
+    """rato_hopper_arrow_tfix_f64: finishes J' w (K, >= n) in z numbering from the red (K, >= 5C + 1) and yout (K, M) of cols mode 0"""
+    K = out.shape[0]
+    ldo, ldr = _rows_ld(out, K, n, "out"), _rows_ld(red, K, 5 * Cn + 1, "red")
+    _index_list(qz, 5 * Cn, "qz")
+    ldw = 0
+    if saa:
+        ldw = _rows_ld(w, K, rr + 1, "w")
+        _per_problem(K, malpha=malpha)
+        if malpha is None or _rows_ld(yout, K, M, "yout") != M:
+            raise ValueError(f"saa: malpha ({K},) and a contiguous yout ({K}, {M})")
+    _launch(out.device, "rato_hopper_arrow_tfix_f64", K, M, Cn, int(bool(saa)), n, _lib.ptr(qz), _lib.ptr(red), ldr,
+            _lib.ptr(malpha if saa else None), _lib.ptr(w if saa else None), ldw, rr if saa else 0, _lib.ptr(yout if saa else None),
+            _lib.ptr(out), ldo)
+    return out
+
+
+def arrow_kkbeta(Cn, d, rr, red, malpha, kk, beta):
+    """rato_hopper_arrow_kkbeta_f64: kk = d0 / (1 + d0 s), beta = d0 malpha from d (K, > rr) and the red (K, >= n_part) of reduce"""
+    K = d.shape[0]
+    _per_problem(K, malpha=malpha, kk=kk, beta=beta)
+    q = 5 * Cn + 2
+    ldd, ldr = _rows_ld(d, K, rr + 1, "d"), _rows_ld(red, K, q * (q + 1) // 2 + 2 * q + 1 + 15 * Cn, "red")
+    _launch(d.device, "rato_hopper_arrow_kkbeta_f64", K, Cn, _lib.ptr(d), ldd, rr, _lib.ptr(red), ldr, _lib.ptr(malpha), _lib.ptr(kk),
+            _lib.ptr(beta))
+
+
+def arrow_einv(e, v, kk, red, out):
+    """rato_hopper_arrow_einv_f64: out = (1 / e) o (v - kk red) for e (K, M) contiguous, v and out (K, >= M), kk and red (K,) (both
+    None: (1 / e) o v, the baseline's)"""
+    K, M = e.shape
+    if _rows_ld(e, K, M, "e") != M:
+        raise ValueError(f"e must be a contiguous device float64 tensor ({K}, {M})")
+    _per_problem(K, kk=kk, red=red)
+    if (kk is None) != (red is None):
+        raise ValueError("kk and red come together")
+    ldv, ldo = _rows_ld(v, K, M, "v"), _rows_ld(out, K, M, "out")
+    _launch(e.device, "rato_hopper_arrow_einv_f64", K, M, _lib.ptr(e), _lib.ptr(v), ldv, _lib.ptr(kk), _lib.ptr(red), _lib.ptr(out), ldo)
+    return out
+
+
+def arrow_rhsfix(Cn, nc, qcol, red, beta, rc):
+    """rato_hopper_arrow_rhsfix_f64: rc (K, >= nc, core numbering) -= B' t from the red (K, >= 5C + 1) of cols mode 1"""
+    K = rc.shape[0]
+    _per_problem(K, beta=beta)
+    _index_list(qcol, 5 * Cn, "qcol")
+    ldrc, ldr = _rows_ld(rc, K, nc, "rc"), _rows_ld(red, K, 5 * Cn + 1, "red")
+    _launch(rc.device, "rato_hopper_arrow_rhsfix_f64", K, Cn, nc, _lib.ptr(qcol), _lib.ptr(red), ldr, _lib.ptr(beta), _lib.ptr(rc), ldrc)
+    return rc
+
+
 class DeviceBackend(_ipm.DeviceBase):
     """the step on the MI355X for the problems of one group (same S, M, phases, method and friction fields; alpha may differ).
     Every call serves the listed problems in ONE launch each; nothing a kernel computes for a problem depends on the others."""
@@ -406,8 +509,9 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
                  script's M = 30); 'arrow': the M sample variables ys are eliminated exactly and the 8(S+1) + 4S + 2 core is
                  factored (``hopper_arrow``): memory and work are O(M C), for any M
       driver     'host' (``ipm.solve_group``: the iterate and the vector algebra on the host) or 'device'
-                 (``ipm.solve_group_device``, backend='device' and newton='dense' only: the iterate stays on the device,
-                 csrc/ipm_driver.hip and csrc/hopper_g.hip, and the clocks hold the time to launch; info["driver"] = 'device')
+                 (``ipm.solve_group_device``, backend='device' only: the iterate stays on the device, csrc/ipm_driver.hip and
+                 csrc/hopper_g.hip, and the clocks hold the time to launch; info["driver"] = 'device'.  With newton='arrow' the
+                 models must be on a GPU with precision='f64')
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
     dual_infeasibility, f, and the final multipliers y, zl, zu with the slacks s and the objective scale sf."""
     if backend not in ('device', 'numpy'):
@@ -415,11 +519,12 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
     if newton not in ('dense', 'arrow'):
         raise ValueError(f"newton must be 'dense' or 'arrow', got {newton!r}")
     _ipm.check_driver(driver, backend)
-    if driver == 'device' and newton == 'arrow':
-        raise ValueError("driver='device' serves the dense Newton step: the arrow backend (newton='arrow') is not yet served")
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
+    if driver == 'device' and newton == 'arrow' and any(m.device.type != 'cuda' or m.precision != 'f64' for m in models):
+        raise ValueError("newton='arrow' under driver='device' works on the partials the fp64 slip kernel leaves on the device: "
+                         "every model needs a GPU and precision='f64'")
     Z0s = [m.initial_guess() for m in models] if Z0s is None else [np.asarray(Z, dtype=np.float64) for Z in Z0s]
     if len(Z0s) != len(models) or any(Z.shape != (m.num_vars,) for Z, m in zip(Z0s, models)):
         raise ValueError("Z0s must hold one (num_vars,) vector per model")

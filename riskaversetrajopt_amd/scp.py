@@ -749,8 +749,8 @@ def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device', newton
     """The hopper script's solve block (hopper.py:642-670) for one model: ``hopper_ipm.solve_batch`` in IPOPT's place, from
     ``Z0`` (default ``model.initial_guess()``) -> dict(Z, xs (S+1, 8), us (S, 4), status, info, total_s).  status is
     'converged' only if the final error E_0 <= tol shows it.  newton: 'dense' or 'arrow' (``hopper_ipm.solve_batch``).
-    ``driver``: 'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device',
-    newton='dense')."""
+    ``driver``: 'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either
+    newton, 'arrow' with a precision='f64' model)."""
     t0 = time.perf_counter()
     Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend, newton=newton, driver=driver)
     xs, us = model.convert_z_to_xs_us_mats(Z)
@@ -789,7 +789,7 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
     solution (:465-479).  With ``results_dir`` the files hopper_base_results.npy and hopper_saa_alpha=<a>_results.npy are
     written (xs then us, ``save_results``), whatever the status.  ``fields``: (intensities, thetas, taus), each (M, 30), in place
     of the draw; ``newton``: 'dense' or 'arrow' (``hopper_ipm.solve_batch``: 'arrow' is the one that scales with M); ``driver``:
-    'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', newton='dense').
+    'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either newton).
     -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)"""
     from . import hopper, hopper_ipm
     alphas = [float(a) for a in alphas]

@@ -19,8 +19,10 @@ every solution's safe fraction and AVaR on the script's 10 000 validation fields
 on the same stream, hopper.py:974-979); and at M = 30 the dense step in the same process.  The file is rewritten after every M,
 and a later call with other M adds them to it.
 
-``--driver host|device|both`` measures the dense solve under the interior-point driver on the host and / or on the device
-(``solve_batch(driver=...)``) instead, into profiles/hopper_solve_device_driver.json: the baseline from
+``--driver host|device|both`` measures the solve under the interior-point driver on the host and / or on the device
+(``solve_batch(driver=...)``) instead, into profiles/hopper_solve_device_driver.json -- or, with ``--newton
+arrow --M 30,1000,10000``, per M into profiles/hopper_solve_large_m_device_driver.json (the training fields of ``--newton
+arrow``; the file is rewritten after every M): the baseline from
 ``initial_guess()``, then the alphas as one batch from the HOST driver's baseline solution (both drivers solve the same
 problems from the same starts); per run and driver the problems' iterations and factorizations, the wall clock of ``--solves``
 solves after a warm-up (ms per batch, ms per lockstep iteration), the clocks' split of one more solve as it is (the time to
@@ -137,73 +139,94 @@ def main_arrow(args):
     print(json.dumps(out))
 
 
-def driver_bench(args):
-    """the script's two runs under the host and / or the device driver -> profiles/hopper_solve_device_driver.json"""
+def measure_drivers(models, Z0s, newton, drivers, solves, S):
+    """one run (a batch of problems from fixed starts) under each driver -> its record in the profile"""
     import time
 
     import torch
-    from riskaversetrajopt_amd import hopper, hopper_ipm, ipm, scp
-    S, M, alphas = args.S, int(args.M), [float(a) for a in args.alphas]
-    fields = hopper.sample_friction_fields(M, np.random.RandomState(1))
-    mk = lambda method, a: hopper.Model(M, method, a, S=S, fields=fields, precision='f64')
-    base = mk('baseline', 0.1)
-    (Zb, _), = hopper_ipm.solve_batch([base])                        # the host driver's baseline: everyone's SAA start
-    xs, us = base.convert_z_to_xs_us_mats(Zb)
-    saa = [mk('saa', a) for a in alphas]
-    runs = {"baseline": ([base], [base.initial_guess()]), "saa": (saa, [scp.hopper_saa_start(m, xs, us) for m in saa])}
-    out = {"device": torch.cuda.get_device_name(0), "S": S, "M": M, "alphas": alphas, "tol": 1e-3, "max_iter": 3000,
-           "newton": "dense", "solves": args.solves, "saa_start": "the host driver's baseline solution", "runs": {}}
-    drivers = ("host", "device") if args.driver == "both" else (args.driver,)
-    for name, (models, Z0s) in runs.items():
-        if not models:
-            continue
-        rec = {}
-        solve = lambda d, ck=None: hopper_ipm.solve_batch(models, Z0s, driver=d, clocks=ck)
-        for d in drivers:
-            solve(d)                                                 # warm-up: code objects, maps, allocator
-            torch.cuda.synchronize()
-            walls = []
-            for _ in range(args.solves):
-                t0 = time.perf_counter()
-                sols = solve(d)
-                walls.append(time.perf_counter() - t0)
-            rounds = max(1, max(info["iterations"] for _, info in sols))
-            launch = {}
-            solve(d, launch)
-            synced = {}
-            ipm.DeviceBase.sync_clocks = True                        # one more solve, a device-wide wait behind every block
-            try:
-                solve(d, synced)
-            finally:
-                ipm.DeviceBase.sync_clocks = False
-            copies, cpu = [0], torch.Tensor.cpu
+    from riskaversetrajopt_amd import hopper_ipm, ipm
+    rec = {}
+    solve = lambda d, ck=None: hopper_ipm.solve_batch(models, Z0s, driver=d, clocks=ck, newton=newton)
+    for d in drivers:
+        solve(d)                                                     # warm-up: code objects, maps, allocator
+        torch.cuda.synchronize()
+        walls = []
+        for _ in range(solves):
+            t0 = time.perf_counter()
+            sols = solve(d)
+            walls.append(time.perf_counter() - t0)
+        rounds = max(1, max(info["iterations"] for _, info in sols))
+        launch = {}
+        solve(d, launch)
+        synced = {}
+        ipm.DeviceBase.sync_clocks = True                            # one more solve, a device-wide wait behind every block
+        try:
+            solve(d, synced)
+        finally:
+            ipm.DeviceBase.sync_clocks = False
+        copies, cpu = [0], torch.Tensor.cpu
 
-            def counting(self, *a, **kw):
-                copies[0] += 1
-                return cpu(self, *a, **kw)
-            torch.Tensor.cpu = counting
-            try:
-                solve(d)
-            finally:
-                torch.Tensor.cpu = cpu
-            per_it = lambda ck: {k: 1e3 * v / rounds for k, v in ck.items()}
-            rec[d] = {"wall_ms": [1e3 * w for w in walls], "median_ms_per_batch": 1e3 * float(np.median(walls)),
-                      "lockstep_iterations": rounds, "median_ms_per_iteration": 1e3 * float(np.median(walls)) / rounds,
-                      "problems": [{"method": m.method, "alpha": float(m.alpha), "status": info["status"],
-                                    "iterations": int(info["iterations"]), "factorizations": int(info["factorizations"]),
-                                    "E0": float(info["E0"]), "f": float(info["f"]), "x_S0": float(Z[8 * S])}
-                                   for m, (Z, info) in zip(models, sols)],
-                      "split_ms_per_iteration": per_it(launch), "split_ms_per_iteration_sync_clocks": per_it(synced),
-                      "device_to_host_copies_per_iteration": copies[0] / rounds}
-        if len(drivers) == 2:
-            rec["host_over_device"] = rec["host"]["median_ms_per_batch"] / rec["device"]["median_ms_per_batch"]
-        out["runs"][name] = rec
+        def counting(self, *a, **kw):
+            copies[0] += 1
+            return cpu(self, *a, **kw)
+        torch.Tensor.cpu = counting
+        try:
+            solve(d)
+        finally:
+            torch.Tensor.cpu = cpu
+        per_it = lambda ck: {k: 1e3 * v / rounds for k, v in ck.items()}
+        rec[d] = {"wall_ms": [1e3 * w for w in walls], "median_ms_per_batch": 1e3 * float(np.median(walls)),
+                  "lockstep_iterations": rounds, "median_ms_per_iteration": 1e3 * float(np.median(walls)) / rounds,
+                  "problems": [{"method": m.method, "alpha": float(m.alpha), "status": info["status"],
+                                "iterations": int(info["iterations"]), "factorizations": int(info["factorizations"]),
+                                "E0": float(info["E0"]), "f": float(info["f"]), "x_S0": float(Z[8 * S])}
+                               for m, (Z, info) in zip(models, sols)],
+                  "split_ms_per_iteration": per_it(launch), "split_ms_per_iteration_sync_clocks": per_it(synced),
+                  "device_to_host_copies_per_iteration": copies[0] / rounds}
+    if len(drivers) == 2:
+        rec["host_over_device"] = rec["host"]["median_ms_per_batch"] / rec["device"]["median_ms_per_batch"]
+    return rec
+
+
+def write_profile(out, path):
     line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
             f.write(line + "\n")
+    return line
+
+
+def driver_bench(args):
+    """the script's two runs under the host and / or the device driver -> profiles/hopper_solve_device_driver.json, or with
+    --newton arrow per M -> profiles/hopper_solve_large_m_device_driver.json"""
+    import torch
+    from riskaversetrajopt_amd import hopper, hopper_ipm, scp
+    S, alphas, newton = args.S, [float(a) for a in args.alphas], args.newton
+    drivers = ("host", "device") if args.driver == "both" else (args.driver,)
+    out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": alphas, "tol": 1e-3, "max_iter": 3000, "newton": newton,
+           "solves": args.solves, "saa_start": "the host driver's baseline solution", "runs": {}}
+
+    def two_runs(M, fields):
+        mk = lambda method, a: hopper.Model(M, method, a, S=S, fields=fields, precision='f64')
+        base = mk('baseline', 0.1)
+        (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)     # the host driver's baseline: everyone's SAA start
+        xs, us = base.convert_z_to_xs_us_mats(Zb)
+        saa = [mk('saa', a) for a in alphas]
+        runs = {"baseline": ([base], [base.initial_guess()]), "saa": (saa, [scp.hopper_saa_start(m, xs, us) for m in saa])}
+        return {name: measure_drivers(models, Z0s, newton, drivers, args.solves, S) for name, (models, Z0s) in runs.items() if models}
+    if newton == "arrow":                                            # the training fields of --newton arrow, per M
+        Ms = [int(m) for m in str(args.M).split(",")]
+        train, _ = script_fields(max(Ms))
+        out["M"] = Ms
+        for M in Ms:
+            out["runs"][str(M)] = two_runs(M, tuple(f[:M] for f in train))
+            write_profile(out, args.out)                             # rewritten after every M
+            print("M = %d done" % M, file=sys.stderr, flush=True)
+    else:
+        out["M"] = int(args.M)
+        out["runs"] = two_runs(out["M"], hopper.sample_friction_fields(out["M"], np.random.RandomState(1)))
+    print(write_profile(out, args.out))
 
 
 def main():
@@ -214,16 +237,16 @@ def main():
     ap.add_argument("--alphas", type=float, nargs="*", default=[0.05, 0.1, 0.2, 0.3, 0.5, 0.75])
     ap.add_argument("--out", default=None)
     ap.add_argument("--driver", choices=("host", "device", "both"), default=None,
-                    help="measure the dense solve under the interior-point driver(s) instead")
+                    help="measure the solve (either --newton) under the interior-point driver(s) instead")
     ap.add_argument("--solves", type=int, default=5, help="with --driver: timed solves per run and driver")
     args = ap.parse_args()
-    if args.driver is not None and args.newton != "dense":
-        raise SystemExit("--driver measures the dense Newton step: the arrow backend is not yet served by driver='device'")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("hopper_solve_bench needs a GPU: nothing here is measured on the host in its place")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "hopper_solve_device_driver.json" if args.driver is not None else
+        args.out = os.path.join(ROOT, "profiles", "hopper_solve_large_m_device_driver.json"
+                                if args.driver is not None and args.newton == "arrow" else
+                                "hopper_solve_device_driver.json" if args.driver is not None else
                                 "hopper_solve_large_m.json" if args.newton == "arrow" else "hopper_solve.json")
     if args.driver is not None:
         return driver_bench(args)
