@@ -97,7 +97,8 @@ extern "C" {
  * layout; rato_scp_run_drone / rato_scp_iter -- the reduced SCP loop as one call; rato_car_ego_final_rows, rato_scp_run_car,
  * rato_scp_batch_run_car -- additions within version 12: the same for the driving problem; rato_drone_rows_plan /
  * rato_car_rows_plan -- a further addition within version 12: the row kernels' launch geometry as a query;
- * rato_hopper_slip_f64 / rato_hopper_slip_f64_nblocks / rato_hopper_slip_hess_blocks_f64 -- likewise: the hopper's slip rows in fp64).
+ * rato_hopper_slip_f64 / rato_hopper_slip_f64_nblocks / rato_hopper_slip_hess_blocks_f64 -- likewise: the hopper's slip rows in fp64;
+ * rato_hopper_slip_f64_fields -- likewise: the same with friction fields per problem).
  * The Python binding refuses a library that reports another version. */
 #define RATO_ABI_VERSION 12
 #define RATO_STATS_IN_LAUNCH 1   /* params.stats_flags */
@@ -1234,12 +1235,24 @@ int rato_scatter_f64(int32_t K, int64_t n, const double* src /* [K][ld_src] */, 
  * RATO_EINVAL without a launch unless S >= 1, 1 <= K <= 65535, M >= 1, ldz >= 8(S+1) + 4S, 0 <= time_jump <= time_land <= S,
  * Z and the fields are non-NULL and, with lam, part and D are non-NULL, lam_r0 >= 0 and ldlam >= lam_r0 + M C.  C = 0 is valid
  * and launches nothing.
+ *
+ * rato_hopper_slip_f64_fields -- a further addition within version 12: the same call with friction fields per problem.  ldf is
+ * the number of doubles between the field arrays of problem k and problem k + 1: problem k reads a + k ldf, theta + k ldf and
+ * tau + k ldf, each [30][M] (ldf > 30 M: the padding is never read).  ldf = 0 shares one set of fields among the K problems,
+ * which is rato_hopper_slip_f64 (that entry is this one with ldf = 0).  Any other ldf (negative, or 0 < ldf < 30 M) is
+ * RATO_EINVAL without a launch.  Launch shape, workspace and the order of every sum do not depend on ldf: row k of a K-problem
+ * call with fields per problem is bitwise the K = 1 call on problem k's fields.
  */
 int rato_hopper_slip_f64_nblocks(int32_t M);
 int rato_hopper_slip_f64(const rato_hopper_nlp_params* p, double mu_nom, int32_t K, int32_t M,
                          const double* Z /* [K][ldz] */, int64_t ldz, const double* a, const double* theta, const double* tau,
                          const double* lam /* [K][ldlam] or NULL */, int64_t ldlam, int64_t lam_r0, double* h, double* dh_dfz,
                          double* dh_dx, double* Zmax, double* part, double* D, void* stream);
+int rato_hopper_slip_f64_fields(const rato_hopper_nlp_params* p, double mu_nom, int32_t K, int32_t M,
+                                const double* Z /* [K][ldz] */, int64_t ldz, const double* a, const double* theta,
+                                const double* tau, int64_t ldf, const double* lam /* [K][ldlam] or NULL */, int64_t ldlam,
+                                int64_t lam_r0, double* h, double* dh_dfz, double* dh_dx, double* Zmax, double* part, double* D,
+                                void* stream);
 
 /* The slip rows' share of hess(lam . g), added IN PLACE into add [K][S+1][78] (the `add` of rato_hopper_nlp_hessian, zeroed or
  * pre-filled by the caller) at the np.tril_indices(12) positions of step t_c: local indices 0, 2, 3 (x0, x2, x3) and 11 (fz),

@@ -288,6 +288,8 @@ SIGNATURES = {
     "rato_hopper_slip_f64_nblocks": (C.c_int, [C.c_int32]),
     "rato_hopper_slip_f64": (C.c_int, [C.POINTER(HopperNlpParams), C.c_double, C.c_int32, C.c_int32, c_float_p, C.c_int64] +
                              [c_float_p] * 4 + [C.c_int64, C.c_int64] + [c_float_p] * 6 + [c_stream]),
+    "rato_hopper_slip_f64_fields": (C.c_int, [C.POINTER(HopperNlpParams), C.c_double, C.c_int32, C.c_int32, c_float_p, C.c_int64] +
+                                    [c_float_p] * 3 + [C.c_int64, c_float_p, C.c_int64, C.c_int64] + [c_float_p] * 6 + [c_stream]),
     "rato_hopper_slip_hess_blocks_f64": (C.c_int, [C.POINTER(HopperNlpParams), C.c_int32, c_float_p, C.c_int64, c_float_p,
                                                    c_float_p, c_stream]),
     "rato_normal_matrix_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64,

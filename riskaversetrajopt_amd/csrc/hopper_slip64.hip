@@ -13,6 +13,10 @@
 // Sums.  Each workgroup reduces its lanes' terms over the samples of a contact row with a fixed-order tree in LDS and writes
 // one partial per (sample tile, problem, contact): part[nblk][K][C][3].  rato_sum_partials_f64 adds the tiles in a fixed order.
 // No atomics: two calls are bitwise equal, and column (k, c) of a K-problem call sees the additions of the K = 1 call.
+//
+// Fields.  rato_hopper_slip_f64 reads one a / theta / tau [30][M] for the K problems; rato_hopper_slip_f64_fields takes ldf, the
+// doubles between the fields of problem k and k + 1 (0: shared).  The offset k ldf is applied in rato_slip64_run_lane, so the
+// launch shape and the order of every sum are those of the shared call, and row k is bitwise the K = 1 call on its own fields.
 #include "rato_common.h"
 #include "rato_hopper_slip64.h"
 
@@ -89,12 +93,13 @@ bool valid(const rato_hopper_nlp_params* p, int32_t K, int64_t ldz, Phases* P) {
 
 extern "C" int rato_hopper_slip_f64_nblocks(int32_t M) { return M < 1 ? 0 : (int)rato_slip64_nblocks(M); }
 
-extern "C" int rato_hopper_slip_f64(const rato_hopper_nlp_params* p, double mu_nom, int32_t K, int32_t M, const double* Z,
-                                    int64_t ldz, const double* a, const double* theta, const double* tau, const double* lam,
-                                    int64_t ldlam, int64_t lam_r0, double* h, double* dh_dfz, double* dh_dx, double* Zmax,
-                                    double* part, double* D, void* stream) {
+extern "C" int rato_hopper_slip_f64_fields(const rato_hopper_nlp_params* p, double mu_nom, int32_t K, int32_t M, const double* Z,
+                                           int64_t ldz, const double* a, const double* theta, const double* tau, int64_t ldf,
+                                           const double* lam, int64_t ldlam, int64_t lam_r0, double* h, double* dh_dfz,
+                                           double* dh_dx, double* Zmax, double* part, double* D, void* stream) {
   Phases P;
   if (!valid(p, K, ldz, &P) || M < 1 || !Z || !a || !theta || !tau) return RATO_EINVAL;
+  if (ldf != 0 && ldf < (int64_t)RATO_S64_NFEAT * M) return RATO_EINVAL;   // 0: one set of fields for the K problems
   if (P.C == 0) return RATO_OK;            // no contact step: nothing to write (the outputs are empty)
   const int64_t ncols = (int64_t)K * P.C * 3;
   if (lam && (!part || !D || lam_r0 < 0 || ldlam < lam_r0 + (int64_t)M * P.C || ncols > 0x7fffffff)) return RATO_EINVAL;
@@ -105,12 +110,20 @@ extern "C" int rato_hopper_slip_f64(const rato_hopper_nlp_params* p, double mu_n
   const int ncg = (P.C + tc - 1) / tc;
   const unsigned gy = Zmax ? 1u : (unsigned)(ncg < 65535 ? ncg : 65535);
   RATO_CLEAR_ERROR();
-  const rato_slip64_args A = {P, mu_nom, (int64_t)M, log2ti, Z, ldz, a, theta, tau, lam, ldlam, lam_r0, h, dh_dfz, dh_dx};
+  const rato_slip64_args A = {P, mu_nom, (int64_t)M, log2ti, Z, ldz, a, theta, tau, lam, ldlam, lam_r0, h, dh_dfz, dh_dx, ldf};
   hipLaunchKernelGGL(hopper_slip64_kernel, dim3((unsigned)nblk, gy, (unsigned)K), dim3(HS_BLOCK), 0, (hipStream_t)stream, A,
                      Zmax, lam ? part : nullptr);
   RATO_LAUNCH_CHECK();
   if (lam) return rato_sum_partials_f64(part, (int32_t)nblk, (int32_t)ncols, 1.0, D, stream);
   return RATO_OK;
+}
+
+extern "C" int rato_hopper_slip_f64(const rato_hopper_nlp_params* p, double mu_nom, int32_t K, int32_t M, const double* Z,
+                                    int64_t ldz, const double* a, const double* theta, const double* tau, const double* lam,
+                                    int64_t ldlam, int64_t lam_r0, double* h, double* dh_dfz, double* dh_dx, double* Zmax,
+                                    double* part, double* D, void* stream) {
+  return rato_hopper_slip_f64_fields(p, mu_nom, K, M, Z, ldz, a, theta, tau, 0, lam, ldlam, lam_r0, h, dh_dfz, dh_dx, Zmax, part,
+                                     D, stream);
 }
 
 extern "C" int rato_hopper_slip_hess_blocks_f64(const rato_hopper_nlp_params* p, int32_t K, const double* Z, int64_t ldz,

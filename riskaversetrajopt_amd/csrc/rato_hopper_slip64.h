@@ -111,10 +111,11 @@ struct rato_slip64_args {
   int log2ti;
   const double* Z;                  // [K][ldz]
   int64_t ldz;
-  const double *a, *theta, *tau;    // [30][M]
+  const double *a, *theta, *tau;    // [30][M], problem k's at + k ldf
   const double* lam;                // [K][ldlam] or NULL, read at lam_r0 + i C + c
   int64_t ldlam, lam_r0;
   double *h, *dh_dfz, *dh_dx;       // [K][C][M], [K][C][M], [K][C][3][M] or NULL
+  int64_t ldf;                      // doubles between the fields of problem k and k + 1; 0 (an aggregate's default): shared
 };
 
 // The lane (sample i, contact c) of problem k: its stores, its lambda-weighted terms t = (D1, D2, D0 shares; 0 for a lane outside
@@ -126,7 +127,8 @@ RATO_S64_HD void rato_slip64_run_lane(const rato_slip64_args& A, int64_t k, int6
   const int64_t M = A.M;
   const int step = rato_slip64_contact_step(c, A.P.time_jump, A.P.time_land);
   const rato_slip64_contact q = rato_slip64_load_contact(A.Z + k * A.ldz, A.P.S, step);
-  const rato_slip64_lane r = rato_slip64_eval(A.a, A.theta, A.tau, M, i, A.mu_nom, q.p, q.fx, q.fz);
+  const int64_t fo = k * A.ldf;     // uniform over the workgroup: one problem per blockIdx.z
+  const rato_slip64_lane r = rato_slip64_eval(A.a + fo, A.theta + fo, A.tau + fo, M, i, A.mu_nom, q.p, q.fx, q.fz);
   const int64_t row = k * C + c;
   if (A.h) A.h[row * M + i] = r.h;
   if (A.dh_dfz) A.dh_dfz[row * M + i] = r.dh_dfz;

@@ -10,7 +10,8 @@ hands to IPOPT (:486-640) on the MI355X.
     flight masks, the constant unit coefficients and the script's row order live here.
   * ``Model(..., precision='f64')``: the sample-dependent part at the precision of the rest, from Z on the device for K problems
     per call (rato_hopper_slip_f64 / rato_hopper_slip_hess_blocks_f64, csrc/hopper_slip64.hip); 'f32' stays the default and
-    the Monte-Carlo / large-M path.
+    the Monte-Carlo / large-M path.  ``fields=`` of ``slip_device_f64`` / ``nlp_device`` gives every problem of a call friction
+    fields of its own (rato_hopper_slip_f64_fields; ``stack_fields_f64``): a grid of alphas x resampled terrains is one batch.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
   * ``Model.initial_guess()`` and ``Model.solve()``: the script's start and its solve (:136-164, :642-669) with the batched
     interior-point method of ``ipm`` on the backends of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip, csrc/chol.hip) in
@@ -184,6 +185,33 @@ def block_symv(S, blocks, x, n=None, out=None):
         _lib.check(_lib.load().rato_hopper_block_symv_f64(K, S, n, _lib.ptr(blocks), _lib.ptr(x), x.shape[1], _lib.ptr(o), o.shape[1],
                                                           _lib.current_stream()), "rato_hopper_block_symv_f64")
     return o
+
+
+def stack_fields_f64(models):
+    """The friction fields of K models of one M on one device as what ``fields=`` of ``Model.slip_device_f64`` / ``nlp_device``
+    takes: (a, theta, tau), each a contiguous fp64 device tensor (K, 30, M) whose row k is ``models[k].fields_f64()`` (so models
+    built with fields='device' / ``from_device`` take part, upcast once).  K x 3 x 30 x M x 8 bytes of device memory."""
+    models = list(models)
+    if not models:
+        raise ValueError("stack_fields_f64 needs at least one model")
+    triples = [m.fields_f64() for m in models]
+    shape, dev = (num_mu_features, models[0].M), triples[0][0].device
+    if any(tuple(t.shape) != shape or t.device != dev for f in triples for t in f):
+        raise ValueError(f"the models' fields must all be {shape} on one device")
+    return tuple(torch.stack([f[j] for f in triples]).contiguous() for j in range(3))
+
+
+def _check_fields(fields, K, M, device):
+    """``fields`` = (a, theta, tau) per problem -> ldf = 30 M, or a ValueError before anything is launched"""
+    shape = (K, num_mu_features, M)
+    if not isinstance(fields, (tuple, list)) or len(fields) != 3:
+        raise ValueError("fields must be (a, theta, tau)")
+    for t, name in zip(fields, ("a", "theta", "tau")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                t.device.type != device.type or (device.index is not None and t.device.index != device.index):
+            raise ValueError(f"fields: {name} must be a contiguous float64 tensor {shape} on {device}, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    return num_mu_features * M
 
 
 def block_variables(S, t):
@@ -539,15 +567,21 @@ class Model:
             Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=self.device)
         return Zs
 
-    def slip_device_f64(self, Zs, lams=None, want=("h", "dh_dfz", "dh_dx", "Zmax")):
+    def slip_device_f64(self, Zs, lams=None, want=("h", "dh_dfz", "dh_dx", "Zmax"), fields=None):
         """rato_hopper_slip_f64 for K problems.  Zs (K, >= 8(S+1) + 4S) host array or device fp64 tensor (rows may be strided);
         lams (K, ncon) multipliers of g (host array or device fp64 tensor, read in place at the risk rows) or None.
         -> dict of fp64 device tensors, those named in ``want``: h (K, C, M), dh_dfz (K, C, M), dh_dx (K, C, 3, M) = dh/d(x0, x2,
         x3) with the end-effector chain applied, Zmax (K, M); and D (K, C, 3) = (D1, D2, D0), the lambda-weighted sample sums of
-        d2h/(dp dfz), d2h/dp2 and dh/dp (None without lams).  One launch, two with lams."""
+        d2h/(dp dfz), d2h/dp2 and dh/dp (None without lams).  One launch, two with lams.
+        ``fields`` = (a, theta, tau), each a contiguous fp64 device tensor (K, 30, M) on the model's device (``stack_fields_f64``):
+        problem k reads its own friction fields (rato_hopper_slip_f64_fields) and the model's are not read; row k is bitwise the
+        K = 1 call on a model that holds fields k.  None: the model's fields for all K problems.  Anything else is a ValueError
+        before a launch."""
         S, M, dev = self.S, self.M, self.device
         if not 0 <= self.time_jump <= self.time_land <= S:
             raise ValueError(f"phase times must satisfy 0 <= time_jump <= time_land <= S, got {self.time_jump}, {self.time_land}")
+        if fields is not None:
+            ldf = _check_fields(fields, Zs.shape[0] if isinstance(Zs, torch.Tensor) else np.atleast_2d(np.asarray(Zs)).shape[0], M, dev)
         Zs = self._device_rows(Zs)
         K, ldz = _rows_of(Zs, n_x * (S + 1) + n_u * S)
         Cn = self.time_jump + (S - self.time_land)
@@ -568,12 +602,18 @@ class Model:
             ldlam = lamd.stride(0) if K > 1 else max(lamd.stride(0), ncon)
             part = e(self._lib.rato_hopper_slip_f64_nblocks(M), K, Cn, 3)
             D = e(K, Cn, 3)
-        a, th, tau = self.fields_f64()
+        outs = [_lib.ptr(out.get(k)) for k in ("h", "dh_dfz", "dh_dx", "Zmax")] + [_lib.ptr(part), _lib.ptr(D)]
         with torch.cuda.device(dev):
-            _lib.check(self._lib.rato_hopper_slip_f64(
-                C.byref(params), mu_nom, K, M, _lib.ptr(Zs), ldz, _lib.ptr(a), _lib.ptr(th), _lib.ptr(tau), _lib.ptr(lamd), ldlam,
-                r0, *(_lib.ptr(out.get(k)) for k in ("h", "dh_dfz", "dh_dx", "Zmax")), _lib.ptr(part), _lib.ptr(D),
-                _lib.current_stream()), "rato_hopper_slip_f64")
+            if fields is not None:                                # C = 0: the library launches nothing, as without fields
+                a, th, tau = fields
+                _lib.check(self._lib.rato_hopper_slip_f64_fields(
+                    C.byref(params), mu_nom, K, M, _lib.ptr(Zs), ldz, _lib.ptr(a), _lib.ptr(th), _lib.ptr(tau), ldf,
+                    _lib.ptr(lamd), ldlam, r0, *outs, _lib.current_stream()), "rato_hopper_slip_f64_fields")
+            else:
+                a, th, tau = self.fields_f64()
+                _lib.check(self._lib.rato_hopper_slip_f64(
+                    C.byref(params), mu_nom, K, M, _lib.ptr(Zs), ldz, _lib.ptr(a), _lib.ptr(th), _lib.ptr(tau), _lib.ptr(lamd),
+                    ldlam, r0, *outs, _lib.current_stream()), "rato_hopper_slip_f64")
         out["D"] = D
         return out
 
@@ -590,12 +630,13 @@ class Model:
                 "rato_hopper_slip_hess_blocks_f64")
         return add
 
-    def _slip_f64(self, Zs, lams=None):
+    def _slip_f64(self, Zs, lams=None, fields=None):
         """one evaluation of the slip kernel and its emission: slip_h (K, C, M), slip_rows (K, M C): h in the risk rows' order
-        i C + c, slip_jac_values (K, nnz_slip): the CSC values of ``_jacobian_pattern`` with the constant part in place, D"""
+        i C + c, slip_jac_values (K, nnz_slip): the CSC values of ``_jacobian_pattern`` with the constant part in place, D.
+        ``fields``: friction fields per problem, as ``slip_device_f64`` takes them"""
         lay = self.nlp_layout()
         Cn, M = lay["C"], self.M
-        r = self.slip_device_f64(Zs, lams, want=("h", "dh_dfz", "dh_dx"))
+        r = self.slip_device_f64(Zs, lams, want=("h", "dh_dfz", "dh_dx"), fields=fields)
         K = r["h"].shape[0]
         st = getattr(self, "_slip_dev", None)
         if st is None:
@@ -944,7 +985,7 @@ class Model:
                                                   2 * (S + 1), 2 * (S + 1), _lib.current_stream()), "rato_scatter_f64")
         return lams[:, :n_x * S].contiguous().view(K, S, n_x), lam_rows
 
-    def nlp_device(self, Zs, lams=None, add=None, fold='host'):
+    def nlp_device(self, Zs, lams=None, add=None, fold='host', fields=None):
         """K problems per call.  Zs (K, nvar) host array or device fp64 tensor (rows may be strided: ldz >= nvar); lams
         (K, ncon) multipliers of g or None; add (K, S+1, 78) blocks added to the Hessian or None.  -> dict of fp64 DEVICE tensors:
         defect (K, S, 8), d_defect (K, S, 8, 12), rows (K, S+1, 2), d_rows (K, S+1, 2, 4), jac_values (K, nnz): the CSC values of
@@ -955,10 +996,16 @@ class Model:
         constant entries in place; with lams the slip rows' share is inside hess_blocks / hess_tril (the multipliers are read
         where they lie).  Four more launches, seven with lams.
         fold='device' (lams a device tensor (K, ld >= ncon)): the multipliers are folded by ``fold_multipliers_device`` and
-        nothing of them is read back; hess_tril is not built (the solver reads the blocks)."""
+        nothing of them is read back; hess_tril is not built (the solver reads the blocks).
+        ``fields`` (precision='f64' only): friction fields per problem, (a, theta, tau) each (K, 30, M), as ``slip_device_f64``
+        takes them; every other row of the NLP does not depend on them."""
         if fold not in ('host', 'device'):
             raise ValueError(f"fold must be 'host' or 'device', got {fold!r}")
         dev = self.device
+        if fields is not None:
+            if self.precision != 'f64':
+                raise ValueError("fields per problem are the fp64 slip path's: the model needs precision='f64'")
+            _check_fields(fields, Zs.shape[0] if isinstance(Zs, torch.Tensor) else np.atleast_2d(np.asarray(Zs)).shape[0], self.M, dev)
         if not isinstance(Zs, torch.Tensor):
             Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=dev)
         if Zs.dim() != 2 or Zs.shape[1] < self.num_vars:
@@ -975,7 +1022,7 @@ class Model:
         if f64:                                                   # the risk group from the same Z, on the device
             if lams is not None and not isinstance(lams, torch.Tensor):
                 lams = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(lams, dtype=np.float64))), device=dev)
-            slip = self._slip_f64(Zs, lams if lams is None or fold == 'host' else lams[:, :self.nlp_layout()["ncon"]])
+            slip = self._slip_f64(Zs, lams if lams is None or fold == 'host' else lams[:, :self.nlp_layout()["ncon"]], fields)
             out.update(slip_h=slip["slip_h"], slip_rows=slip["slip_rows"], slip_jac_values=slip["slip_jac_values"])
         if lams is not None and fold == 'device':
             lam_dyn, lam_rows = self.fold_multipliers_device(lams)

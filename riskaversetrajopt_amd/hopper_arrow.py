@@ -13,7 +13,7 @@ import numpy as np
 
 from . import hopper as _h
 from . import ipm as _ipm
-from .hopper_ipm import (ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, arrow_einv, arrow_kkbeta, arrow_rhsfix, arrow_scale,
+from .hopper_ipm import (GroupFields, ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, arrow_einv, arrow_kkbeta, arrow_rhsfix, arrow_scale,
                          arrow_tfix, assemble_g, csc_matvec, csc_tmatvec, normal_matrix, normal_matrix_host, scatter_rows,
                          upload_maps)
 
@@ -235,7 +235,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     leaves in HBM; the core through ``hopper_ipm.normal_matrix`` on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).
     eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels to the
     host per call of a list method is the vectors the driver works on and O(q) sums; the ``*_t`` methods (the driver on the
-    device) move nothing."""
+    device) move nothing.  The group's models may hold friction fields of their own (``hopper_ipm.GroupFields``)."""
     name, newton = "device", "arrow"
 
     def __init__(self, models):
@@ -260,6 +260,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         if self.nch < 1 or self.npart < 1:
             raise ValueError(f"newton='arrow' on the device serves 1 <= C <= 50 contact steps, got C = {st['C']}")
         self.vals0 = self.dx = self.dfz = self.hessd = self.hess_host = None
+        self.fields = GroupFields(models)
         n_all = len(models)
         self.e, self.d = self._empty(n_all, st["M"]), self._empty(n_all, st["ncon"])
         self.kk, self.beta = np.zeros(n_all), np.zeros(n_all)
@@ -283,7 +284,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
             jac = mp["det_const"][None].repeat(K, 1).contiguous()
             _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
             _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
-            slip = m0.slip_device_f64(Zd, lamd, want=("h", "dh_dfz", "dh_dx"))
+            slip = m0.slip_device_f64(Zd, lamd, want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of(idx))
             add = self._up([_obj_add(m0, sf) for sf in sfs])
             m0.slip_hess_blocks_device_f64(Zd, slip["D"], add)
             lam_dyn, lam_rows = m0.fold_multipliers(np.stack(lams))
@@ -298,7 +299,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         with self.timed("callbacks"):
             Zd = self._up(Zs)
             lin = _h.nlp_linearize_device(self.params, Zd, want=("defect", "rows"))
-            out = self._g_rows(idx, Zs, lin, self.m0.slip_device_f64(Zd, want=("h",))["h"])
+            out = self._g_rows(idx, Zs, lin, self.m0.slip_device_f64(Zd, want=("h",), fields=self.fields.of(idx))["h"])
         return out
 
     def hess_apply(self, idx, X):
@@ -489,7 +490,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         jac = mp["det_const"][None].repeat(K, 1).contiguous()
         _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
         _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
-        slip = m0.slip_device_f64(Z, Y[:, :self.st["ncon"]], want=("h", "dh_dfz", "dh_dx"))
+        slip = m0.slip_device_f64(Z, Y[:, :self.st["ncon"]], want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of())
         add = w["add"].zero_()
         m0.slip_hess_blocks_device_f64(Z, slip["D"], add)
         lam_dyn, lam_rows = m0.fold_multipliers_device(Y)
@@ -500,7 +501,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
 
     def eval_g_t(self, Z):
         lin = _h.nlp_linearize_device(self.params, Z, want=("defect", "rows"))
-        return self._g_t(Z, lin, self.m0.slip_device_f64(Z, want=("h",))["h"])
+        return self._g_t(Z, lin, self.m0.slip_device_f64(Z, want=("h",), fields=self.fields.of())["h"])
 
     def hess_apply_t(self, X):
         """W x of the constraints' part alone (K, n)"""

@@ -376,8 +376,37 @@ def arrow_rhsfix(Cn, nc, qcol, red, beta, rc):
     return rc
 
 
+def _fields_key(m):
+    """what tells one set of friction fields from another: the bytes of the host arrays, or the device arrays' addresses"""
+    host = tuple(getattr(m, name, None) for name in ("intensities", "thetas", "taus"))
+    if all(x is not None for x in host):
+        return tuple(np.asarray(x).tobytes() for x in host)
+    return tuple(t.data_ptr() for t in (m._a, m._th, m._tau))
+
+
+class GroupFields:
+    """The friction fields of a group's models for the slip kernel.  Models that share one set keep the shared call (``of`` gives
+    None: models[0]'s fields serve every problem, as before fields per problem existed).  Otherwise the fields are stacked once
+    as (a, theta, tau), each (K, 30, M) (``hopper.stack_fields_f64``: K x 3 x 30 x M x 8 bytes), and ``of(idx)`` gives the rows of
+    the listed problems: the whole stack in place when they are all of them in order, a gathered copy when some have left."""
+
+    def __init__(self, models):
+        self.K = len(models)
+        key0 = _fields_key(models[0])
+        self.stack = None if all(_fields_key(m) == key0 for m in models[1:]) else _h.stack_fields_f64(models)
+
+    def of(self, idx=None):
+        if self.stack is None:
+            return None
+        if idx is None or list(idx) == list(range(self.K)):
+            return self.stack
+        sel = torch.as_tensor(list(idx), device=self.stack[0].device)
+        return tuple(t.index_select(0, sel) for t in self.stack)
+
+
 class DeviceBackend(_ipm.DeviceBase):
-    """the step on the MI355X for the problems of one group (same S, M, phases, method and friction fields; alpha may differ).
+    """the step on the MI355X for the problems of one group (same S, M, phases and method; alpha and the friction fields may
+    differ: models that do not share one set of fields are served from a stack of theirs, ``GroupFields``).
     Every call serves the listed problems in ONE launch each; nothing a kernel computes for a problem depends on the others."""
     name = "device"
 
@@ -394,6 +423,7 @@ class DeviceBackend(_ipm.DeviceBase):
         self.saa = m0.method != 'baseline' and lay["C"] > 0
         self.alpha_pos = int(lay["nnz_slip"] - 1 - m0.M * lay["C"]) if self.saa else -1
         self.vals0 = self.vals1 = self.hessd = self.hess_host = None
+        self.fields = GroupFields(models)
         # for the driver on the device: M alpha per problem (the sum row of g, and the Jacobian entry above), uploaded once
         self.malpha = torch.as_tensor([m0.M * float(m.alpha) for m in models], dtype=torch.float64, device=self.dev) \
             if m0.method != 'baseline' else None
@@ -407,7 +437,7 @@ class DeviceBackend(_ipm.DeviceBase):
         torch = self.torch
         with self.timed("callbacks"):
             add = self._up([_obj_add(self.m0, sf) for sf in sfs])
-            r = self.m0.nlp_device(self._up(Zs), self._up(lams), add=add)
+            r = self.m0.nlp_device(self._up(Zs), self._up(lams), add=add, fields=self.fields.of(idx))
             self.vals0, self.vals1, self.hessd = r["jac_values"], r["slip_jac_values"], r["hess_blocks"]
             if self.saa:
                 self.vals1[:, self.alpha_pos] = torch.as_tensor([self.m0.M * float(self.models[i].alpha) for i in idx],
@@ -418,7 +448,7 @@ class DeviceBackend(_ipm.DeviceBase):
 
     def eval_g(self, idx, Zs):
         with self.timed("callbacks"):
-            return self._g_rows(idx, Zs, self.m0.nlp_device(self._up(Zs)))
+            return self._g_rows(idx, Zs, self.m0.nlp_device(self._up(Zs), fields=self.fields.of(idx)))
 
     def set_values(self, vals, hess):
         """install given Jacobian values (K, nnz) on the full CSC pattern and step blocks (K, S+1, 78) as the current
@@ -461,7 +491,7 @@ class DeviceBackend(_ipm.DeviceBase):
     def eval_full_t(self, Z, Y):
         """Z (K, n) and the multipliers Y (K, ld >= ncon) -> g (K, ncon); leaves the Jacobian's values and the step blocks of
         hess(Y . g) for the calls below.  The objective's curvature is NOT in the blocks: the driver's diagonal carries it."""
-        r = self.m0.nlp_device(Z, Y, fold='device')
+        r = self.m0.nlp_device(Z, Y, fold='device', fields=self.fields.of())
         self.vals0, self.vals1, self.hessd = r["jac_values"], r["slip_jac_values"], r["hess_blocks"]
         if self.saa:
             self.vals1[:, self.alpha_pos] = self.malpha
@@ -469,7 +499,7 @@ class DeviceBackend(_ipm.DeviceBase):
         return self._g_t(Z, r)
 
     def eval_g_t(self, Z):
-        return self._g_t(Z, self.m0.nlp_device(Z))
+        return self._g_t(Z, self.m0.nlp_device(Z, fields=self.fields.of()))
 
     def matvec_t(self, X):
         """X (K, ld >= n) -> J x (K, ncon)"""
@@ -490,17 +520,17 @@ class DeviceBackend(_ipm.DeviceBase):
 
 
 def _group_key(m):
-    f = tuple(np.asarray(x).tobytes() for x in (getattr(m, "intensities", None), getattr(m, "thetas", None), getattr(m, "taus", None))
-              if x is not None) or (id(m),)
-    return (m.method, m.S, m.M, m.time_jump, m.time_land, f)
+    return (m.method, m.S, m.M, m.time_jump, m.time_land)
 
 
 def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
                 newton='dense', driver='host'):
     """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  The K problems share S, M and the phases;
-    problems of one method and one set of friction fields (alpha may differ) form a group that moves through the K-problem
-    kernels together, the groups one after the other.  A problem that has ended stops changing and leaves the launches; its Z is
-    bitwise what its own K = 1 run returns.
+    problems of one method form a group that moves through the K-problem kernels together (alpha and the friction fields may
+    differ from problem to problem: a grid of alphas x resampled terrains is ONE group), the groups one after the other.  A
+    problem that has ended stops changing and leaves the launches; its Z and info are bitwise what its own K = 1 run returns.
+    On the device a group whose models do not share their fields holds them stacked, K x 3 x 30 x M x 8 bytes (``GroupFields``;
+    fields='device' / ``from_device`` models take part through ``fields_f64()``), and must be on one device.
       Z0s        starting points (default: ``model.initial_guess()``)
       backend    'device' (csrc/hopper_ipm.hip, csrc/chol.hip) or 'numpy' (the step on the host)
       callbacks  backend='numpy' only: one object per model with g(Z), jac_values(Z), hess_blocks(Z, lam, obj_factor)

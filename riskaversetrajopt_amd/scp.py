@@ -818,3 +818,76 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
             save_hopper_result(results_dir, m, r["Z"])
     return {"alphas": alphas, "base": base, "results": results, "status": np.array([r["status"] for r in results]),
             "wall_s": time.perf_counter() - t0}
+
+
+def draw_hopper_saa_fields(num_repeats=30, M=30, M_mc=10000, seed=1):
+    """The friction fields of ``hopper_saa_experiment`` in its draw order, under ONE ``RandomState(seed)``: repeat 0 .. R-1 each
+    draw ``hopper.sample_friction_fields(M, rng)`` in sequence (with the default seed repeat 0 is bitwise ``hopper_experiment``'s
+    draw), then the ``M_mc`` validation fields, last.  Host only.  -> ([repeat] of (intensities, thetas, taus), each (M, 30); the
+    validation triple, each (M_mc, 30))"""
+    from . import hopper
+    rng = np.random.RandomState(seed)
+    repeats = [hopper.sample_friction_fields(M, rng) for _ in range(int(num_repeats))]
+    return repeats, hopper.sample_friction_fields(int(M_mc), rng)
+
+
+def hopper_saa_result_path(results_dir, alpha, repeat):
+    """hopper_saa_alpha=<alpha>_repeat=<r>_results.npy"""
+    return os.path.join(results_dir, f"hopper_saa_alpha={alpha}_repeat={repeat}_results.npy")
+
+
+HOPPER_SAA_REPORT = "hopper_saa_grid_report.npy"
+HOPPER_SAA_REPORT_ARRAYS = ("alphas", "status", "jump", "safe_fraction", "var", "avar")
+
+
+def hopper_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), num_repeats=30, M=30, S=30, seed=1, M_mc=10000, results_dir=None,
+                          tol=1e-3, max_iter=3000, newton='dense', driver='host', device='cuda:0', clocks=None):
+    """The hopper's SAA study over resampled terrains, shaped like ``drone_saa_experiment`` / ``driving_saa_experiment``: R draws
+    of the friction fields (``draw_hopper_saa_fields``), the baseline solved once from ``initial_guess()`` (its fields are zeroed,
+    so it does not depend on the draw), then all A x R SAA problems -- alpha-major, every repeat on its own fields -- in ONE
+    ``hopper_ipm.solve_batch`` call (one lockstep group) from ``hopper_saa_start`` of the baseline's solution, and the script's
+    Monte-Carlo validation (hopper.py:960-1007) of every solution on the ``M_mc`` validation fields: px and the contact forces
+    on the contact steps (``Model.contact_inputs``), ``Model.monte_carlo_statistics`` at the problem's alpha, one solution after
+    the other.  A problem that does not converge raises nothing: its status says so and it is validated like the others.
+    -> dict(alphas, base (the run_hopper dict without total_s), results [alpha][repeat] = (Z, xs, us, status, info), status (A, R)
+    of str, jump (A, R) = x_S[0], safe_fraction / var / avar (A, R), wall_s).
+    With ``results_dir``: hopper_saa_alpha=<a>_repeat=<r>_results.npy per problem (xs then us, ``save_results``) and one
+    hopper_saa_grid_report.npy holding, in this order, alphas (A,), status (A, R), jump, safe_fraction, var, avar (each (A, R)):
+    ``load_results(path, 6)``."""
+    from . import hopper, hopper_ipm
+    alphas = [float(a) for a in alphas]
+    A, R = len(alphas), int(num_repeats)
+    draws, mc_fields = draw_hopper_saa_fields(R, M, M_mc, seed)
+    t0 = time.perf_counter()
+    kw = dict(tol=tol, max_iter=max_iter, backend='device', newton=newton, driver=driver)
+    zero = np.zeros((M, hopper.num_mu_features))                 # what Model makes of any baseline's fields
+    base_model = hopper.Model(M, 'baseline', S=S, fields=(zero, zero, zero), device=device, precision='f64')
+    c0, c1 = {}, {}
+    (Zb, ib), = hopper_ipm.solve_batch([base_model], clocks=c0, **kw)
+    xs, us = base_model.convert_z_to_xs_us_mats(Zb)
+    base = {"Z": Zb, "xs": xs, "us": us, "status": ib["status"], "info": ib}
+    models = [hopper.Model(M, 'saa', a, S=S, fields=draws[r], device=device, precision='f64') for a in alphas for r in range(R)]
+    sols = hopper_ipm.solve_batch(models, [hopper_saa_start(m, xs, us) for m in models], clocks=c1, **kw) if models else []
+    mc_model = hopper.Model(int(M_mc), 'saa', S=S, fields=mc_fields, device=device)
+    results = [[None] * R for _ in alphas]
+    status = np.empty((A, R), dtype='U16')
+    jump, safe, var, avar = (np.zeros((A, R)) for _ in range(4))
+    for k, (m, (Z, info)) in enumerate(zip(models, sols)):
+        i, r = divmod(k, R)
+        x, u = m.convert_z_to_xs_us_mats(Z)
+        results[i][r] = (Z, x, u, info["status"], info)
+        status[i, r], jump[i, r] = info["status"], x[-1, 0]
+        px, forces = m.contact_inputs(Z)
+        st = mc_model.monte_carlo_statistics(px, forces, alpha=m.alpha)
+        safe[i, r], var[i, r], avar[i, r] = st["frac_satisfied"], st["var"], st["cvar"]
+    if clocks is not None:
+        clocks["base"], clocks["saa"] = c0, c1
+    out = {"alphas": alphas, "base": base, "results": results, "status": status, "jump": jump, "safe_fraction": safe, "var": var,
+           "avar": avar, "wall_s": time.perf_counter() - t0}
+    if results_dir is not None:
+        os.makedirs(results_dir, exist_ok=True)
+        for i, a in enumerate(alphas):
+            for r in range(R):
+                save_results(hopper_saa_result_path(results_dir, a, r), results[i][r][1], results[i][r][2])
+        save_results(os.path.join(results_dir, HOPPER_SAA_REPORT), np.asarray(alphas), *(out[k] for k in HOPPER_SAA_REPORT_ARRAYS[1:]))
+    return out

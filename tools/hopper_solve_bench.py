@@ -29,6 +29,16 @@ solves after a warm-up (ms per batch, ms per lockstep iteration), the clocks' sp
 launch under the device driver) and of one with ``sync_clocks`` (a device-wide wait behind every block), and the
 device-to-host copies (``Tensor.cpu()`` calls) per iteration.
 
+``--repeats R`` measures the SAA grid over resampled terrains instead, into profiles/hopper_saa_grid.json: the
+A alphas x R draws of the friction fields (``scp.draw_hopper_saa_fields``, seed 1) from the host driver's baseline solution,
+solved as ONE ``solve_batch`` (one lockstep group of A R problems on their own fields) against the same problems repeat by
+repeat, one ``solve_batch`` of A problems per draw -- what a list of such models executed while the fields were part of the
+group key.  Per M of ``--M`` (a comma-separated list), ``--newton`` and driver (``--driver``, default both), in one process, a
+warm-up solve each, then ``--solves`` timed solves each (median): the wall clock, the lockstep iterations (the batch: its
+slowest member's; repeat by repeat: the sum over the draws of each draw's slowest), the largest and the median per-problem
+iteration count, the status counts, and whether every (Z, info) of the batch is bitwise the repeat-by-repeat one.  The file is
+rewritten after every measurement, and a later call with another M or newton adds to it.
+
 Prints one JSON line.  There is no CPU fallback: without a GPU nothing is measured.
 """
 import argparse
@@ -229,6 +239,76 @@ def driver_bench(args):
     print(write_profile(out, args.out))
 
 
+def grid_bench(args):
+    """the alpha x repeat grid as one batch against repeat by repeat -> profiles/hopper_saa_grid.json"""
+    import time
+
+    import torch
+    from riskaversetrajopt_amd import hopper, hopper_ipm, scp
+    S, alphas, newton, R = args.S, [float(a) for a in args.alphas], args.newton, args.repeats
+    drivers = ("device", "host") if args.driver in (None, "both") else (args.driver,)
+    out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": alphas, "repeats": R, "tol": 1e-3, "max_iter": 3000,
+           "seed": 1, "saa_start": "the host driver's baseline solution", "runs": {}}
+    if args.out and os.path.exists(args.out):                        # a later call adds its runs to the file of an earlier one
+        with open(args.out) as f:
+            old = json.loads(f.readline())
+        if all(old.get(k) == out[k] for k in ("device", "S", "alphas", "repeats", "tol", "max_iter", "seed")):
+            out["runs"] = old.get("runs", {})
+
+    def timed(call, warm):
+        warm()
+        torch.cuda.synchronize()
+        walls = []
+        for _ in range(args.solves):
+            t0 = time.perf_counter()
+            sols = call()
+            walls.append(time.perf_counter() - t0)
+        return sols, walls
+
+    def same(r0, r1):
+        (Z0, i0), (Z1, i1) = r0, r1
+        return Z0.tobytes() == Z1.tobytes() and all(
+            (i0[k].tobytes() == i1[k].tobytes()) if isinstance(i0[k], np.ndarray) else i0[k] == i1[k] for k in i0)
+    for M in [int(m) for m in str(args.M).split(",")]:
+        draws, _ = scp.draw_hopper_saa_fields(R, M, 1, seed=1)
+        zero = np.zeros((M, hopper.num_mu_features))
+        base = hopper.Model(M, 'baseline', S=S, fields=(zero, zero, zero), precision='f64')
+        (Zb, ib), = hopper_ipm.solve_batch([base], newton=newton)
+        xs, us = base.convert_z_to_xs_us_mats(Zb)
+        models = [[hopper.Model(M, 'saa', a, S=S, fields=draws[r], precision='f64') for a in alphas] for r in range(R)]   # [repeat][alpha]
+        starts = [[scp.hopper_saa_start(m, xs, us) for m in row] for row in models]
+        flat_m, flat_z = [m for row in models for m in row], [z for row in starts for z in row]
+        key = "M=%d,newton=%s" % (M, newton)
+        rec = out["runs"].setdefault(key, {"baseline": {"status": ib["status"], "iterations": int(ib["iterations"])},
+                                           "problems": len(flat_m), "stacked_fields_bytes": len(flat_m) * 3 * 30 * M * 8})
+        for d in drivers:
+            kw = dict(driver=d, newton=newton)
+            batch = lambda: hopper_ipm.solve_batch(flat_m, flat_z, **kw)
+            one = lambda r: hopper_ipm.solve_batch(models[r], starts[r], **kw)
+            sols_b, walls_b = timed(batch, batch)
+            sols_r, walls_r = timed(lambda: [sol for r in range(R) for sol in one(r)], lambda: one(0))
+            its = np.array([info["iterations"] for _, info in sols_b])
+            its_r = np.array([info["iterations"] for _, info in sols_r]).reshape(R, len(alphas))
+            status = {}
+            for _, info in sols_b:
+                status[info["status"]] = status.get(info["status"], 0) + 1
+            med_b, med_r = float(np.median(walls_b)), float(np.median(walls_r))
+            rec[d] = {"solves": args.solves, "one_batch": {"wall_ms": [1e3 * w for w in walls_b], "median_ms": 1e3 * med_b, "lockstep_iterations": int(its.max()),
+                                    "median_ms_per_lockstep_iteration": 1e3 * med_b / max(int(its.max()), 1)},
+                      "repeat_by_repeat": {"wall_ms": [1e3 * w for w in walls_r], "median_ms": 1e3 * med_r,
+                                           "lockstep_iterations": int(its_r.max(axis=1).sum()),
+                                           "median_ms_per_lockstep_iteration": 1e3 * med_r / max(int(its_r.max(axis=1).sum()), 1)},
+                      "repeat_by_repeat_over_one_batch": med_r / med_b,
+                      "iterations_per_problem": {"largest": int(its.max()), "median": float(np.median(its)),
+                                                 "slowest": {"alpha": float(flat_m[int(its.argmax())].alpha),
+                                                             "repeat": int(its.argmax()) // len(alphas)}},
+                      "status": status, "batch_is_bitwise_repeat_by_repeat": all(same(a, b) for a, b in zip(sols_b, sols_r))}
+            write_profile(out, args.out)
+            print("%s driver=%s done: one batch %.0f ms, repeat by repeat %.0f ms" % (key, d, 1e3 * med_b, 1e3 * med_r),
+                  file=sys.stderr, flush=True)
+    print(write_profile(out, args.out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--S", type=int, default=30)
@@ -238,16 +318,24 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--driver", choices=("host", "device", "both"), default=None,
                     help="measure the solve (either --newton) under the interior-point driver(s) instead")
-    ap.add_argument("--solves", type=int, default=5, help="with --driver: timed solves per run and driver")
+    ap.add_argument("--solves", type=int, default=5, help="with --driver or --repeats: timed solves per run and driver")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="measure the grid of alphas x this many draws of the fields as one batch against repeat by repeat instead")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("hopper_solve_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.out is None and args.repeats is not None:
+        args.out = os.path.join(ROOT, "profiles", "hopper_saa_grid.json")
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "hopper_solve_large_m_device_driver.json"
                                 if args.driver is not None and args.newton == "arrow" else
                                 "hopper_solve_device_driver.json" if args.driver is not None else
                                 "hopper_solve_large_m.json" if args.newton == "arrow" else "hopper_solve.json")
+    if args.repeats is not None:
+        if args.repeats < 1:
+            raise SystemExit("--repeats needs at least one draw")
+        return grid_bench(args)
     if args.driver is not None:
         return driver_bench(args)
     if args.newton == "arrow":
