@@ -1337,6 +1337,27 @@ int rato_chol_factor_batch_f64(double* A, int32_t n, int64_t lda, int32_t K, int
 int rato_chol_solve_batch_f64(const double* L, int32_t n, int64_t lda, int32_t K, double* B, int32_t nrhs, int64_t ldb,
                               void* stream);
 
+/* ---- The same Cholesky spread over the device (csrc/chol_grid.hip; ipm.chol_factor / chol_solve with method='grid').
+ * ABI: additive (RATO_ABI_VERSION stays 12).  Same layout, panels, arguments and info as the two entries above, and the same
+ * arithmetic per entry in the same order: L, info of the problems that succeed, and X are BITWISE those of
+ * rato_chol_factor_batch_f64 / rato_chol_solve_batch_f64 (what a failed problem's matrix holds is unspecified, as there).
+ * The factorization is a stream-ordered sequence of launches, ONE per panel.  Launch q holds, per problem, a workgroup per
+ * 64-row block below panel q, which applies panel q - 1's update to its own rows of panel q and to the old diagonal block,
+ * factors the 32 x 32 diagonal block for itself and solves its rows in place, and a workgroup per 64 x 64 tile right of panel
+ * q, which applies panel q - 1's update there.  Workgroups of a launch never wait for each other and none reads an entry
+ * another one of the same launch writes: the factored diagonal block goes to work and is copied into A by the next launch.
+ * The first launch sets info[k]; every later launch returns at once for a problem whose info[k] is set.  work: K *
+ * rato_chol_grid_work_doubles(n) doubles of the caller's, contents irrelevant before and after; it may be NULL when the
+ * query returns 0 (n <= rato_chol_panel_width()).  The library
+ * allocates nothing.  The solve runs one workgroup per (problem, right-hand side) with no global load inside a dependent
+ * chain.  No atomics: two calls are bitwise equal and problem k of a batch is bitwise its K = 1 call.  RATO_EINVAL without
+ * a launch and with every output untouched on NULL pointers (work included where the query is positive), n < 1 (solve:
+ * n > 8000), lda < n, ldb < n, nrhs or K outside [1, 65535]. */
+int64_t rato_chol_grid_work_doubles(int32_t n);
+int rato_chol_factor_grid_batch_f64(double* A, int32_t n, int64_t lda, int32_t K, int32_t* info, double* work, void* stream);
+int rato_chol_solve_grid_batch_f64(const double* L, int32_t n, int64_t lda, int32_t K, double* B, int32_t nrhs, int64_t ldb,
+                                   void* stream);
+
 /* ---- Batched dense convex QP solve, fp64 (csrc/qp_ipm.hip): the QPs of the driving Gaussian baseline's SCP
  * (car/driving_gaussian.py:428-456, n = 3S + 1 and m = 4S + 5 before the host presolve), which the reference hands to OSQP.
  * ABI: additive (RATO_ABI_VERSION stays 12).

@@ -308,6 +308,10 @@ SIGNATURES = {
     "rato_chol_factor_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, c_stream]),
     "rato_chol_solve_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int64,
                                             c_stream]),
+    "rato_chol_grid_work_doubles": (C.c_int64, [C.c_int32]),
+    "rato_chol_factor_grid_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, c_float_p, c_stream]),
+    "rato_chol_solve_grid_batch_f64": (C.c_int, [c_float_p, C.c_int32, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int64,
+                                                 c_stream]),
     "rato_qp_ipm_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rato_qp_ipm_batch_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_int64, c_float_p,
                                         C.c_int64, C.c_int64, c_float_p, c_float_p, C.c_int64, C.c_double, C.c_int32, c_float_p,

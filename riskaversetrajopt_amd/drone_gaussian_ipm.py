@@ -233,11 +233,11 @@ class DeviceBackend(_ipm.DeviceBase):
     in ONE launch each; nothing a kernel computes for a problem depends on the others."""
     name = "device"
 
-    def __init__(self, nlps):
+    def __init__(self, nlps, chol='workgroup'):
         self.nlps = nlps
         self.m0 = nlps[0].model
         self.m0._handle()
-        super().__init__(self.m0.device, len(nlps), "matvec")
+        super().__init__(self.m0.device, len(nlps), "matvec", chol=chol)
         self.n, self.n_nl = nlps[0].num_vars, nlps[0].n_nl
         self.st = None
         self.sum_row = self.torch.as_tensor(nlps[0].sum_row()[None, :].copy(), device=self.dev)
@@ -338,12 +338,12 @@ def lagrange(nlp, info):
     return np.concatenate([info["y"][:n_nl], info["zu"][:n] - info["zl"][:n], info["y"][n_nl:]])
 
 
-def make_backend(nlps, backend, callbacks=None):
-    return DeviceBackend(nlps) if backend == 'device' else NumpyBackend(nlps, callbacks)
+def make_backend(nlps, backend, callbacks=None, chol='workgroup'):
+    return DeviceBackend(nlps, chol=chol) if backend == 'device' else NumpyBackend(nlps, callbacks)
 
 
 def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
-                results_dir='results', driver='host'):
+                results_dir='results', driver='host', chol='workgroup'):
     """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  Models of one S form a group that moves
     through the K-problem kernels together (alpha may differ inside it: it enters only the host-side bounds), the groups one
     after the other.  A problem that has ended leaves the launches, a failed factorization is redone for the failed problems
@@ -356,12 +356,15 @@ def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', cal
       driver     'host' (``ipm.solve_group``: the iterate and the vector algebra on the host) or 'device'
                  (``ipm.solve_group_device``, backend='device' only: the iterate stays on the device, csrc/ipm_driver.hip, and
                  the clocks hold the time to launch; info["driver"] = 'device')
+      chol       'workgroup' (csrc/chol.hip) or 'grid' (csrc/chol_grid.hip: the same bits from launches spread over the device);
+                 backend='numpy' ignores it
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
     dual_infeasibility, f, mu, sf (the objective scale), the final multipliers y (m = n_nl + 1), zl, zu (nvar + the slacks), the
     slacks s, and lagrange (ncon) in the script's row order."""
     if backend not in ('device', 'numpy'):
         raise ValueError(f"backend must be 'device' or 'numpy', got {backend!r}")
     _ipm.check_driver(driver, backend)
+    _ipm.check_chol(chol)
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
@@ -378,7 +381,8 @@ def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', cal
     def setup(members):
         group = [Nlp(models[i]) for i in members]
         nlps.update(zip(members, group))
-        return group, make_backend(group, backend, None if callbacks is None else [callbacks[i] for i in members])
+        return group, make_backend(group, backend, None if callbacks is None else [callbacks[i] for i in members],
+                                   chol=chol)
 
     spent = None if clocks is None else {}
     out = _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, spent, driver=driver)

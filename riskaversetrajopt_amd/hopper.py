@@ -911,16 +911,17 @@ class Model:
         return Zp
 
     def solve(self, Z0=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, newton='dense',
-              driver='host'):
+              driver='host', chol='workgroup'):
         """The script's solve (:642-669, its options tol = 1e-3, max_iter = 3000) with the batched interior-point method of
         ``hopper_ipm`` in place of IPOPT -> (Z, info); info["status"] is 'converged' only if the final error shows it.
         newton='arrow' eliminates the M sample variables from the Newton step (the path that scales with M).
         driver='device' (backend='device', either newton; 'arrow' needs precision='f64'): the iterate stays on the device
-        (``ipm.solve_group_device``, csrc/ipm_driver.hip); info["driver"] = 'device'."""
+        (``ipm.solve_group_device``, csrc/ipm_driver.hip); info["driver"] = 'device'.
+        chol: 'workgroup' or 'grid', the device Cholesky (``hopper_ipm.solve_batch``); the result does not depend on it."""
         from . import hopper_ipm
         return hopper_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter, backend=backend,
                                       callbacks=None if callbacks is None else [callbacks], verbose=verbose, newton=newton,
-                                      driver=driver)[0]
+                                      driver=driver, chol=chol)[0]
 
     def _nlp_state(self, K):
         """device-side constants of the emission: the maps (uploaded once) and, per K, the destinations zeroed / pre-filled once"""

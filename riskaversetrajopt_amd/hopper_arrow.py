@@ -238,7 +238,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     device) move nothing.  The group's models may hold friction fields of their own (``hopper_ipm.GroupFields``)."""
     name, newton = "device", "arrow"
 
-    def __init__(self, models):
+    def __init__(self, models, chol='workgroup'):
         import torch
         from . import _lib
         self._lib, self.lib = _lib, _lib.load()
@@ -246,7 +246,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         m0 = self.m0 = models[0]
         if any(m.precision != 'f64' for m in models):
             raise ValueError("the device backend needs Model(..., precision='f64')")
-        super().__init__(m0.device, len(models), "reduction", "assembly", "products")
+        super().__init__(m0.device, len(models), "reduction", "assembly", "products", chol=chol)
         st = self.st = arrow_structure(m0)
         lay = m0.nlp_layout()
         up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
@@ -575,7 +575,7 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
                 self._call("rato_hopper_arrow_cols_f64", K, M, Cn, 1, 1, p(self.dx), p(self.dfz), p(d), d.shape[1], st["r0"], p(t),
                            None, p(w["partc"]), p(w["redc"]))
                 arrow_rhsfix(Cn, nc, self.maps["qcol"], w["redc"], w["beta"], rc)
-            _ipm.chol_solve(self.L, rc[:, None, :])
+            self.chol_solve(self.L, rc[:, None, :])
             if st["saa"]:
                 xq = scatter_rows(rc, nc, w["inv_qcol"], w["xq"], st["q"])
                 arrow_scale(w["beta"], rc, nc - 1, None, w["addc"], 0)

@@ -410,12 +410,12 @@ class DeviceBackend(_ipm.DeviceBase):
     Every call serves the listed problems in ONE launch each; nothing a kernel computes for a problem depends on the others."""
     name = "device"
 
-    def __init__(self, models):
+    def __init__(self, models, chol='workgroup'):
         self.models = models
         m0 = self.m0 = models[0]
         if any(m.precision != 'f64' for m in models):
             raise ValueError("the device backend needs Model(..., precision='f64')")
-        super().__init__(m0.device, len(models))
+        super().__init__(m0.device, len(models), chol=chol)
         st = self.st = structure(m0)
         lay = m0.nlp_layout()
         self.maps = upload_maps(st, self.dev, to_value=st["to_cat"])
@@ -524,7 +524,7 @@ def _group_key(m):
 
 
 def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', callbacks=None, verbose=False, clocks=None,
-                newton='dense', driver='host'):
+                newton='dense', driver='host', chol='workgroup'):
     """Solve the models' NLPs in lockstep -> list of (Z, info), in the models' order.  The K problems share S, M and the phases;
     problems of one method form a group that moves through the K-problem kernels together (alpha and the friction fields may
     differ from problem to problem: a grid of alphas x resampled terrains is ONE group), the groups one after the other.  A
@@ -542,6 +542,9 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
                  (``ipm.solve_group_device``, backend='device' only: the iterate stays on the device, csrc/ipm_driver.hip and
                  csrc/hopper_g.hip, and the clocks hold the time to launch; info["driver"] = 'device'.  With newton='arrow' the
                  models must be on a GPU with precision='f64')
+      chol       'workgroup' (csrc/chol.hip: one workgroup per problem) or 'grid' (csrc/chol_grid.hip: every factorization a
+                 sequence of launches over the whole device; the same bits, so Z and info do not depend on it).  backend='numpy'
+                 ignores it: its Cholesky is NumPy's
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,
     dual_infeasibility, f, and the final multipliers y, zl, zu with the slacks s and the objective scale sf."""
     if backend not in ('device', 'numpy'):
@@ -549,6 +552,7 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
     if newton not in ('dense', 'arrow'):
         raise ValueError(f"newton must be 'dense' or 'arrow', got {newton!r}")
     _ipm.check_driver(driver, backend)
+    _ipm.check_chol(chol)
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
@@ -572,7 +576,7 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
     def setup(members):
         ms = [models[i] for i in members]
         cbs = None if callbacks is None else [callbacks[i] for i in members]
-        return ms, (on_device(ms) if backend == 'device' else on_host(ms, cbs))
+        return ms, (on_device(ms, chol=chol) if backend == 'device' else on_host(ms, cbs))
 
     return _ipm.solve_groups(list(groups.values()), setup, Z0s, tol, max_iter, verbose, clocks, driver=driver)
 

@@ -20,7 +20,8 @@ The driver (``Problem``, ``newton_steps``, ``solve_group``, ``solve_groups``) kn
 x_bounds(), f, grad_f and a backend through name, clock, eval_full / eval_g / matvec / tmatvec / factor / solve /
 hess_apply(idx, X) -> [W x].  It, the line search and the O(n + m) vector algebra run on the host per problem, so a problem's
 iterates do not depend on what else is in the batch.  ``Backend`` / ``DeviceBase`` hold what the backends have in common: the
-clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_solve``: csrc/chol.hip), uploads and row selection,
+clocks, the Cholesky on the host and on the device (``chol_factor`` / ``chol_solve``: csrc/chol.hip, or csrc/chol_grid.hip
+with ``chol='grid'``: the same bits from launches spread over the device), uploads and row selection,
 and ``factor`` / ``solve`` (``DeviceBase``: ``factor_t`` / ``solve_t`` too) on the normal matrix a subclass provides:
 ``normal_matrix_host(i, d, diag)`` on the host, ``normal_matrix(idx, D, diags)`` / ``normal_matrix_t(d, diag, out=)`` on the device.
 
@@ -44,30 +45,66 @@ def chol_panel_width():
     return int(_lib.load().rato_chol_panel_width())
 
 
-def chol_factor(A):
-    """rato_chol_factor_batch_f64 in place on a device fp64 tensor A (K, n, lda) (row-major lower triangle; lda >= n)
-    -> info (K,) int32 device tensor: 0, or j + 1 for the first pivot j that is not positive and finite"""
+CHOL_METHODS = ("workgroup", "grid")
+
+
+def check_chol(method, what="chol"):
+    """-> method, one of CHOL_METHODS; anything else is a ValueError (raised before any device call)"""
+    if method not in CHOL_METHODS:
+        raise ValueError(f"{what} must be one of {CHOL_METHODS}, got {method!r}")
+    return method
+
+
+def chol_grid_work(n, K, device):
+    """the scratch ``chol_factor(method='grid')`` needs for K problems of size n: a device fp64 tensor of
+    K * rato_chol_grid_work_doubles(n) doubles (contents irrelevant; empty when the query returns 0)"""
     import torch
     from . import _lib
+    return torch.empty(int(K) * int(_lib.load().rato_chol_grid_work_doubles(int(n))), dtype=torch.float64, device=device)
+
+
+def chol_factor(A, method='workgroup', work=None):
+    """rato_chol_factor_batch_f64 in place on a device fp64 tensor A (K, n, lda) (row-major lower triangle; lda >= n)
+    -> info (K,) int32 device tensor: 0, or j + 1 for the first pivot j that is not positive and finite.
+    method='grid': rato_chol_factor_grid_batch_f64 (csrc/chol_grid.hip), bitwise the same L, on ``work`` (``chol_grid_work``;
+    None = allocated here)"""
+    import torch
+    from . import _lib
+    check_chol(method, "method")
     if A.dim() != 3 or A.dtype != torch.float64 or not A.is_cuda or not A.is_contiguous() or A.shape[2] < A.shape[1] or A.shape[1] < 1:
         raise ValueError(f"A must be a contiguous device float64 tensor (K, n, lda >= n), got {tuple(A.shape)}")
     info = torch.empty(A.shape[0], dtype=torch.int32, device=A.device)
+    if method == 'grid':
+        lib = _lib.load()
+        need = A.shape[0] * int(lib.rato_chol_grid_work_doubles(A.shape[1]))
+        if work is None:
+            work = torch.empty(need, dtype=torch.float64, device=A.device)
+        elif work.dtype != torch.float64 or work.device != A.device or not work.is_contiguous() or work.numel() < need:
+            raise ValueError(f"work must be a contiguous float64 tensor of at least {need} doubles on {A.device}")
+        with torch.cuda.device(A.device):
+            _lib.check(lib.rato_chol_factor_grid_batch_f64(_lib.ptr(A), A.shape[1], A.shape[2], A.shape[0], _lib.ptr(info),
+                                                           _lib.ptr(work) if need else None, _lib.current_stream()),
+                       "rato_chol_factor_grid_batch_f64")
+        return info
     with torch.cuda.device(A.device):
         _lib.check(_lib.load().rato_chol_factor_batch_f64(_lib.ptr(A), A.shape[1], A.shape[2], A.shape[0], _lib.ptr(info),
                                                           _lib.current_stream()), "rato_chol_factor_batch_f64")
     return info
 
 
-def chol_solve(L, B):
-    """rato_chol_solve_batch_f64: L (K, n, lda) as chol_factor leaves it, B (K, nrhs, ldb >= n) device fp64, solved in place"""
+def chol_solve(L, B, method='workgroup'):
+    """rato_chol_solve_batch_f64: L (K, n, lda) as chol_factor leaves it, B (K, nrhs, ldb >= n) device fp64, solved in place.
+    method='grid': rato_chol_solve_grid_batch_f64, bitwise the same X"""
     import torch
     from . import _lib
+    check_chol(method, "method")
     if L.dim() != 3 or B.dim() != 3 or L.dtype != torch.float64 or B.dtype != torch.float64 or not (L.is_contiguous() and B.is_contiguous()) \
             or B.shape[0] != L.shape[0] or B.shape[2] < L.shape[1] or L.shape[2] < L.shape[1] or L.device != B.device or not L.is_cuda:
         raise ValueError("chol_solve: L (K, n, lda >= n) and B (K, nrhs, ldb >= n) contiguous device float64 tensors")
+    name = "rato_chol_solve_grid_batch_f64" if method == 'grid' else "rato_chol_solve_batch_f64"
     with torch.cuda.device(L.device):
-        _lib.check(_lib.load().rato_chol_solve_batch_f64(_lib.ptr(L), L.shape[1], L.shape[2], L.shape[0], _lib.ptr(B), B.shape[1],
-                                                         B.shape[2], _lib.current_stream()), "rato_chol_solve_batch_f64")
+        _lib.check(getattr(_lib.load(), name)(_lib.ptr(L), L.shape[1], L.shape[2], L.shape[0], _lib.ptr(B), B.shape[1],
+                                              B.shape[2], _lib.current_stream()), name)
     return B
 
 
@@ -120,11 +157,23 @@ class DeviceBase(Backend):
     the device with the factors of all ``n_all`` problems of the group kept in one tensor.  ``factor`` / ``solve`` / ``factor_t``
     stand on the subclass's ``normal_matrix(idx, D, diags)`` and ``normal_matrix_t(d, diag, out=)`` -> Kc (K, n, lda)."""
 
-    def __init__(self, dev, n_all, *more_clocks):
+    def __init__(self, dev, n_all, *more_clocks, chol='workgroup'):
         import torch
         super().__init__(*more_clocks)
         self.torch, self.dev, self.n_all = torch, dev, n_all
         self.slot, self.L, self.Kc = {}, None, None
+        self.chol, self.chol_work = check_chol(chol), None
+
+    def chol_factor(self, Kc):
+        """``chol_factor`` by the backend's method; the grid form's scratch is allocated once, for n_all problems of Kc's n"""
+        if self.chol != 'grid':
+            return chol_factor(Kc)
+        if self.chol_work is None:
+            self.chol_work = chol_grid_work(Kc.shape[1], max(self.n_all, Kc.shape[0]), self.dev)
+        return chol_factor(Kc, method='grid', work=self.chol_work)
+
+    def chol_solve(self, L, B):
+        return chol_solve(L, B) if self.chol != 'grid' else chol_solve(L, B, method='grid')
 
     def _sync(self):
         self.torch.cuda.synchronize(self.dev)
@@ -143,7 +192,7 @@ class DeviceBase(Backend):
     def factor_device(self, idx, Kc):
         """factors Kc (K, n, lda) in place and keeps it as the listed problems' L -> info as a list"""
         torch = self.torch
-        info = chol_factor(Kc)
+        info = self.chol_factor(Kc)
         if self.L is None:
             self.L = torch.empty((self.n_all,) + tuple(Kc.shape[1:]), dtype=torch.float64, device=self.dev)
         self.L[torch.as_tensor(list(idx), device=self.dev)] = Kc
@@ -153,7 +202,7 @@ class DeviceBase(Backend):
         """L L' x = b for the listed problems from their kept factors, B host vectors -> (K, n) host array"""
         L = self.L.index_select(0, self.torch.as_tensor(list(idx), device=self.dev))
         b = self._up(B)[:, None, :].contiguous()
-        chol_solve(L, b)
+        self.chol_solve(L, b)
         return b[:, 0].cpu().numpy()
 
     def factor(self, idx, D, diags):
@@ -183,7 +232,7 @@ class DeviceBase(Backend):
     def factor_all(self, Kc):
         """factors Kc (K, n, lda) of the whole group in place and keeps it as L -> info (K,) int32 device tensor"""
         with self.timed_t("factor"):
-            info = chol_factor(Kc)
+            info = self.chol_factor(Kc)
             self.L = Kc
         return info
 
@@ -196,7 +245,7 @@ class DeviceBase(Backend):
     def solve_t(self, B):
         """L L' x = b in place on B (K, ld >= n), a device tensor, from the factors ``factor_all`` kept"""
         with self.timed_t("solve"):
-            chol_solve(self.L, B[:, None, :])
+            self.chol_solve(self.L, B[:, None, :])
         return B
 
 

@@ -604,7 +604,7 @@ def _drone_gaussian_ipm_result(model, Z, info, trajectory, callback_s, total_s):
 
 
 def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir='results', solver='trust-constr', tol=1e-8,
-                       backend=None, driver='host'):
+                       backend=None, driver='host', chol='workgroup'):
     """The NLP of drone_gaussian.py:400-534 solved with ``scipy.optimize.minimize(method='trust-constr')`` -- the installed
     solver that takes the Hessian of lam . g, which is the script's ``hess_lagrange_dot_g``: the non-linear rows as a
     ``NonlinearConstraint(g, gL, gU, jac, hess)`` (6 equalities, the rest one-sided), the box on u and on the allocations as
@@ -619,7 +619,10 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
     'numpy', the default when ``callbacks`` are given; ``tol``: its E_0 tolerance) -> the same keys with status one of
     'converged' | 'max_iter' | 'line_search', nit = iterations, nfev = factorizations, constr_violation / optimality = the
     primal / dual parts of the final E_0, and ``info`` (``solve_batch``'s, with the multipliers).  ``driver``: 'host' or 'device'
-    (``solver='ipm'`` only: where ``solve_batch`` keeps the iterate)."""
+    (``solver='ipm'`` only: where ``solve_batch`` keeps the iterate).  ``chol``: 'workgroup' or 'grid'
+    (``solver='ipm'`` on the device: which Cholesky; the result does not depend on it)."""
+    from . import ipm as _ipm
+    _ipm.check_chol(chol)
     if driver not in ('host', 'device'):
         raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
     if solver not in ('trust-constr', 'ipm'):
@@ -634,7 +637,7 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
         t0 = time.perf_counter()
         (Z, info), = drone_gaussian_ipm.solve_batch([model], [Z0], tol=tol, max_iter=int(maxiter), backend=backend,
                                                     callbacks=None if callbacks is None else [callbacks], clocks=clocks,
-                                                    driver=driver)
+                                                    driver=driver, chol=chol)
         total = time.perf_counter() - t0
         trajectory = (model.device_callbacks() if callbacks is None else callbacks)["trajectory"]
         return _drone_gaussian_ipm_result(model, Z, info, trajectory, clocks["callbacks"], total)
@@ -689,13 +692,13 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
 
 def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='results', M_mc=10000, seed=0, maxiter=3000,
                               saa_iters=60, saa_M=50, device='cuda:0', solver='trust-constr', tol=1e-8, clocks=None,
-                              driver='host'):
+                              driver='host', chol='workgroup'):
     """The reference's drone Gaussian baseline (drone_gaussian.py:400-534) and the third block of the drone Monte-Carlo report
     (drone_risk.py:742-761) as one call.  The start of every alpha is the SAA repeat-0 solution
     ``results_dir``/drone_alpha=<alpha>_repeat=0.npy, read where it exists and made by ``drone_saa_experiment`` (one repeat)
     where it does not; each alpha is solved by ``run_drone_gaussian`` (``solver='ipm'``: all alphas in ONE
     ``drone_gaussian_ipm.solve_batch`` call on the device, whose clocks ``clocks`` receives and whose ``driver`` is 'host' or
-    'device') and written to drone_gaussian_alpha=<alpha>.npy as
+    'device' and whose ``chol`` is 'workgroup' or 'grid') and written to drone_gaussian_alpha=<alpha>.npy as
     (us, xs); then ONE ``eval_batch_device`` call of a fresh ``drone_risk.Model`` of M_mc samples (drawn under
     ``np.random.seed(seed)``) over the solutions.  Per alpha percentage_safe = mean(max constraint <= 1e-6), as the block
     computes it, and monte_carlo_cost.
@@ -705,6 +708,8 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
     from . import drone_params as P
     from .drone_utils import sample_uncertain_parameters
     alphas = [float(a) for a in alphas]
+    from . import ipm as _ipm
+    _ipm.check_chol(chol)
     if driver not in ('host', 'device'):
         raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
     if driver == 'device' and solver != 'ipm':
@@ -723,7 +728,7 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
         models = [drone_gaussian.Model(S, alpha=a, device=device) for a in alphas]
         ck = {} if clocks is None else clocks
         sols = drone_gaussian_ipm.solve_batch(models, tol=tol, max_iter=int(maxiter), backend='device', clocks=ck,
-                                              results_dir=results_dir, driver=driver)
+                                              results_dir=results_dir, driver=driver, chol=chol)
         for m, (Z, info) in zip(models, sols):
             results.append(_drone_gaussian_ipm_result(m, Z, info, m.device_callbacks()["trajectory"],
                                                       ck["callbacks"] / len(models), ck["wall"] / len(models)))
@@ -745,14 +750,14 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
             "wall_s": wall}
 
 
-def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device', newton='dense', driver='host'):
+def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device', newton='dense', driver='host', chol='workgroup'):
     """The hopper script's solve block (hopper.py:642-670) for one model: ``hopper_ipm.solve_batch`` in IPOPT's place, from
     ``Z0`` (default ``model.initial_guess()``) -> dict(Z, xs (S+1, 8), us (S, 4), status, info, total_s).  status is
     'converged' only if the final error E_0 <= tol shows it.  newton: 'dense' or 'arrow' (``hopper_ipm.solve_batch``).
     ``driver``: 'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either
-    newton, 'arrow' with a precision='f64' model)."""
+    newton, 'arrow' with a precision='f64' model).  ``chol``: 'workgroup' or 'grid' (the device Cholesky)."""
     t0 = time.perf_counter()
-    Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend, newton=newton, driver=driver)
+    Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend, newton=newton, driver=driver, chol=chol)
     xs, us = model.convert_z_to_xs_us_mats(Z)
     return {"Z": Z, "xs": xs, "us": us, "status": info["status"], "info": info, "total_s": time.perf_counter() - t0}
 
@@ -783,14 +788,18 @@ def hopper_saa_start(model, xs, us):
 
 
 def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=1, results_dir=None, tol=1e-3, max_iter=3000,
-                      backend='device', device='cuda:0', clocks=None, newton='dense', fields=None, driver='host'):
+                      backend='device', device='cuda:0', clocks=None, newton='dense', fields=None, driver='host',
+                      chol='workgroup'):
     """The hopper script's two runs (hopper.py:455-680) as one call: the friction fields under ``RandomState(seed)`` (:70-74),
     the baseline from ``initial_guess()``, then every alpha of the SAA problem in ONE lockstep batch from the baseline's
     solution (:465-479).  With ``results_dir`` the files hopper_base_results.npy and hopper_saa_alpha=<a>_results.npy are
     written (xs then us, ``save_results``), whatever the status.  ``fields``: (intensities, thetas, taus), each (M, 30), in place
     of the draw; ``newton``: 'dense' or 'arrow' (``hopper_ipm.solve_batch``: 'arrow' is the one that scales with M); ``driver``:
     'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either newton).
-    -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)"""
+    -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)
+    ``chol``: 'workgroup' or 'grid', the device Cholesky of both runs (``hopper_ipm.solve_batch``; the results do not depend on it)."""
+    from . import ipm as _ipm
+    _ipm.check_chol(chol)
     from . import hopper, hopper_ipm
     alphas = [float(a) for a in alphas]
     if fields is None:
@@ -799,13 +808,13 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
     base_model = hopper.Model(M, 'baseline', S=S, fields=fields, device=device, precision='f64')
     c0 = {}
     (Zb, ib), = hopper_ipm.solve_batch([base_model], tol=tol, max_iter=max_iter, backend=backend, clocks=c0,
-                                        newton=newton, driver=driver)
+                                        newton=newton, driver=driver, chol=chol)
     xs, us = base_model.convert_z_to_xs_us_mats(Zb)
     base = {"Z": Zb, "xs": xs, "us": us, "status": ib["status"], "info": ib}
     models = [hopper.Model(M, 'saa', a, S=S, fields=fields, device=device, precision='f64') for a in alphas]
     c1 = {}
     sols = hopper_ipm.solve_batch(models, [hopper_saa_start(m, xs, us) for m in models], tol=tol, max_iter=max_iter,
-                                  backend=backend, clocks=c1, newton=newton, driver=driver) if models else []
+                                  backend=backend, clocks=c1, newton=newton, driver=driver, chol=chol) if models else []
     results = []
     for m, (Z, info) in zip(models, sols):
         x, u = m.convert_z_to_xs_us_mats(Z)
@@ -841,7 +850,8 @@ HOPPER_SAA_REPORT_ARRAYS = ("alphas", "status", "jump", "safe_fraction", "var", 
 
 
 def hopper_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), num_repeats=30, M=30, S=30, seed=1, M_mc=10000, results_dir=None,
-                          tol=1e-3, max_iter=3000, newton='dense', driver='host', device='cuda:0', clocks=None):
+                          tol=1e-3, max_iter=3000, newton='dense', driver='host', device='cuda:0', clocks=None,
+                          chol='workgroup'):
     """The hopper's SAA study over resampled terrains, shaped like ``drone_saa_experiment`` / ``driving_saa_experiment``: R draws
     of the friction fields (``draw_hopper_saa_fields``), the baseline solved once from ``initial_guess()`` (its fields are zeroed,
     so it does not depend on the draw), then all A x R SAA problems -- alpha-major, every repeat on its own fields -- in ONE
@@ -853,13 +863,15 @@ def hopper_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), num_repeats=3
     of str, jump (A, R) = x_S[0], safe_fraction / var / avar (A, R), wall_s).
     With ``results_dir``: hopper_saa_alpha=<a>_repeat=<r>_results.npy per problem (xs then us, ``save_results``) and one
     hopper_saa_grid_report.npy holding, in this order, alphas (A,), status (A, R), jump, safe_fraction, var, avar (each (A, R)):
-    ``load_results(path, 6)``."""
+    ``load_results(path, 6)``.  ``chol``: 'workgroup' or 'grid', the device Cholesky (the results do not depend on it)."""
     from . import hopper, hopper_ipm
+    from . import ipm as _ipm
+    _ipm.check_chol(chol)
     alphas = [float(a) for a in alphas]
     A, R = len(alphas), int(num_repeats)
     draws, mc_fields = draw_hopper_saa_fields(R, M, M_mc, seed)
     t0 = time.perf_counter()
-    kw = dict(tol=tol, max_iter=max_iter, backend='device', newton=newton, driver=driver)
+    kw = dict(tol=tol, max_iter=max_iter, backend='device', newton=newton, driver=driver, chol=chol)
     zero = np.zeros((M, hopper.num_mu_features))                 # what Model makes of any baseline's fields
     base_model = hopper.Model(M, 'baseline', S=S, fields=(zero, zero, zero), device=device, precision='f64')
     c0, c1 = {}, {}

@@ -32,6 +32,15 @@ the split of a lockstep iteration.
 
     python tools/drone_gaussian_bench.py --solver ipm --driver both [--solves 7]
 
+With ``--solver ipm --chol {workgroup,grid,both}`` it measures the interior-point solve under one or both Choleskys (DESIGN
+§7.ak: csrc/chol.hip, one workgroup per problem, or csrc/chol_grid.hip, one launch per panel over the whole device; the same
+bits) and writes profiles/drone_gaussian_solve_chol_grid.json: the same batch under ``--driver`` (default device; with ``both``,
+both), the methods in this process on one board, each after a warm-up solve, the median of ``--solves`` (default 5 here)
+solves with min and max, the iterations per alpha, the split of a lockstep iteration from one more solve with a device-wide
+wait behind every block, and whether every (Z, info) is bitwise the same under both methods.
+
+    python tools/drone_gaussian_bench.py --solver ipm --chol both [--driver device] [--solves 5]
+
 Prints one JSON line.  There is no CPU fallback: without a GPU the kernel timings fail.
 """
 import argparse
@@ -159,6 +168,64 @@ def driver_bench(args):
     write(out, path)
 
 
+def same_solution(r0, r1):
+    (Z0, i0), (Z1, i1) = r0, r1
+    eq = lambda a, b: a.tobytes() == b.tobytes() if isinstance(a, np.ndarray) else a == b
+    return Z0.tobytes() == Z1.tobytes() and set(i0) == set(i1) and all(eq(i0[k], i1[k]) for k in i0)
+
+
+def chol_bench(args):
+    """the S = 20 batch under one or both Choleskys -> profiles/drone_gaussian_solve_chol_grid.json"""
+    import torch
+    from riskaversetrajopt_amd import drone_gaussian as DG
+    from riskaversetrajopt_amd import drone_gaussian_ipm, scp
+    S, alphas = 20, (0.05, 0.1, 0.2, 0.3)
+    path = args.out or os.path.join(ROOT, "profiles", "drone_gaussian_solve_chol_grid.json")
+    solves = 5 if args.solves is None else args.solves
+    out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": list(alphas), "tol": args.tol, "maxiter": args.maxiter,
+           "start": "SAA repeat 0 (drone_saa_experiment, M = 50, 60 iterations, seed 0)", "solves": solves, "drivers": {}}
+    drivers = ("host", "device") if args.driver == "both" else (args.driver or "device",)
+    methods = ("workgroup", "grid") if args.chol == "both" else (args.chol,)
+    scp.drone_gaussian_experiment(alphas, S=S, results_dir=args.results_dir, maxiter=3, solver='ipm', tol=args.tol)   # the SAA starts
+    models = [DG.Model(S, alpha=a) for a in alphas]
+    Z0s = [m.initial_guess(args.results_dir) for m in models]
+    out["n"] = int(models[0].nvar)
+    for d in drivers:
+        solve = lambda c, ck=None: drone_gaussian_ipm.solve_batch(models, Z0s, tol=args.tol, max_iter=args.maxiter, driver=d,
+                                                                  clocks=ck, chol=c)
+        rec, sols = {}, {}
+        for c in methods:
+            solve(c)                                                 # warm-up of this method: code objects, allocator
+        torch.cuda.synchronize()
+        for c in methods:
+            walls = []
+            for _ in range(solves):
+                t0 = time.perf_counter()
+                sols[c] = solve(c)
+                walls.append(time.perf_counter() - t0)
+            rounds = max(1, max(info["iterations"] for _, info in sols[c]))
+            drone_gaussian_ipm.DeviceBackend.sync_clocks = True      # one more solve, a device-wide wait behind every block
+            try:
+                clocks = {}
+                solve(c, clocks)
+            finally:
+                drone_gaussian_ipm.DeviceBackend.sync_clocks = False
+            rec[c] = {"wall_ms": [1e3 * w for w in walls], "median_wall_ms": 1e3 * float(np.median(walls)),
+                      "min_wall_ms": 1e3 * min(walls), "max_wall_ms": 1e3 * max(walls), "lockstep_iterations": rounds,
+                      "median_ms_per_iteration": 1e3 * float(np.median(walls)) / rounds,
+                      "per_alpha": [{"alpha": a, "status": info["status"], "iterations": info["iterations"],
+                                     "factorizations": info["factorizations"], "E0": info["E0"], "f": info["f"]}
+                                    for a, (_, info) in zip(alphas, sols[c])],
+                      "split_ms_per_iteration_sync_clocks": {k: 1e3 * v / rounds for k, v in clocks.items()}}
+        if len(methods) == 2:
+            w, g = rec["workgroup"], rec["grid"]
+            rec["grid_is_bitwise_workgroup"] = all(same_solution(a, b) for a, b in zip(sols["grid"], sols["workgroup"]))
+            rec["workgroup_over_grid"] = w["median_wall_ms"] / g["median_wall_ms"]
+            rec["grid_wins"], rec["grid_loses"] = g["max_wall_ms"] < w["min_wall_ms"], g["min_wall_ms"] > w["max_wall_ms"]
+        out["drivers"][d] = rec
+    write(out, path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--maxiter", type=int, default=3000)
@@ -169,14 +236,22 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--results-dir", default="results")
     ap.add_argument("--driver", choices=("host", "device", "both"), default=None)
-    ap.add_argument("--solves", type=int, default=7)
+    ap.add_argument("--solves", type=int, default=None, help="timed solves per driver (default 7) or per Cholesky (default 5)")
+    ap.add_argument("--chol", choices=("workgroup", "grid", "both"), default=None,
+                    help="measure the interior-point solve under the Cholesky method(s) instead (with --solver ipm)")
     args = ap.parse_args()
     if args.driver is not None and args.solver != "ipm":
         raise SystemExit("--driver measures the interior-point solve: use it with --solver ipm")
+    if args.chol is not None and args.solver != "ipm":
+        raise SystemExit("--chol measures the interior-point solve: use it with --solver ipm")
 
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("drone_gaussian_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.chol is not None:
+        return chol_bench(args)
+    if args.solves is None:
+        args.solves = 7
     if args.driver is not None:
         return driver_bench(args)
     if args.solver is not None:

@@ -39,6 +39,14 @@ slowest member's; repeat by repeat: the sum over the draws of each draw's slowes
 iteration count, the status counts, and whether every (Z, info) of the batch is bitwise the repeat-by-repeat one.  The file is
 rewritten after every measurement, and a later call with another M or newton adds to it.
 
+``--chol {workgroup,grid,both}`` measures the solve under one or both Choleskys instead (csrc/chol.hip, one
+workgroup per problem, or csrc/chol_grid.hip, one launch per panel over the whole device; the same bits), into
+profiles/hopper_solve_chol_grid.json: under ``--driver`` (default device) and ``--newton``, per M of ``--M``, the baseline from
+``initial_guess()`` and the alphas as one batch from the host driver's baseline solution -- or, with ``--repeats R``, the A R
+problems of the SAA grid as ONE batch.  The methods run in one process, a warm-up solve each, then ``--solves`` timed solves each
+(median, min, max), the per-iteration split of one more solve with ``sync_clocks`` (what is recorded today), and whether every
+(Z, info) is bitwise the same under both.  The file is rewritten after every run, and a later call adds its runs to it.
+
 Prints one JSON line.  There is no CPU fallback: without a GPU nothing is measured.
 """
 import argparse
@@ -309,6 +317,90 @@ def grid_bench(args):
     print(write_profile(out, args.out))
 
 
+def chol_bench(args):
+    """runs under one or both Choleskys -> profiles/hopper_solve_chol_grid.json"""
+    import time
+
+    import torch
+    from riskaversetrajopt_amd import hopper, hopper_ipm, ipm, scp
+    S, alphas, newton, R = args.S, [float(a) for a in args.alphas], args.newton, args.repeats
+    driver = "device" if args.driver in (None, "both") else args.driver
+    methods = ("workgroup", "grid") if args.chol == "both" else (args.chol,)
+    out = {"device": torch.cuda.get_device_name(0), "S": S, "tol": 1e-3, "max_iter": 3000, "solves": args.solves,
+           "saa_start": "the host driver's baseline solution", "runs": {}}
+    if args.out and os.path.exists(args.out):                        # a later call adds its runs to the file of an earlier one
+        with open(args.out) as f:
+            old = json.loads(f.readline())
+        if all(old.get(k) == out[k] for k in ("device", "S", "tol", "max_iter", "solves")):
+            out["runs"] = old.get("runs", {})
+
+    def same(r0, r1):
+        (Z0, i0), (Z1, i1) = r0, r1
+        eq = lambda a, b: a.tobytes() == b.tobytes() if isinstance(a, np.ndarray) else a == b
+        return Z0.tobytes() == Z1.tobytes() and set(i0) == set(i1) and all(eq(i0[k], i1[k]) for k in i0)
+
+    def measure(models, Z0s):
+        solve = lambda c, ck=None: hopper_ipm.solve_batch(models, Z0s, driver=driver, clocks=ck, newton=newton, chol=c)
+        rec, sols = {"problems": len(models), "alphas": sorted({float(m.alpha) for m in models if m.method == 'saa'})}, {}
+        for c in methods:
+            solve(c)                                                 # warm-up of this method: code objects, maps, allocator
+        torch.cuda.synchronize()
+        for c in methods:
+            walls = []
+            for _ in range(args.solves):
+                t0 = time.perf_counter()
+                sols[c] = solve(c)
+                walls.append(time.perf_counter() - t0)
+            rounds = max(1, max(info["iterations"] for _, info in sols[c]))
+            synced = {}
+            ipm.DeviceBase.sync_clocks = True                        # one more solve, a device-wide wait behind every block
+            try:
+                solve(c, synced)
+            finally:
+                ipm.DeviceBase.sync_clocks = False
+            status = {}
+            for _, info in sols[c]:
+                status[info["status"]] = status.get(info["status"], 0) + 1
+            rec[c] = {"wall_ms": [1e3 * w for w in walls], "median_ms_per_batch": 1e3 * float(np.median(walls)),
+                      "min_ms_per_batch": 1e3 * min(walls), "max_ms_per_batch": 1e3 * max(walls), "lockstep_iterations": rounds,
+                      "median_ms_per_iteration": 1e3 * float(np.median(walls)) / rounds, "status": status,
+                      "factorizations": int(sum(info["factorizations"] for _, info in sols[c])),
+                      "split_ms_per_iteration_sync_clocks": {k: 1e3 * v / rounds for k, v in synced.items()}}
+        if len(methods) == 2:
+            w, g = rec["workgroup"], rec["grid"]
+            rec["grid_is_bitwise_workgroup"] = all(same(a, b) for a, b in zip(sols["grid"], sols["workgroup"]))
+            rec["workgroup_over_grid"] = w["median_ms_per_batch"] / g["median_ms_per_batch"]
+            rec["grid_wins"] = g["max_ms_per_batch"] < w["min_ms_per_batch"]
+            rec["grid_loses"] = g["min_ms_per_batch"] > w["max_ms_per_batch"]
+        return rec
+    for M in [int(m) for m in str(args.M).split(",")]:
+        mk = lambda method, a, fields: hopper.Model(M, method, a, S=S, fields=fields, precision='f64')
+        key = "M=%d,newton=%s,driver=%s" % (M, newton, driver)
+        if R is not None:                                            # the SAA grid as one batch (DESIGN §7.aj)
+            draws, _ = scp.draw_hopper_saa_fields(R, M, 1, seed=1)
+            zero = np.zeros((M, hopper.num_mu_features))
+            base = mk('baseline', 0.1, (zero, zero, zero))
+            (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)
+            xs, us = base.convert_z_to_xs_us_mats(Zb)
+            models = [mk('saa', a, draws[r]) for r in range(R) for a in alphas]
+            runs = {key + ",repeats=%d" % R: (models, [scp.hopper_saa_start(m, xs, us) for m in models])}
+        else:
+            fields = tuple(f[:M] for f in script_fields(M)[0]) if newton == "arrow" else \
+                hopper.sample_friction_fields(M, np.random.RandomState(1))
+            base = mk('baseline', 0.1, fields)
+            (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)
+            xs, us = base.convert_z_to_xs_us_mats(Zb)
+            saa = [mk('saa', a, fields) for a in alphas]
+            runs = {key + ",baseline": ([base], [base.initial_guess()]),
+                    key + ",saa": (saa, [scp.hopper_saa_start(m, xs, us) for m in saa])}
+        for name, (models, Z0s) in runs.items():
+            if models:
+                out["runs"][name] = measure(models, Z0s)
+                write_profile(out, args.out)
+                print("%s done" % name, file=sys.stderr, flush=True)
+    print(write_profile(out, args.out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--S", type=int, default=30)
@@ -321,10 +413,18 @@ def main():
     ap.add_argument("--solves", type=int, default=5, help="with --driver or --repeats: timed solves per run and driver")
     ap.add_argument("--repeats", type=int, default=None,
                     help="measure the grid of alphas x this many draws of the fields as one batch against repeat by repeat instead")
+    ap.add_argument("--chol", choices=("workgroup", "grid", "both"), default=None,
+                    help="measure the solve under the Cholesky method(s) instead (--driver, default device; --newton; --repeats)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("hopper_solve_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.chol is not None:
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "hopper_solve_chol_grid.json")
+        if args.repeats is not None and args.repeats < 1:
+            raise SystemExit("--repeats needs at least one draw")
+        return chol_bench(args)
     if args.out is None and args.repeats is not None:
         args.out = os.path.join(ROOT, "profiles", "hopper_saa_grid.json")
     if args.out is None:
