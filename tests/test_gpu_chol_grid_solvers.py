@@ -113,6 +113,51 @@ def test_an_unknown_method_is_refused_by_the_backends():
         ipm.DeviceBase(torch.device(DEV), 1, chol='panel')
 
 
+def test_device_base_scatters_a_failed_retry_and_gathers_a_subset_under_the_grid_cholesky():
+    """the twin of test_hopper_ipm_gpu.py::test_device_base_scatters_a_retry_and_gathers_a_subset, made harsher: all four problems
+    factored at n = 65, problem 2 again with an indefinite matrix (info != 0, the other three factors survive), then with a
+    definite one as a delta_w retry does, then a solve for problems 0, 2, 3.  The factors and X bitwise those of a
+    ``chol='workgroup'`` DeviceBase fed the same sequence; the scratch made once for four problems and reused for the subsets"""
+    import torch
+    from riskaversetrajopt_amd import _lib, ipm
+    from test_gpu_chol_grid import padded as tri_padded, spd
+    n_all, n, j_bad = 4, 65, 40
+    lda = n + PAD
+    As = [spd("bbt", n, 650 + k) for k in range(n_all)]
+    indefinite = spd("bbt", n, 658)
+    indefinite[j_bad, j_bad] = -1.0
+    first, bad, retry = tri_padded(As, lda), tri_padded([indefinite], lda), tri_padded([spd("graded", n, 659)], lda)
+    B = list(np.random.RandomState(65).uniform(-1, 1, (3, n)))
+    got = {}
+    for method in METHODS:
+        be = ipm.DeviceBase(torch.device(DEV), n_all, chol=method)
+        assert be.factor_device([0, 1, 2, 3], first.clone()) == [0] * n_all
+        kept = be.L.cpu().numpy().copy()
+        ptrs = [None if be.chol_work is None else be.chol_work.data_ptr()]
+        info_bad = be.factor_device([2], bad.clone())
+        assert info_bad[0] != 0
+        after = be.L.cpu().numpy()
+        assert all(after[k].tobytes() == kept[k].tobytes() for k in (0, 1, 3))   # the failure stays in row 2
+        ptrs.append(None if be.chol_work is None else be.chol_work.data_ptr())
+        assert be.factor_device([2], retry.clone()) == [0]
+        ptrs.append(None if be.chol_work is None else be.chol_work.data_ptr())
+        Lh = be.L.cpu().numpy()
+        assert all(Lh[k].tobytes() == kept[k].tobytes() for k in (0, 1, 3)) and Lh[2].tobytes() != kept[2].tobytes()
+        X = be.solve_device([0, 2, 3], B)
+        assert X.shape == (3, n) and np.all(np.isfinite(X))
+        got[method] = (info_bad, lower_bytes(be.L, n), X.tobytes())
+        if method == 'grid':
+            assert be.chol_work.numel() == n_all * _lib.load().rato_chol_grid_work_doubles(n)
+            assert ptrs[0] is not None and ptrs[0] == ptrs[1] == ptrs[2]     # allocated once, for four problems
+        else:
+            assert be.chol_work is None
+    assert got["grid"] == got["workgroup"]
+    one = retry.clone()                                               # row 2 is the retry's factor, not the failed one's
+    assert ipm.chol_factor(one).cpu().tolist() == [0]
+    r, c = np.tril_indices(n)
+    assert np.ascontiguousarray(one.cpu().numpy()[:, r, c]).tobytes() == np.frombuffer(got["grid"][1]).reshape(n_all, -1)[2:3].tobytes()
+
+
 # ---- end to end --------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def hopper_problems():
@@ -132,6 +177,11 @@ def test_hopper_solve_is_bitwise_under_the_grid_cholesky(newton, driver):
     kw = dict(newton=newton, driver=driver, max_iter=1000)
     ref = hopper_ipm.solve_batch(e["models"], e["Z0s"], chol='workgroup', **kw)
     got = hopper_ipm.solve_batch(e["models"], e["Z0s"], chol='grid', **kw)
+    retries = [info["factorizations"] - info["iterations"] for _, info in ref]
+    print(f"newton={newton} driver={driver}: delta_w retries of the chol='workgroup' run per problem {retries}")
+    # the reference run met failed factorizations, so the bitwise match below covers the grid form's failing path and the delta_w
+    # retry on its kept scratch; no problem had to be added for it: alpha 0.1 / 0.5 show 40 / 60 retries (32 / 34 iterations)
+    assert max(retries) > 0
     for k, (mm, Z0) in enumerate(zip(e["models"], e["Z0s"])):
         assert got[k][1]["status"] == "converged"
         assert bitwise(got[k], ref[k]), ("chol='grid' differs from chol='workgroup'", k)

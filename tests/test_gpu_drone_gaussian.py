@@ -170,6 +170,30 @@ def test_batch_is_bit_identical_to_single_launches(S):
         assert np.array_equal(hess[k], m.hessian_device(Z[k:k + 1], lam[k:k + 1]).cpu().numpy()[0]), k
 
 
+@pytest.mark.parametrize("K", [64, 65, 130])
+def test_trajectory_of_more_problems_than_one_block_holds(K):
+    """``drone_gaussian_trajectory_kernel`` takes the problem number from the lane, 64 problems a block: a full block, one problem
+    into the second, and a ragged third.  K distinct blends of the two control sequences of ``_drone_gaussian.problems``;
+    every row of mus / Sigmas bitwise its K = 1 launch, rows 0, 63, 64 and K - 1 against the restatement"""
+    S = 3
+    a = np.arange(K) / (K - 1.0)
+    Z = np.stack([R.make_z(a[k] * R.us_wave(S) + (1.0 - a[k]) * R.us_swerve(S),
+                           R.alphas_spread(S, ALPHA) if k % 2 == 0 else R.alphas_uniform(S, ALPHA)) for k in range(K)])
+    m = _model(S)
+    batch = {k: v.cpu().numpy() for k, v in m.linearize_device(Z, want_trajectory=True).items()}
+    assert batch["mus"].shape == (K, S + 1, 6) and batch["Sigmas"].shape == (K, S + 1, 6, 6)
+    for k in range(K):
+        one = m.linearize_device(Z[k:k + 1], want_trajectory=True)
+        for key in ("mus", "Sigmas"):
+            assert batch[key][k].tobytes() == one[key].cpu().numpy()[0].tobytes(), (key, k)
+    for k in sorted({0, 63, 64, K - 1} & set(range(K))):
+        ref = R.evaluate(Z[k], S)
+        for key in ("mus", "Sigmas"):
+            err = _scaled(batch[key][k], ref[key])
+            print(f"S={S} K={K} k={k} {key}: {err:.3e}")
+            assert err <= TOL, (key, k, err)
+
+
 @pytest.mark.parametrize("S", [5, 22])
 def test_null_trajectory_leaves_the_rest_bit_identical(S):
     with_traj, without = _launch(S, 3, want_trajectory=True), _launch(S, 3, want_trajectory=False)

@@ -156,9 +156,15 @@ def same(a, b):
     return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a if a[k] is not None)
 
 
+def shapes(Ms, at_the_limit=(33, 65)):
+    """(M, Cn): every M at Cn = 1, 4, 20, and Cn = 50, the entry points' limit, at M = 33 and 65 (two and three chunks, the last
+    of one sample).  At Cn = 50 the reduction asks for 32 (5 Cn + 3) doubles = 64,768 bytes of dynamic LDS and the right-hand
+    side's fix-up uses 252 of its 256 lanes"""
+    return [(M, Cn) for Cn in (1, 4, 20) for M in Ms] + [(M, 50) for M in at_the_limit]
+
+
 @pytest.mark.parametrize("saa", [True, False], ids=["saa", "baseline"])
-@pytest.mark.parametrize("Cn", [1, 4, 20])
-@pytest.mark.parametrize("M", sample_counts())
+@pytest.mark.parametrize("M,Cn", shapes(sample_counts()))
 def test_kernels_on_designed_buffers(M, Cn, saa):
     assert chunk() == 32 and int(lib()[1].rato_hopper_arrow_nchunks(M)) == -(-M // 32)
     D = Designed(M, Cn, saa, 1000 * Cn + M)
@@ -308,6 +314,9 @@ def test_bad_arguments_return_einval():
     assert L.rato_hopper_arrow_cols_f64(1, 5, 2, 1, 1, b, b, b, D.ldd, D.r0, None, b, b, b, s) == EINVAL          # mode 1 without t
     assert L.rato_hopper_arrow_rows_f64(1, 5, 2, 1, 0, b, b, b, b, None, 0, D.r0, None, b, D.r0 + 9, b, b, s) == EINVAL   # ldo
     assert L.rato_hopper_arrow_rows_f64(1, 5, 2, 1, 1, b, b, b, b, None, D.ldd, D.r0, b, b, 5, None, None, s) == EINVAL   # no d
+    assert L.rato_hopper_arrow_rows_f64(1, 5, 2, 1, 0, b, b, b, b, None, 0, D.r0, None, b, D.ldd, b, b, s) == 0          # C = 2 is served,
+    assert L.rato_hopper_arrow_rows_f64(1, 5, 51, 1, 0, b, b, b, b, None, 0, D.r0, None, b, D.r0 + 5 * 51, b, b, s) == EINVAL   # 51 is not
+    assert L.rato_hopper_arrow_rows_f64(1, 5, 51, 1, 1, b, b, b, b, b, D.r0 + 5 * 51, D.r0, b, b, 5, None, None, s) == EINVAL
     assert L.rato_hopper_arrow_edot_f64(1, 0, b, b, b, b, s) == EINVAL and L.rato_hopper_arrow_eapply_f64(1, 5, b, b, None, b, s) == EINVAL
     torch.cuda.synchronize()
 

@@ -16,7 +16,7 @@ import _hopper_ipm_driver as HD
 import _hopper_nlp as R
 from _drone_gaussian_ipm import padded
 from _hopper_ipm import gamma
-from test_gpu_hopper_arrow import Designed, baseline_small, device_model      # noqa: F401  (baseline_small is a fixture)
+from test_gpu_hopper_arrow import Designed, baseline_small, device_model, shapes      # noqa: F401  (baseline_small is a fixture)
 from test_gpu_hopper_ipm_driver import bitwise, nothing_moves_to_the_host, within
 
 pytestmark = pytest.mark.gpu
@@ -123,8 +123,7 @@ def same_runs(a, b, rows=None):
 
 
 @pytest.mark.parametrize("saa", [True, False], ids=["saa", "baseline"])
-@pytest.mark.parametrize("Cn", [1, 4, 20])
-@pytest.mark.parametrize("M", [1, 2, 32, 33, 65, 161])
+@pytest.mark.parametrize("M,Cn", shapes([1, 2, 32, 33, 65, 161]))
 def test_fixup_kernels_on_designed_buffers(M, Cn, saa):
     from riskaversetrajopt_amd import _lib
     assert int(_lib.load().rato_hopper_arrow_chunk()) == 32           # M: under, at and over one chunk boundary, and several
@@ -176,6 +175,39 @@ def test_fixup_kernels_on_designed_buffers(M, Cn, saa):
     assert r["r_rc"][:, :nc].tobytes() == rc.tobytes() and nan_pad(r["r_rc"], nc)
     # 6. addc = beta * xc[:, nc - 1]
     assert r["addc"].tobytes() == (beta * F.xc[:, -1]).tobytes() and nan_pad(r["a_xc"], nc)
+
+
+@pytest.mark.parametrize("K", [256, 257, 600])
+def test_lane_numbered_fixups_past_their_first_block(K):
+    """``arrow_scale_kernel`` and ``arrow_kkbeta_kernel`` take the problem number from the lane, 256 problems a block: a full
+    block, one problem into the second, and a ragged third.  Graded inputs on padded strides, NaN wherever no kernel may read or
+    write; every problem bitwise the NumPy line of ``test_fixup_kernels_on_designed_buffers``"""
+    import torch
+    m = bind()
+    rng = np.random.RandomState(K)
+    g12 = lambda *s: rng.randn(*s) * 10.0 ** rng.uniform(-6, 6, s)
+    pos12 = lambda *s: 10.0 ** rng.uniform(-6, 6, s)
+    nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float64, device=DEV)
+    # out[k][ocol] = a[k] x[k][col] + add[k], and without add into a vector
+    nx, col, ldo, ocol = 7, 6, 5, 2
+    a, x, add = g12(K), g12(K, nx), g12(K)
+    xt, out, vec = up(x, nx + PAD), nan(K, ldo), nan(K)
+    m.arrow_scale(up(a), xt, col, up(add), out, ocol)
+    m.arrow_scale(up(a), xt, col, None, vec, 0)
+    oh = out.cpu().numpy()
+    assert oh[:, ocol].tobytes() == (a * x[:, col] + add).tobytes() and np.all(np.isnan(np.delete(oh, ocol, axis=1)))
+    assert vec.cpu().numpy().tobytes() == (a * x[:, col]).tobytes()
+    assert np.all(np.isnan(xt.cpu().numpy()[:, nx:]))
+    # kk = d0 / (1 + d0 s), beta = d0 malpha: d0 in column rr of d, s behind G, w and a in red
+    Cn, rr = 1, 4
+    q = 5 * Cn + 2
+    npart, at = q * (q + 1) // 2 + 2 * q + 1 + 15 * Cn, q * (q + 1) // 2 + 2 * q
+    d0, s, ma = pos12(K), pos12(K), K * rng.uniform(0.05, 0.75, K)
+    dh, redh = np.full((K, rr + 1 + PAD), np.nan), np.full((K, npart + PAD), np.nan)
+    dh[:, rr], redh[:, at] = d0, s
+    kk, beta = nan(K), nan(K)
+    m.arrow_kkbeta(Cn, up(dh), rr, up(redh), up(ma), kk, beta)
+    assert kk.cpu().numpy().tobytes() == (d0 / (1.0 + d0 * s)).tobytes() and beta.cpu().numpy().tobytes() == (d0 * ma).tobytes()
 
 
 def test_fixup_entry_points_answer_bad_arguments_with_einval():

@@ -149,10 +149,11 @@ def lower(Lh, n):
 
 @pytest.mark.parametrize("kind", ["bbt", "graded"])
 @pytest.mark.parametrize("pad", [0, 3])
-@pytest.mark.parametrize("n", [288, 289, 321, 400])
+@pytest.mark.parametrize("n", [288, 289, 321, 400, 545, 577])
 def test_cholesky_and_solve_backward_error_at_the_workloads_sizes(n, pad, kind):
     """the assertions of test_cholesky_and_solve_backward_error with K = 2: 288 is the last size of one trip, 289 the first of
-    two in all three loops, 321 one panel more, 400 the workload's"""
+    two in all three loops, 321 one panel more, 400 the workload's; 545 and 577 take a third trip (from row 32 + 512), and 577
+    ends in a diagonal block of one row"""
     import torch
     m = chol()
     assert NB() == 32
