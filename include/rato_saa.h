@@ -1580,6 +1580,32 @@ int rato_ipm_step_setup_f64(const rato_ipm_state* st, const double* Hdv, int64_t
 int rato_ipm_trial_f64(const rato_ipm_state* st, void* stream);
 int rato_ipm_accept_f64(const rato_ipm_state* st, const double* gt, int64_t ldg, void* stream);
 
+/* ---- The same phases spread over the rows (csrc/ipm_driver_grid.hip; ipm.DeviceState(vec='grid'), driver='device_grid';
+ * DESIGN §7.al).  ABI: additive (RATO_ABI_VERSION stays 12).  Same state, arguments and meaning as the five entries above,
+ * and the same arithmetic per entry and per sum in the same order (both forms compile csrc/rato_ipm_rows.h): every array of
+ * the state, the padding and every field of rec are BITWISE what the entry above leaves, after every call, for running and
+ * for ended problems, for a batch and for K = 1.  Elementwise work runs on a grid of (rato_ipm_grid_rows() rows) x (problem);
+ * a scalar that needs every row is made by a stream-ordered sequence of launches (per-block extremes combined by a finishing
+ * launch of one workgroup per problem; each sum by ONE workgroup that walks the full length as the workgroup form does; rec
+ * written by the finishing launches alone).  Workgroups of a launch never wait for each other and none reads what another
+ * one of the same launch writes; no atomics, no private memory, and the library allocates and keeps nothing.  Launches per
+ * call: residuals 3, newton 1 (LADDER: 2, or 1 at flag >= 60), step_setup 3, trial 1, accept 4.
+ * work: rato_ipm_grid_work_doubles(n, nI, m, K) doubles of the caller's, at least; contents irrelevant before the first call,
+ * and owned by the state's calls from then on (accept applies a step exactly once through a token it keeps there).  work_len:
+ * the doubles work holds.  RATO_EINVAL without a launch and with everything untouched on whatever the entries above
+ * refuse, on a NULL work and on work_len below the query.  rato_ipm_grid_work_doubles: positive and non-decreasing in each
+ * argument (0 for n < 1, nI < 0, m < 1 or K < 1). */
+int32_t rato_ipm_grid_rows(void);
+int64_t rato_ipm_grid_work_doubles(int32_t n, int32_t nI, int32_t m, int32_t K);
+int rato_ipm_residuals_grid_f64(const rato_ipm_state* st, const double* g, int64_t ldg, const double* JTy, int64_t ldj, int32_t last,
+                                double* work, int64_t work_len, void* stream);
+int rato_ipm_newton_grid_f64(const rato_ipm_state* st, int32_t phase, const double* a, int64_t lda, const double* b, int64_t ldb,
+                             const int32_t* info, int32_t flag, double* work, int64_t work_len, void* stream);
+int rato_ipm_step_setup_grid_f64(const rato_ipm_state* st, const double* Hdv, int64_t ldh, double* work, int64_t work_len,
+                                 void* stream);
+int rato_ipm_trial_grid_f64(const rato_ipm_state* st, double* work, int64_t work_len, void* stream);
+int rato_ipm_accept_grid_f64(const rato_ipm_state* st, const double* gt, int64_t ldg, double* work, int64_t work_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

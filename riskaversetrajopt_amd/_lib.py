@@ -126,6 +126,15 @@ SIGNATURES = {
     "rato_ipm_step_setup_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_stream]),
     "rato_ipm_trial_f64": (C.c_int, [C.POINTER(IpmState), c_stream]),
     "rato_ipm_accept_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_stream]),
+    "rato_ipm_grid_rows": (C.c_int32, []),
+    "rato_ipm_grid_work_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rato_ipm_residuals_grid_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_float_p, C.c_int64, C.c_int32, c_float_p,
+                                              C.c_int64, c_stream]),
+    "rato_ipm_newton_grid_f64": (C.c_int, [C.POINTER(IpmState), C.c_int32, c_float_p, C.c_int64, c_float_p, C.c_int64, c_float_p,
+                                           C.c_int32, c_float_p, C.c_int64, c_stream]),
+    "rato_ipm_step_setup_grid_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
+    "rato_ipm_trial_grid_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_stream]),
+    "rato_ipm_accept_grid_f64": (C.c_int, [C.POINTER(IpmState), c_float_p, C.c_int64, c_float_p, C.c_int64, c_stream]),
     "rato_abi_version": (C.c_int, []),
     "rato_packed_tile_stride": (C.c_size_t, [C.c_size_t]),
     "rato_packed_buffer_floats": (C.c_size_t, [C.c_size_t, C.c_size_t]),

@@ -22,98 +22,21 @@
 // scalar combinations that decide a branch on the host (E_mu, dual, the step lengths) are restated with that rule (pymax /
 // pymin), and the expressions of the nu rule and the Armijo test are rounded operation by operation as the host rounds them
 // (__dmul_rn / __dadd_rn: the library is built with contraction on).
-#include "rato_common.h"
-
-#include <math.h>
+// The arithmetic itself -- the row formulas, the accumulate expressions, the scalar epilogues -- is csrc/rato_ipm_rows.h, which
+// the grid form (csrc/ipm_driver_grid.hip) compiles too: the kernels below are the loops, the reductions and the barriers.
+#include "rato_ipm_rows.h"
 
 namespace {
 
-constexpr int ID_BLOCK = 256;
-constexpr int ID_WAVES = ID_BLOCK / RATO_WAVE;
-static_assert(ID_WAVES == 4, "the block reductions combine four waves");
-
-__device__ __forceinline__ double nanmax(double a, double b) { return (a != a || b != b) ? (double)NAN : fmax(a, b); }
-__device__ __forceinline__ double pymax(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ double pymin(double a, double b) { return b < a ? b : a; }
-
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double (*sh)[ID_WAVES]) {
-  const int lane = threadIdx.x & (RATO_WAVE - 1), wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const double s = rato::wave_sum_dpp(v[i]);
-    if (lane == 0) sh[i][wave] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = ((sh[i][0] + sh[i][1]) + sh[i][2]) + sh[i][3];
-  __syncthreads();
-}
-
-// MODE 0: the maximum, NaN if any entry is NaN; MODE 1: the minimum, NaNs dropped
-template <int MODE, int N>
-__device__ __forceinline__ void block_extreme(double (&v)[N], double (*sh)[ID_WAVES]) {
-  const int lane = threadIdx.x & (RATO_WAVE - 1), wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = v[i];
-#pragma unroll
-    for (int off = RATO_WAVE / 2; off > 0; off >>= 1) {
-      const double o = __shfl_xor(x, off, RATO_WAVE);
-      x = MODE == 0 ? nanmax(x, o) : fmin(x, o);
-    }
-    if (lane == 0) sh[i][wave] = x;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = sh[i][0];
-#pragma unroll
-    for (int w = 1; w < ID_WAVES; ++w) x = MODE == 0 ? nanmax(x, sh[i][w]) : fmin(x, sh[i][w]);
-    v[i] = x;
-  }
-  __syncthreads();
-}
-
-// distances to the bounds and their reciprocals: 1 / where(has, d, inf)
-struct Dist {
-  bool hasL, hasU;
-  double dL, dU, iL, iU;
-};
-__device__ __forceinline__ Dist dist(double v, double vL, double vU) {
-  Dist b;
-  b.hasL = isfinite(vL);
-  b.hasU = isfinite(vU);
-  b.dL = v - vL;
-  b.dU = vU - v;
-  b.iL = b.hasL ? 1.0 / b.dL : 0.0;
-  b.iU = b.hasU ? 1.0 / b.dU : 0.0;
-  return b;
-}
-
-struct View {   // problem k's rows
-  int n, nv, m;
-  double* rec;
-  int64_t ov, om;
-};
-__device__ __forceinline__ View view(const rato_ipm_state& st) {
-  View w;
-  w.n = st.n;
-  w.nv = st.n + st.nI;
-  w.m = st.m;
-  w.rec = st.rec + (int64_t)blockIdx.x * RATO_IPM_REC;
-  w.ov = (int64_t)blockIdx.x * st.ldv;
-  w.om = (int64_t)blockIdx.x * st.ldm;
-  return w;
-}
+using namespace rato_ipm;
 
 // comp(mu) of Problem.error: max |zl dL - mu| over the lower bounds, max |zu dU - mu| over the upper ones
 __device__ __forceinline__ double complementarity(const rato_ipm_state& st, const View& w, double mu, double (*sh)[ID_WAVES]) {
   double mx[2] = {-INFINITY, -INFINITY};
   for (int i = threadIdx.x; i < w.nv; i += ID_BLOCK) {
     const Dist b = dist(st.v[w.ov + i], st.vL[w.ov + i], st.vU[w.ov + i]);
-    if (b.hasL) mx[0] = nanmax(mx[0], fabs(__dmul_rn(st.zl[w.ov + i], b.dL) - mu));
-    if (b.hasU) mx[1] = nanmax(mx[1], fabs(__dmul_rn(st.zu[w.ov + i], b.dU) - mu));
+    if (b.hasL) mx[0] = nanmax(mx[0], comp_term(st.zl[w.ov + i], b.dL, mu));
+    if (b.hasU) mx[1] = nanmax(mx[1], comp_term(st.zu[w.ov + i], b.dU, mu));
   }
   block_extreme<0>(mx, sh);
   return pymax(pymax(0.0, mx[0]), mx[1]);
@@ -122,7 +45,7 @@ __device__ __forceinline__ double complementarity(const rato_ipm_state& st, cons
 __global__ __launch_bounds__(ID_BLOCK) void ipm_residuals_kernel(rato_ipm_state st, const double* __restrict__ g, int64_t ldg,
                                                                  const double* __restrict__ JTy, int64_t ldj, int last) {
   __shared__ double sh[3][ID_WAVES];
-  const View w = view(st);
+  const View w = view(st, blockIdx.x);
   if (w.rec[RATO_IPM_STATUS] != (double)RATO_IPM_RUNNING) return;
   const int t = threadIdx.x, n = w.n;
   const double sf = w.rec[RATO_IPM_SF], tol = w.rec[RATO_IPM_TOL];
@@ -130,93 +53,29 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_residuals_kernel(rato_ipm_state 
   const double* gk = g + (int64_t)blockIdx.x * ldg;
   const double* jk = JTy + (int64_t)blockIdx.x * ldj;
   double mx[3] = {-INFINITY, -INFINITY, -INFINITY};             // |c|, |rs|, |rz|
-  for (int r = t; r < w.m; r += ID_BLOCK) {
-    const int sl = st.row_slack[r];
-    double cr;
-    if (sl < 0) {
-      cr = gk[r] - st.gL[w.om + r];
-    } else {
-      const int64_t i = w.ov + n + sl;
-      cr = gk[r] - st.v[i];
-      mx[1] = nanmax(mx[1], fabs(-st.y[w.om + r] - st.zl[i] + st.zu[i]));
-    }
-    st.c[w.om + r] = cr;
-    mx[0] = nanmax(mx[0], fabs(cr));
-  }
-  for (int j = t; j < n; j += ID_BLOCK) {
-    const double gf = sf * (st.curv[w.ov + j] * st.v[w.ov + j] + st.lin[w.ov + j]);
-    st.gradf[w.ov + j] = gf;
-    mx[2] = nanmax(mx[2], fabs(gf + jk[j] - st.zl[w.ov + j] + st.zu[w.ov + j]));
-  }
+  for (int r = t; r < w.m; r += ID_BLOCK) residual_m_row(st, w, gk, r, mx);
+  for (int j = t; j < n; j += ID_BLOCK) residual_z_row(st, w, jk, sf, j, mx);
   block_extreme<0>(mx, sh);
   const double prim = mx[0], dual = pymax(mx[2], st.nI > 0 ? mx[1] : 0.0);
   const double E0 = pymax(pymax(dual, prim), complementarity(st, w, 0.0, sh));
-  int status = RATO_IPM_RUNNING, passes = 0;
-  if (!isfinite(E0)) status = 2;
-  else if (E0 <= tol) status = 0;
-  else if (last) status = 1;
+  const int status = residual_status(E0, tol, last);
+  int passes = 0;
   if (status != RATO_IPM_RUNNING) {
-    if (t == 0) {
-      w.rec[RATO_IPM_E0] = E0;
-      w.rec[RATO_IPM_PRIM] = prim;
-      w.rec[RATO_IPM_DUAL] = dual;
-      w.rec[RATO_IPM_STATUS] = (double)status;
-    }
+    if (t == 0) residual_write_ended(w.rec, E0, prim, dual, status);
     return;
   }
-  const double floor_mu = tol / 10.0;
-  while (mu > floor_mu) {                                        // the whole workgroup takes each pass
-    const double Emu = pymax(pymax(dual, prim), complementarity(st, w, mu, sh));
-    if (!(Emu <= 10.0 * mu)) break;
-    mu = pymax(floor_mu, pymin(0.2 * mu, __dmul_rn(mu, sqrt(mu))));
-    nu = 0.0;
-    ++passes;
-  }
-  const double dc = 1e-8 * sqrt(sqrt(mu));
-  for (int i = t; i < w.nv; i += ID_BLOCK) {
-    const Dist b = dist(st.v[w.ov + i], st.vL[w.ov + i], st.vU[w.ov + i]);
-    const double Sig = st.zl[w.ov + i] * b.iL + st.zu[w.ov + i] * b.iU, gb = -mu * b.iL + mu * b.iU;
-    st.Sigma[w.ov + i] = Sig;
-    st.gbar[w.ov + i] = gb;
-    if (i < n) {
-      st.rz[w.ov + i] = st.gradf[w.ov + i] + jk[i] + gb;         // gradf[i]: this lane's own store above
-      st.diag[(int64_t)blockIdx.x * n + i] = (Sig + 0.0) + sf * st.curv[w.ov + i];
-    }
-  }
-  for (int r = t; r < w.m; r += ID_BLOCK) {
-    const int sl = st.row_slack[r];
-    const double cr = st.c[w.om + r];                            // this lane's own store above
-    if (sl < 0) {
-      const double d = 1.0 / dc;
-      st.d[w.om + r] = d;
-      st.w[w.om + r] = d * cr;
-    } else {
-      const int64_t i = w.ov + n + sl;                           // Sigma and gbar of the slack again: no wait for their owner
-      const Dist b = dist(st.v[i], st.vL[i], st.vU[i]);
-      const double Sig = st.zl[i] * b.iL + st.zu[i] * b.iU, gb = -mu * b.iL + mu * b.iU;
-      const double rs = -st.y[w.om + r] + gb;
-      st.rs[w.om + r] = rs;
-      st.d[w.om + r] = Sig;
-      st.w[w.om + r] = Sig * cr + rs;
-    }
-  }
-  if (t == 0) {
-    w.rec[RATO_IPM_E0] = E0;
-    w.rec[RATO_IPM_PRIM] = prim;
-    w.rec[RATO_IPM_DUAL] = dual;
-    w.rec[RATO_IPM_MU] = mu;
-    w.rec[RATO_IPM_NU] = nu;
-    w.rec[RATO_IPM_DW] = 0.0;
-    w.rec[RATO_IPM_DC] = dc;
-    w.rec[RATO_IPM_MU_PASSES] = (double)passes;
-    w.rec[RATO_IPM_SEARCHING] = 0.0;
-  }
+  // the whole workgroup takes each pass
+  mu_loop(mu, nu, passes, tol, dual, prim, [&](double m_) { return complementarity(st, w, m_, sh); });
+  const double dc = dc_of(mu);
+  for (int i = t; i < w.nv; i += ID_BLOCK) prepare_v_row(st, w, jk, mu, sf, i);    // gradf[i]: this lane's own store above
+  for (int r = t; r < w.m; r += ID_BLOCK) prepare_m_row(st, w, dc, mu, r);        // c[r]: this lane's own store above
+  if (t == 0) residual_write_running(w.rec, E0, prim, dual, mu, nu, dc, passes);
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_newton_kernel(rato_ipm_state st, int phase, const double* __restrict__ a,
                                                               int64_t lda, const double* __restrict__ b, int64_t ldb,
                                                               const int32_t* __restrict__ info, int flag) {
-  const View w = view(st);
+  const View w = view(st, blockIdx.x);
   if (w.rec[RATO_IPM_STATUS] != (double)RATO_IPM_RUNNING) return;
   const int t = threadIdx.x, n = w.n;
   const double* ak = a ? a + (int64_t)blockIdx.x * lda : nullptr;
@@ -225,7 +84,7 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_newton_kernel(rato_ipm_state st,
   double dw = w.rec[RATO_IPM_DW];
   switch (phase) {
     case RATO_IPM_PHASE_RHS:
-      for (int j = t; j < n; j += ID_BLOCK) st.dz[w.ov + j] = -(st.rz[w.ov + j] + ak[j]);
+      for (int j = t; j < n; j += ID_BLOCK) newton_rhs_row(st, w, ak, j);
       break;
     case RATO_IPM_PHASE_LADDER: {
       if (info[blockIdx.x] == 0) return;
@@ -234,186 +93,95 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_newton_kernel(rato_ipm_state st,
         if (t == 0) w.rec[RATO_IPM_STATUS] = 2.0;
         return;
       }
-      dw = dw == 0.0 ? 1e-4 : 8.0 * dw;
-      for (int j = t; j < n; j += ID_BLOCK)
-        st.diag[(int64_t)blockIdx.x * n + j] = (st.Sigma[w.ov + j] + dw) + sf * st.curv[w.ov + j];
+      dw = ladder_dw(dw);
+      for (int j = t; j < n; j += ID_BLOCK) newton_ladder_row(st, w, dw, sf, j);
       if (t == 0) w.rec[RATO_IPM_DW] = dw;
       break;
     }
     case RATO_IPM_PHASE_Q:
-      for (int r = t; r < w.m; r += ID_BLOCK) {
-        const int sl = st.row_slack[r];
-        const double lin = ak[r] + st.c[w.om + r];
-        if (sl < 0) {
-          double dyE = st.dyE[w.om + r];
-          if (flag) st.dyE[w.om + r] = dyE = lin / dc;
-          const double r2 = -lin + dc * dyE;
-          st.r2[w.om + r] = r2;
-          st.q[w.om + r] = dyE - r2 / dc;
-        } else {
-          st.q[w.om + r] = st.Sigma[w.ov + n + sl] * lin + st.rs[w.om + r];
-        }
-      }
+      for (int r = t; r < w.m; r += ID_BLOCK) newton_q_row(st, w, ak, dc, flag, r);
       break;
     case RATO_IPM_PHASE_R:
-      for (int j = t; j < n; j += ID_BLOCK) {
-        const double x = st.dz[w.ov + j], h = ak[j] + (sf * st.curv[w.ov + j]) * x;
-        st.ez[w.ov + j] = -(st.rz[w.ov + j] + h + (st.Sigma[w.ov + j] + dw) * x + bk[j]);
-      }
+      for (int j = t; j < n; j += ID_BLOCK) newton_r_row(st, w, ak, bk, sf, dw, j);
       break;
     case RATO_IPM_PHASE_UPDATE:
-      for (int j = t; j < n; j += ID_BLOCK) st.dz[w.ov + j] += st.ez[w.ov + j];
-      for (int r = t; r < w.m; r += ID_BLOCK)
-        if (st.row_slack[r] < 0) st.dyE[w.om + r] += (ak[r] - st.r2[w.om + r]) / dc;
+      for (int j = t; j < n; j += ID_BLOCK) newton_update_z_row(st, w, j);
+      for (int r = t; r < w.m; r += ID_BLOCK) newton_update_m_row(st, w, ak, dc, r);
       break;
     default:                                                     // RATO_IPM_PHASE_FINISH
-      for (int j = t; j < n; j += ID_BLOCK) st.dv[w.ov + j] = st.dz[w.ov + j];
-      for (int r = t; r < w.m; r += ID_BLOCK) {
-        const int sl = st.row_slack[r];
-        if (sl < 0) {
-          st.dy[w.om + r] = st.dyE[w.om + r];
-        } else {
-          const double ds = ak[r] + st.c[w.om + r];
-          st.dv[w.ov + n + sl] = ds;
-          st.dy[w.om + r] = st.Sigma[w.ov + n + sl] * ds + st.rs[w.om + r];
-        }
-      }
+      for (int j = t; j < n; j += ID_BLOCK) newton_finish_z_row(st, w, j);
+      for (int r = t; r < w.m; r += ID_BLOCK) newton_finish_m_row(st, w, ak, r);
   }
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_setup_kernel(rato_ipm_state st, const double* __restrict__ Hdv, int64_t ldh) {
-  __shared__ double sh[10][ID_WAVES];
-  const View w = view(st);
+  __shared__ double sh[SETUP_SUMS][ID_WAVES];
+  const View w = view(st, blockIdx.x);
   if (w.rec[RATO_IPM_STATUS] != (double)RATO_IPM_RUNNING) return;
   const int t = threadIdx.x, n = w.n;
   const double mu = w.rec[RATO_IPM_MU], dw = w.rec[RATO_IPM_DW], sf = w.rec[RATO_IPM_SF];
-  double nu = w.rec[RATO_IPM_NU];
+  const double nu = w.rec[RATO_IPM_NU];
   const double tau = pymax(0.99, 1.0 - mu);
   const double* hk = Hdv + (int64_t)blockIdx.x * ldh;
-  // sums: gradf . dv_z, gbar . dv, dv_z . W dv_z, sum Sigma dv^2, dv_z . dv_z, the two barrier sums, sum curv z^2, sum |c|,
-  // sum lin z
-  double s[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double s[SETUP_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double mn[2] = {INFINITY, INFINITY};                           // the primal and the dual step to the boundary
   for (int i = t; i < w.nv; i += ID_BLOCK) {
-    const double vi = st.v[w.ov + i], dvi = st.dv[w.ov + i], zl = st.zl[w.ov + i], zu = st.zu[w.ov + i];
-    const Dist b = dist(vi, st.vL[w.ov + i], st.vU[w.ov + i]);
-    const double dzl = b.hasL ? mu * b.iL - zl - zl * b.iL * dvi : 0.0;
-    const double dzu = b.hasU ? mu * b.iU - zu + zu * b.iU * dvi : 0.0;
-    st.dzl[w.ov + i] = dzl;
-    st.dzu[w.ov + i] = dzu;
-    if (b.hasL && dvi < 0.0) mn[0] = fmin(mn[0], -tau * b.dL / dvi);
-    if (b.hasU && -dvi < 0.0) mn[0] = fmin(mn[0], -tau * b.dU / -dvi);
-    if (b.hasL && dzl < 0.0) mn[1] = fmin(mn[1], -tau * zl / dzl);
-    if (b.hasU && dzu < 0.0) mn[1] = fmin(mn[1], -tau * zu / dzu);
-    s[1] += st.gbar[w.ov + i] * dvi;
-    s[3] += st.Sigma[w.ov + i] * dvi * dvi;
-    if (b.hasL) s[5] += log(b.dL);
-    if (b.hasU) s[6] += log(b.dU);
+    const double vi = st.v[w.ov + i], dvi = st.dv[w.ov + i];
+    const Dist b = setup_row(st, w, mu, tau, i, vi, dvi, mn);
+    acc_dot(s[1], st.gbar[w.ov + i], dvi);
+    acc_sigma(s[3], st.Sigma[w.ov + i], dvi);
+    acc_log(s[5], b.hasL, b.dL);
+    acc_log(s[6], b.hasU, b.dU);
     if (i < n) {
       const double cv = st.curv[w.ov + i];
-      s[0] += st.gradf[w.ov + i] * dvi;
-      s[2] += dvi * (hk[i] + (sf * cv) * dvi);
-      s[4] += dvi * dvi;
-      s[7] += cv * vi * vi;
-      s[9] += st.lin[w.ov + i] * vi;
+      acc_dot(s[0], st.gradf[w.ov + i], dvi);
+      acc_hess(s[2], dvi, hk[i], sf, cv);
+      acc_square(s[4], dvi);
+      acc_curv(s[7], cv, vi);
+      acc_dot(s[9], st.lin[w.ov + i], vi);
     }
   }
-  for (int r = t; r < w.m; r += ID_BLOCK) s[8] += fabs(st.c[w.om + r]);
+  for (int r = t; r < w.m; r += ID_BLOCK) acc_abs(s[8], st.c[w.om + r]);
   block_sum(s, sh);
   block_extreme<1>(mn, sh);
-  const double a_max = fmin(1.0, mn[0]), a_dual = fmin(1.0, mn[1]);
-  const double c1 = s[8], Dbar = s[0] + s[1], quad = __dadd_rn(__dadd_rn(s[2], s[3]), __dmul_rn(dw, s[4]));
-  if (c1 > 0.0) {
-    const double nu_trial = __dadd_rn(Dbar, __dmul_rn(0.5, pymax(quad, 0.0))) / __dmul_rn(0.9, c1);
-    if (nu < nu_trial) nu = __dadd_rn(nu_trial, 1.0);
-  }
-  const double Dphi = pymin(__dadd_rn(Dbar, -__dmul_rn(nu, c1)), 0.0);
-  const double objective = 0.5 * s[7] + s[9], barrier = -mu * (s[5] + s[6]);
-  const double phi = __dadd_rn(__dadd_rn(__dmul_rn(sf, objective), barrier), __dmul_rn(nu, c1));
-  if (t == 0) {
-    w.rec[RATO_IPM_A_MAX] = a_max;
-    w.rec[RATO_IPM_A_DUAL] = a_dual;
-    w.rec[RATO_IPM_C1] = c1;
-    w.rec[RATO_IPM_DBAR] = Dbar;
-    w.rec[RATO_IPM_QUAD] = quad;
-    w.rec[RATO_IPM_NU] = nu;
-    w.rec[RATO_IPM_DPHI] = Dphi;
-    w.rec[RATO_IPM_PHI] = phi;
-    w.rec[RATO_IPM_BARRIER] = barrier;
-    w.rec[RATO_IPM_OBJECTIVE] = objective;
-    w.rec[RATO_IPM_ALPHA] = a_max;
-    w.rec[RATO_IPM_TRIALS] = 0.0;
-    w.rec[RATO_IPM_SEARCHING] = 1.0;
-    w.rec[RATO_IPM_ACCEPTED] = 0.0;
-  }
-}
-
-__device__ __forceinline__ bool searching(const double* rec) {
-  return rec[RATO_IPM_STATUS] == (double)RATO_IPM_RUNNING && rec[RATO_IPM_SEARCHING] == 1.0;
+  const SetupScalars o = setup_scalars(s, mn, mu, dw, sf, nu);
+  if (t == 0) setup_write(w.rec, o);
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_trial_kernel(rato_ipm_state st) {
-  const View w = view(st);
+  const View w = view(st, blockIdx.x);
   if (!searching(w.rec)) return;
   const double alpha = w.rec[RATO_IPM_ALPHA];
-  for (int i = threadIdx.x; i < w.nv; i += ID_BLOCK) st.vt[w.ov + i] = st.v[w.ov + i] + alpha * st.dv[w.ov + i];
+  for (int i = threadIdx.x; i < w.nv; i += ID_BLOCK) trial_row(st, w, alpha, i);
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_accept_kernel(rato_ipm_state st, const double* __restrict__ gt, int64_t ldg) {
-  __shared__ double sh[5][ID_WAVES];
-  const View w = view(st);
+  __shared__ double sh[ACCEPT_SUMS][ID_WAVES];
+  const View w = view(st, blockIdx.x);
   if (!searching(w.rec)) return;
   const int t = threadIdx.x, n = w.n;
-  const double mu = w.rec[RATO_IPM_MU], nu = w.rec[RATO_IPM_NU], sf = w.rec[RATO_IPM_SF], phi = w.rec[RATO_IPM_PHI];
-  const double Dphi = w.rec[RATO_IPM_DPHI], alpha = w.rec[RATO_IPM_ALPHA], a_dual = w.rec[RATO_IPM_A_DUAL];
-  const int trials = (int)w.rec[RATO_IPM_TRIALS] + 1, iterations = (int)w.rec[RATO_IPM_ITERATIONS];
+  const AcceptIn in = accept_in(w.rec);
   const double* gk = gt + (int64_t)blockIdx.x * ldg;
-  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};                       // the two barrier sums, sum curv z^2, sum |c|, sum lin z
+  double s[ACCEPT_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};             // the two barrier sums, sum curv z^2, sum |c|, sum lin z
   for (int i = t; i < w.nv; i += ID_BLOCK) {
     const double vi = st.vt[w.ov + i];
     const Dist b = dist(vi, st.vL[w.ov + i], st.vU[w.ov + i]);
-    if (b.hasL) s[0] += log(b.dL);
-    if (b.hasU) s[1] += log(b.dU);
+    acc_log(s[0], b.hasL, b.dL);
+    acc_log(s[1], b.hasU, b.dU);
     if (i < n) {
-      s[2] += st.curv[w.ov + i] * vi * vi;
-      s[4] += st.lin[w.ov + i] * vi;
+      acc_curv(s[2], st.curv[w.ov + i], vi);
+      acc_dot(s[4], st.lin[w.ov + i], vi);
     }
   }
-  for (int r = t; r < w.m; r += ID_BLOCK) {
-    const int sl = st.row_slack[r];
-    s[3] += fabs(sl < 0 ? gk[r] - st.gL[w.om + r] : gk[r] - st.vt[w.ov + n + sl]);
-  }
+  for (int r = t; r < w.m; r += ID_BLOCK) acc_abs(s[3], trial_c(st, w, gk, r));
   block_sum(s, sh);
-  const double phi_t = __dadd_rn(__dadd_rn(__dmul_rn(sf, 0.5 * s[2] + s[4]), -mu * (s[0] + s[1])), __dmul_rn(nu, s[3]));
-  const double bound = __dadd_rn(__dadd_rn(phi, __dmul_rn(__dmul_rn(1e-8, alpha), Dphi)),
-                                 __dmul_rn(10.0 * 2.220446049250313e-16, fabs(phi)));
-  const bool accept = isfinite(phi_t) && phi_t <= bound;
+  bool accept;
+  const double phi_t = accept_scalars(s, in, &accept);
   if (accept) {
-    for (int i = t; i < w.nv; i += ID_BLOCK) {
-      const double vi = st.vt[w.ov + i];
-      const Dist b = dist(vi, st.vL[w.ov + i], st.vU[w.ov + i]);
-      const double dL = b.hasL ? b.dL : 1.0, dU = b.hasU ? b.dU : 1.0;
-      const double zl = st.zl[w.ov + i] + a_dual * st.dzl[w.ov + i], zu = st.zu[w.ov + i] + a_dual * st.dzu[w.ov + i];
-      st.v[w.ov + i] = vi;
-      st.zl[w.ov + i] = b.hasL ? fmin(fmax(zl, mu / dL / 1e10), 1e10 * mu / dL) : 0.0;      // kappa_Sigma
-      st.zu[w.ov + i] = b.hasU ? fmin(fmax(zu, mu / dU / 1e10), 1e10 * mu / dU) : 0.0;
-    }
-    for (int r = t; r < w.m; r += ID_BLOCK) st.y[w.om + r] += alpha * st.dy[w.om + r];
+    for (int i = t; i < w.nv; i += ID_BLOCK) accept_v_row(st, w, in.mu, in.a_dual, i);
+    for (int r = t; r < w.m; r += ID_BLOCK) accept_m_row(st, w, in.alpha, r);
   }
-  if (t == 0) {
-    w.rec[RATO_IPM_PHI_T] = phi_t;
-    w.rec[RATO_IPM_TRIALS] = (double)trials;
-    if (accept) {
-      w.rec[RATO_IPM_ITERATIONS] = (double)(iterations + 1);
-      w.rec[RATO_IPM_SEARCHING] = 0.0;
-      w.rec[RATO_IPM_ACCEPTED] = 1.0;
-    } else if (trials >= 40) {
-      w.rec[RATO_IPM_STATUS] = 2.0;
-      w.rec[RATO_IPM_SEARCHING] = 0.0;
-    } else {
-      w.rec[RATO_IPM_ALPHA] = alpha * 0.5;
-    }
-  }
+  if (t == 0) accept_write(w.rec, in, phi_t, accept);
 }
 
 __global__ __launch_bounds__(ID_BLOCK) void ipm_g_rows_kernel(int32_t n, const double* __restrict__ g0, int32_t m0, int64_t ldg0,
@@ -431,18 +199,6 @@ __global__ __launch_bounds__(ID_BLOCK) void ipm_g_rows_kernel(int32_t n, const d
     block_sum(s, sh);
     if (t == 0) gk[m0 + r] = s[0];
   }
-}
-
-bool state_ok(const rato_ipm_state* st) {
-  if (!st || st->K < 1 || st->K > 65535 || st->n < 1 || st->nI < 0 || st->m < 1 || st->nI > st->m ||
-      st->ldv < (int64_t)st->n + st->nI || st->ldm < st->m)
-    return false;
-  const void* p[] = {st->row_slack, st->v, st->zl, st->zu, st->vL, st->vU, st->curv, st->lin, st->y, st->gL, st->rec, st->Sigma, st->gbar,
-                     st->dv, st->dzl, st->dzu, st->vt, st->gradf, st->rz, st->dz, st->ez, st->diag, st->c, st->d, st->w, st->rs,
-                     st->dyE, st->r2, st->q, st->dy};
-  for (const void* q : p)
-    if (!q) return false;
-  return true;
 }
 
 }  // namespace

@@ -214,7 +214,7 @@ class Model:
     def solve(self, Z0=None, tol=1e-8, max_iter=3000, backend='device', results_dir='results', driver='host',
               chol='workgroup'):
         """the NLP by ``drone_gaussian_ipm.solve_batch`` (a batch of one) from ``Z0`` (default: the script's start,
-        ``initial_guess(results_dir)``) -> (Z, info).  ``driver``: 'host' or 'device', ``chol``: 'workgroup' or 'grid' (``solve_batch``'s)"""
+        ``initial_guess(results_dir)``) -> (Z, info).  ``driver``: 'host', 'device' or 'device_grid', ``chol``: 'workgroup' or 'grid' (``solve_batch``'s)"""
         from . import drone_gaussian_ipm
         (Z, info), = drone_gaussian_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter,
                                                     backend=backend, results_dir=results_dir, driver=driver, chol=chol)

@@ -355,7 +355,8 @@ def solve_batch(models, Z0s=None, tol=1e-8, max_iter=3000, backend='device', cal
                  host = the rest (the driver's vector algebra and line-search bookkeeping)
       driver     'host' (``ipm.solve_group``: the iterate and the vector algebra on the host) or 'device'
                  (``ipm.solve_group_device``, backend='device' only: the iterate stays on the device, csrc/ipm_driver.hip, and
-                 the clocks hold the time to launch; info["driver"] = 'device')
+                 the clocks hold the time to launch; info["driver"] = 'device'), or 'device_grid': 'device' with the driver's
+                 own vector kernels spread over the rows (csrc/ipm_driver_grid.hip, DESIGN §7.al: the same bits)
       chol       'workgroup' (csrc/chol.hip) or 'grid' (csrc/chol_grid.hip: the same bits from launches spread over the device);
                  backend='numpy' ignores it
     info: status ('converged' | 'max_iter' | 'line_search'), iterations, factorizations, E0, primal_infeasibility,

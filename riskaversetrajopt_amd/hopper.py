@@ -916,7 +916,8 @@ class Model:
         ``hopper_ipm`` in place of IPOPT -> (Z, info); info["status"] is 'converged' only if the final error shows it.
         newton='arrow' eliminates the M sample variables from the Newton step (the path that scales with M).
         driver='device' (backend='device', either newton; 'arrow' needs precision='f64'): the iterate stays on the device
-        (``ipm.solve_group_device``, csrc/ipm_driver.hip); info["driver"] = 'device'.
+        (``ipm.solve_group_device``, csrc/ipm_driver.hip); info["driver"] = 'device'.  driver='device_grid': the same with the
+        driver's vector kernels spread over the rows (csrc/ipm_driver_grid.hip), bitwise the same result.
         chol: 'workgroup' or 'grid', the device Cholesky (``hopper_ipm.solve_batch``); the result does not depend on it."""
         from . import hopper_ipm
         return hopper_ipm.solve_batch([self], None if Z0 is None else [Z0], tol=tol, max_iter=max_iter, backend=backend,

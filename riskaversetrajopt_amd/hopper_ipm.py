@@ -541,7 +541,9 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
       driver     'host' (``ipm.solve_group``: the iterate and the vector algebra on the host) or 'device'
                  (``ipm.solve_group_device``, backend='device' only: the iterate stays on the device, csrc/ipm_driver.hip and
                  csrc/hopper_g.hip, and the clocks hold the time to launch; info["driver"] = 'device'.  With newton='arrow' the
-                 models must be on a GPU with precision='f64')
+                 models must be on a GPU with precision='f64'), or 'device_grid': 'device' with the driver's own vector kernels
+                 spread over the rows (csrc/ipm_driver_grid.hip, DESIGN §7.al: the same bits, so Z and info do not depend on
+                 it but for info["driver"] = 'device_grid'; it pays where a problem has many thousands of rows)
       chol       'workgroup' (csrc/chol.hip: one workgroup per problem) or 'grid' (csrc/chol_grid.hip: every factorization a
                  sequence of launches over the whole device; the same bits, so Z and info do not depend on it).  backend='numpy'
                  ignores it: its Cholesky is NumPy's
@@ -556,7 +558,7 @@ def solve_batch(models, Z0s=None, tol=1e-3, max_iter=3000, backend='device', cal
     if callbacks is not None and backend != 'numpy':
         raise ValueError("callbacks are the numpy backend's")
     models = list(models)
-    if driver == 'device' and newton == 'arrow' and any(m.device.type != 'cuda' or m.precision != 'f64' for m in models):
+    if _ipm.on_device(driver) and newton == 'arrow' and any(m.device.type != 'cuda' or m.precision != 'f64' for m in models):
         raise ValueError("newton='arrow' under driver='device' works on the partials the fp64 slip kernel leaves on the device: "
                          "every model needs a GPU and precision='f64'")
     Z0s = [m.initial_guess() for m in models] if Z0s is None else [np.asarray(Z, dtype=np.float64) for Z in Z0s]

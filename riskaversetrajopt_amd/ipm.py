@@ -29,8 +29,11 @@ and ``factor`` / ``solve`` (``DeviceBase``: ``factor_t`` / ``solve_t`` too) on t
 holds the state of the K problems in HBM, the vector algebra above is csrc/ipm_driver.hip, and the host keeps the branches
 it needs a read-back for: who is still running, the delta_w ladder, who is still searching.  There the objective is
 sf (1/2 sum curv z^2 + lin . z): the model gives ``curv`` and, if it has a linear part, ``lin`` (both (n,)).
+``driver='device_grid'`` is the same driver with that vector algebra spread over the rows of a problem
+(csrc/ipm_driver_grid.hip, ``DeviceState(vec='grid')``): the same bits from more launches, for problems of many thousands of rows.
 """
 import contextlib
+import functools
 import time
 
 import numpy as np
@@ -532,14 +535,22 @@ def solve_group(models, Z0s, tol, max_iter, be, verbose):
 
 
 # ---- the driver on the device (csrc/ipm_driver.hip) -----------------------------------------------------------------
-DRIVERS = ("host", "device")
+DRIVERS = ("host", "device", "device_grid")
+VECS = ("workgroup", "grid")
+VEC_OF_DRIVER = {"device": "workgroup", "device_grid": "grid"}       # the form of the driver's own vector kernels (§7.al)
+
+
+def on_device(driver):
+    """whether ``driver`` keeps the iterate on the device ('device', or 'device_grid': the same with its vector kernels
+    spread over the rows, csrc/ipm_driver_grid.hip)"""
+    return driver in VEC_OF_DRIVER
 
 
 def check_driver(driver, backend):
     if driver not in DRIVERS:
-        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
-    if driver == 'device' and backend != 'device':
-        raise ValueError(f"driver='device' keeps the iterate on the device: it needs backend='device', got {backend!r}")
+        raise ValueError(f"driver must be 'host', 'device' or 'device_grid', got {driver!r}")
+    if on_device(driver) and backend != 'device':
+        raise ValueError(f"driver={driver!r} keeps the iterate on the device: it needs backend='device', got {backend!r}")
 
 
 def g_rows(n, g0, J1, z, out=None):
@@ -562,15 +573,20 @@ class DeviceState:
     inequality / equality rows, are spread over the rows.  Whatever of a Problem's work vectors exists is uploaded too, so a
     phase can be run from any host state.  ``fill`` is what the padding and the work vectors that do not exist yet hold.
     The methods are the kernels: ``residuals``, ``newton``, ``step_setup``, ``trial``, ``accept``; ``record()`` reads the
-    (K, RATO_IPM_REC) scalars back -- the only read-back an iteration needs."""
+    (K, RATO_IPM_REC) scalars back -- the only read-back an iteration needs.  ``vec``: 'workgroup' (csrc/ipm_driver.hip, one
+    workgroup per problem) or 'grid' (csrc/ipm_driver_grid.hip, DESIGN §7.al: the rows spread over the device, bitwise the
+    same state after every method; its scratch, ``work``, is allocated here once)."""
     NV = ("v", "zl", "zu", "vL", "vU", "Sigma", "gbar", "dv", "dzl", "dzu", "vt")
     N = ("curv", "lin", "gradf", "rz", "dz", "ez")
     M = ("y", "gL", "c", "d", "w", "rs", "dyE", "r2", "q", "dy")
     SCALARS = ("mu", "nu", "dw", "dc", "tol", "E0", "prim", "dual", "a_max", "a_dual", "Dphi", "phi", "alpha", "sf")
 
-    def __init__(self, ps, dev, ldv=None, ldm=None, fill=np.nan):
+    def __init__(self, ps, dev, ldv=None, ldm=None, fill=np.nan, vec='workgroup'):
         import torch
         from . import _lib
+        if vec not in VECS:
+            raise ValueError(f"vec must be 'workgroup' or 'grid', got {vec!r}")
+        self.vec = vec
         p0 = ps[0]
         self.K, self.n, self.m, self.nI = len(ps), p0.n, p0.m, int(np.sum(p0.I))
         self.nv = self.n + self.nI
@@ -607,6 +623,10 @@ class DeviceState:
         fields = [k for k, _ in _lib.IpmState._fields_]              # the struct's pointers follow ldm, named as the tensors are
         self.c_state = _lib.IpmState(self.K, self.n, self.nI, self.m, self.ldv, self.ldm,
                                      *[getattr(self, k).data_ptr() for k in fields[fields.index("ldm") + 1:]])
+        self.work = None
+        if vec == 'grid':
+            size = _lib.load().rato_ipm_grid_work_doubles(self.n, self.nI, self.m, self.K)
+            self.work = torch.empty(size, dtype=torch.float64, device=self.dev)
 
     def _host_vector(self, p, name):
         """what a Problem holds of the named device vector, in the device's layout, or None"""
@@ -655,31 +675,63 @@ class DeviceState:
         """the z part of ``v`` (or ``vt``) as a contiguous (K, n) tensor (a copy on the device)"""
         return getattr(self, of)[:, :self.n].contiguous()
 
+    own_clock = None             # a dict while ``vector_clock()`` measures: every call is then waited for
+
+    @staticmethod
+    def launches(vec, name, args):
+        """the kernel launches of one call (include/rato_saa.h: the grid form's count per entry point)"""
+        if vec == 'workgroup':
+            return 1
+        if name == "rato_ipm_newton":
+            return 1 if args[0] != 1 else 2 if args[-1] < 60 else 1  # RATO_IPM_PHASE_LADDER: rows and finish; finish alone at 60
+        return {"rato_ipm_residuals": 3, "rato_ipm_step_setup": 3, "rato_ipm_trial": 1, "rato_ipm_accept": 4}[name]
+
     def _call(self, name, *args):
-        lib = self.lib
+        """the entry point ``name`` ('rato_ipm_residuals', ...) in this state's form -> None; raises on a status"""
+        lib, clock = self.lib, DeviceState.own_clock
+        full, more = (name + "_grid_f64", (lib.ptr(self.work), self.work.numel())) if self.vec == 'grid' else (name + "_f64", ())
         with self.torch.cuda.device(self.dev):
-            return getattr(lib.load(), name)(self.c_state, *args, lib.current_stream())
+            if clock is not None:
+                self.torch.cuda.synchronize(self.dev)
+                t0 = time.perf_counter()
+            lib.check(getattr(lib.load(), full)(self.c_state, *args, *more, lib.current_stream()), full)
+            if clock is not None:
+                self.torch.cuda.synchronize(self.dev)
+                clock["seconds"] += time.perf_counter() - t0
+                clock["calls"] += 1
+                clock["launches"] += self.launches(self.vec, name, args)
 
     def _ld(self, t):
         return 0 if t is None else t.shape[1]
 
     def residuals(self, g, JTy, last=False):
-        self.lib.check(self._call("rato_ipm_residuals_f64", self.lib.ptr(g), self._ld(g), self.lib.ptr(JTy), self._ld(JTy), int(last)),
-                       "rato_ipm_residuals_f64")
+        self._call("rato_ipm_residuals", self.lib.ptr(g), self._ld(g), self.lib.ptr(JTy), self._ld(JTy), int(last))
 
     def newton(self, phase, a=None, b=None, info=None, flag=0):
         lib = self.lib
-        lib.check(self._call("rato_ipm_newton_f64", lib.IPM_PHASES[phase], lib.ptr(a), self._ld(a), lib.ptr(b), self._ld(b),
-                             lib.ptr(info), int(flag)), "rato_ipm_newton_f64")
+        self._call("rato_ipm_newton", lib.IPM_PHASES[phase], lib.ptr(a), self._ld(a), lib.ptr(b), self._ld(b), lib.ptr(info), int(flag))
 
     def step_setup(self, Hdv):
-        self.lib.check(self._call("rato_ipm_step_setup_f64", self.lib.ptr(Hdv), self._ld(Hdv)), "rato_ipm_step_setup_f64")
+        self._call("rato_ipm_step_setup", self.lib.ptr(Hdv), self._ld(Hdv))
 
     def trial(self):
-        self.lib.check(self._call("rato_ipm_trial_f64"), "rato_ipm_trial_f64")
+        self._call("rato_ipm_trial")
 
     def accept(self, gt):
-        self.lib.check(self._call("rato_ipm_accept_f64", self.lib.ptr(gt), self._ld(gt)), "rato_ipm_accept_f64")
+        self._call("rato_ipm_accept", self.lib.ptr(gt), self._ld(gt))
+
+
+@contextlib.contextmanager
+def vector_clock():
+    """For the profiles (tools/hopper_solve_bench.py --vec): inside, every ``DeviceState`` call is preceded and followed by a
+    device-wide wait and timed -> the dict it fills: ``seconds`` in the driver's own vector kernels, their ``calls`` and
+    ``launches``.  The waits make the solve slower; nothing else changes."""
+    clock = dict(seconds=0.0, calls=0, launches=0)
+    DeviceState.own_clock = clock
+    try:
+        yield clock
+    finally:
+        DeviceState.own_clock = None
 
 
 def newton_steps_device(be, st, run, fact, refine=2):
@@ -718,18 +770,19 @@ def newton_steps_device(be, st, run, fact, refine=2):
     return run
 
 
-def solve_group_device(models, Z0s, tol, max_iter, be, verbose):
+def solve_group_device(models, Z0s, tol, max_iter, be, verbose, driver='device'):
     """``solve_group`` with the iterate on the device: the Problems are made on the host once (bound relaxation, the push into
     the interior, sf), uploaded as a ``DeviceState``, and every lockstep iteration is a chain of K-problem launches; the host
     reads back the scalar record after the residual phase and after each line-search trial, and the info of each
     factorization.  A problem that has ended stays in the launches and is skipped inside them.  ``be`` serves device tensors:
     eval_full_t / eval_g_t / matvec_t / tmatvec_t / hess_apply_t / factor_t / solve_t.  -> [(Z, info)] as ``solve_group``'s,
-    with info["driver"] = 'device'."""
+    with info["driver"] = ``driver``: 'device', or 'device_grid' for the vector kernels' grid form (``DeviceState(vec='grid')``),
+    which changes no bit of the result."""
     from . import _lib
     K = len(models)
     g0 = be.eval_g(list(range(K)), [np.asarray(Z, dtype=np.float64) for Z in Z0s])
     ps = [Problem(m, Z, g, tol) for m, Z, g in zip(models, Z0s, g0)]
-    st = DeviceState(ps, be.dev)
+    st = DeviceState(ps, be.dev, vec=VEC_OF_DRIVER[driver])
     fact = [0] * K
     STATUS, SEARCHING = st.F["status"], st.F["searching"]
     for it in range(max_iter + 1):
@@ -762,16 +815,16 @@ def solve_group_device(models, Z0s, tol, max_iter, be, verbose):
     st.download(ps)
     for p, nf in zip(ps, fact):
         p.factorizations = nf                                        # the device's record does not count them: the host did
-    return _results(ps, be, driver='device')
+    return _results(ps, be, driver=driver)
 
 
 def solve_groups(groups, setup, Z0s, tol, max_iter, verbose, clocks, driver='host'):
     """what a ``solve_batch`` ends with: the groups (lists of problem numbers) one after the other, each by ``solve_group``
-    (``driver='device'``: ``solve_group_device``) on the (models, backend) ``setup(members)`` makes -> [(Z, info)] in the
+    (``driver='device'`` / ``'device_grid'``: ``solve_group_device``) on the (models, backend) ``setup(members)`` makes -> [(Z, info)] in the
     problems' order.  ``clocks`` (a dict, or None) receives the sums of the backends' clocks and the wall clock."""
     out = [None] * sum(len(members) for members in groups)
     t0 = time.perf_counter()
-    run = solve_group_device if driver == 'device' else solve_group
+    run = functools.partial(solve_group_device, driver=driver) if on_device(driver) else solve_group
     for members in groups:
         models, be = setup(members)
         for i, r in zip(members, run(models, [Z0s[i] for i in members], tol, max_iter, be, verbose)):

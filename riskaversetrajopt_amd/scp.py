@@ -618,17 +618,17 @@ def run_drone_gaussian(model, Z0=None, maxiter=3000, callbacks=None, results_dir
     ``solver='ipm'``: the same NLP by ``drone_gaussian_ipm.solve_batch`` (a batch of one; ``backend`` 'device', or
     'numpy', the default when ``callbacks`` are given; ``tol``: its E_0 tolerance) -> the same keys with status one of
     'converged' | 'max_iter' | 'line_search', nit = iterations, nfev = factorizations, constr_violation / optimality = the
-    primal / dual parts of the final E_0, and ``info`` (``solve_batch``'s, with the multipliers).  ``driver``: 'host' or 'device'
-    (``solver='ipm'`` only: where ``solve_batch`` keeps the iterate).  ``chol``: 'workgroup' or 'grid'
+    primal / dual parts of the final E_0, and ``info`` (``solve_batch``'s, with the multipliers).  ``driver``: 'host', 'device'
+    or 'device_grid' (``solver='ipm'`` only: where ``solve_batch`` keeps the iterate).  ``chol``: 'workgroup' or 'grid'
     (``solver='ipm'`` on the device: which Cholesky; the result does not depend on it)."""
     from . import ipm as _ipm
     _ipm.check_chol(chol)
-    if driver not in ('host', 'device'):
-        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
+    if driver not in _ipm.DRIVERS:
+        raise ValueError(f"driver must be 'host', 'device' or 'device_grid', got {driver!r}")
     if solver not in ('trust-constr', 'ipm'):
         raise ValueError(f"solver must be 'trust-constr' or 'ipm', got {solver!r}")
-    if driver == 'device' and solver != 'ipm':
-        raise ValueError("driver='device' is the interior-point method's: it needs solver='ipm'")
+    if _ipm.on_device(driver) and solver != 'ipm':
+        raise ValueError(f"driver={driver!r} is the interior-point method's: it needs solver='ipm'")
     if solver == 'ipm':
         from . import drone_gaussian_ipm
         backend = ('device' if callbacks is None else 'numpy') if backend is None else backend
@@ -697,8 +697,8 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
     (drone_risk.py:742-761) as one call.  The start of every alpha is the SAA repeat-0 solution
     ``results_dir``/drone_alpha=<alpha>_repeat=0.npy, read where it exists and made by ``drone_saa_experiment`` (one repeat)
     where it does not; each alpha is solved by ``run_drone_gaussian`` (``solver='ipm'``: all alphas in ONE
-    ``drone_gaussian_ipm.solve_batch`` call on the device, whose clocks ``clocks`` receives and whose ``driver`` is 'host' or
-    'device' and whose ``chol`` is 'workgroup' or 'grid') and written to drone_gaussian_alpha=<alpha>.npy as
+    ``drone_gaussian_ipm.solve_batch`` call on the device, whose clocks ``clocks`` receives and whose ``driver`` is 'host',
+    'device' or 'device_grid' and whose ``chol`` is 'workgroup' or 'grid') and written to drone_gaussian_alpha=<alpha>.npy as
     (us, xs); then ONE ``eval_batch_device`` call of a fresh ``drone_risk.Model`` of M_mc samples (drawn under
     ``np.random.seed(seed)``) over the solutions.  Per alpha percentage_safe = mean(max constraint <= 1e-6), as the block
     computes it, and monte_carlo_cost.
@@ -710,10 +710,10 @@ def drone_gaussian_experiment(alphas=(0.05, 0.1, 0.2, 0.3), S=20, results_dir='r
     alphas = [float(a) for a in alphas]
     from . import ipm as _ipm
     _ipm.check_chol(chol)
-    if driver not in ('host', 'device'):
-        raise ValueError(f"driver must be 'host' or 'device', got {driver!r}")
-    if driver == 'device' and solver != 'ipm':
-        raise ValueError("driver='device' is the interior-point method's: it needs solver='ipm'")
+    if driver not in _ipm.DRIVERS:
+        raise ValueError(f"driver must be 'host', 'device' or 'device_grid', got {driver!r}")
+    if _ipm.on_device(driver) and solver != 'ipm':
+        raise ValueError(f"driver={driver!r} is the interior-point method's: it needs solver='ipm'")
     os.makedirs(results_dir, exist_ok=True)
     missing = [a for a in alphas if not os.path.isfile(os.path.join(results_dir, f"drone_alpha={a}_repeat=0.npy"))]
     if missing:
@@ -754,7 +754,7 @@ def run_hopper(model, Z0=None, tol=1e-3, max_iter=3000, backend='device', newton
     """The hopper script's solve block (hopper.py:642-670) for one model: ``hopper_ipm.solve_batch`` in IPOPT's place, from
     ``Z0`` (default ``model.initial_guess()``) -> dict(Z, xs (S+1, 8), us (S, 4), status, info, total_s).  status is
     'converged' only if the final error E_0 <= tol shows it.  newton: 'dense' or 'arrow' (``hopper_ipm.solve_batch``).
-    ``driver``: 'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either
+    ``driver``: 'host', 'device' or 'device_grid' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either
     newton, 'arrow' with a precision='f64' model).  ``chol``: 'workgroup' or 'grid' (the device Cholesky)."""
     t0 = time.perf_counter()
     Z, info = model.solve(Z0, tol=tol, max_iter=max_iter, backend=backend, newton=newton, driver=driver, chol=chol)
@@ -795,7 +795,7 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
     solution (:465-479).  With ``results_dir`` the files hopper_base_results.npy and hopper_saa_alpha=<a>_results.npy are
     written (xs then us, ``save_results``), whatever the status.  ``fields``: (intensities, thetas, taus), each (M, 30), in place
     of the draw; ``newton``: 'dense' or 'arrow' (``hopper_ipm.solve_batch``: 'arrow' is the one that scales with M); ``driver``:
-    'host' or 'device' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either newton).
+    'host', 'device' or 'device_grid' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either newton).
     -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)
     ``chol``: 'workgroup' or 'grid', the device Cholesky of both runs (``hopper_ipm.solve_batch``; the results do not depend on it)."""
     from . import ipm as _ipm

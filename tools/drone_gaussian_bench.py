@@ -32,6 +32,9 @@ the split of a lockstep iteration.
 
     python tools/drone_gaussian_bench.py --solver ipm --driver both [--solves 7]
 
+``--driver`` also takes ``device_grid`` (the device driver with its own vector kernels spread over the rows) and
+``all`` (host, device and device_grid; ``both`` stays host and device).  The timed solves of the drivers alternate.
+
 With ``--solver ipm --chol {workgroup,grid,both}`` it measures the interior-point solve under one or both Choleskys (DESIGN
 §7.ak: csrc/chol.hip, one workgroup per problem, or csrc/chol_grid.hip, one launch per panel over the whole device; the same
 bits) and writes profiles/drone_gaussian_solve_chol_grid.json: the same batch under ``--driver`` (default device; with ``both``,
@@ -125,6 +128,9 @@ def solve_bench(args):
         write(out, path)
 
 
+DRIVER_SETS = {"both": ("host", "device"), "all": ("host", "device", "device_grid")}
+
+
 def driver_bench(args):
     """the S = 20 batch under the host and / or the device driver -> profiles/drone_gaussian_solve_device_driver.json"""
     import torch
@@ -134,7 +140,7 @@ def driver_bench(args):
     path = args.out or os.path.join(ROOT, "profiles", "drone_gaussian_solve_device_driver.json")
     out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": list(alphas), "tol": args.tol, "maxiter": args.maxiter,
            "start": "SAA repeat 0 (drone_saa_experiment, M = 50, 60 iterations, seed 0)", "solves": args.solves, "drivers": {}}
-    drivers = ("host", "device") if args.driver == "both" else (args.driver,)
+    drivers = DRIVER_SETS.get(args.driver, (args.driver,))
     # the SAA starts where they are missing (and the code objects of everything around the solve)
     scp.drone_gaussian_experiment(alphas, S=S, results_dir=args.results_dir, maxiter=3, solver='ipm', tol=args.tol)
     models = [DG.Model(S, alpha=a) for a in alphas]
@@ -142,36 +148,45 @@ def driver_bench(args):
     solve = lambda d, ck=None: drone_gaussian_ipm.solve_batch(models, Z0s, tol=args.tol, max_iter=args.maxiter, driver=d, clocks=ck)
     for d in drivers:
         solve(d)                                                     # warm-up: code objects, allocator
-        torch.cuda.synchronize()
-        walls = []
-        for _ in range(args.solves):
+    torch.cuda.synchronize()
+    walls, sols = {d: [] for d in drivers}, {}
+    for _ in range(args.solves):                                     # alternating: a drift of the board meets every driver
+        for d in drivers:
             t0 = time.perf_counter()
-            sols = solve(d)
-            walls.append(time.perf_counter() - t0)
-        rounds = max(1, max(info["iterations"] for _, info in sols))
+            sols[d] = solve(d)
+            walls[d].append(time.perf_counter() - t0)
+    for d in drivers:
+        rounds = max(1, max(info["iterations"] for _, info in sols[d]))
         drone_gaussian_ipm.DeviceBackend.sync_clocks = True          # one more solve, a device-wide wait behind every block
         try:
             clocks = {}
             solve(d, clocks)
         finally:
             drone_gaussian_ipm.DeviceBackend.sync_clocks = False
-        out["drivers"][d] = {"wall_ms": [1e3 * w for w in walls], "median_wall_ms": 1e3 * float(np.median(walls)),
-                             "lockstep_iterations": rounds, "median_ms_per_iteration": 1e3 * float(np.median(walls)) / rounds,
+        w = walls[d]
+        out["drivers"][d] = {"wall_ms": [1e3 * x for x in w], "median_wall_ms": 1e3 * float(np.median(w)),
+                             "min_wall_ms": 1e3 * min(w), "max_wall_ms": 1e3 * max(w),
+                             "lockstep_iterations": rounds, "median_ms_per_iteration": 1e3 * float(np.median(w)) / rounds,
                              "per_alpha": [{"alpha": a, "status": info["status"], "iterations": info["iterations"],
                                             "factorizations": info["factorizations"], "E0": info["E0"], "f": info["f"]}
-                                           for a, (_, info) in zip(alphas, sols)],
+                                           for a, (_, info) in zip(alphas, sols[d])],
                              "split_solve_wall_ms": 1e3 * clocks["wall"],
                              "split_ms_per_iteration": {k: 1e3 * v / rounds for k, v in clocks.items()}}
-    if len(drivers) == 2:
+    if "host" in drivers and "device" in drivers:
         h, dv = out["drivers"]["host"], out["drivers"]["device"]
         out["host_over_device"] = h["median_wall_ms"] / dv["median_wall_ms"]
+    if "device" in drivers and "device_grid" in drivers:
+        dv, dg = out["drivers"]["device"], out["drivers"]["device_grid"]
+        out["device_over_device_grid"] = dv["median_wall_ms"] / dg["median_wall_ms"]
+        out["device_grid_is_bitwise_device"] = all(same_solution(a, b, but=("driver",)) for a, b in zip(sols["device_grid"], sols["device"]))
+        out["command"] = "python tools/drone_gaussian_bench.py " + " ".join(sys.argv[1:])
     write(out, path)
 
 
-def same_solution(r0, r1):
+def same_solution(r0, r1, but=()):
     (Z0, i0), (Z1, i1) = r0, r1
     eq = lambda a, b: a.tobytes() == b.tobytes() if isinstance(a, np.ndarray) else a == b
-    return Z0.tobytes() == Z1.tobytes() and set(i0) == set(i1) and all(eq(i0[k], i1[k]) for k in i0)
+    return Z0.tobytes() == Z1.tobytes() and set(i0) == set(i1) and all(eq(i0[k], i1[k]) for k in i0 if k not in but)
 
 
 def chol_bench(args):
@@ -184,7 +199,7 @@ def chol_bench(args):
     solves = 5 if args.solves is None else args.solves
     out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": list(alphas), "tol": args.tol, "maxiter": args.maxiter,
            "start": "SAA repeat 0 (drone_saa_experiment, M = 50, 60 iterations, seed 0)", "solves": solves, "drivers": {}}
-    drivers = ("host", "device") if args.driver == "both" else (args.driver or "device",)
+    drivers = DRIVER_SETS.get(args.driver, (args.driver or "device",))
     methods = ("workgroup", "grid") if args.chol == "both" else (args.chol,)
     scp.drone_gaussian_experiment(alphas, S=S, results_dir=args.results_dir, maxiter=3, solver='ipm', tol=args.tol)   # the SAA starts
     models = [DG.Model(S, alpha=a) for a in alphas]
@@ -235,7 +250,8 @@ def main():
     ap.add_argument("--solver", choices=("trust-constr", "ipm", "both"), default=None)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--results-dir", default="results")
-    ap.add_argument("--driver", choices=("host", "device", "both"), default=None)
+    ap.add_argument("--driver", choices=("host", "device", "device_grid", "both", "all"), default=None,
+                    help="both: host and device; all: host, device and device_grid")
     ap.add_argument("--solves", type=int, default=None, help="timed solves per driver (default 7) or per Cholesky (default 5)")
     ap.add_argument("--chol", choices=("workgroup", "grid", "both"), default=None,
                     help="measure the interior-point solve under the Cholesky method(s) instead (with --solver ipm)")

@@ -47,6 +47,19 @@ problems of the SAA grid as ONE batch.  The methods run in one process, a warm-u
 (median, min, max), the per-iteration split of one more solve with ``sync_clocks`` (what is recorded today), and whether every
 (Z, info) is bitwise the same under both.  The file is rewritten after every run, and a later call adds its runs to it.
 
+``--driver`` also takes ``device_grid`` (the device driver with its own vector kernels spread over the rows) and
+``all`` (host, device and device_grid; ``both`` stays host and device).
+
+``--vec {workgroup,grid,both}`` measures the solve under one or both forms of the device driver's vector kernels instead
+(driver='device' / 'device_grid': csrc/ipm_driver.hip, one workgroup per problem, or csrc/ipm_driver_grid.hip, a grid over the
+rows; the same bits), into profiles/ipm_driver_grid.json: under ``--newton`` and ``--chol`` (one method, default workgroup), per
+M of ``--M``, the baseline from ``initial_guess()`` and the alphas as one batch from the host driver's baseline solution -- or,
+with ``--repeats R``, the A R problems of the SAA grid as ONE batch.  The forms run in one process, a warm-up solve each, then
+``--solves`` timed solves each, ALTERNATING (median, min, max; ms per batch and per lockstep iteration); then one more solve per
+form inside ``ipm.vector_clock()``, a device-wide wait around every call of the driver's own kernels: their share of the
+iteration, their calls and their launches per iteration; and whether every (Z, info) is bitwise the same under both.  Every
+run records its command line.  The file is rewritten after every run, and a later call adds its runs to it.
+
 Prints one JSON line.  There is no CPU fallback: without a GPU nothing is measured.
 """
 import argparse
@@ -58,6 +71,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+DRIVER_SETS = {"both": ("host", "device"), "all": ("host", "device", "device_grid")}
 
 
 def problem_record(r, S):
@@ -201,8 +217,10 @@ def measure_drivers(models, Z0s, newton, drivers, solves, S):
                                for m, (Z, info) in zip(models, sols)],
                   "split_ms_per_iteration": per_it(launch), "split_ms_per_iteration_sync_clocks": per_it(synced),
                   "device_to_host_copies_per_iteration": copies[0] / rounds}
-    if len(drivers) == 2:
+    if "host" in rec and "device" in rec:
         rec["host_over_device"] = rec["host"]["median_ms_per_batch"] / rec["device"]["median_ms_per_batch"]
+    if "device" in rec and "device_grid" in rec:
+        rec["device_over_device_grid"] = rec["device"]["median_ms_per_batch"] / rec["device_grid"]["median_ms_per_batch"]
     return rec
 
 
@@ -221,7 +239,7 @@ def driver_bench(args):
     import torch
     from riskaversetrajopt_amd import hopper, hopper_ipm, scp
     S, alphas, newton = args.S, [float(a) for a in args.alphas], args.newton
-    drivers = ("host", "device") if args.driver == "both" else (args.driver,)
+    drivers = DRIVER_SETS.get(args.driver, (args.driver,))
     out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": alphas, "tol": 1e-3, "max_iter": 3000, "newton": newton,
            "solves": args.solves, "saa_start": "the host driver's baseline solution", "runs": {}}
 
@@ -254,7 +272,8 @@ def grid_bench(args):
     import torch
     from riskaversetrajopt_amd import hopper, hopper_ipm, scp
     S, alphas, newton, R = args.S, [float(a) for a in args.alphas], args.newton, args.repeats
-    drivers = ("device", "host") if args.driver in (None, "both") else (args.driver,)
+    drivers = ("device", "host") if args.driver in (None, "both") else ("device", "device_grid", "host") if args.driver == "all" \
+        else (args.driver,)
     out = {"device": torch.cuda.get_device_name(0), "S": S, "alphas": alphas, "repeats": R, "tol": 1e-3, "max_iter": 3000,
            "seed": 1, "saa_start": "the host driver's baseline solution", "runs": {}}
     if args.out and os.path.exists(args.out):                        # a later call adds its runs to the file of an earlier one
@@ -317,14 +336,119 @@ def grid_bench(args):
     print(write_profile(out, args.out))
 
 
+def runs_of(args, key_format):
+    """the runs --chol and --vec measure, per M of --M: (name, models, starts) of the baseline from ``initial_guess()`` and of the
+    alphas as one batch from the host driver's baseline solution -- or, with --repeats R, of the A R problems of the SAA grid as ONE
+    batch.  ``key_format`` % (M, newton) names them."""
+    from riskaversetrajopt_amd import hopper, hopper_ipm, scp
+    S, alphas, newton, R = args.S, [float(a) for a in args.alphas], args.newton, args.repeats
+    for M in [int(m) for m in str(args.M).split(",")]:
+        mk = lambda method, a, fields: hopper.Model(M, method, a, S=S, fields=fields, precision='f64')
+        key = key_format % (M, newton)
+        if R is not None:
+            draws, _ = scp.draw_hopper_saa_fields(R, M, 1, seed=1)
+            zero = np.zeros((M, hopper.num_mu_features))
+            base = mk('baseline', 0.1, (zero, zero, zero))
+            (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)
+            xs, us = base.convert_z_to_xs_us_mats(Zb)
+            models = [mk('saa', a, draws[r]) for r in range(R) for a in alphas]
+            yield key + ",repeats=%d" % R, models, [scp.hopper_saa_start(m, xs, us) for m in models]
+            continue
+        fields = tuple(f[:M] for f in script_fields(M)[0]) if newton == "arrow" else \
+            hopper.sample_friction_fields(M, np.random.RandomState(1))
+        base = mk('baseline', 0.1, fields)
+        (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)
+        xs, us = base.convert_z_to_xs_us_mats(Zb)
+        saa = [mk('saa', a, fields) for a in alphas]
+        yield key + ",baseline", [base], [base.initial_guess()]
+        if saa:
+            yield key + ",saa", saa, [scp.hopper_saa_start(m, xs, us) for m in saa]
+
+
+def same_solution(r0, r1, but=()):
+    (Z0, i0), (Z1, i1) = r0, r1
+    eq = lambda a, b: a.tobytes() == b.tobytes() if isinstance(a, np.ndarray) else a == b
+    return Z0.tobytes() == Z1.tobytes() and set(i0) == set(i1) and all(eq(i0[k], i1[k]) for k in i0 if k not in but)
+
+
+def vec_bench(args):
+    """runs under one or both forms of the device driver's vector kernels -> profiles/ipm_driver_grid.json"""
+    import time
+
+    import torch
+    from riskaversetrajopt_amd import _lib, hopper_ipm, ipm
+    chol = args.chol or "workgroup"
+    forms = ("workgroup", "grid") if args.vec == "both" else (args.vec,)
+    driver_of = {v: d for d, v in ipm.VEC_OF_DRIVER.items()}
+    out = {"device": torch.cuda.get_device_name(0), "S": args.S, "tol": 1e-3, "max_iter": 3000, "solves": args.solves,
+           "rows_per_workgroup": int(_lib.load().rato_ipm_grid_rows()),
+           "saa_start": "the host driver's baseline solution", "runs": {}}
+    if args.out and os.path.exists(args.out):                        # a later call adds its runs to the file of an earlier one
+        with open(args.out) as f:
+            old = json.loads(f.readline())
+        if all(old.get(k) == out[k] for k in ("device", "S", "tol", "max_iter", "solves")):
+            out["runs"] = old.get("runs", {})
+
+    def measure(models, Z0s):
+        solve = lambda v, ck=None: hopper_ipm.solve_batch(models, Z0s, driver=driver_of[v], clocks=ck, newton=args.newton, chol=chol)
+        st = hopper_ipm.structure(models[0])
+        rec = {"command": "python tools/hopper_solve_bench.py " + " ".join(sys.argv[1:]), "problems": len(models),
+               "alphas": sorted({float(m.alpha) for m in models if m.method == 'saa'}), "n": int(st["n"]), "m": int(st["ncon"])}
+        sols, walls = {}, {v: [] for v in forms}
+        for v in forms:
+            solve(v)                                                 # warm-up of this form: code objects, maps, allocator
+        torch.cuda.synchronize()
+        for _ in range(args.solves):                                 # alternating: a drift of the board meets both forms
+            for v in forms:
+                t0 = time.perf_counter()
+                sols[v] = solve(v)
+                walls[v].append(time.perf_counter() - t0)
+        for v in forms:
+            rounds = max(1, max(info["iterations"] for _, info in sols[v]))
+            with ipm.vector_clock() as own:                          # one more solve, a device-wide wait around the driver's kernels
+                t0 = time.perf_counter()
+                solve(v)
+                waited = time.perf_counter() - t0
+            synced = {}
+            ipm.DeviceBase.sync_clocks = True                        # and one with a device-wide wait behind every block
+            try:
+                solve(v, synced)
+            finally:
+                ipm.DeviceBase.sync_clocks = False
+            status = {}
+            for _, info in sols[v]:
+                status[info["status"]] = status.get(info["status"], 0) + 1
+            w = walls[v]
+            rec[v] = {"driver": driver_of[v], "wall_ms": [1e3 * x for x in w], "median_ms_per_batch": 1e3 * float(np.median(w)),
+                      "min_ms_per_batch": 1e3 * min(w), "max_ms_per_batch": 1e3 * max(w), "lockstep_iterations": rounds,
+                      "median_ms_per_iteration": 1e3 * float(np.median(w)) / rounds, "status": status,
+                      "factorizations": int(sum(info["factorizations"] for _, info in sols[v])),
+                      "driver_kernels_ms_per_iteration_waited": 1e3 * own["seconds"] / rounds,
+                      "driver_calls_per_iteration": own["calls"] / rounds, "driver_launches_per_iteration": own["launches"] / rounds,
+                      "waited_solve_ms_per_iteration": 1e3 * waited / rounds,
+                      "split_ms_per_iteration_sync_clocks": {k: 1e3 * x / rounds for k, x in synced.items()}}
+        if len(forms) == 2:
+            w, g = rec["workgroup"], rec["grid"]
+            rec["grid_is_bitwise_workgroup"] = all(same_solution(a, b, but=("driver",)) for a, b in zip(sols["grid"], sols["workgroup"]))
+            rec["workgroup_over_grid"] = w["median_ms_per_batch"] / g["median_ms_per_batch"]
+            rec["grid_wins"] = g["max_ms_per_batch"] < w["min_ms_per_batch"]
+            rec["grid_loses"] = g["min_ms_per_batch"] > w["max_ms_per_batch"]
+        return rec
+    for name, models, Z0s in runs_of(args, "M=%d,newton=%s,chol=" + chol):
+        out["runs"][name] = measure(models, Z0s)
+        write_profile(out, args.out)
+        print("%s done" % name, file=sys.stderr, flush=True)
+    print(write_profile(out, args.out))
+
+
 def chol_bench(args):
     """runs under one or both Choleskys -> profiles/hopper_solve_chol_grid.json"""
     import time
 
     import torch
-    from riskaversetrajopt_amd import hopper, hopper_ipm, ipm, scp
-    S, alphas, newton, R = args.S, [float(a) for a in args.alphas], args.newton, args.repeats
-    driver = "device" if args.driver in (None, "both") else args.driver
+    from riskaversetrajopt_amd import hopper_ipm, ipm
+    S, newton = args.S, args.newton
+    driver = "device" if args.driver in (None, "both", "all") else args.driver
     methods = ("workgroup", "grid") if args.chol == "both" else (args.chol,)
     out = {"device": torch.cuda.get_device_name(0), "S": S, "tol": 1e-3, "max_iter": 3000, "solves": args.solves,
            "saa_start": "the host driver's baseline solution", "runs": {}}
@@ -373,31 +497,10 @@ def chol_bench(args):
             rec["grid_wins"] = g["max_ms_per_batch"] < w["min_ms_per_batch"]
             rec["grid_loses"] = g["min_ms_per_batch"] > w["max_ms_per_batch"]
         return rec
-    for M in [int(m) for m in str(args.M).split(",")]:
-        mk = lambda method, a, fields: hopper.Model(M, method, a, S=S, fields=fields, precision='f64')
-        key = "M=%d,newton=%s,driver=%s" % (M, newton, driver)
-        if R is not None:                                            # the SAA grid as one batch
-            draws, _ = scp.draw_hopper_saa_fields(R, M, 1, seed=1)
-            zero = np.zeros((M, hopper.num_mu_features))
-            base = mk('baseline', 0.1, (zero, zero, zero))
-            (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)
-            xs, us = base.convert_z_to_xs_us_mats(Zb)
-            models = [mk('saa', a, draws[r]) for r in range(R) for a in alphas]
-            runs = {key + ",repeats=%d" % R: (models, [scp.hopper_saa_start(m, xs, us) for m in models])}
-        else:
-            fields = tuple(f[:M] for f in script_fields(M)[0]) if newton == "arrow" else \
-                hopper.sample_friction_fields(M, np.random.RandomState(1))
-            base = mk('baseline', 0.1, fields)
-            (Zb, _), = hopper_ipm.solve_batch([base], newton=newton)
-            xs, us = base.convert_z_to_xs_us_mats(Zb)
-            saa = [mk('saa', a, fields) for a in alphas]
-            runs = {key + ",baseline": ([base], [base.initial_guess()]),
-                    key + ",saa": (saa, [scp.hopper_saa_start(m, xs, us) for m in saa])}
-        for name, (models, Z0s) in runs.items():
-            if models:
-                out["runs"][name] = measure(models, Z0s)
-                write_profile(out, args.out)
-                print("%s done" % name, file=sys.stderr, flush=True)
+    for name, models, Z0s in runs_of(args, "M=%d,newton=%s,driver=" + driver):
+        out["runs"][name] = measure(models, Z0s)
+        write_profile(out, args.out)
+        print("%s done" % name, file=sys.stderr, flush=True)
     print(write_profile(out, args.out))
 
 
@@ -408,8 +511,12 @@ def main():
     ap.add_argument("--newton", choices=("dense", "arrow"), default="dense")
     ap.add_argument("--alphas", type=float, nargs="*", default=[0.05, 0.1, 0.2, 0.3, 0.5, 0.75])
     ap.add_argument("--out", default=None)
-    ap.add_argument("--driver", choices=("host", "device", "both"), default=None,
-                    help="measure the solve (either --newton) under the interior-point driver(s) instead")
+    ap.add_argument("--driver", choices=("host", "device", "device_grid", "both", "all"), default=None,
+                    help="measure the solve (either --newton) under the interior-point driver(s) instead; both: host and "
+                         "device, all: host, device and device_grid")
+    ap.add_argument("--vec", choices=("workgroup", "grid", "both"), default=None,
+                    help="measure the solve under the form(s) of the device driver's vector kernels instead (--newton; --chol, one "
+                         "method; --repeats)")
     ap.add_argument("--solves", type=int, default=5, help="with --driver or --repeats: timed solves per run and driver")
     ap.add_argument("--repeats", type=int, default=None,
                     help="measure the grid of alphas x this many draws of the fields as one batch against repeat by repeat instead")
@@ -419,6 +526,14 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("hopper_solve_bench needs a GPU: nothing here is measured on the host in its place")
+    if args.vec is not None:
+        if args.chol == "both" or args.driver is not None:
+            raise SystemExit("--vec compares driver='device' and 'device_grid' under ONE Cholesky: --chol workgroup or grid, no --driver")
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "ipm_driver_grid.json")
+        if args.repeats is not None and args.repeats < 1:
+            raise SystemExit("--repeats needs at least one draw")
+        return vec_bench(args)
     if args.chol is not None:
         if args.out is None:
             args.out = os.path.join(ROOT, "profiles", "hopper_solve_chol_grid.json")
