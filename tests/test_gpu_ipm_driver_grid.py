@@ -53,10 +53,11 @@ def shapes():
         [(R - 6, 3, 20), (R, 7, 0)]
 
 
-def chain(des, sel, vec, ps=None):
+def chain(des, sel, vec, ps=None, keep=None, upto=None):
     """``test_gpu_ipm_driver.device_chain`` with the form as a parameter: residuals, rhs, two ladder attempts, q / r / update
     twice, finish, setup and two trial / accept rounds for the problems ``sel`` of the designed batch, the other kernels'
-    results replaced by the designed vectors -> [(phase, raw state)] after each phase"""
+    results replaced by the designed vectors -> [(phase, raw state)] after each phase.  ``keep``: the phases to take a snapshot
+    after (None: all); ``upto='setup'``: the chain ends after the step setup"""
     import torch
     n, m = des["n"], des["m"]
     ps = [D.problems(des)[k] for k in sel] if ps is None else ps
@@ -64,7 +65,7 @@ def chain(des, sel, vec, ps=None):
     assert (st.work is not None) == (vec == "grid")
     pick = lambda a, length: up(np.asarray(a)[sel], length + PAD)
     trail = []
-    snap = lambda phase: trail.append((phase, raw(st)))
+    snap = lambda phase: trail.append((phase, raw(st))) if keep is None or phase in keep else None
 
     def put(name, a):
         rws = [i for i, k in enumerate(sel) if k < 2]
@@ -93,6 +94,8 @@ def chain(des, sel, vec, ps=None):
     put("dv", des["dv"])
     st.step_setup(pick(des["Hdv"], n))
     snap("setup")
+    if upto == "setup":
+        return trail
     factors = dict(des, ct_factor=[f[sel] for f in des["ct_factor"]])
     for r in range(2):
         st.trial()
@@ -161,11 +164,16 @@ def test_an_accepted_step_is_applied_once():
 
 
 @pytest.mark.parametrize("where", ["zl", "zu", "zl_slack"])
-@pytest.mark.parametrize("shape", [2, 6])
-def test_a_nan_multiplier(shape, where):
+@pytest.mark.parametrize("shape,at", [(2, None), (6, None), (6, "R"), (6, "last"), (7, "R"), (7, "last")],
+                         ids=["2", "6", "6-R", "6-last", "7-R", "7-last"])
+def test_a_nan_multiplier(shape, at, where):
     """one NaN in zl (zu) of a bounded variable of the mu_loop problem: E0 is NaN and the status 'line_search'.  In zl of a
     bounded SLACK the host's max(a, b) rules drop the NaN from dual and from the complementarity, the problem keeps running
-    and the mu loop meets the side's NaN at every pass.  Either way the state is the workgroup form's, byte for byte."""
+    and the mu loop meets the side's NaN at every pass.  Either way the state is the workgroup form's, byte for byte.
+    ``at``: the entry that holds the NaN -- None: the middle of the variables (of the slacks), which is block 0; 'R': the first
+    entry of block 1; 'last': the last entry, in the last, partial block.  Both are slacks' entries (n = 5), of zu for 'zu'
+    and of zl otherwise.  At shape 6 (nv = R + 1) the two are one entry, the only row of block 1; at shape 7 (nv = 2 R + 1)
+    block 1 is a whole block and the last entry is the only row of block 2."""
     from riskaversetrajopt_amd import _lib
     F = {f: i for i, f in enumerate(_lib.IPM_FIELDS)}
     n, mE, mI = shapes()[shape]
@@ -173,7 +181,11 @@ def test_a_nan_multiplier(shape, where):
     got = {}
     for vec in VECS:
         ps = D.problems(des)
-        if where == "zl_slack":
+        if at is not None:
+            pos = rows() if at == "R" else n + mI - 1
+            assert n <= rows() <= pos < n + mI
+            (ps[0].zu if where == "zu" else ps[0].zl)[pos] = np.nan
+        elif where == "zl_slack":
             ps[0].zl[n + mI // 2] = np.nan
         else:
             getattr(ps[0], where)[n // 2] = np.nan
@@ -182,7 +194,7 @@ def test_a_nan_multiplier(shape, where):
         got[vec] = raw(st)
     assert not differing(got["grid"], got["workgroup"]), differing(got["grid"], got["workgroup"])
     rec = got["grid"]["rec"]
-    if where == "zl_slack":
+    if where == "zl_slack" or at is not None:
         assert rec[0, F["status"]] == -1.0 and np.isfinite(rec[0, F["E0"]])
     else:
         assert np.isnan(rec[0, F["E0"]]) and rec[0, F["status"]] == 2.0
