@@ -452,6 +452,45 @@ int rato_hopper_slip_hessian(int32_t M, int32_t C, const float* px, const float*
                              const float* lam, float* Z, float* h, float* dh_dfz, float* dh_dpx, float* part_hess3,
                              void* stream);
 
+/* The script's Monte-Carlo report (hopper.py:960-1007) evaluates K solutions -- the alphas and the baseline, or an alpha x
+ * repeat grid -- on ONE set of validation fields: K solutions in one launch, the hopper counterpart of rato_drone_eval_batch.
+ * ABI: additive (RATO_ABI_VERSION stays 12).
+ *   px, fx, fz [K][ldc] (device, ldc >= C)   the contact inputs of solution k in row k, gathered as for rato_hopper_slip
+ *   a, theta, tau [30][M]                    as rato_hopper_slip
+ *   Z   [K][ldz] (ldz >= M)                  Z[k][m] = max_c (fx[k][c] - mu_m(px[k][c]) fz[k][c]): row k is, to the bit, the Z
+ *                                            that rato_hopper_slip writes for solution k (one device function holds the value
+ *                                            arithmetic of both kernels)
+ *   arg [K][ldz] int32 or NULL               the smallest c (position in the gathered contact list) whose value equals
+ *                                            Z[k][m]: the contact step that slips; -1 when Z[k][m] is -inf (every value NaN).
+ *                                            A call without arg runs the kernel without the index.
+ *   alphas_host [K] HOST doubles, stats_out [K][RATO_N_STATS] device, or both NULL: row k of stats_out is, to the bit, the
+ *                                            rato_risk_stats record of row k of Z at alphas_host[k] (threshold thr; workspace
+ *                                            as rato_risk_stats) -- one rato_risk_stats_batch call per run of consecutive
+ *                                            equal alphas, i.e. one launch per run while M <= 12,288.
+ * Lanes past M and the columns M .. ldz-1 of Z and arg are not written; nothing has to be initialised; no atomics, no
+ * workgroup waits for another; the inputs are read through their device pointers at run time (a captured call sees what
+ * they hold at replay).  Launch shape: a lane is a sample whose 90 feature registers serve k_chunk solutions x C contacts;
+ * grid x = groups of (4 >> nw_log2) sample-waves, y = chunks of k_chunk consecutive solutions (the last may be short); the
+ * contacts of a solution are split over 1 << nw_log2 waves of the workgroup and folded through k_chunk KiB of LDS (2 k_chunk
+ * with arg) by max, ties to the smaller c.  Z and arg are the same bits under every shape.
+ * rato_hopper_eval_batch_plan: the shape the rule picks (host only, no HIP call): about three waves per SIMD where the work
+ * allows it, the contact split (never over more waves than contacts) before a k_chunk of 1.
+ * rato_hopper_eval_batch_shaped: the same call with the shape forced (nw_log2 in {0, 1, 2}, 1 <= k_chunk <= K; -1 = the
+ * rule's value for that argument).
+ * RATO_EINVAL without a launch: M, C or K < 1; ldc < C; ldz < M; a NULL px, fx, fz, a, theta, tau or Z; stats_out without
+ * alphas_host; an alpha outside (0, 1] (with stats_out); an illegal shape; more than 65535 chunks; a fold that needs more than
+ * 160 KiB of LDS. */
+int rato_hopper_eval_batch(int32_t M, int32_t C, int32_t K, const float* px, const float* fx, const float* fz, int64_t ldc,
+                           const float* a, const float* theta, const float* tau, float* Z, int64_t ldz, int32_t* arg,
+                           const double* alphas_host, float thr, void* workspace, size_t workspace_bytes, double* stats_out,
+                           void* stream);
+int rato_hopper_eval_batch_shaped(int32_t M, int32_t C, int32_t K, const float* px, const float* fx, const float* fz,
+                                  int64_t ldc, const float* a, const float* theta, const float* tau, float* Z, int64_t ldz,
+                                  int32_t* arg, const double* alphas_host, float thr, void* workspace, size_t workspace_bytes,
+                                  double* stats_out, void* stream, int32_t nw_log2, int32_t k_chunk);
+int rato_hopper_eval_batch_plan(int32_t M, int32_t C, int32_t K, int32_t* nw_log2, int32_t* k_chunk, int32_t* grid_x,
+                                int32_t* grid_y);
+
 /* ``jacrev(slip_risk_constraints)`` (hopper.py:569 on the rows of :300-367) in the reference's own layout: the CSC VALUE
  * array, written on the device from dh_dfz / dh_dpx [C][M] of the calls above.  Rows ('saa', saa != 0; :351-366):
  * 0 = (M alpha) t + sum y; 1 + i = -y_i; 1 + M + i C + c = h_ic - t - y_i - slack; one trailing zero row; ('baseline',

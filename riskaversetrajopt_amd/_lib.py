@@ -202,6 +202,12 @@ SIGNATURES = {
     "rato_hopper_slip": (C.c_int, [C.c_int32, C.c_int32] + [c_float_p] * 12 + [c_stream]),
     "rato_hopper_slip_host_inputs": (C.c_int, [C.c_int32, C.c_int32] + [c_float_p] * 12 + [c_stream]),
     "rato_hopper_slip_hessian": (C.c_int, [C.c_int32, C.c_int32] + [c_float_p] * 3 + [C.c_int32] + [c_float_p] * 9 + [c_stream]),
+    "rato_hopper_eval_batch": (C.c_int, [C.c_int32] * 3 + [c_float_p] * 3 + [C.c_int64] + [c_float_p] * 4 + [C.c_int64, c_float_p,
+                                         C.POINTER(C.c_double), C.c_float, C.c_void_p, C.c_size_t, c_float_p, c_stream]),
+    "rato_hopper_eval_batch_shaped": (C.c_int, [C.c_int32] * 3 + [c_float_p] * 3 + [C.c_int64] + [c_float_p] * 4 +
+                                      [C.c_int64, c_float_p, C.POINTER(C.c_double), C.c_float, C.c_void_p, C.c_size_t, c_float_p,
+                                       c_stream, C.c_int32, C.c_int32]),
+    "rato_hopper_eval_batch_plan": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 4),
     "rato_hopper_jacobian_nnz": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "rato_hopper_emit_jacobian_values": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double] + [c_float_p] * 4 +
                                          [C.c_int32, c_float_p, c_stream]),

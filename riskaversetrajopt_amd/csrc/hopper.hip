@@ -52,28 +52,13 @@ struct HopperContacts {
 // node in every step).
 // HC = 2: part_hess holds (D1, D2) per contact; HC = 3 (rato_hopper_slip_hessian): also D0 = sum lam dh/dpx, the factor
 // of the end-effector map's own curvature in the reference's Lagrangian Hessian (hopper.py:577-580).
-template <bool DERIV, bool BYVAL, int HC = 2>
-__global__ __launch_bounds__(RATO_BLOCK, DERIV ? 3 : 4) void hopper_slip_kernel(
-    int M_, int C, int nw_log2, const float* __restrict__ px, const float* __restrict__ fx,
-    const float* __restrict__ fz, const HopperContacts hc, const float* __restrict__ a,
-    const float* __restrict__ theta, const float* __restrict__ tau, const float* __restrict__ lam,
-    float* __restrict__ Z, float* __restrict__ h, float* __restrict__ dh_dfz, float* __restrict__ dh_dpx,
-    float* __restrict__ part_hess) {
-  static_assert(NF % 2 == 0, "features are processed in pairs");
-  constexpr int NP = NF / 2;
-  constexpr int WAVES = RATO_BLOCK / RATO_WAVE;
+// The features of sample m as the kernels keep them: 45 packed pairs, theta and tau pre-scaled to revolutions.
+__device__ __forceinline__ void hopper_load_features(const float* __restrict__ a, const float* __restrict__ theta,
+                                                     const float* __restrict__ tau, size_t M, unsigned m,
+                                                     hfloat2 (&fa)[NF / 2], hfloat2 (&rth)[NF / 2], hfloat2 (&rtau)[NF / 2]) {
   constexpr float INV_2PI = 0.15915494309189535f;
-  const size_t M = (size_t)M_;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (SGPR)
-  const int NW = 1 << nw_log2, SW = WAVES >> nw_log2;
-  const int sw = wave >> nw_log2, cw = wave & (NW - 1);
-  const unsigned m_raw = (blockIdx.x * SW + sw) * RATO_WAVE + lane;      // M < 2^31
-  const bool valid = m_raw < (unsigned)M_;
-  const unsigned m = valid ? m_raw : (unsigned)M_ - 1u;
-  hfloat2 fa[NP], rth[NP], rtau[NP];   // amplitude | theta / 2 pi | tau / 2 pi
-
 #pragma unroll
-  for (int k = 0; k < NP; ++k) {
+  for (int k = 0; k < NF / 2; ++k) {
     hfloat2 th, ta;
     fa[k].x = a[(size_t)(2 * k) * M + m];
     fa[k].y = a[(size_t)(2 * k + 1) * M + m];
@@ -84,6 +69,48 @@ __global__ __launch_bounds__(RATO_BLOCK, DERIV ? 3 : 4) void hopper_slip_kernel(
     rth[k] = th * INV_2PI;
     rtau[k] = ta * INV_2PI;
   }
+}
+
+// h = fx - mu_m(p) fz of one (sample, contact) (hopper.py:75-81, :322): the ONE statement of the value arithmetic.  The library
+// is built with -ffp-contract=fast, so the same expression written twice may be contracted differently; hopper_slip_kernel<false, *>
+// and hopper_eval_batch_kernel both call this function, which is what makes their values equal to the bit.
+__device__ __forceinline__ float hopper_slip_value(const hfloat2 (&fa)[NF / 2], const hfloat2 (&rth)[NF / 2],
+                                                   const hfloat2 (&rtau)[NF / 2], float p, float f_x, float f_z) {
+  hfloat2 p2;
+  p2.x = p;
+  p2.y = p;
+  hfloat2 s0 = {0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < NF / 2; ++k) {
+    const hfloat2 r = rth[k] * p2 + rtau[k];   // phase in revolutions (hardware trig unit)
+    hfloat2 cs;
+    cs.x = __builtin_amdgcn_cosf(r.x);
+    cs.y = __builtin_amdgcn_cosf(r.y);
+    s0 += fa[k] * cs;
+  }
+  const float mu = MU_NOM + (s0.x + s0.y);
+  return f_x - mu * f_z;  // hopper.py:322
+}
+
+template <bool DERIV, bool BYVAL, int HC = 2>
+__global__ __launch_bounds__(RATO_BLOCK, DERIV ? 3 : 4) void hopper_slip_kernel(
+    int M_, int C, int nw_log2, const float* __restrict__ px, const float* __restrict__ fx,
+    const float* __restrict__ fz, const HopperContacts hc, const float* __restrict__ a,
+    const float* __restrict__ theta, const float* __restrict__ tau, const float* __restrict__ lam,
+    float* __restrict__ Z, float* __restrict__ h, float* __restrict__ dh_dfz, float* __restrict__ dh_dpx,
+    float* __restrict__ part_hess) {
+  static_assert(NF % 2 == 0, "features are processed in pairs");
+  constexpr int NP = NF / 2;
+  constexpr int WAVES = RATO_BLOCK / RATO_WAVE;
+  const size_t M = (size_t)M_;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (SGPR)
+  const int NW = 1 << nw_log2, SW = WAVES >> nw_log2;
+  const int sw = wave >> nw_log2, cw = wave & (NW - 1);
+  const unsigned m_raw = (blockIdx.x * SW + sw) * RATO_WAVE + lane;      // M < 2^31
+  const bool valid = m_raw < (unsigned)M_;
+  const unsigned m = valid ? m_raw : (unsigned)M_ - 1u;
+  hfloat2 fa[NP], rth[NP], rtau[NP];   // amplitude | theta / 2 pi | tau / 2 pi
+  hopper_load_features(a, theta, tau, M, m, fa, rth, rtau);
   float zmax = -INFINITY;
   extern __shared__ float lds[];        // [WAVES][64] per-wave maxima | [SW][C][HC] per-wave Hessian sums
   float* zred = lds;
@@ -92,6 +119,12 @@ __global__ __launch_bounds__(RATO_BLOCK, DERIV ? 3 : 4) void hopper_slip_kernel(
   for (int c = cw; c < C; c += NW) {
     const float p = BYVAL ? hc.px[c] : px[c], f_x = BYVAL ? hc.fx[c] : fx[c], f_z = BYVAL ? hc.fz[c] : fz[c];
     float l = 0.0f;
+    if (!DERIV) {   // the value alone: the function the batched evaluation shares
+      const float hv = hopper_slip_value(fa, rth, rtau, p, f_x, f_z);
+      zmax = fmaxf(zmax, hv);
+      if (valid && h) h[(size_t)c * M + m] = hv;
+      continue;
+    }
     if (want_hess && valid) l = lam[(size_t)c * M + m];   // consumed after the trig block
     hfloat2 p2;
     p2.x = p;
@@ -103,26 +136,20 @@ __global__ __launch_bounds__(RATO_BLOCK, DERIV ? 3 : 4) void hopper_slip_kernel(
       hfloat2 cs;
       cs.x = __builtin_amdgcn_cosf(r.x);
       cs.y = __builtin_amdgcn_cosf(r.y);
-      if (!DERIV) {
-        s0 += fa[k] * cs;
-      } else {
-        // a theta and a theta^2 are NOT kept in registers (60 VGPRs: 194-202 -> 2 waves per SIMD).  Every product
-        // starts from a trig value, so nothing is loop invariant and nothing can be hoisted back into registers:
-        //   u = a cos,  s0 += u,  s2 += (u r) r;   v = a sin,  s1 += v r      (r = theta / 2 pi; the factors 2 pi and
-        //   (2 pi)^2 are applied once per contact to the sums): 7 packed ops per feature pair instead of 4.
-        hfloat2 sn;
-        sn.x = __builtin_amdgcn_sinf(r.x);
-        sn.y = __builtin_amdgcn_sinf(r.y);
-        const hfloat2 u = fa[k] * cs;
-        s0 += u;
-        s2 += (u * rth[k]) * rth[k];
-        s1 += (fa[k] * sn) * rth[k];
-      }
+      // a theta and a theta^2 are NOT kept in registers (60 VGPRs: 194-202 -> 2 waves per SIMD).  Every product
+      // starts from a trig value, so nothing is loop invariant and nothing can be hoisted back into registers:
+      //   u = a cos,  s0 += u,  s2 += (u r) r;   v = a sin,  s1 += v r      (r = theta / 2 pi; the factors 2 pi and
+      //   (2 pi)^2 are applied once per contact to the sums): 7 packed ops per feature pair instead of 4.
+      hfloat2 sn;
+      sn.x = __builtin_amdgcn_sinf(r.x);
+      sn.y = __builtin_amdgcn_sinf(r.y);
+      const hfloat2 u = fa[k] * cs;
+      s0 += u;
+      s2 += (u * rth[k]) * rth[k];
+      s1 += (fa[k] * sn) * rth[k];
     }
-    if (DERIV) {
-      s1 *= 6.28318530717958647692f;
-      s2 *= 39.4784176043574344753f;
-    }
+    s1 *= 6.28318530717958647692f;
+    s2 *= 39.4784176043574344753f;
     const float mu = MU_NOM + (s0.x + s0.y);
     const float hv = f_x - mu * f_z;  // hopper.py:322
     zmax = fmaxf(zmax, hv);
@@ -358,4 +385,198 @@ extern "C" int rato_hopper_emit_jacobian_values(int32_t M, int32_t C, int32_t sa
                        chain_dev, (int)data_blocks, out);
   RATO_LAUNCH_CHECK();
   return RATO_OK;
+}
+
+// ---- K solutions on one set of validation fields (the script's Monte-Carlo report, hopper.py:960-1007) -------------------------
+// Z[k][m] = max_c hopper_slip_value(sample m, contact c of solution k): the values of hopper_slip_kernel<false, *>, so row k is
+// to the bit the Z of rato_hopper_slip for solution k.  A lane is a sample: its 90 feature registers are loaded once and serve
+// k_chunk solutions x C contacts.  Grid: x = groups of SW sample-waves, y = chunks of k_chunk consecutive solutions (the last
+// one may be short).  The per-(k, c) inputs are wave-uniform and read through device pointers (K C reaches thousands: beyond
+// the kernel-argument path).  NW = 1 << nw_log2 contact-waves share a sample-wave's samples as in hopper_slip_kernel (wave =
+// sw NW + cw takes c = cw, cw + NW, ...); every wave leaves its maximum (and the smallest c that attains it) per solution in
+// LDS, and after ONE barrier the NW waves of a sample-wave fold the chunk's solutions, kk = cw, cw + NW, ... each.  max does not
+// depend on the order and ties go to the smaller c, so Z and arg are the same bits under every shape.  No atomics, nothing to
+// initialise, no workgroup waits for another; lanes past M and the columns M .. ldz-1 are not written.
+namespace {
+// Registers: 90 for the features and 40 around them -- 130 VGPRs, three waves per SIMD, no private memory (bounded to four
+// waves the compiler keeps 128 and spills three registers to scratch inside the solution loop).
+template <bool ARG>
+__global__ __launch_bounds__(RATO_BLOCK, 3) void hopper_eval_batch_kernel(
+    int M_, int C, int K, int nw_log2, int k_chunk, const float* __restrict__ px, const float* __restrict__ fx,
+    const float* __restrict__ fz, long ldc, const float* __restrict__ a, const float* __restrict__ theta,
+    const float* __restrict__ tau, float* __restrict__ Z, int* __restrict__ arg, long ldz) {
+  constexpr int NP = NF / 2;
+  constexpr int WAVES = RATO_BLOCK / RATO_WAVE;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform (SGPR)
+  const int NW = 1 << nw_log2, SW = WAVES >> nw_log2;
+  const int sw = wave >> nw_log2, cw = wave & (NW - 1);
+  const unsigned m_raw = (blockIdx.x * SW + sw) * RATO_WAVE + lane;      // M < 2^31
+  const bool valid = m_raw < (unsigned)M_;
+  const unsigned m = valid ? m_raw : (unsigned)M_ - 1u;
+  hfloat2 fa[NP], rth[NP], rtau[NP];
+  hopper_load_features(a, theta, tau, (size_t)M_, m, fa, rth, rtau);
+  const int k0 = blockIdx.y * k_chunk;
+  const int kn = min(k_chunk, K - k0);
+  extern __shared__ float lds[];        // NW > 1: [k_chunk][WAVES][64] maxima | ARG: the same of their contact indices
+  float* zred = lds;
+  int* ared = reinterpret_cast<int*>(lds + (size_t)k_chunk * RATO_BLOCK);
+  for (int kk = 0; kk < kn; ++kk) {
+    const float* pk = px + (size_t)(k0 + kk) * ldc;
+    const float* fxk = fx + (size_t)(k0 + kk) * ldc;
+    const float* fzk = fz + (size_t)(k0 + kk) * ldc;
+    float zmax = -INFINITY;
+    int amax = -1;
+    for (int c = cw; c < C; c += NW) {
+      const float hv = hopper_slip_value(fa, rth, rtau, pk[c], fxk[c], fzk[c]);
+      if (ARG && hv > zmax) amax = c;   // strict: the first (smallest) c of this wave that attains its maximum
+      zmax = fmaxf(zmax, hv);
+    }
+    if (nw_log2 == 0) {
+      if (valid) {
+        Z[(size_t)(k0 + kk) * ldz + m] = zmax;
+        if (ARG) arg[(size_t)(k0 + kk) * ldz + m] = amax;
+      }
+    } else {
+      zred[kk * RATO_BLOCK + threadIdx.x] = zmax;
+      if (ARG) ared[kk * RATO_BLOCK + threadIdx.x] = amax;
+    }
+  }
+  if (nw_log2 == 0) return;             // uniform over the launch
+  __syncthreads();
+  for (int kk = cw; kk < kn; kk += NW) {
+    const int base = kk * RATO_BLOCK + (sw << nw_log2) * RATO_WAVE + lane;
+    float zmax = zred[base];
+    int amax = ARG ? ared[base] : -1;
+    for (int j = 1; j < NW; ++j) {
+      const float zj = zred[base + j * RATO_WAVE];
+      if (ARG) {
+        const int aj = ared[base + j * RATO_WAVE];
+        if (zj > zmax || (zj == zmax && aj < amax)) amax = aj;   // (both -inf: both -1)
+      }
+      zmax = fmaxf(zmax, zj);
+    }
+    if (valid) {
+      Z[(size_t)(k0 + kk) * ldz + m] = zmax;
+      if (ARG) arg[(size_t)(k0 + kk) * ldz + m] = amax;
+    }
+  }
+}
+
+// The shape rule (host only).  The kernel is transcendental-issue bound, so what matters is that the chip's 1024 SIMDs hold
+// about three waves each: 3072 waves.  A wave costs (k_chunk solutions) x (C / NW contacts) and there are (sample-waves x NW x
+// chunks) of them.  Without a contact split the largest k_chunk that still leaves 3072 waves is taken when it is at least 2
+// (the feature load is then shared by two solutions or more); otherwise the contacts are split 2 and then 4 ways (never over
+// more waves than there are contacts) before k_chunk drops to 1.  With a split the fold keeps k_chunk x 1 KiB (2 with arg) of
+// LDS per workgroup, so k_chunk stops at 16 there.  The chunks are then evened out: grid_y = ceil(K / k_chunk) stays and
+// k_chunk becomes ceil(K / grid_y) (K = 7, k_chunk 4 -> two chunks of 4 and 3 either way; K = 9, k_chunk 6 -> 5 and 4).
+constexpr long HOPPER_EVAL_TARGET_WAVES = 3 * 1024;
+constexpr int HOPPER_EVAL_SPLIT_KCHUNK_MAX = 16;
+
+int hopper_eval_batch_rule(int32_t M, int32_t C, int32_t K, int* nw_log2, int* k_chunk) {
+  if (M < 1 || C < 1 || K < 1) return RATO_EINVAL;
+  const long sample_waves = ((long)M + RATO_WAVE - 1) / RATO_WAVE;
+  int nw_max = 0;
+  while (nw_max < 2 && (2 << nw_max) <= C) ++nw_max;
+  int nw = 0;
+  long kc = 1;
+  for (;; ++nw) {
+    kc = (sample_waves * K << nw) / HOPPER_EVAL_TARGET_WAVES;
+    if (kc >= 2 || nw == nw_max) break;
+  }
+  if (kc < 1) kc = 1;
+  if (kc > K) kc = K;
+  if (nw > 0 && kc > HOPPER_EVAL_SPLIT_KCHUNK_MAX) kc = HOPPER_EVAL_SPLIT_KCHUNK_MAX;
+  const long gy = (K + kc - 1) / kc;
+  kc = (K + gy - 1) / gy;
+  *nw_log2 = nw;
+  *k_chunk = (int)kc;
+  return RATO_OK;
+}
+
+size_t hopper_eval_batch_lds(int nw_log2, int k_chunk, bool want_arg) {
+  return nw_log2 == 0 ? 0 : (size_t)k_chunk * RATO_BLOCK * sizeof(float) * (want_arg ? 2 : 1);
+}
+
+int hopper_eval_batch_impl(int32_t M, int32_t C, int32_t K, const float* px, const float* fx, const float* fz, int64_t ldc,
+                           const float* a, const float* theta, const float* tau, float* Z, int64_t ldz, int32_t* arg,
+                           const double* alphas_host, float thr, void* workspace, size_t workspace_bytes, double* stats_out,
+                           void* stream, int32_t nw_log2, int32_t k_chunk) {
+  RATO_CLEAR_ERROR();
+  if (M < 1 || C < 1 || K < 1 || ldc < C || ldz < M || !px || !fx || !fz || !a || !theta || !tau || !Z) return RATO_EINVAL;
+  if (stats_out && !alphas_host) return RATO_EINVAL;
+  if (stats_out)
+    for (int32_t k = 0; k < K; ++k)
+      if (!(alphas_host[k] > 0.0) || !(alphas_host[k] <= 1.0)) return RATO_EINVAL;
+  int nw_rule = 0, kc_rule = 1;
+  if (hopper_eval_batch_rule(M, C, K, &nw_rule, &kc_rule) != RATO_OK) return RATO_EINVAL;
+  if (nw_log2 == -1) nw_log2 = nw_rule;
+  if (k_chunk == -1) k_chunk = kc_rule;
+  if (nw_log2 < 0 || nw_log2 > 2 || k_chunk < 1 || k_chunk > K) return RATO_EINVAL;
+  const long grid_y = ((long)K + k_chunk - 1) / k_chunk;
+  if (grid_y > 65535) return RATO_EINVAL;
+  const size_t lds = hopper_eval_batch_lds(nw_log2, k_chunk, arg != nullptr);
+  if (lds > RATO_HOPPER_LDS_MAX) return RATO_EINVAL;
+  hipStream_t st = rato::as_stream(stream);
+  const int samples_per_block = RATO_BLOCK >> nw_log2;
+  dim3 grid((unsigned)(((long)M + samples_per_block - 1) / samples_per_block), (unsigned)grid_y), block(RATO_BLOCK);
+  static rato::DynamicLdsLimit lds_limit;
+  {
+    const hipError_t e = lds_limit.ensure(lds, [](size_t) {   // beyond the 64 KB default: both kernels up to a CU's 160 KB, once
+      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(hopper_eval_batch_kernel<true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)RATO_HOPPER_LDS_MAX);
+      if (err == hipSuccess)
+        err = hipFuncSetAttribute(reinterpret_cast<const void*>(hopper_eval_batch_kernel<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)RATO_HOPPER_LDS_MAX);
+      return err;
+    });
+    if (e != hipSuccess) return RATO_EHIP - (int)e;
+  }
+  if (arg)
+    hipLaunchKernelGGL(hopper_eval_batch_kernel<true>, grid, block, lds, st, M, C, K, nw_log2, k_chunk, px, fx, fz, (long)ldc, a,
+                       theta, tau, Z, arg, (long)ldz);
+  else
+    hipLaunchKernelGGL(hopper_eval_batch_kernel<false>, grid, block, lds, st, M, C, K, nw_log2, k_chunk, px, fx, fz, (long)ldc, a,
+                       theta, tau, Z, arg, (long)ldz);
+  RATO_LAUNCH_CHECK();
+  if (!stats_out) return RATO_OK;
+  // one selection call per run of consecutive equal alphas, on the rows of that run
+  for (int32_t k = 0; k < K;) {
+    int32_t e = k + 1;
+    while (e < K && alphas_host[e] == alphas_host[k]) ++e;
+    const int rc = rato_risk_stats_batch(Z + (size_t)k * ldz, M, ldz, e - k, alphas_host[k], thr, workspace, workspace_bytes,
+                                         stats_out + (size_t)k * RATO_N_STATS, stream);
+    if (rc != RATO_OK) return rc;
+    k = e;
+  }
+  return RATO_OK;
+}
+}  // namespace
+
+extern "C" int rato_hopper_eval_batch_plan(int32_t M, int32_t C, int32_t K, int32_t* nw_log2, int32_t* k_chunk,
+                                           int32_t* grid_x, int32_t* grid_y) {
+  int nw = 0, kc = 1;
+  if (!nw_log2 || !k_chunk || !grid_x || !grid_y || hopper_eval_batch_rule(M, C, K, &nw, &kc) != RATO_OK) return RATO_EINVAL;
+  const int samples_per_block = RATO_BLOCK >> nw;
+  *nw_log2 = nw;
+  *k_chunk = kc;
+  *grid_x = (int32_t)(((long)M + samples_per_block - 1) / samples_per_block);
+  *grid_y = (K + kc - 1) / kc;
+  return RATO_OK;
+}
+
+extern "C" int rato_hopper_eval_batch_shaped(int32_t M, int32_t C, int32_t K, const float* px, const float* fx, const float* fz,
+                                             int64_t ldc, const float* a, const float* theta, const float* tau, float* Z,
+                                             int64_t ldz, int32_t* arg, const double* alphas_host, float thr, void* workspace,
+                                             size_t workspace_bytes, double* stats_out, void* stream, int32_t nw_log2,
+                                             int32_t k_chunk) {
+  return hopper_eval_batch_impl(M, C, K, px, fx, fz, ldc, a, theta, tau, Z, ldz, arg, alphas_host, thr, workspace, workspace_bytes,
+                                stats_out, stream, nw_log2, k_chunk);
+}
+
+extern "C" int rato_hopper_eval_batch(int32_t M, int32_t C, int32_t K, const float* px, const float* fx, const float* fz,
+                                      int64_t ldc, const float* a, const float* theta, const float* tau, float* Z, int64_t ldz,
+                                      int32_t* arg, const double* alphas_host, float thr, void* workspace, size_t workspace_bytes,
+                                      double* stats_out, void* stream) {
+  return hopper_eval_batch_impl(M, C, K, px, fx, fz, ldc, a, theta, tau, Z, ldz, arg, alphas_host, thr, workspace, workspace_bytes,
+                                stats_out, stream, -1, -1);
 }

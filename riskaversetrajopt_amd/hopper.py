@@ -12,6 +12,8 @@ hands to IPOPT (:486-640) on the MI355X.
     per call (rato_hopper_slip_f64 / rato_hopper_slip_hess_blocks_f64, csrc/hopper_slip64.hip); 'f32' stays the default and
     the Monte-Carlo / large-M path.  ``fields=`` of ``slip_device_f64`` / ``nlp_device`` gives every problem of a call friction
     fields of its own (rato_hopper_slip_f64_fields; ``stack_fields_f64``): a grid of alphas x resampled terrains is one batch.
+  * ``Model.eval_batch_device``: the script's Monte-Carlo block (:960-1007) for K solutions on the model's fields in one call
+    (rato_hopper_eval_batch, csrc/hopper.hip): Z, the contact that slips and the risk record of every solution.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
   * ``Model.initial_guess()`` and ``Model.solve()``: the script's start and its solve (:136-164, :642-669) with the batched
     interior-point method of ``ipm`` on the backends of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip, csrc/chol.hip) in
@@ -694,6 +696,86 @@ class Model:
         return stats.risk_stats(Z, self.alpha if alpha is None else alpha)
 
     avar = staticmethod(stats.monte_carlo_avar)
+
+    # ---- K solutions on the model's fields in one call (the script's report, hopper.py:960-1007) ---------------------------
+    def contact_inputs_batch(self, Zs):
+        """``contact_inputs`` of K solutions -> (px (K, C), forces (K, C, 2)); row k is bitwise ``contact_inputs(Zs[k])`` (the
+        rows may have different lengths: only the states and controls of a solution are read)."""
+        rows = [self.contact_inputs(Z) for Z in Zs]
+        if not rows:
+            raise ValueError("contact_inputs_batch needs at least one solution")
+        return np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+
+    def eval_batch_plan(self, Cn, K):
+        """(nw_log2, k_chunk, grid_x, grid_y): the launch rato_hopper_eval_batch picks for K solutions of ``Cn`` contacts on this
+        model's fields (rato_hopper_eval_batch_plan; host only)"""
+        v = [C.c_int32(0) for _ in range(4)]
+        _lib.check(self._lib.rato_hopper_eval_batch_plan(self._a.shape[1], int(Cn), int(K), *(C.byref(x) for x in v)),
+                   "rato_hopper_eval_batch_plan")
+        return tuple(x.value for x in v)
+
+    def eval_batch_inputs_device(self, inputs, Cn, alphas=None, want_stats=True, want_arg=False, out=None, workspace=None,
+                                 shape=None):
+        """``eval_batch_device`` on inputs that already lie on the device: ``inputs`` a float32 tensor (3, K, ldc >= Cn) holding
+        px, fx, fz of solution k in row k (read in place at run time: a captured call sees what they hold at replay)."""
+        dev = self.device
+        if not isinstance(inputs, torch.Tensor) or inputs.dtype != torch.float32 or inputs.dim() != 3 or inputs.shape[0] != 3 or \
+                not inputs.is_contiguous() or inputs.device.type != 'cuda' or inputs.shape[2] < Cn or inputs.shape[1] < 1:
+            raise ValueError("inputs must be a contiguous float32 device tensor (3, K, ldc >= C)")
+        K, ldc, M = inputs.shape[1], inputs.shape[2], self._a.shape[1]
+        if alphas is None:
+            alphas = self.alpha
+        al = np.full(K, float(alphas)) if np.ndim(alphas) == 0 else \
+            np.array([1.0 if x is None else float(x) for x in alphas], dtype=np.float64)   # None: the baseline's row, at alpha = 1
+        if al.shape != (K,):
+            raise ValueError(f"alphas must be a scalar or a sequence of K = {K} entries")
+        o = out if out is not None else {}
+        Z = o.get("_Zb")
+        if Z is None or tuple(Z.shape) != (K, M):
+            Z = torch.empty((K, M), dtype=torch.float32, device=dev)
+        rec = ws = arg = None
+        if want_stats:
+            rec = o.get("_recb")
+            if rec is None or tuple(rec.shape) != (K, stats.N_STATS):
+                rec = torch.empty((K, stats.N_STATS), dtype=torch.float64, device=dev)
+            ws = workspace if workspace is not None else o.get("_wsb")
+            if ws is None:
+                ws = stats.new_workspace(M, dev)
+        if want_arg:
+            arg = o.get("_argb")
+            if arg is None or tuple(arg.shape) != (K, M):
+                arg = torch.empty((K, M), dtype=torch.int32, device=dev)
+        o["_Zb"], o["_recb"], o["_wsb"], o["_argb"] = Z, rec, ws, arg
+        args = (M, int(Cn), K, _lib.ptr(inputs[0]), _lib.ptr(inputs[1]), _lib.ptr(inputs[2]), ldc, _lib.ptr(self._a),
+                _lib.ptr(self._th), _lib.ptr(self._tau), _lib.ptr(Z), M, _lib.ptr(arg),
+                al.ctypes.data_as(C.POINTER(C.c_double)) if want_stats else None, float(stats.SATISFIED_THRESHOLD), _lib.ptr(ws),
+                ws.numel() if ws is not None else 0, _lib.ptr(rec))
+        with torch.cuda.device(dev):
+            if shape is None:
+                _lib.check(self._lib.rato_hopper_eval_batch(*args, _lib.current_stream()), "rato_hopper_eval_batch")
+            else:
+                _lib.check(self._lib.rato_hopper_eval_batch_shaped(*args, _lib.current_stream(), int(shape[0]), int(shape[1])),
+                           "rato_hopper_eval_batch_shaped")
+        return (Z, rec, arg) if want_arg else (Z, rec)
+
+    def eval_batch_device(self, px, forces, alphas=None, want_stats=True, want_arg=False, out=None, workspace=None, shape=None):
+        """K solutions on the model's fields in ONE call (rato_hopper_eval_batch): what the script's report does one solution at
+        a time (hopper.py:983-1007).  px (K, C), forces (K, C, 2) (``contact_inputs_batch``), converted to fp32 as ``slip_device``
+        converts them; one upload of the (3, K, C) inputs, no read-back.
+        -> (Z [K][M] device fp32, records [K][N_STATS] device fp64 or None[, arg [K][M] int32 with want_arg]).  Row k of Z and of
+        the records is, to the bit, what ``slip_device`` / ``stats.risk_stats_device`` give for solution k; arg[k][m] is the first
+        contact (position in the gathered list) whose value is Z[k][m], -1 when that is -inf.
+        ``alphas``: a scalar or K entries (default: the model's alpha); an entry of None is meant for the baseline: that row is
+        selected at alpha = 1 and the caller drops its VaR and AVaR.  ``shape`` = (nw_log2, k_chunk) forces the launch shape
+        (rato_hopper_eval_batch_shaped; -1: the rule's value); ``out``: a dict that keeps the buffers between calls."""
+        px = np.ascontiguousarray(px, dtype=np.float32)
+        forces = np.asarray(forces, dtype=np.float32)
+        if px.ndim != 2 or forces.shape != px.shape + (2,) or px.shape[0] < 1 or px.shape[1] < 1:
+            raise ValueError(f"px must be (K, C) and forces (K, C, 2), got {px.shape} and {forces.shape}")
+        host = np.stack([px, forces[..., 0], forces[..., 1]])
+        inputs = torch.from_numpy(host).to(self.device)
+        return self.eval_batch_inputs_device(inputs, px.shape[1], alphas=alphas, want_stats=want_stats, want_arg=want_arg,
+                                             out=out, workspace=workspace, shape=shape)
 
     # ---- the whole NLP (hopper.py:441-453, :491-562, :569-640) -------------------------------------------------------------
     @classmethod

@@ -787,9 +787,101 @@ def hopper_saa_start(model, xs, us):
     return Z0
 
 
+HOPPER_MC_REPORT = "hopper_monte_carlo_report.npy"
+HOPPER_MC_REPORT_ARRAYS = ("alphas", "jump", "frac_satisfied", "var", "avar")
+
+
+def _hopper_mc_alphas(alphas, K):
+    """``alphas`` of ``hopper_monte_carlo_report`` -> a list of K floats / None (None, or anything <= 0: the baseline's row)"""
+    al = [alphas] * K if (alphas is None or np.ndim(alphas) == 0) else list(alphas)
+    if len(al) != K:
+        raise ValueError(f"alphas must be a scalar or a sequence of {K} entries, got {len(al)}")
+    return [None if (a is None or not float(a) > 0.0) else float(a) for a in al]
+
+
+def hopper_monte_carlo_report(mc_model, Zs, alphas, verbose=False, batch=True):
+    """The hopper script's Monte-Carlo block (hopper.py:960-1007) for K solutions ``Zs`` (their NLP vectors; only the states and
+    controls are read) on the validation fields of ``mc_model`` (a ``hopper.Model`` of M_mc samples): per solution the jumped
+    distance x_S[0], the fraction of fields without slip and VaR / AVaR at the solution's alpha.  ``alphas``: a scalar or K
+    entries; None (or 0, the script's ``alphas_and_base``) marks the baseline, for which the script prints no avar (:1003-1007):
+    its ``var`` and ``avar`` are NaN.
+    batch=True: ONE ``Model.eval_batch_device`` call (rato_hopper_eval_batch: all solutions in one launch, one selection launch
+    per run of equal alphas) and one read-back of the K records beside the contact counts; a record whose VaR is NaN (a
+    selection that gave up) falls back to ``Model.monte_carlo_statistics``, as ``monte_carlo_report`` does.  batch=False: the
+    per-solution loop (``slip_device`` + ``stats.risk_stats`` per solution) -- the checker: every array is the same to the bit.
+    -> dict(alphas (K,) with 0.0 for the baseline, jump, frac_satisfied, var, avar (each (K,)), arg_counts (K, C) int64: over the
+    samples that slip (Z > 1e-6), how often contact c -- the first that attains the maximum -- is the one; wall_s)."""
+    from . import stats
+    t0 = time.perf_counter()
+    Zs = [np.asarray(Z, dtype=np.float64) for Z in Zs]
+    K = len(Zs)
+    al = _hopper_mc_alphas(alphas, K)
+    px, forces = mc_model.contact_inputs_batch(Zs)
+    Cn = px.shape[1]
+    jump = np.array([Z[8 * mc_model.S] for Z in Zs])             # xs[-1, 0] (hopper.py:987)
+    frac, var, avar = (np.full(K, np.nan) for _ in range(3))
+    counts = np.zeros((K, Cn), dtype=np.int64)
+    thr = np.float32(stats.SATISFIED_THRESHOLD)
+
+    def _take(k, st):
+        frac[k] = st["frac_satisfied"]
+        if al[k] is not None:
+            var[k], avar[k] = st["var"], st["cvar"]
+
+    if batch:
+        import torch
+        Zd, rec, arg = mc_model.eval_batch_device(px, forces, alphas=al, want_arg=True)
+        # the contact counts over the unsafe samples, on the device, so that ONE tensor comes back: [records | counts]
+        unsafe = (Zd > float(thr)) & (arg >= 0)
+        cnt = torch.zeros((K, Cn), dtype=torch.float64, device=Zd.device)
+        cnt.scatter_add_(1, arg.clamp(min=0).long(), unsafe.double())
+        back = torch.cat([rec, cnt], dim=1).cpu().numpy()
+        counts[:] = np.rint(back[:, stats.N_STATS:]).astype(np.int64)
+        for k in range(K):
+            st = dict(zip(stats._STAT_NAMES, back[k, :stats.N_STATS].tolist()))
+            if np.isnan(st["var"]):
+                st = mc_model.monte_carlo_statistics(px[k], forces[k], alpha=1.0 if al[k] is None else al[k])
+            _take(k, st)
+    else:
+        for k in range(K):
+            r = mc_model.slip_device(px[k], forces[k])
+            _take(k, stats.risk_stats(r["Z"], 1.0 if al[k] is None else al[k]))
+            h = r["h"].cpu().numpy()                             # (C, M)
+            h = np.where(np.isnan(h), -np.inf, h)
+            z = h.max(axis=0)
+            first = np.argmax(h, axis=0)
+            counts[k] = np.bincount(first[z > thr], minlength=Cn)
+    out = {"alphas": np.array([0.0 if a is None else a for a in al]), "jump": jump, "frac_satisfied": frac, "var": var,
+           "avar": avar, "arg_counts": counts}
+    if verbose:                                                  # hopper.py:984-1007
+        for k in range(K):
+            print("---------------------------")
+            print("Monte-Carlo: alpha =", out["alphas"][k])
+            print("jumped distance =", jump[k])
+            print("B_satisfied_vec =", frac[k])
+            if al[k] is not None:
+                print("avar =", avar[k])
+        print("---------------------------------------")
+    out["wall_s"] = time.perf_counter() - t0
+    return out
+
+
+def save_hopper_monte_carlo_report(results_dir, report):
+    """alphas, jump, frac_satisfied, var, avar of a ``hopper_monte_carlo_report`` in one file (``load_results(path, 5)``) -> path"""
+    os.makedirs(results_dir, exist_ok=True)
+    path = os.path.join(results_dir, HOPPER_MC_REPORT)
+    save_results(path, *(report[k] for k in HOPPER_MC_REPORT_ARRAYS))
+    return path
+
+
+def _check_validate(validate):
+    if validate not in ('solo', 'batch'):
+        raise ValueError(f"validate must be 'solo' or 'batch', got {validate!r}")
+
+
 def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=1, results_dir=None, tol=1e-3, max_iter=3000,
                       backend='device', device='cuda:0', clocks=None, newton='dense', fields=None, driver='host',
-                      chol='workgroup'):
+                      chol='workgroup', M_mc=None):
     """The hopper script's two runs (hopper.py:455-680) as one call: the friction fields under ``RandomState(seed)`` (:70-74),
     the baseline from ``initial_guess()``, then every alpha of the SAA problem in ONE lockstep batch from the baseline's
     solution (:465-479).  With ``results_dir`` the files hopper_base_results.npy and hopper_saa_alpha=<a>_results.npy are
@@ -797,11 +889,21 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
     of the draw; ``newton``: 'dense' or 'arrow' (``hopper_ipm.solve_batch``: 'arrow' is the one that scales with M); ``driver``:
     'host', 'device' or 'device_grid' (``ipm.solve_group_device``: the iterate stays on the device; backend='device', either newton).
     -> dict(alphas, base (the run_hopper dict), results [alpha] (dict(Z, xs, us, status, info)), status (A,) of str, wall_s)
-    ``chol``: 'workgroup' or 'grid', the device Cholesky of both runs (``hopper_ipm.solve_batch``; the results do not depend on it)."""
+    ``chol``: 'workgroup' or 'grid', the device Cholesky of both runs (``hopper_ipm.solve_batch``; the results do not depend on it).
+    ``M_mc``: None (default) -- nothing more; an integer -- the script's Monte-Carlo block (:960-1007) on ``M_mc`` validation fields
+    drawn after the model's fields under the same ``RandomState(seed)`` (the draw order of ``draw_hopper_saa_fields(1, M, M_mc,
+    seed)``): ``hopper_monte_carlo_report`` of the alphas and then the baseline, the script's order, returned under
+    "monte_carlo" (the validation fields under "mc_fields") and, with ``results_dir``, written to hopper_monte_carlo_report.npy
+    (alphas, jump, frac_satisfied, var, avar: ``load_results(path, 5)``)."""
     from . import ipm as _ipm
     _ipm.check_chol(chol)
     from . import hopper, hopper_ipm
     alphas = [float(a) for a in alphas]
+    mc_fields = None
+    if M_mc is not None:
+        draws, mc_fields = draw_hopper_saa_fields(1, M, int(M_mc), seed)
+        if fields is None:
+            fields = draws[0]
     if fields is None:
         fields = hopper.sample_friction_fields(M, np.random.RandomState(seed))
     t0 = time.perf_counter()
@@ -825,8 +927,15 @@ def hopper_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), M=30, S=30, seed=
         save_hopper_result(results_dir, base_model, Zb)
         for m, r in zip(models, results):
             save_hopper_result(results_dir, m, r["Z"])
-    return {"alphas": alphas, "base": base, "results": results, "status": np.array([r["status"] for r in results]),
-            "wall_s": time.perf_counter() - t0}
+    out = {"alphas": alphas, "base": base, "results": results, "status": np.array([r["status"] for r in results])}
+    if mc_fields is not None:
+        mc_model = hopper.Model(int(M_mc), 'saa', S=S, fields=mc_fields, device=device)
+        out["monte_carlo"] = hopper_monte_carlo_report(mc_model, [r["Z"] for r in results] + [Zb], alphas + [None])
+        out["mc_fields"] = mc_fields
+        if results_dir is not None:
+            save_hopper_monte_carlo_report(results_dir, out["monte_carlo"])
+    out["wall_s"] = time.perf_counter() - t0
+    return out
 
 
 def draw_hopper_saa_fields(num_repeats=30, M=30, M_mc=10000, seed=1):
@@ -851,14 +960,17 @@ HOPPER_SAA_REPORT_ARRAYS = ("alphas", "status", "jump", "safe_fraction", "var", 
 
 def hopper_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), num_repeats=30, M=30, S=30, seed=1, M_mc=10000, results_dir=None,
                           tol=1e-3, max_iter=3000, newton='dense', driver='host', device='cuda:0', clocks=None,
-                          chol='workgroup'):
+                          chol='workgroup', validate='solo'):
     """The hopper's SAA study over resampled terrains, shaped like ``drone_saa_experiment`` / ``driving_saa_experiment``: R draws
     of the friction fields (``draw_hopper_saa_fields``), the baseline solved once from ``initial_guess()`` (its fields are zeroed,
     so it does not depend on the draw), then all A x R SAA problems -- alpha-major, every repeat on its own fields -- in ONE
     ``hopper_ipm.solve_batch`` call (one lockstep group) from ``hopper_saa_start`` of the baseline's solution, and the script's
     Monte-Carlo validation (hopper.py:960-1007) of every solution on the ``M_mc`` validation fields: px and the contact forces
     on the contact steps (``Model.contact_inputs``), ``Model.monte_carlo_statistics`` at the problem's alpha, one solution after
-    the other.  A problem that does not converge raises nothing: its status says so and it is validated like the others.
+    the other (validate='solo', the default) -- or all A x R solutions in ONE ``Model.eval_batch_device`` call (validate='batch':
+    rato_hopper_eval_batch; the stacking is alpha-major, so the selections are A launches); every returned array is the same to
+    the bit under both, any other value is a ValueError before any work.
+    A problem that does not converge raises nothing: its status says so and it is validated like the others.
     -> dict(alphas, base (the run_hopper dict without total_s), results [alpha][repeat] = (Z, xs, us, status, info), status (A, R)
     of str, jump (A, R) = x_S[0], safe_fraction / var / avar (A, R), wall_s).
     With ``results_dir``: hopper_saa_alpha=<a>_repeat=<r>_results.npy per problem (xs then us, ``save_results``) and one
@@ -867,6 +979,7 @@ def hopper_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), num_repeats=3
     from . import hopper, hopper_ipm
     from . import ipm as _ipm
     _ipm.check_chol(chol)
+    _check_validate(validate)
     alphas = [float(a) for a in alphas]
     A, R = len(alphas), int(num_repeats)
     draws, mc_fields = draw_hopper_saa_fields(R, M, M_mc, seed)
@@ -889,9 +1002,22 @@ def hopper_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3, 0.5, 0.75), num_repeats=3
         x, u = m.convert_z_to_xs_us_mats(Z)
         results[i][r] = (Z, x, u, info["status"], info)
         status[i, r], jump[i, r] = info["status"], x[-1, 0]
-        px, forces = m.contact_inputs(Z)
-        st = mc_model.monte_carlo_statistics(px, forces, alpha=m.alpha)
-        safe[i, r], var[i, r], avar[i, r] = st["frac_satisfied"], st["var"], st["cvar"]
+        if validate == 'solo':
+            px, forces = m.contact_inputs(Z)
+            st = mc_model.monte_carlo_statistics(px, forces, alpha=m.alpha)
+            safe[i, r], var[i, r], avar[i, r] = st["frac_satisfied"], st["var"], st["cvar"]
+    if validate == 'batch' and models:
+        from . import stats
+        inputs = [m.contact_inputs(Z) for m, (Z, _) in zip(models, sols)]
+        _, rec = mc_model.eval_batch_device(np.stack([p for p, _ in inputs]), np.stack([f for _, f in inputs]),
+                                            alphas=[m.alpha for m in models])
+        rec = rec.cpu().numpy()
+        for k, m in enumerate(models):
+            st = dict(zip(stats._STAT_NAMES, rec[k].tolist()))
+            if np.isnan(st["var"]):                    # (a selection that gave up: the recovering per-solution path)
+                st = mc_model.monte_carlo_statistics(*inputs[k], alpha=m.alpha)
+            i, r = divmod(k, R)
+            safe[i, r], var[i, r], avar[i, r] = st["frac_satisfied"], st["var"], st["cvar"]
     if clocks is not None:
         clocks["base"], clocks["saa"] = c0, c1
     out = {"alphas": alphas, "base": base, "results": results, "status": status, "jump": jump, "safe_fraction": safe, "var": var,
