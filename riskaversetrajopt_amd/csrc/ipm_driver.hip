@@ -229,16 +229,7 @@ extern "C" int rato_ipm_residuals_f64(const rato_ipm_state* st, const double* g,
 
 extern "C" int rato_ipm_newton_f64(const rato_ipm_state* st, int32_t phase, const double* a, int64_t lda, const double* b,
                                    int64_t ldb, const int32_t* info, int32_t flag, void* stream) {
-  if (!state_ok(st)) return RATO_EINVAL;
-  const bool rows = phase == RATO_IPM_PHASE_Q || phase == RATO_IPM_PHASE_UPDATE || phase == RATO_IPM_PHASE_FINISH;
-  if (phase == RATO_IPM_PHASE_LADDER) {
-    if (!info || flag < 1) return RATO_EINVAL;
-  } else if (phase == RATO_IPM_PHASE_RHS || phase == RATO_IPM_PHASE_R || rows) {
-    if (!a || lda < (rows ? st->m : st->n)) return RATO_EINVAL;
-    if (phase == RATO_IPM_PHASE_R && (!b || ldb < st->n)) return RATO_EINVAL;
-  } else {
-    return RATO_EINVAL;
-  }
+  if (!state_ok(st) || !newton_args_ok(st, phase, a, lda, b, ldb, info, flag)) return RATO_EINVAL;
   RATO_CLEAR_ERROR();
   hipLaunchKernelGGL(ipm_newton_kernel, dim3((unsigned)st->K), dim3(ID_BLOCK), 0, (hipStream_t)stream, *st, (int)phase, a, lda, b,
                      ldb, info, (int)flag);

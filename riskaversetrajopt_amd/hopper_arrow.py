@@ -4,10 +4,11 @@ they are eliminated exactly and the Cholesky factors the core's Schur complement
 test, since e > 0.  ``ArrowDeviceBackend`` does the work over the samples with csrc/hopper_arrow.hip on the partials
 rato_hopper_slip_f64 leaves and the deterministic rows with ``hopper_ipm``'s ``normal_matrix`` / ``csc_matvec`` / ``csc_tmatvec`` on
 the core's pattern; ``ArrowNumpyBackend`` is its host twin.  Both keep their own factor and solve (the elimination).
-Under ``driver='device'`` ``ArrowDeviceBackend`` serves device tensors: its ``*_t`` methods do the same step
-without a read-back, the host-side fix-ups of the list methods being kernels of csrc/hopper_arrow.hip.
+``ArrowDeviceBackend`` has one step, written on device tensors with every line between two launches a kernel of
+csrc/hopper_arrow.hip: the ``*_t`` methods (``driver='device'``) run it on the group's arrays where they lie, and
+the list methods (``driver='host'``) upload the listed problems' vectors, run it on those problems' rows and download the result.
 """
-import time
+import contextlib
 
 import numpy as np
 
@@ -233,9 +234,9 @@ class ArrowNumpyBackend(_ipm.Backend):
 class ArrowDeviceBackend(_ipm.DeviceBase):
     """The arrowhead step on the MI355X for the problems of one group (csrc/hopper_arrow.hip on the partials rato_hopper_slip_f64
     leaves in HBM; the core through ``hopper_ipm.normal_matrix`` on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).
-    eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels to the
-    host per call of a list method is the vectors the driver works on and O(q) sums; the ``*_t`` methods (the driver on the
-    device) move nothing.  The group's models may hold friction fields of their own (``hopper_ipm.GroupFields``)."""
+    eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels per call
+    of a list method is the vectors the driver works on, up and down once; the ``*_t`` methods (the driver on the device) move
+    nothing.  The group's models may hold friction fields of their own (``hopper_ipm.GroupFields``)."""
     name, newton = "device", "arrow"
 
     def __init__(self, models, chol='workgroup'):
@@ -262,8 +263,8 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         self.vals0 = self.dx = self.dfz = self.hessd = self.hess_host = None
         self.fields = GroupFields(models)
         n_all = len(models)
-        self.e, self.d = self._empty(n_all, st["M"]), self._empty(n_all, st["ncon"])
-        self.kk, self.beta = np.zeros(n_all), np.zeros(n_all)
+        self.e, self.d = self._empty(n_all, st["M"]), self._empty(n_all, st["ncon"])     # what a factorization keeps, by problem
+        self.kk, self.beta, self.d_t = self._empty(n_all), self._empty(n_all), None       # number (d_t: the device driver's d)
 
     def _empty(self, *shape):
         return self.torch.empty(shape, dtype=self.torch.float64, device=self.dev)
@@ -276,14 +277,20 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         slip = np.ascontiguousarray(h.cpu().numpy().transpose(0, 2, 1)).reshape(len(idx), -1)          # row order i C + c
         return [assemble_g(self.models[i], np.asarray(Z), defect[k], rows[k], slip[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
 
+    def _det_values(self, lin, K):
+        """the deterministic rows' Jacobian values (K, n_det): the constant entries, the partials of ``lin`` scattered over them"""
+        mp = self.maps
+        jac = mp["det_const"][None].repeat(K, 1).contiguous()
+        _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
+        _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
+        return jac
+
     def eval_full(self, idx, Zs, lams, sfs):
         with self.timed("callbacks"):
-            m0, mp, K = self.m0, self.maps, len(idx)
+            m0, K = self.m0, len(idx)
             Zd, lamd = self._up(Zs), self._up(lams)
             lin = _h.nlp_linearize_device(self.params, Zd)
-            jac = mp["det_const"][None].repeat(K, 1).contiguous()
-            _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
-            _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
+            jac = self._det_values(lin, K)
             slip = m0.slip_device_f64(Zd, lamd, want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of(idx))
             add = self._up([_obj_add(m0, sf) for sf in sfs])
             m0.slip_hess_blocks_device_f64(Zd, slip["D"], add)
@@ -305,177 +312,178 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     def hess_apply(self, idx, X):
         return [_hess_apply(self.st["hess"], self.hess_host[self.slot[i]], x) for i, x in zip(idx, X)]
 
-    def _sel(self, idx):
-        return self._rows(idx, self.vals0, self.dx, self.dfz, self.hessd)
-
+    # ---- the arrow step, written once on device tensors and served to both drivers.  Each function takes the arrays it reads
+    # (``vals`` = (vals0, dx, dfz, hessd) of its K problems, malpha (K,)), what a factorization keeps (e (K, M), d (K, ld >= ncon),
+    # kk and beta (K,), the factor L) and work buffers ``w`` for K problems; vectors are (K, ld) tensors where they lie.  Nothing
+    # here waits or moves anything to the host: a line between two launches is an ``arrow_*`` binding of ``hopper_ipm``, a gather
+    # or scatter between z numbering, core numbering and the touched columns rato_scatter_f64 with ``arrow_structure``'s maps.
     def _call(self, name, *args):
         with self.torch.cuda.device(self.dev):
             self._lib.check(getattr(self.lib, name)(*args, self._lib.current_stream()), name)
 
-    def matvec(self, idx, X):
-        with self.timed("products"):
-            st, p = self.st, self._lib.ptr
-            M, Cn, K = st["M"], st["C"], len(idx)
-            v0, dx, dfz, _ = self._sel(idx)
-            xh = np.stack(X)
-            x = self._up(X)
-            out = csc_matvec(st, self.maps, v0, None, x)                # the deterministic rows; the risk rows below
-            xq, xy = self._up(list(xh[:, st["qz"]])), x[:, st["y0"]:st["y0"] + M].contiguous()
-            part, red = self._empty(self.nch, K), self._empty(K)
-            self._call("rato_hopper_arrow_rows_f64", K, M, Cn, int(st["saa"]), 0, p(dx), p(dfz), p(xq), p(xy), None, 0, st["r0"],
-                       None, p(out), st["ncon"], p(part), p(red))
-            o = out.cpu().numpy()
-            if st["saa"]:
-                o[:, st["rr"]] = self._malpha(idx) * xh[:, st["n"] - 1] + red.cpu().numpy()
-        return list(o)
+    def _buffers(self, K):
+        """the step's work buffers for K problems"""
+        st = self.st
+        M, q, nc = st["M"], st["q"], st["nc"]
+        return dict(xq=self._empty(K, q), xy=self._empty(K, M), yout=self._empty(K, M), dg=self._empty(K, nc), yd=self._empty(K, M),
+                    rc=self._empty(K, nc), ry=self._empty(K, M), t=self._empty(K, M), rem=self._empty(K, M), addc=self._empty(K),
+                    part1=self._empty(self.nch, K), red1=self._empty(K), partc=self._empty(self.nch, K, 5 * st["C"] + 1),
+                    redc=self._empty(K, 5 * st["C"] + 1), partr=self._empty(self.nch, K, self.npart),
+                    redr=self._empty(K, self.npart))
 
-    def _cols(self, mode, dx, dfz, w, t, yout):
-        """rato_hopper_arrow_cols_f64 -> (K, 5C + 1) host"""
-        st, p = self.st, self._lib.ptr
-        K = w.shape[0]
-        part, red = self._empty(self.nch, K, 5 * st["C"] + 1), self._empty(K, 5 * st["C"] + 1)
-        self._call("rato_hopper_arrow_cols_f64", K, st["M"], st["C"], int(st["saa"]), mode, p(dx), p(dfz), p(w), w.shape[1], st["r0"],
-                   p(t), p(yout), p(part), p(red))
-        return red.cpu().numpy()
-
-    def _minus_fx_total(self, red):
-        """-sum_c of the fx column sums (the slack and t_risk columns hold -1 in every slip row), contacts ascending one
-        problem-wise addition at a time: np.sum over an axis of a (K, C) array picks its order by K"""
-        tot = np.zeros(red.shape[0])
-        for c in range(self.st["C"]):
-            tot -= red[:, 5 * c + 3]
-        return tot
-
-    def tmatvec(self, idx, W):
-        with self.timed("products"):
-            st = self.st
-            M, Cn, K = st["M"], st["C"], len(idx)
-            v0, dx, dfz, _ = self._sel(idx)
-            wh = np.stack(W)
-            w = self._up(W)
-            out = csc_tmatvec(st, self.maps, v0, None, w)
-            yout = self._empty(K, M)
-            red = self._cols(0, dx, dfz, w, None, yout)
-            o = out.cpu().numpy()
-            tot = self._minus_fx_total(red)
-            o[:, st["qz"][:5 * Cn]] += red[:, :5 * Cn]
-            o[:, st["n"] - 2] += tot
-            if st["saa"]:
-                o[:, st["n"] - 1] += self._malpha(idx) * wh[:, st["rr"]] + tot
-                o[:, st["y0"]:st["y0"] + M] = yout.cpu().numpy()
-        return list(o)
-
-    def schur(self, idx, D, diags, out=None):
-        """-> (Shat (K, nc, lda) device tensor, lower triangle; e (K, M) and d (K, ncon) device; red (K, n_part) and d on the
-        host): the core's Schur complement of the listed problems (``out``: a contiguous (K, nc, lda >= nc) tensor to write into)"""
-        st, mp, p = self.st, self.maps, self._lib.ptr
-        M, Cn, nc, K = st["M"], st["C"], st["nc"], len(idx)
-        v0, dx, dfz, hs = self._sel(idx)
-        dh = np.stack(D)
-        d, dgh = self._up(D), np.stack(diags)
-        dg, yd = self._up(list(dgh[:, st["core_z"]])), self._up(list(dgh[:, st["y0"]:st["y0"] + M]))
-        t0 = time.perf_counter()
-        Sh = normal_matrix(nc, st["ncon"], mp, v0, None, d, hs, dg, out=out)       # the deterministic rows' J'DJ + W + the diagonal
-        self._sync()
-        t1 = time.perf_counter()
-        e, part, red = self._empty(K, M), self._empty(self.nch, K, self.npart), self._empty(K, self.npart)
-        self._call("rato_hopper_arrow_reduce_f64", K, M, Cn, int(st["saa"]), p(dx), p(dfz), p(d), st["ncon"], st["r0"], p(yd), p(e),
-                   p(part), p(red))
-        self._sync()
-        t2 = time.perf_counter()
-        ma = self._up([self._malpha(idx)])[0].contiguous()
-        self._call("rato_hopper_arrow_assemble_f64", K, M, Cn, int(st["saa"]), nc, Sh.shape[2], p(mp["qcol"]), p(red), p(d),
-                   st["ncon"], st["r0"], p(ma), p(Sh))
-        self._sync()
-        t3 = time.perf_counter()
-        self.clock["normal"] += t1 - t0
-        self.clock["reduction"] += t2 - t1
-        self.clock["assembly"] += t3 - t2
-        return Sh, e, d, red.cpu().numpy(), dh
-
-    def factor(self, idx, D, diags):
-        torch, st = self.torch, self.st
-        Sh, e, d, red, dh = self.schur(idx, D, diags)
-        t1 = time.perf_counter()
-        info = self.factor_device(idx, Sh)
-        sel = torch.as_tensor(list(idx), device=self.dev)
-        self.e[sel], self.d[sel] = e, d
-        if st["saa"]:
-            q = st["q"]
-            s = red[:, q * (q + 1) // 2 + 2 * q]
-            d0 = dh[:, st["rr"]]
-            self.kk[list(idx)] = d0 / (1.0 + d0 * s)
-            self.beta[list(idx)] = d0 * self._malpha(idx)
-        self.clock["factor"] += time.perf_counter() - t1
-        return info
-
-    def _einv(self, e, v, kk):
-        """E^-1 v for (K, M) device tensors: u o (v - k (u'v))"""
-        p = self._lib.ptr
-        K, M = v.shape
-        kappa = np.zeros(K)
-        if self.st["saa"]:
-            part, red = self._empty(self.nch, K), self._empty(K)
-            self._call("rato_hopper_arrow_edot_f64", K, M, p(e), p(v), p(part), p(red))
-            kappa = kk * red.cpu().numpy()
-        out, kap = self._empty(K, M), self._up([kappa])[0].contiguous()   # kap stays referenced until the launch is queued
-        self._call("rato_hopper_arrow_eapply_f64", K, M, p(e), p(v), p(kap), p(out))
-        return out
-
-    def solve(self, idx, B):
-        with self.timed("solve"):
-            st, p = self.st, self._lib.ptr
-            M, Cn, K, q = st["M"], st["C"], len(idx), st["q"]
-            rows = [self.slot[i] for i in idx]
-            sel = self.torch.as_tensor(list(idx), device=self.dev)
-            ssel = self.torch.as_tensor(rows, device=self.dev)
-            e, d = self.e.index_select(0, sel), self.d.index_select(0, sel)
-            dx, dfz = self.dx.index_select(0, ssel), self.dfz.index_select(0, ssel)
-            kk, beta = self.kk[list(idx)], self.beta[list(idx)]
-            bh = np.stack(B)
-            rc = bh[:, st["core_z"]].copy()
-            ry = self._up(list(bh[:, st["y0"]:st["y0"] + M]))
-            if st["saa"]:
-                t = self._einv(e, ry, kk)
-                red = self._cols(1, dx, dfz, d, t, None)
-                tot = self._minus_fx_total(red)
-                rc[:, st["qcol"][:5 * Cn]] -= red[:, :5 * Cn]
-                rc[:, -2] -= tot
-                rc[:, -1] -= tot + beta * red[:, 5 * Cn]
-            xch = self.solve_device(idx, list(rc))
-            if st["saa"]:
-                rem = self._empty(K, M)                                    # r_y - B x_c
-                xq, addc = self._up(list(xch[:, st["qcol"]])), self._up([beta * xch[:, -1]])[0].contiguous()
-                self._call("rato_hopper_arrow_rows_f64", K, M, Cn, 1, 1, p(dx), p(dfz), p(xq), p(ry), p(d), st["ncon"], st["r0"],
-                           p(addc), p(rem), M, None, None)
-                ry = rem
-            ry = self._einv(e, ry, kk)
-            out = np.empty((K, st["n"]))
-            out[:, st["core_z"]] = xch
-            out[:, st["y0"]:st["y0"] + M] = ry.cpu().numpy()
-        return list(out)
-
-    # ---- the same on device tensors, for ``ipm.solve_group_device`` (DESIGN §7.ai): every call serves the whole group, takes and
-    # returns (K, ld) tensors, waits for nothing and moves nothing to the host.  What the list methods fix up on the host is done
-    # by the ``arrow_*`` bindings of ``hopper_ipm`` (bitwise the host's lines); gathers and scatters between z numbering, core
-    # numbering and the touched columns go through rato_scatter_f64 with the maps of ``arrow_structure``.
     def _work(self):
-        """the work buffers of the group and the uploaded maps, made once"""
+        """the work buffers of the group, its malpha and the uploaded maps, made once"""
         w = getattr(self, "_w", None)
         if w is None:
             st, K, torch = self.st, self.n_all, self.torch
-            M, q, nc = st["M"], st["q"], st["nc"]
             up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
             w = self._w = dict(
-                xq=self._empty(K, q), xy=self._empty(K, M), yout=self._empty(K, M), dg=self._empty(K, nc), yd=self._empty(K, M),
-                rc=self._empty(K, nc), ry=self._empty(K, M), t=self._empty(K, M), rem=self._empty(K, M), addc=self._empty(K),
-                part1=self._empty(self.nch, K), red1=self._empty(K), partc=self._empty(self.nch, K, 5 * st["C"] + 1),
-                redc=self._empty(K, 5 * st["C"] + 1), partr=self._empty(self.nch, K, self.npart), redr=self._empty(K, self.npart),
-                kk=self._empty(K), beta=self._empty(K), malpha=self._up([self._malpha(range(K))])[0].contiguous(),
+                self._buffers(K), malpha=self._up([self._malpha(range(K))])[0].contiguous(),
                 add=self._empty(K, self.m0.S + 1, _h.n_pairs), qz=up(st["qz"], np.int32), core_z=up(st["core_z"], np.int64),
                 inv_qz=up(st["inv_qz"], np.int64), inv_core_z=up(st["inv_core_z"], np.int64), inv_qcol=up(st["inv_qcol"], np.int64))
         return w
 
+    def _jx(self, X, vals, malpha, w):
+        """X (K, ld >= n) -> J x (K, ncon)"""
+        st, p = self.st, self._lib.ptr
+        M, Cn, n, K = st["M"], st["C"], st["n"], X.shape[0]
+        v0, dx, dfz, _ = vals
+        out = csc_matvec(st, self.maps, v0, None, X)                    # the deterministic rows; the risk rows below
+        xq = scatter_rows(X, n, w["inv_qz"], w["xq"], st["q"])
+        xy = w["xy"].copy_(X[:, st["y0"]:st["y0"] + M])
+        self._call("rato_hopper_arrow_rows_f64", K, M, Cn, int(st["saa"]), 0, p(dx), p(dfz), p(xq), p(xy), None, 0, st["r0"], None,
+                   p(out), st["ncon"], p(w["part1"]), p(w["red1"]))
+        if st["saa"]:
+            arrow_scale(malpha, X, n - 1, w["red1"], out, st["rr"])
+        return out
+
+    def _jtw(self, W, vals, malpha, w):
+        """W (K, ld >= ncon) -> J' w (K, n)"""
+        st, p = self.st, self._lib.ptr
+        M, Cn, K = st["M"], st["C"], W.shape[0]
+        v0, dx, dfz, _ = vals
+        out = csc_tmatvec(st, self.maps, v0, None, W)
+        self._call("rato_hopper_arrow_cols_f64", K, M, Cn, int(st["saa"]), 0, p(dx), p(dfz), p(W), W.shape[1], st["r0"], None,
+                   p(w["yout"]), p(w["partc"]), p(w["redc"]))
+        arrow_tfix(M, Cn, st["saa"], st["n"], w["qz"], w["redc"], malpha, W, st["rr"], w["yout"], out)
+        return out
+
+    def _schur(self, d, diag, vals, malpha, e, kk, beta, out, w):
+        """d (K, ld >= ncon) and diag (K, n) -> the core's Schur complement (K, nc, lda), lower triangle, written into ``out`` (a
+        contiguous (K, nc, lda >= nc) tensor; None: a new one): normal_matrix on the core pattern, reduce, assemble.  Fills e
+        (K, M) and, with SAA, kk and beta (K,)."""
+        st, mp, p = self.st, self.maps, self._lib.ptr
+        M, Cn, nc, K = st["M"], st["C"], st["nc"], d.shape[0]
+        v0, dx, dfz, hs = vals
+        with self.timed_t("normal"):
+            dg = scatter_rows(diag, st["n"], w["inv_core_z"], w["dg"], nc)
+            yd = w["yd"].copy_(diag[:, st["y0"]:st["y0"] + M])
+            Kc = normal_matrix(nc, st["ncon"], mp, v0, None, d, hs, dg, out=out)   # the deterministic rows' J'DJ + W + the diagonal
+        with self.timed_t("reduction"):
+            self._call("rato_hopper_arrow_reduce_f64", K, M, Cn, int(st["saa"]), p(dx), p(dfz), p(d), d.shape[1], st["r0"], p(yd),
+                       p(e), p(w["partr"]), p(w["redr"]))
+        with self.timed_t("assembly"):
+            self._call("rato_hopper_arrow_assemble_f64", K, M, Cn, int(st["saa"]), nc, Kc.shape[2], p(mp["qcol"]), p(w["redr"]),
+                       p(d), d.shape[1], st["r0"], p(malpha), p(Kc))
+            if st["saa"]:
+                arrow_kkbeta(Cn, d, st["rr"], w["redr"], malpha, kk, beta)
+        return Kc
+
+    def _einv(self, e, kk, v, out, w):
+        """E^-1 v = u o (v - kk (u'v)), u = 1 / e, for v and out (K, >= M)"""
+        p = self._lib.ptr
+        if not self.st["saa"]:
+            return arrow_einv(e, v, None, None, out)
+        self._call("rato_hopper_arrow_edot_f64", v.shape[0], self.st["M"], p(e), p(v), p(w["part1"]), p(w["red1"]))
+        return arrow_einv(e, v, kk, w["red1"], out)
+
+    def _solve(self, B, vals, kept, w):
+        """the elimination in place on B (K, ld >= n) in z numbering, from what the factorization kept"""
+        st, p = self.st, self._lib.ptr
+        M, Cn, nc, n, K, y0 = st["M"], st["C"], st["nc"], st["n"], B.shape[0], st["y0"]
+        (_, dx, dfz, _), (e, d, kk, beta, L) = vals, kept
+        rc = scatter_rows(B, n, w["inv_core_z"], w["rc"], nc)
+        ry = w["ry"].copy_(B[:, y0:y0 + M])
+        if st["saa"]:
+            t = self._einv(e, kk, ry, w["t"], w)
+            self._call("rato_hopper_arrow_cols_f64", K, M, Cn, 1, 1, p(dx), p(dfz), p(d), d.shape[1], st["r0"], p(t), None,
+                       p(w["partc"]), p(w["redc"]))
+            arrow_rhsfix(Cn, nc, self.maps["qcol"], w["redc"], beta, rc)
+        self.chol_solve(L, rc[:, None, :])
+        if st["saa"]:
+            xq = scatter_rows(rc, nc, w["inv_qcol"], w["xq"], st["q"])
+            arrow_scale(beta, rc, nc - 1, None, w["addc"], 0)
+            self._call("rato_hopper_arrow_rows_f64", K, M, Cn, 1, 1, p(dx), p(dfz), p(xq), p(ry), p(d), d.shape[1], st["r0"],
+                       p(w["addc"]), p(w["rem"]), M, None, None)                   # r_y - B x_c
+            ry = w["rem"]
+        self._einv(e, kk, ry, B[:, y0:y0 + M], w)
+        scatter_rows(rc, nc, w["core_z"], B, n)
+        return B
+
+    # ---- the list methods (the driver on the host): upload the listed problems' vectors, take their rows of the arrays, run the
+    # step, write what is kept back under the problems' numbers, download.  The clocks end in a device-wide wait.
+    def _vals(self):
+        return self.vals0, self.dx, self.dfz, self.hessd
+
+    def _listed(self, idx, *kept):
+        """-> (vals, malpha, w, *kept) of the listed problems: their rows of the value arrays by ``slot``, of malpha and of the
+        ``kept`` arrays by problem number, and work buffers for them -- the group's own arrays when everyone is listed in order"""
+        w = self._work()
+        vals = self._rows(idx, *self._vals())
+        if list(idx) == list(range(self.n_all)):
+            return (vals, w["malpha"], w) + kept
+        sel = self.torch.as_tensor(list(idx), device=self.dev)
+        take = lambda t: t.index_select(0, sel)
+        return (vals, take(w["malpha"]), dict(w, **self._buffers(len(idx)))) + tuple(take(t) for t in kept)
+
+    @contextlib.contextmanager
+    def _waited(self):
+        """``timed_t`` with a device-wide wait behind every block, whatever the class's ``sync_clocks`` says"""
+        self.sync_clocks = True
+        try:
+            yield
+        finally:
+            del self.sync_clocks
+
+    def matvec(self, idx, X):
+        with self.timed("products"):
+            return list(self._jx(self._up(X), *self._listed(idx)).cpu().numpy())
+
+    def tmatvec(self, idx, W):
+        with self.timed("products"):
+            return list(self._jtw(self._up(W), *self._listed(idx)).cpu().numpy())
+
+    def _schur_listed(self, idx, D, diags, out=None):
+        """``_schur`` of the listed problems into arrays of their own -> (Shat, e, d, kk, beta, w), all on the device"""
+        K = len(idx)
+        vals, malpha, w = self._listed(idx)
+        d, e, kk, beta = self._up(D), self._empty(K, self.st["M"]), self._empty(K), self._empty(K)
+        with self._waited():
+            Sh = self._schur(d, self._up(diags), vals, malpha, e, kk, beta, out, w)
+        return Sh, e, d, kk, beta, w
+
+    def schur(self, idx, D, diags, out=None):
+        """-> (Shat (K, nc, lda) device tensor, lower triangle; e (K, M) and d (K, ncon) device; red (K, n_part) and d on the
+        host): the core's Schur complement of the listed problems (``out``: a contiguous (K, nc, lda >= nc) tensor to write into).
+        Nothing that is kept changes."""
+        Sh, e, d, _, _, w = self._schur_listed(idx, D, diags, out)
+        return Sh, e, d, w["redr"].cpu().numpy(), np.stack(D)
+
+    def factor(self, idx, D, diags):
+        Sh, e, d, kk, beta, _ = self._schur_listed(idx, D, diags)
+        with self.timed("factor"):
+            info = self.factor_device(idx, Sh)
+            sel = self.torch.as_tensor(list(idx), device=self.dev)
+            self.e[sel], self.d[sel], self.kk[sel], self.beta[sel] = e, d, kk, beta
+        return info
+
+    def solve(self, idx, B):
+        with self.timed("solve"):
+            vals, _, w, *kept = self._listed(idx, self.e, self.d, self.kk, self.beta, self.L)
+            return list(self._solve(self._up(B), vals, kept, w).cpu().numpy())
+
+    # ---- the same on device tensors, for ``ipm.solve_group_device`` (DESIGN §7.ai): every call serves the whole group where its
+    # arrays lie, takes and returns (K, ld) tensors, waits for nothing and moves nothing to the host
     def _g_t(self, Z, lin, h):
         m0, st = self.m0, self.st
         return _h.g_device(m0._slip_params(), st["M"], st["saa"], Z, lin["defect"], lin["rows"], h, (1, st["M"]),
@@ -485,11 +493,9 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         """Z (K, n) and the multipliers Y (K, ld >= ncon), read where they lie -> g (K, ncon); leaves the deterministic rows'
         values, the slip partials and the step blocks of hess(Y . g) for the calls below.  The objective's curvature is NOT in the
         blocks: the driver's diagonal carries it."""
-        m0, mp, w, K = self.m0, self.maps, self._work(), Z.shape[0]
+        m0, w, K = self.m0, self._work(), Z.shape[0]
         lin = _h.nlp_linearize_device(self.params, Z)
-        jac = mp["det_const"][None].repeat(K, 1).contiguous()
-        _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
-        _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
+        jac = self._det_values(lin, K)
         slip = m0.slip_device_f64(Z, Y[:, :self.st["ncon"]], want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of())
         add = w["add"].zero_()
         m0.slip_hess_blocks_device_f64(Z, slip["D"], add)
@@ -510,78 +516,25 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     def matvec_t(self, X):
         """X (K, ld >= n) -> J x (K, ncon)"""
         with self.timed_t("products"):
-            st, w, p = self.st, self._work(), self._lib.ptr
-            M, Cn, n, K = st["M"], st["C"], st["n"], X.shape[0]
-            out = csc_matvec(st, self.maps, self.vals0, None, X)
-            xq = scatter_rows(X, n, w["inv_qz"], w["xq"], st["q"])
-            xy = w["xy"].copy_(X[:, st["y0"]:st["y0"] + M])
-            self._call("rato_hopper_arrow_rows_f64", K, M, Cn, int(st["saa"]), 0, p(self.dx), p(self.dfz), p(xq), p(xy), None, 0,
-                       st["r0"], None, p(out), st["ncon"], p(w["part1"]), p(w["red1"]))
-            if st["saa"]:
-                arrow_scale(w["malpha"], X, n - 1, w["red1"], out, st["rr"])
-        return out
+            w = self._work()
+            return self._jx(X, self._vals(), w["malpha"], w)
 
     def tmatvec_t(self, W):
         """W (K, ld >= ncon) -> J' w (K, n)"""
         with self.timed_t("products"):
-            st, w, p = self.st, self._work(), self._lib.ptr
-            M, Cn, K = st["M"], st["C"], W.shape[0]
-            out = csc_tmatvec(st, self.maps, self.vals0, None, W)
-            self._call("rato_hopper_arrow_cols_f64", K, M, Cn, int(st["saa"]), 0, p(self.dx), p(self.dfz), p(W), W.shape[1], st["r0"],
-                       None, p(w["yout"]), p(w["partc"]), p(w["redc"]))
-            arrow_tfix(M, Cn, st["saa"], st["n"], w["qz"], w["redc"], w["malpha"], W, st["rr"], w["yout"], out)
-        return out
+            w = self._work()
+            return self._jtw(W, self._vals(), w["malpha"], w)
 
     def factor_t(self, d, diag):
         """d (K, ld >= ncon) and diag (K, n) with the objective's curvature already in it: the core's Schur complement into the
-        kept ``self.Kc`` (normal_matrix on the core pattern, reduce, assemble), factored in place -> info (K,) int32 device tensor.
-        e, kk and beta stay on the device; ``d`` is kept by reference for ``solve_t``."""
-        st, mp, w, p = self.st, self.maps, self._work(), self._lib.ptr
-        M, Cn, nc, K = st["M"], st["C"], st["nc"], d.shape[0]
-        with self.timed_t("normal"):
-            dg = scatter_rows(diag, st["n"], w["inv_core_z"], w["dg"], nc)
-            yd = w["yd"].copy_(diag[:, st["y0"]:st["y0"] + M])
-            self.Kc = normal_matrix(nc, st["ncon"], mp, self.vals0, None, d, self.hessd, dg, out=self.Kc)
-        with self.timed_t("reduction"):
-            self._call("rato_hopper_arrow_reduce_f64", K, M, Cn, int(st["saa"]), p(self.dx), p(self.dfz), p(d), d.shape[1], st["r0"],
-                       p(yd), p(self.e), p(w["partr"]), p(w["redr"]))
-        with self.timed_t("assembly"):
-            self._call("rato_hopper_arrow_assemble_f64", K, M, Cn, int(st["saa"]), nc, self.Kc.shape[2], p(mp["qcol"]), p(w["redr"]),
-                       p(d), d.shape[1], st["r0"], p(w["malpha"]), p(self.Kc))
-            if st["saa"]:
-                arrow_kkbeta(Cn, d, st["rr"], w["redr"], w["malpha"], w["kk"], w["beta"])
-            self.d_t = d
+        kept ``self.Kc``, factored in place -> info (K,) int32 device tensor.  e, kk and beta stay on the device; ``d`` is kept by
+        reference for ``solve_t``."""
+        w = self._work()
+        self.Kc = self._schur(d, diag, self._vals(), w["malpha"], self.e, self.kk, self.beta, self.Kc, w)
+        self.d_t = d
         return self.factor_all(self.Kc)
-
-    def _einv_t(self, v, out):
-        """E^-1 v for (K, >= M) device tensors into ``out``: kappa is formed on the device"""
-        w, p = self._work(), self._lib.ptr
-        K, M = v.shape[0], self.st["M"]
-        if not self.st["saa"]:
-            return arrow_einv(self.e, v, None, None, out)
-        self._call("rato_hopper_arrow_edot_f64", K, M, p(self.e), p(v), p(w["part1"]), p(w["red1"]))
-        return arrow_einv(self.e, v, w["kk"], w["red1"], out)
 
     def solve_t(self, B):
         """the elimination in place on B (K, ld >= n) in z numbering, from what ``factor_t`` kept"""
         with self.timed_t("solve"):
-            st, w, p = self.st, self._work(), self._lib.ptr
-            M, Cn, nc, n, K, y0 = st["M"], st["C"], st["nc"], st["n"], B.shape[0], st["y0"]
-            d = self.d_t
-            rc = scatter_rows(B, n, w["inv_core_z"], w["rc"], nc)
-            ry = w["ry"].copy_(B[:, y0:y0 + M])
-            if st["saa"]:
-                t = self._einv_t(ry, w["t"])
-                self._call("rato_hopper_arrow_cols_f64", K, M, Cn, 1, 1, p(self.dx), p(self.dfz), p(d), d.shape[1], st["r0"], p(t),
-                           None, p(w["partc"]), p(w["redc"]))
-                arrow_rhsfix(Cn, nc, self.maps["qcol"], w["redc"], w["beta"], rc)
-            self.chol_solve(self.L, rc[:, None, :])
-            if st["saa"]:
-                xq = scatter_rows(rc, nc, w["inv_qcol"], w["xq"], st["q"])
-                arrow_scale(w["beta"], rc, nc - 1, None, w["addc"], 0)
-                self._call("rato_hopper_arrow_rows_f64", K, M, Cn, 1, 1, p(self.dx), p(self.dfz), p(xq), p(ry), p(d), d.shape[1],
-                           st["r0"], p(w["addc"]), p(w["rem"]), M, None, None)
-                ry = w["rem"]
-            self._einv_t(ry, B[:, y0:y0 + M])
-            scatter_rows(rc, nc, w["core_z"], B, n)
-        return B
+            return self._solve(B, self._vals(), (self.e, self.d_t, self.kk, self.beta, self.L), self._work())

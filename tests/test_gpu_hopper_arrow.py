@@ -380,6 +380,58 @@ def test_list_methods_on_a_subset_of_the_group(S, M):
             assert np.ascontiguousarray(a[sub]).tobytes() == b.tobytes(), name
 
 
+def gershgorin(st, blocks):
+    """per variable the absolute row sum of W given as step blocks (S+1, 78): W + diag is positive definite for diag above it"""
+    import _hopper_nlp as R
+    Bf = np.abs(R.untril78(blocks))
+    mag = np.zeros(st["n"] + 1)
+    mag[st["block_vars"]] = Bf.sum(axis=2)
+    return mag[:-1]
+
+
+@pytest.mark.parametrize("S,M,method", [(2, 4, 'saa'), (2, 65, 'saa'), (2, 4, 'baseline')])
+def test_refactoring_a_subset_leaves_the_others_factors(S, M, method):
+    """the ladder of ``ipm.newton_steps``: everyone is factored, [2, 0] are factored again with other weights, then everyone is
+    solved for.  What is kept per problem (e, d, kk, beta, L) is addressed by problem number: problem 1's solution does not move
+    by a bit, alone or in the batch, and problems 2 and 0 get bitwise what a fresh backend gives that factored everyone with the
+    new weights in their rows.  Diagonals above W's Gershgorin radius: every factorization succeeds by design."""
+    import _hopper_nlp as R
+    from riskaversetrajopt_amd import ipm as method_ipm
+    m = arrow()
+    flds = H.fields(M)
+    models = [device_model(S, M, method, a, flds) for a in (0.1, 0.2, 0.3)]
+    everyone, sub = list(range(K3)), [2, 0]
+    Z0s = [R.problem(S, M, k) for k in everyone]
+    rng = np.random.RandomState(700 + S + M)
+    lay = models[0].nlp_layout()
+    n, ncon = lay["nvar"], lay["ncon"]
+    lams = list(rng.uniform(-1, 1, (K3, ncon)))
+
+    def backend():
+        be = m.ArrowDeviceBackend(models)
+        ps = [method_ipm.Problem(mm, Z0, g0, H.TOL) for mm, Z0, g0 in zip(models, Z0s, be.eval_g(everyone, Z0s))]
+        be.eval_full(everyone, [p.z.copy() for p in ps], lams, [p.sf for p in ps])
+        return be
+    be = backend()
+    radius = np.stack([gershgorin(be.st["hess"], be.hess_host[k]) for k in everyone])
+    B = list(rng.randn(K3, n))
+    D, diags = 10.0 ** rng.uniform(-3, 3, (K3, ncon)), radius + 10.0 ** rng.uniform(-3, 3, (K3, n))
+    D2, diags2 = D.copy(), diags.copy()
+    D2[sub], diags2[sub] = 10.0 ** rng.uniform(-3, 3, (2, ncon)), radius[sub] + 10.0 ** rng.uniform(-3, 3, (2, n))
+    assert be.factor(everyone, list(D), list(diags)) == [0] * K3
+    X = np.stack(be.solve(everyone, B))
+    assert be.factor(sub, list(D2[sub]), list(diags2[sub])) == [0, 0]
+    X2, X3 = np.stack(be.solve(everyone, B)), np.stack(be.solve([1], [B[1]]))
+    fresh = backend()
+    assert fresh.factor(everyone, list(D2), list(diags2)) == [0] * K3
+    Xf = np.stack(fresh.solve(everyone, B))
+    assert np.all(np.isfinite(X)) and np.all(np.isfinite(X2))
+    assert X2[1].tobytes() == X[1].tobytes() and X3[0].tobytes() == X[1].tobytes()
+    for k in sub:
+        assert X2[k].tobytes() == Xf[k].tobytes(), k
+        assert X2[k].tobytes() != X[k].tobytes(), k                   # the new weights did arrive
+
+
 @pytest.fixture(scope="module")
 def baseline_small():
     """the S = 6, M = 4 baseline by the device arrow step, and the largest |f_device - f_numpy| of the DENSE step over the

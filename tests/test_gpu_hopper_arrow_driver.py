@@ -16,7 +16,8 @@ import _hopper_ipm_driver as HD
 import _hopper_nlp as R
 from _drone_gaussian_ipm import padded
 from _hopper_ipm import gamma
-from test_gpu_hopper_arrow import Designed, baseline_small, device_model, shapes      # noqa: F401  (baseline_small is a fixture)
+from test_gpu_hopper_arrow import (Designed, baseline_small, device_model, gershgorin,    # noqa: F401  (baseline_small is a fixture)
+                                   shapes)
 from test_gpu_hopper_ipm_driver import bitwise, nothing_moves_to_the_host, within
 
 pytestmark = pytest.mark.gpu
@@ -251,14 +252,6 @@ def test_fixup_entry_points_answer_bad_arguments_with_einval():
 
 
 # ---- the backend on device tensors against its list methods -------------------------------------------------------------------
-def gershgorin(st, blocks):
-    """per variable the absolute row sum of W given as step blocks (S+1, 78): W + diag is positive definite for diag above it"""
-    Bf = np.abs(R.untril78(blocks))
-    mag = np.zeros(st["n"] + 1)
-    mag[st["block_vars"]] = Bf.sum(axis=2)
-    return mag[:-1]
-
-
 @pytest.mark.parametrize("method", ["saa", "baseline"])
 @pytest.mark.parametrize("S,M", [(2, 4), (2, 65), (6, 4), (6, 65)])
 def test_backend_on_tensors_against_the_list_methods(S, M, method, monkeypatch):
@@ -337,8 +330,8 @@ def test_backend_on_tensors_against_the_list_methods(S, M, method, monkeypatch):
     assert len(kept) == 1 and np.where(low, kept[0].cpu().numpy()[:, :, :nc], 0.0).tobytes() == np.where(low, Sh[:, :, :nc], 0.0).tobytes()
     assert bt.e.cpu().numpy().tobytes() == e.tobytes()
     if saa:
-        w = bt._work()
-        assert w["kk"].cpu().numpy().tobytes() == be.kk.tobytes() and w["beta"].cpu().numpy().tobytes() == be.beta.tobytes()
+        assert bt.kk.cpu().numpy().tobytes() == be.kk.cpu().numpy().tobytes()
+        assert bt.beta.cpu().numpy().tobytes() == be.beta.cpu().numpy().tobytes()
     assert got["x"].cpu().numpy()[:, :n].tobytes() == sol.tobytes()
     # W x: both within gamma_13 of the exact sum
     Wx = got["Wx"].cpu().numpy()
