@@ -98,7 +98,8 @@ extern "C" {
  * rato_scp_batch_run_car -- additions within version 12: the same for the driving problem; rato_drone_rows_plan /
  * rato_car_rows_plan -- a further addition within version 12: the row kernels' launch geometry as a query;
  * rato_hopper_slip_f64 / rato_hopper_slip_f64_nblocks / rato_hopper_slip_hess_blocks_f64 -- likewise: the hopper's slip rows in fp64;
- * rato_hopper_slip_f64_fields -- likewise: the same with friction fields per problem).
+ * rato_hopper_slip_f64_fields -- likewise: the same with friction fields per problem;
+ * rato_risk_stats_shaped -- likewise: the selection at the workgroup sizes of the launches that carry their statistics).
  * The Python binding refuses a library that reports another version. */
 #define RATO_ABI_VERSION 12
 #define RATO_STATS_IN_LAUNCH 1   /* params.stats_flags */
@@ -1051,6 +1052,17 @@ int rato_risk_stats_init(void* workspace, size_t workspace_bytes, void* stream);
 #define RATO_N_STATS 11
 int rato_risk_stats(const float* Z, int64_t M, double alpha, float thr,
                     void* workspace, size_t workspace_bytes, double* out, void* stream);
+
+/* The same record by the selection bodies at nt threads per workgroup (256, 512 or 1024; anything else: RATO_EINVAL), with
+ * no producer to wait for: what the statistics workgroups of a launch that carries its own statistics run (params.stats_*:
+ * 512 threads at the end of the row-parallel linearize launches, 256 at the end of the tiled eval launches; 1024 is
+ * rato_risk_stats' own size), reachable on any Z.  Placed by those launches' rule: one workgroup for M <= 12,288, otherwise
+ * ceil(M / (4 nt)) <= 64 cooperating workgroups, RATO_EINVAL beyond 64 * 16 * nt samples (nothing is launched, out is
+ * not written).  Arguments and their errors as rato_risk_stats; the exactly defined entries of the record are those of
+ * rato_risk_stats to the bit, the fp64 sums equal to summation order.  For tests of the selection at the sizes production
+ * runs it at.  ABI: additive (RATO_ABI_VERSION stays 12). */
+int rato_risk_stats_shaped(const float* Z, int64_t M, double alpha, float thr, void* workspace, size_t workspace_bytes,
+                           double* out, void* stream, int32_t nt);
 
 /* Recovery path: the same statistics by the launch-per-pass form (which waits for nothing) on a workspace re-initialised
  * on the stream.  For a caller whose rato_risk_stats record came back NaN although Z is finite -- the one-launch forms

@@ -238,6 +238,7 @@ __device__ void rs_small_body(const float* __restrict__ Z, long M, double alpha,
                               unsigned* magic = nullptr) {
   constexpr int KEYS = (int)(RS_SMALL_MAX / NT), NW = NT / RATO_WAVE;
   static_assert(RS_CAND_MAX + 8 <= B1, "the candidate list reuses the histogram's LDS");
+  static_assert(RS_CAND_MAX <= NT, "the pairwise ranking gives every candidate a thread of its own");
   if (sig) {
     // (magic: the workspace's tag -- a workspace that was never initialised, or that an earlier launch un-tagged, holds
     //  no trustworthy flag: fail loudly instead of waiting on it)

@@ -340,6 +340,29 @@ __global__ __launch_bounds__(RS1_T) void rs_coop(const float* __restrict__ Z, lo
   rs_coop_body<RS1_T>(Z, M, alpha, k, var_is_max, thr, G, ws, out, (int)blockIdx.x, 0, h, red);   // rato_select.h (stand-alone)
 }
 
+// ---- The two bodies at a chosen workgroup size, with no producer (rato_risk_stats_shaped): what the statistics
+// workgroups of the row-parallel linearize launches (NT = 512) and of the tiled eval launches (NT = 256) run, reachable
+// on any Z.  Dynamic LDS laid out as stats_tail_run lays it out: h | red | redmax, rs_body_lds_bytes<NT>() bytes.
+template <int NT>
+__global__ __launch_bounds__(NT) void rs_small_shaped(const float* __restrict__ Z, long M, double alpha, unsigned k,
+                                                      int var_is_max, float thr, double* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char rs_shaped_lds[];
+  unsigned* h = reinterpret_cast<unsigned*>(rs_shaped_lds);
+  double* red = reinterpret_cast<double*>(h + B1);
+  float* redmax = reinterpret_cast<float*>(red + 6 * (NT / RATO_WAVE));
+  rs_small_body<NT>(Z, M, alpha, k, var_is_max, thr, out, nullptr, h, red, redmax);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void rs_coop_shaped(const float* __restrict__ Z, long M, double alpha, unsigned k,
+                                                     int var_is_max, float thr, int G, Workspace* __restrict__ ws,
+                                                     double* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char rs_shaped_lds[];
+  unsigned* h = reinterpret_cast<unsigned*>(rs_shaped_lds);
+  double* red = reinterpret_cast<double*>(h + B1);
+  rs_coop_body<NT>(Z, M, alpha, k, var_is_max, thr, G, ws, out, (int)blockIdx.x, 0, h, red);
+}
+
 // one workgroup: zero the whole workspace, then tag it
 __global__ __launch_bounds__(RATO_BLOCK) void rs_init_kernel(Workspace* __restrict__ ws) {
   unsigned* w = reinterpret_cast<unsigned*>(ws);
@@ -628,6 +651,42 @@ extern "C" int rato_risk_stats_init(void* workspace, size_t workspace_bytes, voi
 extern "C" int rato_risk_stats(const float* Z, int64_t M, double alpha, float thr, void* workspace,
                                size_t workspace_bytes, double* out, void* stream) {
   return risk_stats_impl(Z, M, alpha, thr, workspace, workspace_bytes, out, nullptr, 0, 0, 1.0, nullptr, stream);
+}
+
+namespace {
+template <int NT>
+int risk_stats_shaped_launch(const float* Z, int64_t M, double alpha, float thr, Workspace* ws, double* out, hipStream_t st) {
+  int G = 0;
+  if (stats_tail_workgroups<NT>(M, G) < 0) return RATO_EINVAL;   // beyond the one-launch forms at this workgroup size
+  unsigned k;
+  int var_is_max;
+  stats_rank(M, alpha, k, var_is_max);
+  if (G == 0)
+    hipLaunchKernelGGL(rs_small_shaped<NT>, dim3(1), dim3(NT), rs_body_lds_bytes<NT>(), st, Z, (long)M, alpha, k, var_is_max, thr, out);
+  else
+    hipLaunchKernelGGL(rs_coop_shaped<NT>, dim3((unsigned)G), dim3(NT), rs_body_lds_bytes<NT>(), st, Z, (long)M, alpha, k, var_is_max,
+                       thr, G, ws, out);
+  RATO_LAUNCH_CHECK();
+  return RATO_OK;
+}
+}  // namespace
+
+// rato_risk_stats by the selection bodies at nt threads per workgroup, placed by the rule of the launches that carry their
+// own statistics (stats_rank, stats_tail_workgroups<nt>): one workgroup up to 12,288 samples, G cooperating ones up to
+// 64 * 16 * nt.  No producer to wait for.
+extern "C" int rato_risk_stats_shaped(const float* Z, int64_t M, double alpha, float thr, void* workspace, size_t workspace_bytes,
+                                      double* out, void* stream, int32_t nt) {
+  RATO_CLEAR_ERROR();
+  if (!Z || !out || !workspace || M <= 0 || M >= (int64_t)0xffffffffLL || !(alpha > 0.0) || !(alpha <= 1.0)) return RATO_EINVAL;
+  if (workspace_bytes < sizeof(Workspace)) return RATO_EINVAL;
+  hipStream_t st = rato::as_stream(stream);
+  Workspace* ws = static_cast<Workspace*>(workspace);
+  switch (nt) {
+    case 256: return risk_stats_shaped_launch<256>(Z, M, alpha, thr, ws, out, st);
+    case 512: return risk_stats_shaped_launch<512>(Z, M, alpha, thr, ws, out, st);
+    case 1024: return risk_stats_shaped_launch<1024>(Z, M, alpha, thr, ws, out, st);
+    default: return RATO_EINVAL;
+  }
 }
 
 // The records of K rows of Z [K][ldz] (the Z of K control sequences on one sample batch: rato_*_eval_batch) -> out [K][N]:

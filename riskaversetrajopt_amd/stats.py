@@ -72,6 +72,24 @@ def risk_stats_device(Z, alpha, thr=SATISFIED_THRESHOLD, workspace=None, out=Non
     return out
 
 
+def risk_stats_shaped_device(Z, alpha, nt, thr=SATISFIED_THRESHOLD, workspace=None, out=None, stream=None):
+    """``risk_stats_device`` by the selection bodies at ``nt`` threads per workgroup (rato_risk_stats_shaped): 512 is what
+    rides at the end of the row-parallel linearize launches, 256 at the end of the tiled eval launches, 1024 the
+    stand-alone size.  ``RatoError`` for any other ``nt`` and beyond 64 * 16 * nt samples (``out`` is then not written)."""
+    lib = _lib.load()
+    Z = _as_device_f32(Z)
+    M = Z.numel()
+    if workspace is None:
+        workspace = new_workspace(M, Z.device)
+    if out is None:
+        out = torch.empty(N_STATS, dtype=torch.float64, device=Z.device)
+    _lib.check(lib.rato_risk_stats_shaped(_lib.ptr(Z), M, float(alpha), float(thr), _lib.ptr(workspace),
+                                          workspace.numel(), _lib.ptr(out),
+                                          _lib.current_stream() if stream is None else stream, int(nt)),
+               "rato_risk_stats_shaped")
+    return out
+
+
 # ---- statistics in the producer's own launch (rato_saa.h: params.stats_*) -------------------------------------------
 FUSED_MAX_M = 524288               # 64 statistics workgroups x 512 threads x 16 keys
 
