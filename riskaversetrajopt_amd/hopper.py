@@ -14,6 +14,11 @@ hands to IPOPT (:486-640) on the MI355X.
     fields of its own (rato_hopper_slip_f64_fields; ``stack_fields_f64``): a grid of alphas x resampled terrains is one batch.
   * ``Model.eval_batch_device``: the script's Monte-Carlo block (:960-1007) for K solutions on the model's fields in one call
     (rato_hopper_eval_batch, csrc/hopper.hip): Z, the contact that slips and the risk record of every solution.
+  * The evaluation of the NLP at Z on the device is a sequence of stages, each written once here and read by everyone -- the
+    callbacks below, ``nlp_device`` and the two device backends of ``hopper_ipm`` / ``hopper_arrow``: the one params struct
+    (``_slip_params``), ``_device_rows`` (host array or device tensor in), ``nlp_linearize_device``, ``det_jacobian_values``,
+    ``slip_device_f64`` / ``_slip_f64``, ``hess_blocks_device`` (fold, slip share, Hessian), ``hess_tril_device`` (the only owner
+    of the O(nvar^2) tril template), ``g_values_device`` and on the host ``assemble_g`` / ``_risk_rows`` / ``objective_blocks``.
   * ``Model.ipopt_callbacks()``: eval_f, eval_grad_f, eval_g, eval_jac_g, eval_h with the script's signatures, and its bounds.
   * ``Model.initial_guess()`` and ``Model.solve()``: the script's start and its solve (:136-164, :642-669) with the batched
     interior-point method of ``ipm`` on the backends of ``hopper_ipm`` (Newton step: csrc/hopper_ipm.hip, csrc/chol.hip) in
@@ -222,6 +227,14 @@ def block_variables(S, t):
     return np.concatenate([n_x * t + np.arange(n_x), u]).astype(np.int64)
 
 
+def objective_blocks(S, factor, out=None):
+    """factor hess_f as step blocks (S+1, 78): 2 R on u0 and u1 of every step, R = 1 (:443-448); added into ``out`` when given"""
+    add = np.zeros((S + 1, n_pairs)) if out is None else out
+    tr, tc = np.tril_indices(n_l)
+    add[:S, np.flatnonzero((tr == tc) & ((tr == n_x) | (tr == n_x + 1)))] += 2.0 * float(factor)
+    return add
+
+
 class Model:
     def __init__(self, M, method='baseline', alpha=0.1, S=S, fields=None, device='cuda:0', rng=None,
                  verbose=False, phases=None, precision='f32'):
@@ -385,20 +398,15 @@ class Model:
     def slip_risk_constraints(self, Z):
         """hopper.py:300-367 -> gs (1 + M + M*C + 1,) ['saa'] or (M*C,) ['baseline']."""
         Z = np.asarray(Z, dtype=np.float64)
+        return self._risk_rows(Z, self._slip_rows_host(Z))
+
+    def _slip_rows_host(self, Z):
+        """the slip values of one problem from a launch of their own, on the host in the risk rows' order i C + c"""
         if self.precision == 'f64':
-            h = self.slip_device_f64(Z[None], want=("h",))["h"][0].cpu().numpy()          # (C,M)
-            return self._risk_rows(Z, np.ascontiguousarray(h.T).reshape(-1))
-        _, _, ys, slack_var, t_risk = self.convert_z_to_variables(Z)
-        px, forces = self.contact_inputs(Z)
-        h = self.slip_device(px, forces, want_Z=False)["h"].t().double().cpu().numpy()   # (M,C)
-        M, Cn = h.shape
-        if self.method == 'baseline':
-            return (h - slack_var).reshape(M * Cn)
-        gs = np.zeros(1 + M + M * Cn + 1)
-        gs[0] = (M * self.alpha) * t_risk + np.sum(ys)
-        gs[1:1 + M] = -ys
-        gs[1 + M:1 + M + M * Cn] = (h - t_risk - ys[:, None] - slack_var).reshape(M * Cn)
-        return gs
+            h = self.slip_device_f64(Z[None], want=("h",))["h"][0]                         # (C,M)
+        else:
+            h = self.slip_device(*self.contact_inputs(Z), want_Z=False)["h"].double()
+        return np.ascontiguousarray(h.cpu().numpy().T).reshape(-1)
 
     def slip_partials(self, px, forces):
         """(h, dh/dfz, dh/dpx), each (M,C) — the sample-dependent slices of jac_g."""
@@ -559,15 +567,18 @@ class Model:
         return risk + n_risk + n_u * S + 1 + 3 * S, risk + (1 + M if saa else 0)
 
     def _slip_params(self):
+        """the model's one rato_hopper_nlp_params struct: every device call of the model and of its backends reads this one"""
         p = getattr(self, "_slip_p", None)
         if p is None:
             p = self._slip_p = nlp_params(self.S, self.time_jump, self.time_land, self.dt)
         return p
 
-    def _device_rows(self, Zs):
-        if not isinstance(Zs, torch.Tensor):
-            Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=self.device)
-        return Zs
+    def _device_rows(self, a):
+        """Z or the multipliers, a host array (one row or K) or a device tensor -> a device fp64 tensor (K, ld); a tensor is
+        taken as it is"""
+        if not isinstance(a, torch.Tensor):
+            a = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))), device=self.device)
+        return a
 
     def slip_device_f64(self, Zs, lams=None, want=("h", "dh_dfz", "dh_dx", "Zmax"), fields=None):
         """rato_hopper_slip_f64 for K problems.  Zs (K, >= 8(S+1) + 4S) host array or device fp64 tensor (rows may be strided);
@@ -582,9 +593,9 @@ class Model:
         S, M, dev = self.S, self.M, self.device
         if not 0 <= self.time_jump <= self.time_land <= S:
             raise ValueError(f"phase times must satisfy 0 <= time_jump <= time_land <= S, got {self.time_jump}, {self.time_land}")
-        if fields is not None:
-            ldf = _check_fields(fields, Zs.shape[0] if isinstance(Zs, torch.Tensor) else np.atleast_2d(np.asarray(Zs)).shape[0], M, dev)
         Zs = self._device_rows(Zs)
+        if fields is not None:
+            ldf = _check_fields(fields, Zs.shape[0], M, dev)
         K, ldz = _rows_of(Zs, n_x * (S + 1) + n_u * S)
         Cn = self.time_jump + (S - self.time_land)
         params = self._slip_params()
@@ -597,8 +608,7 @@ class Model:
         ldlam = r0 = 0
         if lams is not None:
             ncon, r0 = self.risk_rows_offset()
-            lamd = lams if isinstance(lams, torch.Tensor) else \
-                torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(lams, dtype=np.float64))), device=dev)
+            lamd = self._device_rows(lams)
             if tuple(lamd.shape) != (K, ncon) or lamd.dtype != torch.float64 or lamd.device != Zs.device or lamd.stride(1) != 1:
                 raise ValueError(f"lams must be (K, ncon) = ({K}, {ncon}) float64 with contiguous rows, got {tuple(lamd.shape)}")
             ldlam = lamd.stride(0) if K > 1 else max(lamd.stride(0), ncon)
@@ -1006,21 +1016,36 @@ class Model:
                                       callbacks=None if callbacks is None else [callbacks], verbose=verbose, newton=newton,
                                       driver=driver, chol=chol)[0]
 
-    def _nlp_state(self, K):
-        """device-side constants of the emission: the maps (uploaded once) and, per K, the destinations zeroed / pre-filled once"""
+    def _nlp_state(self):
+        """device-side constants of the emission, uploaded once and here alone: the maps, and per K the destinations pre-filled
+        (jac_templates) or zeroed (tril_templates) by the two functions below, each when it is first asked for"""
         st = getattr(self, "_nlp_dev", None)
         if st is None:
             lay = self.nlp_layout()
             up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=self.device)
-            st = dict(params=nlp_params(self.S, self.time_jump, self.time_land, self.dt), map_defect=up(lay["map_defect"]),
-                      map_rows=up(lay["map_rows"]), scale_rows=up(lay["scale_rows"]), map_hess=up(lay["map_hess"].reshape(-1)),
-                      det_const=up(lay["det_const"]), templates={})
-            self._nlp_dev = st
-        if K not in st["templates"]:
-            n_tril = self.num_vars * (self.num_vars + 1) // 2
-            st["templates"][K] = (st["det_const"][None].repeat(K, 1).contiguous(),
-                                  torch.zeros((K, n_tril), dtype=torch.float64, device=self.device))
+            st = self._nlp_dev = dict(map_defect=up(lay["map_defect"]), map_rows=up(lay["map_rows"]), scale_rows=up(lay["scale_rows"]),
+                                      map_hess=up(lay["map_hess"].reshape(-1)), det_const=up(lay["det_const"]),
+                                      jac_templates={}, tril_templates={})
         return st
+
+    def det_jacobian_values(self, lin, K):
+        """the deterministic rows' Jacobian values (K, n_det) in ``nlp_layout()``'s det_indices / det_indptr order: a copy of the
+        constant entries with the partials d_defect and d_rows of ``nlp_linearize_device`` scattered over it (three launches)"""
+        st = self._nlp_state()
+        if K not in st["jac_templates"]:
+            st["jac_templates"][K] = st["det_const"][None].repeat(K, 1).contiguous()
+        jac = st["jac_templates"][K].clone()
+        scatter_f64(lin["d_defect"].view(K, -1), st["map_defect"], jac)
+        scatter_f64(lin["d_rows"].view(K, -1), st["map_rows"], jac, st["scale_rows"])
+        return jac
+
+    def hess_tril_device(self, blocks):
+        """step blocks (K, S+1, 78) -> the tril-packed Hessian (K, nvar (nvar+1)/2) in np.tril_indices(nvar) order.  Its zeroed
+        template is O(M^2) per problem and is made here, for the callers that read hess_tril, and nowhere else"""
+        st, K = self._nlp_state(), blocks.shape[0]
+        if K not in st["tril_templates"]:
+            st["tril_templates"][K] = torch.zeros((K, self.num_vars * (self.num_vars + 1) // 2), dtype=torch.float64, device=self.device)
+        return scatter_f64(blocks.view(K, -1), st["map_hess"], st["tril_templates"][K].clone())
 
     def fold_multipliers(self, lams):
         """(K, ncon) multipliers of g -> lam_dyn (K, S, 8), lam_rows (K, S+1, 2): the no-slip and contact multipliers on the
@@ -1074,88 +1099,86 @@ class Model:
         (K, ncon) multipliers of g or None; add (K, S+1, 78) blocks added to the Hessian or None.  -> dict of fp64 DEVICE tensors:
         defect (K, S, 8), d_defect (K, S, 8, 12), rows (K, S+1, 2), d_rows (K, S+1, 2, 4), jac_values (K, nnz): the CSC values of
         the deterministic rows' Jacobian in ``nlp_layout()``'s det_indices / det_indptr order; and with lams: hess_blocks
-        (K, S+1, 78), hess_tril (K, nvar (nvar+1)/2) in np.tril_indices(nvar) order.  Four launches without lams, six with.
+        (K, S+1, 78), hess_tril (K, nvar (nvar+1)/2) in np.tril_indices(nvar) order.  Four launches without lams, six with, plus
+        one scatter for the fold (under fold='host' too, which folded on the host before and so has gained that launch).
         precision='f64' adds the risk group, from the same Z on the device (no host gather): slip_h (K, C, M), slip_rows
         (K, M C) = h in the risk rows' order i C + c, slip_jac_values (K, nnz_slip) in ``_jacobian_pattern`` order with the
         constant entries in place; with lams the slip rows' share is inside hess_blocks / hess_tril (the multipliers are read
         where they lie).  Four more launches, seven with lams.
-        fold='device' (lams a device tensor (K, ld >= ncon)): the multipliers are folded by ``fold_multipliers_device`` and
-        nothing of them is read back; hess_tril is not built (the solver reads the blocks).
+        The multipliers, uploaded first when they are a host array (K, ncon), are folded by ``fold_multipliers_device`` (a device
+        tensor may be (K, ld >= ncon)) and nothing of them is read back: ``hess_blocks_device`` is the one sequence under both
+        folds.  fold='device': hess_tril is not built (the solver reads the blocks), so its O(nvar^2) template is never made.
         ``fields`` (precision='f64' only): friction fields per problem, (a, theta, tau) each (K, 30, M), as ``slip_device_f64``
         takes them; every other row of the NLP does not depend on them."""
         if fold not in ('host', 'device'):
             raise ValueError(f"fold must be 'host' or 'device', got {fold!r}")
-        dev = self.device
+        if fields is not None and self.precision != 'f64':
+            raise ValueError("fields per problem are the fp64 slip path's: the model needs precision='f64'")
+        Zs = self._device_rows(Zs)
         if fields is not None:
-            if self.precision != 'f64':
-                raise ValueError("fields per problem are the fp64 slip path's: the model needs precision='f64'")
-            _check_fields(fields, Zs.shape[0] if isinstance(Zs, torch.Tensor) else np.atleast_2d(np.asarray(Zs)).shape[0], self.M, dev)
-        if not isinstance(Zs, torch.Tensor):
-            Zs = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(Zs, dtype=np.float64))), device=dev)
+            _check_fields(fields, Zs.shape[0], self.M, self.device)
         if Zs.dim() != 2 or Zs.shape[1] < self.num_vars:
             raise ValueError(f"Zs must be (K, >= {self.num_vars}), got {tuple(Zs.shape)}")
         K = Zs.shape[0]
-        st = self._nlp_state(K)
-        jac_t, hess_t = st["templates"][K]
-        out = nlp_linearize_device(st["params"], Zs)
-        jac = jac_t.clone()
-        scatter_f64(out["d_defect"].view(K, -1), st["map_defect"], jac)
-        scatter_f64(out["d_rows"].view(K, -1), st["map_rows"], jac, st["scale_rows"])
-        out["jac_values"] = jac
-        f64 = self.precision == 'f64'
-        if f64:                                                   # the risk group from the same Z, on the device
-            if lams is not None and not isinstance(lams, torch.Tensor):
-                lams = torch.as_tensor(np.ascontiguousarray(np.atleast_2d(np.asarray(lams, dtype=np.float64))), device=dev)
-            slip = self._slip_f64(Zs, lams if lams is None or fold == 'host' else lams[:, :self.nlp_layout()["ncon"]], fields)
+        out = nlp_linearize_device(self._slip_params(), Zs)
+        out["jac_values"] = self.det_jacobian_values(out, K)
+        lams, D = None if lams is None else self._device_rows(lams), None
+        if self.precision == 'f64':                               # the risk group from the same Z, on the device
+            slip = self._slip_f64(Zs, None if lams is None else lams[:, :self.nlp_layout()["ncon"]], fields)
             out.update(slip_h=slip["slip_h"], slip_rows=slip["slip_rows"], slip_jac_values=slip["slip_jac_values"])
-        if lams is not None and fold == 'device':
-            lam_dyn, lam_rows = self.fold_multipliers_device(lams)
-            if lam_dyn.shape[0] != K:
-                raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")
-            if f64 and self.nlp_layout()["C"] > 0:
-                add = torch.zeros((K, self.S + 1, n_pairs), dtype=torch.float64, device=dev) if add is None else add.clone()
-                self.slip_hess_blocks_device_f64(Zs, slip["D"], add)
-            out["hess_blocks"] = nlp_hessian_device(st["params"], Zs, lam_dyn, lam_rows, add)
-        elif lams is not None:
-            lam_dyn, lam_rows = self.fold_multipliers(lams.cpu().numpy() if isinstance(lams, torch.Tensor) else lams)
-            if lam_dyn.shape[0] != K:
-                raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")
+            D = slip["D"]
+        if lams is not None:
             if add is not None and not isinstance(add, torch.Tensor):
-                add = torch.as_tensor(np.ascontiguousarray(add, dtype=np.float64), device=dev)
-            if f64 and self.nlp_layout()["C"] > 0:                # the caller's add is left as it is
-                add = torch.zeros((K, self.S + 1, n_pairs), dtype=torch.float64, device=dev) if add is None else add.clone()
-                self.slip_hess_blocks_device_f64(Zs, slip["D"], add)
-            blocks = nlp_hessian_device(st["params"], Zs, torch.as_tensor(lam_dyn, device=dev),
-                                        torch.as_tensor(lam_rows, device=dev), add)
-            tril = hess_t.clone()
-            scatter_f64(blocks.view(K, -1), st["map_hess"], tril)
-            out["hess_blocks"], out["hess_tril"] = blocks, tril
+                add = torch.as_tensor(np.ascontiguousarray(add, dtype=np.float64), device=self.device)
+            out["hess_blocks"] = self.hess_blocks_device(Zs, lams, add, D)
+            if fold == 'host':
+                out["hess_tril"] = self.hess_tril_device(out["hess_blocks"])
         return out
 
-    def g(self, Z, _lin=None):
-        """:491-514: all ten groups in the script's order (float64); the risk group is ``slip_risk_constraints`` (fp32 path), or with
-        precision='f64' the fp64 slip rows of the same ``nlp_device`` call"""
-        Z = np.asarray(Z, dtype=np.float64)
+    def hess_blocks_device(self, Zs, lams, add=None, D=None, in_place=False):
+        """The step blocks of hess(lams . g) + add, (K, S+1, 78), by the one sequence every consumer runs: the multipliers lams
+        (device, (K, ld >= ncon)) folded where they lie, the slip rows' share (D (K, C, 3) of ``slip_device_f64`` on the same Zs
+        and lams; None: the fp32 path, whose share the caller has put into ``add``) added into a copy of ``add`` (K, S+1, 78)
+        -- the caller's tensor is left as it is, unless it is a scratch buffer of the caller's and ``in_place`` says so --
+        then rato_hopper_nlp_hessian.  Nothing moves to the host."""
+        K = Zs.shape[0]
+        lam_dyn, lam_rows = self.fold_multipliers_device(lams)
+        if lam_dyn.shape[0] != K:
+            raise ValueError(f"Zs and lams must hold the same K problems, got {K} and {lam_dyn.shape[0]}")
+        if D is not None and self.nlp_layout()["C"] > 0:
+            if not in_place:
+                add = torch.zeros((K, self.S + 1, n_pairs), dtype=torch.float64, device=self.device) if add is None else add.clone()
+            self.slip_hess_blocks_device_f64(Zs, D, add)
+        return nlp_hessian_device(self._slip_params(), Zs, lam_dyn, lam_rows, add)
+
+    def g_values_device(self, Zs, fields=None):
+        """what g is assembled from and nothing else, precision='f64': defect (K, S, 8) and rows (K, S+1, 2) (the linearize call
+        without its derivatives) and slip_h (K, C, M) (the slip call without its partials), device tensors; two launches"""
+        Zs = self._device_rows(Zs)
+        out = nlp_linearize_device(self._slip_params(), Zs, want=("defect", "rows"))
+        out["slip_h"] = self.slip_device_f64(Zs, want=("h",), fields=fields)["h"]
+        return out
+
+    def assemble_g(self, Z, defect, rows, slip_rows):
+        """g in the script's order (:491-514), all ten groups (float64), from what the device leaves for one problem (host
+        arrays): defect (S, 8), rows (S+1, 2) and the slip values in the risk rows' order i C + c (not read without contacts)"""
         lay = self.nlp_layout()
-        r = _lin if _lin is not None else self.nlp_device(Z[None])
-        defect, rows = r["defect"][0].cpu().numpy(), r["rows"][0].cpu().numpy()
         xs, us = self.convert_z_to_xs_us_mats(Z)
         st, tj, tl = lay["states"], self.time_jump, self.time_land
-        if lay["C"] == 0:
-            risk = self._risk_without_contacts(Z)
-        elif self.precision == 'f64':
-            risk = self._risk_rows(Z, r["slip_rows"][0].cpu().numpy())
-        else:
-            risk = self.slip_risk_constraints(Z)
+        risk = self._risk_rows(Z, slip_rows if lay["C"] > 0 else np.zeros(0))       # no contact: :339-367 with num_contacts = 0
         return np.concatenate([defect.reshape(-1), xs[0] - state_initial, (xs[-1] - state_final)[4:6], rows[st, 0], rows[st, 1],
                                -rows[tj:tl, 1], risk, us.reshape(-1), [Z[-2]], xs[1:, 3], xs[1:, 7], xs[1:, 6]])
 
-    def _risk_without_contacts(self, Z):
-        """the risk group when no step is in contact (:339-367 with num_contacts = 0)"""
-        if self.method == 'baseline':
-            return np.zeros(0)
-        _, _, ys, _, t_risk = self.convert_z_to_variables(Z)
-        return np.concatenate([[(self.M * self.alpha) * t_risk + np.sum(ys)], -ys, [0.0]])
+    def g(self, Z, _lin=None):
+        """``assemble_g`` on one ``nlp_device`` call; the slip values are the fp32 kernel's (``slip_device``), or with
+        precision='f64' the fp64 slip rows of the same call"""
+        Z = np.asarray(Z, dtype=np.float64)
+        r = _lin if _lin is not None else self.nlp_device(Z[None])
+        if self.precision == 'f64':
+            slip_rows = r["slip_rows"][0].cpu().numpy()
+        else:
+            slip_rows = self._slip_rows_host(Z) if self.nlp_layout()["C"] > 0 else None
+        return self.assemble_g(Z, r["defect"][0].cpu().numpy(), r["rows"][0].cpu().numpy(), slip_rows)
 
     def jac_g(self, Z, _lin=None):
         """jacrev(g)(Z) (:569) as a scipy CSC (ncon, nvar) in the script's row and column order, with a FIXED structural
@@ -1206,12 +1229,8 @@ class Model:
         return blocks[:, tr, tc]
 
     def _hess_add(self, Z, lam, obj_factor):
-        # precision='f64': nlp_device adds the slip share on the device
-        add = self.slip_hessian_blocks(Z, lam) if self.precision != 'f64' else np.zeros((self.S + 1, n_pairs))
-        tr, tc = np.tril_indices(n_l)
-        diag_u = np.flatnonzero((tr == tc) & ((tr == n_x) | (tr == n_x + 1)))
-        add[:self.S, diag_u] += 2.0 * float(obj_factor)          # hess_f: 2 R on u0 and u1, R = 1 (:443-448)
-        return add
+        """the fp32 slip share (precision='f64': nlp_device adds it on the device) plus the objective's blocks"""
+        return objective_blocks(self.S, obj_factor, out=self.slip_hessian_blocks(Z, lam) if self.precision != 'f64' else None)
 
     def _hess_device(self, Z, lam, obj_factor):
         Z = np.asarray(Z, dtype=np.float64)

@@ -3,7 +3,9 @@ same step as the dense one for any M.  The M variables ys enter Kc only through 
 they are eliminated exactly and the Cholesky factors the core's Schur complement (8(S+1) + 4S + 2 columns) -- the same inertia
 test, since e > 0.  ``ArrowDeviceBackend`` does the work over the samples with csrc/hopper_arrow.hip on the partials
 rato_hopper_slip_f64 leaves and the deterministic rows with ``hopper_ipm``'s ``normal_matrix`` / ``csc_matvec`` / ``csc_tmatvec`` on
-the core's pattern; ``ArrowNumpyBackend`` is its host twin.  Both keep their own factor and solve (the elimination).
+the core's pattern; ``ArrowNumpyBackend`` is its host twin.  Both keep their own factor and solve (the elimination).  The
+evaluation itself is ``hopper.Model``'s: ``ArrowDeviceBackend._evaluate`` is a call sequence over its stages that keeps the slip
+partials, and g, W x and the group's constants are ``hopper_ipm.HopperDeviceBase``'s.
 ``ArrowDeviceBackend`` has one step, written on device tensors with every line between two launches a kernel of
 csrc/hopper_arrow.hip: the ``*_t`` methods (``driver='device'``) run it on the group's arrays where they lie, and
 the list methods (``driver='host'``) upload the listed problems' vectors, run it on those problems' rows and download the result.
@@ -14,9 +16,8 @@ import numpy as np
 
 from . import hopper as _h
 from . import ipm as _ipm
-from .hopper_ipm import (GroupFields, ModelCallbacks, _hess_apply, _obj_add, _pattern_maps, arrow_einv, arrow_kkbeta, arrow_rhsfix, arrow_scale,
-                         arrow_tfix, assemble_g, csc_matvec, csc_tmatvec, normal_matrix, normal_matrix_host, scatter_rows,
-                         upload_maps)
+from .hopper_ipm import (HopperDeviceBase, ModelCallbacks, _hess_apply, _pattern_maps, arrow_einv, arrow_kkbeta, arrow_rhsfix, arrow_scale,
+                         arrow_tfix, csc_matvec, csc_tmatvec, normal_matrix, normal_matrix_host, scatter_rows, upload_maps)
 
 
 def arrow_structure(model):
@@ -231,37 +232,28 @@ class ArrowNumpyBackend(_ipm.Backend):
         return out
 
 
-class ArrowDeviceBackend(_ipm.DeviceBase):
-    """The arrowhead step on the MI355X for the problems of one group (csrc/hopper_arrow.hip on the partials rato_hopper_slip_f64
-    leaves in HBM; the core through ``hopper_ipm.normal_matrix`` on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).
-    eval_full keeps the partials: neither the slip CSC values nor the tril-packed Hessian are ever formed.  What travels per call
-    of a list method is the vectors the driver works on, up and down once; the ``*_t`` methods (the driver on the device) move
-    nothing.  The group's models may hold friction fields of their own (``hopper_ipm.GroupFields``)."""
-    name, newton = "device", "arrow"
+class ArrowDeviceBackend(HopperDeviceBase):
+    """The arrowhead step on the MI355X (csrc/hopper_arrow.hip on the partials rato_hopper_slip_f64 leaves in HBM; the core
+    through ``hopper_ipm.normal_matrix`` on the deterministic pattern and the Cholesky of ``ipm.DeviceBase``).  Its evaluation
+    is the stages of ``hopper.Model`` with the slip partials kept: neither the slip CSC values nor the tril-packed Hessian are
+    ever formed, and nothing in it grows faster than O(M C).  What travels per call of a list method is the vectors the driver
+    works on, up and down once; the ``*_t`` methods (the driver on the device) move nothing."""
+    newton = "arrow"
 
     def __init__(self, models, chol='workgroup'):
         import torch
         from . import _lib
         self._lib, self.lib = _lib, _lib.load()
-        self.models = models
-        m0 = self.m0 = models[0]
-        if any(m.precision != 'f64' for m in models):
-            raise ValueError("the device backend needs Model(..., precision='f64')")
-        super().__init__(m0.device, len(models), "reduction", "assembly", "products", chol=chol)
-        st = self.st = arrow_structure(m0)
-        lay = m0.nlp_layout()
-        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
+        super().__init__(models, "reduction", "assembly", "products", chol=chol)
+        st = self.st = arrow_structure(self.m0)
+        self.hess_st = st["hess"]
         self.maps = upload_maps(st["det"], self.dev, to_col=st["core_z"], col_ptr=st["det_indptr_z"])     # x and J'w in z numbering
-        self.maps.update(qcol=up(st["qcol"], np.int32), map_defect=up(lay["map_defect"], np.int64),
-                         map_rows=up(lay["map_rows"], np.int64), scale_rows=up(lay["scale_rows"], np.float64),
-                         det_const=up(lay["det_const"], np.float64))
-        self.params = _h.nlp_params(m0.S, m0.time_jump, m0.time_land, m0.dt)
+        self.maps["qcol"] = torch.as_tensor(np.ascontiguousarray(st["qcol"], dtype=np.int32), device=self.dev)
         self.nch = int(self.lib.rato_hopper_arrow_nchunks(st["M"]))
         self.npart = int(self.lib.rato_hopper_arrow_npart(st["C"]))
         if self.nch < 1 or self.npart < 1:
             raise ValueError(f"newton='arrow' on the device serves 1 <= C <= 50 contact steps, got C = {st['C']}")
-        self.vals0 = self.dx = self.dfz = self.hessd = self.hess_host = None
-        self.fields = GroupFields(models)
+        self.vals0 = self.dx = self.dfz = None
         n_all = len(models)
         self.e, self.d = self._empty(n_all, st["M"]), self._empty(n_all, st["ncon"])     # what a factorization keeps, by problem
         self.kk, self.beta, self.d_t = self._empty(n_all), self._empty(n_all), None       # number (d_t: the device driver's d)
@@ -269,48 +261,17 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
     def _empty(self, *shape):
         return self.torch.empty(shape, dtype=self.torch.float64, device=self.dev)
 
-    def _malpha(self, idx):
-        return np.array([self.st["M"] * float(self.models[i].alpha) for i in idx])
-
-    def _g_rows(self, idx, Zs, lin, h):
-        defect, rows = lin["defect"].cpu().numpy(), lin["rows"].cpu().numpy()
-        slip = np.ascontiguousarray(h.cpu().numpy().transpose(0, 2, 1)).reshape(len(idx), -1)          # row order i C + c
-        return [assemble_g(self.models[i], np.asarray(Z), defect[k], rows[k], slip[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
-
-    def _det_values(self, lin, K):
-        """the deterministic rows' Jacobian values (K, n_det): the constant entries, the partials of ``lin`` scattered over them"""
-        mp = self.maps
-        jac = mp["det_const"][None].repeat(K, 1).contiguous()
-        _h.scatter_f64(lin["d_defect"].view(K, -1), mp["map_defect"], jac)
-        _h.scatter_f64(lin["d_rows"].view(K, -1), mp["map_rows"], jac, mp["scale_rows"])
-        return jac
-
-    def eval_full(self, idx, Zs, lams, sfs):
-        with self.timed("callbacks"):
-            m0, K = self.m0, len(idx)
-            Zd, lamd = self._up(Zs), self._up(lams)
-            lin = _h.nlp_linearize_device(self.params, Zd)
-            jac = self._det_values(lin, K)
-            slip = m0.slip_device_f64(Zd, lamd, want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of(idx))
-            add = self._up([_obj_add(m0, sf) for sf in sfs])
-            m0.slip_hess_blocks_device_f64(Zd, slip["D"], add)
-            lam_dyn, lam_rows = m0.fold_multipliers(np.stack(lams))
-            self.hessd = _h.nlp_hessian_device(self.params, Zd, self._up(list(lam_dyn)), self._up(list(lam_rows)), add)
-            self.vals0, self.dx, self.dfz = jac, slip["dh_dx"], slip["dh_dfz"]
-            self.slot = {i: k for k, i in enumerate(idx)}
-            self.hess_host = self.hessd.cpu().numpy()
-            out = self._g_rows(idx, Zs, lin, slip["h"])
-        return out
-
-    def eval_g(self, idx, Zs):
-        with self.timed("callbacks"):
-            Zd = self._up(Zs)
-            lin = _h.nlp_linearize_device(self.params, Zd, want=("defect", "rows"))
-            out = self._g_rows(idx, Zs, lin, self.m0.slip_device_f64(Zd, want=("h",), fields=self.fields.of(idx))["h"])
-        return out
-
-    def hess_apply(self, idx, X):
-        return [_hess_apply(self.st["hess"], self.hess_host[self.slot[i]], x) for i, x in zip(idx, X)]
+    def _evaluate(self, Z, Y, add, idx):
+        """the stages of ``hopper.Model`` on device tensors Z (K, >= n) and Y (K, ld >= ncon) for the listed problems (None: the
+        whole group): leaves the deterministic rows' values, the slip partials and the step blocks of hess(Y . g) + add (``add``:
+        a scratch buffer, used in place) -> (defect, rows, slip_h), what g is assembled from"""
+        m0 = self.m0
+        lin = _h.nlp_linearize_device(m0._slip_params(), Z)
+        self.vals0 = m0.det_jacobian_values(lin, Z.shape[0])
+        slip = m0.slip_device_f64(Z, Y[:, :self.st["ncon"]], want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of(idx))
+        self.dx, self.dfz = slip["dh_dx"], slip["dh_dfz"]
+        self.hessd = m0.hess_blocks_device(Z, Y, add, slip["D"], in_place=True)
+        return lin["defect"], lin["rows"], slip["h"]
 
     # ---- the arrow step, written once on device tensors and served to both drivers.  Each function takes the arrays it reads
     # (``vals`` = (vals0, dx, dfz, hessd) of its K problems, malpha (K,)), what a factorization keeps (e (K, M), d (K, ld >= ncon),
@@ -332,14 +293,13 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
                     redr=self._empty(K, self.npart))
 
     def _work(self):
-        """the work buffers of the group, its malpha and the uploaded maps, made once"""
+        """the work buffers of the group and the uploaded maps, made once"""
         w = getattr(self, "_w", None)
         if w is None:
             st, K, torch = self.st, self.n_all, self.torch
             up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=self.dev)
             w = self._w = dict(
-                self._buffers(K), malpha=self._up([self._malpha(range(K))])[0].contiguous(),
-                add=self._empty(K, self.m0.S + 1, _h.n_pairs), qz=up(st["qz"], np.int32), core_z=up(st["core_z"], np.int64),
+                self._buffers(K), add=self._empty(K, self.m0.S + 1, _h.n_pairs), qz=up(st["qz"], np.int32), core_z=up(st["core_z"], np.int64),
                 inv_qz=up(st["inv_qz"], np.int64), inv_core_z=up(st["inv_core_z"], np.int64), inv_qcol=up(st["inv_qcol"], np.int64))
         return w
 
@@ -431,10 +391,10 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
         w = self._work()
         vals = self._rows(idx, *self._vals())
         if list(idx) == list(range(self.n_all)):
-            return (vals, w["malpha"], w) + kept
+            return (vals, self.malpha, w) + kept
         sel = self.torch.as_tensor(list(idx), device=self.dev)
         take = lambda t: t.index_select(0, sel)
-        return (vals, take(w["malpha"]), dict(w, **self._buffers(len(idx)))) + tuple(take(t) for t in kept)
+        return (vals, take(self.malpha), dict(w, **self._buffers(len(idx)))) + tuple(take(t) for t in kept)
 
     @contextlib.contextmanager
     def _waited(self):
@@ -484,53 +444,25 @@ class ArrowDeviceBackend(_ipm.DeviceBase):
 
     # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group where its
     # arrays lie, takes and returns (K, ld) tensors, waits for nothing and moves nothing to the host
-    def _g_t(self, Z, lin, h):
-        m0, st = self.m0, self.st
-        return _h.g_device(m0._slip_params(), st["M"], st["saa"], Z, lin["defect"], lin["rows"], h, (1, st["M"]),
-                           self._work()["malpha"])
-
     def eval_full_t(self, Z, Y):
-        """Z (K, n) and the multipliers Y (K, ld >= ncon), read where they lie -> g (K, ncon); leaves the deterministic rows'
-        values, the slip partials and the step blocks of hess(Y . g) for the calls below.  The objective's curvature is NOT in the
-        blocks: the driver's diagonal carries it."""
-        m0, w, K = self.m0, self._work(), Z.shape[0]
-        lin = _h.nlp_linearize_device(self.params, Z)
-        jac = self._det_values(lin, K)
-        slip = m0.slip_device_f64(Z, Y[:, :self.st["ncon"]], want=("h", "dh_dfz", "dh_dx"), fields=self.fields.of())
-        add = w["add"].zero_()
-        m0.slip_hess_blocks_device_f64(Z, slip["D"], add)
-        lam_dyn, lam_rows = m0.fold_multipliers_device(Y)
-        self.hessd = _h.nlp_hessian_device(self.params, Z, lam_dyn, lam_rows, add)
-        self.vals0, self.dx, self.dfz = jac, slip["dh_dx"], slip["dh_dfz"]
-        self.slot = {i: i for i in range(K)}
-        return self._g_t(Z, lin, slip["h"])
-
-    def eval_g_t(self, Z):
-        lin = _h.nlp_linearize_device(self.params, Z, want=("defect", "rows"))
-        return self._g_t(Z, lin, self.m0.slip_device_f64(Z, want=("h",), fields=self.fields.of())["h"])
-
-    def hess_apply_t(self, X):
-        """W x of the constraints' part alone (K, n)"""
-        return _h.block_symv(self.m0.S, self.hessd, X, self.st["n"])
+        """the base's, with the group's kept ``add`` buffer zeroed as the scratch the slip share goes into"""
+        return super().eval_full_t(Z, Y, self._work()["add"].zero_())
 
     def matvec_t(self, X):
         """X (K, ld >= n) -> J x (K, ncon)"""
         with self.timed_t("products"):
-            w = self._work()
-            return self._jx(X, self._vals(), w["malpha"], w)
+            return self._jx(X, self._vals(), self.malpha, self._work())
 
     def tmatvec_t(self, W):
         """W (K, ld >= ncon) -> J' w (K, n)"""
         with self.timed_t("products"):
-            w = self._work()
-            return self._jtw(W, self._vals(), w["malpha"], w)
+            return self._jtw(W, self._vals(), self.malpha, self._work())
 
     def factor_t(self, d, diag):
         """d (K, ld >= ncon) and diag (K, n) with the objective's curvature already in it: the core's Schur complement into the
         kept ``self.Kc``, factored in place -> info (K,) int32 device tensor.  e, kk and beta stay on the device; ``d`` is kept by
         reference for ``solve_t``."""
-        w = self._work()
-        self.Kc = self._schur(d, diag, self._vals(), w["malpha"], self.e, self.kk, self.beta, self.Kc, w)
+        self.Kc = self._schur(d, diag, self._vals(), self.malpha, self.e, self.kk, self.beta, self.Kc, self._work())
         self.d_t = d
         return self.factor_all(self.Kc)
 

@@ -7,13 +7,16 @@ redundant rows.)
 launch; 'numpy' does the whole step on the host, callbacks injected or taken one problem at a time from the Model.  The three
 kernels of csrc/hopper_ipm.hip are bound once, as ``normal_matrix``, ``csc_matvec`` and ``csc_tmatvec`` on device tensors (with
 ``upload_maps`` for their index lists): both hopper device backends, on lists and on tensors, are adapters over them, and
-``ipm.Backend`` / ``ipm.DeviceBase`` supply factor and solve.
+``ipm.Backend`` / ``ipm.DeviceBase`` supply factor and solve.  Neither backend evaluates the NLP itself: ``HopperDeviceBase``
+holds what they share (the models, ``GroupFields``, M alpha per problem, g and W x on either driver) over the stages of
+``hopper.Model``, and ``DeviceBackend`` / ``hopper_arrow.ArrowDeviceBackend`` add the slip outputs they keep, their products and
+their matrix.
 
 driver='device' (``ipm.solve_group_device``) keeps the iterate in HBM: the device backend then serves device
 tensors (eval_full_t ... normal_matrix_t below), g is assembled by rato_hopper_g_f64, W x is rato_hopper_block_symv_f64 and the
-multipliers are folded by rato_scatter_f64 (csrc/hopper_g.hip, ``Model.fold_multipliers_device``); nothing but the scalar
-record and the factorization's info comes back during an iteration.  Both Newton steps are served: the arrow backend's
-host-side fix-ups are the ``arrow_*`` bindings below.
+multipliers are folded by rato_scatter_f64 (csrc/hopper_g.hip, ``Model.fold_multipliers_device``, as under the host driver);
+nothing but the scalar record and the factorization's info comes back during an iteration.  Both Newton steps are served: the
+arrow backend's host-side fix-ups are the ``arrow_*`` bindings below.
 
 newton='arrow' (``hopper_arrow``) is the same step for any M: the M variables ys are eliminated exactly and the
 Cholesky factors the core's Schur complement; newton='dense' (the default) is the step over all variables.
@@ -129,11 +132,8 @@ def _hess_apply(st, blocks, x):
 
 
 def _obj_add(model, sf):
-    """sf hess_f as step blocks (S+1, 78): 2 R on u0 and u1, R = 1 (:443-448)"""
-    tr, tc = np.tril_indices(_h.n_l)
-    add = np.zeros((model.S + 1, _h.n_pairs))
-    add[:model.S, np.flatnonzero((tr == tc) & ((tr == _h.n_x) | (tr == _h.n_x + 1)))] = 2.0 * sf
-    return add
+    """sf hess_f as step blocks (S+1, 78): ``hopper.objective_blocks``"""
+    return _h.objective_blocks(model.S, sf)
 
 
 # ---- backends ----------------------------------------------------------------------------------------------------------------
@@ -193,14 +193,7 @@ class NumpyBackend(_ipm.Backend):
         return normal_matrix_host(self.st, self.vals[i], d, self.hess[i], diag)
 
 
-def assemble_g(model, Z, defect, rows, slip_rows):
-    """g in the script's order (:491-514) from what ``nlp_device`` leaves for one problem (host arrays)"""
-    lay = model.nlp_layout()
-    xs, us = model.convert_z_to_xs_us_mats(Z)
-    stt, tj, tl = lay["states"], model.time_jump, model.time_land
-    risk = model._risk_without_contacts(Z) if lay["C"] == 0 else model._risk_rows(Z, slip_rows)
-    return np.concatenate([defect.reshape(-1), xs[0] - _h.state_initial, (xs[-1] - _h.state_final)[4:6], rows[stt, 0], rows[stt, 1],
-                           -rows[tj:tl, 1], risk, us.reshape(-1), [Z[-2]], xs[1:, 3], xs[1:, 7], xs[1:, 6]])
+assemble_g = _h.Model.assemble_g     # (model, Z, defect, rows, slip_rows) -> g of one problem on the host; ``Model.g`` calls the same
 
 
 # ---- the kernels of csrc/hopper_ipm.hip on device fp64 tensors: each entry point is called here and nowhere else ----------------
@@ -404,51 +397,95 @@ class GroupFields:
         return tuple(t.index_select(0, sel) for t in self.stack)
 
 
-class DeviceBackend(_ipm.DeviceBase):
-    """the step on the MI355X for the problems of one group (same S, M, phases and method; alpha and the friction fields may
-    differ: models that do not share one set of fields are served from a stack of theirs, ``GroupFields``).
-    Every call serves the listed problems in ONE launch each; nothing a kernel computes for a problem depends on the others."""
+class HopperDeviceBase(_ipm.DeviceBase):
+    """What the hopper's two backends on the device share, for the problems of one group (same S, M, phases and method; alpha
+    and the friction fields may differ: models that do not share one set of fields are served from a stack of theirs,
+    ``GroupFields``): the models, M alpha per problem on the device, g on either driver from the stages of ``hopper.Model``, and
+    W x.  A subclass sets ``st`` and ``hess_st`` (the ``block_vars`` and n that ``_hess_apply`` reads) and defines
+    ``_evaluate(Z, Y, add, idx)`` on device tensors -- the call sequence over the Model's stages that leaves ``hessd`` and the
+    slip outputs it keeps, for the listed problems (None: the whole group), and returns (defect, rows, slip_h) -- then its
+    products and its matrix."""
     name = "device"
 
-    def __init__(self, models, chol='workgroup'):
+    def __init__(self, models, *more_clocks, chol='workgroup'):
         self.models = models
         m0 = self.m0 = models[0]
         if any(m.precision != 'f64' for m in models):
             raise ValueError("the device backend needs Model(..., precision='f64')")
-        super().__init__(m0.device, len(models), chol=chol)
-        st = self.st = structure(m0)
+        super().__init__(m0.device, len(models), *more_clocks, chol=chol)
         lay = m0.nlp_layout()
-        self.maps = upload_maps(st, self.dev, to_value=st["to_cat"])
-        # the one Jacobian value that depends on alpha (row 0 of the t_risk column): patched per problem after the group's call
-        self.saa = m0.method != 'baseline' and lay["C"] > 0
-        self.alpha_pos = int(lay["nnz_slip"] - 1 - m0.M * lay["C"]) if self.saa else -1
-        self.vals0 = self.vals1 = self.hessd = self.hess_host = None
+        self.Cn, self.saa = lay["C"], m0.method != 'baseline'
+        # M alpha per problem, uploaded once: the sum row of g and the one Jacobian value that depends on alpha (row 0 of the
+        # t_risk column, at ``alpha_pos`` of the slip CSC values; -1 where there is none)
+        self.malpha = torch.as_tensor([m0.M * float(m.alpha) for m in models], dtype=torch.float64, device=self.dev)
+        self.alpha_pos = int(lay["nnz_slip"] - 1 - m0.M * lay["C"]) if self.saa and lay["C"] > 0 else -1
         self.fields = GroupFields(models)
-        # for the driver on the device: M alpha per problem (the sum row of g, and the Jacobian entry above), uploaded once
-        self.malpha = torch.as_tensor([m0.M * float(m.alpha) for m in models], dtype=torch.float64, device=self.dev) \
-            if m0.method != 'baseline' else None
-
-    def _g_rows(self, idx, Zs, r):
-        defect, rows = r["defect"].cpu().numpy(), r["rows"].cpu().numpy()
-        slip = r["slip_rows"].cpu().numpy() if self.m0.nlp_layout()["C"] > 0 else [None] * len(idx)
-        return [assemble_g(self.models[i], np.asarray(Z), defect[k], rows[k], slip[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
+        self.hessd = self.hess_host = None
 
     def eval_full(self, idx, Zs, lams, sfs):
-        torch = self.torch
         with self.timed("callbacks"):
-            add = self._up([_obj_add(self.m0, sf) for sf in sfs])
-            r = self.m0.nlp_device(self._up(Zs), self._up(lams), add=add, fields=self.fields.of(idx))
-            self.vals0, self.vals1, self.hessd = r["jac_values"], r["slip_jac_values"], r["hess_blocks"]
-            if self.saa:
-                self.vals1[:, self.alpha_pos] = torch.as_tensor([self.m0.M * float(self.models[i].alpha) for i in idx],
-                                                                dtype=torch.float64, device=self.dev)
+            parts = self._evaluate(self._up(Zs), self._up(lams), self._up([_obj_add(self.m0, sf) for sf in sfs]), idx)
             self.slot = {i: k for k, i in enumerate(idx)}
             self.hess_host = self.hessd.cpu().numpy()
-            return self._g_rows(idx, Zs, r)
+            return self._g_rows(idx, Zs, *parts)
+
+    def _g_rows(self, idx, Zs, defect, rows, slip_h):
+        """g of the listed problems as host vectors, from the device tensors defect (K, S, 8), rows (K, S+1, 2) and the slip
+        values h (K, C, M), ordered i C + c here on the host"""
+        defect, rows = defect.cpu().numpy(), rows.cpu().numpy()
+        slip = np.ascontiguousarray(slip_h.cpu().numpy().transpose(0, 2, 1)).reshape(len(idx), self.m0.M * self.Cn)
+        return [assemble_g(self.models[i], np.asarray(Z), defect[k], rows[k], slip[k]) for k, (i, Z) in enumerate(zip(idx, Zs))]
 
     def eval_g(self, idx, Zs):
         with self.timed("callbacks"):
-            return self._g_rows(idx, Zs, self.m0.nlp_device(self._up(Zs), fields=self.fields.of(idx)))
+            r = self.m0.g_values_device(self._up(Zs), self.fields.of(idx))
+            return self._g_rows(idx, Zs, r["defect"], r["rows"], r["slip_h"])
+
+    def hess_apply(self, idx, X):
+        return [_hess_apply(self.hess_st, self.hess_host[self.slot[i]], x) for i, x in zip(idx, X)]
+
+    # ---- the same on device tensors, for ``ipm.solve_group_device``: the whole group, nothing waits or moves to the host
+    def eval_full_t(self, Z, Y, add=None):
+        """Z (K, n) and the multipliers Y (K, ld >= ncon), read where they lie -> g (K, ncon); leaves what the subclass keeps of
+        the evaluation and the step blocks of hess(Y . g) for its other calls.  The objective's curvature is NOT in the blocks:
+        the driver's diagonal carries it."""
+        parts = self._evaluate(Z, Y, add, None)
+        self.slot = {i: i for i in range(Z.shape[0])}
+        return self._g_t(Z, *parts)
+
+    def _g_t(self, Z, defect, rows, slip_h):
+        m0 = self.m0
+        return _h.g_device(m0._slip_params(), m0.M, self.saa, Z, defect, rows, slip_h if self.Cn > 0 else None, (1, m0.M), self.malpha)
+
+    def eval_g_t(self, Z):
+        r = self.m0.g_values_device(Z, self.fields.of())
+        return self._g_t(Z, r["defect"], r["rows"], r["slip_h"])
+
+    def hess_apply_t(self, X):
+        """W x of the constraints' part alone (K, n): the objective's sf curv x is added where the result is used
+        (csrc/ipm_driver.hip)"""
+        return _h.block_symv(self.m0.S, self.hessd, X, self.st["n"])
+
+
+class DeviceBackend(HopperDeviceBase):
+    """the dense step on the MI355X: the slip CSC values are kept next to the deterministic rows', and the normal matrix is
+    J' D J + W over all variables.  Every call serves the listed problems in ONE launch each; nothing a kernel computes for a
+    problem depends on the others."""
+
+    def __init__(self, models, chol='workgroup'):
+        super().__init__(models, chol=chol)
+        st = self.st = self.hess_st = structure(self.m0)
+        self.maps = upload_maps(st, self.dev, to_value=st["to_cat"])
+        self.vals0 = self.vals1 = None
+
+    def _evaluate(self, Z, Y, add, idx):
+        """``nlp_device`` on device tensors for the listed problems (None: the whole group): keeps both value arrays, with M alpha
+        patched in per problem, and the step blocks -> (defect, rows, slip_h), what g is assembled from"""
+        r = self.m0.nlp_device(Z, Y, add=add, fold='device', fields=self.fields.of(idx))
+        self.vals0, self.vals1, self.hessd = r["jac_values"], r["slip_jac_values"], r["hess_blocks"]
+        if self.alpha_pos >= 0:
+            self.vals1[:, self.alpha_pos] = self.malpha if idx is None else self.malpha[list(idx)]
+        return r["defect"], r["rows"], r["slip_h"]
 
     def set_values(self, vals, hess):
         """install given Jacobian values (K, nnz) on the full CSC pattern and step blocks (K, S+1, 78) as the current
@@ -459,9 +496,6 @@ class DeviceBackend(_ipm.DeviceBase):
         self.hess_host = np.ascontiguousarray(hess, dtype=np.float64)
         self.hessd = self._up(self.hess_host)
         self.slot = {i: i for i in range(vals.shape[0])}
-
-    def hess_apply(self, idx, X):
-        return [_hess_apply(self.st, self.hess_host[self.slot[i]], x) for i, x in zip(idx, X)]
 
     def _sel(self, idx):
         return self._rows(idx, self.vals0, self.vals1, self.hessd)
@@ -481,26 +515,8 @@ class DeviceBackend(_ipm.DeviceBase):
         return normal_matrix(self.st["n"], self.st["ncon"], self.maps, v0, v1, d, hs if with_hess else None, dg, out=out)
 
     # ---- the same on device tensors, for ``ipm.solve_group_device``: every call serves the whole group, takes and returns
-    # (K, ld) tensors, waits for nothing and moves nothing to the host.  ``factor_t`` and ``solve_t`` are DeviceBase's.
-    def _g_t(self, Z, r):
-        m0 = self.m0
-        Cn = m0.nlp_layout()["C"]
-        return _h.g_device(m0._slip_params(), m0.M, m0.method != 'baseline', Z, r["defect"], r["rows"],
-                           r["slip_rows"] if Cn > 0 else None, (Cn, 1), self.malpha)
-
-    def eval_full_t(self, Z, Y):
-        """Z (K, n) and the multipliers Y (K, ld >= ncon) -> g (K, ncon); leaves the Jacobian's values and the step blocks of
-        hess(Y . g) for the calls below.  The objective's curvature is NOT in the blocks: the driver's diagonal carries it."""
-        r = self.m0.nlp_device(Z, Y, fold='device', fields=self.fields.of())
-        self.vals0, self.vals1, self.hessd = r["jac_values"], r["slip_jac_values"], r["hess_blocks"]
-        if self.saa:
-            self.vals1[:, self.alpha_pos] = self.malpha
-        self.slot = {i: i for i in range(Z.shape[0])}
-        return self._g_t(Z, r)
-
-    def eval_g_t(self, Z):
-        return self._g_t(Z, self.m0.nlp_device(Z, fields=self.fields.of()))
-
+    # (K, ld) tensors, waits for nothing and moves nothing to the host.  ``factor_t`` and ``solve_t`` are DeviceBase's, the
+    # evaluation and W x HopperDeviceBase's.
     def matvec_t(self, X):
         """X (K, ld >= n) -> J x (K, ncon)"""
         return csc_matvec(self.st, self.maps, self.vals0, self.vals1, X)
@@ -508,11 +524,6 @@ class DeviceBackend(_ipm.DeviceBase):
     def tmatvec_t(self, W):
         """W (K, ld >= ncon) -> J' w (K, n)"""
         return csc_tmatvec(self.st, self.maps, self.vals0, self.vals1, W)
-
-    def hess_apply_t(self, X):
-        """W x of the constraints' part alone (K, n): the objective's sf curv x is added where the result is used
-        (csrc/ipm_driver.hip)"""
-        return _h.block_symv(self.m0.S, self.hessd, X, self.st["n"])
 
     def normal_matrix_t(self, d, diag, out=None):
         """d (K, ld >= ncon), diag (K, n) with the objective's curvature already in it -> Kc (K, n, lda)"""

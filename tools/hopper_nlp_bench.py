@@ -67,16 +67,13 @@ def main():
         lams = np.random.RandomState(3).uniform(-1, 1, (K, ncon))
         Zd = torch.as_tensor(Zs, device=m.device)
         lam_dyn, lam_rows = (torch.as_tensor(a, device=m.device) for a in m.fold_multipliers(lams))
-        st = m._nlp_state(K)
-        p, (jac_t, hess_t) = st["params"], st["templates"][K]
+        p = m._slip_params()
         lin = hopper.nlp_linearize_device(p, Zd)
         blocks = hopper.nlp_hessian_device(p, Zd, lam_dyn, lam_rows)
 
-        def emit():
-            jac, tril = jac_t.clone(), hess_t.clone()
-            hopper.scatter_f64(lin["d_defect"].view(K, -1), st["map_defect"], jac)
-            hopper.scatter_f64(lin["d_rows"].view(K, -1), st["map_rows"], jac, st["scale_rows"])
-            hopper.scatter_f64(blocks.view(K, -1), st["map_hess"], tril)
+        def emit():                                                  # the two stages of the emission, their templates made once
+            m.det_jacobian_values(lin, K)
+            m.hess_tril_device(blocks)
         out["linearize"][f"K{K}"] = time_call(lambda: hopper.nlp_linearize_device(p, Zd), args.reps, args.rounds)
         out["hessian"][f"K{K}"] = time_call(lambda: hopper.nlp_hessian_device(p, Zd, lam_dyn, lam_rows), args.reps, args.rounds)
         out["emission"][f"K{K}"] = time_call(emit, args.reps, args.rounds)
