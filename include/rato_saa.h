@@ -99,7 +99,8 @@ extern "C" {
  * rato_car_rows_plan -- a further addition within version 12: the row kernels' launch geometry as a query;
  * rato_hopper_slip_f64 / rato_hopper_slip_f64_nblocks / rato_hopper_slip_hess_blocks_f64 -- likewise: the hopper's slip rows in fp64;
  * rato_hopper_slip_f64_fields -- likewise: the same with friction fields per problem;
- * rato_risk_stats_shaped -- likewise: the selection at the workgroup sizes of the launches that carry their statistics).
+ * rato_risk_stats_shaped -- likewise: the selection at the workgroup sizes of the launches that carry their statistics;
+ * rato_risk_stats_rows / _rows_init / _rows_workspace_bytes / _rows_plan -- likewise: K rows, each with its own alpha, at any M).
  * The Python binding refuses a library that reports another version. */
 #define RATO_ABI_VERSION 12
 #define RATO_STATS_IN_LAUNCH 1   /* params.stats_flags */
@@ -289,6 +290,33 @@ int rato_drone_obstacle_constraints_metric(const rato_drone_params* p, int32_t m
 /* the records of K rows of Z [K][ldz] -> out [K][RATO_N_STATS] (one launch while M <= 12,288) */
 int rato_risk_stats_batch(const float* Z, int64_t M, int64_t ldz, int32_t K, double alpha, float thr, void* workspace,
                           size_t workspace_bytes, double* out, void* stream);
+
+/* The records of K rows of Z [K][ldz], row k at its OWN alphas[k] (ABI 12, additive): the K selections behind a batched
+ * rollout whatever the alphas of its rows are and whatever M is.  alphas is a DEVICE array of K doubles -- nothing is
+ * uploaded, every workgroup ranks its row itself by the host rule (floor(alpha * (double)M), M - that - 1, the wrap to
+ * the maximum: IEEE-exact on both sides), and the call can be captured.
+ *   M <= 12,288: ONE launch of K workgroups; the workspace is not read (it may be NULL).
+ *   beyond:      FIVE stream-ordered launches over (workgroups of a row) x (rows) -- the launch-per-pass form, which waits
+ *                for nothing and needs no co-residency -- on K workspaces, one per row
+ *                (rato_risk_stats_rows_workspace_bytes; rato_risk_stats_rows_init zeroes and tags every one that fits).
+ * Guarantees:
+ *   - while M <= 12,288 row k is, to the bit and in all RATO_N_STATS entries, rato_risk_stats(Z_k, M, alphas[k]);
+ *   - beyond, row k is, to the bit and in all entries, rato_risk_stats_recover(Z_k, M, alphas[k]): the same workgroups per
+ *     row, the same fold, the same bits.  Hence it equals rato_risk_stats exactly in VaR, fraction, max, count, rank,
+ *     #{Z > t}, #{Z == t} and t, and to summation order in mean, tail sum and CVaR;
+ *   - an alphas[k] outside (0, 1], or NaN, gives row k a NaN record and disturbs no other row; that row's histograms are
+ *     left zeroed like every other's.  A workspace that was never initialised gives NaN records in every row;
+ *   - nothing is read beyond column M of a row; deterministic run to run (integer atomics, fixed-order fp64 folds).
+ * RATO_EINVAL before any launch: Z, alphas or out NULL; K < 1 or K > 65535; M <= 0 or M >= 2^32 - 1; ldz < M; beyond
+ * 12,288 a workspace that is NULL or smaller than rato_risk_stats_rows_workspace_bytes(M, K). */
+size_t rato_risk_stats_rows_workspace_bytes(int64_t M, int32_t K);   /* K workspaces beyond the one-workgroup form; 0 below */
+int rato_risk_stats_rows_init(void* workspace, size_t workspace_bytes, void* stream);
+int rato_risk_stats_rows(const float* Z, int64_t M, int64_t ldz, int32_t K, const double* alphas /* device [K] */, float thr,
+                         void* workspace, size_t workspace_bytes, double* out /* [K][RATO_N_STATS] */, void* stream);
+/* host only, nothing is launched: the number of launches of the call (1 or 5) and the workgroups per row of each
+ * (1 in the one-workgroup form; beyond, the single-row rule: 4 elements per thread up to 256 workgroups, then 16, floor
+ * 256, cap 1024).  Either pointer may be NULL. */
+int rato_risk_stats_rows_plan(int64_t M, int32_t K, int32_t* launches, int32_t* blocks_per_row);
 
 /* ---------------------------------------------------------------- driving */
 

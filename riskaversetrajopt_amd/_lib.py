@@ -278,6 +278,11 @@ SIGNATURES = {
                                       c_float_p, C.c_int64, C.c_double, C.c_float, C.c_void_p, C.c_size_t, c_float_p, c_stream]),
     "rato_risk_stats_batch": (C.c_int, [c_float_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_float, C.c_void_p,
                                         C.c_size_t, c_float_p, c_stream]),
+    "rato_risk_stats_rows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "rato_risk_stats_rows_init": (C.c_int, [C.c_void_p, C.c_size_t, c_stream]),
+    "rato_risk_stats_rows": (C.c_int, [c_float_p, C.c_int64, C.c_int64, C.c_int32, c_float_p, C.c_float, C.c_void_p,
+                                       C.c_size_t, c_float_p, c_stream]),
+    "rato_risk_stats_rows_plan": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rato_car_eval_stats_in_launch": (C.c_int, [C.c_int32]),
     "rato_car_stats_in_launch": (C.c_int, [C.c_int32, C.c_int32]),
     "rato_risk_stats_recover": (C.c_int, [c_float_p, C.c_int64, C.c_double, C.c_float, C.c_void_p, C.c_size_t,

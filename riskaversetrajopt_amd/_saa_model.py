@@ -119,6 +119,28 @@ class SaaModel:
         o["_Zb"], o["_recb"], o["_wsb"] = Z, rec, workspace
         return Z, rec, workspace
 
+    def _check_alphas(self, alpha, alphas, K):
+        """``eval_batch_device(alphas=...)``: K entries, and no scalar ``alpha`` beside them"""
+        if alpha is not None:
+            raise ValueError("pass either alpha (one for every row) or alphas (one per row), not both")
+        n = alphas.numel() if isinstance(alphas, torch.Tensor) else len(alphas)
+        if n != K:
+            raise ValueError(f"alphas has {n} entries for {K} control sequences")
+
+    def _rows_records(self, o, Z, M, alphas, workspace):
+        """The records of the rows of Z [K][ld], row k at alphas[k] (rato_risk_stats_rows behind the rollouts' launch);
+        the record buffer and the rows workspace are kept in ``o``"""
+        K = Z.shape[0]
+        rec = o.get("_recrows")
+        if rec is None or tuple(rec.shape) != (K, stats.N_STATS):
+            rec = torch.empty((K, stats.N_STATS), dtype=torch.float64, device=self.device)
+        if workspace is None and o.get("_wsrows_shape") == (M, K):
+            workspace = o.get("_wsrows")
+        if workspace is None:
+            workspace = stats.new_rows_workspace(M, K, self.device)
+        o["_recrows"], o["_wsrows"], o["_wsrows_shape"] = rec, workspace, (M, K)
+        return stats.risk_stats_rows_device(Z, alphas, workspace=workspace, out=rec, M=M)
+
     def _fused_step(self, us_mat, alpha, M, workspace, stats_out, **kw):
         """``step_device`` where the linearize launch computes the statistics of its own Z: -> (result dict, record)"""
         if workspace is None:

@@ -94,6 +94,189 @@ __device__ void flush_hist(unsigned* lds_hist, unsigned* __restrict__ ghist) {
   }
 }
 
+// ---- The launch-per-pass form: five stream-ordered launches (three histogram passes, the tail sums, the fold), the
+// kernel boundary being the only hand-off -- no workgroup waits for another, integer atomics only.  The bodies of
+// stats.hip's rs_pass1 / rs_pass2 / rs_pass3 / rs_tail / rs_final (one row: workgroup bid = blockIdx.x of nblk =
+// gridDim.x) and of the K-row grid of stats_rows.hip (row blockIdx.y with its own Workspace, bid = blockIdx.x of nblk =
+// gridDim.x): written once, so that a row of the grid is the single-row call to the bit.  RATO_BLOCK threads.
+
+// workgroups per row: 4 elements per thread up to 256 workgroups, then more elements per thread (every workgroup flushes
+// its LDS histogram with global atomics: at M ~ 1e6 of CLUSTERED values 1000 workgroups hammering the same few bins
+// cost 60 us per call, 256 workgroups 33 us; tools/stats_time.py), capped at RS_MAX_BLOCKS for very large M.
+inline long rs_pass_blocks(int64_t M) {
+  long nb = ((long)M + RATO_BLOCK * 4 - 1) / (RATO_BLOCK * 4);
+  if (nb > 256) {
+    nb = ((long)M + RATO_BLOCK * 16 - 1) / (RATO_BLOCK * 16);
+    if (nb < 256) nb = 256;
+  }
+  if (nb > RS_MAX_BLOCKS) nb = RS_MAX_BLOCKS;
+  if (nb < 1) nb = 1;
+  return nb;
+}
+
+__device__ __forceinline__ void rs_pass1_body(const float* __restrict__ Z, long M, float thr, Workspace* __restrict__ ws,
+                                              int bid, int nblk) {
+  __shared__ unsigned h[B1];
+  __shared__ double red[3][RATO_BLOCK / RATO_WAVE];
+  for (int i = threadIdx.x; i < B1; i += RATO_BLOCK) h[i] = 0;
+  __syncthreads();
+  double sum = 0.0, cnt = 0.0;
+  float mx = -INFINITY;
+  for (long i = (long)bid * RATO_BLOCK + threadIdx.x; i < M; i += (long)nblk * RATO_BLOCK) {
+    const float z = Z[i];
+    atomicAdd(&h[key_of(z) >> 21], 1u);
+    sum += (double)z;
+    cnt += (z <= thr) ? 1.0 : 0.0;
+    mx = fmaxf(mx, z);
+  }
+  flush_hist<B1>(h, ws->hist1);
+  sum = rato::wave_sum(sum);
+  cnt = rato::wave_sum(cnt);
+  mx = rato::wave_max(mx);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][wave] = sum;
+    red[1][wave] = cnt;
+    red[2][wave] = (double)mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0, c = 0, m = -INFINITY;
+    for (int w = 0; w < RATO_BLOCK / RATO_WAVE; ++w) {
+      s += red[0][w];
+      c += red[1][w];
+      m = fmax(m, red[2][w]);
+    }
+    ws->blockpart[bid][0] = s;
+    ws->blockpart[bid][1] = c;
+    ws->blockpart[bid][2] = m;
+  }
+}
+
+__device__ __forceinline__ void rs_pass2_body(const float* __restrict__ Z, long M, unsigned k, Workspace* __restrict__ ws,
+                                              int bid, int nblk) {
+  __shared__ unsigned h[B2];
+  for (int i = threadIdx.x; i < B2; i += RATO_BLOCK) h[i] = 0;
+  unsigned b1, k1;
+  find_bin<B1>(ws->hist1, k, b1, k1);
+  for (long i = (long)bid * RATO_BLOCK + threadIdx.x; i < M; i += (long)nblk * RATO_BLOCK) {
+    const unsigned key = key_of(Z[i]);
+    if ((key >> 21) == b1) atomicAdd(&h[(key >> 10) & (B2 - 1)], 1u);
+  }
+  flush_hist<B2>(h, ws->hist2);
+}
+
+__device__ __forceinline__ void rs_pass3_body(const float* __restrict__ Z, long M, unsigned k, Workspace* __restrict__ ws,
+                                              int bid, int nblk) {
+  __shared__ unsigned h[B3];
+  for (int i = threadIdx.x; i < B3; i += RATO_BLOCK) h[i] = 0;
+  unsigned b1, k1, b2, k2;
+  find_bin<B1>(ws->hist1, k, b1, k1);
+  find_bin<B2>(ws->hist2, k1, b2, k2);
+  const unsigned prefix = (b1 << 11) | b2;
+  for (long i = (long)bid * RATO_BLOCK + threadIdx.x; i < M; i += (long)nblk * RATO_BLOCK) {
+    const unsigned key = key_of(Z[i]);
+    if ((key >> 10) == prefix) atomicAdd(&h[key & (B3 - 1)], 1u);
+  }
+  flush_hist<B3>(h, ws->hist3);
+}
+
+__device__ __forceinline__ void rs_tail_body(const float* __restrict__ Z, long M, unsigned k, Workspace* __restrict__ ws,
+                                             int bid, int nblk) {
+  __shared__ double red[3][RATO_BLOCK / RATO_WAVE];
+  unsigned b1, k1, b2, k2, b3, k3;
+  find_bin<B1>(ws->hist1, k, b1, k1);
+  find_bin<B2>(ws->hist2, k1, b2, k2);
+  find_bin<B3>(ws->hist3, k2, b3, k3);
+  const float t = value_of((b1 << 21) | (b2 << 10) | b3);
+  double tail = 0.0, ngt = 0.0, neq = 0.0;
+  for (long i = (long)bid * RATO_BLOCK + threadIdx.x; i < M; i += (long)nblk * RATO_BLOCK) {
+    const float z = Z[i];
+    tail += (z > t) ? ((double)z - (double)t) : 0.0;
+    ngt += (z > t) ? 1.0 : 0.0;
+    neq += (z == t) ? 1.0 : 0.0;
+  }
+  tail = rato::wave_sum(tail);
+  ngt = rato::wave_sum(ngt);
+  neq = rato::wave_sum(neq);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = tail;
+    red[1][threadIdx.x >> 6] = ngt;
+    red[2][threadIdx.x >> 6] = neq;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0, g = 0, e = 0;
+    for (int w = 0; w < RATO_BLOCK / RATO_WAVE; ++w) {
+      s += red[0][w];
+      g += red[1][w];
+      e += red[2][w];
+    }
+    ws->blockpart[bid][3] = s;
+    ws->blockpart[bid][4] = g;
+    ws->blockpart[bid][5] = e;
+    if (bid == 0) ws->tstar = t;
+  }
+}
+
+// One workgroup per row.  valid == false (the K-row grid: a row whose alpha is outside (0, 1]; its passes were skipped):
+// the histograms are zeroed all the same and the record is NaN.
+__device__ __forceinline__ void rs_final_body(long M, double alpha, unsigned k, int var_is_max, int nblocks,
+                                              Workspace* __restrict__ ws, double* __restrict__ out, bool valid) {
+  // leaves the three histograms zeroed for the next call (the workspace starts zeroed: rato_risk_stats_init), so a
+  // call is 5 launches instead of 6
+  // (zeroed by a kernel rather than hipMemsetAsync: memset nodes of this size did not replay correctly inside a
+  // captured hipGraph on ROCm 7.2)
+  const bool ok = valid && ws->magic == RS_MAGIC;
+  for (int i = threadIdx.x; i < B1 + B2 + B3; i += RATO_BLOCK) ws->hist1[i] = 0;   // hist1..3 are contiguous
+  if (!ok) {   // never initialised: the histograms held garbage -> fail loudly instead of returning numbers
+    if (threadIdx.x < RATO_N_STATS) out[threadIdx.x] = __longlong_as_double(0x7ff8000000000000LL);
+    return;
+  }
+  if (threadIdx.x >= RATO_WAVE) return;
+  // one wave: lane i folds blocks i, i+64, ... in order, then a fixed shuffle tree (deterministic)
+  const int lane = threadIdx.x;
+  double s = 0, c = 0, m = -INFINITY, tail = 0, ngt = 0, neq = 0;
+  for (int b = lane; b < nblocks; b += RATO_WAVE) {
+    s += ws->blockpart[b][0];
+    c += ws->blockpart[b][1];
+    m = fmax(m, ws->blockpart[b][2]);
+    tail += ws->blockpart[b][3];
+    ngt += ws->blockpart[b][4];
+    neq += ws->blockpart[b][5];
+  }
+  s = rato::wave_sum(s);
+  c = rato::wave_sum(c);
+  tail = rato::wave_sum(tail);
+  ngt = rato::wave_sum(ngt);
+  neq = rato::wave_sum(neq);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, RATO_WAVE));
+  if (lane != 0) return;
+  const double t = (double)ws->tstar;
+  // VaR = sort(Z)[M - floor(alpha M) - 1]; when floor(alpha M) == M the reference's
+  // index is -1, which NumPy wraps to the LAST element (drone_main_plot.py:651).
+  out[0] = var_is_max ? m : t;
+  out[1] = t + (tail / (double)M) / alpha;     // CVaR (drone_risk.py:694)
+  out[2] = c / (double)M;                      // fraction satisfied
+  out[3] = s / (double)M;
+  out[4] = m;
+  out[5] = c;
+  out[6] = tail;
+  out[7] = (double)k;
+  out[8] = ngt;                                // #{Z > t}
+  out[9] = neq;                                // #{Z == t}
+  out[10] = t;                                 // the Rockafellar-Uryasev minimiser itself (== out[0] unless var_is_max)
+}
+
+// one workgroup (RATO_BLOCK threads): zero the whole workspace, then tag it
+__device__ __forceinline__ void rs_init_body(Workspace* __restrict__ ws) {
+  unsigned* w = reinterpret_cast<unsigned*>(ws);
+  const int n = (int)(sizeof(Workspace) / sizeof(unsigned));
+  for (int i = threadIdx.x; i < n; i += RATO_BLOCK) w[i] = 0;
+  __syncthreads();
+  if (threadIdx.x == 0) ws->magic = RS_MAGIC;
+}
 
 // Companion launches: every workgroup waits (thread 0 polls, bounded by the clock like find_bin_coop) until the
 // producer has raised `flag`; -> false when the wait expired (the caller then reports NaN statistics).
@@ -122,6 +305,7 @@ __device__ bool wait_signal(unsigned* flag) {
 
 
 constexpr long RS_SMALL_MAX = 12 * 1024;   // crossover with the cooperative form: 14.0 vs 14.7 us at M = 1e4, 19.1 vs 15.6 us at M = 2e4
+constexpr int RS1_T = 1024;                                       // threads of the stand-alone one-workgroup form (stats.hip: rs_small)
 constexpr int RS_COOP_KEYS = 16;                                  // keys per thread (registers)
 constexpr int RS_COOP_MAX_WG = 64;
 
@@ -607,7 +791,9 @@ struct StatsTail {
 };
 
 // ascending 0-based rank of sort(Z)[M - floor(alpha M) - 1] (drone_main_plot.py:649-651); alpha M == M wraps to the maximum
-inline void stats_rank(int64_t M, double alpha, unsigned& k, int& var_is_max) {
+// (host and device: the K-row grid of stats_rows.hip ranks every row from its own alpha in the kernel -- one product, one
+//  floor and integer arithmetic, so both sides give the same k)
+__host__ __device__ inline void stats_rank(int64_t M, double alpha, unsigned& k, int& var_is_max) {
   long xth = (long)floor(alpha * (double)M);
   long kk = (long)M - xth - 1;
   var_is_max = 0;

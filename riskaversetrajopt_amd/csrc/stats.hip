@@ -119,157 +119,31 @@ __global__ __launch_bounds__(RATO_BLOCK) void count_nonfinite_kernel(const float
 }
 
 // ------------------------------------------------------------- risk stats
+// The launch-per-pass form of the selection: the bodies live in rato_select.h (rs_pass1_body .. rs_final_body), shared
+// with the K-row grid of stats_rows.hip.  Here: one row, workgroup blockIdx.x of gridDim.x.
 __global__ __launch_bounds__(RATO_BLOCK) void rs_pass1(const float* __restrict__ Z, long M, float thr,
                                                        Workspace* __restrict__ ws) {
-  __shared__ unsigned h[B1];
-  __shared__ double red[3][RATO_BLOCK / RATO_WAVE];
-  for (int i = threadIdx.x; i < B1; i += RATO_BLOCK) h[i] = 0;
-  __syncthreads();
-  double sum = 0.0, cnt = 0.0;
-  float mx = -INFINITY;
-  for (long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x; i < M; i += (long)gridDim.x * RATO_BLOCK) {
-    const float z = Z[i];
-    atomicAdd(&h[key_of(z) >> 21], 1u);
-    sum += (double)z;
-    cnt += (z <= thr) ? 1.0 : 0.0;
-    mx = fmaxf(mx, z);
-  }
-  flush_hist<B1>(h, ws->hist1);
-  sum = rato::wave_sum(sum);
-  cnt = rato::wave_sum(cnt);
-  mx = rato::wave_max(mx);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wave] = sum;
-    red[1][wave] = cnt;
-    red[2][wave] = (double)mx;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0, c = 0, m = -INFINITY;
-    for (int w = 0; w < RATO_BLOCK / RATO_WAVE; ++w) {
-      s += red[0][w];
-      c += red[1][w];
-      m = fmax(m, red[2][w]);
-    }
-    ws->blockpart[blockIdx.x][0] = s;
-    ws->blockpart[blockIdx.x][1] = c;
-    ws->blockpart[blockIdx.x][2] = m;
-  }
+  rs_pass1_body(Z, M, thr, ws, (int)blockIdx.x, (int)gridDim.x);
 }
 
 __global__ __launch_bounds__(RATO_BLOCK) void rs_pass2(const float* __restrict__ Z, long M, unsigned k,
                                                        Workspace* __restrict__ ws) {
-  __shared__ unsigned h[B2];
-  for (int i = threadIdx.x; i < B2; i += RATO_BLOCK) h[i] = 0;
-  unsigned b1, k1;
-  find_bin<B1>(ws->hist1, k, b1, k1);
-  for (long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x; i < M; i += (long)gridDim.x * RATO_BLOCK) {
-    const unsigned key = key_of(Z[i]);
-    if ((key >> 21) == b1) atomicAdd(&h[(key >> 10) & (B2 - 1)], 1u);
-  }
-  flush_hist<B2>(h, ws->hist2);
+  rs_pass2_body(Z, M, k, ws, (int)blockIdx.x, (int)gridDim.x);
 }
 
 __global__ __launch_bounds__(RATO_BLOCK) void rs_pass3(const float* __restrict__ Z, long M, unsigned k,
                                                        Workspace* __restrict__ ws) {
-  __shared__ unsigned h[B3];
-  for (int i = threadIdx.x; i < B3; i += RATO_BLOCK) h[i] = 0;
-  unsigned b1, k1, b2, k2;
-  find_bin<B1>(ws->hist1, k, b1, k1);
-  find_bin<B2>(ws->hist2, k1, b2, k2);
-  const unsigned prefix = (b1 << 11) | b2;
-  for (long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x; i < M; i += (long)gridDim.x * RATO_BLOCK) {
-    const unsigned key = key_of(Z[i]);
-    if ((key >> 10) == prefix) atomicAdd(&h[key & (B3 - 1)], 1u);
-  }
-  flush_hist<B3>(h, ws->hist3);
+  rs_pass3_body(Z, M, k, ws, (int)blockIdx.x, (int)gridDim.x);
 }
 
 __global__ __launch_bounds__(RATO_BLOCK) void rs_tail(const float* __restrict__ Z, long M, unsigned k,
                                                       Workspace* __restrict__ ws) {
-  __shared__ double red[3][RATO_BLOCK / RATO_WAVE];
-  unsigned b1, k1, b2, k2, b3, k3;
-  find_bin<B1>(ws->hist1, k, b1, k1);
-  find_bin<B2>(ws->hist2, k1, b2, k2);
-  find_bin<B3>(ws->hist3, k2, b3, k3);
-  const float t = value_of((b1 << 21) | (b2 << 10) | b3);
-  double tail = 0.0, ngt = 0.0, neq = 0.0;
-  for (long i = (long)blockIdx.x * RATO_BLOCK + threadIdx.x; i < M; i += (long)gridDim.x * RATO_BLOCK) {
-    const float z = Z[i];
-    tail += (z > t) ? ((double)z - (double)t) : 0.0;
-    ngt += (z > t) ? 1.0 : 0.0;
-    neq += (z == t) ? 1.0 : 0.0;
-  }
-  tail = rato::wave_sum(tail);
-  ngt = rato::wave_sum(ngt);
-  neq = rato::wave_sum(neq);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = tail;
-    red[1][threadIdx.x >> 6] = ngt;
-    red[2][threadIdx.x >> 6] = neq;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0, g = 0, e = 0;
-    for (int w = 0; w < RATO_BLOCK / RATO_WAVE; ++w) {
-      s += red[0][w];
-      g += red[1][w];
-      e += red[2][w];
-    }
-    ws->blockpart[blockIdx.x][3] = s;
-    ws->blockpart[blockIdx.x][4] = g;
-    ws->blockpart[blockIdx.x][5] = e;
-    if (blockIdx.x == 0) ws->tstar = t;
-  }
+  rs_tail_body(Z, M, k, ws, (int)blockIdx.x, (int)gridDim.x);
 }
 
 __global__ __launch_bounds__(RATO_BLOCK) void rs_final(long M, double alpha, unsigned k, int var_is_max, int nblocks,
                                                         Workspace* __restrict__ ws, double* __restrict__ out) {
-  // leaves the three histograms zeroed for the next call (the workspace starts zeroed: rato_risk_stats_init), so a
-  // call is 5 launches instead of 6
-  // (zeroed by a kernel rather than hipMemsetAsync: memset nodes of this size did not replay correctly inside a
-  // captured hipGraph on ROCm 7.2)
-  const bool ok = ws->magic == RS_MAGIC;
-  for (int i = threadIdx.x; i < B1 + B2 + B3; i += RATO_BLOCK) ws->hist1[i] = 0;   // hist1..3 are contiguous
-  if (!ok) {   // never initialised: the histograms held garbage -> fail loudly instead of returning numbers
-    if (threadIdx.x < RATO_N_STATS) out[threadIdx.x] = __longlong_as_double(0x7ff8000000000000LL);
-    return;
-  }
-  if (threadIdx.x >= RATO_WAVE) return;
-  // one wave: lane i folds blocks i, i+64, ... in order, then a fixed shuffle tree (deterministic)
-  const int lane = threadIdx.x;
-  double s = 0, c = 0, m = -INFINITY, tail = 0, ngt = 0, neq = 0;
-  for (int b = lane; b < nblocks; b += RATO_WAVE) {
-    s += ws->blockpart[b][0];
-    c += ws->blockpart[b][1];
-    m = fmax(m, ws->blockpart[b][2]);
-    tail += ws->blockpart[b][3];
-    ngt += ws->blockpart[b][4];
-    neq += ws->blockpart[b][5];
-  }
-  s = rato::wave_sum(s);
-  c = rato::wave_sum(c);
-  tail = rato::wave_sum(tail);
-  ngt = rato::wave_sum(ngt);
-  neq = rato::wave_sum(neq);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, RATO_WAVE));
-  if (lane != 0) return;
-  const double t = (double)ws->tstar;
-  // VaR = sort(Z)[M - floor(alpha M) - 1]; when floor(alpha M) == M the reference's
-  // index is -1, which NumPy wraps to the LAST element (drone_main_plot.py:651).
-  out[0] = var_is_max ? m : t;
-  out[1] = t + (tail / (double)M) / alpha;     // CVaR (drone_risk.py:694)
-  out[2] = c / (double)M;                      // fraction satisfied
-  out[3] = s / (double)M;
-  out[4] = m;
-  out[5] = c;
-  out[6] = tail;
-  out[7] = (double)k;
-  out[8] = ngt;                                // #{Z > t}
-  out[9] = neq;                                // #{Z == t}
-  out[10] = t;                                 // the Rockafellar-Uryasev minimiser itself (== out[0] unless var_is_max)
+  rs_final_body(M, alpha, k, var_is_max, nblocks, ws, out, true);
 }
 
 // ---- ONE workgroup, ONE launch for M <= RS_SMALL_MAX (BASELINE configs C2 / C3: M = 1e4): Z is read from memory
@@ -282,8 +156,6 @@ __global__ __launch_bounds__(RATO_BLOCK) void rs_final(long M, double alpha, uns
 //  was built and measured at 25-108 us for M = 1e4-1e5 against 20 us for six launches: one CU needs 11-23 us of issue
 //  time for 1e5 elements, and constraint values cluster in 4 key bins per binade, so almost nothing is filtered by the
 //  first pass.  Removed; git history has it.)
-constexpr int RS1_T = 1024;
-
 __global__ __launch_bounds__(RS1_T) void rs_small(const float* __restrict__ Z, long M, double alpha, unsigned k,
                                                   int var_is_max, float thr, double* __restrict__ out,
                                                   const float* __restrict__ part, int nblocks, int ncols,
@@ -365,11 +237,7 @@ __global__ __launch_bounds__(NT) void rs_coop_shaped(const float* __restrict__ Z
 
 // one workgroup: zero the whole workspace, then tag it
 __global__ __launch_bounds__(RATO_BLOCK) void rs_init_kernel(Workspace* __restrict__ ws) {
-  unsigned* w = reinterpret_cast<unsigned*>(ws);
-  const int n = (int)(sizeof(Workspace) / sizeof(unsigned));
-  for (int i = blockIdx.x * RATO_BLOCK + threadIdx.x; i < n; i += gridDim.x * RATO_BLOCK) w[i] = 0;
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x == 0) ws->magic = RS_MAGIC;
+  rs_init_body(ws);
 }
 
 // ------------------------------------------------------------ gathered records
@@ -621,13 +489,7 @@ int risk_stats_impl(const float* Z, int64_t M, double alpha, float thr, void* wo
   // Grid: 4 elements per thread up to 256 workgroups, then more elements per thread (every workgroup flushes its
   // LDS histogram with global atomics: at M ~ 1e6 of CLUSTERED values 1000 workgroups hammering the same few bins
   // cost 60 us per call, 256 workgroups 33 us; tools/stats_time.py), capped at RS_MAX_BLOCKS for very large M.
-  long nb = (M + RATO_BLOCK * 4 - 1) / (RATO_BLOCK * 4);
-  if (nb > 256) {
-    nb = (M + RATO_BLOCK * 16 - 1) / (RATO_BLOCK * 16);
-    if (nb < 256) nb = 256;
-  }
-  if (nb > RS_MAX_BLOCKS) nb = RS_MAX_BLOCKS;
-  if (nb < 1) nb = 1;
+  const long nb = rs_pass_blocks(M);   // rato_select.h
   dim3 grid((unsigned)nb), block(RATO_BLOCK);
   hipLaunchKernelGGL(rs_pass1, grid, block, 0, st, Z, (long)M, thr, ws);
   hipLaunchKernelGGL(rs_pass2, grid, block, 0, st, Z, (long)M, k, ws);

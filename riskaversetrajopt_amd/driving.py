@@ -192,19 +192,27 @@ class Model(SaaModel):
                                            _lib.ptr(g), _lib.current_stream()), "rato_car_eval")
         return Z, xs, g
 
-    def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None):
+    def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None, alphas=None):
         """K control sequences on the model's batch in ONE call (rato_car_eval_batch; the reference's Monte-Carlo report,
         driving.py:675-740, evaluates its 4 alpha x 30 repeats one at a time).  ``us_batch`` (K, S, n_u) ->
         (Z [K][M] device, records [K][N_STATS] device double or None); row k equals ``eval_device`` /
-        ``stats.risk_stats_device`` on sequence k to the bit."""
+        ``stats.risk_stats_device`` on sequence k to the bit.
+        ``alphas`` (K entries; not together with ``alpha``): row k is selected at its own alphas[k] -- the rollouts run
+        without statistics and ONE ``stats.risk_stats_rows_device`` call follows them (``workspace`` is then a
+        ``stats.new_rows_workspace``)."""
         dW, x0, ws, wr = self._dW, self._x0, self._ws, self._wr
         if dW is None:
             raise _lib.RatoError("eval_batch_device reads a materialised dW (this Model regenerates its noise)")
-        alpha = self.alpha if alpha is None else alpha
         M = ws.numel()
         us = self._us_batch_device(us_batch)
         K = us.shape[0]
-        Z, rec, workspace = self._batch_buffers(out if out is not None else {}, K, M, M, want_stats, workspace)
+        o = out if out is not None else {}
+        if alphas is not None:
+            self._check_alphas(alpha, alphas, K)
+            Z, _ = self.eval_batch_device(us, want_stats=False, out=o)
+            return Z, self._rows_records(o, o["_Zb"], M, alphas, workspace)
+        alpha = self.alpha if alpha is None else alpha
+        Z, rec, workspace = self._batch_buffers(o, K, M, M, want_stats, workspace)
         p = self._params(M)
         _lib.check(self._lib.rato_car_eval_batch(
             C.byref(p), K, _lib.ptr(us), _lib.ptr(dW), _lib.ptr(x0), _lib.ptr(ws), _lib.ptr(wr), _lib.ptr(Z), M, float(alpha),

@@ -230,22 +230,30 @@ class Model(SaaModel):
         return Z[:M], (xs[..., :M] if want_xs else None), (g[..., :M] if want_g else None)
 
     def eval_batch_device(self, us_batch, alpha=None, want_stats=True, out=None, workspace=None, metric='quadratic',
-                          want_arg=False, tol=None):
+                          want_arg=False, tol=None, alphas=None):
         """K control sequences on the model's batch in ONE call (rato_drone_eval_batch): what the reference's Monte-Carlo
         report does one sequence at a time for its 4 alpha x 30 repeats (drone_risk.py:697-725).  ``us_batch``
         (K, S, n_u) -> (Z [K][M] device, records [K][N_STATS] device double or None).  Row k equals, to the bit, what
         ``eval_device`` / ``stats.risk_stats_device`` give for sequence k.  ``metric`` / ``want_arg`` / ``tol`` as in
-        ``eval_device`` (rato_drone_eval_batch_metric); ``want_arg=True`` appends arg [K][M] (int32)."""
+        ``eval_device`` (rato_drone_eval_batch_metric); ``want_arg=True`` appends arg [K][M] (int32).
+        ``alphas`` (K entries; not together with ``alpha``): row k is selected at its own alphas[k] -- the rollouts run
+        without statistics and ONE ``stats.risk_stats_rows_device`` call follows them (two launches for a whole
+        alpha x repeat grid while M <= 12,288, six beyond; ``workspace`` is then a ``stats.new_rows_workspace``)."""
         dW, mass, Qsym, M = self._inputs(None)
         metric_id = self._metric(metric)
         if dW is None:
             if metric_id or want_arg:
                 raise ValueError("metric='euclidean' / want_arg=True read a materialised dW (this Model regenerates its noise)")
             raise _lib.RatoError("eval_batch_device reads a materialised dW (this Model regenerates its noise)")
-        alpha = self.alpha if alpha is None else alpha
         us = self._us_batch_device(us_batch)
         K, ld = us.shape[0], mass.numel()
-        Z, rec, workspace = self._batch_buffers(out if out is not None else {}, K, M, ld, want_stats, workspace)
+        o = out if out is not None else {}
+        if alphas is not None:
+            self._check_alphas(alpha, alphas, K)
+            r = self.eval_batch_device(us, want_stats=False, out=o, metric=metric, want_arg=want_arg, tol=tol)
+            return (r[0], self._rows_records(o, o["_Zb"], M, alphas, workspace)) + tuple(r[2:])
+        alpha = self.alpha if alpha is None else alpha
+        Z, rec, workspace = self._batch_buffers(o, K, M, ld, want_stats, workspace)
         p = self._params(M, ld)
         if tol is not None:
             p.tol, p.tol64 = float(tol), float(tol)

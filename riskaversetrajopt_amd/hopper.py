@@ -725,9 +725,13 @@ class Model:
         return tuple(x.value for x in v)
 
     def eval_batch_inputs_device(self, inputs, Cn, alphas=None, want_stats=True, want_arg=False, out=None, workspace=None,
-                                 shape=None):
+                                 shape=None, selection='entry'):
         """``eval_batch_device`` on inputs that already lie on the device: ``inputs`` a float32 tensor (3, K, ldc >= Cn) holding
-        px, fx, fz of solution k in row k (read in place at run time: a captured call sees what they hold at replay)."""
+        px, fx, fz of solution k in row k (read in place at run time: a captured call sees what they hold at replay).
+        ``selection``: 'entry' -- the entry point selects (one launch per run of equal alphas); 'rows' -- it runs without
+        statistics and ONE ``stats.risk_stats_rows_device`` call follows (``workspace``: a ``stats.new_rows_workspace``)."""
+        if selection not in ('entry', 'rows'):
+            raise ValueError(f"selection must be 'entry' or 'rows', got {selection!r}")
         dev = self.device
         if not isinstance(inputs, torch.Tensor) or inputs.dtype != torch.float32 or inputs.dim() != 3 or inputs.shape[0] != 3 or \
                 not inputs.is_contiguous() or inputs.device.type != 'cuda' or inputs.shape[2] < Cn or inputs.shape[1] < 1:
@@ -740,6 +744,18 @@ class Model:
         if al.shape != (K,):
             raise ValueError(f"alphas must be a scalar or a sequence of K = {K} entries")
         o = out if out is not None else {}
+        if want_stats and selection == 'rows':
+            r = self.eval_batch_inputs_device(inputs, Cn, want_stats=False, want_arg=want_arg, out=o, shape=shape)
+            rec = o.get("_recrows")
+            if rec is None or tuple(rec.shape) != (K, stats.N_STATS):
+                rec = torch.empty((K, stats.N_STATS), dtype=torch.float64, device=dev)
+            ws = workspace if workspace is not None else (o.get("_wsrows") if o.get("_wsrows_shape") == (M, K) else None)
+            if ws is None:
+                ws = stats.new_rows_workspace(M, K, dev)
+            o["_recrows"], o["_wsrows"], o["_wsrows_shape"] = rec, ws, (M, K)
+            with torch.cuda.device(dev):
+                stats.risk_stats_rows_device(r[0], al, workspace=ws, out=rec)
+            return (r[0], rec) + tuple(r[2:])
         Z = o.get("_Zb")
         if Z is None or tuple(Z.shape) != (K, M):
             Z = torch.empty((K, M), dtype=torch.float32, device=dev)
@@ -768,7 +784,8 @@ class Model:
                            "rato_hopper_eval_batch_shaped")
         return (Z, rec, arg) if want_arg else (Z, rec)
 
-    def eval_batch_device(self, px, forces, alphas=None, want_stats=True, want_arg=False, out=None, workspace=None, shape=None):
+    def eval_batch_device(self, px, forces, alphas=None, want_stats=True, want_arg=False, out=None, workspace=None, shape=None,
+                          selection='entry'):
         """K solutions on the model's fields in ONE call (rato_hopper_eval_batch): what the script's report does one solution at
         a time (hopper.py:983-1007).  px (K, C), forces (K, C, 2) (``contact_inputs_batch``), converted to fp32 as ``slip_device``
         converts them; one upload of the (3, K, C) inputs, no read-back.
@@ -777,7 +794,8 @@ class Model:
         contact (position in the gathered list) whose value is Z[k][m], -1 when that is -inf.
         ``alphas``: a scalar or K entries (default: the model's alpha); an entry of None is meant for the baseline: that row is
         selected at alpha = 1 and the caller drops its VaR and AVaR.  ``shape`` = (nw_log2, k_chunk) forces the launch shape
-        (rato_hopper_eval_batch_shaped; -1: the rule's value); ``out``: a dict that keeps the buffers between calls."""
+        (rato_hopper_eval_batch_shaped; -1: the rule's value); ``out``: a dict that keeps the buffers between calls;
+        ``selection``: as in ``eval_batch_inputs_device``."""
         px = np.ascontiguousarray(px, dtype=np.float32)
         forces = np.asarray(forces, dtype=np.float32)
         if px.ndim != 2 or forces.shape != px.shape + (2,) or px.shape[0] < 1 or px.shape[1] < 1:
@@ -785,7 +803,7 @@ class Model:
         host = np.stack([px, forces[..., 0], forces[..., 1]])
         inputs = torch.from_numpy(host).to(self.device)
         return self.eval_batch_inputs_device(inputs, px.shape[1], alphas=alphas, want_stats=want_stats, want_arg=want_arg,
-                                             out=out, workspace=workspace, shape=shape)
+                                             out=out, workspace=workspace, shape=shape, selection=selection)
 
     # ---- the whole NLP (hopper.py:441-453, :491-562, :569-640) -------------------------------------------------------------
     @classmethod

@@ -241,24 +241,26 @@ def draw_saa_batches(num_repeats=30, M=50, S=None, seed=0):
 
 
 def drone_saa_experiment(alphas=(0.05, 0.1, 0.2, 0.3), num_repeats=30, M=50, S=20, iters=60, seed=0, mc_model=None,
-                         results_dir=None, n_threads=None, device='cuda:0'):
+                         results_dir=None, n_threads=None, device='cuda:0', mc='per_alpha'):
     """The reference's drone SAA experiment (drone_risk.py:480-539, :697-725) as one call: the sample batches drawn in the
     reference's order (``draw_saa_batches``), the alpha x repeat grid solved in ONE lockstep batch
     (``run_drone_reduced_batch``; each alpha reuses the same batches), with ``mc_model`` the Monte-Carlo report per alpha
-    (``monte_carlo_report``), with ``results_dir`` the reference's result files drone_alpha=<alpha>_repeat=<r>.npy (us, then
-    xs: ``save_results``).  -> dict(alphas, results [alpha][repeat] (the run_drone_reduced_batch dicts), us (A, R, S, 3),
+    (``monte_carlo_report``; mc='grid': all alphas in one call, ``monte_carlo_report_grid``), with ``results_dir`` the
+    reference's result files drone_alpha=<alpha>_repeat=<r>.npy (us, then xs: ``save_results``).  -> dict(alphas, results [alpha][repeat] (the run_drone_reduced_batch dicts), us (A, R, S, 3),
     reports {alpha: report} (with mc_model), rounds, wall_s)"""
     from . import drone_risk
     batches = draw_saa_batches(num_repeats, M, S, seed)
     alphas = [float(a) for a in alphas]
     models = [drone_risk.Model(S, *batches[r], 'saa', a, device=device) for a in alphas for r in range(num_repeats)]
     return _saa_experiment(models, run_drone_reduced_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir,
-                           "drone")
+                           "drone", mc)
 
 
-def _saa_experiment(models, run_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir, name):
+def _saa_experiment(models, run_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir, name, mc='per_alpha'):
     """drone_saa_experiment / driving_saa_experiment once the alpha-major grid of ``models`` is built: ONE batched solve
     (``run_batch``), the result files <name>_alpha=<alpha>_repeat=<r>.npy and the Monte-Carlo reports"""
+    if mc not in ('per_alpha', 'grid'):
+        raise ValueError(f"mc must be 'per_alpha' or 'grid', got {mc!r}")
     _sync()
     t0 = time.perf_counter()
     res = run_batch(models, num_scp_iters_max=iters, n_threads=n_threads)
@@ -274,7 +276,9 @@ def _saa_experiment(models, run_batch, iters, n_threads, alphas, num_repeats, mc
                 xs = models[i * num_repeats + r].us_to_state_trajectories(us[i, r])
                 xs = xs.cpu().numpy() if hasattr(xs, "cpu") else np.asarray(xs)
                 save_results(os.path.join(results_dir, f"{name}_alpha={a}_repeat={r}.npy"), us[i, r], xs)
-    if mc_model is not None:
+    if mc_model is not None and mc == 'grid':
+        out["reports"] = monte_carlo_report_grid(mc_model, us, alphas)
+    elif mc_model is not None:
         out["reports"] = {a: monte_carlo_report(mc_model, list(us[i]), a) for i, a in enumerate(alphas)}
     return out
 
@@ -404,11 +408,11 @@ def draw_driving_saa_batches(alphas, num_repeats=30, M=50, S=None, seed=0):
 
 
 def driving_saa_experiment(alphas=(0.01, 0.02, 0.05, 0.1), num_repeats=30, M=50, S=20, iters=15, seed=0, mc_model=None,
-                           results_dir=None, n_threads=None, device='cuda:0'):
+                           results_dir=None, n_threads=None, device='cuda:0', mc='per_alpha'):
     """The reference's driving SAA experiment (driving.py:467-529, :672-700) as one call, shaped like
     ``drone_saa_experiment``: the samples of every (alpha, repeat) drawn in the reference's order
     (``draw_driving_saa_batches``), the grid solved in ONE lockstep batch (``run_driving_reduced_batch``), with ``mc_model``
-    the Monte-Carlo report per alpha, with ``results_dir`` the reference's result files driving_alpha=<alpha>_repeat=<r>.npy
+    the Monte-Carlo report per alpha (mc='grid': all alphas in one call), with ``results_dir`` the reference's result files driving_alpha=<alpha>_repeat=<r>.npy
     (us, then xs).  -> dict(alphas, results [alpha][repeat], us (A, R, S, 2), reports {alpha: report} (with mc_model), rounds,
     wall_s, models)"""
     from . import driving
@@ -417,7 +421,7 @@ def driving_saa_experiment(alphas=(0.01, 0.02, 0.05, 0.1), num_repeats=30, M=50,
     models = [driving.Model(M, 'saa', a, S=S, device=device, samples=draws[i][r])
               for i, a in enumerate(alphas) for r in range(num_repeats)]
     return _saa_experiment(models, run_driving_reduced_batch, iters, n_threads, alphas, num_repeats, mc_model, results_dir,
-                           "driving")
+                           "driving", mc)
 
 
 def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
@@ -453,6 +457,11 @@ def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
         us_list = []
     for us in us_list:
         _append(mc_model.monte_carlo_statistics(us, alpha=alpha), us)
+    return _mc_aggregate(frac, avar, var, cost, verbose)
+
+
+def _mc_aggregate(frac, avar, var, cost, verbose=False):
+    """the dict of ``monte_carlo_report`` from the per-solution values"""
     out = {"frac_satisfied": np.array(frac), "avar": np.array(avar), "var": np.array(var), "cost": np.array(cost)}
     for k in ("frac_satisfied", "avar", "cost"):
         out[k + "_mean"], out[k + "_median"] = float(np.mean(out[k])), float(np.median(out[k]))
@@ -464,6 +473,38 @@ def monte_carlo_report(mc_model, us_list, alpha, verbose=False):
         print("avar (median) =", out["avar_median"])
         print("cost (median) =", out["cost_median"])
     return out
+
+
+def monte_carlo_report_grid(mc_model, us_grid, alphas, verbose=False):
+    """``{alpha: monte_carlo_report(mc_model, us_grid[i], alpha)}`` for the whole alpha x repeat grid ``us_grid``
+    (A, R, S, n_u) in ONE ``Model.eval_batch_device(alphas=...)`` call: the A x R rollouts in one launch, then the A x R
+    exact selections, every row at its own alpha, in one more (rato_risk_stats_rows; five beyond 12,288 validation samples)
+    -- where the loop over ``monte_carlo_report`` makes one library call and one read-back per alpha.  Every report is the
+    dict ``monte_carlo_report`` returns, to the bit while M_mc <= 12,288; beyond, mean-type entries (avar) agree to the
+    order of the fp64 sums, the exactly defined ones (var, frac_satisfied) to the bit."""
+    from . import stats
+    us_grid = np.asarray(us_grid)
+    alphas = [float(a) for a in alphas]
+    A, R = us_grid.shape[:2]
+    if len(alphas) != A:
+        raise ValueError(f"us_grid has {A} alpha rows for {len(alphas)} alphas")
+    _, rec = mc_model.eval_batch_device(us_grid.reshape((A * R,) + us_grid.shape[2:]), alphas=np.repeat(alphas, R))
+    rec = rec.cpu().numpy().reshape(A, R, -1)
+    reports = {}
+    for i, a in enumerate(alphas):
+        frac, avar, var, cost = [], [], [], []
+        for r in range(R):
+            st = dict(zip(stats._STAT_NAMES, rec[i, r].tolist()))
+            if np.isnan(st["var"]):                    # (as monte_carlo_report: the recovering per-solution path)
+                st = mc_model.monte_carlo_statistics(us_grid[i, r], alpha=a)
+            frac.append(st["frac_satisfied"])
+            avar.append(st["cvar"])
+            var.append(st["var"])
+            cost.append(mc_model.monte_carlo_cost(us_grid[i, r]))
+            if verbose:
+                print("B_satisfied_vec =", frac[-1])
+        reports[a] = _mc_aggregate(frac, avar, var, cost, verbose)
+    return reports
 
 
 def driving_gaussian_tol():
@@ -799,7 +840,7 @@ def _hopper_mc_alphas(alphas, K):
     return [None if (a is None or not float(a) > 0.0) else float(a) for a in al]
 
 
-def hopper_monte_carlo_report(mc_model, Zs, alphas, verbose=False, batch=True):
+def hopper_monte_carlo_report(mc_model, Zs, alphas, verbose=False, batch=True, selection='entry'):
     """The hopper script's Monte-Carlo block (hopper.py:960-1007) for K solutions ``Zs`` (their NLP vectors; only the states and
     controls are read) on the validation fields of ``mc_model`` (a ``hopper.Model`` of M_mc samples): per solution the jumped
     distance x_S[0], the fraction of fields without slip and VaR / AVaR at the solution's alpha.  ``alphas``: a scalar or K
@@ -809,6 +850,8 @@ def hopper_monte_carlo_report(mc_model, Zs, alphas, verbose=False, batch=True):
     per run of equal alphas) and one read-back of the K records beside the contact counts; a record whose VaR is NaN (a
     selection that gave up) falls back to ``Model.monte_carlo_statistics``, as ``monte_carlo_report`` does.  batch=False: the
     per-solution loop (``slip_device`` + ``stats.risk_stats`` per solution) -- the checker: every array is the same to the bit.
+    selection='rows' (with batch=True): the K selections as ONE ``stats.risk_stats_rows_device`` call behind the rollouts, whatever
+    the alphas are (``Model.eval_batch_device``).
     -> dict(alphas (K,) with 0.0 for the baseline, jump, frac_satisfied, var, avar (each (K,)), arg_counts (K, C) int64: over the
     samples that slip (Z > 1e-6), how often contact c -- the first that attains the maximum -- is the one; wall_s)."""
     from . import stats
@@ -830,7 +873,7 @@ def hopper_monte_carlo_report(mc_model, Zs, alphas, verbose=False, batch=True):
 
     if batch:
         import torch
-        Zd, rec, arg = mc_model.eval_batch_device(px, forces, alphas=al, want_arg=True)
+        Zd, rec, arg = mc_model.eval_batch_device(px, forces, alphas=al, want_arg=True, selection=selection)
         # the contact counts over the unsafe samples, on the device, so that ONE tensor comes back: [records | counts]
         unsafe = (Zd > float(thr)) & (arg >= 0)
         cnt = torch.zeros((K, Cn), dtype=torch.float64, device=Zd.device)

@@ -141,6 +141,76 @@ def risk_stats(Z, alpha, thr=SATISFIED_THRESHOLD, workspace=None):
     return dict(zip(_STAT_NAMES, out.tolist()))
 
 
+# ---- K rows, each with its own alpha (rato_risk_stats_rows) ---------------------------------------------------------
+def new_rows_workspace(M, K, device):
+    """The workspace of ``risk_stats_rows_device`` for K rows of M samples, initialised (rato_risk_stats_rows_init): K
+    single-row workspaces beyond the one-workgroup form (M > 12,288), EMPTY below it (that form reads none).  Reusable for
+    any number of stream-ordered calls on ONE stream at a time."""
+    lib = _lib.load()
+    ws = torch.empty(lib.rato_risk_stats_rows_workspace_bytes(int(M), int(K)), dtype=torch.uint8, device=device)
+    if ws.numel():
+        with torch.cuda.device(ws.device):
+            _lib.check(lib.rato_risk_stats_rows_init(_lib.ptr(ws), ws.numel(), _lib.current_stream()),
+                       "rato_risk_stats_rows_init")
+    return ws
+
+
+def alphas_device(alphas, K, device):
+    """``alphas`` (a sequence of K numbers, or a device fp64 tensor of K entries) as the device fp64 tensor the rows
+    call reads."""
+    if isinstance(alphas, torch.Tensor):
+        if not (alphas.is_cuda and alphas.dtype == torch.float64 and alphas.is_contiguous()):
+            raise _lib.RatoError("alphas must be a contiguous device fp64 tensor (or a host sequence)")
+        a = alphas
+    else:
+        a = torch.as_tensor(np.asarray(alphas, dtype=np.float64).reshape(-1), device=device)
+    if a.numel() != K:
+        raise ValueError(f"alphas has {a.numel()} entries for {K} rows")
+    return a
+
+
+def risk_stats_rows_device(Z, alphas, thr=SATISFIED_THRESHOLD, workspace=None, out=None, stream=None, M=None):
+    """The records of the K rows of Z, row k at ``alphas[k]`` (rato_risk_stats_rows) -> device double (K, N_STATS).
+    Z: (K, ldz >= M) fp32 device tensor with contiguous rows (``M``: the samples of a row when ldz > M); ``alphas``: a
+    sequence of K numbers or a device fp64 tensor.  One launch while M <= 12,288, five beyond, whatever K is and whatever
+    the alphas are; a row whose alpha is outside (0, 1] gets a NaN record.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    if not (isinstance(Z, torch.Tensor) and Z.is_cuda and Z.dtype == torch.float32 and Z.dim() == 2 and Z.stride(1) == 1
+            and (Z.shape[0] == 1 or Z.stride(0) >= Z.shape[1])):
+        raise _lib.RatoError("Z must be a (K, ldz) fp32 device tensor with contiguous rows (no CPU fallback)")
+    K = Z.shape[0]
+    ldz = Z.stride(0) if K > 1 else Z.shape[1]
+    M = Z.shape[1] if M is None else int(M)
+    if M > Z.shape[1]:
+        raise ValueError(f"M = {M} exceeds the row length {Z.shape[1]}")
+    a = alphas_device(alphas, K, Z.device)
+    if workspace is None:
+        workspace = new_rows_workspace(M, K, Z.device)
+    if out is None:
+        out = torch.empty((K, N_STATS), dtype=torch.float64, device=Z.device)
+    _lib.check(lib.rato_risk_stats_rows(_lib.ptr(Z), M, ldz, K, _lib.ptr(a), float(thr),
+                                        _lib.ptr(workspace) if workspace.numel() else None, workspace.numel(),
+                                        _lib.ptr(out), _lib.current_stream() if stream is None else stream),
+               "rato_risk_stats_rows")
+    return out
+
+
+def risk_stats_rows(Z, alphas, thr=SATISFIED_THRESHOLD):
+    """-> the list of the K dicts ``risk_stats`` returns, row k at ``alphas[k]``.  A NaN record of a row with a valid
+    alpha (an unclean workspace) is recovered through ``risk_stats`` on that row."""
+    if not isinstance(Z, torch.Tensor):
+        Z = torch.as_tensor(np.asarray(Z, dtype=np.float32), device='cuda:0')
+    al = alphas.cpu().numpy() if isinstance(alphas, torch.Tensor) else np.asarray(alphas, dtype=np.float64)
+    out = risk_stats_rows_device(Z, alphas, thr).cpu().numpy()
+    recs = []
+    for k in range(out.shape[0]):
+        if np.isnan(out[k, 0]) and 0.0 < al[k] <= 1.0 and count_nonfinite(Z[k].contiguous()) == 0:
+            recs.append(risk_stats(Z[k], float(al[k]), thr))
+        else:
+            recs.append(dict(zip(_STAT_NAMES, out[k].tolist())))
+    return recs
+
+
 def monte_carlo_statistics(model, us_mat, alpha=None):
     """``Model.monte_carlo_statistics`` of the drone and the driving problem -- fused device path: rollout -> Z -> fraction
     satisfied, VaR, CVaR (``model.mc_step_device``: one call, for small batches one launch).  A NaN record on finite Z (a
